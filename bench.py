@@ -2,7 +2,7 @@
 """Headline benchmark: points/sec of the MHCT hot path (positions -> Splat ->
 Slice, forward + backward) on synthetic 4096-point clouds.
 
-  python bench.py --gpus N --steps K --warmup W [--mode op|ddp-step]
+  python bench.py --gpus N --steps K --warmup W [--mode op|ddp-step] [--full] [--dump-outputs DIR]
 
 mode op (default).  A "step" is one fwd+bwd pass of the hot path over one batch of synthetic input
 (BASELINE.json north-star op-level shape: B=8, N=4096, H=64 heads, 32x32 grid, C=16 features/head), inputs
@@ -18,11 +18,18 @@ B=8 clouds x 4096 points per GPU, cross-entropy, SGD) under DistributedDataParal
 N > 1 without a launcher: this process starts N ranks of itself (cloud_transformers_amd/launch.py) before it
 touches the GPU and returns their exit code; under `torch.distributed.run` it is one rank.
 
-Prints ONE JSON line (rank 0).  Besides the driver's contract it carries
-  roofline     — the dominant kernel's algorithmic bytes / its HIP-event time vs 8 TB/s
+Prints ONE JSON line (rank 0).  A plain run measures the headline figure only: set-up, warm-up, the K timed steps,
+the outputs if --dump-outputs is given, the line.  With --full (mode op) the line also carries
+  roofline     — the dominant kernel's algorithmic bytes / its HIP-event time vs 8 TB/s (and every pass's, from
+                 per-pass HIP-event timings taken in front of the steps), the exact ties of the clouds, the launch tags
   cpu_baseline — the CPU oracle (a port of the reference's PyTorch CPU path) timed on this host on a bounded
                  sample of the same workload: all physical cores, and one thread (the reference's own setting,
                  train_segmentation.py:25)
+  ddp_step     — N > 1: the data-parallel training step, run by the same ranks after the op-level numbers
+
+--dump-outputs DIR (mode op): after the timed steps, rank 0 writes what its last step computed — the arrays a caller of
+the step receives: out, g_feat, g_keys — as DIR/<name>.npy in float32 (see dump_outputs), so that two builds can be
+compared output for output: with the same arguments the inputs are the same from run to run.
 """
 import argparse
 import json
@@ -37,13 +44,17 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec (MI355X_MICROARCH.md); measured copy ceiling 6290
 METRIC = "points/sec fwd+bwd MHCT, 4096-pt batch, 1/2/4/8 MI355X; % HBM roofline"   # BASELINE.json
+# untimed steps in front of the W warm-up steps of a plain run: about the GPU time --full's per-pass timings take there
+# (203 launches of each pass), so that the K timed steps start at the clocks they start at in a --full run
+PLAIN_CLOCK_STEPS = 200
+DUMP_ELEMENTS = 1 << 22    # per dumped array: 16 MiB of float32 (48 MiB for the three)
 
 
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=200)
-    p.add_argument("--warmup", type=int, default=20)
+    p.add_argument("--steps", type=int, default=None, help="timed steps (default 200; mode ddp-step: 20)")
+    p.add_argument("--warmup", type=int, default=None, help="warm-up steps (default 20; mode ddp-step: 3)")
     p.add_argument("--mode", default="op", choices=["op", "ddp-step"])
     p.add_argument("--batch", type=int, default=8)
     p.add_argument("--points", type=int, default=4096)
@@ -61,7 +72,20 @@ def parse():
     p.add_argument("--ddp-steps", type=int, default=10, help="timed steps of the attached data-parallel training step")
     p.add_argument("--ddp-timeout", type=int, default=240, help="seconds the attached step may take before the line goes out without it")
     p.add_argument("--cpu-seconds", type=float, default=25.0, help="budget of the CPU baseline leg")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: per-pass timings and roofline, ties, launch tags, "
+                        "the CPU baseline (unless --no-cpu-baseline) and, N > 1, the attached data-parallel step (unless --no-ddp-step)")
+    p.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (mode op)")
+    args = p.parse_args()
+    if args.steps is None:
+        args.steps = 20 if args.mode == "ddp-step" else 200      # a training step is ~100x longer than the op step
+    if args.warmup is None:
+        args.warmup = 3 if args.mode == "ddp-step" else 20
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.mode != "op":
+        p.error("--dump-outputs: mode op only")
+    return args
 
 
 def time_passes(step, iters=200):
@@ -214,6 +238,22 @@ def count_ties(step):
     return ties
 
 
+def dump_outputs(path, arrays, seed=0):
+    """path/<name>.npy in float32 for each of `arrays` ({name: tensor}): the whole tensor when it holds at most DUMP_ELEMENTS
+    elements, else DUMP_ELEMENTS of its elements, flattened, at positions drawn from a CPU generator seeded with `seed` (sorted;
+    the same positions in every run of the same shape)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_ELEMENTS:
+            g = torch.Generator().manual_seed(seed)
+            idx = torch.randint(t.numel(), (DUMP_ELEMENTS,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def emit(line):
     """Print the result as the LAST line of stdout: RCCL writes its version banner through C stdio, which — when stdout
     is a file or a pipe — sits in libc's buffer until exit and would land after a Python print; flush it first."""
@@ -291,12 +331,15 @@ def run_op(args):
         for _ in range(k):
             run()
 
-    # The per-pass HIP-event timings (the roofline's kernel time) are taken BEFORE the step timing, on every rank: the
+    # The per-pass HIP-event timings (--full: the roofline's kernel time) are taken BEFORE the step timing, on every rank: the
     # driver's short runs (W = 5 warm-up steps = 1 ms, K = 20 steps = 4 ms) otherwise measure the GPU's clock ramp after
     # the idle seconds of set-up and graph capture — same build, same box: 150-160 M points/s with W = 5, 167 M with
-    # W = 200 (a 20-step burst after idle runs at 0.24 ms per step, tools/dev/lat_probe.py; sustained load: 0.195).  The
-    # line says so (`config.order`).
-    passes = time_passes(step)
+    # W = 200 (a 20-step burst after idle runs at 0.24 ms per step, tools/dev/lat_probe.py; sustained load: 0.195).  A plain
+    # run replays PLAIN_CLOCK_STEPS untimed steps in their place.  The line says so (`config.order`).
+    if args.full:
+        passes = time_passes(step)
+    else:
+        run_steps(PLAIN_CLOCK_STEPS)
     run_steps(args.warmup)
     barrier(dist)
     torch.cuda.synchronize()
@@ -314,33 +357,18 @@ def run_op(args):
         rank_ms = [float(g.item()) for g in gathered]
     dt = max_over_ranks(dist, dt)
     ms = dt / args.steps * 1e3
-    # (counted BEHIND the timed steps: its host synchronisations between the per-pass timings and a short timed region let the
-    #  clocks fall again — the driver's `--steps 20 --warmup 5` read 163 M points/s with it in front, 176 M with it here)
-    ties = count_ties(step)
-    if dist is not None:
-        t = torch.tensor([ties], device="cuda", dtype=torch.int64)
-        dist.all_reduce(t)
-        ties = int(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"out": step.out, "g_feat": step.g_feat, "g_keys": step.g_keys()})
+    if args.full:
+        # (counted BEHIND the timed steps: its host synchronisations between the per-pass timings and a short timed region let
+        #  the clocks fall again — `--steps 20 --warmup 5` read 163 M points/s with it in front, 176 M with it here)
+        ties = count_ties(step)
+        if dist is not None:
+            t = torch.tensor([ties], device="cuda", dtype=torch.int64)
+            dist.all_reduce(t)
+            ties = int(t.item())
 
     if rank == 0:
-        alg = step.algorithmic_bytes()
-        tags = step.launch_tags()
-        # dominant KERNEL: the longest pass that is a single launch (profiles/*_kernel_stats.csv lists every kernel's
-        # average for cross-checking)
-        single = [p for p in step.PASSES if "+" not in tags[p]] or list(step.PASSES)
-        dom = max(single, key=lambda k: passes[k])
-        dom_bytes = alg[dom]
-        achieved = dom_bytes / (passes[dom] * 1e-3) / 1e9
-        # the committed PMC passes were collected on the default workload only
-        default_shape = (B, N, H, C, W, dim, args.reduce) == (8, 4096, 64, 16, 32, 2, "max")
-        exact = step.HEADLINE_KERNELS if default_shape else {}      # full instantiated names: only the default workload has a PMC record
-        traffic = measured_traffic(exact[dom]) if default_shape else None
-        roofline_passes = {}
-        for p in step.PASSES:
-            gbs = alg[p] / (passes[p] * 1e-3) / 1e9
-            kern = step.KERNEL_OF.get(tags[p], tags[p])
-            roofline_passes[p] = {"kernel": kern, "bytes": alg[p], "ms": passes[p], "achieved": gbs, "frac": gbs / HBM_PEAK_GBS,
-                                  "traffic": measured_traffic(exact[p]) if default_shape and "+" not in tags[p] else None}
         out = {
             "metric": METRIC,
             "value": world * B * N / (dt / args.steps),
@@ -360,7 +388,34 @@ def run_op(args):
                        "world_size_seen": world,
                        "hip_graph": graph is not None, "steps_per_graph": gs if multi is not None else 1,
                        "order": "per-pass HIP-event timings (203 launches of each pass back to back: 3-9 % longer than inside the "
-                                "replayed step, profiles/r6_headline_replay_trace.txt), then W warm-up steps, then the K timed steps"},
+                                "replayed step, profiles/r6_headline_replay_trace.txt), then W warm-up steps, then the K timed steps"
+                                if args.full else
+                                "%d untimed steps (in place of --full's per-pass timings), then W warm-up steps, then the K "
+                                "timed steps" % PLAIN_CLOCK_STEPS},
+            "rank_ms_per_step": rank_ms,
+        }
+    else:
+        out = {}
+    if rank == 0 and args.full:
+        alg = step.algorithmic_bytes()
+        tags = step.launch_tags()
+        # dominant KERNEL: the longest pass that is a single launch (profiles/*_kernel_stats.csv lists every kernel's
+        # average for cross-checking)
+        single = [p for p in step.PASSES if "+" not in tags[p]] or list(step.PASSES)
+        dom = max(single, key=lambda k: passes[k])
+        dom_bytes = alg[dom]
+        achieved = dom_bytes / (passes[dom] * 1e-3) / 1e9
+        # the committed PMC passes were collected on the default workload only
+        default_shape = (B, N, H, C, W, dim, args.reduce) == (8, 4096, 64, 16, 32, 2, "max")
+        exact = step.HEADLINE_KERNELS if default_shape else {}      # full instantiated names: only the default workload has a PMC record
+        traffic = measured_traffic(exact[dom]) if default_shape else None
+        roofline_passes = {}
+        for p in step.PASSES:
+            gbs = alg[p] / (passes[p] * 1e-3) / 1e9
+            kern = step.KERNEL_OF.get(tags[p], tags[p])
+            roofline_passes[p] = {"kernel": kern, "bytes": alg[p], "ms": passes[p], "achieved": gbs, "frac": gbs / HBM_PEAK_GBS,
+                                  "traffic": measured_traffic(exact[p]) if default_shape and "+" not in tags[p] else None}
+        out.update({
             "roofline": {"bound": "hbm", "kernel": step.KERNEL_OF.get(tags[dom], tags[dom]),
                          "pass": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
@@ -375,17 +430,14 @@ def run_op(args):
             # exact ties of the Splat(max) maxima in the clouds of ALL ranks (each costs its plane's workgroup a redo: the
             # step of a rank with ties runs a few per cent longer, and the value is the max over ranks)
             "ties_seen": ties,
-            "rank_ms_per_step": rank_ms,
             "kernels": {p: step.KERNEL_OF.get(t, t) for p, t in tags.items()},
             "step_roofline": {"algorithmic_bytes_per_step": alg["total"],
                               "achieved_GBs": alg["total"] / (ms * 1e-3) / 1e9,
                               "frac_of_8TBs": alg["total"] / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
-    else:
-        out = {}
-    if dist is not None and not args.no_ddp_step:
+    if dist is not None and args.full and not args.no_ddp_step:
         # N > 1 ranks: the op-level numbers above are taken; now the SAME ranks run the data-parallel training step (mode ddp-step's
         # workload: DDP gradient all-reduce + SyncBatchNorm exchanges on RCCL) and rank 0 attaches it to the ONE line — `value`
         # stays the op-level throughput, `ddp_step.value` is what BASELINE's ">= 6x DDP throughput at 8 GPUs vs 1" is read from
@@ -630,20 +682,18 @@ def main():
         if have is not None and have < args.gpus:
             raise SystemExit("bench.py --gpus %d: only %d GPU(s) visible" % (args.gpus, have))
         raise SystemExit(launch.spawn_ranks(os.path.abspath(__file__), sys.argv[1:], args.gpus,
-                                            capture=not args.no_graph and (args.mode == "ddp-step" or not args.no_ddp_step)))
+                                            capture=not args.no_graph and (args.mode == "ddp-step" or (args.full and not args.no_ddp_step))))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if launch.under_launcher() and world != args.gpus:
         print("bench: --gpus %d but the launcher started %d rank(s); reporting n_gpus=%d" % (args.gpus, world, world),
               file=sys.stderr)
-    captures_collectives = not args.no_graph and (args.mode == "ddp-step" or (world > 1 and not args.no_ddp_step))
+    captures_collectives = not args.no_graph and (args.mode == "ddp-step" or (world > 1 and args.full and not args.no_ddp_step))
     if captures_collectives:
         # torch's recipe for capturing collectives (notes/cuda.rst): with the process group's watchdog polling events of a
         # capturing stream the capture dies.  The price — a hung collective is not aborted, the job hangs instead of exiting —
         # is paid only by runs that capture (launch.rank_env(capture=True) does the same for spawned ranks)
         os.environ.setdefault("TORCH_NCCL_ASYNC_ERROR_HANDLING", "0")
     if args.mode == "ddp-step":
-        if args.steps == 200 and args.warmup == 20:      # defaults are the op benchmark's: a training step is ~100x longer
-            args.steps, args.warmup = 20, 3
         return run_ddp_step(args)
     return run_op(args)
 

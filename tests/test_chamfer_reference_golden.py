@@ -45,11 +45,9 @@ def test_oracle_chamfer_equals_the_references_kernel(case):
 
 def test_every_reference_target_of_the_oracle_makefile_has_a_rule():
     """`make -n ref` lists a recipe for each of the reference builds (the grid-subsampling rule was once lost in an edit and only
-    a cold build of a clean checkout showed it)."""
+    a cold build of a clean checkout showed it; `-n` reads no source, so no upstream checkout is needed)."""
     import subprocess
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if not os.path.isdir("/root/reference/emd_linear"):
-        pytest.skip("the reference is not mounted here")
     r = subprocess.run(["make", "-C", os.path.join(here, "oracle"), "-n", "-B", "ref"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-500:]
     for name in ("libgrid_subsampling_ref.so", "emd_reference.so", "emd_reference_strict.so", "chamfer_reference.so"):

@@ -1,7 +1,7 @@
 """cloud_transformers_amd.data.datasets against the reference's loaders (datasets/scanobjectnn.py:87-125,
-datasets/s3dis_v2.py:494-574) on synthetic files: same seeds -> same items.  The reference side runs in a child process
-with a stand-in `h5py` module that serves the same arrays from .npz (h5py is not installed here; reading HDF5 is h5py's job
-on both sides); build container only."""
+datasets/s3dis_v2.py:494-574) on synthetic files: same seeds -> same items.  Each side runs in a child process with a
+stand-in `h5py` module that serves the same arrays from .npz (h5py is not installed here; reading HDF5 is h5py's job on both
+sides); the reference side's items are tests/golden/datasets_reference_items.npz, written by tests/golden/gen_datasets_golden.py."""
 import os
 import subprocess
 import sys
@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+GOLDEN = os.path.join(ROOT, "tests", "golden", "datasets_reference_items.npz")
 
 
 def make_files(d):
@@ -72,16 +72,19 @@ np.savez(os.path.join(d, side + "_items.npz"), **out)
 """
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference not mounted (build container only)")
+def run_side(side, d, ref=None):
+    """the loaders' items on the files of make_files(d) -> d/<side>_items.npz (side "ref": the upstream checkout `ref`)"""
+    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
+    r = subprocess.run([sys.executable, "-c", CHILD.replace("@REF@", repr(ref)).replace("@ROOT@", repr(ROOT)), side, d],
+                       capture_output=True, text=True, timeout=600, env=env, cwd=d)
+    assert r.returncode == 0, (side, r.stderr[-3000:])
+    return os.path.join(d, side + "_items.npz")
+
+
 def test_items_equal_the_reference_loaders(tmp_path):
     d = str(tmp_path)
     make_files(d)
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    for side in ("ref", "ours"):
-        r = subprocess.run([sys.executable, "-c", CHILD.replace("@REF@", repr(REF)).replace("@ROOT@", repr(ROOT)), side, d], capture_output=True, text=True,
-                           timeout=600, env=env, cwd="/tmp")
-        assert r.returncode == 0, (side, r.stderr[-3000:])
-    a, b = np.load(os.path.join(d, "ref_items.npz")), np.load(os.path.join(d, "ours_items.npz"))
+    a, b = np.load(GOLDEN), np.load(run_side("ours", d))
     assert sorted(a.files) == sorted(b.files) and len(a.files) > 100
     for k in a.files:
         assert a[k].shape == b[k].shape and a[k].dtype == b[k].dtype, k

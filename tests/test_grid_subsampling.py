@@ -1,12 +1,20 @@
 """csrc/host/grid_subsampling.cpp (ct_grid_subsample, include/cloudct_host.h) against the REFERENCE's own C++
-(cpp_wrappers/cpp_subsampling/grid_subsampling/grid_subsampling.cpp:4-104, compiled where it lies into oracle/_ref — build
-container only) and against a numpy restatement that runs everywhere.  Rows are compared as sets (the reference's order is
-its hash map's): points and features BIT FOR BIT (same float sums in input order), classes exactly."""
+(cpp_wrappers/cpp_subsampling/grid_subsampling/grid_subsampling.cpp:4-104: row counts and digests of its results in
+tests/golden/grid_subsampling_reference.json, written by tests/golden/gen_grid_subsampling_golden.py) and against a numpy
+restatement.  Rows are compared as sets (the reference's order is its hash map's): points and features BIT FOR BIT (same
+float sums in input order), classes exactly."""
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 
 from cloud_transformers_amd.data import subsampling as S
-from oracle import grid_ref
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "grid_subsampling_reference.json")
+REF_CASES = [(20000, 0.04, 10), (5000, 0.3, 11), (4096, 1.5, 12)]
+REF_VARIANTS = ((True, True), (True, False), (False, True), (False, False))
 
 
 def numpy_restatement(points, features, classes, dl):
@@ -71,13 +79,28 @@ def test_return_layout_follows_the_reference_wrapper():
     assert S.compute(np.zeros((0, 3), np.float32), sampleDl=0.1).shape == (0, 3)
 
 
-@pytest.mark.skipif(not grid_ref.available(), reason="oracle/_ref is built from /root/reference (build container only)")
-@pytest.mark.parametrize("n,dl,seed", [(20000, 0.04, 10), (5000, 0.3, 11), (4096, 1.5, 12)])
-def test_matches_the_reference_cpp(n, dl, seed):
+def reference_cloud(n, seed):
     pts, feats, labels = cloud(n, seed)
     # clustered part: many points per cell, long float sums
     pts[: n // 2] = (pts[: n // 2] * 0.05).astype(np.float32)
-    for use_f, use_c in ((True, True), (True, False), (False, True), (False, False)):
+    return pts, feats, labels
+
+
+def golden_key(n, dl, seed, use_f, use_c):
+    return "%d,%g,%d,features=%d,classes=%d" % (n, dl, seed, use_f, use_c)
+
+
+def rows_digest(P, F, C):
+    rows = np.ascontiguousarray(as_sorted_rows(P, F, C), np.float32)
+    return {"rows": int(rows.shape[0]), "cols": int(rows.shape[1]), "sha256": hashlib.sha256(rows.tobytes()).hexdigest()}
+
+
+@pytest.mark.parametrize("n,dl,seed", REF_CASES)
+def test_matches_the_reference_cpp(n, dl, seed):
+    with open(GOLDEN) as f:
+        golden = json.load(f)
+    pts, feats, labels = reference_cloud(n, seed)
+    for use_f, use_c in REF_VARIANTS:
         f = feats if use_f else None
         c = labels if use_c else None
         got = S.compute(pts, features=f, classes=c, sampleDl=dl)
@@ -85,6 +108,4 @@ def test_matches_the_reference_cpp(n, dl, seed):
         P = got[0]
         F = got[1] if use_f else None
         C = (got[2] if use_f else got[1]) if use_c else None
-        Pr, Fr, Cr = grid_ref.compute(pts, f, c, dl)
-        assert P.shape == Pr.shape
-        assert np.array_equal(as_sorted_rows(P, F, C), as_sorted_rows(Pr, Fr, Cr)), (use_f, use_c)
+        assert rows_digest(P, F, C) == golden[golden_key(n, dl, seed, use_f, use_c)], (use_f, use_c)

@@ -6,7 +6,7 @@ set -u
 R=$(cd "$(dirname "$0")/../.." && pwd)
 OUT=$R/gpurun_out
 rm -rf $OUT/prof_hl; mkdir -p $OUT/prof_hl
-(cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace --output-format csv -d $OUT/prof_hl -o h -- python3 $R/bench.py --no-cpu-baseline --steps 200 --warmup 20 > $OUT/prof_hl/bench.log 2>&1)
+(cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace --output-format csv -d $OUT/prof_hl -o h -- python3 $R/bench.py --full --no-cpu-baseline --steps 200 --warmup 20 > $OUT/prof_hl/bench.log 2>&1)
 python3 - "$OUT" <<'PY' > $OUT/headline_replay_trace.txt
 import csv, glob, sys, json, collections, statistics
 out = sys.argv[1]
@@ -43,4 +43,4 @@ for line in open(out + "/prof_hl/bench.log"):
         print("bench line of this (profiled) run: %.1f M points/s, %.4f ms per step; passes_ms %s" % (d["value"] / 1e6, d["ms_per_step"], {k: round(v, 4) for k, v in d["passes_ms"].items()}))
 PY
 cat $OUT/headline_replay_trace.txt
-python3 $R/bench.py --no-cpu-baseline > $OUT/r6_bench_line_a.json 2> $OUT/r6_bench_line_a.err; tail -c 600 $OUT/r6_bench_line_a.json
+python3 $R/bench.py --full --no-cpu-baseline > $OUT/r6_bench_line_a.json 2> $OUT/r6_bench_line_a.err; tail -c 600 $OUT/r6_bench_line_a.json

@@ -1,7 +1,7 @@
 #!/bin/bash
 # quick FETCH_SIZE / WRITE_SIZE per kernel of the bench step (two short PMC passes); prints MB per launch
 R=/root/repo; OUT=$R/gpurun_out; mkdir -p $OUT; cd /tmp && export TMPDIR=/tmp
-A="--steps 10 --warmup 2 --no-cpu-baseline --no-graph $@"
+A="--steps 10 --warmup 2 --full --no-cpu-baseline --no-graph $@"
 rm -rf $OUT/q_fetch $OUT/q_write
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/q_fetch -- python3 $R/bench.py $A > /dev/null 2> $OUT/q_fetch.err
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/q_write -- python3 $R/bench.py $A > /dev/null 2> $OUT/q_write.err

@@ -8,9 +8,9 @@ mkdir -p $O
 case "${1:-bench}" in
 bench)   # the bench.py lines (default workload, C4, sum, the DDP step graphed / eager / without the forced exchange) and the
          # rocprofv3 passes of the default command (kernel stats, HBM traffic, SQ counters)
-  python bench.py > $O/ev_bench_line.json 2> $O/ev_bench_line.err
-  python bench.py --feat 4 --no-cpu-baseline > $O/ev_bench_line_C4.json 2>> $O/ev_bench_line.err
-  python bench.py --reduce sum --no-cpu-baseline > $O/ev_bench_line_sum.json 2>> $O/ev_bench_line.err
+  python bench.py --full > $O/ev_bench_line.json 2> $O/ev_bench_line.err
+  python bench.py --full --feat 4 --no-cpu-baseline > $O/ev_bench_line_C4.json 2>> $O/ev_bench_line.err
+  python bench.py --full --reduce sum --no-cpu-baseline > $O/ev_bench_line_sum.json 2>> $O/ev_bench_line.err
   python bench.py --mode ddp-step --steps 10 --warmup 3 > $O/ev_bench_line_ddp_step.json 2> $O/ev_ddp.err
   python bench.py --mode ddp-step --steps 10 --warmup 3 --no-graph > $O/ev_bench_line_ddp_step_eager.json 2>> $O/ev_ddp.err
   CLOUDCT_SYNCBN_FORCE=0 python bench.py --mode ddp-step --steps 10 --warmup 3 > $O/ev_bench_line_ddp_step_noexchange.json 2>> $O/ev_ddp.err

@@ -5,7 +5,7 @@ set -u
 R=/root/repo
 OUT=$R/gpurun_out
 mkdir -p $OUT
-if [ $# -eq 0 ]; then set -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-graph; fi
+if [ $# -eq 0 ]; then set -- python3 $R/bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-graph; fi
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS \
   --output-format csv -d $OUT/pmc_sq_a -o a -- "$@" > /dev/null 2> $OUT/pmc_sq_a.err

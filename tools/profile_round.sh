@@ -9,7 +9,7 @@ R=/root/repo
 OUT=$R/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 50 --warmup 5 --no-cpu-baseline"
+ARGS="--steps 50 --warmup 5 --full --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_stats -- python3 $R/bench.py $ARGS > $OUT/prof_stats_bench.json 2> $OUT/prof_stats.err
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/prof_fetch -- python3 $R/bench.py $ARGS --no-graph > $OUT/prof_fetch_bench.json 2> $OUT/prof_fetch.err
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/prof_write -- python3 $R/bench.py $ARGS --no-graph > $OUT/prof_write_bench.json 2> $OUT/prof_write.err
