@@ -1669,13 +1669,13 @@ int hot_threads(int nq) {
 // at B8 N4096: LDS 28-39 % busy, vector ALU 30-39 %, profiles/r5_zoo_counters.txt).  One 1024-thread workgroup with one quad per
 // thread doubles the waves: 64^2 C16 Slice backward 40.0 -> 34.6 us, Splat(max) backward 45.4 -> 34.7; 16^3 C16 54.0 -> 45.7, 58.5 ->
 // 47.9 (profiles/r6_wide.txt).  Where two workgroups fit a CU (8^3 C32) the same launch LOSES (63 -> 70 us): not taken there.
-// CLOUDCT_WIDE=0 turns it off (A/B runs).
+// CLOUDCT_WIDE=0 turns it off (A/B runs); so does CT_DEBUG_NO_WIDE, within one process (tests of narrow against wide).
 bool wide_enabled() {
   static const int env = [] {
     const char* e = getenv("CLOUDCT_WIDE");
     return e ? atoi(e) : 1;
   }();
-  return env != 0 && kHotThreads < kHotWideThreads;
+  return env != 0 && (t_dbg_flags.load(std::memory_order_relaxed) & CT_DEBUG_NO_WIDE) == 0 && kHotThreads < kHotWideThreads;
 }
 bool hot_wide(size_t lds, int nq) { return wide_enabled() && lds > (size_t)kHalfCuLdsBytes && nq > kHotThreads; }
 // does even a four-channel chunk of the fused Slice backward (conv tile + accumulators + counters) take more than half a CU's LDS?
@@ -2524,6 +2524,7 @@ int launch_splat_max_bwd(RasterArgs a, const GridW<DIM>& g, const Plan& p, bool 
     if (hipMemcpyAsync(ws, a.tile_in, need, hipMemcpyDeviceToDevice, st) != hipSuccess) return CT_ELAUNCH;
     a.claim = (unsigned*)ws;
     CT_LAUNCH((splat_max_bwd_kernel<DIM, FROM_KEYS, false, false>), grid, p.threads, 0, st, a, g);
+    note("splat_max_bwd_global");
     return CT_OK;
   }
   if constexpr (DIM == 2) {

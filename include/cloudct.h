@@ -29,7 +29,8 @@ extern "C" {
 #endif
 
 /* 2 (round 6): ct_plane_sort / ct_plane_sort_bytes / ct_slice_bwd_ps / ct_bn_group_reduce_bwd_copy added, ct_debug_set_pw_kernel
- * removed, since version 1 — a stale library selected by CLOUDCT_LIB fails this check instead of failing at symbol binding. */
+ * removed, since version 1 — a stale library selected by CLOUDCT_LIB fails this check instead of failing at symbol binding.
+ * (The test-hook flag CT_DEBUG_NO_WIDE was added later without a bump: an additive debug bit, no symbol or signature changed.) */
 #define CT_ABI_VERSION 2
 
 /* status codes */
@@ -122,6 +123,8 @@ int ct_splat_bwd_ex(const float* keys, const float* feat, const void* pad, int p
 #define CT_DEBUG_FORCE_SORTED 32 /* use them on every layout they can take, however few (b,h) planes there are */
 #define CT_DEBUG_FORCE_SORTED_SEG 64 /* 2D: the sorted-SEGMENT kernel (csrc/ct_raster_sorted3d.h, DIM = 2) wherever it is legal; 3D grids
                                         take it under CT_DEBUG_FORCE_SORTED already */
+#define CT_DEBUG_NO_WIDE 128   /* keep the 1024-thread WIDE launches of the hot backward kernels off (as CLOUDCT_WIDE=0, which is read
+                                  once per process): the narrow and the wide form compared within one process */
 void ct_debug_set_flags(unsigned flags);
 const char* ct_debug_last_launch(void);
 /* point segments of the hot Splat(max) backward (ct_splat_bwd_tk): 0 automatic, 1 never, n > 1: n wherever legal */
