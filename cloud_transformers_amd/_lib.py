@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("CLOUDCT_LIB") or os.path.join(LIB_DIR, "libcloudct.so
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 
 HIP_SOURCES = ["ct_raster.hip", "ct_mhct.hip", "ct_lattice.hip", "ct_gconv.hip", "ct_chamfer.hip", "ct_emd.hip",
-               "ct_adain.hip", "ct_bnorm.hip", "ct_pwgemm.hip"]
+               "ct_adain.hip", "ct_bnorm.hip", "ct_pwgemm.hip", "ct_nbr.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared",
                # index/weight math must round exactly like the reference's fp32 op sequence
                "-ffp-contract=off"]
@@ -79,6 +79,8 @@ DEBUG_NO_SORTED = 16
 DEBUG_FORCE_SORTED = 32
 DEBUG_FORCE_SORTED_SEG = 64
 DEBUG_NO_WIDE = 128
+NBR_K_MAX = 16384          # ct_nbr_radius: keys a query keeps in LDS
+NBR_MAX_CELLS = 1 << 26    # ct_nbr_* grids
 
 _lock = threading.Lock()
 _lib = None
@@ -203,6 +205,7 @@ def load_host():
 _vp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 _ll = ctypes.c_longlong
 _ip = ctypes.POINTER(ctypes.c_int)
+_fp = ctypes.POINTER(ctypes.c_float)
 
 # name -> (restype, argtypes); mirrors include/cloudct.h one to one
 SIGNATURES = {
@@ -305,6 +308,10 @@ SIGNATURES = {
     "ct_pw_gemm_rs_add": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _sz, _i, _i, _i, _i, _vp]),
     "ct_amax_rows_f32": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "ct_pw_prep_weight_rs": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "ct_nbr_index_workspace_bytes": (_sz, [ctypes.c_int64, _ip]),
+    "ct_nbr_index_build": (_i, [_vp, ctypes.c_int64, _fp, _f, _ip, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ct_nbr_radius": (_i, [_vp, _vp, _fp, _f, _ip, _vp, _i, _f, _i, _vp, _vp, _vp, _vp]),
+    "ct_nbr_nearest": (_i, [_vp, _vp, _fp, _f, _ip, _vp, ctypes.c_int64, _vp, _vp, _vp]),
 }
 
 
@@ -345,3 +352,7 @@ def check(status, what):
 
 def int_array(values):
     return (ctypes.c_int * len(values))(*[int(v) for v in values])
+
+
+def float_array(values):
+    return (ctypes.c_float * len(values))(*[float(v) for v in values])

@@ -1,0 +1,310 @@
+"""The S3DIS KPConv protocol (configs/s3dis_kpconv.yaml; datasets/s3dis_closer.py, datasets/s3dis_closer_train.py:70-170,
+datasets/s3dis_closer_utils.py:252-333) with its neighbour work on the GPU (cloud_transformers_amd.neighbors.GridIndex).
+
+- `load_areas`: the Stanford3dDataset_v1.2 text layout -> one cloud per Area, grid-subsampled on the host
+  (data.subsampling.grid_subsampling), cached as .npz arrays (s3dis_closer.py:132-201).
+- `SphereSampler`: the potential-field sphere picking and the item layout of S3DISSeg (s3dis_closer.py:239-276,302-361),
+  batched, on the device.  Same semantics, not the reference's numpy random stream.
+- `VoteEvaluator`: the validation voting and the sub-sampled / full-resolution IoUs (s3dis_closer_train.py:134-167,
+  s3dis_closer_utils.py:252-333) with device scatters and device confusion matrices.
+
+Unlike the rest of `data`, the sampler and the evaluator keep their tensors on a HIP device."""
+import math
+import os
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from .subsampling import grid_subsampling
+
+LABEL_TO_NAMES = {0: "ceiling", 1: "floor", 2: "wall", 3: "beam", 4: "column", 5: "window", 6: "door", 7: "chair", 8: "table",
+                  9: "bookcase", 10: "sofa", 11: "board", 12: "clutter"}
+NAME_TO_LABEL = {v: k for k, v in LABEL_TO_NAMES.items()}
+COLOR_MEAN = (0.5136457, 0.49523646, 0.44921124)        # s3dis_closer.py:118-119
+COLOR_STD = (0.18308958, 0.18415008, 0.19252081)
+TRAIN_AREAS = ["Area_1", "Area_2", "Area_3", "Area_4", "Area_6"]
+VAL_AREAS = ["Area_5"]
+
+
+@dataclass
+class Area:
+    """One Area as one cloud: the raw points (colours 0..255, labels) and the grid-subsampled cloud (colours / 255)."""
+    name: str
+    points: np.ndarray       # f32 [N, 3]
+    colors: np.ndarray       # f32 [N, 3], 0..255
+    labels: np.ndarray       # i32 [N]
+    sub_points: np.ndarray   # f32 [M, 3]
+    sub_colors: np.ndarray   # f32 [M, 3], 0..1
+    sub_labels: np.ndarray   # i32 [M]
+
+
+def _area_name(a):
+    return "Area_%d" % a if isinstance(a, (int, np.integer)) else str(a)
+
+
+def _object_label(object_name):
+    tmp = object_name[:-4].split("_")[0]
+    if tmp in NAME_TO_LABEL:
+        return NAME_TO_LABEL[tmp]
+    if tmp == "stairs":
+        return NAME_TO_LABEL["clutter"]
+    raise ValueError("Unknown object name: " + str(tmp))
+
+
+def _read_area(folder):
+    """s3dis_closer.py:142-176: every room's Annotations/*.txt (x y z r g b per line), rooms and objects in name order."""
+    pts, cols, labs = [], [], []
+    for room in sorted(os.listdir(folder)):
+        ann = os.path.join(folder, room, "Annotations")
+        if not os.path.isdir(ann):
+            continue
+        for obj in sorted(os.listdir(ann)):
+            if obj[-4:] != ".txt":
+                continue
+            label = _object_label(obj)
+            data = np.loadtxt(os.path.join(ann, obj), dtype=np.float64, ndmin=2)
+            if data.size == 0:
+                continue
+            pts.append(data[:, 0:3].astype(np.float32))
+            cols.append(data[:, 3:6].astype(np.uint8).astype(np.float32))
+            labs.append(np.full(data.shape[0], label, dtype=np.int32))
+    if not pts:
+        raise ValueError("no annotated objects under %s" % folder)
+    return np.concatenate(pts), np.concatenate(cols), np.concatenate(labs)
+
+
+def load_areas(data_root, areas, sampleDl=0.04, cache_dir=None):
+    """Areas (names 'Area_k' or numbers k) of `data_root` — the Stanford3dDataset_v1.2 folder or its parent — as `Area`s.
+    With `cache_dir`, each Area's arrays are kept in <cache_dir>/<Area>_<sampleDl:.3f>.npz and read back from there."""
+    root = data_root
+    if os.path.isdir(os.path.join(data_root, "Stanford3dDataset_v1.2")):
+        root = os.path.join(data_root, "Stanford3dDataset_v1.2")
+    out = []
+    for a in areas:
+        name = _area_name(a)
+        cache = os.path.join(cache_dir, "%s_%.3f.npz" % (name, sampleDl)) if cache_dir else None
+        if cache and os.path.exists(cache):
+            with np.load(cache, allow_pickle=False) as z:
+                out.append(Area(name, *(z[k] for k in ("points", "colors", "labels", "sub_points", "sub_colors", "sub_labels"))))
+            continue
+        points, colors, labels = _read_area(os.path.join(root, name))
+        if sampleDl > 0:
+            sub_points, sub_colors, sub_labels = grid_subsampling(points, features=colors, labels=labels[:, None], sampleDl=sampleDl)
+            sub_colors = sub_colors / np.float32(255.0)
+            sub_labels = np.squeeze(sub_labels, axis=1)
+        else:
+            sub_points, sub_colors, sub_labels = points, colors / np.float32(255.0), labels
+        area = Area(name, points, colors, labels, sub_points.astype(np.float32), sub_colors.astype(np.float32),
+                    sub_labels.astype(np.int32))
+        if cache:
+            os.makedirs(cache_dir, exist_ok=True)
+            tmp = cache + ".%d.tmp.npz" % os.getpid()
+            np.savez(tmp, points=area.points, colors=area.colors, labels=area.labels, sub_points=area.sub_points,
+                     sub_colors=area.sub_colors, sub_labels=area.sub_labels)
+            os.replace(tmp, cache)
+        out.append(area)
+    return out
+
+
+def scene_seg_features(input_features_dim, pc, color, height):
+    """get_scene_seg_features (s3dis_closer.py:49-65) over a batch: pc [B,N,3], color [B,N,3], height [B,N,1] -> [B,F,N]."""
+    if input_features_dim == 1:
+        f = height
+    elif input_features_dim == 3:
+        f = color
+    elif input_features_dim == 4:
+        f = torch.cat([color, height], -1)
+    elif input_features_dim == 5:
+        f = torch.cat([torch.ones_like(height), color, height], -1)
+    elif input_features_dim == 6:
+        f = torch.cat([color, pc], -1)
+    elif input_features_dim == 7:
+        f = torch.cat([color, height, pc], -1)
+    else:
+        raise NotImplementedError("input_features_dim %r" % (input_features_dim,))
+    return f.transpose(1, 2).contiguous()
+
+
+class SphereSampler:
+    """Spheres of `in_radius` picked by the potential field of S3DISSeg (s3dis_closer.py:239-276), items laid out as its
+    __getitem__ (:302-361), B at a time.  State on `device`: the subsampled clouds, their GridIndex and the potentials
+    (`potentials[c]`, f32; `min_potentials` f32[clouds]).  `last_picks` keeps (cloud, point, pick point f32[3]) of every item of
+    the last `sample` call, in order, so that a test can replay the potential updates."""
+
+    def __init__(self, areas, num_points, in_radius=2.0, input_features_dim=4, color_drop=0.2, device="cuda", generator=None,
+                 cell=None):
+        from ..neighbors import GridIndex
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("SphereSampler needs a HIP device; there is no CPU fallback")
+        if generator is None:
+            generator = torch.Generator(device=self.device)
+            generator.seed()
+        self.gen = generator
+        self.num_points, self.in_radius = int(num_points), float(in_radius)
+        self.input_features_dim, self.color_drop = int(input_features_dim), float(color_drop)
+        if self.input_features_dim not in (1, 3, 4, 5, 6, 7):
+            raise NotImplementedError("input_features_dim %r" % (input_features_dim,))
+        dev = self.device
+        self.sub_points = [torch.from_numpy(np.ascontiguousarray(a.sub_points, np.float32)).to(dev) for a in areas]
+        self.indices = [GridIndex(p, cell) for p in self.sub_points]
+        sizes = [p.shape[0] for p in self.sub_points]
+        self.offsets = torch.tensor([0] + list(np.cumsum(sizes)[:-1]), dtype=torch.int64, device=dev)
+        self._all_points = torch.cat(self.sub_points)
+        self._all_colors = torch.from_numpy(np.concatenate([np.asarray(a.sub_colors, np.float32) for a in areas])).to(dev)
+        self._all_labels = torch.from_numpy(np.concatenate([np.asarray(a.sub_labels) for a in areas]).astype(np.int64)).to(dev)
+        # s3dis_closer.py:241-245: uniform potentials in [0, 1e-3)
+        self.potentials = [torch.rand(n, generator=self.gen, device=dev) * 1e-3 for n in sizes]
+        self.min_potentials = torch.stack([p.min() for p in self.potentials])
+        self._mean = torch.tensor(COLOR_MEAN, dtype=torch.float32, device=dev)
+        self._std = torch.tensor(COLOR_STD, dtype=torch.float32, device=dev)
+        self.last_picks = []
+
+    def _pick(self):
+        """One item (s3dis_closer.py:247-276): pick, sorted radius query cut to num_points, Tukey update of the potentials."""
+        ci = 0 if len(self.potentials) == 1 else int(torch.argmin(self.min_potentials))
+        pot = self.potentials[ci]
+        pi = torch.argmin(pot)
+        r = self.in_radius
+        noise = torch.randn(3, generator=self.gen, device=self.device) * (r / 10)
+        pick = self.sub_points[ci][pi] + noise
+        idx, d2, count = self.indices[ci].query_radius(pick[None], r, self.num_points)
+        idx, d2 = idx[0], d2[0]
+        valid = idx >= 0
+        tukey = torch.where(valid, torch.square(1 - d2 / (r * r)), torch.zeros_like(d2))
+        pot.index_add_(0, idx.clamp(min=0), tukey)
+        self.min_potentials[ci] = pot.min()
+        self.last_picks.append((ci, pi, pick))
+        return ci, pick, idx, count[0]
+
+    def sample(self, B):
+        """B items: points f32[B,N,3] (centred on the pick point), mask i32[B,N], features f32[B,F,N], labels i64[B,N],
+        cloud_index i64[B], input_inds i64[B,N] (indices into the item's subsampled cloud)."""
+        self.last_picks = []
+        items = [self._pick() for _ in range(B)]
+        dev, N = self.device, self.num_points
+        cloud = torch.tensor([it[0] for it in items], dtype=torch.int64, device=dev)
+        picks = torch.stack([it[1] for it in items])                                    # [B, 3]
+        idx = torch.stack([it[2] for it in items])                                      # [B, N], sorted by (d2, index)
+        count = torch.stack([it[3] for it in items])
+        nvalid = torch.clamp(count, max=N)
+        slot = torch.arange(N, device=dev)[None, :]
+        live = slot < nvalid[:, None]
+        # a random permutation of the valid slots (:333-335), then padding drawn from them with replacement (:336-337)
+        keys = torch.where(live, torch.rand(B, N, generator=self.gen, device=dev), torch.full((B, N), 2.0, device=dev))
+        perm = torch.argsort(keys, dim=1)
+        pad = torch.floor(torch.rand(B, N, generator=self.gen, device=dev) * nvalid[:, None]).long().clamp_(0, N - 1)
+        src = torch.where(live, perm, perm.gather(1, pad))
+        input_inds = idx.gather(1, src).clamp_(min=0)
+        mask = live.to(torch.int32)
+        g = input_inds + self.offsets[cloud][:, None]
+        original = self._all_points[g]                                                  # [B, N, 3]
+        points = original - picks[:, None, :]
+        height = original[:, :, 2:]
+        colors = (self._all_colors[g] - self._mean) / self._std
+        drop = (torch.rand(B, generator=self.gen, device=dev) > self.color_drop).float()
+        colors = colors * drop[:, None, None]
+        labels = self._all_labels[g]
+        features = scene_seg_features(self.input_features_dim, points, colors, height)
+        return points, mask, features, labels, cloud, input_inds
+
+
+def iou_from_confusions(confusions):
+    """IoU_from_confusions (s3dis_closer_utils.py:252-279) on a torch tensor [..., C, C] (rows truth, columns prediction)."""
+    c = confusions if confusions.is_floating_point() else confusions.double()
+    tp = torch.diagonal(c, dim1=-2, dim2=-1)
+    tp_fn = c.sum(-1)
+    tp_fp = c.sum(-2)
+    iou = tp / (tp_fp + tp_fn - tp + 1e-6)
+    absent = tp_fn < 1e-3
+    counts = (~absent).to(c.dtype).sum(-1, keepdim=True)
+    miou = iou.sum(-1, keepdim=True) / (counts + 1e-6)
+    return iou + absent.to(c.dtype) * miou
+
+
+def _confusion(truth, pred, C):
+    """sklearn confusion_matrix(truth, pred, labels=arange(C)) on the device: i64 [C, C]."""
+    return torch.bincount(truth.long() * C + pred.long(), minlength=C * C)[:C * C].view(C, C)
+
+
+class VoteEvaluator:
+    """Validation voting (s3dis_closer_train.py:70-167) on the device.  Per subsampled cloud: the summed logits, the vote
+    counts (from 1e-6) and the running smoothed logits; `add` applies the reference's per-item loop (:134-145) item by item
+    (items of one batch may share points), `sub_ious` / `full_ious` are sub_s3dis_metrics / s3dis_metrics
+    (s3dis_closer_utils.py:282-333), the full-resolution one through the nearest subsampled point of every raw point
+    (GridIndex.nearest, computed once and kept on the device)."""
+
+    def __init__(self, areas, num_classes=13, smooth=0.95, device="cuda"):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("VoteEvaluator needs a HIP device; there is no CPU fallback")
+        self.areas, self.C, self.smooth = list(areas), int(num_classes), float(smooth)
+        dev = self.device
+        sizes = [a.sub_points.shape[0] for a in self.areas]
+        self.sizes = sizes
+        self.offsets = torch.tensor([0] + list(np.cumsum(sizes)[:-1]), dtype=torch.int64, device=dev)
+        self.total = int(sum(sizes))
+        # one extra column: the write target of masked slots, so that padding never touches a real point
+        self.logits_sum = torch.zeros(self.C, self.total + 1, dtype=torch.float32, device=dev)
+        self.counts = torch.full((1, self.total + 1), 1e-6, dtype=torch.float32, device=dev)
+        self.running = torch.zeros(self.C, self.total + 1, dtype=torch.float32, device=dev)
+        self.sub_labels = torch.from_numpy(np.concatenate([np.asarray(a.sub_labels) for a in self.areas]).astype(np.int64)).to(dev)
+        props = np.zeros(self.C, dtype=np.float32)
+        for k in range(self.C):
+            props[k] = np.sum([np.sum(a.labels == k) for a in self.areas])
+        self.val_proportions = torch.from_numpy(props).to(dev)
+        self._proj = None
+
+    def add(self, pred, mask, cloud_index, input_inds):
+        """pred f32[B,C,N] (logits), mask [B,N], cloud_index i64[B], input_inds i64[B,N] — one batch of the loop."""
+        pred = pred.detach().float()
+        B = pred.shape[0]
+        live = mask.to(self.device).bool()
+        g = input_inds.to(self.device).long() + self.offsets[cloud_index.to(self.device).long()][:, None]
+        g = torch.where(live, g, torch.full_like(g, self.total))
+        a = 1.0 - self.smooth
+        for b in range(B):
+            lg, gb = pred[b], g[b]
+            self.logits_sum.index_add_(1, gb, torch.where(live[b][None], lg, torch.zeros_like(lg)))
+            self.counts.index_add_(1, gb, live[b][None].float())
+            self.running[:, gb] = self.smooth * self.running[:, gb] + a * lg
+
+    def vote_logits(self):
+        """vote_logits_sum / vote_counts over all clouds, f32[C, total]."""
+        return (self.logits_sum / self.counts)[:, :self.total]
+
+    def _sub(self, logits):
+        pred = torch.argmax(logits, dim=0)
+        conf = _confusion(self.sub_labels, pred, self.C).float()
+        conf = conf * (self.val_proportions / (conf.sum(1) + 1e-6))[:, None]
+        iou = iou_from_confusions(conf)
+        return iou.cpu().numpy(), float(iou.mean())
+
+    def sub_ious(self, running=False):
+        """sub_s3dis_metrics: IoUs of the subsampled clouds, confusion rescaled to the raw class proportions; running=True
+        scores the running smoothed logits instead of the vote average."""
+        return self._sub(self.running[:, :self.total] if running else self.vote_logits())
+
+    def projections(self):
+        """Per Area, the nearest subsampled point of every raw point (s3dis_closer.py:285-299), i64 on the device."""
+        if self._proj is None:
+            from ..neighbors import GridIndex
+            proj = []
+            for a in self.areas:
+                index = GridIndex(torch.from_numpy(np.ascontiguousarray(a.sub_points, np.float32)).to(self.device))
+                idx, _ = index.nearest(torch.from_numpy(np.ascontiguousarray(a.points, np.float32)).to(self.device))
+                proj.append(idx)
+            self._proj = proj
+        return self._proj
+
+    def full_ious(self):
+        """s3dis_metrics: IoUs at full resolution, every raw point taking the vote of its nearest subsampled point."""
+        logits = self.vote_logits()
+        conf = torch.zeros(self.C, self.C, dtype=torch.int64, device=self.device)
+        for a, off, proj in zip(self.areas, self.offsets.tolist(), self.projections()):
+            pred = torch.argmax(logits[:, off + proj], dim=0)
+            truth = torch.from_numpy(np.asarray(a.labels).astype(np.int64)).to(self.device)
+            conf += _confusion(truth, pred, self.C)
+        iou = iou_from_confusions(conf)
+        return iou.cpu().numpy(), float(iou.mean())

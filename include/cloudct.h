@@ -30,7 +30,9 @@ extern "C" {
 
 /* 2 (round 6): ct_plane_sort / ct_plane_sort_bytes / ct_slice_bwd_ps / ct_bn_group_reduce_bwd_copy added, ct_debug_set_pw_kernel
  * removed, since version 1 — a stale library selected by CLOUDCT_LIB fails this check instead of failing at symbol binding.
- * (The test-hook flag CT_DEBUG_NO_WIDE was added later without a bump: an additive debug bit, no symbol or signature changed.) */
+ * (The test-hook flag CT_DEBUG_NO_WIDE was added later without a bump: an additive debug bit, no symbol or signature changed.
+ * The neighbour-search entry points ct_nbr_* were added under version 2 as well: additive symbols, which the loader's
+ * missing-symbol scan checks.) */
 #define CT_ABI_VERSION 2
 
 /* status codes */
@@ -616,6 +618,42 @@ int ct_pw_gemm_rs(int mode, const float* a, const float* b, float* out, const fl
 int ct_pw_gemm_rs_add(int mode, const float* a, const float* b, float* out, const float* addend, const float* amax_a, int n_amax_a,
                       int rows_a, const float* amax_b, int n_amax_b, int rows_b, void* workspace, size_t workspace_bytes, int B,
                       int Co, int Ci, int N, ct_stream_t s);
+
+/* ------------------------------------------------------------------------
+ * Neighbour search of the S3DIS KPConv protocol over a uniform grid (replaces the CPU
+ * sklearn.neighbors.KDTree of datasets/s3dis_closer.py:204 `KDTree(sub_points)`,
+ * :262-265,319-322 `query_radius(pick_point, r, sort_results=True)` cut to num_points,
+ * :290 `query(points)`).  Added under CT_ABI_VERSION 2 (additive: the loader's
+ * missing-symbol scan refuses a library built before them).
+ *
+ * Grid: origin f32[3] and dims int[3] (host arrays), cell edge h > 0, at most 2^26 cells;
+ * cell of p = floor((p - origin) / h) per axis, clamped to the grid (points outside the
+ * box land in an edge cell and are still found exactly), cell id (iz*ny + iy)*nx + ix,
+ * so one x-row of cells is one contiguous range of the order.
+ * Squared distances are ((dx*dx) + (dy*dy)) + (dz*dz), d = p - c, in fp32 without
+ * contraction: numpy float32 computes the same bits.
+ *
+ * ct_nbr_index_build: points f32[M,3] (1 <= M < 2^31) -> cell_start i32[ncells+1] (points of
+ * cell c are order[cell_start[c] .. cell_start[c+1])), order i32[M] (a counting sort of the
+ * point ids by cell; the order inside a cell follows atomics), sorted f32[M,4] (x, y, z and
+ * the point id's bits, in that order: what the queries read; 16-byte aligned, CT_EINVAL
+ * otherwise, in the build and in both queries).  Workspace:
+ * ct_nbr_index_workspace_bytes (0 = bad arguments).
+ * ct_nbr_radius: for each of Q centres f32[Q,3], count i64[Q] = #points with d2 <= r*r (not
+ * truncated); idx i64[Q,K] / d2 f32[Q,K] = the first min(count, K) of them by (d2, index)
+ * ascending, then -1 / +inf.  K <= 16384, r >= 0.  One workgroup per centre.
+ * ct_nbr_nearest: for each of Q queries f32[Q,3] (any position; 1 <= Q < 2^31 per call, one
+ * launch: larger sets go in several calls), the nearest point's index i64[Q] (lowest index on
+ * ties) and d2 f32[Q]; no workspace.
+ * ---------------------------------------------------------------------- */
+size_t ct_nbr_index_workspace_bytes(int64_t M, const int* dims);
+int ct_nbr_index_build(const float* points, int64_t M, const float* origin, float h, const int* dims,
+                       int32_t* cell_start, int32_t* order, float* sorted, void* workspace, size_t workspace_bytes,
+                       ct_stream_t s);
+int ct_nbr_radius(const int32_t* cell_start, const float* sorted, const float* origin, float h, const int* dims,
+                  const float* centres, int Q, float r, int K, int64_t* idx, float* d2, int64_t* count, ct_stream_t s);
+int ct_nbr_nearest(const int32_t* cell_start, const float* sorted, const float* origin, float h, const int* dims,
+                   const float* queries, int64_t Q, int64_t* idx, float* d2, ct_stream_t s);
 
 #ifdef __cplusplus
 }
