@@ -4,11 +4,13 @@ datasets/s3dis_closer_utils.py:252-333) with its neighbour work on the GPU (clou
 - `load_areas`: the Stanford3dDataset_v1.2 text layout -> one cloud per Area, grid-subsampled on the host
   (data.subsampling.grid_subsampling), cached as .npz arrays (s3dis_closer.py:132-201).
 - `SphereSampler`: the potential-field sphere picking and the item layout of S3DISSeg (s3dis_closer.py:239-276,302-361),
-  batched, on the device.  Same semantics, not the reference's numpy random stream.
+  batched, on the device (`plan` picks, `items` assembles them in one `ct_kp_items` launch, optionally augmented by
+  `Augment`: the training transforms of s3dis_closer_utils.py:38-149).  Same semantics, not the reference's numpy random stream.
 - `VoteEvaluator`: the validation voting and the sub-sampled / full-resolution IoUs (s3dis_closer_train.py:134-167,
   s3dis_closer_utils.py:252-333) with device scatters and device confusion matrices.
 
 Unlike the rest of `data`, the sampler and the evaluator keep their tensors on a HIP device."""
+import copy
 import math
 import os
 from dataclasses import dataclass
@@ -129,8 +131,8 @@ def scene_seg_features(input_features_dim, pc, color, height):
 class SphereSampler:
     """Spheres of `in_radius` picked by the potential field of S3DISSeg (s3dis_closer.py:239-276), items laid out as its
     __getitem__ (:302-361), B at a time.  State on `device`: the subsampled clouds, their GridIndex and the potentials
-    (`potentials[c]`, f32; `min_potentials` f32[clouds]).  `last_picks` keeps (cloud, point, pick point f32[3]) of every item of
-    the last `sample` call, in order, so that a test can replay the potential updates."""
+    (`potentials[c]`, f32; `min_potentials` f32[clouds]).  `last_picks` keeps (cloud, point, pick point f32[3]) of every pick of
+    the last `plan` (or `sample`) call, in order, so that a test can replay the potential updates."""
 
     def __init__(self, areas, num_points, in_radius=2.0, input_features_dim=4, color_drop=0.2, device="cuda", generator=None,
                  cell=None):
@@ -160,6 +162,7 @@ class SphereSampler:
         self._mean = torch.tensor(COLOR_MEAN, dtype=torch.float32, device=dev)
         self._std = torch.tensor(COLOR_STD, dtype=torch.float32, device=dev)
         self.last_picks = []
+        self.last_augment = (None, None, None)
 
     def _pick(self):
         """One item (s3dis_closer.py:247-276): pick, sorted radius query cut to num_points, Tukey update of the potentials."""
@@ -176,38 +179,137 @@ class SphereSampler:
         pot.index_add_(0, idx.clamp(min=0), tukey)
         self.min_potentials[ci] = pot.min()
         self.last_picks.append((ci, pi, pick))
-        return ci, pick, idx, count[0]
+        return ci, pick
 
-    def sample(self, B):
-        """B items: points f32[B,N,3] (centred on the pick point), mask i32[B,N], features f32[B,F,N], labels i64[B,N],
-        cloud_index i64[B], input_inds i64[B,N] (indices into the item's subsampled cloud)."""
+    def plan(self, n):
+        """n picks by the potential field (`_pick`, advancing the potentials): (cloud i64[n], pick points f32[n, 3]), on the
+        device; `last_picks` gets them in order."""
         self.last_picks = []
-        items = [self._pick() for _ in range(B)]
+        cloud, picks = [], []
+        for _ in range(int(n)):
+            ci, pick = self._pick()
+            cloud.append(ci)
+            picks.append(pick)
+        return torch.tensor(cloud, dtype=torch.int64, device=self.device), torch.stack(picks)
+
+    def items(self, cloud, picks, augment=None, generator=None):
+        """The items of picks (cloud i64[B], pick points f32[B, 3]), the 6-tuple of `sample`: one radius query per distinct cloud,
+        then the batch assembly `ct_kp_items`.  Draws, from `generator` (default: the sampler's own): the slot keys
+        rand(B, N), the padding rand(B, N), the colour drop rand(B); with `augment` (an `Augment`), then the angles, scales
+        and mirrors rand(B, 3) each and the jitter randn(B, N, 3).  `last_augment` keeps the (R, s, j) of the last call."""
+        gen = self.gen if generator is None else generator
         dev, N = self.device, self.num_points
-        cloud = torch.tensor([it[0] for it in items], dtype=torch.int64, device=dev)
-        picks = torch.stack([it[1] for it in items])                                    # [B, 3]
-        idx = torch.stack([it[2] for it in items])                                      # [B, N], sorted by (d2, index)
-        count = torch.stack([it[3] for it in items])
+        cloud = cloud.to(dev)
+        picks = picks.to(dev, torch.float32).contiguous()
+        B = picks.shape[0]
+        idx = torch.empty(B, N, dtype=torch.int64, device=dev)
+        count = torch.empty(B, dtype=torch.int64, device=dev)
+        host_cloud = cloud.tolist()
+        for ci in sorted(set(host_cloud)):
+            rows = [b for b, c in enumerate(host_cloud) if c == ci]
+            sel = torch.tensor(rows, dtype=torch.int64, device=dev) if len(rows) < B else None
+            q_idx, _, q_count = self.indices[ci].query_radius(picks if sel is None else picks[sel], self.in_radius, N)
+            if sel is None:
+                idx, count = q_idx, q_count
+            else:
+                idx[sel], count[sel] = q_idx, q_count
         nvalid = torch.clamp(count, max=N)
-        slot = torch.arange(N, device=dev)[None, :]
-        live = slot < nvalid[:, None]
-        # a random permutation of the valid slots (:333-335), then padding drawn from them with replacement (:336-337)
-        keys = torch.where(live, torch.rand(B, N, generator=self.gen, device=dev), torch.full((B, N), 2.0, device=dev))
+        live = torch.arange(N, device=dev)[None, :] < nvalid[:, None]
+        # a random permutation of the valid slots (:333-335); the argsort stays in torch, which decides the order of ties
+        keys = torch.where(live, torch.rand(B, N, generator=gen, device=dev), torch.full((B, N), 2.0, device=dev))
         perm = torch.argsort(keys, dim=1)
-        pad = torch.floor(torch.rand(B, N, generator=self.gen, device=dev) * nvalid[:, None]).long().clamp_(0, N - 1)
-        src = torch.where(live, perm, perm.gather(1, pad))
-        input_inds = idx.gather(1, src).clamp_(min=0)
-        mask = live.to(torch.int32)
-        g = input_inds + self.offsets[cloud][:, None]
-        original = self._all_points[g]                                                  # [B, N, 3]
-        points = original - picks[:, None, :]
-        height = original[:, :, 2:]
-        colors = (self._all_colors[g] - self._mean) / self._std
-        drop = (torch.rand(B, generator=self.gen, device=dev) > self.color_drop).float()
-        colors = colors * drop[:, None, None]
-        labels = self._all_labels[g]
-        features = scene_seg_features(self.input_features_dim, points, colors, height)
+        u_pad = torch.rand(B, N, generator=gen, device=dev)
+        drop = (torch.rand(B, generator=gen, device=dev) > self.color_drop).float()
+        R = s = j = None
+        if augment is not None:
+            R, s, j = augment.draw(B, N, gen, dev)
+        self.last_augment = (R, s, j)
+        points, mask, features, labels, input_inds = kp_items(idx, count, perm, u_pad, self.offsets[cloud], picks, drop,
+                                                              self._all_points, self._all_colors, self._all_labels, COLOR_MEAN,
+                                                              COLOR_STD, self.input_features_dim, R, s, j)
         return points, mask, features, labels, cloud, input_inds
+
+    def sample(self, B, augment=None):
+        """B items: points f32[B,N,3] (centred on the pick point), mask i32[B,N], features f32[B,F,N], labels i64[B,N],
+        cloud_index i64[B], input_inds i64[B,N] (indices into the item's subsampled cloud): `items(*plan(B), augment)`."""
+        return self.items(*self.plan(B), augment=augment)
+
+
+def kp_items(idx, count, perm, u_pad, offset, picks, drop, points, colors, labels, mean, std, F, R=None, s=None, j=None):
+    """ct_kp_items (include/cloudct.h): (points f32[B,N,3], mask i32[B,N], features f32[B,F,N], labels i64[B,N],
+    input_inds i64[B,N]) of B items from their ball queries (idx i64[B,N], count i64[B]), slot order `perm`, padding draws
+    `u_pad`, per-item cloud offset and pick point, colour drop, the concatenated sub-clouds, the colour mean / std (host
+    sequences of 3) and the optional augmentation."""
+    from .. import _lib
+    from ..ops import _dev, _on, _stream
+    _dev(idx)
+    dev = idx.device
+    B, N = idx.shape
+    if (R is None) != (s is None) or (R is None) != (j is None):
+        raise ValueError("kp_items: pass R, s and j together, or none of them")
+    mean_c, std_c = _lib.float_array(mean), _lib.float_array(std)
+    aug = [t.contiguous() if t is not None else None for t in (R, s, j)]
+    ins = [t.contiguous() for t in (idx, count, perm, u_pad, offset, picks, drop, points, colors, labels)]
+    out_p = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
+    mask = torch.empty(B, N, dtype=torch.int32, device=dev)
+    feats = torch.empty(B, int(F), N, dtype=torch.float32, device=dev)
+    out_l = torch.empty(B, N, dtype=torch.int64, device=dev)
+    inds = torch.empty(B, N, dtype=torch.int64, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
+    with _on(dev):
+        _lib.check(_lib.load().ct_kp_items(*[t.data_ptr() for t in ins], points.shape[0], mean_c, std_c, *[ptr(t) for t in aug],
+                                           B, N, int(F), out_p.data_ptr(), mask.data_ptr(), feats.data_ptr(), out_l.data_ptr(),
+                                           inds.data_ptr(), _stream(dev)), "ct_kp_items")
+    return out_p, mask, feats, out_l, inds
+
+
+def angle_axis(angle, axis):
+    """angle_axis (s3dis_closer_utils.py:8-36) over a batch: angles f64[...] about the unit `axis` -> f32[..., 3, 3], built in
+    float64 as cos*I + sin*[u]x + (1 - cos)*u u^T, in that order, then rounded to float32."""
+    angle = angle.double()
+    u = torch.tensor(axis, dtype=torch.float64, device=angle.device)
+    u = u / torch.linalg.norm(u)
+    cross = torch.tensor([[0.0, -u[2], u[1]], [u[2], 0.0, -u[0]], [-u[1], u[0], 0.0]], dtype=torch.float64, device=angle.device)
+    c, s_ = torch.cos(angle)[..., None, None], torch.sin(angle)[..., None, None]
+    eye = torch.eye(3, dtype=torch.float64, device=angle.device)
+    return (c * eye + s_ * cross + (1.0 - c) * torch.outer(u, u)).float()
+
+
+def rotation_factors(angles):
+    """(Rx, Ry, Rz) f32[B, 3, 3] of angles [B, 3] (x, y, z): PointcloudRandomRotate's factors (s3dis_closer_utils.py:76-93)."""
+    return tuple(angle_axis(angles[:, a], ax) for a, ax in enumerate(([1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0])))
+
+
+@dataclass
+class Augment:
+    """PointcloudRandomRotate + PointcloudScaleAndJitter with the values of train_segmentation_kpconv.py:84-130: an angle per
+    axis uniform in +-range, R = Rz Ry Rx (factors in float64 rounded to f32, composed in f32); a scale per axis uniform in
+    [scale_low, scale_high), its sign flipped with probability 1/2 on the axes `symmetries` names; a jitter per point and
+    axis, normal with `std`, clipped at +-clip."""
+    x_range: float = 0.0
+    y_range: float = 0.0
+    z_range: float = 3.1415926
+    scale_low: float = 0.7
+    scale_high: float = 1.3
+    std: float = 0.001
+    clip: float = 0.05
+    symmetries: tuple = (1, 0, 0)
+
+    def draw(self, B, N, generator, device):
+        """(R f32[B,3,3], s f32[B,3], j f32[B,N,3]): angles, scales, mirrors rand(B, 3) each, then jitter randn(B, N, 3)."""
+        u_ang = torch.rand(B, 3, generator=generator, device=device)
+        u_scale = torch.rand(B, 3, generator=generator, device=device)
+        u_sym = torch.rand(B, 3, generator=generator, device=device)
+        jit = torch.randn(B, N, 3, generator=generator, device=device)
+        ranges = torch.tensor([self.x_range, self.y_range, self.z_range], dtype=torch.float64, device=device)
+        angles = (u_ang.double() * 2.0 - 1.0) * ranges
+        Rx, Ry, Rz = rotation_factors(angles)
+        R = torch.matmul(torch.matmul(Rz, Ry), Rx)
+        sym = torch.tensor([float(v) for v in self.symmetries], dtype=torch.float64, device=device)
+        sign = (torch.round(u_sym.double()) * 2.0 - 1.0) * sym + (1.0 - sym)
+        s = ((self.scale_low + (self.scale_high - self.scale_low) * u_scale.double()) * sign).float()
+        j = torch.clamp(jit * self.std, -self.clip, self.clip)
+        return R.contiguous(), s.contiguous(), j.contiguous()
 
 
 def iou_from_confusions(confusions):
@@ -255,6 +357,8 @@ class VoteEvaluator:
             props[k] = np.sum([np.sum(a.labels == k) for a in self.areas])
         self.val_proportions = torch.from_numpy(props).to(dev)
         self._proj = None
+        # the confusion of the items' own predictions over one vote pass (s3dis_part_metrics), i64 [C, C] + a dump bin
+        self.part_conf = torch.zeros(self.C * self.C + 1, dtype=torch.int64, device=dev)
 
     def add(self, pred, mask, cloud_index, input_inds):
         """pred f32[B,C,N] (logits), mask [B,N], cloud_index i64[B], input_inds i64[B,N] — one batch of the loop."""
@@ -264,11 +368,49 @@ class VoteEvaluator:
         g = input_inds.to(self.device).long() + self.offsets[cloud_index.to(self.device).long()][:, None]
         g = torch.where(live, g, torch.full_like(g, self.total))
         a = 1.0 - self.smooth
+        truth = self.sub_labels[torch.clamp(g, max=self.total - 1)]
+        cell = torch.where(live, truth * self.C + torch.argmax(pred, dim=1), torch.full_like(g, self.C * self.C))
+        self.part_conf += torch.bincount(cell.reshape(-1), minlength=self.C * self.C + 1)
         for b in range(B):
             lg, gb = pred[b], g[b]
             self.logits_sum.index_add_(1, gb, torch.where(live[b][None], lg, torch.zeros_like(lg)))
             self.counts.index_add_(1, gb, live[b][None].float())
             self.running[:, gb] = self.smooth * self.running[:, gb] + a * lg
+
+    def reset_votes(self):
+        """A new validation (s3dis_closer_train.py:75-80): zero vote sums, counts back to 1e-6, and a new vote pass.  The
+        running smoothed logits persist (train_segmentation_kpconv.py:206-207)."""
+        self.logits_sum.zero_()
+        self.counts.fill_(1e-6)
+        self.start_pass()
+
+    def start_pass(self):
+        """A new vote pass: the part confusion starts from zero."""
+        self.part_conf.zero_()
+
+    def synced(self, dist):
+        """The evaluator with its vote sums, vote counts and part confusion SUMmed over the ranks of `dist` (all-reduces on
+        copies: this rank's own state keeps accumulating); itself without an active process group.  The running logits
+        stay per rank, as in the reference.  Counts: every rank but 0 contributes its votes without the 1e-6 floor, so that
+        the sum keeps one floor."""
+        from .. import parallel
+        if not parallel._active(dist):
+            return self
+        self.projections()
+        out = copy.copy(self)
+        out.logits_sum, out.part_conf = self.logits_sum.clone(), self.part_conf.clone()
+        out.counts = self.counts.clone() if dist.get_rank() == 0 else torch.round(self.counts - 1e-6)
+        for t in (out.logits_sum, out.counts, out.part_conf):
+            dist.all_reduce(t)
+        return out
+
+    def part_ious(self):
+        """s3dis_part_metrics: IoUs of the items' own predictions over the current vote pass, the confusion rescaled to
+        the raw class proportions."""
+        conf = self.part_conf[:self.C * self.C].view(self.C, self.C).float()
+        conf = conf * (self.val_proportions / (conf.sum(1) + 1e-6))[:, None]
+        iou = iou_from_confusions(conf)
+        return iou.cpu().numpy(), float(iou.mean())
 
     def vote_logits(self):
         """vote_logits_sum / vote_counts over all clouds, f32[C, total]."""

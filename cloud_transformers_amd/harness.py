@@ -12,8 +12,10 @@ package's layers and checkpoints stay interchangeable.
 * data: `SyntheticClouds` produces batches of the shapes and dtypes the reference loaders yield (no files needed); with
   `data.kind` in the config (or `Trainer(dataset=...)`) the loop runs on `data/datasets.py`'s readers instead — `scanobjectnn`
   (datasets/scanobjectnn.py: `data.path` = the .h5 / .npz file) and `s3dis` (datasets/s3dis_v2.py: `data.path` = the
-  indoor3d_sem_seg_hdf5_data directory), items equal to the reference loaders' under the same seeds.  The remaining dataset
-  variants (s3dis_closer*, GRNet completion, image_point) stay out of scope.
+  indoor3d_sem_seg_hdf5_data directory), items equal to the reference loaders' under the same seeds.  `s3dis_kpconv`
+  (`data.path` = the Stanford3dDataset_v1.2 folder) selects the `segmentation_kpconv` task: sphere items sampled on the
+  device, masked cross-entropy with gradient clipping, vote validation and per-epoch checkpoints (train_kpconv.py,
+  train_segmentation_kpconv.py).  The remaining dataset variants (GRNet completion, image_point) stay out of scope.
 """
 import copy
 import datetime
@@ -172,9 +174,14 @@ class SyntheticClouds(torch.utils.data.Dataset):
 
 
 def make_dataset(cfg, task, n_classes, length=64, channels=3, train=True):
-    """The dataset `data.kind` of the config names: "synthetic" (default), "scanobjectnn" or "s3dis" (data/datasets.py)."""
+    """The dataset `data.kind` of the config names: "synthetic" (default), "scanobjectnn" or "s3dis" (data/datasets.py);
+    "s3dis_kpconv" gives the (train, validation) Areas of train_kpconv.load_kpconv_areas (`train=False`: no train Areas)."""
     data = cfg["data"]
     kind = str(data.get("kind", "synthetic")).lower()
+    if kind == "s3dis_kpconv":
+        assert task == "segmentation_kpconv", "S3DIS KPConv items are (points, mask, features, labels): the segmentation_kpconv task"
+        from .train_kpconv import load_kpconv_areas
+        return load_kpconv_areas(cfg, train=train)
     if kind == "synthetic":
         return SyntheticClouds(task, data["num_points"], n_classes, length=length, channels=channels)
     from .data import datasets as D
@@ -186,7 +193,7 @@ def make_dataset(cfg, task, n_classes, length=64, channels=3, train=True):
         assert task == "segmentation", "S3DIS blocks are (points, labels): the segmentation task"
         return D.Indoor3DSemSeg(data["path"], data["num_points"], train=train, aug=bool(data.get("aug", train)),
                                 test_area=data.get("test_area", "Area_5"), data_precent=float(data.get("data_precent", 1.0)))
-    raise ValueError("data.kind must be synthetic, scanobjectnn or s3dis (got %r)" % kind)
+    raise ValueError("data.kind must be synthetic, scanobjectnn, s3dis or s3dis_kpconv (got %r)" % kind)
 
 
 class Trainer:
@@ -196,11 +203,18 @@ class Trainer:
     `task`: "segmentation" (loss = CE(pred[:, :, 0], labels), train_segmentation.py:178), "classification"
     (loss = CE(logits, label) + seg_weight * BCE-with-logits(mask), train_classification.py) or "completion"
     (loss = mean sqrt(EMD(rec, gt, 0.005, 50)) + chamfer_weight * loss_chamfer(rec, gt), train_inpainter.py:186-192;
-    `n_classes` is then the size of the partial cloud)."""
+    `n_classes` is then the size of the partial cloud) or "segmentation_kpconv" (selected by `data.kind: s3dis_kpconv` too:
+    loss = sum(CE * mask) / sum(mask) of model(points, mask, features), gradients clipped to `train.clip_grad_norm` (10),
+    validation every `train.val_step` epochs and after the last, `generator_epoch_{e}.t7` / `g_opt_epoch_{e}.t7` every
+    `train.save_each_epoch` epochs; `dataset` may be the (train, validation) Areas — train_kpconv.py)."""
 
     def __init__(self, cfg, task, n_classes, device=None, dist=None, exp_name="exp", dataset_length=64, make_dirs=True,
                  channels=3, dataset=None):
         self.cfg = cfg = copy.deepcopy(cfg)
+        if task == "segmentation_kpconv" or str(cfg["data"].get("kind", "")).lower() == "s3dis_kpconv":
+            from .train_kpconv import kpconv_config
+            task, self.cfg = "segmentation_kpconv", kpconv_config(cfg)
+            cfg = self.cfg
         self.task, self.dist = task, dist
         self.rank = dist.get_rank() if parallel._active(dist) else 0
         self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -248,15 +262,26 @@ class Trainer:
         self.scheduler = make_scheduler(self.optimizer, tr["scheduler"]) if "scheduler" in tr else None
         # `dataset`: any torch Dataset whose items have the task's layout; else what `data.kind` of the config names
         data = dataset if dataset is not None else make_dataset(cfg, task, n_classes, length=dataset_length, channels=channels)
-        self.sampler = torch.utils.data.distributed.DistributedSampler(data) if parallel._active(dist) else None
-        self.loader = torch.utils.data.DataLoader(data, batch_size=cfg["data"]["batch_size"], shuffle=self.sampler is None,
-                                                  num_workers=int(cfg["data"].get("num_workers", 0)), sampler=self.sampler,
-                                                  drop_last=bool(cfg["data"].get("drop_last", True)),
-                                                  worker_init_fn=worker_init_fn)
+        self.kp, self.clip, self.val_records = None, None, []
+        if task == "segmentation_kpconv":
+            from .train_kpconv import KPConvData
+            # one iteration over the loader is one epoch of device batches (a plan of sphere picks, sharded over the ranks)
+            self.kp = self.loader = KPConvData(cfg, self.device, dist, areas=data)
+            self.sampler, self.clip = None, float(tr["clip_grad_norm"])
+        else:
+            self.sampler = torch.utils.data.distributed.DistributedSampler(data) if parallel._active(dist) else None
+            self.loader = torch.utils.data.DataLoader(data, batch_size=cfg["data"]["batch_size"], shuffle=self.sampler is None,
+                                                      num_workers=int(cfg["data"].get("num_workers", 0)), sampler=self.sampler,
+                                                      drop_last=bool(cfg["data"].get("drop_last", True)),
+                                                      worker_init_fn=worker_init_fn)
         self.ce, self.bce = nn.CrossEntropyLoss(), nn.BCEWithLogitsLoss()
         self.iters = 0
 
     def _loss(self, batch):
+        if self.task == "segmentation_kpconv":
+            from .train_kpconv import masked_cross_entropy
+            points, mask, features, labels = batch
+            return masked_cross_entropy(self.model(points, mask, features), labels, mask)
         if self.task == "segmentation":
             pts, labels = batch
             pcd = pts.permute(0, 2, 1)[:, :, None].to(self.device)                    # (B, channels, 1, N)
@@ -280,15 +305,38 @@ class Trainer:
         return (self.ce(logits, label.to(self.device).long())
                 + w * self.bce(mask_pred.reshape(mask.shape[0], -1), mask.to(self.device).float()))     # (ScanObjectNN's mask is int64)
 
-    def save(self):
+    def save(self, epoch=None):
+        """`generator_iter_{iters}.t7` / `g_opt_iter_{iters}.t7`; with `epoch`, `generator_epoch_{epoch}.t7` / `g_opt_epoch_{epoch}.t7`."""
         if self.rank == 0 and self.exp_dir is not None:
             parallel.save_exp_parallel([self.model, self.optimizer], ["generator", "g_opt"], exp_path=self.exp_dir,
-                                       epoch=self.iters, epoch_name="iter")
+                                       epoch=self.iters if epoch is None else epoch, epoch_name="iter" if epoch is None else "epoch")
+
+    def validate(self, num_votes, epoch):
+        """segmentation_kpconv: one validation of `num_votes` vote passes (train_kpconv.KPConvData.validate) on the unwrapped
+        model; the records go to the writer and, on rank 0, to <exp>/kpconv_val.jsonl.  Returns them."""
+        import json
+        records = self.kp.validate(parallel._plain_module(self.model), num_votes, epoch)
+        if self.rank == 0:
+            for rec in records:
+                step = self.iters
+                for k in ("loss", "part_miou", "running_sub_miou", "sub_miou", "full_miou"):
+                    self.writer.add_scalar("val/%s_v%d" % (k, rec["vote"]), rec[k], global_step=step)
+            if self.exp_dir is not None:
+                with open(str(Path(self.exp_dir) / "kpconv_val.jsonl"), "a") as f:
+                    for rec in records:
+                        f.write(json.dumps(rec) + "\n")
+        self.val_records += records
+        return records
+
+    def _clip(self):
+        if self.clip is not None:
+            torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.clip)
 
     # -- one training step -------------------------------------------------------------------------------------------
     def _eager_step(self, batch):
         loss = self._loss(batch)
         loss.backward()
+        self._clip()
         self.optimizer.step()
         self.optimizer.zero_grad()
         return loss.detach()
@@ -371,6 +419,7 @@ class Trainer:
         graph.replay()
         for p, g in zip((p for p in self.model.parameters() if p.requires_grad), grads):
             p.grad = g
+        self._clip()
         self.optimizer.step()
         return static_loss.detach().clone()
 
@@ -425,12 +474,24 @@ class Trainer:
                     if self.rank == 0:
                         self.writer.add_scalar("train/batch_time", (time.time() - end) / log_each, global_step=self.iters)
                     end = time.time()
-                if self.iters % tr.get("save_each", 1 << 62) == 0:
+                if self.kp is None and self.iters % tr.get("save_each", 1 << 62) == 0:
                     self.save()
                 if max_iters is not None and self.iters >= max_iters:
                     flush()
                     return history
+            if self.kp is not None:
+                # train_segmentation_kpconv.py:240-266: 2-vote validation every val_step epochs, checkpoints per epoch
+                flush()
+                e = epoch + 1
+                if self.rank == 0:
+                    self.writer.add_scalar("learning_rate", self.optimizer.param_groups[0]["lr"], global_step=e)
+                if e % int(tr["val_step"]) == 0:
+                    self.validate(int(tr["val_votes"]), e)
+                if e % int(tr["save_each_epoch"]) == 0:
+                    self.save(epoch=e)
         flush()
+        if self.kp is not None:
+            self.validate(int(tr["final_votes"]), "Last")
         return history
 
 

@@ -31,8 +31,8 @@ extern "C" {
 /* 2 (round 6): ct_plane_sort / ct_plane_sort_bytes / ct_slice_bwd_ps / ct_bn_group_reduce_bwd_copy added, ct_debug_set_pw_kernel
  * removed, since version 1 — a stale library selected by CLOUDCT_LIB fails this check instead of failing at symbol binding.
  * (The test-hook flag CT_DEBUG_NO_WIDE was added later without a bump: an additive debug bit, no symbol or signature changed.
- * The neighbour-search entry points ct_nbr_* were added under version 2 as well: additive symbols, which the loader's
- * missing-symbol scan checks.) */
+ * The neighbour-search entry points ct_nbr_* and the item assembly ct_kp_items were added under version 2 as well: additive
+ * symbols, which the loader's missing-symbol scan checks.) */
 #define CT_ABI_VERSION 2
 
 /* status codes */
@@ -654,6 +654,31 @@ int ct_nbr_radius(const int32_t* cell_start, const float* sorted, const float* o
                   const float* centres, int Q, float r, int K, int64_t* idx, float* d2, int64_t* count, ct_stream_t s);
 int ct_nbr_nearest(const int32_t* cell_start, const float* sorted, const float* origin, float h, const int* dims,
                    const float* queries, int64_t Q, int64_t* idx, float* d2, ct_stream_t s);
+
+/* ------------------------------------------------------------------------
+ * Batch assembly of the S3DIS KPConv items (datasets/s3dis_closer.py:319-361) with the optional
+ * rotation / scale / jitter of its training transforms (datasets/s3dis_closer_utils.py:38-93), one
+ * launch.  Added under CT_ABI_VERSION 2 (additive, as ct_nbr_*).
+ *
+ * B items (1 <= B <= 65535), N slots (1 <= N <= 16384, the K of ct_nbr_radius), nvalid_b =
+ * min(count_b, N).  Inputs (device): qidx i64[B,N] / count i64[B] (ct_nbr_radius of the pick
+ * points), perm i64[B,N] (the argsort of the slot keys), u_pad f32[B,N] (padding draws), offset
+ * i64[B] (the item's cloud in the concatenated sub-clouds), pick f32[B,3], drop f32[B] (0 or 1),
+ * points f32[M,3], colors f32[M,3] (0..1), labels i64[M]; color_mean / color_std: host f32[3].
+ * Optional augmentation, all three or none (CT_EINVAL otherwise): R f32[B,3,3], s f32[B,3],
+ * j f32[B,N,3].  Per slot n: pad = clamp((int64)floorf(u_pad * (float)nvalid), 0, N-1),
+ * src = n < nvalid ? perm[n] : perm[pad], ind = max(qidx[src], 0), g = offset + ind;
+ * p = points[g] - pick; with augmentation p'_i = (((R_i0*p_x + R_i1*p_y) + R_i2*p_z) * s_i) + j_i;
+ * colour = ((colors[g] - mean) / std) * drop.  Outputs: out_points p' f32[B,N,3], mask i32
+ * (n < nvalid), features f32[B,F,N] (F in {1,3,4,5,6,7}: the layout of get_scene_seg_features,
+ * height = the un-augmented points[g].z, F = 6/7 take p'), out_labels labels[g] i64, input_inds
+ * ind i64.  src and g are clamped into range as a guard; valid inputs never need it.
+ * ---------------------------------------------------------------------- */
+int ct_kp_items(const int64_t* qidx, const int64_t* count, const int64_t* perm, const float* u_pad, const int64_t* offset,
+                const float* pick, const float* drop, const float* points, const float* colors, const int64_t* labels,
+                int64_t M, const float* color_mean, const float* color_std, const float* R, const float* s, const float* j,
+                int B, int N, int F, float* out_points, int32_t* mask, float* features, int64_t* out_labels,
+                int64_t* input_inds, ct_stream_t st);
 
 #ifdef __cplusplus
 }
