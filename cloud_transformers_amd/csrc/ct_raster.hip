@@ -16,6 +16,7 @@
 #include "ct_common.h"
 #include <string.h>
 #include <type_traits>
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 
@@ -389,9 +390,6 @@ __global__ void __launch_bounds__(1024, DIM == 2 ? 8 : 4) scatter_add_fx_stream_
 //   group's LDS atomics, so a wave keeps CG KiB of HBM reads in flight instead of CG*256 B.
 //   grid = (nchunks, H, B)
 // ---------------------------------------------------------------------------
-#ifndef CT_SCATTER3_CUBES
-#define CT_SCATTER3_CUBES 1      // the 3D Splat forward instantiated for the zoo's 8^3 / 16^3 grids
-#endif
 template <int DIM, bool ADD, bool HAS_PAD, int WT = 0>
 __global__ void __launch_bounds__(DIM == 2 ? 1024 : 512, DIM == 2 ? 8 : 4) scatter_quad_kernel(RasterArgs a, GridW<DIM> g_arg) {
   GridW<DIM> g = g_arg;
@@ -1309,7 +1307,26 @@ void note(const char* tag) {
   if (n) t_last[n++] = '+';
   memcpy(t_last + n, tag, m + 1);
 }
-inline bool hot_enabled() { return (t_dbg_flags.load(std::memory_order_relaxed) & CT_DEBUG_NO_HOT) == 0; }
+
+// The run-time switches, read ONCE per entry point — where note_reset() is called, and in each workspace / segment query — and
+// passed down by value: every step of a call sees the same values, and so do a query and a launch made under the same settings.
+struct Switches {
+  unsigned flags;      // ct_debug_set_flags (CT_DEBUG_*)
+  int nseg;            // point segments of the hot Splat(max) backward: ct_debug_set_nseg, else CLOUDCT_SPLAT_BWD_NSEG (0: automatic)
+  int sorted;          // CLOUDCT_SORTED (-1: not set; 0 turns the sorted forms off)
+  bool wide;           // CLOUDCT_WIDE (0 turns the WIDE launches off)
+  bool has(unsigned f) const { return (flags & f) != 0; }
+  bool hot() const { return !has(CT_DEBUG_NO_HOT); }
+};
+Switches read_switches() {
+  static const auto env = [](const char* name, int unset) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : unset;
+  };
+  static const int sorted = env("CLOUDCT_SORTED", -1), wide = env("CLOUDCT_WIDE", 1), nseg = env("CLOUDCT_SPLAT_BWD_NSEG", 0);
+  const int dbg = t_dbg_nseg.load(std::memory_order_relaxed);
+  return {t_dbg_flags.load(std::memory_order_relaxed), dbg ? dbg : nseg, sorted, wide != 0};
+}
 
 // ---------------------------------------------------------------------------
 // host-side planning
@@ -1402,18 +1419,42 @@ int set_lds(K kernel, size_t bytes) {
   } while (0)
 
 
+// Kernel selection: run-time values that are template constants of a kernel become compile-time ones through generic lambdas.
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+// f(int_c<V>) for the V among VS... that equals v
+template <int... VS, typename F>
+int pick(int v, F&& f) {
+  int r = CT_EINVAL;
+  (void)((v == VS && ((r = f(int_c<VS>{})), true)) || ...);
+  return r;
+}
+
+// f(has a padding mask, grid extent), both as constants: the extent is the edge W of a square / cubic grid where W is one of
+// EXTENTS... — the instances a kernel family has — and 0, the form for any grid, otherwise.  PAD_GENERAL: the family's padded
+// launches take the general form whatever the grid (its kernels are not instantiated for padding and an extent).
+template <bool PAD_GENERAL, int... EXTENTS, int DIM, typename F>
+int with_pad_extent(const RasterArgs& a, const GridW<DIM>& g, F&& f) {
+  int w = g.W[0];
+  for (int j = 1; j < DIM; ++j)
+    if (g.W[j] != w) w = 0;
+  if (((w != EXTENTS) && ...)) w = 0;
+  auto with_extent = [&](auto pad) {
+    if constexpr (PAD_GENERAL && decltype(pad)::value) return f(pad, int_c<0>{});
+    else return pick<EXTENTS..., 0>(w, [&](auto wt) { return f(pad, wt); });
+  };
+  return a.pad_dtype != CT_PAD_NONE ? with_extent(std::true_type{}) : with_extent(std::false_type{});
+}
+
 // quad kernels are specialised on "has a padding mask" (compile-time: no per-element select
-// on the common no-padding path); TARGS = (DIM, MODE, CG, THREADS, STATS)
-#define CT_QUAD_T(DIMV, MODE, CG, THREADS, STATS, PAD) quad_kernel<DIMV, MODE, CG, THREADS, STATS, PAD>
-#define CT_STRIP(...) __VA_ARGS__
-#define CT_LAUNCH_QUAD(TARGS, GRID, NT, LDS, STREAM, ARGS, GW)                                        \
-  do {                                                                                                \
-    if ((ARGS).pad_dtype != CT_PAD_NONE)                                                              \
-      CT_LAUNCH((CT_QUAD_T_APPLY_(CT_STRIP TARGS, true)), GRID, NT, LDS, STREAM, ARGS, GW);           \
-    else                                                                                              \
-      CT_LAUNCH((CT_QUAD_T_APPLY_(CT_STRIP TARGS, false)), GRID, NT, LDS, STREAM, ARGS, GW);          \
-  } while (0)
-#define CT_QUAD_T_APPLY_(...) CT_QUAD_T(__VA_ARGS__)
+// on the common no-padding path)
+template <int DIM, int MODE, int CG, int THREADS, bool STATS>
+int launch_quad(dim3 grid, int threads, size_t lds, hipStream_t st, const RasterArgs& a, const GridW<DIM>& g) {
+  if (a.pad_dtype != CT_PAD_NONE) CT_LAUNCH((quad_kernel<DIM, MODE, CG, THREADS, STATS, true>), grid, threads, lds, st, a, g);
+  else CT_LAUNCH((quad_kernel<DIM, MODE, CG, THREADS, STATS, false>), grid, threads, lds, st, a, g);
+  return CT_OK;
+}
 
 // the quad scatters (4 points per thread, dwordx4) need corners from keys and 16-byte aligned rows
 bool scatter_quad_ok(const RasterArgs& a, bool from_keys, int G) {
@@ -1430,25 +1471,22 @@ int scatter_quad_threads(int dim, int N) {
 // workgroups the forward scatter's channel chunks aim for: one per CU in 2D, two in 3D (eight corners of atomics per point); with two
 // or more planes per CU (the headline: 512) a plane's channels still go to TWO workgroups — 1024 thinner workgroups balance the
 // tail better than 512 (measured: profiles/r5_nsplit_want.txt)
-#ifndef CT_SCATTER_WANT
-#define CT_SCATTER_WANT (DIM == 3 ? 512 : ((long long)a.B * a.H >= 512 ? 2ll * a.B * a.H : 256))
-#endif
 // scatter: Splat fwd (max/sum) and Slice bwd g_grid
 template <int DIM, bool FROM_KEYS>
-int run_scatter(RasterArgs a, const int* W, bool sum, hipStream_t st) {
+int run_scatter(const Switches sw, RasterArgs a, const int* W, bool sum, hipStream_t st) {
   GridW<DIM> g = make_grid<DIM>(W);
-  Plan p = make_plan(a.B, a.H, a.C, a.N, g.G, 1, CT_SCATTER_WANT);
+  Plan p = make_plan(a.B, a.H, a.C, a.N, g.G, 1, DIM == 3 ? 512 : ((long long)a.B * a.H >= 512 ? 2ll * a.B * a.H : 256));
   a.CC = p.CC;
   a.nchunks = p.nchunks;
   dim3 grid(p.nchunks, a.H, a.B);
   if (p.lds_tile) {
     if (sum) {
       if constexpr (DIM == 2 && FROM_KEYS) {
-        const int r = run_scatter_add_hot(a, g, st);
+        const int r = run_scatter_add_hot(sw, a, g, st);
         if (r != CT_EINVAL) return r;
       }
       if constexpr (DIM == 3 && FROM_KEYS) {
-        const int r = run_scatter_add_sorted3(a, g, st);      // small 3D grids, one sorted segment per plane
+        const int r = run_scatter_add_sorted3(sw, a, g, st);      // small 3D grids, one sorted segment per plane
         if (r != CT_EINVAL) return r;
       }
       constexpr int kRegCh = 8;
@@ -1469,11 +1507,15 @@ int run_scatter(RasterArgs a, const int* W, bool sum, hipStream_t st) {
     } else {
       if (scatter_quad_ok(a, FROM_KEYS, g.G)) {
         const int qt = scatter_quad_threads(DIM, a.N);
-        if (a.pad_dtype != CT_PAD_NONE) CT_LAUNCH((scatter_quad_kernel<DIM, false, true>), grid, qt, p.lds_bytes, st, a, g);
-        else if (DIM == 2 && g.W[0] == 32 && g.W[DIM - 1] == 32) CT_LAUNCH((scatter_quad_kernel<DIM, false, false, DIM == 2 ? 32 : 0>), grid, qt, p.lds_bytes, st, a, g);
-        else if (DIM == 3 && CT_SCATTER3_CUBES && g.W[0] == 8 && g.W[1] == 8 && g.W[DIM - 1] == 8) CT_LAUNCH((scatter_quad_kernel<DIM, false, false, DIM == 3 ? 8 : 0>), grid, qt, p.lds_bytes, st, a, g);
-        else if (DIM == 3 && CT_SCATTER3_CUBES && g.W[0] == 16 && g.W[1] == 16 && g.W[DIM - 1] == 16) CT_LAUNCH((scatter_quad_kernel<DIM, false, false, DIM == 3 ? 16 : 0>), grid, qt, p.lds_bytes, st, a, g);
-        else CT_LAUNCH((scatter_quad_kernel<DIM, false, false>), grid, qt, p.lds_bytes, st, a, g);
+        // instantiated for the headline's 32 x 32 grid and the zoo's 8^3 / 16^3 cubes beside the general form
+        auto launch = [&](auto pad, auto wt) {
+          CT_LAUNCH((scatter_quad_kernel<DIM, false, decltype(pad)::value, decltype(wt)::value>), grid, qt, p.lds_bytes, st, a, g);
+          return CT_OK;
+        };
+        int r;
+        if constexpr (DIM == 2) r = with_pad_extent<true, 32>(a, g, launch);
+        else r = with_pad_extent<true, 8, 16>(a, g, launch);
+        if (r != CT_OK) return r;
         note("scatter_quad_max");
       } else {
         CT_LAUNCH((scatter_kernel<DIM, FROM_KEYS, false, true>), grid, p.threads, p.lds_bytes, st, a, g);
@@ -1550,9 +1592,6 @@ int launch_sum_parts(const float* parts, float* out, size_t n, size_t stride, in
 // aligned rows, enough (b,h) planes to fill the chip with one workgroup per plane
 // ---------------------------------------------------------------------------
 constexpr int kHalfCuLdsBytes = 80 * 1024;     // two workgroups per CU
-#ifndef CT_FUSED_LDS_BUDGET
-#define CT_FUSED_LDS_BUDGET kHalfCuLdsBytes
-#endif
 
 struct HotPlan {
   int CC, nchunks;
@@ -1565,9 +1604,9 @@ struct HotPlan {
 // words of the single-tie repair and of its search
 constexpr size_t kSplatBwdFixed = 16 + 3 * 64 * 4 + 64;
 
-bool hot_chunks(int C, size_t per_ch, size_t fixed, HotPlan& hp, long long budget = kHalfCuLdsBytes) {
+bool hot_chunks(int C, size_t per_ch, size_t fixed, HotPlan& hp) {
   if ((C & 3) != 0) return false;
-  long long cc = (budget - (long long)fixed) / (long long)per_ch;
+  long long cc = ((long long)kHalfCuLdsBytes - (long long)fixed) / (long long)per_ch;
   cc &= ~3ll;
   if (cc < 4) {
     cc = ((long long)kBigLdsBytes - (long long)fixed) / (long long)per_ch;
@@ -1585,8 +1624,8 @@ bool hot_chunks(int C, size_t per_ch, size_t fixed, HotPlan& hp, long long budge
 // Backward hot kernels: chunks of a plane may be dealt to `ncg` workgroups when there are too few (b,h) planes to fill
 // the chip with one workgroup per plane (the zoo's B8 x H16 blocks: 128 planes) — thinner chunks, more workgroups;
 // each group's partial g_keys goes to the workspace.  Pure shape arithmetic: the workspace queries use it too.
-bool hot_bwd_plan(int B, int H, int C, int G, size_t per_ch, size_t fixed, long long budget, HotPlan& hp, int& ncg) {
-  if (!hot_chunks(C, per_ch, fixed, hp, budget)) return false;
+bool hot_bwd_plan(int B, int H, int C, int G, size_t per_ch, size_t fixed, HotPlan& hp, int& ncg) {
+  if (!hot_chunks(C, per_ch, fixed, hp)) return false;
   ncg = 1;
   const long long planes = (long long)B * H;
   if (planes >= 256 || C <= 4) return true;
@@ -1617,47 +1656,82 @@ bool tickets_cover(const void* tickets, long long planes, int ncg, int nseg) {
 // better below (N2048), and 10-40 us WORSE at the decoders' 0.5-1.5 MiB (B2 N16384: 39 -> 49, 67 -> 106 us).
 bool fold_pays(size_t bytes_per_fold) { return bytes_per_fold <= 192 * 1024; }
 
-bool hot_shape_ok(const RasterArgs& a, int G, uintptr_t ptr_bits) {
-  return hot_enabled() && (a.N & 3) == 0 && (G & 3) == 0 && (a.C & 3) == 0 && (ptr_bits & 15) == 0 &&
-         ((long long)a.B * a.H >= 32 || (t_dbg_flags & CT_DEBUG_FORCE_HOT));
+// Where the partial results of a backward launch go and who adds them.  A plane's channels may be dealt to `ncg` workgroups
+// (chunk groups), each with its own partial g_keys, and its points cut into `nseg` segments, each with its own partial g_grid
+// tile; the partials live in the caller's workspace as [ncg][g_keys] then [nseg][g_grid] (an area is absent where its count is
+// 1) and are added in a fixed order: by the plane's last workgroup (arrival tickets: "folded") or by sum_parts launches behind
+// the kernel, keys first.  The workspace queries and the launches size the areas from this one description.
+struct Partials {
+  long long planes;      // B * H
+  int dim, N, C, G, ncg, nseg;
+  // bytes of one g_grid fold (what a plane's last workgroup adds alone) — the families differ: nseg * ceil(C / ncg) * G * 4 in
+  // the fused forms (a group's share of the channels), nseg * per_wg * 4 * G * 4 on sorted segments (its share of the
+  // four-channel groups), none where a plane is never segmented
+  size_t grid_fold;
+  // the launch's side (apply)
+  void* ws = nullptr;
+  float* keys_out = nullptr;
+  float* grid_out = nullptr;
+  const float* keys_add = nullptr;
+  bool fold = false;
+
+  size_t gpos_n() const { return (size_t)planes * dim * N; }      // floats of g_keys, of g_grid
+  size_t grid_n() const { return (size_t)planes * C * G; }
+  size_t keys_bytes() const { return ncg > 1 ? (size_t)ncg * gpos_n() * 4 : 0; }
+  size_t grid_bytes() const { return nseg > 1 ? (size_t)nseg * grid_n() * 4 : 0; }
+  size_t bytes() const { return keys_bytes() + grid_bytes(); }
+  bool fits(const void* w, size_t w_bytes) const { return bytes() == 0 || (w != nullptr && w_bytes >= bytes()); }
+  bool folds(const void* tickets) const {
+    return (ncg > 1 || nseg > 1) && tickets_cover(tickets, planes, ncg, nseg) &&
+           fold_pays(ncg > 1 ? (size_t)ncg * dim * (N / nseg) * 4 : 0) && fold_pays(nseg > 1 ? grid_fold : 0);
+  }
+  // Points the launch at the partial areas.  `keys` and a.tile_out are the call's own outputs, `add` the incoming key cotangent
+  // (Splat(max) backward; null otherwise): several groups leave it to the final sum, one group adds it in its own store.
+  // Without a fold the tickets are withheld from the kernel.
+  void apply(RasterArgs& a, void* w, float* keys, const float* add) {
+    ws = w; keys_out = keys; grid_out = a.tile_out; keys_add = add;
+    a.ncg = ncg;
+    a.g_pos = ncg > 1 ? (float*)ws : keys;
+    a.gpos_stride = ncg > 1 ? gpos_n() : 0;
+    if (ncg > 1) a.gpos_add = nullptr;
+    if (nseg > 1) a.tile_out = (float*)((char*)ws + keys_bytes());
+    a.fold_gpos = keys; a.fold_grid = grid_out; a.fold_add = ncg > 1 ? add : nullptr;
+    fold = folds(a.tickets);
+    if (!fold) a.tickets = nullptr;
+  }
+  // the launch works on one segment: a.N points of rows a.Nrow long
+  void segment(RasterArgs& a) const { a.nseg = nseg; a.Nrow = a.N; a.N = a.N / nseg; }
+  // behind the launch: with arrival tickets the plane's last workgroup has added the partials itself
+  int finish(hipStream_t st) const {
+    if (fold) {
+      note("folded");
+      return CT_OK;
+    }
+    if (ncg > 1 && launch_sum_parts((const float*)ws, keys_out, gpos_n(), gpos_n(), ncg, keys_add, st) != CT_OK) return CT_ELAUNCH;
+    if (nseg > 1 && launch_sum_parts((const float*)((const char*)ws + keys_bytes()), grid_out, grid_n(), grid_n(), nseg, nullptr, st) != CT_OK)
+      return CT_ELAUNCH;
+    return CT_OK;
+  }
+};
+
+bool hot_shape_ok(const Switches sw, int B, int H, int C, int N, int G, uintptr_t ptr_bits) {
+  return sw.hot() && (N & 3) == 0 && (G & 3) == 0 && (C & 3) == 0 && (ptr_bits & 15) == 0 &&
+         ((long long)B * H >= 32 || sw.has(CT_DEBUG_FORCE_HOT));
+}
+bool hot_shape_ok(const Switches sw, const RasterArgs& a, int G, uintptr_t ptr_bits) {
+  return hot_shape_ok(sw, a.B, a.H, a.C, a.N, G, ptr_bits);
 }
 
-// kernels are instantiated for the 32 x 32 grid of the headline shape, the zoo's 64 x 64 and 16 x 16 (extent a template constant:
-// immediate corner offsets, half-widths, cell count) and for any grid
-#ifndef CT_HOT2_SQUARES
-#define CT_HOT2_SQUARES 1
-#endif
-#ifndef CT_SORTED_HEADLINE
-#define CT_SORTED_HEADLINE 1      // the sorted Slice backward with the headline's point and channel counts as constants too
-#endif
-#define CT_HOT_KERNEL0(KERNEL, PADV, WTV) KERNEL<PADV, WTV>
-#define CT_HOT_KERNEL1(KERNEL, PADV, WTV, QPTV) KERNEL<PADV, WTV, QPTV>
-#define CT_LAUNCH_HOT_(MK, GRID, NT, LDS, STREAM, ARGS, GW, ...)                          \
-  do {                                                                                   \
-    if ((ARGS).pad_dtype != CT_PAD_NONE)                                                  \
-      CT_LAUNCH((MK(true, 0, ##__VA_ARGS__)), GRID, NT, LDS, STREAM, ARGS, GW);           \
-    else if ((GW).W[0] == 32 && (GW).W[1] == 32)                                          \
-      CT_LAUNCH((MK(false, 32, ##__VA_ARGS__)), GRID, NT, LDS, STREAM, ARGS, GW);         \
-    else if (CT_HOT2_SQUARES && (GW).W[0] == 64 && (GW).W[1] == 64)                       \
-      CT_LAUNCH((MK(false, 64, ##__VA_ARGS__)), GRID, NT, LDS, STREAM, ARGS, GW);         \
-    else if (CT_HOT2_SQUARES && (GW).W[0] == 16 && (GW).W[1] == 16)                       \
-      CT_LAUNCH((MK(false, 16, ##__VA_ARGS__)), GRID, NT, LDS, STREAM, ARGS, GW);         \
-    else                                                                                  \
-      CT_LAUNCH((MK(false, 0, ##__VA_ARGS__)), GRID, NT, LDS, STREAM, ARGS, GW);          \
-  } while (0)
-
-// the sorted-plane kernels (ct_raster_sorted.h) also know the 16 x 16 grid of the H16 blocks at compile time
-#define CT_LAUNCH_SORTED_(MK, GRID, NT, LDS, STREAM, ARGS, GW, ...)                       \
-  do {                                                                                   \
-    if ((ARGS).pad_dtype != CT_PAD_NONE)                                                  \
-      CT_LAUNCH((MK(true, 0, ##__VA_ARGS__)), GRID, NT, LDS, STREAM, ARGS, GW);           \
-    else if ((GW).W[0] == 32 && (GW).W[1] == 32)                                          \
-      CT_LAUNCH((MK(false, 32, ##__VA_ARGS__)), GRID, NT, LDS, STREAM, ARGS, GW);         \
-    else if ((GW).W[0] == 16 && (GW).W[1] == 16)                                          \
-      CT_LAUNCH((MK(false, 16, ##__VA_ARGS__)), GRID, NT, LDS, STREAM, ARGS, GW);         \
-    else                                                                                  \
-      CT_LAUNCH((MK(false, 0, ##__VA_ARGS__)), GRID, NT, LDS, STREAM, ARGS, GW);          \
-  } while (0)
+// The extents the hot kernels are instantiated for (the extent a template constant: immediate corner offsets, half-widths, cell
+// count) beside the form for any grid.  2D: the 32 x 32 grid of the headline shape, the zoo's 64 x 64 and 16 x 16 — padding takes the
+// general form; 3D: the zoo's cubic grids 8^3 and 16^3 (profiles/r5_hot3_cubes.txt) — the WIDE launches: 16^3 only — with and
+// without padding.
+template <int DIM, bool WIDE, typename F>
+int with_hot_extent(const RasterArgs& a, const GridW<DIM>& g, F&& f) {
+  if constexpr (DIM == 2) return with_pad_extent<true, 32, 64, 16>(a, g, f);
+  else if constexpr (WIDE) return with_pad_extent<false, 16>(a, g, f);
+  else return with_pad_extent<false, 8, 16>(a, g, f);
+}
 
 int hot_threads(int nq) {
   const int t = round_threads(nq);
@@ -1670,35 +1744,67 @@ int hot_threads(int nq) {
 // thread doubles the waves: 64^2 C16 Slice backward 40.0 -> 34.6 us, Splat(max) backward 45.4 -> 34.7; 16^3 C16 54.0 -> 45.7, 58.5 ->
 // 47.9 (profiles/r6_wide.txt).  Where two workgroups fit a CU (8^3 C32) the same launch LOSES (63 -> 70 us): not taken there.
 // CLOUDCT_WIDE=0 turns it off (A/B runs); so does CT_DEBUG_NO_WIDE, within one process (tests of narrow against wide).
-bool wide_enabled() {
-  static const int env = [] {
-    const char* e = getenv("CLOUDCT_WIDE");
-    return e ? atoi(e) : 1;
-  }();
-  return env != 0 && (t_dbg_flags.load(std::memory_order_relaxed) & CT_DEBUG_NO_WIDE) == 0 && kHotThreads < kHotWideThreads;
-}
-bool hot_wide(size_t lds, int nq) { return wide_enabled() && lds > (size_t)kHalfCuLdsBytes && nq > kHotThreads; }
+bool wide_enabled(const Switches sw) { return sw.wide && !sw.has(CT_DEBUG_NO_WIDE) && kHotThreads < kHotWideThreads; }
+bool hot_wide(const Switches sw, size_t lds, int nq) { return wide_enabled(sw) && lds > (size_t)kHalfCuLdsBytes && nq > kHotThreads; }
 // does even a four-channel chunk of the fused Slice backward (conv tile + accumulators + counters) take more than half a CU's LDS?
 // (then its launches are WIDE and a point segment may hold 8192 points: two quads per thread of a 1024-thread workgroup —
 //  64^2 C16 B2 N16384: 2 segments instead of 4, 47.0 -> 37.7 us; 16^3 C16: 60.7 -> 48.1, profiles/r6_wide.txt)
-bool slice_bwd_wide_shape(int G, int C) {
-  return wide_enabled() && (size_t)(G + C + 2) * 4 + (size_t)4 * G * 8 > (size_t)kHalfCuLdsBytes;
+bool slice_bwd_wide_shape(const Switches sw, int G, int C) {
+  return wide_enabled(sw) && (size_t)(G + C + 2) * 4 + (size_t)4 * G * 8 > (size_t)kHalfCuLdsBytes;
 }
-#define CT_HOT_KERNEL1W(KERNEL, PADV, WTV, QPTV) KERNEL<PADV, WTV, QPTV, kHotWideThreads>
+
+// The form a backward hot kernel is launched in for nq quads of points per workgroup: 512-thread workgroups or WIDE ones, and the
+// quads a thread keeps in registers (1, 2; 0: the loop form, any number of quads through the workgroup's rows).  What a family has:
+enum HotForms {
+  kQuadForms,          // fused Slice backward: one or two quads per thread (a segment holds no more)
+  kQuadOrLoopForms,    // 2D Splat(max) backward: beyond two quads (WIDE: beyond one) the loop form
+  kLoopForm            // 3D Splat(max) backward (see run_splat_max_bwd_hot)
+};
+struct LaunchForm {
+  bool wide;
+  int qpt, threads;
+};
+LaunchForm launch_form(const Switches sw, size_t lds, int nq, HotForms forms) {
+  LaunchForm f;
+  f.wide = hot_wide(sw, lds, nq);
+  const int cap = f.wide ? kHotWideThreads : kHotThreads;
+  if (forms == kLoopForm) f.qpt = 0;
+  else if (nq <= cap) f.qpt = 1;
+  else if (forms == kQuadForms || (!f.wide && nq <= 2 * cap)) f.qpt = 2;
+  else f.qpt = 0;
+  const int t = round_threads(f.qpt == 2 ? (nq + 1) >> 1 : nq);
+  f.threads = t > cap ? cap : t;
+  return f;
+}
 
 // Slice forward / gather with the channel-interleaved tile.  CT_EINVAL: not eligible.
-int run_gather_hot(RasterArgs a, const GridW<2>& g, hipStream_t st) {
+template <int DIM>
+int run_gather_hot(const Switches sw, RasterArgs a, const GridW<DIM>& g, hipStream_t st) {
   const uintptr_t bits = (uintptr_t)a.pos.keys | (uintptr_t)a.dst | (uintptr_t)a.tile_in;
-  if (!hot_shape_ok(a, g.G, bits)) return CT_EINVAL;
+  if (!hot_shape_ok(sw, a, g.G, bits)) return CT_EINVAL;
   HotPlan hp;
   if (!hot_chunks(a.C, (size_t)g.G * 4, 0, hp)) return CT_EINVAL;
+  if constexpr (DIM == 3) {
+    // few planes: thinner chunks give more workgroups (the tile is staged once per chunk either way)
+    while ((long long)a.B * a.H * hp.nchunks < 256 && hp.CC > 4) {
+      hp.CC = ((hp.CC / 2) + 3) & ~3;
+      hp.nchunks = (a.C + hp.CC - 1) / hp.CC;
+      hp.lds = (size_t)hp.CC * g.G * 4;
+    }
+  }
   a.CC = hp.CC; a.nchunks = hp.nchunks; a.ncg = hp.nchunks;
-  a.nsplit = pick_nsplit(a.B, a.H, hp.nchunks, a.N, 2);
+  a.nsplit = pick_nsplit(a.B, a.H, hp.nchunks, a.N, DIM);
   const int nq = ((a.N >> 2) + a.nsplit - 1) / a.nsplit;
   dim3 grid(hp.nchunks * a.nsplit, a.H, a.B);
-#define CT_MK_GATHER(PADV, WTV) CT_HOT_KERNEL0(gather_ci_kernel, PADV, WTV)
-  CT_LAUNCH_HOT_(CT_MK_GATHER, grid, hot_threads(nq), hp.lds, st, a, g);
-  note("gather_ci");
+  const int r = with_hot_extent<DIM, false>(a, g, [&](auto pad, auto wt) {
+    constexpr bool PAD = decltype(pad)::value;
+    constexpr int WT = decltype(wt)::value;
+    if constexpr (DIM == 2) CT_LAUNCH((gather_ci_kernel<PAD, WT>), grid, hot_threads(nq), hp.lds, st, a, g);
+    else CT_LAUNCH((gather_ci3_kernel<PAD, WT>), grid, hot_threads(nq), hp.lds, st, a, g);
+    return CT_OK;
+  });
+  if (r != CT_OK) return r;
+  note(DIM == 2 ? "gather_ci" : "gather_ci3");
   return CT_OK;
 }
 
@@ -1708,8 +1814,8 @@ int run_gather_hot(RasterArgs a, const GridW<2>& g, hipStream_t st) {
 // fixed order afterwards (sum_parts_kernel) — N-split + second-stage merge, still bitwise reproducible.  The partial tiles
 // are small where this matters (grids of 16^2 .. 16^3 cells), and the 32 planes of such a batch become 128 workgroups.
 // Returns 0 when N cannot be cut into equal float4-addressable segments.
-int slice_bwd_segments(int B, int H, int C, int N, int G, int dim) {
-  const int cap = 8 * (slice_bwd_wide_shape(G, C) ? kHotWideThreads : kHotThreads);
+int slice_bwd_segments(const Switches sw, int B, int H, int C, int N, int G, int dim) {
+  const int cap = 8 * (slice_bwd_wide_shape(sw, G, C) ? kHotWideThreads : kHotThreads);
   if (N <= cap) return 1;
   int nseg = (N + cap - 1) / cap;
   while (nseg <= 64 && (N % nseg != 0 || ((N / nseg) & 3) != 0)) ++nseg;
@@ -1723,51 +1829,36 @@ int slice_bwd_segments(int B, int H, int C, int N, int G, int dim) {
   return nseg;
 }
 
-// Slice backward, fused.  CT_EINVAL: not eligible.  ws: scratch for the chunk groups' partial g_keys (may be null: then
-// only shapes that need a single group per plane qualify).
+// The fused Slice backward's chunks and chunk groups for a cloud cut into nseg segments: conv tile and accumulators of a channel
+// (8 bytes per cell) behind the plane's counters and channel maxima
+bool slice_bwd_fused_plan(int B, int H, int C, int G, int nseg, HotPlan& hp, int& ncg) {
+  return hot_bwd_plan(B * nseg, H, C, G, (size_t)G * 8, (size_t)(G + C + 2) * 4, hp, ncg);
+}
+Partials fused_partials(long long planes, int dim, int N, int C, int G, int ncg, int nseg) {
+  return {planes, dim, N, C, G, ncg, nseg, (size_t)nseg * ((C + ncg - 1) / ncg) * G * 4};
+}
+
 // channel-group workgroups per plane of the sorted kernels: enough workgroups for the CUs, at least two groups each
 int sorted_groups(long long planes, int C) {
   int ncg = 1;
   while (planes * ncg < 256 && (C >> 2) / (2 * ncg) >= 2) ncg *= 2;
   return ncg;
 }
-
-// sorted segments on small grids (ct_raster_sorted3d.h; defined with the 3D forms below)
-template <int DIM>
-size_t sorted3_workspace(int B, int H, int C, int N, const GridW<DIM>& g);
-template <int DIM>
-int run_slice_bwd_sorted3(RasterArgs a, const float* grid, float* g_pos, const GridW<DIM>& g, void* ws, size_t ws_bytes, hipStream_t st);
-
-size_t slice_bwd_hot_workspace(int B, int H, int C, int N, const GridW<2>& g) {
-  HotPlan hp;
-  int ncg = 1;
-  const int nseg = slice_bwd_segments(B, H, C, N, g.G, 2);
-  if ((C & 3) || (N & 3) || (g.G & 3) || nseg == 0) return 0;
-  size_t sorted_need = sorted3_workspace<2>(B, H, C, N, g);       // sorted segments (taken at few planes, or forced: 0 where not legal)
-  // the sorted kernel's channel-group workgroups (few planes): partial g_keys
-  if (nseg == 1 && N <= 4096 && sorted_groups((long long)B * H, C) > 1) {
-    const size_t need1 = (size_t)sorted_groups((long long)B * H, C) * B * H * 2 * N * 4;
-    sorted_need = need1 > sorted_need ? need1 : sorted_need;
-  }
-  if (!hot_bwd_plan(B * nseg, H, C, g.G, (size_t)g.G * 8, (size_t)(g.G + C + 2) * 4, CT_FUSED_LDS_BUDGET, hp, ncg)) return sorted_need;
-  const size_t fused_need = (ncg > 1 ? (size_t)ncg * B * H * 2 * N * 4 : 0) + (nseg > 1 ? (size_t)nseg * B * H * C * g.G * 4 : 0);
-  return fused_need > sorted_need ? fused_need : sorted_need;
+// ... of a sorted-plane launch: a test that forces the form gets the group split on small shapes too
+int sorted_plane_groups(const Switches sw, long long planes, int C) {
+  const int ncg = sorted_groups(planes, C);
+  return sw.has(CT_DEBUG_FORCE_SORTED) && planes * ncg < 256 ? ((C >> 2) >= 2 ? 2 : 1) : ncg;
 }
 
 // Sorted-plane kernels (ct_raster_sorted.h): one 1024-thread workgroup per (b, h) plane; every thread owns at most two items
 // (N / 4 + 3 G / 4 <= 2048), positions and counts fit 16 bits, the carve-up fits a CU's LDS.  Worth it only where there is a
 // plane per CU at least (the kernel does not split a plane) and three channel groups to spread the sort over.  CLOUDCT_SORTED=0
 // turns the form off (A/B runs).
-bool sorted_plane_ok(const RasterArgs& a, int G) {
-  static const int env = [] {
-    const char* e = getenv("CLOUDCT_SORTED");
-    return e ? atoi(e) : -1;
-  }();
-  const unsigned f = t_dbg_flags.load(std::memory_order_relaxed);
-  if ((f & CT_DEBUG_NO_SORTED) || (env == 0 && !(f & CT_DEBUG_FORCE_SORTED))) return false;
+bool sorted_plane_ok(const Switches sw, const RasterArgs& a, int G) {
+  if (sw.has(CT_DEBUG_NO_SORTED) || (sw.sorted == 0 && !sw.has(CT_DEBUG_FORCE_SORTED))) return false;
   if (a.N > 4096 || (a.N & 3) || (a.C & 3) || (G & 3) || a.N / 4 + (3 * G) / 4 > kMaxItems) return false;
   if (sort_lds(G, a.N, a.C).total > (size_t)kBigLdsBytes) return false;
-  if (f & CT_DEBUG_FORCE_SORTED) return true;
+  if (sw.has(CT_DEBUG_FORCE_SORTED)) return true;
   // the sort is paid once per plane and workgroup, the gain per four-channel group: B8 H64 N4096 32^2, sorted | scatter form
   // C4 27.8 | 23.1 us, C8 38.7 | 38.3, C12 51.3 | 57.6, C16 60.3 | 69.5, C32 99.9 | 138.9 (profiles/r5_sorted_channels.txt);
   // with fewer planes than CUs the scatter form is further from its best and two groups per workgroup already pay
@@ -1784,159 +1875,161 @@ bool plane_sort_ok(int N, int dim, int G) {
          sort_lds(G, N, 64).total <= (size_t)kBigLdsBytes;
 }
 
-int run_slice_bwd_hot(RasterArgs a, const float* grid, float* g_pos, const GridW<2>& g, void* ws, size_t ws_bytes, hipStream_t st) {
+// the sorted-plane kernels also know the 16 x 16 grid of the H16 blocks at compile time (padding: the general form)
+template <bool PRESORTED, bool GATHER>
+int launch_sorted_plane(const RasterArgs& a, const GridW<2>& g, dim3 wgrid, size_t lds, hipStream_t st) {
+  return with_pad_extent<true, 32, 16>(a, g, [&](auto pad, auto wt) {
+    CT_LAUNCH((slice_bwd_sorted_kernel<decltype(pad)::value, decltype(wt)::value, PRESORTED, GATHER>), wgrid, kSortThreads, lds, st, a, g);
+    return CT_OK;
+  });
+}
+
+// Slice backward on the plane's points sorted by base cell, items of <= 4 entries per thread (ct_raster_sorted.h), for a call
+// sorted_plane_ok() admits.  CT_EINVAL: not here (the fused form takes the call).
+int run_slice_bwd_sorted(const Switches sw, RasterArgs a, const float* grid, float* g_pos, const GridW<2>& g, void* ws, size_t ws_bytes,
+                         hipStream_t st) {
+  const long long planes = (long long)a.B * a.H;
+  Partials parts = {planes, 2, a.N, a.C, g.G, sorted_plane_groups(sw, planes, a.C), 1, 0};
+  // no scratch for the partial key cotangents: one workgroup per plane — which only fills the chip where there is a plane
+  // per CU (else the scatter form, unless a test forces the sorted one)
+  if (!parts.fits(ws, ws_bytes)) {
+    if (planes < 256 && !sw.has(CT_DEBUG_FORCE_SORTED)) return CT_EINVAL;
+    parts.ncg = 1;
+  }
+  a.tile_in = grid;
+  a.CC = 4; a.nchunks = a.C >> 2;
+  a.nseg = 1; a.Nrow = 0;      // the kernel takes whole planes: never segmented, rows of a.N points
+  parts.apply(a, ws, g_pos, nullptr);
+  const SortLds L = sort_lds(g.G, a.N, a.C);
+  dim3 wgrid(parts.ncg, a.H, a.B);
+  if (a.sorted != nullptr) {
+    a.sorted_stride = sort_record_bytes(a.N);
+    const int r = launch_sorted_plane<true, true>(a, g, wgrid, L.total, st);
+    if (r != CT_OK) return r;
+    note(parts.ncg > 1 ? "slice_bwd_presorted_groups" : "slice_bwd_presorted");
+  } else {
+    // the headline's point and channel counts as constants too (profiles/r5_hot2_squares.txt)
+    if (a.pad_dtype == CT_PAD_NONE && g.W[0] == 32 && g.W[1] == 32 && a.N == 4096 && a.C == 16 && a.ncg == 1) {
+      CT_LAUNCH((slice_bwd_sorted_kernel<false, 32, false, true, 4096, 16>), wgrid, kSortThreads, L.total, st, a, g);
+    } else {
+      const int r = launch_sorted_plane<false, true>(a, g, wgrid, L.total, st);
+      if (r != CT_OK) return r;
+    }
+    note(parts.ncg > 1 ? "slice_bwd_sorted_groups" : "slice_bwd_sorted");
+  }
+  return parts.finish(st);
+}
+
+// sorted segments on small grids (ct_raster_sorted3d.h; defined with the 3D forms below)
+template <int DIM>
+int run_slice_bwd_sorted3(const Switches sw, RasterArgs a, const float* grid, float* g_pos, const GridW<DIM>& g, void* ws, size_t ws_bytes,
+                          hipStream_t st);
+
+// Slice backward, fused.  CT_EINVAL: not eligible.  ws: scratch for the chunk groups' partial g_keys and the segments' partial
+// g_grid (may be null: then only shapes that need a single group per plane and a single segment qualify).
+template <int DIM>
+int run_slice_bwd_hot(const Switches sw, RasterArgs a, const float* grid, float* g_pos, const GridW<DIM>& g, void* ws, size_t ws_bytes,
+                      hipStream_t st) {
   const uintptr_t bits = (uintptr_t)a.pos.keys | (uintptr_t)a.src | (uintptr_t)a.tile_out | (uintptr_t)grid | (uintptr_t)g_pos |
                          (uintptr_t)ws;
-  const int nseg = slice_bwd_segments(a.B, a.H, a.C, a.N, g.G, 2);
-  if (!hot_shape_ok(a, g.G, bits) || nseg == 0) return CT_EINVAL;
+  const long long planes = (long long)a.B * a.H;
+  const int nseg = slice_bwd_segments(sw, a.B, a.H, a.C, a.N, g.G, DIM);
+  if (!hot_shape_ok(sw, a, g.G, bits) || nseg == 0) return CT_EINVAL;
   {
-    const int r = run_slice_bwd_sorted3<2>(a, grid, g_pos, g, ws, ws_bytes, st);      // small grids, few planes: sorted segments
+    const int r = run_slice_bwd_sorted3<DIM>(sw, a, grid, g_pos, g, ws, ws_bytes, st);      // small grids (2D: and few planes): sorted segments
     if (r != CT_EINVAL) return r;
   }
   // few workgroups (32 planes of 4096 points or less): one or two workgroups per plane lose to the split-N scatter +
   // gather pair (measured 67 vs 49 us on 64^2 C16, 49 vs 33 on 16^2 C16); long clouds are cut into segments (above)
-  if ((long long)a.B * a.H * nseg < 64 && !(t_dbg_flags & CT_DEBUG_FORCE_HOT)) return CT_EINVAL;
-  if (nseg == 1 && sorted_plane_ok(a, g.G)) {
-    // the plane's points sorted by base cell, items of <= 4 entries per thread (ct_raster_sorted.h)
-    int sg = (t_dbg_flags & CT_DEBUG_FORCE_SORTED) && (long long)a.B * a.H * sorted_groups((long long)a.B * a.H, a.C) < 256
-                 ? ((a.C >> 2) >= 2 ? 2 : 1)          // tests: the group split on small shapes too
-                 : sorted_groups((long long)a.B * a.H, a.C);
-    const size_t gpos_n = (size_t)a.B * a.H * 2 * a.N;
-    // no scratch for the partial key cotangents: one workgroup per plane — which only fills the chip where there is a plane
-    // per CU (else the scatter form below, unless a test forces the sorted one)
-    bool sorted_here = true;
-    if (sg > 1 && (!ws || ws_bytes < (size_t)sg * gpos_n * 4)) {
-      sg = 1;
-      sorted_here = (long long)a.B * a.H >= 256 || (t_dbg_flags & CT_DEBUG_FORCE_SORTED);
-    }
-    if (sorted_here) {
-    a.tile_in = grid;
-    a.CC = 4; a.nchunks = a.C >> 2; a.ncg = sg; a.nseg = 1; a.Nrow = 0;
-    a.g_pos = sg > 1 ? (float*)ws : g_pos;
-    a.gpos_stride = sg > 1 ? gpos_n : 0;
-    a.fold_gpos = g_pos;
-    const bool fold = sg > 1 && tickets_cover(a.tickets, (long long)a.B * a.H, sg, 1) && fold_pays((size_t)sg * 2 * a.N * 4);
-    if (!fold) a.tickets = nullptr;
-    const SortLds L = sort_lds(g.G, a.N, a.C);
-#ifdef CT_SORT_STAGGER
-    { const char* e = getenv("CLOUDCT_SORT_STAGGER"); a.cnt_mask = e ? atoi(e) : 0; }
-#endif
-    dim3 wgrid(sg, a.H, a.B);
-#define CT_MK_SLICE_BWD_SORTED(PADV, WTV, PSV) slice_bwd_sorted_kernel<PADV, WTV, PSV>
-    if (a.sorted != nullptr) {
-      a.sorted_stride = sort_record_bytes(a.N);
-      CT_LAUNCH_SORTED_(CT_MK_SLICE_BWD_SORTED, wgrid, kSortThreads, L.total, st, a, g, true);
-      note(sg > 1 ? "slice_bwd_presorted_groups" : "slice_bwd_presorted");
-    } else {
-      if (CT_SORTED_HEADLINE && a.pad_dtype == CT_PAD_NONE && g.W[0] == 32 && g.W[1] == 32 && a.N == 4096 && a.C == 16 && a.ncg == 1)
-        CT_LAUNCH((slice_bwd_sorted_kernel<false, 32, false, true, 4096, 16>), wgrid, kSortThreads, L.total, st, a, g);
-      else
-        CT_LAUNCH_SORTED_(CT_MK_SLICE_BWD_SORTED, wgrid, kSortThreads, L.total, st, a, g, false);
-      note(sg > 1 ? "slice_bwd_sorted_groups" : "slice_bwd_sorted");
-    }
-    if (fold) {
-      note("folded");
-    } else if (sg > 1) {
-      CT_CLEAR_ERROR();
-      if (launch_sum_parts((const float*)ws, g_pos, gpos_n, gpos_n, sg, nullptr, st) != CT_OK) return CT_ELAUNCH;
-      CT_CHECK_LAUNCH();
-    }
-    return CT_OK;
+  if (planes * nseg < 64 && !sw.has(CT_DEBUG_FORCE_HOT)) return CT_EINVAL;
+  if constexpr (DIM == 2) {
+    if (nseg == 1 && sorted_plane_ok(sw, a, g.G)) {
+      const int r = run_slice_bwd_sorted(sw, a, grid, g_pos, g, ws, ws_bytes, st);
+      if (r != CT_EINVAL) return r;
     }
   }
   HotPlan hp;
   int ncg = 1;
-  if (!hot_bwd_plan(a.B * nseg, a.H, a.C, g.G, (size_t)g.G * 8, (size_t)(g.G + a.C + 2) * 4, CT_FUSED_LDS_BUDGET, hp, ncg)) return CT_EINVAL;
-  const size_t gpos_n = (size_t)a.B * a.H * 2 * a.N;
-  const size_t grid_n = (size_t)a.B * a.H * a.C * g.G;
-  if (nseg > 1 && (!ws || ws_bytes < (ncg > 1 ? (size_t)ncg * gpos_n * 4 : 0) + (size_t)nseg * grid_n * 4)) return CT_EINVAL;
-  if (ncg > 1 && (!ws || ws_bytes < (size_t)ncg * gpos_n * 4)) {
-    // no scratch for the partial sums: one group per plane if there are planes enough to be worth it
-    if ((long long)a.B * a.H < 128 && !(t_dbg_flags & CT_DEBUG_FORCE_HOT)) return CT_EINVAL;
-    if (!hot_chunks(a.C, (size_t)g.G * 8, (size_t)(g.G + a.C + 2) * 4, hp, CT_FUSED_LDS_BUDGET)) return CT_EINVAL;
+  if (!slice_bwd_fused_plan(a.B, a.H, a.C, g.G, nseg, hp, ncg)) return CT_EINVAL;
+  if (!fused_partials(planes, DIM, a.N, a.C, g.G, ncg, nseg).fits(ws, ws_bytes)) {
+    // no scratch for the partial sums: one group per plane if there are planes enough to be worth it (segments cannot do without)
+    if (nseg > 1 || (planes < 128 && !sw.has(CT_DEBUG_FORCE_HOT))) return CT_EINVAL;
+    if (!hot_chunks(a.C, (size_t)g.G * 8, (size_t)(g.G + a.C + 2) * 4, hp)) return CT_EINVAL;
     ncg = 1;
   }
+  Partials parts = fused_partials(planes, DIM, a.N, a.C, g.G, ncg, nseg);
   a.tile_in = grid;
-  a.CC = hp.CC; a.nchunks = hp.nchunks; a.ncg = ncg;
-  a.g_pos = ncg > 1 ? (float*)ws : g_pos;
-  a.gpos_stride = ncg > 1 ? gpos_n : 0;
-  float* const g_grid = a.tile_out;
-  float* const grid_parts = nseg > 1 ? (float*)((char*)ws + (ncg > 1 ? (size_t)ncg * gpos_n * 4 : 0)) : nullptr;
-  if (nseg > 1) a.tile_out = grid_parts;
-  a.nseg = nseg; a.Nrow = a.N; a.N = a.N / nseg;
-  // with arrival tickets the plane's last workgroup adds the partials itself: no sum_parts launches behind the kernel
-  const bool fold = (ncg > 1 || nseg > 1) && tickets_cover(a.tickets, (long long)a.B * a.H, ncg, nseg) &&
-                    fold_pays(ncg > 1 ? (size_t)ncg * 2 * a.N * 4 : 0) &&
-                    fold_pays(nseg > 1 ? (size_t)nseg * ((a.C + ncg - 1) / ncg) * g.G * 4 : 0);
-  if (!fold) a.tickets = nullptr;
-  a.fold_gpos = g_pos; a.fold_grid = g_grid;
+  a.CC = hp.CC; a.nchunks = hp.nchunks;
+  parts.apply(a, ws, g_pos, nullptr);
+  parts.segment(a);
   dim3 wgrid(ncg, a.H, a.B * nseg);
-  const int nq = a.N >> 2;
-#define CT_MK_SLICE_BWD(PADV, WTV, QPTV) slice_bwd_fused_kernel<PADV, WTV, QPTV, true>
-#define CT_MK_SLICE_BWD_WIDE(PADV, WTV, QPTV) slice_bwd_fused_kernel<PADV, WTV, QPTV, true, kHotWideThreads>
-  if (hot_wide(hp.lds, nq) && nq <= kHotWideThreads) CT_LAUNCH_HOT_(CT_MK_SLICE_BWD_WIDE, wgrid, round_threads(nq), hp.lds, st, a, g, 1);
-  else if (hot_wide(hp.lds, nq)) CT_LAUNCH_HOT_(CT_MK_SLICE_BWD_WIDE, wgrid, round_threads((nq + 1) >> 1), hp.lds, st, a, g, 2);
-  else if (nq <= kHotThreads) CT_LAUNCH_HOT_(CT_MK_SLICE_BWD, wgrid, hot_threads(nq), hp.lds, st, a, g, 1);
-  else CT_LAUNCH_HOT_(CT_MK_SLICE_BWD, wgrid, hot_threads((nq + 1) >> 1), hp.lds, st, a, g, 2);
-  note(nseg > 1 ? "slice_bwd_fused_segments" : ncg > 1 ? "slice_bwd_fused_groups" : "slice_bwd_fused");
-  if (hot_wide(hp.lds, nq)) note("wide");
-  if (fold) {
-    note("folded");
-    return CT_OK;
-  }
-  if (ncg > 1) {
-    CT_CLEAR_ERROR();
-    if (launch_sum_parts((const float*)ws, g_pos, gpos_n, gpos_n, ncg, nullptr, st) != CT_OK) return CT_ELAUNCH;
-    CT_CHECK_LAUNCH();
-  }
-  if (nseg > 1) {
-    CT_CLEAR_ERROR();
-    if (launch_sum_parts(grid_parts, g_grid, grid_n, grid_n, nseg, nullptr, st) != CT_OK) return CT_ELAUNCH;
-    CT_CHECK_LAUNCH();
-  }
-  return CT_OK;
+  const LaunchForm lf = launch_form(sw, hp.lds, a.N >> 2, kQuadForms);
+  auto launch = [&](auto wide, auto qpt) {
+    constexpr bool WIDE = decltype(wide)::value;
+    constexpr int QPT = decltype(qpt)::value, NTB = WIDE ? kHotWideThreads : kHotThreads;
+    return with_hot_extent<DIM, WIDE>(a, g, [&](auto pad, auto wt) {
+      constexpr bool PAD = decltype(pad)::value;
+      constexpr int WT = decltype(wt)::value;
+      if constexpr (DIM == 2) CT_LAUNCH((slice_bwd_fused_kernel<PAD, WT, QPT, true, NTB>), wgrid, lf.threads, hp.lds, st, a, g);
+      else CT_LAUNCH((slice_bwd_fused3_kernel<PAD, QPT, WT, NTB>), wgrid, lf.threads, hp.lds, st, a, g);
+      return CT_OK;
+    });
+  };
+  const int r = lf.wide ? pick<1, 2>(lf.qpt, [&](auto qpt) { return launch(std::true_type{}, qpt); })
+                        : pick<1, 2>(lf.qpt, [&](auto qpt) { return launch(std::false_type{}, qpt); });
+  if (r != CT_OK) return r;
+  if constexpr (DIM == 2) note(nseg > 1 ? "slice_bwd_fused_segments" : ncg > 1 ? "slice_bwd_fused_groups" : "slice_bwd_fused");
+  else note(nseg > 1 ? "slice_bwd_fused3_segments" : ncg > 1 ? "slice_bwd_fused3_groups" : "slice_bwd_fused3");
+  if (lf.wide) note("wide");
+  return parts.finish(st);
 }
 
 // The scatter-add alone (Splat(sum) forward, ct_slice_bwd_grid) on the fused kernel without its gather side.
-int run_scatter_add_hot(RasterArgs a, const GridW<2>& g, hipStream_t st) {
+int run_scatter_add_hot(const Switches sw, RasterArgs a, const GridW<2>& g, hipStream_t st) {
   const uintptr_t bits = (uintptr_t)a.pos.keys | (uintptr_t)a.src | (uintptr_t)a.tile_out;
-  if (!hot_shape_ok(a, g.G, bits) || a.N > 8 * kHotThreads) return CT_EINVAL;
-  if (sorted_plane_ok(a, g.G)) {       // the sorted-plane kernel without its gather side (ct_raster_sorted.h)
+  if (!hot_shape_ok(sw, a, g.G, bits) || a.N > 8 * kHotThreads) return CT_EINVAL;
+  if (sorted_plane_ok(sw, a, g.G)) {       // the sorted-plane kernel without its gather side (ct_raster_sorted.h)
     const int sg = sorted_groups((long long)a.B * a.H, a.C);      // (no g_keys here: the groups share nothing)
     a.CC = 4; a.nchunks = a.C >> 2; a.ncg = sg; a.nseg = 1; a.Nrow = 0; a.tickets = nullptr; a.tile_in = nullptr; a.sorted = nullptr;
-    const SortLds L = sort_lds(g.G, a.N, a.C);
-    dim3 wgrid(sg, a.H, a.B);
-#define CT_MK_SCATTER_ADD_SORTED(PADV, WTV) slice_bwd_sorted_kernel<PADV, WTV, false, false>
-    CT_LAUNCH_SORTED_(CT_MK_SCATTER_ADD_SORTED, wgrid, kSortThreads, L.total, st, a, g);
+    const int r = launch_sorted_plane<false, false>(a, g, dim3(sg, a.H, a.B), sort_lds(g.G, a.N, a.C).total, st);
+    if (r != CT_OK) return r;
     note("scatter_add_sorted");
     return CT_OK;
   }
   HotPlan hp;
   if (!hot_chunks(a.C, (size_t)g.G * 4, (size_t)(g.G + a.C + 2) * 4, hp)) return CT_EINVAL;
   int ncg = 1;
-  hot_bwd_plan(a.B, a.H, a.C, g.G, (size_t)g.G * 4, (size_t)(g.G + a.C + 2) * 4, kHalfCuLdsBytes, hp, ncg);   // no g_keys: groups are free
+  hot_bwd_plan(a.B, a.H, a.C, g.G, (size_t)g.G * 4, (size_t)(g.G + a.C + 2) * 4, hp, ncg);   // no g_keys: groups are free
   a.CC = hp.CC; a.nchunks = hp.nchunks; a.ncg = ncg;
   a.tickets = nullptr;
   dim3 wgrid(ncg, a.H, a.B);
-  const int nq = a.N >> 2;
-#define CT_MK_SCATTER_ADD(PADV, WTV, QPTV) slice_bwd_fused_kernel<PADV, WTV, QPTV, false>
-  if (nq <= kHotThreads) CT_LAUNCH_HOT_(CT_MK_SCATTER_ADD, wgrid, hot_threads(nq), hp.lds, st, a, g, 1);
-  else CT_LAUNCH_HOT_(CT_MK_SCATTER_ADD, wgrid, hot_threads((nq + 1) >> 1), hp.lds, st, a, g, 2);
+  const int nq = a.N >> 2, qpt = nq <= kHotThreads ? 1 : 2;      // (the scatter-add alone has no WIDE instances)
+  const int r = pick<1, 2>(qpt, [&](auto q) {
+    return with_hot_extent<2, false>(a, g, [&](auto pad, auto wt) {
+      CT_LAUNCH((slice_bwd_fused_kernel<decltype(pad)::value, decltype(wt)::value, decltype(q)::value, false>), wgrid,
+                hot_threads(qpt == 2 ? (nq + 1) >> 1 : nq), hp.lds, st, a, g);
+      return CT_OK;
+    });
+  });
+  if (r != CT_OK) return r;
   note("scatter_add_fused");
   return CT_OK;
 }
 
 // Splat(sum) backward in one pass.  CT_EINVAL: not eligible.
-int run_splat_sum_bwd_hot(RasterArgs a, const GridW<2>& g, hipStream_t st) {
+int run_splat_sum_bwd_hot(const Switches sw, RasterArgs a, const GridW<2>& g, hipStream_t st) {
   const uintptr_t bits = (uintptr_t)a.pos.keys | (uintptr_t)a.src | (uintptr_t)a.dst | (uintptr_t)a.g_pos | (uintptr_t)a.tile_in;
-  if (!hot_shape_ok(a, g.G, bits)) return CT_EINVAL;
+  if (!hot_shape_ok(sw, a, g.G, bits)) return CT_EINVAL;
   const size_t lds = (size_t)a.C * g.G * 4;
   if (lds > (size_t)kBigLdsBytes) return CT_EINVAL;
   a.nsplit = pick_nsplit(a.B, a.H, 1, a.N);
   const int nq = ((a.N >> 2) + a.nsplit - 1) / a.nsplit;
   dim3 grid(a.nsplit, a.H, a.B);
-#define CT_MK_SPLAT_SUM_BWD(PADV, WTV) CT_HOT_KERNEL0(splat_sum_bwd_kernel, PADV, WTV)
-  CT_LAUNCH_HOT_(CT_MK_SPLAT_SUM_BWD, grid, hot_threads(nq), lds, st, a, g);
+  const int r = with_hot_extent<2, false>(a, g, [&](auto pad, auto wt) {
+    CT_LAUNCH((splat_sum_bwd_kernel<decltype(pad)::value, decltype(wt)::value>), grid, hot_threads(nq), lds, st, a, g);
+    return CT_OK;
+  });
+  if (r != CT_OK) return r;
   note("splat_sum_bwd_hot");
   return CT_OK;
 }
@@ -1947,16 +2040,10 @@ int run_splat_sum_bwd_hot(RasterArgs a, const GridW<2>& g, hipStream_t st) {
 // cloud outgrows a workgroup's registers (2D: N > 4096), as long as re-staging the plane's tiles per segment stays within
 // ~4x the segment's own point traffic (nseg * G <= 4 N: fine for 8^3 .. 64^2 / 16^3 at the zoo's sizes, not for 128^2).
 // CLOUDCT_SPLAT_BWD_NSEG / ct_debug_set_nseg = 1: off, n > 1: that many where legal (A/B runs, tests of the 3D form).
-int splat_bwd_segments(int B, int H, int C, int N, int G, int dim, size_t lds_per_wg) {
-  static const int env_forced = [] {
-    const char* e = getenv("CLOUDCT_SPLAT_BWD_NSEG");
-    return e ? atoi(e) : 0;
-  }();
-  const int dbg = t_dbg_nseg.load(std::memory_order_relaxed);
-  const int forced = dbg ? dbg : env_forced;
-  if (forced == 1) return 1;
+int splat_bwd_segments(const Switches sw, int B, int H, int C, int N, int G, int dim) {
+  if (sw.nseg == 1) return 1;
   auto legal = [&](int ns) { return ns >= 1 && ns <= 64 && N % (4 * ns) == 0 && N / ns >= 256 && (long long)ns * G <= 4ll * N; };
-  if (forced > 1) return legal(forced) ? forced : 1;
+  if (sw.nseg > 1) return legal(sw.nseg) ? sw.nseg : 1;
   // Measured (tools/zoo_sweep.py, B8 N4096 / B2 N16384, H16): 16^2 C16 29.2 -> 23.5 / 39.1 -> 24.0 us; but 8^3 C32 56.6 -> 72.6,
   // 16^3 C16 59 -> 75, 64^2 C16 47 -> 58: a segment's threads walk ALL channels, so there are nchunks-times fewer waves in
   // flight than with chunk groups, and every segment re-stages every chunk.  Automatic only where the plane's tiles are one
@@ -1964,156 +2051,100 @@ int splat_bwd_segments(int B, int H, int C, int N, int G, int dim, size_t lds_pe
   if ((size_t)C * G * 8 > 32 * 1024 || N < 4096) return 1;
   // ~256 workgroups: B8 N4096 nseg 2 / 4 / 8 = 20.3 / 22.1 / 27.1 us, B2 N16384 nseg 4 / 8 / 16 = 31.3 / 20.1 / 23.1 (tools/dev/nseg_sweep.py)
   const long long planes = (long long)B * H;
-  const long long target = 256;
-  (void)lds_per_wg;
   int nseg = 1;
-  while (planes * nseg < target && legal(2 * nseg) && N / (2 * nseg) >= 1024) nseg *= 2;
+  while (planes * nseg < 256 && legal(2 * nseg) && N / (2 * nseg) >= 1024) nseg *= 2;
   while (dim == 2 && N / nseg > 8 * kHotThreads && legal(2 * nseg)) nseg *= 2;      // the register form: <= 4096 points
   return nseg;
 }
 
-// can the hot Splat(max) backward take this call?  ncg: chunk groups (partial g_keys through the workspace); nseg: point
-// segments (preferred where legal: nothing to add up); single: one group whose threads own their quads
+// The two plans of the hot Splat(max) backward, shape arithmetic shared by the launch, the workspace query and
+// ct_splat_bwd_tk_segments.  Point segments: every workgroup stages every chunk, so the chunks are as fat as LDS allows (no chunk
+// groups); returns the segments (1: none), 0 where no chunk fits LDS.  Chunk groups: partial g_keys through the workspace.
+int splat_bwd_segments_plan(const Switches sw, int B, int H, int C, int N, int G, int dim, HotPlan& hp) {
+  return hot_chunks(C, (size_t)G * 8, kSplatBwdFixed, hp) ? splat_bwd_segments(sw, B, H, C, N, G, dim) : 0;
+}
+bool splat_bwd_groups_plan(int B, int H, int C, int G, HotPlan& hp, int& ncg) {
+  return hot_bwd_plan(B, H, C, G, (size_t)G * 8, kSplatBwdFixed, hp, ncg);
+}
+
+// can the hot Splat(max) backward take this call?  ncg: chunk groups; nseg: point segments (preferred where legal: nothing to
+// add up)
 template <int DIM>
-bool splat_bwd_hot_plan(const RasterArgs& a, const GridW<DIM>& g, HotPlan& hp, int& ncg, int& nseg, bool& single) {
+bool splat_bwd_hot_plan(const Switches sw, const RasterArgs& a, const GridW<DIM>& g, HotPlan& hp, int& ncg, int& nseg) {
   const uintptr_t bits = (uintptr_t)a.pos.keys | (uintptr_t)a.src | (uintptr_t)a.dst | (uintptr_t)a.g_pos |
                          (uintptr_t)a.tile_in | (uintptr_t)a.tile_in2 | (uintptr_t)a.gpos_add;
   nseg = 1;
-  if (!hot_shape_ok(a, g.G, bits)) return false;
-  // segments first: every workgroup stages every chunk, so the chunks are as fat as LDS allows (no chunk groups)
+  if (!hot_shape_ok(sw, a, g.G, bits)) return false;
   if (a.tickets != nullptr && tickets_cover(a.tickets, (long long)a.B * a.H, 1, 1) && (long long)a.B * a.H <= kTicketHalf / 2 &&
       ((uintptr_t)a.tickets & 7) == 0 && (a.gpos_add == nullptr || a.gpos_add != a.g_pos)) {
     HotPlan sp;
-    if (hot_chunks(a.C, (size_t)g.G * 8, kSplatBwdFixed, sp)) {
-      const int ns = splat_bwd_segments(a.B, a.H, a.C, a.N, g.G, DIM, sp.lds);
-      if (ns > 1) {
-        hp = sp; ncg = 1; nseg = ns; single = true;
-        return true;
-      }
+    const int ns = splat_bwd_segments_plan(sw, a.B, a.H, a.C, a.N, g.G, DIM, sp);
+    if (ns > 1) {
+      hp = sp; ncg = 1; nseg = ns;
+      return true;
     }
   }
-  if (!hot_bwd_plan(a.B, a.H, a.C, g.G, (size_t)g.G * 8, kSplatBwdFixed, kHalfCuLdsBytes, hp, ncg)) return false;
-  if constexpr (DIM == 2) {
-    single = (a.N >> 2) <= 2 * kHotThreads;
-  } else {
+  if (!splat_bwd_groups_plan(a.B, a.H, a.C, g.G, hp, ncg)) return false;
+  if constexpr (DIM == 3) {
     // a workgroup walks all N points of its plane: with fewer workgroups than CUs (16^3 at B2 H16: 128) the generic
     // kernel's thinner single-channel chunks win (72 vs 147 us)
-    if ((long long)a.B * a.H * ncg < 256 && !(t_dbg_flags & CT_DEBUG_FORCE_HOT)) return false;
-    single = true;       // (the loop form: every thread owns its quads' rows)
+    if ((long long)a.B * a.H * ncg < 256 && !sw.has(CT_DEBUG_FORCE_HOT)) return false;
   }
   return true;
 }
 
-size_t splat_bwd_hot_workspace(int B, int H, int C, int N, const GridW<2>& g) {
+// the chunk groups' partial g_keys (whichever family a call ends up on, the scratch is enough)
+template <int DIM>
+size_t splat_bwd_hot_workspace(int B, int H, int C, int N, const GridW<DIM>& g) {
   HotPlan hp;
   int ncg = 1;
-  if ((C & 3) || (N & 3) || (g.G & 3)) return 0;
-  if (!hot_bwd_plan(B, H, C, g.G, (size_t)g.G * 8, kSplatBwdFixed, kHalfCuLdsBytes, hp, ncg)) return 0;
-  return ncg > 1 ? (size_t)ncg * B * H * 2 * N * 4 : 0;
+  if ((C & 3) || (N & 3) || (g.G & 3) || !splat_bwd_groups_plan(B, H, C, g.G, hp, ncg)) return 0;
+  return Partials{(long long)B * H, DIM, N, C, g.G, ncg, 1, 0}.bytes();
 }
 
-int run_splat_max_bwd_hot(RasterArgs a, const GridW<2>& g, const HotPlan& hp, int ncg, int nseg, void* ws, hipStream_t st) {
-  a.CC = hp.CC; a.nchunks = hp.nchunks; a.ncg = ncg;
-  float* const out = a.g_pos;
-  const float* const add = a.gpos_add;
-  const size_t gpos_n = (size_t)a.B * a.H * 2 * a.N;
-#define CT_MK_SPLAT_BWD(PADV, WTV, QPTV) CT_HOT_KERNEL1(splat_max_bwd_hot_kernel, PADV, WTV, QPTV)
-#define CT_MK_SPLAT_BWD_WIDE(PADV, WTV, QPTV) CT_HOT_KERNEL1W(splat_max_bwd_hot_kernel, PADV, WTV, QPTV)
-  if (nseg > 1) {       // point segments: ncg == 1, tickets present (splat_bwd_hot_plan)
-    a.nseg = nseg; a.Nrow = a.N; a.N = a.N / nseg;
-    dim3 wgrid(1, a.H, a.B * nseg);
-    const int nq = a.N >> 2;
-    if (hot_wide(hp.lds, nq) && nq <= kHotWideThreads) CT_LAUNCH_HOT_(CT_MK_SPLAT_BWD_WIDE, wgrid, round_threads(nq), hp.lds, st, a, g, 1);
-    else if (hot_wide(hp.lds, nq)) CT_LAUNCH_HOT_(CT_MK_SPLAT_BWD_WIDE, wgrid, kHotWideThreads, hp.lds, st, a, g, 0);
-    else if (nq <= kHotThreads) CT_LAUNCH_HOT_(CT_MK_SPLAT_BWD, wgrid, hot_threads(nq), hp.lds, st, a, g, 1);
-    else if (nq <= 2 * kHotThreads) CT_LAUNCH_HOT_(CT_MK_SPLAT_BWD, wgrid, hot_threads((nq + 1) >> 1), hp.lds, st, a, g, 2);
-    else CT_LAUNCH_HOT_(CT_MK_SPLAT_BWD, wgrid, kHotThreads, hp.lds, st, a, g, 0);
-    note("splat_max_bwd_hot_segments");
+// Several groups: the partial sums go through the workspace and the final sum adds the incoming cotangent; one group (or point
+// segments: ncg == 1, tickets present, no fold) adds it in its own store — every thread owns its rows.
+// The 3D kernel runs in its loop form only (a quad's g_keys share is added to the workgroup's rows per chunk): with the 12 values
+// of a quad kept in registers across chunks — and the corner setup of all four points hoisted out of the channel loop by the
+// compiler — it spilled 170-450 registers and lost to the generic kernel (118 vs 72 us on 16^3 C16 B8 N4096); now 53 us.
+template <int DIM>
+int run_splat_max_bwd_hot(const Switches sw, RasterArgs a, const GridW<DIM>& g, const HotPlan& hp, int ncg, int nseg, void* ws, hipStream_t st) {
+  a.CC = hp.CC; a.nchunks = hp.nchunks;
+  Partials parts = {(long long)a.B * a.H, DIM, a.N, a.C, g.G, ncg, nseg, 0};
+  if (nseg > 1) {      // (ncg == 1: no partial g_keys, and the segments' tickets serve the plane's tie test, not a fold)
+    a.ncg = ncg;
+    parts.segment(a);
+  } else {
+    parts.apply(a, ws, a.g_pos, a.gpos_add);
+  }
+  dim3 wgrid(ncg, a.H, a.B * nseg);
+  const LaunchForm lf = launch_form(sw, hp.lds, a.N >> 2, DIM == 2 ? kQuadOrLoopForms : kLoopForm);
+  auto launch = [&](auto wide, auto qpt) {
+    constexpr bool WIDE = decltype(wide)::value;
+    constexpr int QPT = decltype(qpt)::value, NTB = WIDE ? kHotWideThreads : kHotThreads;
+    return with_hot_extent<DIM, WIDE>(a, g, [&](auto pad, auto wt) {
+      constexpr bool PAD = decltype(pad)::value;
+      constexpr int WT = decltype(wt)::value;
+      if constexpr (DIM == 2) CT_LAUNCH((splat_max_bwd_hot_kernel<PAD, WT, QPT, NTB>), wgrid, lf.threads, hp.lds, st, a, g);
+      else CT_LAUNCH((splat_max_bwd_hot3_kernel<PAD, QPT, WT, NTB>), wgrid, lf.threads, hp.lds, st, a, g);
+      return CT_OK;
+    });
+  };
+  int r;
+  if constexpr (DIM == 2)
+    r = lf.wide ? pick<1, 0>(lf.qpt, [&](auto qpt) { return launch(std::true_type{}, qpt); })
+                : pick<1, 2, 0>(lf.qpt, [&](auto qpt) { return launch(std::false_type{}, qpt); });
+  else
+    r = lf.wide ? launch(std::true_type{}, int_c<0>{}) : launch(std::false_type{}, int_c<0>{});
+  if (r != CT_OK) return r;
+  if (nseg > 1) {
+    note(DIM == 2 ? "splat_max_bwd_hot_segments" : "splat_max_bwd_hot3_segments");
     return CT_OK;
   }
-  const bool fold = ncg > 1 && tickets_cover(a.tickets, (long long)a.B * a.H, ncg, 1) && fold_pays((size_t)ncg * 2 * a.N * 4);
-  if (!fold) a.tickets = nullptr;
-  if (ncg > 1) {
-    a.g_pos = (float*)ws;
-    a.gpos_stride = gpos_n;
-    a.gpos_add = nullptr;
-    a.fold_gpos = out; a.fold_add = add;
-  }
-  dim3 wgrid(ncg, a.H, a.B);
-  const int nq = a.N >> 2;
-  if (hot_wide(hp.lds, nq) && nq <= kHotWideThreads) CT_LAUNCH_HOT_(CT_MK_SPLAT_BWD_WIDE, wgrid, round_threads(nq), hp.lds, st, a, g, 1);
-  else if (hot_wide(hp.lds, nq)) CT_LAUNCH_HOT_(CT_MK_SPLAT_BWD_WIDE, wgrid, kHotWideThreads, hp.lds, st, a, g, 0);
-  else if (nq <= kHotThreads) CT_LAUNCH_HOT_(CT_MK_SPLAT_BWD, wgrid, hot_threads(nq), hp.lds, st, a, g, 1);
-  else if (nq <= 2 * kHotThreads) CT_LAUNCH_HOT_(CT_MK_SPLAT_BWD, wgrid, hot_threads((nq + 1) >> 1), hp.lds, st, a, g, 2);
-  else CT_LAUNCH_HOT_(CT_MK_SPLAT_BWD, wgrid, kHotThreads, hp.lds, st, a, g, 0);
-  note(ncg > 1 ? "splat_max_bwd_hot_groups" : "splat_max_bwd_hot");
-  if (hot_wide(hp.lds, nq)) note("wide");
-  if (fold) {
-    note("folded");
-    return CT_OK;
-  }
-  if (ncg > 1) {
-    CT_CLEAR_ERROR();
-    if (launch_sum_parts((const float*)ws, out, gpos_n, gpos_n, ncg, add, st) != CT_OK) return CT_ELAUNCH;
-    CT_CHECK_LAUNCH();
-  }
-  return CT_OK;
-}
-
-
-// ---- 3D forms (ct_raster_hot3d.h) ----
-#define CT_LAUNCH_HOT3_(KPAD, KNOPAD, GRID, NT, LDS, STREAM, ARGS, GW)                    \
-  do {                                                                                   \
-    if ((ARGS).pad_dtype != CT_PAD_NONE) CT_LAUNCH((KPAD), GRID, NT, LDS, STREAM, ARGS, GW); \
-    else CT_LAUNCH((KNOPAD), GRID, NT, LDS, STREAM, ARGS, GW);                             \
-  } while (0)
-// the same for kernels instantiated for the zoo's cubic grids (8^3, 16^3: the extent a template constant) beside the general form
-#ifndef CT_HOT3_CUBES
-#define CT_HOT3_CUBES 1
-#endif
-inline int cube_of(const GridW<3>& g) {
-  if (!CT_HOT3_CUBES || g.W[0] != g.W[1] || g.W[1] != g.W[2]) return 0;
-  return g.W[0] == 8 ? 8 : g.W[0] == 16 ? 16 : 0;
-}
-#define CT_LAUNCH_HOT3W_(KERNEL, QPTV, GRID, NT, LDS, STREAM, ARGS, GW)                                              \
-  do {                                                                                                               \
-    const int cube_ = cube_of(GW);                                                                                   \
-    if (cube_ == 8) CT_LAUNCH_HOT3_((KERNEL<true, QPTV, 8>), (KERNEL<false, QPTV, 8>), GRID, NT, LDS, STREAM, ARGS, GW);       \
-    else if (cube_ == 16) CT_LAUNCH_HOT3_((KERNEL<true, QPTV, 16>), (KERNEL<false, QPTV, 16>), GRID, NT, LDS, STREAM, ARGS, GW); \
-    else CT_LAUNCH_HOT3_((KERNEL<true, QPTV, 0>), (KERNEL<false, QPTV, 0>), GRID, NT, LDS, STREAM, ARGS, GW);                    \
-  } while (0)
-// the WIDE launches (hot_wide): 1024-thread workgroups, for the 16^3 cube and any grid
-#define CT_LAUNCH_HOT3WIDE_(KERNEL, QPTV, GRID, NT, LDS, STREAM, ARGS, GW)                                           \
-  do {                                                                                                               \
-    if (cube_of(GW) == 16)                                                                                           \
-      CT_LAUNCH_HOT3_((KERNEL<true, QPTV, 16, kHotWideThreads>), (KERNEL<false, QPTV, 16, kHotWideThreads>), GRID, NT, LDS, STREAM, ARGS, GW); \
-    else                                                                                                             \
-      CT_LAUNCH_HOT3_((KERNEL<true, QPTV, 0, kHotWideThreads>), (KERNEL<false, QPTV, 0, kHotWideThreads>), GRID, NT, LDS, STREAM, ARGS, GW);   \
-  } while (0)
-
-int run_gather_hot(RasterArgs a, const GridW<3>& g, hipStream_t st) {
-  const uintptr_t bits = (uintptr_t)a.pos.keys | (uintptr_t)a.dst | (uintptr_t)a.tile_in;
-  if (!hot_shape_ok(a, g.G, bits)) return CT_EINVAL;
-  HotPlan hp;
-  if (!hot_chunks(a.C, (size_t)g.G * 4, 0, hp)) return CT_EINVAL;
-  // few planes: thinner chunks give more workgroups (the tile is staged once per chunk either way)
-  while ((long long)a.B * a.H * hp.nchunks < 256 && hp.CC > 4) {
-    hp.CC = ((hp.CC / 2) + 3) & ~3;
-    hp.nchunks = (a.C + hp.CC - 1) / hp.CC;
-    hp.lds = (size_t)hp.CC * g.G * 4;
-  }
-  a.CC = hp.CC; a.nchunks = hp.nchunks; a.ncg = hp.nchunks;
-  a.nsplit = pick_nsplit(a.B, a.H, hp.nchunks, a.N, 3);
-  const int nq = ((a.N >> 2) + a.nsplit - 1) / a.nsplit;
-  dim3 grid(hp.nchunks * a.nsplit, a.H, a.B);
-  {
-    const int cube = cube_of(g);
-    if (cube == 8) CT_LAUNCH_HOT3_((gather_ci3_kernel<true, 8>), (gather_ci3_kernel<false, 8>), grid, hot_threads(nq), hp.lds, st, a, g);
-    else if (cube == 16) CT_LAUNCH_HOT3_((gather_ci3_kernel<true, 16>), (gather_ci3_kernel<false, 16>), grid, hot_threads(nq), hp.lds, st, a, g);
-    else CT_LAUNCH_HOT3_((gather_ci3_kernel<true, 0>), (gather_ci3_kernel<false, 0>), grid, hot_threads(nq), hp.lds, st, a, g);
-  }
-  note("gather_ci3");
-  return CT_OK;
+  if constexpr (DIM == 2) note(ncg > 1 ? "splat_max_bwd_hot_groups" : "splat_max_bwd_hot");
+  else note(ncg > 1 ? "splat_max_bwd_hot3_groups" : "splat_max_bwd_hot3");
+  if (lf.wide) note("wide");
+  return parts.finish(st);
 }
 
 // Sorted-segment kernels for small 3D grids (ct_raster_sorted3d.h): 512-thread workgroups of at most 2048 points (nseg point
@@ -2123,16 +2154,15 @@ int run_gather_hot(RasterArgs a, const GridW<3>& g, hipStream_t st) {
 struct Sorted3Plan {
   int nseg, ncg, n;
   size_t lds;
+  Partials partials(long long planes, int dim, int N, int C, int G) const {
+    const int per_wg = ((C >> 2) + ncg - 1) / ncg;
+    return {planes, dim, N, C, G, ncg, nseg, (size_t)nseg * per_wg * 4 * G * 4};
+  }
 };
-bool sorted3_plan(int B, int H, int C, int N, int G, int dim, bool gather, Sorted3Plan& p) {
-  static const int env = [] {
-    const char* e = getenv("CLOUDCT_SORTED");
-    return e ? atoi(e) : -1;
-  }();
-  const unsigned f = t_dbg_flags.load(std::memory_order_relaxed);
-  const bool forced = (f & (dim == 3 ? CT_DEBUG_FORCE_SORTED : CT_DEBUG_FORCE_SORTED_SEG)) != 0;
-  if ((f & CT_DEBUG_NO_SORTED) || (env == 0 && !forced)) return false;
-  if (dim == 2 && !forced && (f & CT_DEBUG_FORCE_SORTED)) return false;      // (tests of the one-workgroup-per-plane 2D kernel)
+bool sorted3_plan(const Switches sw, int B, int H, int C, int N, int G, int dim, bool gather, Sorted3Plan& p) {
+  const bool forced = sw.has(dim == 3 ? CT_DEBUG_FORCE_SORTED : CT_DEBUG_FORCE_SORTED_SEG);
+  if (sw.has(CT_DEBUG_NO_SORTED) || (sw.sorted == 0 && !forced)) return false;
+  if (dim == 2 && !forced && sw.has(CT_DEBUG_FORCE_SORTED)) return false;      // (tests of the one-workgroup-per-plane 2D kernel)
   if ((N & 3) || (C & 3) || (G & 3) || G > 1024) return false;
   int nseg = (N + kS3MaxPoints - 1) / kS3MaxPoints;
   while (nseg <= 64 && (N % nseg != 0 || ((N / nseg) & 3) != 0)) ++nseg;
@@ -2148,240 +2178,88 @@ bool sorted3_plan(int B, int H, int C, int N, int G, int dim, bool gather, Sorte
   // g_keys: its groups share nothing, one group per workgroup is fine)
   while (planes * nseg * ncg < 512 && ngroups / (2 * ncg) >= (gather ? 2 : 1)) ncg *= 2;
   if (forced && ncg == 1 && ngroups >= 2 && planes * nseg < 256) ncg = 2;      // tests: the group split on small shapes too
-  {
-    static const int env_ncg = [] {      // experiments: CLOUDCT_S3_NCG = channel-group workgroups per segment
-      const char* e = getenv("CLOUDCT_S3_NCG");
-      return e ? atoi(e) : 0;
-    }();
-    if (env_ncg > 0 && env_ncg <= ngroups) ncg = env_ncg;
-  }
   p.nseg = nseg; p.ncg = ncg; p.n = n; p.lds = lds;
   if (forced) return true;
   // the sort is paid per workgroup, the gain per group: worth it where the chip fills and there are groups to spread it over
   return planes * nseg * ncg >= 256 && ngroups / ncg >= (gather ? 2 : 1);
 }
 
-template <int DIM>
-size_t sorted3_workspace(int B, int H, int C, int N, const GridW<DIM>& g) {
-  Sorted3Plan p;
-  if (!sorted3_plan(B, H, C, N, g.G, DIM, true, p)) return 0;
-  return (p.ncg > 1 ? (size_t)p.ncg * B * H * DIM * N * 4 : 0) + (p.nseg > 1 ? (size_t)p.nseg * B * H * C * g.G * 4 : 0);
+// the 8^3 cube known at compile time; the same kernel on small 2D grids (DIM = 2: one face): the zoo's 16 x 16 (padding: the
+// general form)
+template <int DIM, bool GATHER>
+int launch_sorted_seg(const RasterArgs& a, const GridW<DIM>& g, dim3 wgrid, size_t lds, hipStream_t st) {
+  auto f = [&](auto pad, auto wt) {
+    CT_LAUNCH((slice_bwd_sorted_seg_kernel<decltype(pad)::value, DIM, decltype(wt)::value, GATHER>), wgrid, kS3Threads, lds, st, a, g);
+    return CT_OK;
+  };
+  if constexpr (DIM == 3) return with_pad_extent<true, 8>(a, g, f);
+  else return with_pad_extent<true, 16>(a, g, f);
 }
-
-size_t slice_bwd_hot_workspace(int B, int H, int C, int N, const GridW<3>& g) {
-  HotPlan hp;
-  int ncg = 1;
-  const size_t sorted_need = sorted3_workspace(B, H, C, N, g);
-  const int nseg = slice_bwd_segments(B, H, C, N, g.G, 3);
-  if ((C & 3) || (N & 3) || (g.G & 3) || nseg == 0) return sorted_need;
-  if (!hot_bwd_plan(B * nseg, H, C, g.G, (size_t)g.G * 8, (size_t)(g.G + C + 2) * 4, CT_FUSED_LDS_BUDGET, hp, ncg)) return sorted_need;
-  const size_t fused_need = (ncg > 1 ? (size_t)ncg * B * H * 3 * N * 4 : 0) + (nseg > 1 ? (size_t)nseg * B * H * C * g.G * 4 : 0);
-  return fused_need > sorted_need ? fused_need : sorted_need;
-}
-
-#define CT_LAUNCH_SORTED3_(GATHERV, GRID, LDS, STREAM, ARGS, GW)                                                            \
-  do {                                                                                                                     \
-    if ((ARGS).pad_dtype != CT_PAD_NONE) CT_LAUNCH((slice_bwd_sorted_seg_kernel<true, 3, 0, GATHERV>), GRID, kS3Threads, LDS, STREAM, ARGS, GW); \
-    else if (cube_of(GW) == 8) CT_LAUNCH((slice_bwd_sorted_seg_kernel<false, 3, 8, GATHERV>), GRID, kS3Threads, LDS, STREAM, ARGS, GW);         \
-    else CT_LAUNCH((slice_bwd_sorted_seg_kernel<false, 3, 0, GATHERV>), GRID, kS3Threads, LDS, STREAM, ARGS, GW);           \
-  } while (0)
-// the same kernel on small 2D grids (DIM = 2: one face); the zoo's 16 x 16 known at compile time
-#define CT_LAUNCH_SORTED2S_(GATHERV, GRID, LDS, STREAM, ARGS, GW)                                                           \
-  do {                                                                                                                     \
-    if ((ARGS).pad_dtype != CT_PAD_NONE) CT_LAUNCH((slice_bwd_sorted_seg_kernel<true, 2, 0, GATHERV>), GRID, kS3Threads, LDS, STREAM, ARGS, GW); \
-    else if ((GW).W[0] == 16 && (GW).W[1] == 16) CT_LAUNCH((slice_bwd_sorted_seg_kernel<false, 2, 16, GATHERV>), GRID, kS3Threads, LDS, STREAM, ARGS, GW); \
-    else CT_LAUNCH((slice_bwd_sorted_seg_kernel<false, 2, 0, GATHERV>), GRID, kS3Threads, LDS, STREAM, ARGS, GW);           \
-  } while (0)
 
 // The scatter-add alone (Splat(sum) forward, ct_slice_bwd_grid) on ONE sorted segment per plane (there is no workspace for partial
 // tiles behind these entry points): the sorted kernel without its gather side; the channel groups share nothing.  Measured against
 // scatter_add_fx_reg (8^3 C32 B8 N2048, reduce=sum, tools/dev/zoo_shape.py): see profiles/r6_zoo_shape_checks.txt.
-int run_scatter_add_sorted3(RasterArgs a, const GridW<3>& g, hipStream_t st) {
+int run_scatter_add_sorted3(const Switches sw, RasterArgs a, const GridW<3>& g, hipStream_t st) {
   const uintptr_t bits = (uintptr_t)a.pos.keys | (uintptr_t)a.src | (uintptr_t)a.tile_out;
   Sorted3Plan p;
-  if (!hot_shape_ok(a, g.G, bits) || !sorted3_plan(a.B, a.H, a.C, a.N, g.G, 3, false, p) || p.nseg != 1) return CT_EINVAL;
+  if (!hot_shape_ok(sw, a, g.G, bits) || !sorted3_plan(sw, a.B, a.H, a.C, a.N, g.G, 3, false, p) || p.nseg != 1) return CT_EINVAL;
   a.CC = 4; a.nchunks = a.C >> 2; a.ncg = p.ncg; a.nseg = 1; a.Nrow = a.N; a.tickets = nullptr; a.tile_in = nullptr;
   a.g_pos = nullptr; a.gpos_stride = 0; a.sorted = nullptr;
-  dim3 wgrid(p.ncg, a.H, a.B);
-  CT_LAUNCH_SORTED3_(false, wgrid, p.lds, st, a, g);
+  const int r = launch_sorted_seg<3, false>(a, g, dim3(p.ncg, a.H, a.B), p.lds, st);
+  if (r != CT_OK) return r;
   note("scatter_add_sorted3");
   return CT_OK;
 }
 
-// Slice backward on sorted segments.  CT_EINVAL: not eligible (the scatter form below takes the call).
+// Slice backward on sorted segments.  CT_EINVAL: not eligible (the scatter form takes the call).
 template <int DIM>
-int run_slice_bwd_sorted3(RasterArgs a, const float* grid, float* g_pos, const GridW<DIM>& g, void* ws, size_t ws_bytes, hipStream_t st) {
+int run_slice_bwd_sorted3(const Switches sw, RasterArgs a, const float* grid, float* g_pos, const GridW<DIM>& g, void* ws, size_t ws_bytes,
+                          hipStream_t st) {
+  const long long planes = (long long)a.B * a.H;
   Sorted3Plan p;
-  if (!sorted3_plan(a.B, a.H, a.C, a.N, g.G, DIM, true, p)) return CT_EINVAL;
+  if (!sorted3_plan(sw, a.B, a.H, a.C, a.N, g.G, DIM, true, p)) return CT_EINVAL;
   if constexpr (DIM == 2) {
     // 2D: only where the one-workgroup-per-plane sorted kernel (ct_raster_sorted.h) would leave the chip part empty or split a
     // plane's channel groups over workgroups that each sort the whole plane — few planes (the H16 blocks' 16 x 16 head): two
-    // 512-thread workgroups per CU on 2048-point segments instead (profiles/r6_zoo_shape_checks.txt).  CLOUDCT_SORTED2S=0: off.
-    static const int env2 = [] {
-      const char* e = getenv("CLOUDCT_SORTED2S");
-      return e ? atoi(e) : 1;
-    }();
-    if (!(t_dbg_flags & CT_DEBUG_FORCE_SORTED_SEG) && (env2 == 0 || (long long)a.B * a.H >= 256)) return CT_EINVAL;
+    // 512-thread workgroups per CU on 2048-point segments instead (profiles/r6_zoo_shape_checks.txt).  The workspace query does
+    // not apply this: it covers the family wherever it is legal.
+    if (!sw.has(CT_DEBUG_FORCE_SORTED_SEG) && planes >= 256) return CT_EINVAL;
   }
-  const size_t gpos_n = (size_t)a.B * a.H * DIM * a.N;
-  const size_t grid_n = (size_t)a.B * a.H * a.C * g.G;
-  const size_t keys_need = p.ncg > 1 ? (size_t)p.ncg * gpos_n * 4 : 0, need = keys_need + (p.nseg > 1 ? (size_t)p.nseg * grid_n * 4 : 0);
-  if (need > 0 && (!ws || ws_bytes < need)) return CT_EINVAL;
+  Partials parts = p.partials(planes, DIM, a.N, a.C, g.G);
+  if (!parts.fits(ws, ws_bytes)) return CT_EINVAL;
   a.tile_in = grid;
-  a.CC = 4; a.nchunks = a.C >> 2; a.ncg = p.ncg;
-  a.g_pos = p.ncg > 1 ? (float*)ws : g_pos;
-  a.gpos_stride = p.ncg > 1 ? gpos_n : 0;
-  float* const g_grid = a.tile_out;
-  float* const grid_parts = p.nseg > 1 ? (float*)((char*)ws + keys_need) : nullptr;
-  if (p.nseg > 1) a.tile_out = grid_parts;
-  a.nseg = p.nseg; a.Nrow = a.N; a.N = p.n;
-  const int per_wg = ((a.C >> 2) + p.ncg - 1) / p.ncg;
-  const bool fold = (p.ncg > 1 || p.nseg > 1) && tickets_cover(a.tickets, (long long)a.B * a.H, p.ncg, p.nseg) &&
-                    fold_pays(p.ncg > 1 ? (size_t)p.ncg * DIM * a.N * 4 : 0) &&
-                    fold_pays(p.nseg > 1 ? (size_t)p.nseg * per_wg * 4 * g.G * 4 : 0);
-  if (!fold) a.tickets = nullptr;
-  a.fold_gpos = g_pos; a.fold_grid = g_grid;
-  dim3 wgrid(p.ncg, a.H, a.B * p.nseg);
-  if constexpr (DIM == 3) {
-    CT_LAUNCH_SORTED3_(true, wgrid, p.lds, st, a, g);
-    note(p.nseg > 1 ? "slice_bwd_sorted3_segments" : p.ncg > 1 ? "slice_bwd_sorted3_groups" : "slice_bwd_sorted3");
-  } else {
-    CT_LAUNCH_SORTED2S_(true, wgrid, p.lds, st, a, g);
-    note(p.nseg > 1 ? "slice_bwd_sorted2s_segments" : p.ncg > 1 ? "slice_bwd_sorted2s_groups" : "slice_bwd_sorted2s");
-  }
-  if (fold) {
-    note("folded");
-    return CT_OK;
-  }
-  if (p.ncg > 1) {
-    CT_CLEAR_ERROR();
-    if (launch_sum_parts((const float*)ws, g_pos, gpos_n, gpos_n, p.ncg, nullptr, st) != CT_OK) return CT_ELAUNCH;
-    CT_CHECK_LAUNCH();
-  }
-  if (p.nseg > 1) {
-    CT_CLEAR_ERROR();
-    if (launch_sum_parts(grid_parts, g_grid, grid_n, grid_n, p.nseg, nullptr, st) != CT_OK) return CT_ELAUNCH;
-    CT_CHECK_LAUNCH();
-  }
-  return CT_OK;
+  a.CC = 4; a.nchunks = a.C >> 2;
+  parts.apply(a, ws, g_pos, nullptr);
+  parts.segment(a);
+  const int r = launch_sorted_seg<DIM, true>(a, g, dim3(p.ncg, a.H, a.B * p.nseg), p.lds, st);
+  if (r != CT_OK) return r;
+  if constexpr (DIM == 3) note(p.nseg > 1 ? "slice_bwd_sorted3_segments" : p.ncg > 1 ? "slice_bwd_sorted3_groups" : "slice_bwd_sorted3");
+  else note(p.nseg > 1 ? "slice_bwd_sorted2s_segments" : p.ncg > 1 ? "slice_bwd_sorted2s_groups" : "slice_bwd_sorted2s");
+  return parts.finish(st);
 }
 
-int run_slice_bwd_hot(RasterArgs a, const float* grid, float* g_pos, const GridW<3>& g, void* ws, size_t ws_bytes, hipStream_t st) {
-  const uintptr_t bits = (uintptr_t)a.pos.keys | (uintptr_t)a.src | (uintptr_t)a.tile_out | (uintptr_t)grid | (uintptr_t)g_pos |
-                         (uintptr_t)ws;
-  const int nseg = slice_bwd_segments(a.B, a.H, a.C, a.N, g.G, 3);
-  if (!hot_shape_ok(a, g.G, bits) || nseg == 0) return CT_EINVAL;
-  {
-    const int r = run_slice_bwd_sorted3(a, grid, g_pos, g, ws, ws_bytes, st);      // small grids: sorted segments
-    if (r != CT_EINVAL) return r;
+// Scratch of the hot Slice backward: the maximum over the families a call may end up on — sorted segments, the sorted-plane
+// kernel's channel groups (2D), the fused form — each sized by the plan its launch makes (whether the launch then takes the
+// family depends on more: planes, pointers, the scratch itself).
+template <int DIM>
+size_t slice_bwd_hot_workspace(const Switches sw, int B, int H, int C, int N, const GridW<DIM>& g) {
+  const long long planes = (long long)B * H;
+  const int nseg = slice_bwd_segments(sw, B, H, C, N, g.G, DIM);
+  if ((C & 3) || (N & 3) || (g.G & 3) || nseg == 0) return 0;
+  size_t need = 0;
+  Sorted3Plan sp;
+  if (sorted3_plan(sw, B, H, C, N, g.G, DIM, true, sp)) need = sp.partials(planes, DIM, N, C, g.G).bytes();
+  if constexpr (DIM == 2) {
+    if (nseg == 1 && N <= 4096) {
+      // (the unforced group count too: the debug flags are process-wide and may change between the query and the call)
+      const int sg = std::max(sorted_groups(planes, C), sorted_plane_groups(sw, planes, C));
+      need = std::max(need, Partials{planes, 2, N, C, g.G, sg, 1, 0}.bytes());
+    }
   }
-  // few workgroups (32 planes of 4096 points or less): one or two workgroups per plane lose to the split-N scatter +
-  // gather pair (measured 67 vs 49 us on 64^2 C16, 49 vs 33 on 16^2 C16); long clouds are cut into segments (above)
-  if ((long long)a.B * a.H * nseg < 64 && !(t_dbg_flags & CT_DEBUG_FORCE_HOT)) return CT_EINVAL;
   HotPlan hp;
   int ncg = 1;
-  if (!hot_bwd_plan(a.B * nseg, a.H, a.C, g.G, (size_t)g.G * 8, (size_t)(g.G + a.C + 2) * 4, CT_FUSED_LDS_BUDGET, hp, ncg)) return CT_EINVAL;
-  const size_t gpos_n = (size_t)a.B * a.H * 3 * a.N;
-  const size_t grid_n = (size_t)a.B * a.H * a.C * g.G;
-  if (nseg > 1 && (!ws || ws_bytes < (ncg > 1 ? (size_t)ncg * gpos_n * 4 : 0) + (size_t)nseg * grid_n * 4)) return CT_EINVAL;
-  if (ncg > 1 && (!ws || ws_bytes < (size_t)ncg * gpos_n * 4)) {
-    if ((long long)a.B * a.H < 128 && !(t_dbg_flags & CT_DEBUG_FORCE_HOT)) return CT_EINVAL;
-    if (!hot_chunks(a.C, (size_t)g.G * 8, (size_t)(g.G + a.C + 2) * 4, hp, CT_FUSED_LDS_BUDGET)) return CT_EINVAL;
-    ncg = 1;
-  }
-  a.tile_in = grid;
-  a.CC = hp.CC; a.nchunks = hp.nchunks; a.ncg = ncg;
-  a.g_pos = ncg > 1 ? (float*)ws : g_pos;
-  a.gpos_stride = ncg > 1 ? gpos_n : 0;
-  float* const g_grid = a.tile_out;
-  float* const grid_parts = nseg > 1 ? (float*)((char*)ws + (ncg > 1 ? (size_t)ncg * gpos_n * 4 : 0)) : nullptr;
-  if (nseg > 1) a.tile_out = grid_parts;
-  a.nseg = nseg; a.Nrow = a.N; a.N = a.N / nseg;
-  const bool fold = (ncg > 1 || nseg > 1) && tickets_cover(a.tickets, (long long)a.B * a.H, ncg, nseg) &&     // see the 2D form
-                    fold_pays(ncg > 1 ? (size_t)ncg * 3 * a.N * 4 : 0) &&
-                    fold_pays(nseg > 1 ? (size_t)nseg * ((a.C + ncg - 1) / ncg) * g.G * 4 : 0);
-  if (!fold) a.tickets = nullptr;
-  a.fold_gpos = g_pos; a.fold_grid = g_grid;
-  dim3 wgrid(ncg, a.H, a.B * nseg);
-  const int nq = a.N >> 2;
-  if (hot_wide(hp.lds, nq) && nq <= kHotWideThreads)
-    CT_LAUNCH_HOT3WIDE_(slice_bwd_fused3_kernel, 1, wgrid, round_threads(nq), hp.lds, st, a, g);
-  else if (hot_wide(hp.lds, nq))
-    CT_LAUNCH_HOT3WIDE_(slice_bwd_fused3_kernel, 2, wgrid, round_threads((nq + 1) >> 1), hp.lds, st, a, g);
-  else if (nq <= kHotThreads)
-    CT_LAUNCH_HOT3W_(slice_bwd_fused3_kernel, 1, wgrid, hot_threads(nq), hp.lds, st, a, g);
-  else
-    CT_LAUNCH_HOT3W_(slice_bwd_fused3_kernel, 2, wgrid, hot_threads((nq + 1) >> 1), hp.lds, st, a, g);
-  note(nseg > 1 ? "slice_bwd_fused3_segments" : ncg > 1 ? "slice_bwd_fused3_groups" : "slice_bwd_fused3");
-  if (hot_wide(hp.lds, nq)) note("wide");
-  if (fold) {
-    note("folded");
-    return CT_OK;
-  }
-  if (ncg > 1) {
-    CT_CLEAR_ERROR();
-    if (launch_sum_parts((const float*)ws, g_pos, gpos_n, gpos_n, ncg, nullptr, st) != CT_OK) return CT_ELAUNCH;
-    CT_CHECK_LAUNCH();
-  }
-  if (nseg > 1) {
-    CT_CLEAR_ERROR();
-    if (launch_sum_parts(grid_parts, g_grid, grid_n, grid_n, nseg, nullptr, st) != CT_OK) return CT_ELAUNCH;
-    CT_CHECK_LAUNCH();
-  }
-  return CT_OK;
-}
-
-// The 3D hot Splat(max) backward runs in its loop form only (a quad's g_keys share is added to the workgroup's rows per
-// chunk): with the 12 values of a quad kept in registers across chunks — and the corner setup of all four points hoisted
-// out of the channel loop by the compiler — it spilled 170-450 registers and lost to the generic kernel (118 vs 72 us on
-// 16^3 C16 B8 N4096); now 53 us.
-size_t splat_bwd_hot_workspace(int B, int H, int C, int N, const GridW<3>& g) {
-  HotPlan hp;
-  int ncg = 1;
-  if ((C & 3) || (N & 3) || (g.G & 3)) return 0;
-  if (!hot_bwd_plan(B, H, C, g.G, (size_t)g.G * 8, kSplatBwdFixed, kHalfCuLdsBytes, hp, ncg)) return 0;
-  return ncg > 1 ? (size_t)ncg * B * H * 3 * N * 4 : 0;
-}
-
-int run_splat_max_bwd_hot(RasterArgs a, const GridW<3>& g, const HotPlan& hp, int ncg, int nseg, void* ws, hipStream_t st) {
-  a.CC = hp.CC; a.nchunks = hp.nchunks; a.ncg = ncg;
-  float* const out = a.g_pos;
-  const float* const add = a.gpos_add;
-  const size_t gpos_n = (size_t)a.B * a.H * 3 * a.N;
-  if (nseg > 1) {       // point segments (see the 2D form)
-    a.nseg = nseg; a.Nrow = a.N; a.N = a.N / nseg;
-    dim3 wgrid(1, a.H, a.B * nseg);
-    if (hot_wide(hp.lds, a.N >> 2)) CT_LAUNCH_HOT3WIDE_(splat_max_bwd_hot3_kernel, 0, wgrid, round_threads(a.N >> 2), hp.lds, st, a, g);
-    else CT_LAUNCH_HOT3W_(splat_max_bwd_hot3_kernel, 0, wgrid, hot_threads(a.N >> 2), hp.lds, st, a, g);
-    note("splat_max_bwd_hot3_segments");
-    return CT_OK;
-  }
-  const bool fold = ncg > 1 && tickets_cover(a.tickets, (long long)a.B * a.H, ncg, 1) && fold_pays((size_t)ncg * 3 * a.N * 4);
-  if (!fold) a.tickets = nullptr;
-  if (ncg > 1) {
-    a.g_pos = (float*)ws;
-    a.gpos_stride = gpos_n;
-    a.gpos_add = nullptr;
-    a.fold_gpos = out; a.fold_add = add;
-  }
-  dim3 wgrid(ncg, a.H, a.B);
-  const int nq = a.N >> 2;
-  // always the loop form (g_keys partials stored per chunk): keeping a quad's 12 g_keys values in registers across the
-  // chunks makes the 3D kernel spill
-  if (hot_wide(hp.lds, nq)) CT_LAUNCH_HOT3WIDE_(splat_max_bwd_hot3_kernel, 0, wgrid, round_threads(nq), hp.lds, st, a, g);
-  else CT_LAUNCH_HOT3W_(splat_max_bwd_hot3_kernel, 0, wgrid, hot_threads(nq), hp.lds, st, a, g);
-  note(ncg > 1 ? "splat_max_bwd_hot3_groups" : "splat_max_bwd_hot3");
-  if (hot_wide(hp.lds, nq)) note("wide");
-  if (fold) {
-    note("folded");
-    return CT_OK;
-  }
-  if (ncg > 1) {
-    CT_CLEAR_ERROR();
-    if (launch_sum_parts((const float*)ws, out, gpos_n, gpos_n, ncg, add, st) != CT_OK) return CT_ELAUNCH;
-    CT_CHECK_LAUNCH();
-  }
-  return CT_OK;
+  if (slice_bwd_fused_plan(B, H, C, g.G, nseg, hp, ncg)) need = std::max(need, fused_partials(planes, DIM, N, C, g.G, ncg, nseg).bytes());
+  return need;
 }
 
 // ---- banded kernels (ct_raster_band.h): four-channel heads on grids too large for the hot kernels ----
@@ -2392,10 +2270,10 @@ int run_splat_max_bwd_hot(RasterArgs a, const GridW<3>& g, const HotPlan& hp, in
 // kernels re-read only the keys (C x).  So the bands serve what nothing else serves well: grids whose single-channel tile
 // exceeds a CU's LDS (> 40K cells: 256^2, 64^3 ...), which otherwise run on global atomics, nondeterministically.
 template <int DIM>
-bool band_plan(const RasterArgs& a, const GridW<DIM>& g, uintptr_t ptr_bits, int& R, int& nb, size_t& lds) {
+bool band_plan(const Switches sw, const RasterArgs& a, const GridW<DIM>& g, uintptr_t ptr_bits, int& R, int& nb, size_t& lds) {
   const int S = g.G / g.W[0];
-  if (!hot_enabled() || a.C != 4 || (a.N & 3) != 0 || (S & 3) != 0 || (ptr_bits & 15) != 0 || g.W[0] < 4) return false;
-  if ((size_t)g.G * 4 <= (size_t)kBigLdsBytes && !(t_dbg_flags & CT_DEBUG_FORCE_BAND)) return false;
+  if (!sw.hot() || a.C != 4 || (a.N & 3) != 0 || (S & 3) != 0 || (ptr_bits & 15) != 0 || g.W[0] < 4) return false;
+  if ((size_t)g.G * 4 <= (size_t)kBigLdsBytes && !sw.has(CT_DEBUG_FORCE_BAND)) return false;
   const size_t fixed = (size_t)(kBandCnt + 8) * 4 + band_ring_bytes<DIM>();
   auto bytes = [&](int r) { return (size_t)(r + 2) * S * 32 + fixed; };
   int r = (int)(((size_t)kHalfCuLdsBytes - fixed) / ((size_t)S * 32)) - 2;
@@ -2413,11 +2291,11 @@ bool band_plan(const RasterArgs& a, const GridW<DIM>& g, uintptr_t ptr_bits, int
 }
 
 template <int DIM>
-int run_band_slice_bwd(RasterArgs a, const float* grid, float* g_pos, const GridW<DIM>& g, hipStream_t st) {
+int run_band_slice_bwd(const Switches sw, RasterArgs a, const float* grid, float* g_pos, const GridW<DIM>& g, hipStream_t st) {
   const uintptr_t bits = (uintptr_t)a.pos.keys | (uintptr_t)a.src | (uintptr_t)a.tile_out | (uintptr_t)grid | (uintptr_t)g_pos;
   int R, nb;
   size_t lds;
-  if (!band_plan<DIM>(a, g, bits, R, nb, lds)) return CT_EINVAL;
+  if (!band_plan<DIM>(sw, a, g, bits, R, nb, lds)) return CT_EINVAL;
   a.tile_in = grid; a.g_pos = g_pos;
   a.nsplit = R; a.ncg = nb; a.tickets = nullptr;
   dim3 wgrid(nb, a.H, a.B);
@@ -2429,12 +2307,12 @@ int run_band_slice_bwd(RasterArgs a, const float* grid, float* g_pos, const Grid
 
 // (needs an incoming key cotangent that is not the output: a band with exact ties is redone from it)
 template <int DIM>
-int run_band_splat_bwd(RasterArgs a, const GridW<DIM>& g, hipStream_t st) {
+int run_band_splat_bwd(const Switches sw, RasterArgs a, const GridW<DIM>& g, hipStream_t st) {
   const uintptr_t bits = (uintptr_t)a.pos.keys | (uintptr_t)a.src | (uintptr_t)a.dst | (uintptr_t)a.g_pos | (uintptr_t)a.tile_in |
                          (uintptr_t)a.tile_in2 | (uintptr_t)a.gpos_add;
   int R, nb;
   size_t lds;
-  if ((a.gpos_add != nullptr && a.gpos_add == a.g_pos) || !band_plan<DIM>(a, g, bits, R, nb, lds)) return CT_EINVAL;
+  if ((a.gpos_add != nullptr && a.gpos_add == a.g_pos) || !band_plan<DIM>(sw, a, g, bits, R, nb, lds)) return CT_EINVAL;
   a.nsplit = R; a.ncg = nb; a.tickets = nullptr;
   dim3 wgrid(nb, a.H, a.B);
   if (a.pad_dtype != CT_PAD_NONE) CT_LAUNCH((band_splat_bwd_kernel<DIM, true>), wgrid, kBandThreads, lds, st, a, g);
@@ -2450,7 +2328,7 @@ __global__ void __launch_bounds__(256) add_inplace_kernel(float* y, const float*
 }
 
 template <int DIM, bool FROM_KEYS>
-int run_gather(RasterArgs a, const int* W, hipStream_t st) {
+int run_gather(const Switches sw, RasterArgs a, const int* W, hipStream_t st) {
   GridW<DIM> g = make_grid<DIM>(W);
   Plan p = make_plan(a.B, a.H, a.C, a.N, g.G, 1);
   a.CC = p.CC;
@@ -2459,15 +2337,14 @@ int run_gather(RasterArgs a, const int* W, hipStream_t st) {
   int threads = round_threads((a.N + a.nsplit - 1) / a.nsplit);
   dim3 grid(p.nchunks * a.nsplit, a.H, a.B);
   if constexpr (FROM_KEYS) {
-    const int r = run_gather_hot(a, g, st);
+    const int r = run_gather_hot<DIM>(sw, a, g, st);
     if (r != CT_EINVAL) return r;
   }
   if constexpr (DIM == 2) {   // 3D exceeds the register budget of the quad form: generic kernel
     if (quad_ok(a, FROM_KEYS, p.lds_tile) && (g.G & 3) == 0) {
       note("gather_quad");
       a.ncg = p.nchunks;   // one chunk per workgroup
-      CT_LAUNCH_QUAD((2, QM_GATHER, CT_QUAD_CG, CT_QUAD_THREADS, false), grid, quad_threads(a.N, a.nsplit), p.lds_bytes, st, a, g);
-      return CT_OK;
+      return launch_quad<2, QM_GATHER, CT_QUAD_CG, CT_QUAD_THREADS, false>(grid, quad_threads(a.N, a.nsplit), p.lds_bytes, st, a, g);
     }
   }
   if (p.lds_tile) CT_LAUNCH((gather_kernel<DIM, FROM_KEYS, true>), grid, threads, p.lds_bytes, st, a, g);
@@ -2495,9 +2372,8 @@ int run_gather_gw(RasterArgs a, const int* W, hipStream_t st) {
   int threads = round_threads((a.N + a.nsplit - 1) / a.nsplit);
   dim3 grid(a.ncg * a.nsplit, a.H, a.B);
   if (quad_ok(a, FROM_KEYS, p.lds_tile) && (g.G & 3) == 0) {
-    CT_LAUNCH_QUAD((DIM, QM_GATHER_GW, (DIM == 2 ? CT_QUAD_CG : 2), CT_QUAD_THREADS, false), grid, quad_threads(a.N, a.nsplit), p.lds_bytes, st, a, g);
     note("gather_gw_quad");
-    return CT_OK;
+    return launch_quad<DIM, QM_GATHER_GW, (DIM == 2 ? CT_QUAD_CG : 2), CT_QUAD_THREADS, false>(grid, quad_threads(a.N, a.nsplit), p.lds_bytes, st, a, g);
   }
   if (p.lds_tile) CT_LAUNCH((gather_gw_kernel<DIM, FROM_KEYS, true>), grid, threads, p.lds_bytes, st, a, g);
   else CT_LAUNCH((gather_gw_kernel<DIM, FROM_KEYS, false>), grid, threads, 0, st, a, g);
@@ -2528,7 +2404,6 @@ int launch_splat_max_bwd(RasterArgs a, const GridW<DIM>& g, const Plan& p, bool 
     return CT_OK;
   }
   if constexpr (DIM == 2) {
-#ifndef CT_NO_WHOLE_HEAD
     // whole-head form: z and g_z tiles of ALL channels of a (b,h) plane resident (<= 160 KiB,
     // one 1024-thread workgroup per CU): one staging pass, keys read once, g_keys written once
     const size_t wh_bytes = (size_t)2 * a.C * g.G * 4;
@@ -2539,16 +2414,13 @@ int launch_splat_max_bwd(RasterArgs a, const GridW<DIM>& g, const Plan& p, bool 
       a.accumulate = accumulate;
       int t = round_threads(a.N >> 2);
       dim3 wgrid(1, a.H, a.B);
-      if (t > 512) CT_LAUNCH_QUAD((2, QM_SPLAT_MAX_BWD, CT_QUAD_CG, 1024, false), wgrid, 1024, wh_bytes, st, a, g);
-      else CT_LAUNCH_QUAD((2, QM_SPLAT_MAX_BWD, CT_QUAD_CG, 512, false), wgrid, t, wh_bytes, st, a, g);
       note("splat_max_bwd_whole_head");
-      return CT_OK;
+      return t > 512 ? launch_quad<2, QM_SPLAT_MAX_BWD, CT_QUAD_CG, 1024, false>(wgrid, 1024, wh_bytes, st, a, g)
+                     : launch_quad<2, QM_SPLAT_MAX_BWD, CT_QUAD_CG, 512, false>(wgrid, t, wh_bytes, st, a, g);
     }
-#endif
     if (two && quad_ok(a, FROM_KEYS, true) && (g.G & 3) == 0) {
-      CT_LAUNCH_QUAD((2, QM_SPLAT_MAX_BWD, CT_QUAD_CG, CT_QUAD_THREADS, false), grid, quad_threads(a.N, 1), p.lds_bytes, st, a, g);
       note("splat_max_bwd_quad");
-      return CT_OK;
+      return launch_quad<2, QM_SPLAT_MAX_BWD, CT_QUAD_CG, CT_QUAD_THREADS, false>(grid, quad_threads(a.N, 1), p.lds_bytes, st, a, g);
     }
   }
   if (two) CT_LAUNCH((splat_max_bwd_kernel<DIM, FROM_KEYS, true, true>), grid, p.threads, p.lds_bytes, st, a, g);
@@ -2558,32 +2430,28 @@ int launch_splat_max_bwd(RasterArgs a, const GridW<DIM>& g, const Plan& p, bool 
 }
 
 template <int DIM, bool FROM_KEYS>
-int run_splat_max_bwd(RasterArgs a, const int* W, void* ws, size_t ws_bytes, hipStream_t st) {
+int run_splat_max_bwd(const Switches sw, RasterArgs a, const int* W, void* ws, size_t ws_bytes, hipStream_t st) {
   GridW<DIM> g = make_grid<DIM>(W);
   if constexpr (FROM_KEYS) {
-    if (t_dbg_flags & CT_DEBUG_FORCE_BAND) {
-      const int r = run_band_splat_bwd<DIM>(a, g, st);
+    if (sw.has(CT_DEBUG_FORCE_BAND)) {
+      const int r = run_band_splat_bwd<DIM>(sw, a, g, st);
       if (r != CT_EINVAL) return r;
     }
     HotPlan hp;
-    bool single = false;
     int ncg = 1, nseg = 1;
-    if (splat_bwd_hot_plan<DIM>(a, g, hp, ncg, nseg, single)) {
+    if (splat_bwd_hot_plan<DIM>(sw, a, g, hp, ncg, nseg)) {
       // In-place accumulation (gpos_add == g_pos) by ONE group whose g_keys sums go through memory (2D beyond the register
       // form, every 3D call): the optimistic pass leaves incoming + its result in g_pos chunk by chunk, and a plane with exact
       // ties would start its single-winner redo from THAT (incoming + optimistic + claims).  Not eligible: the
       // caller computes the plain cotangent into its scratch (this very kernel, not accumulating) and adds it.
       const bool reg_form = DIM == 2 && (a.N >> 2) <= 2 * kHotThreads;
       if (a.gpos_add != nullptr && a.gpos_add == a.g_pos && ncg == 1 && nseg == 1 && !reg_form) return CT_EINVAL;
-      const size_t need = ncg > 1 ? (size_t)ncg * a.B * a.H * DIM * a.N * 4 : 0;
-      // several groups: the partial sums go through the workspace and the final sum adds the incoming cotangent; one
-      // group (or point segments): the kernel adds it in its own store — every thread owns its rows
-      if (need <= ws_bytes && (ws || !need) && ((uintptr_t)ws & 15) == 0)
-        return run_splat_max_bwd_hot(a, g, hp, ncg, nseg, ws, st);
+      if (Partials{(long long)a.B * a.H, DIM, a.N, a.C, g.G, ncg, 1, 0}.fits(ws, ws_bytes) && ((uintptr_t)ws & 15) == 0)
+        return run_splat_max_bwd_hot<DIM>(sw, a, g, hp, ncg, nseg, ws, st);
     }
     a.tickets = nullptr;
-    if (!(t_dbg_flags & CT_DEBUG_NO_BAND)) {
-      const int r = run_band_splat_bwd<DIM>(a, g, st);
+    if (!sw.has(CT_DEBUG_NO_BAND)) {
+      const int r = run_band_splat_bwd<DIM>(sw, a, g, st);
       if (r != CT_EINVAL) return r;
     }
   }
@@ -2610,11 +2478,7 @@ int run_splat_max_bwd(RasterArgs a, const int* W, void* ws, size_t ws_bytes, hip
   const int ncg = a.ncg;
   const int r = launch_splat_max_bwd<DIM, FROM_KEYS>(a, g, p, two, g_pos_out, parts, ws, ws_bytes, accumulate, st);
   if (r != CT_OK) return r;
-  if (parts) {
-    CT_CLEAR_ERROR();
-    if (launch_sum_parts((const float*)ws, g_pos_out, gpos_n, gpos_n, ncg, accumulate ? g_pos_out : nullptr, st) != CT_OK) return CT_ELAUNCH;
-    CT_CHECK_LAUNCH();
-  }
+  if (parts) return launch_sum_parts((const float*)ws, g_pos_out, gpos_n, gpos_n, ncg, accumulate ? g_pos_out : nullptr, st);
   return CT_OK;
 }
 
@@ -2628,19 +2492,19 @@ int slice_bwd_stats_nsplit(int B, int H, int N) {
 
 // Slice backward, hot path: returns CT_EINVAL when the shape is not eligible.
 template <int DIM>
-int run_slice_bwd_fast(RasterArgs a, const float* grid, float* g_pos, const int* W, void* ws, size_t ws_bytes, hipStream_t st) {
+int run_slice_bwd_fast(const Switches sw, RasterArgs a, const float* grid, float* g_pos, const int* W, void* ws, size_t ws_bytes, hipStream_t st) {
   GridW<DIM> g = make_grid<DIM>(W);
   if ((g.G & 3) != 0) return CT_EINVAL;
-  if (t_dbg_flags & CT_DEBUG_FORCE_BAND) {       // tests: the banded kernel on grids the hot kernels would take
-    const int r = run_band_slice_bwd<DIM>(a, grid, g_pos, g, st);
+  if (sw.has(CT_DEBUG_FORCE_BAND)) {       // tests: the banded kernel on grids the hot kernels would take
+    const int r = run_band_slice_bwd<DIM>(sw, a, grid, g_pos, g, st);
     if (r != CT_EINVAL) return r;
   }
   {
-    const int r = run_slice_bwd_hot(a, grid, g_pos, g, ws, ws_bytes, st);
+    const int r = run_slice_bwd_hot<DIM>(sw, a, grid, g_pos, g, ws, ws_bytes, st);
     if (r != CT_EINVAL) return r;
   }
-  if (!(t_dbg_flags & CT_DEBUG_NO_BAND)) {
-    const int r = run_band_slice_bwd<DIM>(a, grid, g_pos, g, st);
+  if (!sw.has(CT_DEBUG_NO_BAND)) {
+    const int r = run_band_slice_bwd<DIM>(sw, a, grid, g_pos, g, st);
     if (r != CT_EINVAL) return r;
   }
   // gather side: tile + [CC] maxima + [G] counters in LDS
@@ -2684,10 +2548,9 @@ int run_slice_bwd_fast(RasterArgs a, const float* grid, float* g_pos, const int*
   }
   ga.stats = stats;
   dim3 ggrid(ga.nsplit, a.H, a.B);
-  if constexpr (DIM == 2)
-    CT_LAUNCH_QUAD((2, QM_GATHER_GW, CT_QUAD_CG, CT_QUAD_THREADS, true), ggrid, quad_threads(a.N, ga.nsplit), pg.lds_bytes + extra, st, ga, g);
-  else
-    CT_LAUNCH_QUAD((3, QM_GATHER_GW, 2, CT_QUAD_THREADS, true), ggrid, quad_threads(a.N, ga.nsplit), pg.lds_bytes + extra, st, ga, g);
+  if (launch_quad<DIM, QM_GATHER_GW, (DIM == 2 ? CT_QUAD_CG : 2), CT_QUAD_THREADS, true>(ggrid, quad_threads(a.N, ga.nsplit), pg.lds_bytes + extra, st,
+                                                                                         ga, g) != CT_OK)
+    return CT_ELAUNCH;
   // scatter side
   RasterArgs sa = a;
   sa.CC = ps.CC; sa.nchunks = ps.nchunks;
@@ -2727,10 +2590,11 @@ int splat_fwd_impl(PosSrc pos, const float* feat, const void* pad, int pad_dtype
   if (!valid_common(B, H, C, N, dim, W) || !feat || !grid || !valid_pad(pad, pad_dtype)) return CT_EINVAL;
   if (reduce != CT_REDUCE_MAX0 && reduce != CT_REDUCE_SUM) return CT_EINVAL;
   note_reset();
+  const Switches sw = read_switches();
   RasterArgs a = base_args(B, H, C, N, pad, pad_dtype);
   a.pos = pos; a.src = feat; a.tile_out = grid;
-  return dim == 2 ? run_scatter<2, FROM_KEYS>(a, W, reduce == CT_REDUCE_SUM, st)
-                  : run_scatter<3, FROM_KEYS>(a, W, reduce == CT_REDUCE_SUM, st);
+  return dim == 2 ? run_scatter<2, FROM_KEYS>(sw, a, W, reduce == CT_REDUCE_SUM, st)
+                  : run_scatter<3, FROM_KEYS>(sw, a, W, reduce == CT_REDUCE_SUM, st);
 }
 
 // g_pos_add: null (g_pos = result), g_pos itself (g_pos += result: CT_BWD_ACCUMULATE_KEYS) or another tensor of the same
@@ -2739,9 +2603,10 @@ template <bool FROM_KEYS>
 int splat_bwd_impl(PosSrc pos, const float* feat, const void* pad, int pad_dtype, const float* grid,
                    const float* g_grid, float* g_feat, float* g_pos, void* ws, size_t ws_bytes,
                    int B, int H, int C, int N, int dim, const int* W, int reduce, hipStream_t st,
-                   const float* g_pos_add = nullptr, void* tickets = nullptr) {
+                   const float* g_pos_add = nullptr, void* tickets = nullptr, const Switches* outer = nullptr) {
   if (!valid_common(B, H, C, N, dim, W) || !feat || !g_grid || !g_feat || !g_pos || !valid_pad(pad, pad_dtype)) return CT_EINVAL;
   note_reset();
+  const Switches sw = outer ? *outer : read_switches();      // (outer: the call below on its own behalf)
   if (g_pos_add != nullptr) {
     // The hot Splat(max) backward adds in its own store; every other path computes the plain result — into the tail of the
     // workspace when the sum is in place — and adds.
@@ -2755,7 +2620,7 @@ int splat_bwd_impl(PosSrc pos, const float* feat, const void* pad, int pad_dtype
       a.accumulate = in_place ? 1 : 0;
       a.gpos_add = g_pos_add;
       a.tickets = (unsigned*)tickets;
-      const int r = dim == 2 ? run_splat_max_bwd<2, FROM_KEYS>(a, W, ws, head, st) : run_splat_max_bwd<3, FROM_KEYS>(a, W, ws, head, st);
+      const int r = dim == 2 ? run_splat_max_bwd<2, FROM_KEYS>(sw, a, W, ws, head, st) : run_splat_max_bwd<3, FROM_KEYS>(sw, a, W, ws, head, st);
       if (r != CT_EINVAL) return r;
     }
     if constexpr (FROM_KEYS) {
@@ -2763,13 +2628,13 @@ int splat_bwd_impl(PosSrc pos, const float* feat, const void* pad, int pad_dtype
         RasterArgs a = base_args(B, H, C, N, pad, pad_dtype);
         a.pos = pos; a.src = feat; a.dst = g_feat; a.g_pos = g_pos; a.tile_in = g_grid;
         a.gpos_add = g_pos_add;
-        const int r = run_splat_sum_bwd_hot(a, make_grid<2>(W), st);
+        const int r = run_splat_sum_bwd_hot(sw, a, make_grid<2>(W), st);
         if (r != CT_EINVAL) return r;
       }
     }
     float* tmp = in_place ? (float*)((char*)ws + head) : g_pos;
     const int r = splat_bwd_impl<FROM_KEYS>(pos, feat, pad, pad_dtype, grid, g_grid, g_feat, tmp, ws, head, B, H, C, N, dim, W,
-                                            reduce, st, nullptr, tickets);
+                                            reduce, st, nullptr, tickets, &sw);
     if (r != CT_OK) return r;
     CT_CLEAR_ERROR();
     hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)((gpos_n + 255) / 256)), dim3(256), 0, st, g_pos,
@@ -2784,18 +2649,18 @@ int splat_bwd_impl(PosSrc pos, const float* feat, const void* pad, int pad_dtype
     if (!grid) return CT_EINVAL;
     a.tile_in = grid; a.tile_in2 = g_grid;
     a.tickets = (unsigned*)tickets;
-    return dim == 2 ? run_splat_max_bwd<2, FROM_KEYS>(a, W, ws, ws_bytes, st)
-                    : run_splat_max_bwd<3, FROM_KEYS>(a, W, ws, ws_bytes, st);
+    return dim == 2 ? run_splat_max_bwd<2, FROM_KEYS>(sw, a, W, ws, ws_bytes, st)
+                    : run_splat_max_bwd<3, FROM_KEYS>(sw, a, W, ws, ws_bytes, st);
   } else if (reduce == CT_REDUCE_SUM) {
     // linear op: g_feat = Slice(g_grid), gw = sum_c g_grid * feat
     a.tile_in = g_grid;
     if constexpr (FROM_KEYS) {
       if (dim == 2) {
-        const int r = run_splat_sum_bwd_hot(a, make_grid<2>(W), st);
+        const int r = run_splat_sum_bwd_hot(sw, a, make_grid<2>(W), st);
         if (r != CT_EINVAL) return r;
       }
     }
-    int r = dim == 2 ? run_gather<2, FROM_KEYS>(a, W, st) : run_gather<3, FROM_KEYS>(a, W, st);
+    int r = dim == 2 ? run_gather<2, FROM_KEYS>(sw, a, W, st) : run_gather<3, FROM_KEYS>(sw, a, W, st);
     if (r != CT_OK) return r;
     return dim == 2 ? run_gather_gw<2, FROM_KEYS>(a, W, st) : run_gather_gw<3, FROM_KEYS>(a, W, st);
   }
@@ -2807,9 +2672,10 @@ int slice_fwd_impl(PosSrc pos, const float* grid, const void* pad, int pad_dtype
                    int B, int H, int C, int N, int dim, const int* W, hipStream_t st) {
   if (!valid_common(B, H, C, N, dim, W) || !grid || !out || !valid_pad(pad, pad_dtype)) return CT_EINVAL;
   note_reset();
+  const Switches sw = read_switches();
   RasterArgs a = base_args(B, H, C, N, pad, pad_dtype);
   a.pos = pos; a.tile_in = grid; a.dst = out;
-  return dim == 2 ? run_gather<2, FROM_KEYS>(a, W, st) : run_gather<3, FROM_KEYS>(a, W, st);
+  return dim == 2 ? run_gather<2, FROM_KEYS>(sw, a, W, st) : run_gather<3, FROM_KEYS>(sw, a, W, st);
 }
 
 template <bool FROM_KEYS>
@@ -2818,6 +2684,7 @@ int slice_bwd_impl(PosSrc pos, const float* grid, const void* pad, int pad_dtype
                    void* ws = nullptr, size_t ws_bytes = 0, void* tickets = nullptr, const void* sorted = nullptr) {
   if (!valid_common(B, H, C, N, dim, W) || !grid || !g_out || !g_grid || !g_pos || !valid_pad(pad, pad_dtype)) return CT_EINVAL;
   note_reset();
+  const Switches sw = read_switches();
   RasterArgs a = base_args(B, H, C, N, pad, pad_dtype);
   a.pos = pos; a.src = g_out; a.tile_out = g_grid;
   a.tickets = (unsigned*)tickets;          // only the hot kernels (run_slice_bwd_hot) fold; every other path ignores them
@@ -2829,10 +2696,10 @@ int slice_bwd_impl(PosSrc pos, const float* grid, const void* pad, int pad_dtype
   if (FROM_KEYS && (N & 3) == 0) {
     // fast path: g_keys first (its kernel also leaves the scatter's quantum statistics in g_grid),
     // then the streaming fixed-point scatter-add
-    int r = dim == 2 ? run_slice_bwd_fast<2>(a, grid, g_pos, W, ws, ws_bytes, st) : run_slice_bwd_fast<3>(a, grid, g_pos, W, ws, ws_bytes, st);
+    int r = dim == 2 ? run_slice_bwd_fast<2>(sw, a, grid, g_pos, W, ws, ws_bytes, st) : run_slice_bwd_fast<3>(sw, a, grid, g_pos, W, ws, ws_bytes, st);
     if (r != CT_EINVAL) return r;       // CT_EINVAL: shape not eligible, use the generic pair below
   }
-  int r = dim == 2 ? run_scatter<2, FROM_KEYS>(a, W, true, st) : run_scatter<3, FROM_KEYS>(a, W, true, st);
+  int r = dim == 2 ? run_scatter<2, FROM_KEYS>(sw, a, W, true, st) : run_scatter<3, FROM_KEYS>(sw, a, W, true, st);
   if (r != CT_OK) return r;
   a.tile_out = nullptr; a.tile_in = grid; a.g_pos = g_pos;
   return dim == 2 ? run_gather_gw<2, FROM_KEYS>(a, W, st) : run_gather_gw<3, FROM_KEYS>(a, W, st);
@@ -2921,11 +2788,8 @@ static size_t splat_bwd_workspace_generic(int B, int H, int C, int N, int dim, c
 size_t ct_splat_bwd_workspace_bytes(int B, int H, int C, int N, int dim, const int* W, int reduce) {
   if (!valid_common(B, H, C, N, dim, W) || reduce != CT_REDUCE_MAX0) return 0;
   size_t n = splat_bwd_workspace_generic(B, H, C, N, dim, W);
-  {                     // the hot kernels' chunk groups (whichever family a call ends up on, the scratch is enough)
-    const size_t hot = dim == 2 ? splat_bwd_hot_workspace(B, H, C, N, make_grid<2>(W)) : splat_bwd_hot_workspace(B, H, C, N, make_grid<3>(W));
-    if (hot > n) n = hot;
-  }
-  return n;
+  const size_t hot = dim == 2 ? splat_bwd_hot_workspace(B, H, C, N, make_grid<2>(W)) : splat_bwd_hot_workspace(B, H, C, N, make_grid<3>(W));
+  return std::max(n, hot);
 }
 
 int ct_splat_bwd(const float* keys, const float* feat, const void* pad, int pad_dtype, const float* grid,
@@ -2977,7 +2841,8 @@ int ct_slice_bwd(const float* keys, const float* grid, const void* pad, int pad_
 
 size_t ct_slice_bwd_workspace_bytes(int B, int H, int C, int N, int dim, const int* W) {
   if (!valid_common(B, H, C, N, dim, W)) return 0;
-  const size_t hot = dim == 2 ? slice_bwd_hot_workspace(B, H, C, N, make_grid<2>(W)) : slice_bwd_hot_workspace(B, H, C, N, make_grid<3>(W));
+  const Switches sw = read_switches();
+  const size_t hot = dim == 2 ? slice_bwd_hot_workspace(sw, B, H, C, N, make_grid<2>(W)) : slice_bwd_hot_workspace(sw, B, H, C, N, make_grid<3>(W));
   // the two-kernel form's per-split statistics (run_slice_bwd_fast): [nsplit][B*H*C][2] words
   const int ns = slice_bwd_stats_nsplit(B, H, N);
   const size_t stats = ns > 1 ? (size_t)ns * B * H * C * 8 : 0;
@@ -2995,18 +2860,20 @@ int ct_slice_bwd_ws(const float* keys, const float* grid, const void* pad, int p
 void ct_debug_set_nseg(int nseg) { t_dbg_nseg.store(nseg, std::memory_order_relaxed); }
 
 int ct_splat_bwd_tk_segments(int B, int H, int C, int N, int dim, const int* W) {
-  if (!valid_common(B, H, C, N, dim, W) || !hot_enabled() || (N & 3) || (C & 3)) return 1;
+  if (!valid_common(B, H, C, N, dim, W)) return 1;
+  const Switches sw = read_switches();
   long long G = 1;
   for (int j = 0; j < dim; ++j) G *= W[j];
-  if ((G & 3) || ((long long)B * H < 32 && !(t_dbg_flags & CT_DEBUG_FORCE_HOT)) || (long long)B * H > CT_TICKETS_BYTES / 8) return 1;
+  if (!hot_shape_ok(sw, B, H, C, N, (int)G, 0) || (long long)B * H > CT_TICKETS_BYTES / 8) return 1;
+  if (sw.has(CT_DEBUG_FORCE_BAND) && C == 4 && ((G / W[0]) & 3) == 0 && W[0] >= 4) return 2;
   HotPlan sp;
-  if ((t_dbg_flags & CT_DEBUG_FORCE_BAND) && C == 4 && ((G / W[0]) & 3) == 0 && W[0] >= 4) return 2;
-  if (!hot_chunks(C, (size_t)G * 8, kSplatBwdFixed, sp)) {
+  const int nseg = splat_bwd_segments_plan(sw, B, H, C, N, (int)G, dim, sp);
+  if (nseg == 0) {
     // the banded kernels (ct_raster_band.h: grids beyond a CU's LDS) redo a band with exact ties from the incoming
     // cotangent: a second tensor too
-    return (C == 4 && ((G / W[0]) & 3) == 0 && W[0] >= 4 && (size_t)G * 4 > (size_t)kBigLdsBytes && !(t_dbg_flags & CT_DEBUG_NO_BAND)) ? 2 : 1;
+    return (C == 4 && ((G / W[0]) & 3) == 0 && W[0] >= 4 && (size_t)G * 4 > (size_t)kBigLdsBytes && !sw.has(CT_DEBUG_NO_BAND)) ? 2 : 1;
   }
-  return splat_bwd_segments(B, H, C, N, (int)G, dim, sp.lds);
+  return nseg;
 }
 
 int ct_tickets_init(void* tickets, ct_stream_t s) {

@@ -232,10 +232,6 @@ __device__ __forceinline__ void scatter_float_channel(const RasterArgs& a, const
   }
 }
 
-#ifndef CT_FUSED_PAIR
-#define CT_FUSED_PAIR 1
-#endif
-
 // GATHER = false: the scatter-add alone (Splat(sum) forward, ct_slice_bwd_grid): no conv tile, no g_keys.
 // NTB: the launch's thread bound — kHotWideThreads for the WIDE launches (one 1024-thread workgroup per CU where the tiles leave no
 // room for a second 512-thread one: 16 waves per CU instead of 8, see hot_wide in ct_raster.hip)
@@ -400,11 +396,9 @@ __global__ void __launch_bounds__(NTB, CT_FUSED_WAVES) slice_bwd_fused_kernel(Ra
           any_float = true;
         }
       }
-#if CT_FUSED_PAIR
       // channel pairs share a 64-bit accumulator word: a pair with a float-path channel takes the float path whole
       if (iq[0] == 0.0f || iq[1] == 0.0f) iq[0] = iq[1] = 0.0f;
       if (iq[2] == 0.0f || iq[3] == 0.0f) iq[2] = iq[3] = 0.0f;
-#endif
       const float4* Tq = T4 + (size_t)cq * G;
       int* accq = acc + (size_t)(cq * 4) * G;
 #pragma unroll
@@ -454,7 +448,6 @@ __global__ void __launch_bounds__(NTB, CT_FUSED_WAVES) slice_bwd_fused_kernel(Ra
           //  branch here, so that the point's work stays one basic block in source order.  Issuing the next point's
           //  gathers ahead of these atomics was measured: no gain.)
           const ct_f2 cw01 = {p.cw[0], p.cw[1]}, cw23 = {p.cw[2], p.cw[3]};
-#if CT_FUSED_PAIR
           // Two channels per LDS atomic: the pair's fixed-point values go into one 64-bit word {lo = channel 2k, hi =
           // channel 2k+1} as hi * 2^32 + lo in two's complement (high word = hi + (lo >> 31)), so the word holds
           // sum(hi) * 2^32 + sum(lo) exactly and the halves are recovered at write-out.  ds_add_u64 5.5 ns against
@@ -472,18 +465,6 @@ __global__ void __launch_bounds__(NTB, CT_FUSED_WAVES) slice_bwd_fused_kernel(Ra
               atomicAdd(Tc + off[v], val);
             }
           }
-#else
-#pragma unroll
-          for (int cj = 0; cj < 4; ++cj) {
-            int* Tc = accq + cj * G + p.base;
-            const float fq = fv[cj][i] * iq[cj];          // power-of-two scale: exact
-            const ct_f2 p01 = cw01 * fq, p23 = cw23 * fq; // v_pk_mul_f32
-            atomicAdd(Tc + off[0], cvt_rpi(p01.x));
-            atomicAdd(Tc + off[1], cvt_rpi(p01.y));
-            atomicAdd(Tc + off[2], cvt_rpi(p23.x));
-            atomicAdd(Tc + off[3], cvt_rpi(p23.y));
-          }
-#endif
           __builtin_amdgcn_sched_barrier(0);     // one point at a time: keeps the live set inside the register budget
         }
       }
@@ -493,19 +474,14 @@ __global__ void __launch_bounds__(NTB, CT_FUSED_WAVES) slice_bwd_fused_kernel(Ra
           float q, iqd;
           bool fixed;
           fx_quantum(__uint_as_float(s_max[ch0 + cj]) * Kf, q, iqd, fixed);
-#if CT_FUSED_PAIR
           if (iq[cj] == 0.0f)      // this channel's pair is on the float path: its half of the pair's words holds a float
             scatter_float_channel<HAS_PAD>(a, g, bh, b, ch0 + cj, (float*)(accq + (size_t)(cj >> 1) * 2 * G) + (cj & 1), 2, so);
-#else
-          if (!fixed) scatter_float_channel<HAS_PAD>(a, g, bh, b, ch0 + cj, (float*)(accq + cj * G), 1, so);
-#endif
         }
       }
     }
     __syncthreads();
     // write the chunk out (and clear the accumulators for the next chunk in the same sweep)
     const bool more = chunk + a.ncg < a.nchunks;
-#if CT_FUSED_PAIR
     // a thread takes 4 cells of a channel pair: two 16-byte reads of {lo, hi} words -> one float4 per channel
     for (int t = tid; t < (cc >> 1) * (G >> 2); t += blockDim.x) {
       const int pr = t / (G >> 2), cell = (t - pr * (G >> 2)) << 2;
@@ -530,20 +506,6 @@ __global__ void __launch_bounds__(NTB, CT_FUSED_WAVES) slice_bwd_fused_kernel(Ra
       st_part4(gout + (size_t)(2 * pr + 1) * G + cell, ob, fold_grid);
       if (more) w[0] = w[1] = make_int4(0, 0, 0, 0);
     }
-#else
-    for (int t = tid; t < (cc * G) >> 2; t += blockDim.x) {
-      const int ch = (t << 2) / G;                 // G % 4 == 0: a float4 never straddles channels
-      float q, iqd;
-      bool fixed;
-      fx_quantum(__uint_as_float(s_max[c0 + ch]) * Kf, q, iqd, fixed);
-      const int4 r = ((const int4*)acc)[t];
-      float4 o;
-      if (fixed) o = make_float4((float)r.x * q, (float)r.y * q, (float)r.z * q, (float)r.w * q);
-      else o = make_float4(__int_as_float(r.x), __int_as_float(r.y), __int_as_float(r.z), __int_as_float(r.w));
-      st_part4(gout + ((size_t)t << 2), o, fold_grid);
-      if (more) ((int4*)acc)[t] = make_int4(0, 0, 0, 0);
-    }
-#endif
     // (the next chunk's staging overwrites T4 only: every gather of this chunk is behind the barrier above)
   }
 #pragma unroll
@@ -1121,12 +1083,7 @@ __global__ void __launch_bounds__(NTB, 4) splat_max_bwd_hot_kernel(RasterArgs a,
   } else if (threadIdx.x < 20) {
     s_cnt[kTieSumPos + threadIdx.x] = 0;       // the pass's bit sums, the words of splat_bwd_fix_mem
   }
-#ifdef CT_EXP_CLAIMS_ONLY       // experiment: no optimistic pass, every plane with single-winner claims (the cost of a tie-proof single pass)
-  tie = nsg == 1;
-  if (nsg > 1)
-#endif
   splat_bwd_plane_pass<HAS_PAD, false, WT, QPT>(a, g, ZG, s_cnt, bh, b, wg.cgi, N, R, gs, tie, grp);
-#ifndef CT_EXP_CLAIMS_ONLY
   if constexpr (QPT > 0) {
     if (tie && grp != nullptr) {    // block-uniform
       const int G = WT ? WT * WT : g.G;
@@ -1185,7 +1142,6 @@ __global__ void __launch_bounds__(NTB, 4) splat_max_bwd_hot_kernel(RasterArgs a,
       tie = false;
     }
   }
-#endif
   if constexpr (QPT == 0) {       // the through-memory form: the key cotangents are in their rows, one surplus match is repaired there
     if (CT_TIE_FIX && tie && nsg == 1 && s_cnt[1] - s_cnt[0] == 1) {
       const unsigned gbits = (unsigned)(s_cnt[kTieSumPos] - s_cnt[kTieSumNeg]);

@@ -202,10 +202,8 @@ __global__ void __launch_bounds__(NTB, 4) slice_bwd_fused3_kernel(RasterArgs a, 
           any_float = true;
         }
       }
-#if CT_FUSED_PAIR
       if (iq[0] == 0.0f || iq[1] == 0.0f) iq[0] = iq[1] = 0.0f;      // 64-bit {lo, hi} words: see slice_bwd_fused_kernel
       if (iq[2] == 0.0f || iq[3] == 0.0f) iq[2] = iq[3] = 0.0f;
-#endif
       const float4* Tq = T4 + (size_t)cq * G;
       int* accq = acc + (size_t)(cq * 4) * G;
 #pragma unroll
@@ -258,7 +256,6 @@ __global__ void __launch_bounds__(NTB, 4) slice_bwd_fused3_kernel(RasterArgs a, 
           gs[0][i][1] += gd[1];
           gs[0][i][2] += gd[2];
           asm volatile("" : "+v"(gs[0][i][0]), "+v"(gs[0][i][1]), "+v"(gs[0][i][2]));
-#if CT_FUSED_PAIR
 #pragma unroll
           for (int pj = 0; pj < 2; ++pj) {
             unsigned long long* Tc = (unsigned long long*)accq + (size_t)pj * G + p.base;
@@ -269,15 +266,6 @@ __global__ void __launch_bounds__(NTB, 4) slice_bwd_fused3_kernel(RasterArgs a, 
               atomicAdd(Tc + off[v], ((unsigned long long)(unsigned)(hi + (lo >> 31)) << 32) | (unsigned)lo);
             }
           }
-#else
-#pragma unroll
-          for (int cj = 0; cj < 4; ++cj) {
-            int* Tc = accq + cj * G + p.base;
-            const float fq = fv[cj][i] * iq[cj];
-#pragma unroll
-            for (int v = 0; v < 8; ++v) atomicAdd(Tc + off[v], cvt_rpi(fq * p.cw[v]));
-          }
-#endif
           __builtin_amdgcn_sched_barrier(0);
         }
         if (!kKeepGs && active[u])      // (the workgroup's last share of a quad is the finished partial: handed off when folded)
@@ -290,15 +278,9 @@ __global__ void __launch_bounds__(NTB, 4) slice_bwd_fused3_kernel(RasterArgs a, 
           float q, iqd;
           bool fixed;
           fx_quantum(__uint_as_float(s_max[ch0 + cj]) * Kf, q, iqd, fixed);
-#if CT_FUSED_PAIR
           constexpr int es = 2;
           if (iq[cj] == 0.0f) {
             float* row_acc = (float*)(accq + (size_t)(cj >> 1) * 2 * G) + (cj & 1);
-#else
-          constexpr int es = 1;
-          if (!fixed) {
-            float* row_acc = (float*)(accq + cj * G);
-#endif
             const float* src = a.src + (bh * a.C + ch0 + cj) * (size_t)Nr + so;
             for (int qd = tid; qd < (N >> 2); qd += blockDim.x) {
               const int nn = qd << 2;
@@ -321,7 +303,6 @@ __global__ void __launch_bounds__(NTB, 4) slice_bwd_fused3_kernel(RasterArgs a, 
     }
     __syncthreads();
     const bool more = chunk + a.ncg < a.nchunks;
-#if CT_FUSED_PAIR
     for (int t = tid; t < (cc >> 1) * (G >> 2); t += blockDim.x) {
       const int pr = t / (G >> 2), cell = (t - pr * (G >> 2)) << 2;
       float qa, qb, iqd;
@@ -344,20 +325,6 @@ __global__ void __launch_bounds__(NTB, 4) slice_bwd_fused3_kernel(RasterArgs a, 
       st_part4(gout + (size_t)(2 * pr + 1) * G + cell, ob, fold_grid);
       if (more) w[0] = w[1] = make_int4(0, 0, 0, 0);
     }
-#else
-    for (int t = tid; t < (cc * G) >> 2; t += blockDim.x) {
-      const int ch = (t << 2) / G;
-      float q, iqd;
-      bool fixed;
-      fx_quantum(__uint_as_float(s_max[c0 + ch]) * Kf, q, iqd, fixed);
-      const int4 r = ((const int4*)acc)[t];
-      float4 o;
-      if (fixed) o = make_float4((float)r.x * q, (float)r.y * q, (float)r.z * q, (float)r.w * q);
-      else o = make_float4(__int_as_float(r.x), __int_as_float(r.y), __int_as_float(r.z), __int_as_float(r.w));
-      st_part4(gout + ((size_t)t << 2), o, fold_grid);
-      if (more) ((int4*)acc)[t] = make_int4(0, 0, 0, 0);
-    }
-#endif
   }
   if (kKeepGs) {
     if (active[0]) {

@@ -420,12 +420,7 @@ __global__ void __launch_bounds__(kSortThreads, 8) plane_sort_kernel(RasterArgs 
 
 // ---------------------------------------------------------------------------
 // KF': Slice backward on the sorted plane.  grid = (1, H, B), kSortThreads threads.
-// CT_SORT_ABL (experiments, tools/dev/build_raster_exp.sh): 1 = the sort and the epilogue only, 2 = + staging, barriers and
-// write-out (no items).  Results are wrong then: timing only.
 // ---------------------------------------------------------------------------
-#ifndef CT_SORT_ABL
-#define CT_SORT_ABL 0
-#endif
 // byte offset of slot j's weights (8 x its sorted position); its stage word is at twice that
 #define CT_E8(S, u, j) (((j) & 1) ? ((S).ent8[u][(j) >> 1] >> 16) : ((S).ent8[u][(j) >> 1] & 0xffffu))
 #ifndef CT_SB
@@ -471,40 +466,24 @@ __global__ void __launch_bounds__(kSortThreads) slice_bwd_sorted_kernel(RasterAr
   auto request1 = [&](int grp, int cj) {          // one channel of group grp: the quad's g_out and the thread's conv cell
     const float4 t = ld_stream4(src0 + (size_t)(grp * 4 + cj) * N + ln0);
     gq[cj][0] = t.x; gq[cj][1] = t.y; gq[cj][2] = t.z; gq[cj][3] = t.w;
-#if CT_SORT_ABL == 5        // experiment: no conv loads (wrong g_keys): what do the 64 one-dword load instructions per group cost?
-    cvq[cj] = 1.0f;
-#else
     if constexpr (GATHER) cvq[cj] = ld_stream(cnv0 + (size_t)(grp * 4 + cj) * G + lc0);
-#endif
   };
   auto request = [&](int grp) {
 #pragma unroll
     for (int cj = 0; cj < 4; ++cj) request1(grp, cj);
   };
-#ifdef CT_SORT_STAGGER
-  if ((blockIdx.y + blockIdx.z) & 1) {      // experiment: odd planes start late, so that sort and streaming phases of different CUs interleave
-    const long long t0 = clock64();
-    while (clock64() - t0 < (long long)a.cnt_mask) __builtin_amdgcn_s_sleep(8);
-  }
-#endif
   PlaneKeys PK;
   if constexpr (!PRESORTED) load_plane_keys(a, g, W1, bh, PK);
   SortedPlane S;
   if constexpr (PRESORTED) load_sorted_plane(a, a.sorted + bh * a.sorted_stride, lds_raw, L, S);
-#ifndef CT_SORT_LATE_REQUEST
-#define CT_SORT_LATE_REQUEST 1
-#endif
-  if (PRESORTED || !CT_SORT_LATE_REQUEST) request(cgi);
+  if (PRESORTED) request(cgi);
   float pv[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) pv[i] = (HAS_PAD && has) ? ct_load_pad(a.pad, a.pad_dtype, (size_t)b * N + n0 + i) : 1.0f;
 
   // (the first group's rows are requested behind the keys' use: 28 MB asked for at once by all CUs made every plane wait ~2 k
   //  cycles longer for its 32 KiB of keys)
-  if constexpr (!PRESORTED) {
-    if (CT_SORT_LATE_REQUEST) sort_plane(a, PK, G, W1, sort_ptrs(lds_raw, L, C), C, S, nullptr, [&]() { request(cgi); });
-    else sort_plane(a, PK, G, W1, sort_ptrs(lds_raw, L, C), C, S);
-  }
+  if constexpr (!PRESORTED) sort_plane(a, PK, G, W1, sort_ptrs(lds_raw, L, C), C, S, nullptr, [&]() { request(cgi); });
   else __syncthreads();            // K (and the cleared channel maxima) for everybody
   for (int i = tid; i < G; i += kSortThreads) ((int4*)acc)[i] = make_int4(0, 0, 0, 0);
   if (tid == 0) Sg[N] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);       // what the slots beyond an item's entries read
@@ -516,7 +495,6 @@ __global__ void __launch_bounds__(kSortThreads) slice_bwd_sorted_kernel(RasterAr
 #pragma unroll
     for (int j = 0; j < kItemLen; ++j) gsx[u][j] = gsy[u][j] = 0.0f;
 
-#if CT_SORT_ABL != 1
   // one four-channel group; `more`: another group follows — its rows are requested as soon as this one's are staged (a
   // compile-time flag: a conditional request would make the compiler copy, and so wait for, the loaded registers at once)
   auto group = [&](const int grp, auto more) {
@@ -567,7 +545,6 @@ __global__ void __launch_bounds__(kSortThreads) slice_bwd_sorted_kernel(RasterAr
       }
       iq[cj] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(iq[cj])));      // wave-uniform: a scalar register
     }
-#if CT_SORT_ABL != 2
     // One loop per item: an entry's channels and weights are read once and feed both sides; the next entry's reads are issued
     // before this entry's arithmetic, the conv corners before anything else.  The NEXT group's eight global loads are issued
     // one channel per entry of the first item: a CU's vector-memory path takes ~3 k cycles to issue the 80 KiB of a group, and
@@ -589,13 +566,7 @@ __global__ void __launch_bounds__(kSortThreads) slice_bwd_sorted_kernel(RasterAr
       for (int v = 0; v < 4; ++v) s01[v] = s23[v] = ct_f2{0.0f, 0.0f};
 #pragma unroll
       for (int j = 0; j < kItemLen; ++j) {
-#ifndef CT_SORT_SPREAD
-#define CT_SORT_SPREAD 1      // channels of the next group requested per entry of the first item (2: two per entry, over the first two)
-#endif
-        if constexpr (spread) {
-          if (CT_SORT_SPREAD == 1) request1(grp + ncg, j);
-          else if (j < 2) { request1(grp + ncg, 2 * j); request1(grp + ncg, 2 * j + 1); }
-        }
+        if constexpr (spread) request1(grp + ncg, j);      // one channel of the next group per entry of the first item
         const float4 x = xn;
         const float2 wf = wn;
         if (j + 1 < kItemLen) {
@@ -641,9 +612,6 @@ __global__ void __launch_bounds__(kSortThreads) slice_bwd_sorted_kernel(RasterAr
     };
     item(std::integral_constant<int, 0>{});              // always: it carries the next group's loads
     if (S.cell[1] >= 0) item(std::integral_constant<int, 1>{});
-#else
-    if constexpr (decltype(more)::value) request(grp + ncg);
-#endif
     if (grp == 1) CT_STAMP(21);
     if (grp == 1) CT_WSTAMP(40 + (threadIdx.x >> 6));
     if (any_float) {           // block-uniform, rare: IEEE float atomics for a channel with inf / NaN (or beyond the fixed-point bound)
@@ -674,7 +642,6 @@ __global__ void __launch_bounds__(kSortThreads) slice_bwd_sorted_kernel(RasterAr
   for (; grp + ncg < ngroups; grp += ncg) group(grp, std::true_type{});
   group(grp, std::false_type{});
   CT_STAMP(9);
-#endif
   if constexpr (!GATHER) return;
   // g_keys: from the item owners (sorted order) back to the point owners through LDS (the stage area is free: the last
   // group's readers are behind the barrier above)

@@ -253,13 +253,6 @@ __device__ __forceinline__ void scatter_float_channel3(const RasterArgs& a, cons
   }
 }
 
-#ifndef CT_S2_PREFETCH
-#define CT_S2_PREFETCH 1
-#endif
-#ifndef CT_S3_PREFETCH
-#define CT_S3_PREFETCH 0      // 1: the next group's rows requested during this group's first item (20 more live registers: spills)
-#endif
-
 // ---------------------------------------------------------------------------
 // KF3': Slice backward on the sorted segment.  grid = (ncg, H, B * nseg), kS3Threads threads.
 //   a.N: points of a segment (<= kS3MaxPoints), a.Nrow: row length, a.nseg / a.ncg: segments / channel-group workgroups per plane
@@ -279,7 +272,7 @@ __global__ void __launch_bounds__(kS3Threads, 4) slice_bwd_sorted_seg_kernel(Ras
   constexpr int kFaces = DIM == 3 ? 2 : 1;
   // the next group's rows requested during this group's first item (20 more live registers): the 2D form with its grid known at
   // compile time has them to spare (126 registers), the 3D form spills 27 with it (54 vs 49 us)
-  constexpr bool kPrefetch = CT_S3_PREFETCH != 0 || (DIM == 2 && WK > 0 && CT_S2_PREFETCH != 0);
+  constexpr bool kPrefetch = DIM == 2 && WK > 0;
   // cell offsets of the in-face corners {0, sx, sy, sx + sy}; 3D: the z = 1 face is +1 (z fastest); 2D: x slowest, y fastest
   const int sy = DIM == 3 ? g.W[DIM - 1] : 1, sx = DIM == 3 ? g.W[1] * g.W[DIM - 1] : g.W[1];
   const Sort3Lds L = sort3_lds(G, n, C, DIM);
