@@ -149,6 +149,14 @@ __device__ __forceinline__ void st_stream4(float* p, float4 v) {
 }
 __device__ __forceinline__ float ld_stream(const float* p) { return __builtin_nontemporal_load(p); }
 
+// Launch tags (test hooks, host state): every entry point that picks among kernel families calls note_reset() on entry and
+// note("family") for each kernel it launches; ct_debug_last_launch() returns the tags joined with '+'.  Defined once, in
+// ct_raster.hip (the library is linked from one object per source); internal to the library.
+namespace ct_tags {
+__attribute__((visibility("hidden"))) void note_reset();
+__attribute__((visibility("hidden"))) void note(const char* tag);
+}  // namespace ct_tags
+
 // hipGetLastError() is sticky across unrelated runtime calls of the host
 // framework (e.g. a hipEventQuery that returned hipErrorNotReady), so every
 // entry point clears it first (CT_CLEAR_ERROR) and checks after its launches.

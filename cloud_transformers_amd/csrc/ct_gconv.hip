@@ -35,6 +35,12 @@ typedef float floatx4 __attribute__((ext_vector_type(4)));
 // the forward / backward-data pass takes the K-split kernel (0 = default)
 std::atomic<unsigned> t_gconv_debug{0};
 
+// Launch tags (ct_common.h): the three entry points reset the tag, and every launch_* names the kernel family and the host-side
+// choices that change the device code path (one tag per kernel, then its variants, all joined with '+'), once its plan is
+// settled and before it touches the device.  tests/gconv_families.py holds one row per tag.
+using ct_tags::note;
+using ct_tags::note_reset;
+
 constexpr int kThreads = 256;                // small tiles: several workgroups per CU
 constexpr int kThreadsBig = 1024;            // tiles that leave room for one or two workgroups per CU
 constexpr int kP = 4;                      // position groups per wave sharing one A read
@@ -1964,6 +1970,7 @@ int launch_c4_mfma3(GconvArgs a, hipStream_t st) {
   CSX += (16 - (CSX & 31) + 32) & 31;                         // == 16 (mod 32): the four channels' 16-float runs fall on all 32 banks twice
   const size_t lds = ((size_t)3 * 4 * CSX + (size_t)2 * 4 * TH * a.W + 2 * kSlack) * 4;
   dim3 grid(nH * nZ, a.groups, a.B);
+  note("c4_mfma3");
   CT_CLEAR_ERROR();
   if (a.transposed) {
     if (set_lds_attr(gconv_c4_mfma3_kernel<true>, lds) != CT_OK) return CT_ELAUNCH;
@@ -1981,6 +1988,7 @@ int launch_c4(GconvArgs a, int dim, hipStream_t st) {
   if (!plan_tiles_min_halo(a, dim, 0, 0, 4, 4, kLdsBudget) && !plan_tiles_min_halo(a, dim, 0, 0, 4, 4, kLdsBudgetMax)) return CT_EINVAL;
   const size_t lds = (size_t)4 * a.plane * 4 + 2 * kSlack * 4;
   dim3 grid(a.nD * a.nH, a.groups, a.B);
+  note("c4_valu");
   CT_CLEAR_ERROR();
 #define CT_C4_LAUNCH(DIMV, TR)                                                              \
   do {                                                                                      \
@@ -2020,6 +2028,8 @@ int launch_fwd4(GconvArgs a, int dim, hipStream_t st) {
   a.msplit = pick_msplit(a);
   dim3 grid(a.nD * a.nH * a.msplit, a.groups, a.B);
   const int threads = lds > 48 * 1024 ? kThreadsBig : kThreads;
+  note(threads == kThreadsBig ? "quad_1024" : "quad_256");
+  if (a.msplit > 1) note("quad_msplit");
   CT_CLEAR_ERROR();
   if (dim == 2) {
     if (set_lds_attr(gconv_fwd4_kernel<2>, lds) != CT_OK) return CT_ELAUNCH;
@@ -2062,6 +2072,9 @@ int launch_fwd4k(GconvArgs a, int dim, hipStream_t st) {
     const int maxi = items <= kWaves ? 1 : (items <= 2 * kWaves ? 2 : 4);
     // whole 16-channel rows at 16-byte aligned addresses move by LDS-DMA
     const int dma = (a.Cin % 16 == 0 && a.Cout % 16 == 0 && (((uintptr_t)a.w) & 15) == 0) ? 1 : 0;
+    note(pass == 0 ? (dma ? "ksplit_one_dma" : "ksplit_one_elem") : (dma ? "ksplit_tiled_dma" : "ksplit_tiled_elem"));
+    note(maxi == 1 ? "ksplit_items1" : maxi == 2 ? "ksplit_items2" : "ksplit_items4");
+    if (msplit > 1) note("ksplit_msplit");
     CT_CLEAR_ERROR();
 #define CT_F4K_LAUNCH(DIMV, MAXIV, TRV)                                                                \
     do {                                                                                               \
@@ -2099,6 +2112,7 @@ int tiny_cob(const GconvArgs& a, int dim) {
 int launch_tiny(GconvArgs a, int dim, int cob, hipStream_t st) {
   const size_t lds = tiny_lds(a, dim, cob);
   dim3 grid((a.Cout + cob - 1) / cob, a.groups);
+  note(dim == 2 ? "dense2d" : "dense3d");
   CT_CLEAR_ERROR();
   if (dim == 2) {
     if (set_lds_attr(gconv_tiny_kernel<2>, lds) != CT_OK) return CT_ELAUNCH;
@@ -2144,6 +2158,8 @@ int launch_fwd(GconvArgs a, int dim, hipStream_t st) {
   a.msplit = pick_msplit(a);
   dim3 grid(a.nD * a.nH * a.msplit, a.groups, a.B);
   const int threads = lds > 48 * 1024 ? kThreadsBig : kThreads;
+  note("onepos");
+  if (a.msplit > 1) note("onepos_msplit");
   CT_CLEAR_ERROR();
   if (dim == 2) {
     if (set_lds_attr(gconv_fwd_kernel<2>, lds) != CT_OK) return CT_ELAUNCH;
@@ -2213,6 +2229,8 @@ int launch_wrw_ring(GconvArgs a, int dim, const float* g_y, float* g_w, float* g
   WrwRingPlan p;
   if (!plan_wrw_ring(a, dim, p)) return CT_EINVAL;
   if (ws && ws_bytes < wrw_ring_workspace(a, p)) return CT_EWORKSPACE;
+  note(ws ? "wrw_ring_ws" : "wrw_ring_atomics");
+  if (ws) note("wrw_reduce");
   if (!ws && hipMemsetAsync(g_w, 0, (size_t)a.groups * a.Cout * a.Cin * a.taps * 4, st) != hipSuccess) return CT_ELAUNCH;
   dim3 grid(p.chunks, a.groups);
   if (dim == 2) {
@@ -2242,6 +2260,8 @@ int launch_c4_wrw(GconvArgs a, int dim, const float* g_y, float* g_w, float* g_b
   WrwRingPlan p;
   if (!plan_wrw_ring(a, dim, p, 4)) return CT_EINVAL;
   if (ws_bytes < c4_wrw_workspace(a, p)) return CT_EWORKSPACE;
+  note("wrw_c4_ring");
+  note("wrw_c4_reduce");
   dim3 grid(p.chunks, a.groups);
   if (dim == 2) {
     if (set_lds_attr(gconv_wrw_ring_kernel<2, true, kThreads>, p.lds) != CT_OK) return CT_ELAUNCH;
@@ -2281,6 +2301,8 @@ size_t c4_wrw_mfma3_workspace(const GconvArgs& a, const C4WrwPlan& p) {
 
 int launch_c4_wrw_mfma3(GconvArgs a, const C4WrwPlan& p, const float* g_y, float* g_w, float* g_bias, float* ws, size_t ws_bytes, hipStream_t st) {
   if (ws_bytes < c4_wrw_mfma3_workspace(a, p)) return CT_EWORKSPACE;
+  note("wrw_c4_mfma3");
+  note("wrw_c4_reduce");
   dim3 grid(p.nZ, a.groups, a.B);
   CT_CLEAR_ERROR();
   if (set_lds_attr(gconv_c4_wrw_mfma3_kernel, p.lds) != CT_OK) return CT_ELAUNCH;
@@ -2295,11 +2317,12 @@ int launch_c4_wrw_mfma3(GconvArgs a, const C4WrwPlan& p, const float* g_y, float
 // backward-weight, tile kernel (any row length): plan + launch
 int launch_wrw_tiles(GconvArgs a, int dim, const float* g_y, float* g_w, hipStream_t st) {
   const int B = a.B, groups = a.groups;
-  if (hipMemsetAsync(g_w, 0, (size_t)groups * a.Cout * a.Cin * a.taps * 4, st) != hipSuccess) return CT_ELAUNCH;
   // LDS: 16 input planes with halo + 16 rows of g_y + the cross-wave reduction buffer
   const size_t red_bytes = (size_t)(kThreads / 64) * 3 * 256 * 4;
   if (!plan_tiles(a, dim, (size_t)16 * 4, 1024 + red_bytes, 16, /*plane == 4 (mod 32): 16-byte aligned for the DMA*/ 4,
-                  kLdsBudgetWrw)) return CT_EINVAL;
+                  kLdsBudgetWrw)) return CT_EINVAL;       // (before anything is written: a refused call leaves g_w as it was)
+  note("wrw_tiles");
+  if (hipMemsetAsync(g_w, 0, (size_t)groups * a.Cout * a.Cin * a.taps * 4, st) != hipSuccess) return CT_ELAUNCH;
   const int gstride_max = ((a.TD * a.TH * a.W + 3) & ~3) | 1;
   const size_t lds = ((size_t)16 * a.plane + (size_t)16 * gstride_max) * 4 + red_bytes + 2 * kSlack * 4;
   const int U = B * a.nD * a.nH;
@@ -2344,6 +2367,7 @@ bool wrw_small_eligible(const GconvArgs& a, int dim) {
 int launch_wrw_small(GconvArgs a, int dim, const float* g_y, float* g_w, float* g_bias, hipStream_t st) {
   const size_t lds = wrw_small_lds(a, dim);
   dim3 grid(((a.Cin + 15) / 16) * ((a.Cout + 15) / 16), a.groups);
+  note("wrw_small_valu");
   CT_CLEAR_ERROR();
 #define CT_WS_LAUNCH(DIMV, WTV)                                                                    \
   do {                                                                                             \
@@ -2402,6 +2426,8 @@ int launch_wrw_mfma(GconvArgs a, int dim, WrwMfmaPlan p, const float* g_y, float
   float* wsp = p.ksplit > 1 ? ws : nullptr;
   const int CiB = (a.Cin + 15) / 16, CoB = (a.Cout + 15) / 16;
   dim3 grid(CiB * CoB * p.ksplit, a.groups);
+  note(wsp ? "wrw_small_mfma_ksplit" : "wrw_small_mfma");
+  if (wsp) note("wrw_reduce");
   CT_CLEAR_ERROR();
 #define CT_WM_LAUNCH(DIMV, WTV)                                                                     \
   do {                                                                                              \
@@ -2452,6 +2478,7 @@ int ct_gconv_fwd(const float* x, const float* w, const float* bias, float* y,
   int r = gconv_common(a, B, groups, Cin, Cout, dim, W);
   if (r != CT_OK) return r;
   a.x = x; a.w = w; a.bias = bias; a.y = y; a.transposed = 0;
+  note_reset();
   return launch_fwd(a, dim, (hipStream_t)s);
 }
 
@@ -2463,6 +2490,8 @@ int ct_gconv_bwd_data(const float* g_y, const float* w, float* g_x,
   int r = gconv_common(a, B, groups, Cout, Cin, dim, W);
   if (r != CT_OK) return r;
   a.x = g_y; a.w = w; a.bias = nullptr; a.y = g_x; a.transposed = 1;
+  note_reset();
+  note("bwd_data");                                                // the same kernels with TR / a.transposed set
   return launch_fwd(a, dim, (hipStream_t)s);
 }
 
@@ -2482,7 +2511,7 @@ size_t ct_gconv_bwd_weight_workspace_bytes(int B, int groups, int Cin, int Cout,
     C4WrwPlan p4m;
     size_t need4 = plan_wrw_ring(a, dim, p4, 4) ? c4_wrw_workspace(a, p4) : 0;
     if (plan_c4_wrw_mfma3(a, dim, p4m) && c4_wrw_mfma3_workspace(a, p4m) > need4) need4 = c4_wrw_mfma3_workspace(a, p4m);
-    if (need4) return need4;
+    if (plan_wrw_ring(a, dim, p4, 4)) return need4;               // (no four-channel ring plan: the launch may take any form below)
   }
   WrwRingPlan p;
   size_t need = plan_wrw_ring(a, dim, p) ? wrw_ring_workspace(a, p) : 0;
@@ -2500,6 +2529,7 @@ int ct_gconv_bwd_weight(const float* x, const float* g_y, float* g_w, float* g_b
   int r = gconv_common(a, B, groups, Cin, Cout, dim, W);
   if (r != CT_OK) return r;
   a.x = x; a.transposed = 0;
+  note_reset();
   hipStream_t st = (hipStream_t)s;
   CT_CLEAR_ERROR();
   const bool aligned = ((((uintptr_t)x) | ((uintptr_t)g_y)) & 15) == 0;
@@ -2519,9 +2549,11 @@ int ct_gconv_bwd_weight(const float* x, const float* g_y, float* g_w, float* g_b
   if (workspace && aligned && plan_c4_wrw_mfma3(a, dim, p4m) && !(t_gconv_debug.load(std::memory_order_relaxed) & 2) &&
       workspace_bytes >= c4_wrw_mfma3_workspace(a, p4m))
     return launch_c4_wrw_mfma3(a, p4m, g_y, g_w, g_bias, (float*)workspace, workspace_bytes, st);
-  if (workspace && aligned && c4_wrw_eligible(a)) {
-    r = launch_c4_wrw(a, dim, g_y, g_w, g_bias, (float*)workspace, workspace_bytes, st);
-  } else {
+  // (the four-channel ring takes unaligned tensors too — the ring kernel stages them element-wise, its own `vec` flag — and it
+  // must: ct_gconv_bwd_weight_workspace_bytes sizes a four-channel group's workspace for the four-channel plans only)
+  r = CT_EINVAL;
+  if (workspace && c4_wrw_eligible(a)) r = launch_c4_wrw(a, dim, g_y, g_w, g_bias, (float*)workspace, workspace_bytes, st);
+  if (r == CT_EINVAL) {                                            // not a four-channel group, no workspace, or no four-channel plan
     r = (a.W & 3) == 0 ? launch_wrw_ring(a, dim, g_y, g_w, g_bias, (float*)workspace, workspace_bytes, st) : CT_EINVAL;
     if (r == CT_EINVAL) {                                          // rows off the 16-byte grid, or rings that do not fit LDS
       ring_bias = false;
@@ -2530,6 +2562,7 @@ int ct_gconv_bwd_weight(const float* x, const float* g_y, float* g_w, float* g_b
   }
   if (r != CT_OK) return r;
   if (g_bias && !ring_bias) {
+    note("bias_grad");
     const size_t vol = (size_t)a.D * a.H * a.W;
     hipLaunchKernelGGL(gconv_bias_grad_kernel, dim3(groups * Cout), dim3(256), 0, st, g_y, g_bias, B, groups * Cout, vol);
   }

@@ -1296,17 +1296,8 @@ std::atomic<int> t_dbg_nseg{0};          // ct_debug_set_nseg: point segments of
 std::mutex t_last_mu;
 char t_last[256] = "";
 
-void note_reset() {
-  std::lock_guard<std::mutex> lk(t_last_mu);
-  t_last[0] = 0;
-}
-void note(const char* tag) {
-  std::lock_guard<std::mutex> lk(t_last_mu);
-  size_t n = strlen(t_last), m = strlen(tag);
-  if (n + m + 2 >= sizeof(t_last)) return;
-  if (n) t_last[n++] = '+';
-  memcpy(t_last + n, tag, m + 1);
-}
+using ct_tags::note;          // declared in ct_common.h (shared with ct_gconv.hip), defined below this namespace
+using ct_tags::note_reset;
 
 // The run-time switches, read ONCE per entry point — where note_reset() is called, and in each workspace / segment query — and
 // passed down by value: every step of a call sees the same values, and so do a query and a launch made under the same settings.
@@ -2706,6 +2697,18 @@ int slice_bwd_impl(PosSrc pos, const float* grid, const void* pad, int pad_dtype
 }
 
 }  // namespace
+
+void ct_tags::note_reset() {
+  std::lock_guard<std::mutex> lk(t_last_mu);
+  t_last[0] = 0;
+}
+void ct_tags::note(const char* tag) {
+  std::lock_guard<std::mutex> lk(t_last_mu);
+  size_t n = strlen(t_last), m = strlen(tag);
+  if (n + m + 2 >= sizeof(t_last)) return;
+  if (n) t_last[n++] = '+';
+  memcpy(t_last + n, tag, m + 1);
+}
 
 // ---------------------------------------------------------------------------
 // C ABI

@@ -115,7 +115,7 @@ int ct_splat_bwd_ex(const float* keys, const float* feat, const void* pad, int p
 
 /* Test hooks (process-wide host state, never read by a kernel): flags select kernel families so that the
  * parity tests can compare them on identical inputs (atomic: set on one thread, read by entry points on any); the tag string
- * names the kernels the last Splat / Slice entry point launched — whichever thread called it, e.g. autograd's — and is
+ * names the kernels the last Splat / Slice or grouped-convolution entry point launched — whichever thread called it, e.g. autograd's — and is
  * returned as a copy owned by the calling thread (writers and readers serialise on a mutex). */
 #define CT_DEBUG_NO_HOT 1      /* keep the hot-shape kernels (csrc/ct_raster_hot.h) off */
 #define CT_DEBUG_FORCE_HOT 2   /* use them for every eligible layout, however few (b,h) planes there are */
@@ -514,8 +514,15 @@ int ct_mhct_core_bwd_fused(const float* keys, const float* feat, const void* pad
  * ct_mhct_core_status copies the workspace's status word to the host AFTER synchronising the stream (a test helper, the
  * only call of this library that waits for the device): 0 = no cluster gave up waiting for its partners. */
 void ct_debug_set_core(unsigned flags);
-/* Test hook of the grouped convolution: bit 0 = small-volume weight gradients take the vector-ALU kernel instead of the
- * matrix-core one (A/B measurements, tools/gconv64_bench.py). */
+/* Test hook of the grouped convolution (process-wide, read by the three ct_gconv entry points):
+ *   bit 0 (1)   small-volume weight gradients take the vector-ALU kernel instead of the matrix-core one (A/B measurements,
+ *               tools/gconv64_bench.py);
+ *   bit 1 (2)   four-channel 3D groups never take the matrix-core kernels (forward, backward-data and weight gradient);
+ *   bit 2 (4)   four-channel 3D groups take the matrix-core forward / backward-data kernel wherever its plan fits, whatever the
+ *               size (default: from 2 M positions); bit 1 wins over bit 2;
+ *   bits 8..15  input channels per group from which forward / backward-data take the K-split kernel (0: the default, 32).
+ * The three entry points name the kernels they launched through ct_debug_last_launch, as the Splat / Slice entry points do: one
+ * tag per kernel and per host-side choice that changes its code path, joined with '+' (tests/gconv_families.py lists them). */
 void ct_debug_set_gconv(unsigned flags);
 /* Test hook of the EMD auction: bit 0 = the per-batch update (GetMax, Assign, next list) on one workgroup per batch in every
  * iteration (default: several workgroups per batch while the batch has more than 1024 unassigned points). */

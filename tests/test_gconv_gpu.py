@@ -235,7 +235,9 @@ def test_four_channel_3d_groups_on_the_matrix_cores(B, G, W):
             y = torch.full_like(x, float("nan"))
             gx = torch.full_like(x, float("nan"))
             _lib.check(lib.ct_gconv_fwd(_ptr(x), _ptr(w), _ptr(b), _ptr(y), B, G, 4, 4, 3, Wa, _stream()), "fwd")
+            assert lib.ct_debug_last_launch() == (b"c4_mfma3" if flag == 4 else b"c4_valu")
             _lib.check(lib.ct_gconv_bwd_data(_ptr(x), _ptr(w), _ptr(gx), B, G, 4, 4, 3, Wa, _stream()), "bwd_data")
+            assert lib.ct_debug_last_launch() == (b"bwd_data+c4_mfma3" if flag == 4 else b"bwd_data+c4_valu")
             outs[flag] = (y, gx)
     finally:
         lib.ct_debug_set_gconv(0)
@@ -262,6 +264,10 @@ def test_four_channel_3d_groups_on_the_matrix_cores(B, G, W):
             gw = torch.full((G * 4, 4, 3, 3, 3), float("nan"), device="cuda")
             gb = torch.full((G * 4,), float("nan"), device="cuda")
             _lib.check(lib.ct_gconv_bwd_weight(_ptr(x), _ptr(gy), _ptr(gw), _ptr(gb), _ptr(ws), nws, B, G, 4, 4, 3, Wa, _stream()), "wrw")
+            # (the matrix-core plan keeps a ring of slices per wave of four rows: at 33 rows of 48 and 20 rows of 64 floats the
+            # rings exceed LDS, and both runs take the ring kernel)
+            mfma3 = flag == 0 and W not in ((9, 33, 48), (2, 20, 64))
+            assert lib.ct_debug_last_launch() == (b"wrw_c4_mfma3+wrw_c4_reduce" if mfma3 else b"wrw_c4_ring+wrw_c4_reduce")
             res.append((gw, gb))
     finally:
         lib.ct_debug_set_gconv(0)
@@ -293,6 +299,9 @@ def test_small_volume_weight_gradient_on_the_matrix_cores(B, G, Ci, Co, W):
             gw = torch.full((G * Co, Ci) + (3,) * dim, float("nan"), device="cuda")
             gb = torch.full((G * Co,), float("nan"), device="cuda")
             _lib.check(lib.ct_gconv_bwd_weight(_ptr(x), _ptr(gy), _ptr(gw), _ptr(gb), _ptr(ws), nws, B, G, Ci, Co, dim, Wa, _stream()), "wrw")
+            if flag == 0:      # the batch is split over workgroups while the channel blocks alone leave the chip uncovered
+                ksplit = B >= 2 and ((Ci + 15) // 16) * ((Co + 15) // 16) * G < 256
+                assert lib.ct_debug_last_launch() == (b"wrw_small_mfma_ksplit+wrw_reduce" if ksplit else b"wrw_small_mfma")
             res.append((gw, gb))
     finally:
         lib.ct_debug_set_gconv(0)
