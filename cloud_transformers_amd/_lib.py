@@ -266,6 +266,9 @@ SIGNATURES = {
     "ct_bn_group_apply_bwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "ct_bn_relu_fwd_amax": (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp]),
     "ct_bn_relu_bwd_amax": (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "ct_bn_eval_supported": (_i, [_i, _i, _i]),
+    "ct_bn_eval_fwd": (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _i, _i, _i, _f, _i, _vp]),
+    "ct_bn_eval_group_fwd": (_i, [_vp, _i, _i, _i, _vp]),
     "ct_bn_stats_fwd": (_i, [_vp, _ll, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "ct_bn_apply_fwd": (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _vp, _i, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _vp,
                              _i, _i, _i, _f, _f, _i, _vp]),

@@ -902,3 +902,176 @@ extern "C" int ct_bn_apply_bwd_amax(const float* x, long long x_batch_stride, co
   return bn_apply_bwd_impl(amax_out, x, x_batch_stride, weight, bias, mean, rstd, gy, gy_batch_stride, sum_g, sum_gxhat, count, gx,
                            gx_batch_stride, B, C, N, relu, s);
 }
+
+// ---- eval-mode BatchNorm1d (+ ReLU, + skip): a per-channel affine on the stored statistics ----
+//   y = relu?( ((x - running_mean_c) * rstd_c) * weight_c + bias_c ) [+ residual],   rstd_c = 1 / sqrt(running_var_c + eps)
+// in torch's operation order (the mean is subtracted first: x * scale + shift cancels when |mean| >> |x - mean|).  No
+// reduction over the channel, nothing saved, nothing written but y and amax_out: one streaming pass, bounded by its bytes
+// (read x, write y, read residual).
+//
+// Decomposition: no statistic ties a channel to one workgroup any more, so an item's channels are cut into `split` runs of
+// quads (floats on the scalar path) each, one workgroup per run — the key norms of a block have 3H = 48 channels, and a
+// workgroup per channel would leave four fifths of the CUs idle at B6 N8192.  A channel whose maximum is asked for
+// (amax_out) is NOT cut: its one workgroup folds the maximum of the values it stored through LDS, as the training kernels
+// do — no partial maxima, no arrival counters (this ABI passes no workspace, and counters owned by the library would be
+// shared by launches on concurrent streams), no second launch, and the result does not depend on any arrival order.  The
+// norms that are cut in practice are the key / values norms, whose outputs feed the lattice and Splat, not a GEMM.
+struct BnEvalItem {
+  const float* x;
+  const float* weight;
+  const float* bias;
+  const float* mean;
+  const float* var;
+  const float* residual;   // nullable
+  float* y;
+  float* amax_out;         // nullable; non-null implies split == 1
+  long long xbs, ybs, rbs;
+  int C, relu, split;
+  float eps;
+};
+struct BnEvalTable {
+  int n, B, N;
+  int wstart[kBnMaxItems + 1];   // first workgroup of every item (C * split workgroups each)
+  BnEvalItem item[kBnMaxItems];
+};
+
+constexpr int kEvalUnroll = 4;          // loads in flight per thread
+constexpr int kEvalTargetWgs = 1024;    // workgroups a launch is cut towards: 2 resident per CU x 256 CUs, two rounds
+constexpr int kEvalMinPerThread = 2;    // a run is not cut below this many quads per thread
+
+__device__ __forceinline__ float bn_eval_one(float x, float mu, float rs, float w, float be, int relu) {
+  const float o = ((x - mu) * rs) * w + be;
+  return relu ? fmaxf(o, 0.0f) : o;
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(kThreads) bn_eval_kernel(BnEvalTable t) {
+  __shared__ float red[1][kWaves];
+  int wg = blockIdx.x, i = 0;
+  while (i + 1 < t.n && wg >= t.wstart[i + 1]) ++i;
+  wg -= t.wstart[i];
+  const BnEvalItem& a = t.item[i];
+  const int c = wg / a.split, part = wg - c * a.split;
+  const unsigned total = (unsigned)chan_items<VEC>(t.B, t.N);
+  const unsigned run = (total + (unsigned)a.split - 1u) / (unsigned)a.split;
+  const unsigned lo = (unsigned)part * run;
+  const unsigned hi = lo + run < total ? lo + run : total;
+  const float mu = a.mean[c], rs = 1.0f / sqrtf(a.var[c] + a.eps), w = a.weight[c], be = a.bias[c];
+  const float* __restrict__ x = a.x;
+  const float* __restrict__ res = a.residual;
+  float* __restrict__ y = a.y;
+  float am = 0.f;
+  for (unsigned base = lo + threadIdx.x; base < hi; base += kEvalUnroll * kThreads) {
+    if (VEC) {
+      float4 v[kEvalUnroll], r[kEvalUnroll];
+#pragma unroll
+      for (int k = 0; k < kEvalUnroll; ++k) {
+        const unsigned e = base + k * kThreads;
+        if (e < hi) {
+          v[k] = *reinterpret_cast<const float4*>(x + item_offset<true>((int)e, t.N, c, a.xbs));
+          if (res) r[k] = *reinterpret_cast<const float4*>(res + item_offset<true>((int)e, t.N, c, a.rbs));
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < kEvalUnroll; ++k) {
+        const unsigned e = base + k * kThreads;
+        if (e < hi) {
+          float4 o;
+          o.x = bn_eval_one(v[k].x, mu, rs, w, be, a.relu);
+          o.y = bn_eval_one(v[k].y, mu, rs, w, be, a.relu);
+          o.z = bn_eval_one(v[k].z, mu, rs, w, be, a.relu);
+          o.w = bn_eval_one(v[k].w, mu, rs, w, be, a.relu);
+          if (res) { o.x += r[k].x; o.y += r[k].y; o.z += r[k].z; o.w += r[k].w; }
+          *reinterpret_cast<float4*>(y + item_offset<true>((int)e, t.N, c, a.ybs)) = o;
+          am = fmaxf(fmaxf(am, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+        }
+      }
+    } else {
+      float v[kEvalUnroll], r[kEvalUnroll];
+#pragma unroll
+      for (int k = 0; k < kEvalUnroll; ++k) {
+        const unsigned e = base + k * kThreads;
+        if (e < hi) {
+          v[k] = x[item_offset<false>((int)e, t.N, c, a.xbs)];
+          if (res) r[k] = res[item_offset<false>((int)e, t.N, c, a.rbs)];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < kEvalUnroll; ++k) {
+        const unsigned e = base + k * kThreads;
+        if (e < hi) {
+          float o = bn_eval_one(v[k], mu, rs, w, be, a.relu);
+          if (res) o += r[k];
+          y[item_offset<false>((int)e, t.N, c, a.ybs)] = o;
+          am = fmaxf(am, fabsf(o));
+        }
+      }
+    }
+  }
+  if (a.amax_out) {      // (uniform over the workgroup; split == 1: this workgroup stored the whole channel)
+    am = block_max(am, red);
+    if (threadIdx.x == 0) a.amax_out[c] = am;
+  }
+}
+
+// one value per channel is legal here (no variance is taken); a channel is indexed with 32-bit integers
+static bool eval_shape_ok(int B, int C, int N) {
+  if (B <= 0 || C <= 0 || N <= 0) return false;
+  return (long long)B * N <= 0x7fffffffLL;
+}
+
+extern "C" int ct_bn_eval_supported(int B, int C, int N) { return eval_shape_ok(B, C, N) ? 1 : 0; }
+
+extern "C" int ct_bn_eval_group_fwd(const ct_bn_fwd_item* items, int n, int B, int N, ct_stream_t s) {
+  if (!items || n < 1 || n > kBnMaxItems) return CT_EINVAL;
+  BnEvalTable t{};
+  t.n = n; t.B = B; t.N = N;
+  bool vec = true;
+  long long Ct = 0;
+  for (int i = 0; i < n; ++i) {
+    const ct_bn_fwd_item& it = items[i];
+    if (!it.x || !it.weight || !it.bias || !it.y || !it.running_mean || !it.running_var || !(it.eps >= 0.0f)) return CT_EINVAL;
+    if (!eval_shape_ok(B, it.C, N)) return CT_EINVAL;
+    BnEvalItem& a = t.item[i];
+    a = BnEvalItem{it.x, it.weight, it.bias, it.running_mean, it.running_var, it.residual, it.y, it.amax_out, 0, 0, 0,
+                   it.C, it.relu, 1, it.eps};
+    if (!stride_ok(it.x_batch_stride, it.C, N, a.xbs) || !stride_ok(it.y_batch_stride, it.C, N, a.ybs) ||
+        !stride_ok(it.residual_batch_stride, it.C, N, a.rbs))
+      return CT_EINVAL;
+    vec = vec && (N & 3) == 0 && ((a.xbs | a.ybs | a.rbs) & 3) == 0 &&
+          ((((uintptr_t)a.x) | ((uintptr_t)a.y) | ((uintptr_t)a.residual)) & 15) == 0;
+    Ct += it.C;
+  }
+  // runs per channel: towards kEvalTargetWgs workgroups in the launch, never below kEvalMinPerThread items a thread
+  const long long per = vec ? (long long)B * (N >> 2) : (long long)B * N;
+  long long split = (kEvalTargetWgs + Ct - 1) / Ct;
+  const long long most = per / ((long long)kThreads * kEvalMinPerThread);
+  if (split > most) split = most;
+  if (split < 1) split = 1;
+  long long w0 = 0;
+  for (int i = 0; i < n; ++i) {
+    t.item[i].split = t.item[i].amax_out ? 1 : (int)split;
+    t.wstart[i] = (int)w0;
+    w0 += (long long)t.item[i].C * t.item[i].split;
+    if (w0 > 0x7fffffffLL) return CT_EINVAL;
+  }
+  t.wstart[n] = (int)w0;
+  hipStream_t stream = (hipStream_t)s;
+  CT_CLEAR_ERROR();
+  if (vec) hipLaunchKernelGGL(bn_eval_kernel<true>, dim3((unsigned)w0), dim3(kThreads), 0, stream, t);
+  else hipLaunchKernelGGL(bn_eval_kernel<false>, dim3((unsigned)w0), dim3(kThreads), 0, stream, t);
+  CT_CHECK_LAUNCH();
+  return CT_OK;
+}
+
+extern "C" int ct_bn_eval_fwd(const float* x, long long x_batch_stride, const float* weight, const float* bias,
+                              const float* running_mean, const float* running_var, const float* residual,
+                              long long residual_batch_stride, float* y, long long y_batch_stride, float* amax_out,
+                              int B, int C, int N, float eps, int relu, ct_stream_t s) {
+  ct_bn_fwd_item it{};
+  it.x = x; it.x_batch_stride = x_batch_stride; it.weight = weight; it.bias = bias;
+  it.running_mean = const_cast<float*>(running_mean); it.running_var = const_cast<float*>(running_var);
+  it.residual = residual; it.residual_batch_stride = residual_batch_stride; it.y = y; it.y_batch_stride = y_batch_stride;
+  it.amax_out = amax_out; it.C = C; it.eps = eps; it.relu = relu;
+  return ct_bn_eval_group_fwd(&it, 1, B, N, s);
+}

@@ -61,14 +61,21 @@ def run_after(module_list, input, residual=None):
     """Apply an `after` Sequential (and add `residual` to its result); a training-mode nn.BatchNorm1d directly followed by
     nn.ReLU runs as the fused ct_bn_relu kernels when the shape qualifies (ops.bn_relu_eligible), the skip connection
     added in the same pass when that pair ends the stack (an nn.SyncBatchNorm too: ops exchanges the group's statistics
-    over its process group) — eval mode and every other layer go through their own forward."""
+    over its process group); the same pair in eval mode runs as ct_bn_eval_fwd where autograd records nothing
+    (ops.bn_eval_eligible) — an eval forward with gradients and every other layer go through their own forward."""
     layers = list(module_list)
     i = 0
     while i < len(layers):
         layer = layers[i]
-        if i + 1 < len(layers) and type(layers[i + 1]) is nn.ReLU and ops.bn_relu_eligible(layer, input):
-            last = i + 2 == len(layers)
-            fuse_res = last and residual is not None and residual.shape == input.shape and residual.dtype == input.dtype
+        pair = i + 1 < len(layers) and type(layers[i + 1]) is nn.ReLU
+        fuse_res = (pair and i + 2 == len(layers) and residual is not None and residual.shape == input.shape
+                    and residual.dtype == input.dtype)
+        if pair and not layer.training and ops.bn_eval_eligible(layer, input, residual=residual if fuse_res else None):
+            input = ops.bn_eval(input, layer, relu=True, residual=residual if fuse_res else None)
+            if fuse_res:
+                residual = None
+            i += 2
+        elif pair and ops.bn_relu_eligible(layer, input):
             input = ops.bn_relu(input, layer, relu=True, residual=residual if fuse_res else None)
             if fuse_res:
                 residual = None
@@ -123,12 +130,16 @@ class _MHCTCore(nn.Module):
 
     def _norm_keys_values(self, key_values):
         """key_bn on the first 3H channels, values_bn on the rest (multihead_ct.py:89-91): fused kernels on the slices
-        where they lie when both norms qualify, the modules on split views otherwise (eval mode, ...)."""
+        where they lie when both norms qualify (training: ops.split_bn; eval without gradients: ops.split_bn_eval), the
+        modules on split views otherwise."""
         Ck = self.heads * 3
         Cv = key_values.size(1) - Ck
         if (ops.bn_relu_eligible(self.key_bn, key_values, Ck) and ops.bn_relu_eligible(self.values_bn, key_values, Cv)
                 and ops.norms_share_group([self.key_bn, self.values_bn])):
             return ops.split_bn(key_values, self.key_bn, self.values_bn)
+        if (not self.key_bn.training and ops.bn_eval_eligible(self.key_bn, key_values, Ck)
+                and ops.bn_eval_eligible(self.values_bn, key_values, Cv)):
+            return ops.split_bn_eval(key_values, self.key_bn, self.values_bn)
         k_part, v_part = torch.split(key_values, [Ck, Cv], dim=1)   # backward: one cat
         return self.key_bn(k_part), self.values_bn(v_part)
 
@@ -377,6 +388,8 @@ class MultiHeadUnion(_UnionBase):
                 residual, kvs = ops.union_keys_values(x, convs, kbs, vbs, passthrough=True)
             else:
                 residual, kvs = self.shortcut(x), ops.union_keys_values(x, convs, kbs, vbs)
+        elif ops.union_keys_values_eval_eligible(x, convs, kbs, vbs):      # eval, nothing recorded: same stacking, forward only
+            residual, kvs = self.shortcut(x), ops.union_keys_values_eval(x, convs, kbs, vbs)
         else:
             residual, kvs = self.shortcut(x), None
         for r, s, _ in _run_heads([(lambda a=a, i=i: a._forward_pre(x, orig_pcd, None if kvs is None else kvs[i]))
@@ -388,6 +401,9 @@ class MultiHeadUnion(_UnionBase):
         if (len(pres) > 1 and all(len(n) == 2 and type(n[1]) is nn.ReLU and ops.bn_relu_eligible(n[0], p)
                                   for n, p in zip(norms, pres)) and ops.norms_share_group([n[0] for n in norms])):
             joined = ops.join_bn_relu(pres, [n[0] for n in norms])
+        elif len(pres) > 1 and all(len(n) == 2 and type(n[1]) is nn.ReLU and not n[0].training and ops.bn_eval_eligible(n[0], p)
+                                   for n, p in zip(norms, pres)):
+            joined = ops.join_bn_relu_eval(pres, [n[0] for n in norms])
         else:
             joined = torch.cat([run_after(n, p) for n, p in zip(norms, pres)], dim=1)
         return run_after(self.after, joined, residual), stats

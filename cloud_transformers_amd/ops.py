@@ -1515,6 +1515,175 @@ def bn_relu(x, bn, relu=True, residual=None):
 
 
 # ---------------------------------------------------------------------------
+# eval-mode BatchNorm1d / SyncBatchNorm (+ ReLU, + skip): a per-channel affine on the stored statistics (ct_bn_eval_*)
+# ---------------------------------------------------------------------------
+# Forward only, on purpose: plain functions that save nothing, taken only where autograd would record nothing.  An eval
+# forward WITH gradients keeps the modules' own path.  "0": every eval norm through its module (A/B runs).
+BN_EVAL = os.environ.get("CLOUDCT_BN_EVAL", "1") != "0"
+_bn_eval_supported = {}
+
+
+def _records_nothing(*tensors):
+    """True when autograd would record nothing for an op on `tensors` (None entries skipped)."""
+    return not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in tensors)
+
+
+def _bn_eval_norm_ok(bn, B, C, N):
+    """An eval-mode affine norm of C channels with running statistics whose shape ct_bn_eval_* takes."""
+    if not (type(bn) in _BN_TYPES and not bn.training and bn.affine and bn.track_running_stats
+            and bn.running_mean is not None and bn.running_var is not None and C == bn.num_features
+            and bn.weight.dtype == torch.float32 and bn.running_mean.dtype == torch.float32):
+        return False
+    key = (B, C, N)
+    ok = _bn_eval_supported.get(key)
+    if ok is None:
+        ok = _bn_eval_supported[key] = bool(_lib.load().ct_bn_eval_supported(*key))
+    return ok
+
+
+def bn_eval_eligible(bn, x, channels=None, residual=None):
+    """True when `bn` applied to x (or, with `channels`, to a slice of that many of its channels) can run as
+    ct_bn_eval_fwd: an nn.BatchNorm1d / nn.SyncBatchNorm (exactly) in eval mode, affine, with running statistics; x CUDA
+    fp32 [B,C,N] contiguous and 16-byte aligned; a shape ct_bn_eval_supported takes; and nothing for autograd to record
+    (grad mode off, or none of x, the affine parameters and `residual` requires grad)."""
+    if not (BN_EVAL and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()
+            and x.data_ptr() % 16 == 0):
+        return False
+    if residual is not None and not (residual.is_cuda and residual.dtype == torch.float32 and residual.dim() == 3):
+        return False
+    C = x.size(1) if channels is None else channels
+    return (_bn_eval_norm_ok(bn, x.size(0), C, x.size(2)) and bn.weight.device == x.device
+            and _records_nothing(x, bn.weight, bn.bias, residual))
+
+
+def _bn_eval_item(bn, x_ptr, xbs, y_ptr, ybs, relu, res=None, rbs=0, amax=None):
+    return dict(x=x_ptr, xbs=xbs, C=bn.num_features, w=_f32c(bn.weight.detach()), b=_f32c(bn.bias.detach()),
+                rm=_f32c(bn.running_mean), rv=_f32c(bn.running_var), eps=float(bn.eps), relu=int(bool(relu)),
+                res=res, rbs=rbs, y=y_ptr, ybs=ybs, amax=amax)
+
+
+def _bn_eval_group(items, B, N):
+    """Run eval norms over the same (B, N): ONE ct_bn_eval_group_fwd launch for 2..BN_GROUP_MAX of them, one launch per norm
+    otherwise (a single norm, more than BN_GROUP_MAX, or CLOUDCT_BN_GROUP=0), as _bn_group_fwd.  items: _bn_eval_item dicts."""
+    lib = _lib.load()
+    if 1 < len(items) <= _lib.BN_GROUP_MAX and BN_GROUP_LAUNCH:
+        arr = (_lib.BnFwdItem * len(items))()
+        for e, it in zip(arr, items):
+            e.x, e.x_batch_stride, e.weight, e.bias = it["x"], it["xbs"], _ptr(it["w"]), _ptr(it["b"])
+            e.running_mean, e.running_var = _ptr(it["rm"]), _ptr(it["rv"])
+            e.residual, e.residual_batch_stride, e.y, e.y_batch_stride = it["res"], it["rbs"], it["y"], it["ybs"]
+            e.amax_out, e.C, e.eps, e.relu = it["amax"], it["C"], it["eps"], it["relu"]
+        _lib.check(lib.ct_bn_eval_group_fwd(ctypes.addressof(arr), len(items), B, N, _stream()), "ct_bn_eval_group_fwd")
+        return
+    for it in items:
+        _lib.check(lib.ct_bn_eval_fwd(it["x"], it["xbs"], _ptr(it["w"]), _ptr(it["b"]), _ptr(it["rm"]), _ptr(it["rv"]), it["res"],
+                                      it["rbs"], it["y"], it["ybs"], it["amax"], B, it["C"], N, it["eps"], it["relu"], _stream()),
+                   "ct_bn_eval_fwd")
+
+
+def bn_eval(x, bn, relu=True, residual=None):
+    """relu?(bn(x)) [+ residual] of an eval-mode norm in one pass (ct_bn_eval_fwd); the caller checked
+    bn_eval_eligible(bn, x, residual=residual).  Reads the running statistics, writes nothing but the result, which carries
+    its per-channel maxima for the pointwise GEMM that reads it next."""
+    _dev(x, residual)
+    x = _f32c(x)
+    B, C, N = x.shape
+    y = torch.empty_like(x)
+    rbs = 0
+    if residual is not None:
+        rbs = _batch_stride(residual, C, N)
+        if rbs is None:
+            residual, rbs = _f32c(residual), 0
+    slots = _amax_slots(C, x.device)
+    with _on(x.device):
+        _bn_eval_group([_bn_eval_item(bn, _ptr(x), 0, _ptr(y), 0, relu, _ptr(residual), rbs, _ptr(slots))], B, N)
+    return tag_amax(y, slots)
+
+
+def split_bn_eval(x, bn_a, bn_b):
+    """(bn_a(x[:, :Ca]), bn_b(x[:, Ca:])) of two eval-mode norms in one launch, the halves of x read where they lie; the
+    caller checked bn_eval_eligible for both (each against its own slice's channels)."""
+    _dev(x)
+    x = _f32c(x)
+    B, C, N = x.shape
+    Ca = bn_a.num_features
+    assert bn_b.num_features == C - Ca
+    items, outs = [], []
+    for c0, bn in ((0, bn_a), (Ca, bn_b)):
+        y = torch.empty(B, bn.num_features, N, device=x.device, dtype=torch.float32)
+        items.append(_bn_eval_item(bn, _ptr(x) + c0 * N * 4, C * N, _ptr(y), 0, False))
+        outs.append(y)
+    with _on(x.device):
+        _bn_eval_group(items, B, N)
+    return outs[0], outs[1]
+
+
+def join_bn_relu_eval(xs, bns):
+    """cat([relu(bn(x)) for x, bn in zip(xs, bns)], dim=1) of eval-mode norms: every norm writes its channel range of the
+    result where it belongs, and the result carries one maxima tag over all its channels; the caller checked
+    bn_eval_eligible for every pair."""
+    xs = [_f32c(x) for x in xs]
+    _dev(*xs)
+    B, _, N = xs[0].shape
+    Ct = sum(x.size(1) for x in xs)
+    y = torch.empty(B, Ct, N, device=xs[0].device, dtype=torch.float32)
+    slots = _amax_slots(Ct, y.device)
+    items, c0 = [], 0
+    for x, bn in zip(xs, bns):
+        items.append(_bn_eval_item(bn, _ptr(x), 0, _ptr(y) + c0 * N * 4, Ct * N, True,
+                                   amax=None if slots is None else _ptr(slots) + 4 * c0))
+        c0 += x.size(1)
+    with _on(y.device):
+        _bn_eval_group(items, B, N)
+    return tag_amax(y, slots)
+
+
+def union_keys_values_eval_eligible(x, convs, key_bns, values_bns):
+    """Plain bias-free 1x1 Conv1d projections of the same input, eval-mode norms ct_bn_eval_* takes, and nothing for
+    autograd to record."""
+    if not (BN_EVAL and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()
+            and x.data_ptr() % 16 == 0 and len(convs) > 1):
+        return False
+    watched = [x]
+    for conv, kb, vb in zip(convs, key_bns, values_bns):
+        if not (isinstance(conv, torch.nn.Conv1d) and conv.kernel_size == (1,) and conv.stride == (1,) and conv.padding == (0,)
+                and conv.dilation == (1,) and conv.groups == 1 and conv.bias is None and conv.in_channels == x.size(1)
+                and conv.out_channels == kb.num_features + vb.num_features and conv.weight.dtype == torch.float32):
+            return False
+        for bn in (kb, vb):
+            if not (_bn_eval_norm_ok(bn, x.size(0), bn.num_features, x.size(2)) and bn.weight.device == x.device):
+                return False
+            watched += [bn.weight, bn.bias]
+        if conv.weight.device != x.device:
+            return False
+        watched.append(conv.weight)
+    return _records_nothing(*watched)
+
+
+def union_keys_values_eval(x, convs, key_bns, values_bns):
+    """[(key_bn_i(y_i[:, :Ck]), values_bn_i(y_i[:, Ck:])) with y_i = conv_i(x)] for the heads of a union block in eval mode:
+    ONE stacked projection GEMM, then the 2n norms on its channel ranges in one launch (2n <= BN_GROUP_MAX); the caller
+    checked union_keys_values_eval_eligible."""
+    x = _f32c(x)
+    _dev(x)
+    B, _, N = x.shape
+    Wc = torch.cat([conv.weight.detach()[:, :, 0] for conv in convs], dim=0)        # [sum Co, Cin]
+    Ct = Wc.size(0)
+    y = pw_forward(Wc, x)[0]                                                        # [B, sum Co, N]
+    items, outs, c0 = [], [], 0
+    for kb, vb in zip(key_bns, values_bns):
+        for bn in (kb, vb):
+            o = torch.empty(B, bn.num_features, N, device=x.device, dtype=torch.float32)
+            items.append(_bn_eval_item(bn, _ptr(y) + c0 * N * 4, Ct * N, _ptr(o), 0, False))
+            outs.append(o)
+            c0 += bn.num_features
+    assert c0 == Ct, "key_bn + values_bn must cover the projections"
+    with _on(x.device):
+        _bn_eval_group(items, B, N)
+    return [(outs[2 * i], outs[2 * i + 1]) for i in range(len(convs))]
+
+
+# ---------------------------------------------------------------------------
 # functional entry points
 # ---------------------------------------------------------------------------
 def positions(keys, tensor_size, heads, dim):

@@ -385,6 +385,27 @@ int ct_bn_apply_bwd_amax(const float* x, long long x_batch_stride, const float* 
                          const float* sum_g, const float* sum_gxhat, const float* count, float* gx,
                          long long gx_batch_stride, float* amax_out, int B, int C, int N, int relu, ct_stream_t s);
 
+/* Eval-mode BatchNorm1d / SyncBatchNorm (+ ReLU, + skip): a per-channel affine on the stored statistics, forward only,
+ *   y[b,c,n] = relu?( ((x - running_mean[c]) * rstd_c) * weight[c] + bias[c] ) [+ residual[b,c,n]],
+ *   rstd_c = 1 / sqrt(running_var[c] + eps)
+ * in torch's operation order (the mean is subtracted first).  x, y, residual and their batch strides as ct_bn_relu_fwd (0 =
+ * contiguous; a channel slice of a wider tensor is read, a channel range of a concatenation written, where it lies); y does
+ * not overlap x or residual.  Rows that are 16-byte addressable (N % 4 == 0, strides % 4 == 0, aligned bases) move as
+ * float4, all others float by float.  Nothing is written but y and amax_out f32[C] (nullable): max |y| per channel of the
+ * values as stored (after ReLU and skip), the contract of ct_bn_relu_fwd_amax; the running statistics are read-only here
+ * and both are required.  Shapes: B*N >= 1 (one value per channel is legal: no variance is taken), B*N < 2^31
+ * (ct_bn_eval_supported != 0).  Channels are cut over several workgroups when the launch has few of them; a channel
+ * whose amax_out is asked for stays with one workgroup, which folds the maximum itself (no second launch, no atomics).
+ * ct_bn_eval_group_fwd: n <= 8 norms over the same (B, N) in one launch, as ct_bn_group_fwd; of ct_bn_fwd_item it reads x,
+ * weight, bias, running_mean, running_var, residual, y, amax_out, the strides, C, eps and relu — save_mean, save_rstd,
+ * momentum and num_batches_tracked are ignored and may be null.  Added under CT_ABI_VERSION 2 (additive). */
+int ct_bn_eval_supported(int B, int C, int N);
+int ct_bn_eval_fwd(const float* x, long long x_batch_stride, const float* weight, const float* bias,
+                   const float* running_mean, const float* running_var, const float* residual,
+                   long long residual_batch_stride, float* y, long long y_batch_stride, float* amax_out,
+                   int B, int C, int N, float eps, int relu, ct_stream_t s);
+int ct_bn_eval_group_fwd(const ct_bn_fwd_item* items, int n, int B, int N, ct_stream_t s);
+
 /* ------------------------------------------------------------------------
  * Adaptive instance normalisation of the AdaIN blocks (AdaIn1dUpd: layers/utils.py:82-97 =
  * InstanceNorm1d(affine=False, eps) -> * (gamma + 1) -> + beta; followed by ReLU in `after`,
