@@ -15,7 +15,10 @@ package's layers and checkpoints stay interchangeable.
   indoor3d_sem_seg_hdf5_data directory), items equal to the reference loaders' under the same seeds.  `s3dis_kpconv`
   (`data.path` = the Stanford3dDataset_v1.2 folder) selects the `segmentation_kpconv` task: sphere items sampled on the
   device, masked cross-entropy with gradient clipping, vote validation and per-epoch checkpoints (train_kpconv.py,
-  train_segmentation_kpconv.py).  The remaining dataset variants (GRNet completion, image_point) stay out of scope.
+  train_segmentation_kpconv.py).  `shapenet_completion` (the `completion` task; `data.category_path`, `data.partial_path`,
+  `data.gt_path`, `data.n_renders`, `data.input_size`, `data.gt_size` as configs/inpainting.yaml has them) reads the
+  ShapeNetCompletion .pcd files (data/completion.py) and prepares every batch on the device; one validation per epoch
+  (train_completion.py, train_inpainter.py).  The image_point variant stays out of scope.
 """
 import copy
 import datetime
@@ -175,9 +178,14 @@ class SyntheticClouds(torch.utils.data.Dataset):
 
 def make_dataset(cfg, task, n_classes, length=64, channels=3, train=True):
     """The dataset `data.kind` of the config names: "synthetic" (default), "scanobjectnn" or "s3dis" (data/datasets.py);
-    "s3dis_kpconv" gives the (train, validation) Areas of train_kpconv.load_kpconv_areas (`train=False`: no train Areas)."""
+    "s3dis_kpconv" gives the (train, validation) Areas of train_kpconv.load_kpconv_areas (`train=False`: no train Areas);
+    "shapenet_completion" the TRAIN (`train=False`: VAL) subset of data/completion.py's ShapeNetDataLoader."""
     data = cfg["data"]
     kind = str(data.get("kind", "synthetic")).lower()
+    if kind == "shapenet_completion":
+        assert task == "completion", "ShapeNet completion items are (partial cloud, complete cloud): the completion task"
+        from .data.completion import DatasetSubset, shapenet_loader
+        return shapenet_loader(data).get_dataset(DatasetSubset.TRAIN if train else DatasetSubset.VAL)
     if kind == "s3dis_kpconv":
         assert task == "segmentation_kpconv", "S3DIS KPConv items are (points, mask, features, labels): the segmentation_kpconv task"
         from .train_kpconv import load_kpconv_areas
@@ -193,7 +201,7 @@ def make_dataset(cfg, task, n_classes, length=64, channels=3, train=True):
         assert task == "segmentation", "S3DIS blocks are (points, labels): the segmentation task"
         return D.Indoor3DSemSeg(data["path"], data["num_points"], train=train, aug=bool(data.get("aug", train)),
                                 test_area=data.get("test_area", "Area_5"), data_precent=float(data.get("data_precent", 1.0)))
-    raise ValueError("data.kind must be synthetic, scanobjectnn, s3dis or s3dis_kpconv (got %r)" % kind)
+    raise ValueError("data.kind must be synthetic, scanobjectnn, s3dis, s3dis_kpconv or shapenet_completion (got %r)" % kind)
 
 
 class Trainer:
@@ -206,7 +214,9 @@ class Trainer:
     `n_classes` is then the size of the partial cloud) or "segmentation_kpconv" (selected by `data.kind: s3dis_kpconv` too:
     loss = sum(CE * mask) / sum(mask) of model(points, mask, features), gradients clipped to `train.clip_grad_norm` (10),
     validation every `train.val_step` epochs and after the last, `generator_epoch_{e}.t7` / `g_opt_epoch_{e}.t7` every
-    `train.save_each_epoch` epochs; `dataset` may be the (train, validation) Areas — train_kpconv.py)."""
+    `train.save_each_epoch` epochs; `dataset` may be the (train, validation) Areas — train_kpconv.py).  With `data.kind:
+    shapenet_completion` the completion task's batches are prepared on the device (data/completion.py CompletionBatches)
+    and `fit` validates once per epoch (`validate`)."""
 
     def __init__(self, cfg, task, n_classes, device=None, dist=None, exp_name="exp", dataset_length=64, make_dirs=True,
                  channels=3, dataset=None):
@@ -263,7 +273,16 @@ class Trainer:
         # `dataset`: any torch Dataset whose items have the task's layout; else what `data.kind` of the config names
         data = dataset if dataset is not None else make_dataset(cfg, task, n_classes, length=dataset_length, channels=channels)
         self.kp, self.clip, self.val_records = None, None, []
-        if task == "segmentation_kpconv":
+        self.shapenet, self.val_loader, self.best_val = str(cfg["data"].get("kind", "")).lower() == "shapenet_completion", None, None
+        if self.shapenet:
+            from .data.completion import CompletionBatches
+            assert task == "completion", "data.kind shapenet_completion is the completion task"
+            self.sampler = torch.utils.data.distributed.DistributedSampler(data) if parallel._active(dist) else None
+            self.loader = CompletionBatches(data, cfg["data"]["batch_size"], self.device, seed=int(cfg["data"].get("seed", 0)),
+                                            rank=self.rank, shuffle=True, drop_last=bool(cfg["data"].get("drop_last", True)),
+                                            num_workers=int(cfg["data"].get("num_workers", 0)), sampler=self.sampler,
+                                            worker_init_fn=worker_init_fn)
+        elif task == "segmentation_kpconv":
             from .train_kpconv import KPConvData
             # one iteration over the loader is one epoch of device batches (a plan of sphere picks, sharded over the ranks)
             self.kp = self.loader = KPConvData(cfg, self.device, dist, areas=data)
@@ -311,10 +330,69 @@ class Trainer:
             parallel.save_exp_parallel([self.model, self.optimizer], ["generator", "g_opt"], exp_path=self.exp_dir,
                                        epoch=self.iters if epoch is None else epoch, epoch_name="iter" if epoch is None else "epoch")
 
-    def validate(self, num_votes, epoch):
-        """segmentation_kpconv: one validation of `num_votes` vote passes (train_kpconv.KPConvData.validate) on the unwrapped
-        model; the records go to the writer and, on rank 0, to <exp>/kpconv_val.jsonl.  Returns them."""
+    def _validate_completion(self, epoch, dataset=None):
+        """train_inpainter.py:253-311: eval mode, no grad, the VAL subset in batches of `data.batch_size_val`; per batch
+        sqrt(EMD(rec, gt, val_emd_eps, val_emd_iters)).mean(1).mean() and loss_chamfer, averaged over the batches and the
+        ranks (sums and the count stay on the device until the one read at the end)."""
         import json
+        from .chamfer import loss_chamfer
+        from .data.completion import CompletionBatches
+        from .emd import emdModule
+        cfg, tr = self.cfg, self.cfg["train"]
+        if self.val_loader is None or dataset is not None:
+            data = dataset if dataset is not None else make_dataset(cfg, "completion", None, train=False)
+            smp = torch.utils.data.distributed.DistributedSampler(data, shuffle=False) if parallel._active(self.dist) else None
+            self.val_loader = CompletionBatches(data, cfg["data"].get("batch_size_val", cfg["data"]["batch_size"]), self.device,
+                                                seed=int(cfg["data"].get("seed", 0)) + 7919, rank=self.rank, sampler=smp,
+                                                num_workers=int(cfg["data"].get("num_workers", 0)), worker_init_fn=worker_init_fn)
+        eps, iters = float(tr.get("val_emd_eps", 0.004)), int(tr.get("val_emd_iters", 3000))
+        w = float(tr.get("chamfer_weight", 1.0))
+        model = self.model
+        was_training = model.training
+        model.eval()
+        self.val_loader.set_epoch(epoch if isinstance(epoch, int) else 0)
+        sums = torch.zeros(4, dtype=torch.float64, device=self.device)            # loss, loss_emd, loss_chamfer, batches
+        with torch.no_grad():
+            for noise, part, gt in self.val_loader:
+                out = model(noise, part.permute(0, 2, 1)[:, :, None])
+                rec = out[0] if isinstance(out, (tuple, list)) else out
+                gt4 = gt.permute(0, 2, 1)[:, :, None]
+                dist, _ = emdModule()(rec[:, :, 0].permute(0, 2, 1), gt4[:, :, 0].permute(0, 2, 1), eps, iters)
+                l_emd = torch.sqrt(dist).mean(1).mean()
+                l_cd = loss_chamfer(rec, gt4)
+                sums += torch.stack([l_emd + w * l_cd, l_emd, l_cd, torch.ones_like(l_cd)]).double()
+        model.train(was_training)
+        if parallel._active(self.dist):
+            self.dist.all_reduce(sums)
+        s = sums.tolist()
+        n = max(s[3], 1.0)
+        rec = {"epoch": epoch, "iters": self.iters, "batches": int(s[3]), "loss": s[0] / n, "loss_emd": s[1] / n,
+               "loss_chamfer": s[2] / n}
+        best = self.best_val is None or rec["loss"] < self.best_val
+        rec["best"] = bool(best)
+        if best:
+            self.best_val = rec["loss"]
+        if self.rank == 0:
+            step = epoch if isinstance(epoch, int) else self.iters
+            for k in ("loss", "loss_emd", "loss_chamfer"):
+                self.writer.add_scalar("val/val_" + k, rec[k], global_step=step)
+            if self.exp_dir is not None:
+                with open(str(Path(self.exp_dir) / "completion_val.jsonl"), "a") as f:
+                    f.write(json.dumps(rec) + "\n")
+                if best:
+                    parallel.save_exp_parallel([self.model, self.optimizer], ["generator", "g_opt"], exp_path=self.exp_dir,
+                                               epoch=0, epoch_name="best")
+        self.val_records.append(rec)
+        return [rec]
+
+    def validate(self, num_votes=None, epoch=None):
+        """segmentation_kpconv: one validation of `num_votes` vote passes (train_kpconv.KPConvData.validate) on the unwrapped
+        model; the records go to the writer and, on rank 0, to <exp>/kpconv_val.jsonl.  Returns them.
+        completion (`num_votes` is not used): one pass over the VAL subset (`_validate_completion`), its record appended to
+        <exp>/completion_val.jsonl and, on a new minimum of the loss, `generator_best_0.t7` / `g_opt_best_0.t7` saved."""
+        import json
+        if self.task == "completion":
+            return self._validate_completion(epoch)
         records = self.kp.validate(parallel._plain_module(self.model), num_votes, epoch)
         if self.rank == 0:
             for rec in records:
@@ -489,6 +567,9 @@ class Trainer:
                     self.validate(int(tr["val_votes"]), e)
                 if e % int(tr["save_each_epoch"]) == 0:
                     self.save(epoch=e)
+            if self.shapenet:
+                flush()
+                self.validate(epoch=epoch)                # train_inpainter.py:253-311: once per epoch
         flush()
         if self.kp is not None:
             self.validate(int(tr["final_votes"]), "Last")

@@ -1,0 +1,135 @@
+"""Training and evaluation of the ShapeNet completion protocol (train_inpainter.py, eval_inpainting.py) on the device: the
+`completion` task of `harness.Trainer` on `data.kind: shapenet_completion`.
+
+    python -m cloud_transformers_amd.train_completion EXP -c configs/inpainting.yaml [--gpus N] [--eval]
+
+The config is the reference's YAML as it is (`data.category_path`, `data.partial_path`, `data.gt_path`, `data.n_renders`,
+`data.input_size`, `data.gt_size`, `data.batch_size`, `data.batch_size_val`); `data.kind` is filled in.
+
+- training: batches prepared on the device (data/completion.py CompletionBatches), EMD + Chamfer loss, one validation per
+  epoch (`Trainer.validate`: <exp>/completion_val.jsonl, `generator_best_0.t7` on a new minimum).
+- `--eval` (eval_inpainting.py:163-226): restore `restore.generator`, then the TEST subset in batches of one: dense =
+  reconstruction / 2, `Metrics.get` (F-Score@0.01, Chamfer x 1000) and the dense Chamfer loss x 1000 per sample, averaged
+  per taxonomy and overall; the table is printed and written to <exp>/completion_test.json.
+- `--gpus N > 1`: N ranks through `launch.spawn_ranks`, one process group over RCCL (training only)."""
+import argparse
+import copy
+import json
+import os
+import sys
+
+import torch
+
+COMPLETION_DATA = {"kind": "shapenet_completion", "n_renders": 1, "input_size": 2048, "gt_size": 16384, "seed": 0}
+COMPLETION_TRAIN = {"val_emd_eps": 0.004, "val_emd_iters": 3000, "emd_eps": 0.005, "emd_iters": 50}
+
+
+def completion_config(cfg):
+    """A copy of `cfg` with the protocol's defaults (train_inpainter.py:186-192, :267-269) under the keys it lacks;
+    `data.batch_size_val` defaults to `data.batch_size`."""
+    cfg = copy.deepcopy(cfg)
+    for key, defaults in (("data", COMPLETION_DATA), ("train", COMPLETION_TRAIN)):
+        sect = cfg.setdefault(key, {})
+        for k, v in defaults.items():
+            sect.setdefault(k, v)
+    cfg["data"].setdefault("batch_size_val", cfg["data"].get("batch_size", 1))
+    return cfg
+
+
+def evaluate(model, cfg, device, exp_dir=None, generator=None, verbose=True):
+    """test_net of eval_inpainting.py:132-230 -> {"names": metric names, "taxonomies": {id: {"count", "avg"}}, "overall":
+    {"count", "avg"}, "dense_loss": mean dense Chamfer x 1000}; printed as the reference prints it and, with `exp_dir`,
+    written to <exp_dir>/completion_test.json."""
+    from .data.completion import DatasetSubset, collate_fn, completion_items, shapenet_loader
+    from .metrics import AverageMeter, ChamferDistance, Metrics
+    ds = shapenet_loader(cfg["data"]).get_dataset(DatasetSubset.TEST)
+    loader = torch.utils.data.DataLoader(ds, batch_size=1, num_workers=int(cfg["data"].get("num_workers", 0)), collate_fn=collate_fn,
+                                         shuffle=False)
+    if generator is None:
+        generator = torch.Generator(device=device).manual_seed(int(cfg["data"].get("seed", 0)) * 1000003 + 104729)
+    was_training = model.training
+    model.eval()
+    chamfer_dist = ChamferDistance()
+    test_losses, test_metrics, category_metrics = AverageMeter(["DenseLoss"]), AverageMeter(Metrics.names()), {}
+    with torch.no_grad():
+        for taxonomy_id, model_id, data in loader:
+            taxonomy_id = taxonomy_id[0] if isinstance(taxonomy_id[0], str) else taxonomy_id[0].item()
+            gt = data["gtcloud"].to(device)
+            part, noise, _ = completion_items(data["partial_cloud"].to(device), gt.shape[1], scale=2.0, generator=generator)
+            out = model(noise, part.permute(0, 2, 1)[:, :, None])
+            rec = out[0] if isinstance(out, (tuple, list)) else out
+            dense = (rec / 2)[:, :, 0].permute(0, 2, 1).contiguous()
+            test_losses.update([chamfer_dist(dense, gt).item() * 1000])
+            m = Metrics.get(dense, gt)
+            test_metrics.update(m)
+            category_metrics.setdefault(taxonomy_id, AverageMeter(Metrics.names())).update(m)
+    model.train(was_training)
+    res = {"names": Metrics.names(),
+           "taxonomies": {str(t): {"count": am.count(0), "avg": am.avg()} for t, am in category_metrics.items()},
+           "overall": {"count": test_metrics.count(0), "avg": test_metrics.avg()},
+           "dense_loss": test_losses.avg(0)}
+    if verbose:
+        print("============================ TEST RESULTS ============================")
+        print("\t".join(["Taxonomy", "#Sample"] + res["names"]))
+        for t, row in res["taxonomies"].items():
+            print("\t".join([t, str(row["count"])] + ["%.4f" % v for v in row["avg"]]))
+        print("\t".join(["Overall", str(res["overall"]["count"])] + ["%.4f" % v for v in res["overall"]["avg"]]))
+    if exp_dir is not None:
+        with open(os.path.join(str(exp_dir), "completion_test.json"), "w") as f:
+            json.dump(res, f, indent=1)
+    return res
+
+
+def _parse(argv):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("exp_name")
+    ap.add_argument("-c", "--config", required=True)
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--eval", action="store_true", help="restore restore.generator, then the per-taxonomy table of the TEST subset")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    """Train one experiment (returns the validation records of this rank) or, with --eval, evaluate it (returns the table)."""
+    from . import harness, launch, parallel
+    argv = list(sys.argv[1:] if argv is None else argv)
+    args = _parse(argv)
+    if args.gpus > 1 and not args.eval and not launch.under_launcher():
+        rest = [a for i, a in enumerate(argv) if a != "--gpus" and (i == 0 or argv[i - 1] != "--gpus") and not a.startswith("--gpus=")]
+        cfg = harness.load_config(args.config)
+        rc = launch.spawn_ranks(os.path.abspath(__file__), rest, args.gpus, capture=bool(cfg.get("train", {}).get("hip_graph", False)))
+        if rc != 0:
+            raise SystemExit(rc)
+        return []
+    dist = None
+    if launch.under_launcher():
+        import torch.distributed as dist
+        local = int(os.environ.get("LOCAL_RANK", "0"))
+        torch.cuda.set_device(local)
+        dist.init_process_group("nccl", rank=int(os.environ["RANK"]), world_size=int(os.environ["WORLD_SIZE"]),
+                                device_id=torch.device("cuda", local))
+    try:
+        cfg = completion_config(harness.load_config(args.config))
+        n_in = int(cfg["data"]["input_size"])
+        if args.eval:
+            if "generator" not in cfg.get("restore", {}):
+                raise SystemExit("--eval needs restore.generator in the config")
+            from .data.completion import DatasetSubset, shapenet_loader
+            tr = harness.Trainer(cfg, "completion", n_in, dist=dist, exp_name=args.exp_name,
+                                 dataset=shapenet_loader(cfg["data"]).get_dataset(DatasetSubset.TEST))
+            return evaluate(parallel._plain_module(tr.model), cfg, tr.device, exp_dir=tr.exp_dir)
+        tr = harness.Trainer(cfg, "completion", n_in, dist=dist, exp_name=args.exp_name)
+        tr.fit()
+        return tr.val_records
+    finally:
+        if dist is not None:
+            dist.destroy_process_group()
+
+
+if __name__ == "__main__":
+    if __package__ in (None, ""):            # started as a file by launch.spawn_ranks
+        sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+        from cloud_transformers_amd.train_completion import main as _main
+        _main()
+    else:
+        main()

@@ -32,7 +32,7 @@ extern "C" {
  * removed, since version 1 — a stale library selected by CLOUDCT_LIB fails this check instead of failing at symbol binding.
  * (The test-hook flag CT_DEBUG_NO_WIDE was added later without a bump: an additive debug bit, no symbol or signature changed.
  * The neighbour-search entry points ct_nbr_* and the item assembly ct_kp_items were added under version 2 as well: additive
- * symbols, which the loader's missing-symbol scan checks.) */
+ * symbols, which the loader's missing-symbol scan checks.  ct_completion_items was added the same way.) */
 #define CT_ABI_VERSION 2
 
 /* status codes */
@@ -707,6 +707,31 @@ int ct_kp_items(const int64_t* qidx, const int64_t* count, const int64_t* perm, 
                 int64_t M, const float* color_mean, const float* color_std, const float* R, const float* s, const float* j,
                 int B, int N, int F, float* out_points, int32_t* mask, float* features, int64_t* out_labels,
                 int64_t* input_inds, ct_stream_t st);
+
+/* ------------------------------------------------------------------------
+ * Batch assembly of the ShapeNet completion items (utils/pcd_utils.py:24-51, partial_postproces,
+ * fed `scale * partial` as train_inpainter.py:180 feeds it 2 * partial), one launch, every random
+ * draw passed in.  Added under CT_ABI_VERSION 2 (additive, as ct_nbr_* and ct_kp_items).
+ *
+ * B clouds (1 <= B <= 65535) of n_in rows (1 <= n_in <= 16384), gt columns (n_in <= gt <= 2^24).
+ * Inputs (device): partial f32[B,n_in,3] (zero rows are padding), perm i64[B,n_in] (a permutation of
+ * 0..n_in-1 per cloud: the argsort of plain random keys), u_dup f32[B,n_in] in [0,1), sphere
+ * f32[B,3,gt] (candidate noise points); scale: host float, finite and non-zero.
+ * With q_i = scale * partial[b,i] (one fp32 multiply): row i is valid unless q_i.x == 0 && q_i.y == 0
+ * && q_i.z == 0 (IEEE ==: -0 is zero, a NaN row is valid); v = count[b] = the number of valid rows;
+ * c[0..v) = the valid q_i in ascending i.  Outputs: part f32[B,n_in,3]: for j < v the j-th valid row
+ * met walking perm[b,0], perm[b,1], ...; for j >= v, c[k] with k = clamp((int)floorf(u_dup[b,j] *
+ * (float)v), 0, v-1).  noise f32[B,4,gt]: columns m < gt-v are sphere[b,:,m] with label 0, columns
+ * m >= gt-v are c[m-(gt-v)] with label 1.  count i32[B].
+ * v == 0 (the reference raises there: randint with high <= 0): part[b] is all zeros, noise[b] is all
+ * sphere columns with label 0 and count[b] = 0; callers can look at count.  perm entries outside
+ * 0..n_in-1 are clamped into range as a guard; when perm is not a permutation, rows of part below v
+ * may be left unwritten, nothing is written out of bounds.
+ * Null pointers, sizes outside the limits and a zero or non-finite scale -> CT_EINVAL before anything
+ * touches the device.
+ * ---------------------------------------------------------------------- */
+int ct_completion_items(const float* partial, const int64_t* perm, const float* u_dup, const float* sphere, float scale,
+                        int B, int n_in, int64_t gt, float* part, float* noise, int32_t* count, ct_stream_t s);
 
 #ifdef __cplusplus
 }
