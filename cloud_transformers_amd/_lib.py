@@ -63,7 +63,7 @@ class AdainBwdItem(ctypes.Structure):
                 ("gamma_beta_batch_stride", ctypes.c_longlong)]
 
 
-ABI_VERSION = 2      # CT_ABI_VERSION of include/cloudct.h
+ABI_VERSION = 3      # CT_ABI_VERSION of include/cloudct.h
 BN_GROUP_MAX = 8
 CT_OK = 0
 REDUCE = {"max": 0, "sum": 1}
@@ -250,35 +250,18 @@ SIGNATURES = {
     "ct_lattice_so3_bwd": (_i, [_vp, _vp, _vp, _f] + [_vp] * 14 + [_vp, _sz, _i, _i, _i, _i, _vp]),
     "ct_so3_exp_fwd": (_i, [_vp, _vp, _i, _f, _vp]),
     "ct_so3_exp_bwd": (_i, [_vp, _vp, _vp, _i, _f, _vp]),
-    "ct_adain_fwd": (_i, [_vp, _ll, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _i, _i, _i, _f, _i, _vp]),
-    "ct_adain_bwd": (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _i, _i, _i, _i, _vp]),
-    "ct_adain_fwd_amax": (_i, [_vp, _ll, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _vp, _ll, _i, _i, _i, _f, _i, _vp]),
-    "ct_adain_bwd_amax": (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _ll, _i, _i, _i, _i, _vp]),
-    "ct_bn_relu_supported": (_i, [_i, _i, _i]),
-    "ct_bn_relu_fwd": (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp]),
-    "ct_bn_relu_bwd": (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _i, _i, _i, _i, _vp]),
     "ct_adain_group_fwd": (_i, [_vp, _i, _i, _i, _vp]),
     "ct_adain_group_bwd": (_i, [_vp, _i, _i, _i, _vp]),
+    "ct_bn_relu_supported": (_i, [_i, _i, _i]),
     "ct_bn_group_fwd": (_i, [_vp, _i, _i, _i, _vp]),
     "ct_bn_group_bwd": (_i, [_vp, _i, _i, _i, _vp]),
-    "ct_bn_group_stats_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp]),
-    "ct_bn_group_apply_fwd": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
-    "ct_bn_group_reduce_bwd": (_i, [_vp, _i, _i, _i, _vp, _vp]),
-    "ct_bn_group_reduce_bwd_copy": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
-    "ct_bn_group_apply_bwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
-    "ct_bn_relu_fwd_amax": (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp]),
-    "ct_bn_relu_bwd_amax": (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    # the exchange phases: (items, n, first, run, B, N, ...) - the whole group's table, the run of items to launch
+    "ct_bn_group_stats_fwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ct_bn_group_apply_fwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "ct_bn_group_reduce_bwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "ct_bn_group_apply_bwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ct_bn_eval_supported": (_i, [_i, _i, _i]),
-    "ct_bn_eval_fwd": (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _i, _i, _i, _f, _i, _vp]),
     "ct_bn_eval_group_fwd": (_i, [_vp, _i, _i, _i, _vp]),
-    "ct_bn_stats_fwd": (_i, [_vp, _ll, _vp, _vp, _vp, _i, _i, _i, _vp]),
-    "ct_bn_apply_fwd": (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _vp, _i, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _vp,
-                             _i, _i, _i, _f, _f, _i, _vp]),
-    "ct_bn_reduce_bwd": (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ct_bn_apply_bwd": (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _vp]),
-    "ct_bn_apply_fwd_amax": (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _vp, _i, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _vp,
-                                  _vp, _i, _i, _i, _f, _f, _i, _vp]),
-    "ct_bn_apply_bwd_amax": (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _i, _i, _i, _i, _vp]),
     "ct_gconv_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _ip, _vp]),
     "ct_gconv_bwd_data": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _ip, _vp]),
     "ct_gconv_supported": (_i, [_i, _i, _i, _i, _i, _ip]),

@@ -392,23 +392,8 @@ static int adain_fwd_launch_table(AdainTable& t, bool vec, hipStream_t stream) {
   return CT_OK;
 }
 
-static int adain_fwd_impl(const float* x, long long x_batch_stride, const float* gamma_beta, const float* residual,
-                          long long residual_batch_stride, float* y, long long y_batch_stride, float* mean, float* rstd,
-                          float* amax_out, long long amax_batch_stride, int B, int C, int N, float eps, int relu, ct_stream_t s) {
-  if (B < 0 || C < 0 || N < 0 || !(eps >= 0.0f)) return CT_EINVAL;
-  if ((size_t)B * C == 0 || N == 0) return CT_OK;
-  if ((size_t)B * C > 0x7fffffffull) return CT_EINVAL;
-  AdainArgs a{x, gamma_beta, mean, rstd, B, C, N, eps, relu, 0, 0, residual, 0, amax_out, amax_batch_stride ? amax_batch_stride : C,
-              2LL * C};
-  bool vec;
-  const int rc = adain_fwd_prepare(a, y, x_batch_stride, y_batch_stride, residual_batch_stride, vec);
-  if (rc != CT_OK) return rc;
-  AdainTable t{};
-  t.n = 1; t.rstart[0] = 0; t.rstart[1] = B * C; t.item[0] = a; t.y[0] = y;
-  return adain_fwd_launch_table(t, vec, (hipStream_t)s);
-}
-
-// Up to kAdainMaxItems norms over the same (B, N) in one launch: ct_adain_fwd_amax of every item (non-empty shapes only).
+// Up to kAdainMaxItems norms over the same (B, N) in one launch (non-empty shapes only: the caller owns the empty ones);
+// a single norm is a table with n = 1.
 extern "C" int ct_adain_group_fwd(const ct_adain_fwd_item* items, int n, int B, int N, ct_stream_t s) {
   if (!items || n < 1 || n > kAdainMaxItems || B < 1 || N < 1) return CT_EINVAL;
   AdainTable t{};
@@ -436,23 +421,6 @@ extern "C" int ct_adain_group_fwd(const ct_adain_fwd_item* items, int n, int B, 
   return adain_fwd_launch_table(t, vec_all, (hipStream_t)s);
 }
 
-extern "C" int ct_adain_fwd(const float* x, long long x_batch_stride, const float* gamma_beta, const float* residual,
-                            long long residual_batch_stride, float* y, long long y_batch_stride, float* mean, float* rstd,
-                            int B, int C, int N, float eps, int relu, ct_stream_t s) {
-  return adain_fwd_impl(x, x_batch_stride, gamma_beta, residual, residual_batch_stride, y, y_batch_stride, mean, rstd, nullptr, 0,
-                        B, C, N, eps, relu, s);
-}
-
-// with amax_out f32 (nullable): amax_out[b * amax_batch_stride + c] = max |y| of row (b, c); stride 0 = C
-extern "C" int ct_adain_fwd_amax(const float* x, long long x_batch_stride, const float* gamma_beta, const float* residual,
-                                 long long residual_batch_stride, float* y, long long y_batch_stride, float* mean, float* rstd,
-                                 float* amax_out, long long amax_batch_stride, int B, int C, int N, float eps, int relu,
-                                 ct_stream_t s) {
-  if (amax_batch_stride != 0 && amax_batch_stride < C) return CT_EINVAL;
-  return adain_fwd_impl(x, x_batch_stride, gamma_beta, residual, residual_batch_stride, y, y_batch_stride, mean, rstd, amax_out,
-                        amax_batch_stride, B, C, N, eps, relu, s);
-}
-
 static int adain_bwd_prepare(AdainBwdArgs& a, long long x_batch_stride, long long gy_batch_stride, long long gx_batch_stride,
                              bool& vec) {
   if (!a.x || !a.gy || !a.gx || !a.gamma_beta || !a.mean || !a.rstd || !a.g_gamma_beta) return CT_EINVAL;
@@ -473,26 +441,6 @@ static int adain_bwd_launch_table(AdainBwdTable& t, bool vec, hipStream_t stream
   }
   CT_CHECK_LAUNCH();
   return CT_OK;
-}
-
-static int adain_bwd_impl(const float* x, long long x_batch_stride, const float* gamma_beta, const float* mean,
-                          const float* rstd, const float* gy, long long gy_batch_stride, float* gx,
-                          long long gx_batch_stride, float* g_gamma_beta, float* amax_out, long long amax_batch_stride, int B, int C,
-                          int N, int relu, ct_stream_t s) {
-  hipStream_t stream = (hipStream_t)s;
-  if (B < 0 || C < 0 || N < 0) return CT_EINVAL;
-  if ((size_t)B * C == 0) return CT_OK;
-  if (!gamma_beta || !mean || !rstd || !g_gamma_beta) return CT_EINVAL;
-  if ((size_t)B * C > 0x7fffffffull) return CT_EINVAL;
-  if (N == 0) return hipMemsetAsync(g_gamma_beta, 0, (size_t)B * 2 * C * sizeof(float), stream) == hipSuccess ? CT_OK : CT_ELAUNCH;
-  AdainBwdArgs a{x, gamma_beta, mean, rstd, gy, gx, g_gamma_beta, B, C, N, relu, 0, 0, 0, amax_out,
-                 amax_batch_stride ? amax_batch_stride : C, 2LL * C};
-  bool vec;
-  const int rc = adain_bwd_prepare(a, x_batch_stride, gy_batch_stride, gx_batch_stride, vec);
-  if (rc != CT_OK) return rc;
-  AdainBwdTable t{};
-  t.n = 1; t.rstart[0] = 0; t.rstart[1] = B * C; t.item[0] = a;
-  return adain_bwd_launch_table(t, vec, stream);
 }
 
 extern "C" int ct_adain_group_bwd(const ct_adain_bwd_item* items, int n, int B, int N, ct_stream_t s) {
@@ -519,21 +467,4 @@ extern "C" int ct_adain_group_bwd(const ct_adain_bwd_item* items, int n, int B, 
   }
   t.rstart[n] = (int)r0;
   return adain_bwd_launch_table(t, vec_all, (hipStream_t)s);
-}
-
-extern "C" int ct_adain_bwd(const float* x, long long x_batch_stride, const float* gamma_beta, const float* mean,
-                            const float* rstd, const float* gy, long long gy_batch_stride, float* gx,
-                            long long gx_batch_stride, float* g_gamma_beta, int B, int C, int N, int relu, ct_stream_t s) {
-  return adain_bwd_impl(x, x_batch_stride, gamma_beta, mean, rstd, gy, gy_batch_stride, gx, gx_batch_stride, g_gamma_beta, nullptr, 0,
-                        B, C, N, relu, s);
-}
-
-// with amax_out f32 (nullable): amax_out[b * amax_batch_stride + c] = max |gx| of row (b, c); stride 0 = C
-extern "C" int ct_adain_bwd_amax(const float* x, long long x_batch_stride, const float* gamma_beta, const float* mean,
-                                 const float* rstd, const float* gy, long long gy_batch_stride, float* gx,
-                                 long long gx_batch_stride, float* g_gamma_beta, float* amax_out, long long amax_batch_stride,
-                                 int B, int C, int N, int relu, ct_stream_t s) {
-  if (amax_batch_stride != 0 && amax_batch_stride < C) return CT_EINVAL;
-  return adain_bwd_impl(x, x_batch_stride, gamma_beta, mean, rstd, gy, gy_batch_stride, gx, gx_batch_stride, g_gamma_beta, amax_out,
-                        amax_batch_stride, B, C, N, relu, s);
 }

@@ -524,7 +524,7 @@ bool reg_ok(int B, int N) { return (N & 3) == 0 && (long long)B * (N >> 2) <= (l
     default: hipLaunchKernelGGL((KERNEL<8>), dim3(C), dim3(kThreads), 0, stream, __VA_ARGS__); break;    \
   }
 
-// 1 when ct_bn_relu_fwd / _bwd take (B, C, N): every shape with 2 <= B*N < 2^31.  Channels with N % 4 == 0 and
+// 1 when ct_bn_group_fwd / _bwd take (B, C, N): every shape with 2 <= B*N < 2^31.  Channels with N % 4 == 0 and
 // B*N <= 32768 are held in registers (one read, one write); the others are re-read per pass.
 extern "C" int ct_bn_relu_supported(int B, int C, int N) { return shape_ok(B, C, N) ? 1 : 0; }
 
@@ -563,16 +563,6 @@ static int bn_fwd_launch_table(BnTable& t, bool vec, hipStream_t stream) {
   return CT_OK;
 }
 
-static int bn_fwd_launch(BnArgs a, float* y, long long x_batch_stride, long long y_batch_stride, long long residual_batch_stride,
-                         hipStream_t stream) {
-  bool vec;
-  const int rc = bn_fwd_prepare(a, y, x_batch_stride, y_batch_stride, residual_batch_stride, vec);
-  if (rc != CT_OK) return rc;
-  BnTable t{};
-  t.n = 1; t.cstart[0] = 0; t.cstart[1] = a.C; t.item[0] = a; t.y[0] = y;
-  return bn_fwd_launch_table(t, vec, stream);
-}
-
 static int bn_bwd_prepare(BnBwdArgs& a, long long x_batch_stride, long long gy_batch_stride, long long gx_batch_stride, bool& vec) {
   if (!shape_ok(a.B, a.C, a.N)) return CT_EINVAL;
   if (!stride_ok(x_batch_stride, a.C, a.N, a.xbs) || !stride_ok(gy_batch_stride, a.C, a.N, a.gybs) ||
@@ -597,17 +587,7 @@ static int bn_bwd_launch_table(BnBwdTable& t, bool vec, hipStream_t stream) {
   return CT_OK;
 }
 
-static int bn_bwd_launch(BnBwdArgs a, long long x_batch_stride, long long gy_batch_stride, long long gx_batch_stride,
-                         hipStream_t stream) {
-  bool vec;
-  const int rc = bn_bwd_prepare(a, x_batch_stride, gy_batch_stride, gx_batch_stride, vec);
-  if (rc != CT_OK) return rc;
-  BnBwdTable t{};
-  t.n = 1; t.cstart[0] = 0; t.cstart[1] = a.C; t.item[0] = a;
-  return bn_bwd_launch_table(t, vec, stream);
-}
-
-// Up to kBnMaxItems norms over the same (B, N) in one launch: ct_bn_relu_fwd_amax / _bwd_amax of every item.
+// Up to kBnMaxItems norms over the same (B, N) in one launch; a single norm is a table with n = 1.
 extern "C" int ct_bn_group_fwd(const ct_bn_fwd_item* items, int n, int B, int N, ct_stream_t s) {
   if (!items || n < 1 || n > kBnMaxItems) return CT_EINVAL;
   BnTable t{};
@@ -657,22 +637,38 @@ extern "C" int ct_bn_group_bwd(const ct_bn_bwd_item* items, int n, int B, int N,
   return bn_bwd_launch_table(t, vec_all, (hipStream_t)s);
 }
 
-// ---- the norms of a group around ONE statistics exchange (SyncBatchNorm): each phase of all items in ONE launch ----
-// Buffer layouts (Ct = sum of the items' C, item i's channels start at c0_i):
+// ---- the norms of a group around ONE statistics exchange (SyncBatchNorm): each phase of a run of items in ONE launch ----
+// Buffer layouts (Ct = sum of the C of ALL n items, item i's channels start at c0_i):
 //   local / every rank's block of `gathered` (stride 2 Ct + 1): [mean: Ct | sum (x - mean)^2: Ct | count: 1]
 //   sums: [sum g': Ct | sum g' xhat: Ct]
-static int bn_group_fwd_table(const ct_bn_fwd_item* items, int n, int B, int N, int mode, float* local, const float* gathered,
-                              int world, float* count_out, BnTable& t, bool& vec_all) {
-  if (!items || n < 1 || n > kBnMaxItems) return CT_EINVAL;
-  int Ct = 0;
-  for (int i = 0; i < n; ++i) Ct += items[i].C;
-  const long long stride = 2ll * Ct + 1;
-  t.n = n;
-  vec_all = true;
-  int c0 = 0;
+// A launch covers items [first, first + run), 1 <= run <= kBnMaxItems; n itself is not capped: the layout belongs to the
+// group, the launch to the run.  The count slot is written by the run that holds item 0.
+template <typename Item>
+static int bn_group_range(const Item* items, int n, int first, int run, int& Ct, int& c_first) {
+  if (!items || n < 1 || first < 0 || run < 1 || run > kBnMaxItems || first > n - run) return CT_EINVAL;
+  long long c = 0;
   for (int i = 0; i < n; ++i) {
+    if (items[i].C < 1) return CT_EINVAL;
+    if (i == first) c_first = (int)c;
+    c += items[i].C;
+    if (c > 0x3fffffffLL) return CT_EINVAL;   // 2 Ct + 1 is an int offset
+  }
+  Ct = (int)c;
+  return CT_OK;
+}
+
+static int bn_group_fwd_table(const ct_bn_fwd_item* items, int n, int first, int run, int B, int N, int mode, float* local,
+                              const float* gathered, int world, float* count_out, BnTable& t, bool& vec_all) {
+  int Ct, c0;
+  if (bn_group_range(items, n, first, run, Ct, c0) != CT_OK) return CT_EINVAL;
+  const long long stride = 2ll * Ct + 1;
+  t.n = run;
+  vec_all = true;
+  int cl = 0;                 // first workgroup (channel) of the item within this launch
+  for (int j = 0; j < run; ++j) {
+    const int i = first + j;
     const ct_bn_fwd_item& it = items[i];
-    if (!it.x || it.C < 1) return CT_EINVAL;
+    if (!it.x) return CT_EINVAL;
     BnArgs a{};
     bool vec;
     int rc;
@@ -680,7 +676,7 @@ static int bn_group_fwd_table(const ct_bn_fwd_item* items, int n, int B, int N, 
       a = BnArgs{it.x, nullptr, nullptr, nullptr, nullptr, local + c0, local + Ct + c0, B, it.C, N, 0.0f, 0.0f, 0, 0, 0, nullptr, 0,
                  nullptr, 1, i == 0 ? local + 2 * Ct : nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr};
       rc = bn_fwd_prepare(a, const_cast<float*>(it.x), it.x_batch_stride, it.x_batch_stride, 0, vec);
-      t.y[i] = const_cast<float*>(it.x);
+      t.y[j] = const_cast<float*>(it.x);
     } else {
       if (!it.weight || !it.bias || !it.y || !it.save_mean || !it.save_rstd || !(it.eps >= 0.0f)) return CT_EINVAL;
       if ((it.running_mean == nullptr) != (it.running_var == nullptr)) return CT_EINVAL;
@@ -688,46 +684,47 @@ static int bn_group_fwd_table(const ct_bn_fwd_item* items, int n, int B, int N, 
                  it.momentum, it.relu, 0, 0, it.residual, 0, it.num_batches_tracked, 2, i == 0 ? count_out : nullptr,
                  gathered + c0, gathered + Ct + c0, gathered + 2 * Ct, world, stride, it.amax_out};
       rc = bn_fwd_prepare(a, it.y, it.x_batch_stride, it.y_batch_stride, it.residual_batch_stride, vec);
-      t.y[i] = it.y;
+      t.y[j] = it.y;
     }
     if (rc != CT_OK) return rc;
     vec_all = vec_all && vec;
-    t.cstart[i] = c0;
-    t.item[i] = a;
+    t.cstart[j] = cl;
+    t.item[j] = a;
+    cl += it.C;
     c0 += it.C;
   }
-  t.cstart[n] = c0;
+  t.cstart[run] = cl;
   return CT_OK;
 }
 
-extern "C" int ct_bn_group_stats_fwd(const ct_bn_fwd_item* items, int n, int B, int N, float* local, ct_stream_t s) {
+extern "C" int ct_bn_group_stats_fwd(const ct_bn_fwd_item* items, int n, int first, int run, int B, int N, float* local,
+                                     ct_stream_t s) {
   if (!local) return CT_EINVAL;
   BnTable t{};
   bool vec;
-  const int rc = bn_group_fwd_table(items, n, B, N, 1, local, nullptr, 0, nullptr, t, vec);
+  const int rc = bn_group_fwd_table(items, n, first, run, B, N, 1, local, nullptr, 0, nullptr, t, vec);
   return rc != CT_OK ? rc : bn_fwd_launch_table(t, vec, (hipStream_t)s);
 }
 
-extern "C" int ct_bn_group_apply_fwd(const ct_bn_fwd_item* items, int n, int B, int N, const float* gathered, int world,
-                                     float* count_total, ct_stream_t s) {
+extern "C" int ct_bn_group_apply_fwd(const ct_bn_fwd_item* items, int n, int first, int run, int B, int N, const float* gathered,
+                                     int world, float* count_total, ct_stream_t s) {
   if (!gathered || world < 1) return CT_EINVAL;
   BnTable t{};
   bool vec;
-  const int rc = bn_group_fwd_table(items, n, B, N, 2, nullptr, gathered, world, count_total, t, vec);
+  const int rc = bn_group_fwd_table(items, n, first, run, B, N, 2, nullptr, gathered, world, count_total, t, vec);
   return rc != CT_OK ? rc : bn_fwd_launch_table(t, vec, (hipStream_t)s);
 }
 
-static int bn_group_bwd_table(const ct_bn_bwd_item* items, int n, int B, int N, int mode, float* sums, const float* count,
-                              BnBwdTable& t, bool& vec_all, float* sums_copy = nullptr) {
-  if (!items || n < 1 || n > kBnMaxItems || !sums) return CT_EINVAL;
-  int Ct = 0;
-  for (int i = 0; i < n; ++i) Ct += items[i].C;
-  t.n = n;
+static int bn_group_bwd_table(const ct_bn_bwd_item* items, int n, int first, int run, int B, int N, int mode, float* sums,
+                              float* sums_copy, const float* count, BnBwdTable& t, bool& vec_all) {
+  int Ct, c0;
+  if (!sums || bn_group_range(items, n, first, run, Ct, c0) != CT_OK) return CT_EINVAL;
+  t.n = run;
   vec_all = true;
-  int c0 = 0;
-  for (int i = 0; i < n; ++i) {
-    const ct_bn_bwd_item& it = items[i];
-    if (!it.x || !it.weight || !it.bias || !it.save_mean || !it.save_rstd || !it.gy || it.C < 1) return CT_EINVAL;
+  int cl = 0;
+  for (int j = 0; j < run; ++j) {
+    const ct_bn_bwd_item& it = items[first + j];
+    if (!it.x || !it.weight || !it.bias || !it.save_mean || !it.save_rstd || !it.gy) return CT_EINVAL;
     BnBwdArgs a{};
     bool vec;
     int rc;
@@ -744,163 +741,30 @@ static int bn_group_bwd_table(const ct_bn_bwd_item* items, int n, int B, int N, 
     }
     if (rc != CT_OK) return rc;
     vec_all = vec_all && vec;
-    t.cstart[i] = c0;
-    t.item[i] = a;
+    t.cstart[j] = cl;
+    t.item[j] = a;
+    cl += it.C;
     c0 += it.C;
   }
-  t.cstart[n] = c0;
+  t.cstart[run] = cl;
   return CT_OK;
 }
 
-extern "C" int ct_bn_group_reduce_bwd(const ct_bn_bwd_item* items, int n, int B, int N, float* sums, ct_stream_t s) {
+// sums_copy (nullable): a second copy of this rank's sums, which stays when the collective overwrites `sums` in place
+extern "C" int ct_bn_group_reduce_bwd(const ct_bn_bwd_item* items, int n, int first, int run, int B, int N, float* sums,
+                                      float* sums_copy, ct_stream_t s) {
   BnBwdTable t{};
   bool vec;
-  const int rc = bn_group_bwd_table(items, n, B, N, 1, sums, nullptr, t, vec);
+  const int rc = bn_group_bwd_table(items, n, first, run, B, N, 1, sums, sums_copy, nullptr, t, vec);
   return rc != CT_OK ? rc : bn_bwd_launch_table(t, vec, (hipStream_t)s);
 }
 
-extern "C" int ct_bn_group_reduce_bwd_copy(const ct_bn_bwd_item* items, int n, int B, int N, float* sums, float* sums_copy,
-                                           ct_stream_t s) {
-  if (!sums_copy) return CT_EINVAL;
+extern "C" int ct_bn_group_apply_bwd(const ct_bn_bwd_item* items, int n, int first, int run, int B, int N, const float* sums,
+                                     const float* count, ct_stream_t s) {
   BnBwdTable t{};
   bool vec;
-  const int rc = bn_group_bwd_table(items, n, B, N, 1, sums, nullptr, t, vec, sums_copy);
+  const int rc = bn_group_bwd_table(items, n, first, run, B, N, 2, const_cast<float*>(sums), nullptr, count, t, vec);
   return rc != CT_OK ? rc : bn_bwd_launch_table(t, vec, (hipStream_t)s);
-}
-
-extern "C" int ct_bn_group_apply_bwd(const ct_bn_bwd_item* items, int n, int B, int N, const float* sums, const float* count,
-                                     ct_stream_t s) {
-  BnBwdTable t{};
-  bool vec;
-  const int rc = bn_group_bwd_table(items, n, B, N, 2, const_cast<float*>(sums), count, t, vec);
-  return rc != CT_OK ? rc : bn_bwd_launch_table(t, vec, (hipStream_t)s);
-}
-
-extern "C" int ct_bn_relu_fwd(const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                              float* running_mean, float* running_var, long long* num_batches_tracked,
-                              const float* residual, long long residual_batch_stride, float* y, long long y_batch_stride,
-                              float* save_mean, float* save_rstd, int B, int C, int N, float eps, float momentum,
-                              int relu, ct_stream_t s) {
-  if (!x || !weight || !bias || !y || !save_mean || !save_rstd || !(eps >= 0.0f)) return CT_EINVAL;
-  if ((running_mean == nullptr) != (running_var == nullptr)) return CT_EINVAL;
-  BnArgs a{x, weight, bias, running_mean, running_var, save_mean, save_rstd, B, C, N, eps, momentum, relu, 0, 0,
-           residual, 0, num_batches_tracked, 0, nullptr, nullptr, nullptr, nullptr, 0, 0};
-  return bn_fwd_launch(a, y, x_batch_stride, y_batch_stride, residual_batch_stride, (hipStream_t)s);
-}
-
-extern "C" int ct_bn_relu_bwd(const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                              const float* save_mean, const float* save_rstd, const float* gy, long long gy_batch_stride,
-                              float* gx, long long gx_batch_stride, float* g_weight, float* g_bias, int B, int C, int N,
-                              int relu, ct_stream_t s) {
-  if (!x || !weight || !bias || !save_mean || !save_rstd || !gy || !gx || !g_weight || !g_bias) return CT_EINVAL;
-  BnBwdArgs a{x, weight, bias, save_mean, save_rstd, gy, gx, g_weight, g_bias, B, C, N, relu, 0, 0, 0, 0, nullptr, nullptr, nullptr};
-  return bn_bwd_launch(a, x_batch_stride, gy_batch_stride, gx_batch_stride, (hipStream_t)s);
-}
-
-// The same two with amax_out f32[C] (nullable): max |y| / max |gx| per channel, for ct_pw_gemm's operand scale.
-extern "C" int ct_bn_relu_fwd_amax(const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                                   float* running_mean, float* running_var, long long* num_batches_tracked,
-                                   const float* residual, long long residual_batch_stride, float* y, long long y_batch_stride,
-                                   float* save_mean, float* save_rstd, float* amax_out, int B, int C, int N, float eps,
-                                   float momentum, int relu, ct_stream_t s) {
-  if (!x || !weight || !bias || !y || !save_mean || !save_rstd || !(eps >= 0.0f)) return CT_EINVAL;
-  if ((running_mean == nullptr) != (running_var == nullptr)) return CT_EINVAL;
-  BnArgs a{x, weight, bias, running_mean, running_var, save_mean, save_rstd, B, C, N, eps, momentum, relu, 0, 0,
-           residual, 0, num_batches_tracked, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, amax_out};
-  return bn_fwd_launch(a, y, x_batch_stride, y_batch_stride, residual_batch_stride, (hipStream_t)s);
-}
-
-extern "C" int ct_bn_relu_bwd_amax(const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                                   const float* save_mean, const float* save_rstd, const float* gy, long long gy_batch_stride,
-                                   float* gx, long long gx_batch_stride, float* g_weight, float* g_bias, float* amax_out,
-                                   int B, int C, int N, int relu, ct_stream_t s) {
-  if (!x || !weight || !bias || !save_mean || !save_rstd || !gy || !gx || !g_weight || !g_bias) return CT_EINVAL;
-  BnBwdArgs a{x, weight, bias, save_mean, save_rstd, gy, gx, g_weight, g_bias, B, C, N, relu, 0, 0, 0, 0, nullptr, nullptr, nullptr,
-              amax_out};
-  return bn_bwd_launch(a, x_batch_stride, gy_batch_stride, gx_batch_stride, (hipStream_t)s);
-}
-
-// ---- the same norm split around a statistics exchange between ranks (SyncBatchNorm under data parallelism) ----
-
-extern "C" int ct_bn_stats_fwd(const float* x, long long x_batch_stride, float* mean, float* m2, float* count, int B, int C,
-                               int N, ct_stream_t s) {
-  if (!x || !mean || !m2) return CT_EINVAL;
-  BnArgs a{x, nullptr, nullptr, nullptr, nullptr, mean, m2, B, C, N, 0.0f, 0.0f, 0, 0, 0, nullptr, 0, nullptr,
-           1, count, nullptr, nullptr, nullptr, 0, 0};
-  return bn_fwd_launch(a, const_cast<float*>(x), x_batch_stride, x_batch_stride, 0, (hipStream_t)s);
-}
-
-static int bn_apply_fwd_impl(float* amax_out, const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                               const float* g_mean, const float* g_m2, const float* g_count, int world, long long g_stride,
-                               float* running_mean, float* running_var, long long* num_batches_tracked,
-                               const float* residual, long long residual_batch_stride, float* y, long long y_batch_stride,
-                               float* save_mean, float* save_rstd, float* count_total, int B, int C, int N, float eps,
-                               float momentum, int relu, ct_stream_t s) {
-  if (!x || !weight || !bias || !y || !g_mean || !g_m2 || !g_count || !save_mean || !save_rstd || !(eps >= 0.0f) ||
-      world < 1 || g_stride < 1)
-    return CT_EINVAL;
-  if ((running_mean == nullptr) != (running_var == nullptr)) return CT_EINVAL;
-  BnArgs a{x, weight, bias, running_mean, running_var, save_mean, save_rstd, B, C, N, eps, momentum, relu, 0, 0,
-           residual, 0, num_batches_tracked, 2, count_total, g_mean, g_m2, g_count, world, g_stride, amax_out};
-  return bn_fwd_launch(a, y, x_batch_stride, y_batch_stride, residual_batch_stride, (hipStream_t)s);
-}
-
-extern "C" int ct_bn_apply_fwd(const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                               const float* g_mean, const float* g_m2, const float* g_count, int world, long long g_stride,
-                               float* running_mean, float* running_var, long long* num_batches_tracked,
-                               const float* residual, long long residual_batch_stride, float* y, long long y_batch_stride,
-                               float* save_mean, float* save_rstd, float* count_total, int B, int C, int N, float eps,
-                               float momentum, int relu, ct_stream_t s) {
-  return bn_apply_fwd_impl(nullptr, x, x_batch_stride, weight, bias, g_mean, g_m2, g_count, world, g_stride, running_mean, running_var,
-                           num_batches_tracked, residual, residual_batch_stride, y, y_batch_stride, save_mean, save_rstd, count_total,
-                           B, C, N, eps, momentum, relu, s);
-}
-
-// with amax_out f32[C] (nullable), as ct_bn_relu_fwd_amax
-extern "C" int ct_bn_apply_fwd_amax(const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                                    const float* g_mean, const float* g_m2, const float* g_count, int world, long long g_stride,
-                                    float* running_mean, float* running_var, long long* num_batches_tracked,
-                                    const float* residual, long long residual_batch_stride, float* y, long long y_batch_stride,
-                                    float* save_mean, float* save_rstd, float* count_total, float* amax_out, int B, int C, int N,
-                                    float eps, float momentum, int relu, ct_stream_t s) {
-  return bn_apply_fwd_impl(amax_out, x, x_batch_stride, weight, bias, g_mean, g_m2, g_count, world, g_stride, running_mean,
-                           running_var, num_batches_tracked, residual, residual_batch_stride, y, y_batch_stride, save_mean,
-                           save_rstd, count_total, B, C, N, eps, momentum, relu, s);
-}
-
-extern "C" int ct_bn_reduce_bwd(const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                                const float* mean, const float* rstd, const float* gy, long long gy_batch_stride,
-                                float* sum_g, float* sum_gxhat, int B, int C, int N, int relu, ct_stream_t s) {
-  if (!x || !weight || !bias || !mean || !rstd || !gy || !sum_g || !sum_gxhat) return CT_EINVAL;
-  BnBwdArgs a{x, weight, bias, mean, rstd, gy, const_cast<float*>(x), sum_gxhat, sum_g, B, C, N, relu, 0, 0, 0,
-              1, nullptr, nullptr, nullptr};
-  return bn_bwd_launch(a, x_batch_stride, gy_batch_stride, x_batch_stride, (hipStream_t)s);
-}
-
-static int bn_apply_bwd_impl(float* amax_out, const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                               const float* mean, const float* rstd, const float* gy, long long gy_batch_stride,
-                               const float* sum_g, const float* sum_gxhat, const float* count, float* gx,
-                               long long gx_batch_stride, int B, int C, int N, int relu, ct_stream_t s) {
-  if (!x || !weight || !bias || !mean || !rstd || !gy || !gx || !sum_g || !sum_gxhat || !count) return CT_EINVAL;
-  BnBwdArgs a{x, weight, bias, mean, rstd, gy, gx, nullptr, nullptr, B, C, N, relu, 0, 0, 0, 2, sum_g, sum_gxhat, count, amax_out};
-  return bn_bwd_launch(a, x_batch_stride, gy_batch_stride, gx_batch_stride, (hipStream_t)s);
-}
-
-extern "C" int ct_bn_apply_bwd(const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                               const float* mean, const float* rstd, const float* gy, long long gy_batch_stride,
-                               const float* sum_g, const float* sum_gxhat, const float* count, float* gx,
-                               long long gx_batch_stride, int B, int C, int N, int relu, ct_stream_t s) {
-  return bn_apply_bwd_impl(nullptr, x, x_batch_stride, weight, bias, mean, rstd, gy, gy_batch_stride, sum_g, sum_gxhat, count, gx,
-                           gx_batch_stride, B, C, N, relu, s);
-}
-
-// with amax_out f32[C] (nullable), as ct_bn_relu_bwd_amax
-extern "C" int ct_bn_apply_bwd_amax(const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                                    const float* mean, const float* rstd, const float* gy, long long gy_batch_stride,
-                                    const float* sum_g, const float* sum_gxhat, const float* count, float* gx,
-                                    long long gx_batch_stride, float* amax_out, int B, int C, int N, int relu, ct_stream_t s) {
-  return bn_apply_bwd_impl(amax_out, x, x_batch_stride, weight, bias, mean, rstd, gy, gy_batch_stride, sum_g, sum_gxhat, count, gx,
-                           gx_batch_stride, B, C, N, relu, s);
 }
 
 // ---- eval-mode BatchNorm1d (+ ReLU, + skip): a per-channel affine on the stored statistics ----
@@ -1062,16 +926,4 @@ extern "C" int ct_bn_eval_group_fwd(const ct_bn_fwd_item* items, int n, int B, i
   else hipLaunchKernelGGL(bn_eval_kernel<false>, dim3((unsigned)w0), dim3(kThreads), 0, stream, t);
   CT_CHECK_LAUNCH();
   return CT_OK;
-}
-
-extern "C" int ct_bn_eval_fwd(const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                              const float* running_mean, const float* running_var, const float* residual,
-                              long long residual_batch_stride, float* y, long long y_batch_stride, float* amax_out,
-                              int B, int C, int N, float eps, int relu, ct_stream_t s) {
-  ct_bn_fwd_item it{};
-  it.x = x; it.x_batch_stride = x_batch_stride; it.weight = weight; it.bias = bias;
-  it.running_mean = const_cast<float*>(running_mean); it.running_var = const_cast<float*>(running_var);
-  it.residual = residual; it.residual_batch_stride = residual_batch_stride; it.y = y; it.y_batch_stride = y_batch_stride;
-  it.amax_out = amax_out; it.C = C; it.eps = eps; it.relu = relu;
-  return ct_bn_eval_group_fwd(&it, 1, B, N, s);
 }

@@ -61,7 +61,7 @@ def run_after(module_list, input, residual=None):
     """Apply an `after` Sequential (and add `residual` to its result); a training-mode nn.BatchNorm1d directly followed by
     nn.ReLU runs as the fused ct_bn_relu kernels when the shape qualifies (ops.bn_relu_eligible), the skip connection
     added in the same pass when that pair ends the stack (an nn.SyncBatchNorm too: ops exchanges the group's statistics
-    over its process group); the same pair in eval mode runs as ct_bn_eval_fwd where autograd records nothing
+    over its process group); the same pair in eval mode runs as ct_bn_eval_group_fwd where autograd records nothing
     (ops.bn_eval_eligible) — an eval forward with gradients and every other layer go through their own forward."""
     layers = list(module_list)
     i = 0

@@ -98,7 +98,7 @@ class AdaIn1dUpd(nn.Module):
         kernel (forward_style passes it and skips the nn.ReLU); `residual` is added to the result in the same pass."""
         gamma_beta = self.gamma_beta(z)
         if x.dtype == torch.float32 and x.dim() == 3:
-            return ops.adain(x, gamma_beta, self.instance_norm.eps, relu, residual)    # one HIP launch (ct_adain_fwd); raises off the GPU
+            return ops.adain(x, gamma_beta, self.instance_norm.eps, relu, residual)    # one HIP launch (ct_adain_group_fwd, a table of one); raises off the GPU
         if not x.is_cuda:
             raise RuntimeError("cloud_transformers_amd has no CPU fallback: AdaIn1dUpd needs a HIP tensor")
         # other layouts / floating types on the GPU: torch's own composition

@@ -142,7 +142,7 @@ PW_AMAX_MAX = 32768     # partial maxima ct_pw_gemm folds per operand
 
 
 def _amax_slots(C, device):
-    """Maxima buffer for a producer kernel (ct_bn_relu_*_amax: one slot per channel; ct_adain_*_amax: one per (cloud, channel)),
+    """Maxima buffer for a producer kernel (ct_bn_group_* / ct_bn_eval_group_fwd: one slot per channel; ct_adain_group_*: one per (cloud, channel)),
     or None when the consumer could not use it (library GEMMs selected, or more slots than ct_pw_gemm folds)."""
     if PW_GEMM != "split16" or C > PW_AMAX_MAX:
         return None
@@ -804,28 +804,58 @@ def _gb_arg(gb, B, C):
     return gb.contiguous(), 0
 
 
+def _runs(n, step):
+    """(first, run) of every launch over a table of n items taken `step` at a time."""
+    return [(first, min(step, n - first)) for first in range(0, n, step)]
+
+
+def _at(arr, first):
+    """Address of item `first` of a ctypes item array."""
+    return ctypes.addressof(arr) + first * ctypes.sizeof(arr._type_)
+
+
+def _adain_fwd_table(items):
+    """ct_adain_fwd_item array.  items: dicts with x (ptr), xbs, gb, gbbs (optional), res, rbs, y (ptr), ybs, mean, rstd, amax
+    (ptr or None), abs (amax batch stride), C, eps, relu."""
+    arr = (_lib.AdainFwdItem * len(items))()
+    for e, it in zip(arr, items):
+        e.x, e.x_batch_stride, e.gamma_beta, e.residual, e.residual_batch_stride = it["x"], it["xbs"], _ptr(it["gb"]), it["res"], it["rbs"]
+        e.y, e.y_batch_stride, e.mean, e.rstd = it["y"], it["ybs"], _ptr(it["mean"]), _ptr(it["rstd"])
+        e.amax_out, e.amax_batch_stride, e.C, e.eps, e.relu = it["amax"], it["abs"], it["C"], float(it["eps"]), int(it["relu"])
+        e.gamma_beta_batch_stride = it.get("gbbs", 0)
+    return arr
+
+
+def _adain_bwd_table(items):
+    """ct_adain_bwd_item array.  items: dicts with x (ptr), xbs, gb, gbbs (optional), mean, rstd, gy (ptr), gybs, gx (ptr), gxbs,
+    g_gb, amax, abs, C, relu."""
+    arr = (_lib.AdainBwdItem * len(items))()
+    for e, it in zip(arr, items):
+        e.x, e.x_batch_stride, e.gamma_beta, e.mean, e.rstd = it["x"], it["xbs"], _ptr(it["gb"]), _ptr(it["mean"]), _ptr(it["rstd"])
+        e.gy, e.gy_batch_stride, e.gx, e.gx_batch_stride, e.g_gamma_beta = it["gy"], it["gybs"], it["gx"], it["gxbs"], _ptr(it["g_gb"])
+        e.amax_out, e.amax_batch_stride, e.C, e.relu = it["amax"], it["abs"], it["C"], int(it["relu"])
+        e.gamma_beta_batch_stride = it.get("gbbs", 0)
+    return arr
+
+
+def _adain_runs(n):
+    """AdaIN's launch rule: runs of BN_GROUP_MAX norms, or one by one with the switch off."""
+    return _runs(n, _lib.BN_GROUP_MAX if BN_GROUP_LAUNCH else 1)
+
+
 def _adain_group_fwd(items, B, N):
-    """ct_adain_fwd_amax of every item — in ONE launch when there are several (ct_adain_group_fwd).  items: dicts with x (ptr),
-    xbs, gb, res, rbs, y (ptr), ybs, mean, rstd, amax (ptr or None), abs (amax batch stride), C, eps, relu."""
+    """The adaptive instance norms `items` (_adain_fwd_table) over the same (B, N), BN_GROUP_MAX to a launch (ct_adain_group_fwd).
+    The empty shapes end here: the library takes none."""
     lib = _lib.load()
     if B == 0 or N == 0:
         return
-    items = [it for it in items if it["C"] > 0]
-    step = _lib.BN_GROUP_MAX if BN_GROUP_LAUNCH else 1
-    for i0 in range(0, len(items), step):
-        chunk = items[i0:i0 + step]
-        arr = (_lib.AdainFwdItem * len(chunk))()
-        for e, it in zip(arr, chunk):
-            e.x, e.x_batch_stride, e.gamma_beta, e.residual, e.residual_batch_stride = it["x"], it["xbs"], _ptr(it["gb"]), it["res"], it["rbs"]
-            e.y, e.y_batch_stride, e.mean, e.rstd = it["y"], it["ybs"], _ptr(it["mean"]), _ptr(it["rstd"])
-            e.amax_out, e.amax_batch_stride, e.C, e.eps, e.relu = it["amax"], it["abs"], it["C"], float(it["eps"]), int(it["relu"])
-            e.gamma_beta_batch_stride = it.get("gbbs", 0)
-        _lib.check(lib.ct_adain_group_fwd(ctypes.addressof(arr), len(chunk), B, N, _stream()), "ct_adain_group_fwd")
+    arr = _adain_fwd_table([it for it in items if it["C"] > 0])
+    for first, run in _adain_runs(len(arr)):
+        _lib.check(lib.ct_adain_group_fwd(_at(arr, first), run, B, N, _stream()), "ct_adain_group_fwd")
 
 
 def _adain_group_bwd(items, B, N):
-    """ct_adain_bwd_amax of every item, in ONE launch when there are several.  items: dicts with x (ptr), xbs, gb, mean, rstd,
-    gy (ptr), gybs, gx (ptr), gxbs, g_gb, amax, abs, C, relu."""
+    """Backward of _adain_group_fwd (items: _adain_bwd_table).  Rows without points have zero gamma / beta gradients."""
     lib = _lib.load()
     if B == 0:
         return
@@ -833,17 +863,9 @@ def _adain_group_bwd(items, B, N):
         for it in items:
             it["g_gb"].zero_()
         return
-    items = [it for it in items if it["C"] > 0]
-    step = _lib.BN_GROUP_MAX if BN_GROUP_LAUNCH else 1
-    for i0 in range(0, len(items), step):
-        chunk = items[i0:i0 + step]
-        arr = (_lib.AdainBwdItem * len(chunk))()
-        for e, it in zip(arr, chunk):
-            e.x, e.x_batch_stride, e.gamma_beta, e.mean, e.rstd = it["x"], it["xbs"], _ptr(it["gb"]), _ptr(it["mean"]), _ptr(it["rstd"])
-            e.gy, e.gy_batch_stride, e.gx, e.gx_batch_stride, e.g_gamma_beta = it["gy"], it["gybs"], it["gx"], it["gxbs"], _ptr(it["g_gb"])
-            e.amax_out, e.amax_batch_stride, e.C, e.relu = it["amax"], it["abs"], it["C"], int(it["relu"])
-            e.gamma_beta_batch_stride = it.get("gbbs", 0)
-        _lib.check(lib.ct_adain_group_bwd(ctypes.addressof(arr), len(chunk), B, N, _stream()), "ct_adain_group_bwd")
+    arr = _adain_bwd_table([it for it in items if it["C"] > 0])
+    for first, run in _adain_runs(len(arr)):
+        _lib.check(lib.ct_adain_group_bwd(_at(arr, first), run, B, N, _stream()), "ct_adain_group_bwd")
 
 
 class UnionKeysValuesAdaInFn(torch.autograd.Function):
@@ -1018,70 +1040,62 @@ def norms_share_group(bns):
     return all(type(bn) is first and _sync_group(bn) is group for bn in bns[1:])
 
 
+def _bn_runs(n):
+    """BatchNorm's launch rule (training and eval): 2..BN_GROUP_MAX norms make ONE run; a single norm, more than BN_GROUP_MAX
+    or CLOUDCT_BN_GROUP=0 go one by one."""
+    return _runs(n, n if 1 < n <= _lib.BN_GROUP_MAX and BN_GROUP_LAUNCH else 1)
+
+
+def _bn_fwd_table(items, stats=None):
+    """ct_bn_fwd_item array.  items: dicts with x (data_ptr), xbs, C, w, b, rm, rv, eps, relu, res (ptr or None), rbs, y (ptr),
+    ybs and, optionally, amax (ptr to C floats: the per-channel max |y| as written), nbt and mom (training).  stats: the
+    (save_mean, save_rstd) tensors of every item (training)."""
+    arr = (_lib.BnFwdItem * len(items))()
+    for i, (e, it) in enumerate(zip(arr, items)):
+        e.x, e.x_batch_stride, e.weight, e.bias = it["x"], it["xbs"], _ptr(it["w"]), _ptr(it["b"])
+        e.running_mean, e.running_var, e.num_batches_tracked = _ptr(it["rm"]), _ptr(it["rv"]), _ptr(it.get("nbt"))
+        e.residual, e.residual_batch_stride, e.y, e.y_batch_stride = it["res"], it["rbs"], it["y"], it["ybs"]
+        if stats is not None:
+            e.save_mean, e.save_rstd = _ptr(stats[i][0]), _ptr(stats[i][1])
+        e.amax_out, e.C, e.eps, e.momentum, e.relu = it.get("amax"), it["C"], float(it["eps"]), float(it.get("mom", 0.0)), int(it["relu"])
+    return arr
+
+
+def _bn_bwd_table(items, grads=None):
+    """ct_bn_bwd_item array.  items: dicts with x, xbs, C, w, b, mean, rstd, gy (ptr), gybs, gx (ptr), gxbs, relu and, optionally,
+    amax.  grads: the (g_weight, g_bias) tensors of every item (None around an exchange: the sums buffer holds them)."""
+    arr = (_lib.BnBwdItem * len(items))()
+    for i, (e, it) in enumerate(zip(arr, items)):
+        e.x, e.x_batch_stride, e.weight, e.bias = it["x"], it["xbs"], _ptr(it["w"]), _ptr(it["b"])
+        e.save_mean, e.save_rstd, e.gy, e.gy_batch_stride = _ptr(it["mean"]), _ptr(it["rstd"]), it["gy"], it["gybs"]
+        e.gx, e.gx_batch_stride, e.amax_out = it["gx"], it["gxbs"], it.get("amax")
+        if grads is not None:
+            e.g_weight, e.g_bias = _ptr(grads[i][0]), _ptr(grads[i][1])
+        e.C, e.relu = it["C"], int(it["relu"])
+    return arr
+
+
 def _bn_group_fwd(items, B, N, device, group):
-    """Run the norms of one group.  items: dicts with x (data_ptr), xbs, C, w, b, rm, rv, nbt, eps, mom, relu, res (ptr or
-    None), rbs, y (ptr), ybs and, optionally, amax (ptr to C floats: the per-channel max |y| as written).  Returns ([(mean, rstd)] per item, count) — count is None without a group, else a 1-float
-    device tensor with the job's values per channel.  With a group: local statistics of ALL items into one buffer, ONE
-    all_gather, then the normalising kernels merge the ranks' statistics themselves (csrc/ct_bnorm.hip mode 1 / 2)."""
+    """Run the norms of one group (items: _bn_fwd_table).  Returns ([(mean, rstd)] per item, count) — count is None without a
+    group, else a 1-float device tensor with the job's values per channel.  With a group: local statistics of ALL items into
+    one buffer, ONE all_gather, then the normalising kernels merge the ranks' statistics themselves (csrc/ct_bnorm.hip mode
+    1 / 2).  Either way the launches cover the runs of _bn_runs: the whole group at once, or its norms one by one."""
     global _sync_stats_collectives
     lib = _lib.load()
-    stats = []
-    if group is None and 1 < len(items) <= _lib.BN_GROUP_MAX and BN_GROUP_LAUNCH:
-        # the norms of a block's group in ONE launch (a workgroup per channel of every norm)
-        arr = (_lib.BnFwdItem * len(items))()
-        for e, it in zip(arr, items):
-            mean = torch.empty(it["C"], device=device, dtype=torch.float32)
-            rstd = torch.empty_like(mean)
-            e.x, e.x_batch_stride, e.weight, e.bias = it["x"], it["xbs"], _ptr(it["w"]), _ptr(it["b"])
-            e.running_mean, e.running_var, e.num_batches_tracked = _ptr(it["rm"]), _ptr(it["rv"]), _ptr(it["nbt"])
-            e.residual, e.residual_batch_stride, e.y, e.y_batch_stride = it["res"], it["rbs"], it["y"], it["ybs"]
-            e.save_mean, e.save_rstd, e.amax_out = _ptr(mean), _ptr(rstd), it.get("amax")
-            e.C, e.eps, e.momentum, e.relu = it["C"], float(it["eps"]), float(it["mom"]), int(it["relu"])
-            stats.append((mean, rstd))
-        _lib.check(lib.ct_bn_group_fwd(ctypes.addressof(arr), len(items), B, N, _stream()), "ct_bn_group_fwd")
-        return stats, None
+    n = len(items)
+    stats = [(torch.empty(it["C"], device=device, dtype=torch.float32), torch.empty(it["C"], device=device, dtype=torch.float32))
+             for it in items]
+    arr = _bn_fwd_table(items, stats)
     if group is None:
-        for it in items:
-            mean = torch.empty(it["C"], device=device, dtype=torch.float32)
-            rstd = torch.empty_like(mean)
-            _lib.check(lib.ct_bn_relu_fwd_amax(it["x"], it["xbs"], _ptr(it["w"]), _ptr(it["b"]), _ptr(it["rm"]), _ptr(it["rv"]),
-                                               _ptr(it["nbt"]), it["res"], it["rbs"], it["y"], it["ybs"], _ptr(mean), _ptr(rstd),
-                                               it.get("amax"), B, it["C"], N, float(it["eps"]), float(it["mom"]),
-                                               int(it["relu"]), _stream()), "ct_bn_relu_fwd")
-            stats.append((mean, rstd))
+        for first, run in _bn_runs(n):
+            _lib.check(lib.ct_bn_group_fwd(_at(arr, first), run, B, N, _stream()), "ct_bn_group_fwd")
         return stats, None
     import torch.distributed as dist
     world = dist.get_world_size(group)
-    Ct = sum(it["C"] for it in items)
-    stride = 2 * Ct + 1
+    stride = 2 * sum(it["C"] for it in items) + 1           # [mean: Ct | m2: Ct | count]: the table's layout, ct_bn_group_stats_fwd
     local = torch.empty(stride, device=device, dtype=torch.float32)
-    if len(items) <= _lib.BN_GROUP_MAX and BN_GROUP_LAUNCH:
-        # every phase of the group in ONE launch: statistics -> all_gather -> normalise (2 launches + 1 collective per group)
-        arr = (_lib.BnFwdItem * len(items))()
-        outs = []
-        for e, it in zip(arr, items):
-            mean = torch.empty(it["C"], device=device, dtype=torch.float32)
-            rstd = torch.empty_like(mean)
-            e.x, e.x_batch_stride, e.weight, e.bias = it["x"], it["xbs"], _ptr(it["w"]), _ptr(it["b"])
-            e.running_mean, e.running_var, e.num_batches_tracked = _ptr(it["rm"]), _ptr(it["rv"]), _ptr(it["nbt"])
-            e.residual, e.residual_batch_stride, e.y, e.y_batch_stride = it["res"], it["rbs"], it["y"], it["ybs"]
-            e.save_mean, e.save_rstd, e.amax_out = _ptr(mean), _ptr(rstd), it.get("amax")
-            e.C, e.eps, e.momentum, e.relu = it["C"], float(it["eps"]), float(it["mom"]), int(it["relu"])
-            outs.append((mean, rstd))
-        _lib.check(lib.ct_bn_group_stats_fwd(ctypes.addressof(arr), len(items), B, N, _ptr(local), _stream()), "ct_bn_group_stats_fwd")
-        gathered = torch.empty(world * stride, device=device, dtype=torch.float32)
-        work = dist.all_gather_into_tensor(gathered, local, group=group, async_op=True)
-        _sync_stats_collectives += 1
-        count = torch.empty(1, device=device, dtype=torch.float32)
-        work.wait()                   # stream-level wait (no host synchronisation with the RCCL backend)
-        _lib.check(lib.ct_bn_group_apply_fwd(ctypes.addressof(arr), len(items), B, N, _ptr(gathered), world, _ptr(count), _stream()),
-                   "ct_bn_group_apply_fwd")
-        return outs, count
-    base, c0 = local.data_ptr(), 0
-    for i, it in enumerate(items):
-        _lib.check(lib.ct_bn_stats_fwd(it["x"], it["xbs"], base + 4 * c0, base + 4 * (Ct + c0),
-                                       base + 4 * (stride - 1) if i == 0 else None, B, it["C"], N, _stream()), "ct_bn_stats_fwd")
-        c0 += it["C"]
+    for first, run in _bn_runs(n):
+        _lib.check(lib.ct_bn_group_stats_fwd(ctypes.addressof(arr), n, first, run, B, N, _ptr(local), _stream()), "ct_bn_group_stats_fwd")
     gathered = torch.empty(world * stride, device=device, dtype=torch.float32)
     # non-blocking: the collective is enqueued on RCCL's own stream (behind the statistics kernels) and the compute stream
     # waits for it only where the first normalising kernel is enqueued — the host prepares those launches meanwhile, and
@@ -1089,89 +1103,44 @@ def _bn_group_fwd(items, B, N, device, group):
     work = dist.all_gather_into_tensor(gathered, local, group=group, async_op=True)
     _sync_stats_collectives += 1
     count = torch.empty(1, device=device, dtype=torch.float32)
-    outs = [(torch.empty(it["C"], device=device, dtype=torch.float32), torch.empty(it["C"], device=device, dtype=torch.float32))
-            for it in items]
     work.wait()                       # stream-level wait (no host synchronisation with the RCCL backend)
-    gb, c0 = gathered.data_ptr(), 0
-    for i, it in enumerate(items):
-        mean, rstd = outs[i]
-        _lib.check(lib.ct_bn_apply_fwd_amax(it["x"], it["xbs"], _ptr(it["w"]), _ptr(it["b"]), gb + 4 * c0, gb + 4 * (Ct + c0),
-                                            gb + 4 * (stride - 1), world, stride, _ptr(it["rm"]), _ptr(it["rv"]), _ptr(it["nbt"]),
-                                            it["res"], it["rbs"], it["y"], it["ybs"], _ptr(mean), _ptr(rstd),
-                                            _ptr(count) if i == 0 else None, it.get("amax"), B, it["C"], N, float(it["eps"]),
-                                            float(it["mom"]), int(it["relu"]), _stream()), "ct_bn_apply_fwd")
-        stats.append((mean, rstd))
-        c0 += it["C"]
+    for first, run in _bn_runs(n):
+        _lib.check(lib.ct_bn_group_apply_fwd(ctypes.addressof(arr), n, first, run, B, N, _ptr(gathered), world, _ptr(count), _stream()),
+                   "ct_bn_group_apply_fwd")
     # (`gathered` is read by the kernels just enqueued: torch's caching allocator keeps it alive on this stream)
     return stats, count
 
 
 def _bn_group_bwd(items, B, N, device, group, count):
-    """Backward of a norm group.  items: dicts with x, xbs, C, w, b, mean, rstd, gy (ptr), gybs, gx (ptr), gxbs, relu.
-    Returns [(g_weight, g_bias)] per item (this rank's sums: DDP averages parameter gradients itself).  With a group:
-    the two per-channel sums of ALL items into one buffer, ONE all_reduce, then the input-gradient kernels."""
+    """Backward of a norm group (items: _bn_bwd_table), over the same runs as the forward.  Returns [(g_weight, g_bias)] per
+    item (this rank's sums: DDP averages parameter gradients itself).  With a group: the two per-channel sums of ALL items
+    into one buffer, ONE all_reduce, then the input-gradient kernels."""
     global _sync_stats_collectives
     lib = _lib.load()
-    out = []
-    if group is None and 1 < len(items) <= _lib.BN_GROUP_MAX and BN_GROUP_LAUNCH:
-        arr = (_lib.BnBwdItem * len(items))()
-        for e, it in zip(arr, items):
-            g_w = torch.empty(it["C"], device=device, dtype=torch.float32)
-            g_b = torch.empty_like(g_w)
-            e.x, e.x_batch_stride, e.weight, e.bias = it["x"], it["xbs"], _ptr(it["w"]), _ptr(it["b"])
-            e.save_mean, e.save_rstd, e.gy, e.gy_batch_stride = _ptr(it["mean"]), _ptr(it["rstd"]), it["gy"], it["gybs"]
-            e.gx, e.gx_batch_stride, e.g_weight, e.g_bias, e.amax_out = it["gx"], it["gxbs"], _ptr(g_w), _ptr(g_b), it.get("amax")
-            e.C, e.relu = it["C"], int(it["relu"])
-            out.append((g_w, g_b))
-        _lib.check(lib.ct_bn_group_bwd(ctypes.addressof(arr), len(items), B, N, _stream()), "ct_bn_group_bwd")
-        return out
+    n = len(items)
     if group is None:
-        for it in items:
-            g_w = torch.empty(it["C"], device=device, dtype=torch.float32)
-            g_b = torch.empty_like(g_w)
-            _lib.check(lib.ct_bn_relu_bwd_amax(it["x"], it["xbs"], _ptr(it["w"]), _ptr(it["b"]), _ptr(it["mean"]), _ptr(it["rstd"]),
-                                               it["gy"], it["gybs"], it["gx"], it["gxbs"], _ptr(g_w), _ptr(g_b), it.get("amax"),
-                                               B, it["C"], N, int(it["relu"]), _stream()), "ct_bn_relu_bwd")
-            out.append((g_w, g_b))
+        out = [(torch.empty(it["C"], device=device, dtype=torch.float32), torch.empty(it["C"], device=device, dtype=torch.float32))
+               for it in items]
+        arr = _bn_bwd_table(items, out)
+        for first, run in _bn_runs(n):
+            _lib.check(lib.ct_bn_group_bwd(_at(arr, first), run, B, N, _stream()), "ct_bn_group_bwd")
         return out
     import torch.distributed as dist
     Ct = sum(it["C"] for it in items)
     sums = torch.empty(2 * Ct, device=device, dtype=torch.float32)       # [sum g' | sum g' * xhat]
-    if len(items) <= _lib.BN_GROUP_MAX and BN_GROUP_LAUNCH:
-        arr = (_lib.BnBwdItem * len(items))()
-        for e, it in zip(arr, items):
-            e.x, e.x_batch_stride, e.weight, e.bias = it["x"], it["xbs"], _ptr(it["w"]), _ptr(it["b"])
-            e.save_mean, e.save_rstd, e.gy, e.gy_batch_stride = _ptr(it["mean"]), _ptr(it["rstd"]), it["gy"], it["gybs"]
-            e.gx, e.gx_batch_stride, e.g_weight, e.g_bias, e.amax_out = it["gx"], it["gxbs"], None, None, it.get("amax")
-            e.C, e.relu = it["C"], int(it["relu"])
-        local = torch.empty_like(sums)                                    # this rank's g_bias / g_weight: written by the same launch
-        _lib.check(lib.ct_bn_group_reduce_bwd_copy(ctypes.addressof(arr), len(items), B, N, _ptr(sums), _ptr(local), _stream()),
-                   "ct_bn_group_reduce_bwd_copy")
-        work = dist.all_reduce(sums, group=group, async_op=True)
-        _sync_stats_collectives += 1
-        work.wait()
-        _lib.check(lib.ct_bn_group_apply_bwd(ctypes.addressof(arr), len(items), B, N, _ptr(sums), _ptr(count), _stream()),
-                   "ct_bn_group_apply_bwd")
-        c0 = 0
-        for it in items:
-            out.append((local[Ct + c0:Ct + c0 + it["C"]], local[c0:c0 + it["C"]]))
-            c0 += it["C"]
-        return out
-    sb, c0 = sums.data_ptr(), 0
-    for it in items:
-        _lib.check(lib.ct_bn_reduce_bwd(it["x"], it["xbs"], _ptr(it["w"]), _ptr(it["b"]), _ptr(it["mean"]), _ptr(it["rstd"]),
-                                        it["gy"], it["gybs"], sb + 4 * c0, sb + 4 * (Ct + c0), B, it["C"], N, int(it["relu"]),
-                                        _stream()), "ct_bn_reduce_bwd")
-        c0 += it["C"]
-    local = sums.clone()                                                  # this rank's g_bias / g_weight
+    arr = _bn_bwd_table(items)
+    local = torch.empty_like(sums)                                        # this rank's g_bias / g_weight: written by the same launches
+    for first, run in _bn_runs(n):
+        _lib.check(lib.ct_bn_group_reduce_bwd(ctypes.addressof(arr), n, first, run, B, N, _ptr(sums), _ptr(local), _stream()),
+                   "ct_bn_group_reduce_bwd")
     work = dist.all_reduce(sums, group=group, async_op=True)             # non-blocking, as in _bn_group_fwd
     _sync_stats_collectives += 1
     work.wait()
-    c0 = 0
+    for first, run in _bn_runs(n):
+        _lib.check(lib.ct_bn_group_apply_bwd(ctypes.addressof(arr), n, first, run, B, N, _ptr(sums), _ptr(count), _stream()),
+                   "ct_bn_group_apply_bwd")
+    out, c0 = [], 0
     for it in items:
-        _lib.check(lib.ct_bn_apply_bwd_amax(it["x"], it["xbs"], _ptr(it["w"]), _ptr(it["b"]), _ptr(it["mean"]), _ptr(it["rstd"]),
-                                            it["gy"], it["gybs"], sb + 4 * c0, sb + 4 * (Ct + c0), _ptr(count), it["gx"], it["gxbs"],
-                                            it.get("amax"), B, it["C"], N, int(it["relu"]), _stream()), "ct_bn_apply_bwd")
         out.append((local[Ct + c0:Ct + c0 + it["C"]], local[c0:c0 + it["C"]]))
         c0 += it["C"]
     return out
@@ -1484,7 +1453,7 @@ _BN_TYPES = (torch.nn.BatchNorm1d, torch.nn.SyncBatchNorm)
 
 def bn_relu_eligible(bn, x, channels=None):
     """True when `bn` (an nn.BatchNorm1d, exactly) applied to x (or, with `channels`, to a slice of that many of its
-    channels) can run as ct_bn_relu_*: training mode with running statistics and a fixed momentum, affine, CUDA fp32
+    channels) can run as ct_bn_group_*: training mode with running statistics and a fixed momentum, affine, CUDA fp32
     [B,C,N] contiguous, and a shape the register-resident kernels take (ct_bn_relu_supported)."""
     C = x.size(1) if channels is None and x.dim() == 3 else channels
     if not (type(bn) in _BN_TYPES and bn.training and bn.affine and bn.track_running_stats
@@ -1543,7 +1512,7 @@ def _bn_eval_norm_ok(bn, B, C, N):
 
 def bn_eval_eligible(bn, x, channels=None, residual=None):
     """True when `bn` applied to x (or, with `channels`, to a slice of that many of its channels) can run as
-    ct_bn_eval_fwd: an nn.BatchNorm1d / nn.SyncBatchNorm (exactly) in eval mode, affine, with running statistics; x CUDA
+    ct_bn_eval_group_fwd: an nn.BatchNorm1d / nn.SyncBatchNorm (exactly) in eval mode, affine, with running statistics; x CUDA
     fp32 [B,C,N] contiguous and 16-byte aligned; a shape ct_bn_eval_supported takes; and nothing for autograd to record
     (grad mode off, or none of x, the affine parameters and `residual` requires grad)."""
     if not (BN_EVAL and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()
@@ -1563,26 +1532,16 @@ def _bn_eval_item(bn, x_ptr, xbs, y_ptr, ybs, relu, res=None, rbs=0, amax=None):
 
 
 def _bn_eval_group(items, B, N):
-    """Run eval norms over the same (B, N): ONE ct_bn_eval_group_fwd launch for 2..BN_GROUP_MAX of them, one launch per norm
-    otherwise (a single norm, more than BN_GROUP_MAX, or CLOUDCT_BN_GROUP=0), as _bn_group_fwd.  items: _bn_eval_item dicts."""
+    """Run eval norms over the same (B, N) (ct_bn_eval_group_fwd), over the runs of _bn_runs as _bn_group_fwd.  items:
+    _bn_eval_item dicts."""
     lib = _lib.load()
-    if 1 < len(items) <= _lib.BN_GROUP_MAX and BN_GROUP_LAUNCH:
-        arr = (_lib.BnFwdItem * len(items))()
-        for e, it in zip(arr, items):
-            e.x, e.x_batch_stride, e.weight, e.bias = it["x"], it["xbs"], _ptr(it["w"]), _ptr(it["b"])
-            e.running_mean, e.running_var = _ptr(it["rm"]), _ptr(it["rv"])
-            e.residual, e.residual_batch_stride, e.y, e.y_batch_stride = it["res"], it["rbs"], it["y"], it["ybs"]
-            e.amax_out, e.C, e.eps, e.relu = it["amax"], it["C"], it["eps"], it["relu"]
-        _lib.check(lib.ct_bn_eval_group_fwd(ctypes.addressof(arr), len(items), B, N, _stream()), "ct_bn_eval_group_fwd")
-        return
-    for it in items:
-        _lib.check(lib.ct_bn_eval_fwd(it["x"], it["xbs"], _ptr(it["w"]), _ptr(it["b"]), _ptr(it["rm"]), _ptr(it["rv"]), it["res"],
-                                      it["rbs"], it["y"], it["ybs"], it["amax"], B, it["C"], N, it["eps"], it["relu"], _stream()),
-                   "ct_bn_eval_fwd")
+    arr = _bn_fwd_table(items)
+    for first, run in _bn_runs(len(items)):
+        _lib.check(lib.ct_bn_eval_group_fwd(_at(arr, first), run, B, N, _stream()), "ct_bn_eval_group_fwd")
 
 
 def bn_eval(x, bn, relu=True, residual=None):
-    """relu?(bn(x)) [+ residual] of an eval-mode norm in one pass (ct_bn_eval_fwd); the caller checked
+    """relu?(bn(x)) [+ residual] of an eval-mode norm in one pass (ct_bn_eval_group_fwd); the caller checked
     bn_eval_eligible(bn, x, residual=residual).  Reads the running statistics, writes nothing but the result, which carries
     its per-channel maxima for the pointwise GEMM that reads it next."""
     _dev(x, residual)

@@ -32,8 +32,12 @@ extern "C" {
  * removed, since version 1 — a stale library selected by CLOUDCT_LIB fails this check instead of failing at symbol binding.
  * (The test-hook flag CT_DEBUG_NO_WIDE was added later without a bump: an additive debug bit, no symbol or signature changed.
  * The neighbour-search entry points ct_nbr_* and the item assembly ct_kp_items were added under version 2 as well: additive
- * symbols, which the loader's missing-symbol scan checks.  ct_completion_items was added the same way.) */
-#define CT_ABI_VERSION 2
+ * symbols, which the loader's missing-symbol scan checks.  ct_completion_items was added the same way.)
+ * 3: the item table is the only norm interface.  Removed: the positional forms ct_bn_relu_fwd / _bwd (and _amax), ct_bn_stats_fwd,
+ * ct_bn_apply_fwd / _bwd (and _amax), ct_bn_reduce_bwd, ct_bn_eval_fwd, ct_adain_fwd / _bwd (and _amax) — a single norm is a table
+ * with n = 1 — and ct_bn_group_reduce_bwd_copy, whose sums_copy is now a nullable argument of ct_bn_group_reduce_bwd.  Changed:
+ * the four exchange phases ct_bn_group_{stats,apply}_fwd / {reduce,apply}_bwd take the whole table plus the run of items to launch. */
+#define CT_ABI_VERSION 3
 
 /* status codes */
 #define CT_OK 0
@@ -296,17 +300,11 @@ int ct_so3_exp_bwd(const float* log_R, const float* g_R, float* g_log_R, int H, 
  * write), longer channels and rows that are not float4-addressable are re-read per pass.
  * ---------------------------------------------------------------------- */
 int ct_bn_relu_supported(int B, int C, int N);
-int ct_bn_relu_fwd(const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                   float* running_mean, float* running_var, long long* num_batches_tracked, const float* residual,
-                   long long residual_batch_stride, float* y, long long y_batch_stride, float* save_mean,
-                   float* save_rstd, int B, int C, int N, float eps, float momentum, int relu, ct_stream_t s);
-int ct_bn_relu_bwd(const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                   const float* save_mean, const float* save_rstd, const float* gy, long long gy_batch_stride,
-                   float* gx, long long gx_batch_stride, float* g_weight, float* g_bias, int B, int C, int N, int relu,
-                   ct_stream_t s);
-/* Several norms over the same (B, N) in ONE launch (n <= 8): the key / values norms of a block's heads on channel ranges of the
- * stacked projection, the heads' `after` norms on ranges of the concatenation (layers/multihead_ct.py:89-91,67-68) — one
- * workgroup per channel of every norm.  Fields as the arguments of ct_bn_relu_fwd_amax / ct_bn_relu_bwd_amax. */
+/* One to eight norms over the same (B, N) in ONE launch — a single norm is a table with n = 1; the key / values norms of a
+ * block's heads on channel ranges of the stacked projection, the heads' `after` norms on ranges of the concatenation
+ * (layers/multihead_ct.py:89-91,67-68) are tables of several — one workgroup per channel of every norm.  amax_out f32[C]
+ * (nullable): max |y| (after ReLU and skip) / max |g_x| per channel, a by-product of the pass — the operand maxima
+ * ct_pw_gemm needs for the pointwise convolution that reads y / g_x next (n_amax = C). */
 typedef struct {
   const float* x; long long x_batch_stride; const float* weight; const float* bias; float* running_mean; float* running_var;
   long long* num_batches_tracked; const float* residual; long long residual_batch_stride; float* y; long long y_batch_stride;
@@ -319,91 +317,44 @@ typedef struct {
 } ct_bn_bwd_item;
 int ct_bn_group_fwd(const ct_bn_fwd_item* items, int n, int B, int N, ct_stream_t s);
 int ct_bn_group_bwd(const ct_bn_bwd_item* items, int n, int B, int N, ct_stream_t s);
-/* The same group around ONE statistics exchange between ranks (SyncBatchNorm, train_segmentation.py:128): every phase of
- * all n norms in one launch — 2 launches + 1 collective per group and direction instead of 2 n + 1.  Ct = sum of the items' C,
- * item i's channels start at c0_i:
+/* The same group around ONE statistics exchange between ranks — nn.SyncBatchNorm under data parallelism
+ * (train_segmentation.py:128-130 converts every BatchNorm of the model): every phase of the group's norms in one launch — 2
+ * launches + 1 collective per group and direction instead of 2 n + 1.  `items` is the WHOLE group (n >= 1, not capped): Ct
+ * = sum of all n items' C and item i's channel offset c0_i in the buffers below come from all of them.  A call launches the
+ * items [first, first + run), 1 <= run <= 8; first = 0, run = n is the whole group at once.  A bad range is CT_EINVAL.
  *   ct_bn_group_stats_fwd : local f32[2 Ct + 1] = [mean | sum (x - mean)^2 | count] of THIS rank's batch (only x, C and
- *                           x_batch_stride of the items are read);
- *   ct_bn_group_apply_fwd : gathered f32[world][2 Ct + 1] (the ranks' `local` blocks, one all_gather) -> y, save_mean,
- *                           save_rstd, running statistics, amax_out of every item; count_total f32[1] = values per channel
- *                           of the whole job;
+ *                           x_batch_stride of the items are read); the count is written by the run that holds item 0;
+ *   ct_bn_group_apply_fwd : gathered f32[world][2 Ct + 1] (the ranks' `local` blocks, one all_gather), merged per channel by
+ *                           the parallel-variance rule -> y, save_mean, save_rstd, running statistics, amax_out of the run's
+ *                           items; count_total f32[1] (nullable) = values per channel of the whole job (run of item 0);
  *   ct_bn_group_reduce_bwd: sums f32[2 Ct] = [sum g' | sum g' xhat] of this rank (g_weight / g_bias / gx of the items unused);
- *   ct_bn_group_apply_bwd : sums all-reduced over the ranks + count -> gx, amax_out of every item. */
-int ct_bn_group_stats_fwd(const ct_bn_fwd_item* items, int n, int B, int N, float* local, ct_stream_t s);
-int ct_bn_group_apply_fwd(const ct_bn_fwd_item* items, int n, int B, int N, const float* gathered, int world,
-                          float* count_total, ct_stream_t s);
-int ct_bn_group_reduce_bwd(const ct_bn_bwd_item* items, int n, int B, int N, float* sums, ct_stream_t s);
-/* the same, leaving a second copy of the sums in sums_copy f32[2 Ct] (same layout): the all_reduce runs in place on `sums`, the copy
- * stays this rank's g_bias / g_weight (torch: grad of the SyncBatchNorm's affine parameters is local, DDP averages it) — one launch
- * less per norm group than cloning the buffer */
-int ct_bn_group_reduce_bwd_copy(const ct_bn_bwd_item* items, int n, int B, int N, float* sums, float* sums_copy, ct_stream_t s);
-int ct_bn_group_apply_bwd(const ct_bn_bwd_item* items, int n, int B, int N, const float* sums, const float* count,
-                          ct_stream_t s);
-/* The same two with amax_out f32[C] (nullable): max |y| (after ReLU and skip) / max |g_x| per channel, a by-product of the
- * pass — the operand maxima ct_pw_gemm needs for the pointwise convolution that reads y / g_x next (n_amax = C). */
-int ct_bn_relu_fwd_amax(const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                        float* running_mean, float* running_var, long long* num_batches_tracked,
-                        const float* residual, long long residual_batch_stride, float* y, long long y_batch_stride,
-                        float* save_mean, float* save_rstd, float* amax_out, int B, int C, int N, float eps,
-                        float momentum, int relu, ct_stream_t s);
-int ct_bn_relu_bwd_amax(const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                        const float* save_mean, const float* save_rstd, const float* gy, long long gy_batch_stride,
-                        float* gx, long long gx_batch_stride, float* g_weight, float* g_bias, float* amax_out,
-                        int B, int C, int N, int relu, ct_stream_t s);
-
-/* The same norm split around an exchange of statistics between ranks — nn.SyncBatchNorm under data parallelism
- * (train_segmentation.py:128-130 converts every BatchNorm of the model).  Forward: ct_bn_stats_fwd on every norm of a
- * block into ONE buffer (mean[C], sum of squared deviations[C] per norm, this rank's count), one all_gather of that
- * buffer, then ct_bn_apply_fwd per norm, which merges the ranks' statistics itself (parallel-variance rule) and
- * normalises (+ ReLU, + skip).  Backward: ct_bn_reduce_bwd per norm into one buffer (these are also this rank's weight /
- * bias gradients), one all_reduce(sum), ct_bn_apply_bwd.  g_mean / g_m2 point at rank 0's entries of the norm's channels
- * inside the gathered buffer, g_count at rank 0's count; rank r's are g_stride floats further. */
-int ct_bn_stats_fwd(const float* x, long long x_batch_stride, float* mean, float* m2, float* count /* nullable */,
-                    int B, int C, int N, ct_stream_t s);
-int ct_bn_apply_fwd(const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                    const float* g_mean, const float* g_m2, const float* g_count, int world, long long g_stride,
-                    float* running_mean, float* running_var, long long* num_batches_tracked, const float* residual,
-                    long long residual_batch_stride, float* y, long long y_batch_stride, float* save_mean,
-                    float* save_rstd, float* count_total /* nullable */, int B, int C, int N, float eps, float momentum,
-                    int relu, ct_stream_t s);
-int ct_bn_reduce_bwd(const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                     const float* mean, const float* rstd, const float* gy, long long gy_batch_stride,
-                     float* sum_g, float* sum_gxhat, int B, int C, int N, int relu, ct_stream_t s);
-int ct_bn_apply_bwd(const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                    const float* mean, const float* rstd, const float* gy, long long gy_batch_stride,
-                    const float* sum_g, const float* sum_gxhat, const float* count, float* gx, long long gx_batch_stride,
-                    int B, int C, int N, int relu, ct_stream_t s);
-/* ct_bn_apply_fwd / _bwd with amax_out f32[C] (nullable), as ct_bn_relu_fwd_amax / _bwd_amax. */
-int ct_bn_apply_fwd_amax(const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                         const float* g_mean, const float* g_m2, const float* g_count, int world, long long g_stride,
-                         float* running_mean, float* running_var, long long* num_batches_tracked, const float* residual,
-                         long long residual_batch_stride, float* y, long long y_batch_stride, float* save_mean,
-                         float* save_rstd, float* count_total, float* amax_out, int B, int C, int N, float eps,
-                         float momentum, int relu, ct_stream_t s);
-int ct_bn_apply_bwd_amax(const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                         const float* mean, const float* rstd, const float* gy, long long gy_batch_stride,
-                         const float* sum_g, const float* sum_gxhat, const float* count, float* gx,
-                         long long gx_batch_stride, float* amax_out, int B, int C, int N, int relu, ct_stream_t s);
+ *                           sums_copy f32[2 Ct] (nullable) receives the same values: the all_reduce runs in place on `sums`,
+ *                           the copy stays this rank's g_bias / g_weight (torch: the gradient of a SyncBatchNorm's affine
+ *                           parameters is local, DDP averages it) — one launch less than cloning the buffer;
+ *   ct_bn_group_apply_bwd : sums all-reduced over the ranks + count -> gx, amax_out of the run's items. */
+int ct_bn_group_stats_fwd(const ct_bn_fwd_item* items, int n, int first, int run, int B, int N, float* local, ct_stream_t s);
+int ct_bn_group_apply_fwd(const ct_bn_fwd_item* items, int n, int first, int run, int B, int N, const float* gathered,
+                          int world, float* count_total, ct_stream_t s);
+int ct_bn_group_reduce_bwd(const ct_bn_bwd_item* items, int n, int first, int run, int B, int N, float* sums,
+                           float* sums_copy /* nullable */, ct_stream_t s);
+int ct_bn_group_apply_bwd(const ct_bn_bwd_item* items, int n, int first, int run, int B, int N, const float* sums,
+                          const float* count, ct_stream_t s);
 
 /* Eval-mode BatchNorm1d / SyncBatchNorm (+ ReLU, + skip): a per-channel affine on the stored statistics, forward only,
  *   y[b,c,n] = relu?( ((x - running_mean[c]) * rstd_c) * weight[c] + bias[c] ) [+ residual[b,c,n]],
  *   rstd_c = 1 / sqrt(running_var[c] + eps)
- * in torch's operation order (the mean is subtracted first).  x, y, residual and their batch strides as ct_bn_relu_fwd (0 =
+ * in torch's operation order (the mean is subtracted first).  x, y, residual and their batch strides as ct_bn_group_fwd (0 =
  * contiguous; a channel slice of a wider tensor is read, a channel range of a concatenation written, where it lies); y does
  * not overlap x or residual.  Rows that are 16-byte addressable (N % 4 == 0, strides % 4 == 0, aligned bases) move as
  * float4, all others float by float.  Nothing is written but y and amax_out f32[C] (nullable): max |y| per channel of the
- * values as stored (after ReLU and skip), the contract of ct_bn_relu_fwd_amax; the running statistics are read-only here
+ * values as stored (after ReLU and skip), the contract of ct_bn_group_fwd's; the running statistics are read-only here
  * and both are required.  Shapes: B*N >= 1 (one value per channel is legal: no variance is taken), B*N < 2^31
  * (ct_bn_eval_supported != 0).  Channels are cut over several workgroups when the launch has few of them; a channel
  * whose amax_out is asked for stays with one workgroup, which folds the maximum itself (no second launch, no atomics).
- * ct_bn_eval_group_fwd: n <= 8 norms over the same (B, N) in one launch, as ct_bn_group_fwd; of ct_bn_fwd_item it reads x,
+ * ct_bn_eval_group_fwd: 1 <= n <= 8 norms over the same (B, N) in one launch, as ct_bn_group_fwd; of ct_bn_fwd_item it reads x,
  * weight, bias, running_mean, running_var, residual, y, amax_out, the strides, C, eps and relu — save_mean, save_rstd,
  * momentum and num_batches_tracked are ignored and may be null.  Added under CT_ABI_VERSION 2 (additive). */
 int ct_bn_eval_supported(int B, int C, int N);
-int ct_bn_eval_fwd(const float* x, long long x_batch_stride, const float* weight, const float* bias,
-                   const float* running_mean, const float* running_var, const float* residual,
-                   long long residual_batch_stride, float* y, long long y_batch_stride, float* amax_out,
-                   int B, int C, int N, float eps, int relu, ct_stream_t s);
 int ct_bn_eval_group_fwd(const ct_bn_fwd_item* items, int n, int B, int N, ct_stream_t s);
 
 /* ------------------------------------------------------------------------
@@ -417,15 +368,11 @@ int ct_bn_eval_group_fwd(const ct_bn_fwd_item* items, int n, int B, int N, ct_st
  * Every [B,C,N] argument has a batch stride in floats (0 = C*N, contiguous; >= C*N for a channel slice of a wider
  * tensor — keys_bn / values_bn on the halves of keys_values_pred, multihead_ct_adain.py:108-111); `residual` (nullable)
  * is added after the ReLU (the union's skip connection, :216), its cotangent is gy itself.
+ * One to eight adaptive instance norms over the same (B, N) in ONE launch, as ct_bn_group_fwd / _bwd (a single norm is a table
+ * with n = 1).  B >= 1, N >= 1 and every C >= 1: the empty shapes are the caller's.  amax_out (nullable):
+ * amax_out[b * amax_batch_stride + c] = max |y| / max |g_x| of row (b, c), a by-product of the pass (amax_batch_stride 0 = C)
+ * — operand maxima for ct_pw_gemm, as ct_bn_group_fwd's.
  * ---------------------------------------------------------------------- */
-int ct_adain_fwd(const float* x, long long x_batch_stride, const float* gamma_beta, const float* residual,
-                 long long residual_batch_stride, float* y, long long y_batch_stride, float* mean, float* rstd,
-                 int B, int C, int N, float eps, int relu, ct_stream_t s);
-int ct_adain_bwd(const float* x, long long x_batch_stride, const float* gamma_beta, const float* mean, const float* rstd,
-                 const float* gy, long long gy_batch_stride, float* gx, long long gx_batch_stride, float* g_gamma_beta,
-                 int B, int C, int N, int relu, ct_stream_t s);
-/* Several adaptive instance norms over the same (B, N) in ONE launch (n <= 8), as ct_bn_group_fwd / _bwd: fields as the
- * arguments of ct_adain_fwd_amax / ct_adain_bwd_amax. */
 typedef struct {
   const float* x; long long x_batch_stride; const float* gamma_beta; const float* residual; long long residual_batch_stride;
   float* y; long long y_batch_stride; float* mean; float* rstd; float* amax_out; long long amax_batch_stride; int C; float eps;
@@ -441,15 +388,6 @@ typedef struct {
 } ct_adain_bwd_item;
 int ct_adain_group_fwd(const ct_adain_fwd_item* items, int n, int B, int N, ct_stream_t s);
 int ct_adain_group_bwd(const ct_adain_bwd_item* items, int n, int B, int N, ct_stream_t s);
-/* The same two with amax_out (nullable): amax_out[b * amax_batch_stride + c] = max |y| / max |g_x| of row (b, c), a by-product of
- * the pass (amax_batch_stride 0 = C) — operand maxima for ct_pw_gemm, as ct_bn_relu_fwd_amax. */
-int ct_adain_fwd_amax(const float* x, long long x_batch_stride, const float* gamma_beta, const float* residual,
-                      long long residual_batch_stride, float* y, long long y_batch_stride, float* mean, float* rstd,
-                      float* amax_out, long long amax_batch_stride, int B, int C, int N, float eps, int relu, ct_stream_t s);
-int ct_adain_bwd_amax(const float* x, long long x_batch_stride, const float* gamma_beta, const float* mean,
-                      const float* rstd, const float* gy, long long gy_batch_stride, float* gx, long long gx_batch_stride,
-                      float* g_gamma_beta, float* amax_out, long long amax_batch_stride, int B, int C, int N, int relu,
-                      ct_stream_t s);
 
 /* ------------------------------------------------------------------------
  * Grouped 3^dim convolution over the rasterised planes / volumes, stride 1, padding 1
@@ -597,8 +535,8 @@ int ct_emd_bwd(const float* xyz1, const float* xyz2, const float* g_dist, const 
  *                partial sums added in a fixed order: deterministic)
  * amax_a / amax_b: device f32[n_amax_*] whose maximum is (an upper bound within ~2^10 of) max |.| of the
  * whole operand tensor; the GEMM folds them when it starts.  Either ct_amax_f32's ct_amax_len()
- * partial maxima, or what the kernel that produced the operand left behind (ct_bn_relu_fwd_amax /
- * _bwd_amax: one per channel; ct_adain_*_amax: one per (cloud, channel)); n_amax_* <= 32768.  NULL = scale 1 (the caller then guarantees
+ * partial maxima, or what the kernel that produced the operand left behind (ct_bn_group_fwd /
+ * _bwd: one per channel; ct_adain_group_*: one per (cloud, channel)); n_amax_* <= 32768.  NULL = scale 1 (the caller then guarantees
  * |values| < 65504).  Co, Ci, N multiples of 4,
  * 16-byte aligned pointers -> CT_EINVAL otherwise.  Workspace: ct_pw_gemm_workspace_bytes.
  * ---------------------------------------------------------------------- */
@@ -630,7 +568,7 @@ int ct_pw_gemm(int mode, const float* a, const float* b, float* out, const float
  * every output's own operands.  Both operands of the weight gradient can be row-scaled (its summed index is the point, not
  * the channel); in the forward and the data gradient the activation's summed index IS the channel, so it keeps one scale
  * (rows_b is ignored there) and its term of the bound stays M_b * sum_k |a_ik|: a contribution that is itself 2^-17 of the
- * row's largest.  Producers of per-row maxima: ct_bn_relu_*_amax / ct_bn_apply_*_amax (per channel), ct_adain_*_amax (per
+ * row's largest.  Producers of per-row maxima: ct_bn_group_* / ct_bn_eval_group_fwd (per channel), ct_adain_group_* (per
  * (cloud, channel)), ct_amax_rows_f32 (x f32[B,C,N] -> f32[C]), ct_pw_prep_weight_rs (W -> rowmax f32[ceil(Ci/32)][Co] for
  * CT_PW_FWD, colmax f32[ceil(Co/32)][Ci] for CT_PW_DGRAD_T, and W^T).  n_amax_* <= 32768.  rows_* = 0: ct_pw_gemm. */
 int ct_amax_rows_f32(const float* x, int B, int C, int N, float* amax, ct_stream_t s);

@@ -1,4 +1,4 @@
-"""Fused adaptive instance norm (ct_adain_fwd / ct_adain_bwd) against the CPU oracle's
+"""Fused adaptive instance norm (ct_adain_group_fwd / ct_adain_group_bwd) against the CPU oracle's
 restatement of AdaIn1dUpd (oracle/ref_cpu.py:_adain, reference layers/utils.py:82-97),
 forward and backward (oracle gradients by torch autograd in float64), tolerance 1e-4."""
 import numpy as np
@@ -82,14 +82,39 @@ def test_forward_style_fuses_the_following_relu():
 
 
 def test_adain_abi_rejects_bad_arguments():
-    from cloud_transformers_amd import _lib
+    import ctypes
+    from cloud_transformers_amd import _lib, ops
     lib = _lib.load()
     x = torch.zeros(1, 1, 4, device="cuda")
-    assert lib.ct_adain_fwd(None, 0, None, None, 0, None, 0, None, None, 1, 1, 4, 1e-5, 0, None) == -1
     p = x.data_ptr()
-    assert lib.ct_adain_fwd(p, 0, p, None, 0, p, 0, p, p, -1, 1, 4, 1e-5, 0, None) == -1
-    assert lib.ct_adain_fwd(p, 2, p, None, 0, p, 0, p, p, 1, 1, 4, 1e-5, 0, None) == -1      # batch stride < C*N
-    assert lib.ct_adain_fwd(None, 0, None, None, 0, None, 0, None, None, 0, 8, 4, 1e-5, 0, None) == 0      # empty batch: nothing to do
+
+    def call(B=1, N=4, n=1, **fields):
+        it = _lib.AdainFwdItem(**{**dict(x=p, gamma_beta=p, y=p, mean=p, rstd=p, C=1, eps=1e-5), **fields})
+        return lib.ct_adain_group_fwd(ctypes.addressof(it), n, B, N, None)
+
+    assert call(x=None, gamma_beta=None, y=None, mean=None, rstd=None) == -1
+    assert call(B=-1) == -1
+    assert call(x_batch_stride=2) == -1                      # batch stride < C*N
+    assert call(n=0) == -1 and call(n=9) == -1 and lib.ct_adain_group_fwd(None, 1, 1, 4, None) == -1
+    assert call(B=0) == -1 and call(N=0) == -1 and call(C=0) == -1     # the empty shapes are the caller's (ops.adain below)
+    torch.cuda.synchronize()
+    assert float(x.abs().max()) == 0.0                       # nothing was launched
+    # an empty batch and rows without points are no-ops of ops.adain: the empty result, zero gamma / beta gradients, no launch
+    fwd, bwd, calls = lib.ct_adain_group_fwd, lib.ct_adain_group_bwd, []
+    lib.ct_adain_group_fwd = lambda *a: (calls.append("fwd"), fwd(*a))[1]
+    lib.ct_adain_group_bwd = lambda *a: (calls.append("bwd"), bwd(*a))[1]
+    try:
+        for B, C, N in ((0, 8, 4), (2, 3, 0)):
+            xe = torch.zeros(B, C, N, device="cuda", requires_grad=True)
+            gb = torch.randn(B, 2, C, device="cuda", requires_grad=True)
+            y = ops.adain(xe, gb, 1e-5, True)
+            assert y.shape == (B, C, N)
+            y.sum().backward()
+            assert xe.grad.shape == (B, C, N)
+            assert gb.grad.shape == (B, 2, C) and float(gb.grad.abs().sum()) == 0.0
+    finally:
+        lib.ct_adain_group_fwd, lib.ct_adain_group_bwd = fwd, bwd
+    assert calls == []
 
 
 @pytest.mark.parametrize("N", [4096, 20000])          # register-resident rows and the strided kernel

@@ -1,4 +1,4 @@
-"""CPU-side checks of the eval-mode BatchNorm path: the three ct_bn_eval_* symbols are exported and reject bad arguments
+"""CPU-side checks of the eval-mode BatchNorm path: the two ct_bn_eval_* symbols are exported and reject bad arguments
 before anything touches a device, and ops.bn_eval_eligible keeps CPU tensors, training-mode norms and norms without
 running statistics on the modules' own path."""
 import ctypes
@@ -17,7 +17,7 @@ def lib():
 def test_symbols_are_exported(lib):
     from cloud_transformers_amd import _lib
     raw = ctypes.CDLL(_lib.LIB_PATH)
-    for name in ("ct_bn_eval_supported", "ct_bn_eval_fwd", "ct_bn_eval_group_fwd"):
+    for name in ("ct_bn_eval_supported", "ct_bn_eval_group_fwd"):
         assert hasattr(raw, name) and name in _lib.SIGNATURES
     assert lib.ct_bn_eval_supported(6, 48, 8192) == 1
     assert lib.ct_bn_eval_supported(1, 3, 1) == 1                # one value per channel: legal without a variance
@@ -33,7 +33,9 @@ def test_argument_checks_without_gpu(lib):
     B, C, N = 2, 8, 64
 
     def call(x=p, xbs=0, w=p, b=p, rm=p, rv=p, res=None, rbs=0, y=p, ybs=0, B=B, N=N):
-        return lib.ct_bn_eval_fwd(x, xbs, w, b, rm, rv, res, rbs, y, ybs, None, B, C, N, 1e-5, 1, None)
+        it = _lib.BnFwdItem(x=x, x_batch_stride=xbs, weight=w, bias=b, running_mean=rm, running_var=rv, residual=res,
+                            residual_batch_stride=rbs, y=y, y_batch_stride=ybs, C=C, eps=1e-5, relu=1)
+        return lib.ct_bn_eval_group_fwd(ctypes.addressof(it), 1, B, N, None)
 
     assert call(x=None) == -1 and call(w=None) == -1 and call(b=None) == -1 and call(y=None) == -1
     assert call(rm=None) == -1 and call(rv=None) == -1 and call(rm=None, rv=None) == -1

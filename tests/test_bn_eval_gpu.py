@@ -1,4 +1,4 @@
-"""GPU parity of the eval-mode BatchNorm kernels (ct_bn_eval_fwd / ct_bn_eval_group_fwd) and of their entry points in
+"""GPU parity of the eval-mode BatchNorm kernels (ct_bn_eval_group_fwd, tables of one and of several norms) and of their entry points in
 ops (bn_eval, split_bn_eval, join_bn_relu_eval, union_keys_values_eval) against torch's eval batch norm in float64 on
 the CPU, and the dispatch of layers.multihead_ct.run_after.
 
@@ -208,7 +208,9 @@ def test_abi_argument_checks():
     B, C, N = 2, 8, 64
 
     def call(x=p, xbs=0, w=p, b=p, rm=p, rv=p, res=None, rbs=0, y=p, ybs=0, B=B, N=N):
-        return lib.ct_bn_eval_fwd(x, xbs, w, b, rm, rv, res, rbs, y, ybs, None, B, C, N, 1e-5, 1, None)
+        it = _lib.BnFwdItem(x=x, x_batch_stride=xbs, weight=w, bias=b, running_mean=rm, running_var=rv, residual=res,
+                            residual_batch_stride=rbs, y=y, y_batch_stride=ybs, C=C, eps=1e-5, relu=1)
+        return lib.ct_bn_eval_group_fwd(ctypes.addressof(it), 1, B, N, None)
 
     assert call(x=None) == -1 and call(w=None) == -1 and call(b=None) == -1 and call(y=None) == -1
     assert call(rv=None) == -1 and call(rm=None) == -1           # one running buffer only
@@ -231,7 +233,7 @@ def test_abi_argument_checks():
 
 
 def _expected_split(B, N, channels):
-    """The runs a channel without maxima is cut into (include/cloudct.h, ct_bn_eval_fwd): towards 1024 workgroups in the
+    """The runs a channel without maxima is cut into (include/cloudct.h, ct_bn_eval_group_fwd): towards 1024 workgroups in the
     launch, never below 2048 quads (floats on the scalar path) a run."""
     per = B * (N // 4) if N % 4 == 0 else B * N
     return max(1, min(-(-1024 // channels), per // 2048)), per
@@ -257,7 +259,7 @@ def test_channels_cut_over_several_workgroups(B, Ca, Cb, N, runs, short):
     xc = x.cuda()
     with torch.no_grad():
         outs = ops.split_bn_eval(xc, mods[0], mods[1])
-        single = torch.full((B, Cb, N), float("nan"), device="cuda")          # one norm, one launch: ct_bn_eval_fwd, no maxima
+        single = torch.full((B, Cb, N), float("nan"), device="cuda")          # one norm, one launch: a table of one, no maxima
         ops._bn_eval_group([ops._bn_eval_item(mods[1], xc.data_ptr() + Ca * N * 4, (Ca + Cb) * N, single.data_ptr(), 0, False)], B, N)
     for y, (ref, bound), name in zip(outs, refs, ("first", "second")):
         _check(y, ref, bound, "cut %s B%d N%d runs %d" % (name, B, N, split))
@@ -267,7 +269,7 @@ def test_channels_cut_over_several_workgroups(B, Ca, Cb, N, runs, short):
 
 @pytest.mark.parametrize("grouped", [True, False])
 def test_more_norms_than_a_group_holds_run_one_launch_each(grouped):
-    """Nine norms into one concatenation: more than BN_GROUP_MAX, so one ct_bn_eval_fwd launch per norm; with
+    """Nine norms into one concatenation: more than BN_GROUP_MAX, so one ct_bn_eval_group_fwd launch of n = 1 per norm; with
     ops.BN_GROUP_LAUNCH off (CLOUDCT_BN_GROUP=0) two norms take the same route."""
     from cloud_transformers_amd import _lib, ops
     torch.manual_seed(6)
@@ -279,16 +281,15 @@ def test_more_norms_than_a_group_holds_run_one_launch_each(grouped):
     ref, bound = torch.cat([p[0] for p in parts], dim=1), torch.cat([p[1] for p in parts], dim=1)
     mods = [m.cuda() for m in mods]
     lib = _lib.load()
-    single, group, calls = lib.ct_bn_eval_fwd, lib.ct_bn_eval_group_fwd, []
-    lib.ct_bn_eval_fwd = lambda *a: (calls.append("one"), single(*a))[1]
-    lib.ct_bn_eval_group_fwd = lambda *a: (calls.append("group"), group(*a))[1]
+    group, calls = lib.ct_bn_eval_group_fwd, []
+    lib.ct_bn_eval_group_fwd = lambda items, n, *a: (calls.append(n), group(items, n, *a))[1]
     switch = ops.BN_GROUP_LAUNCH
     ops.BN_GROUP_LAUNCH = grouped
     try:
         with torch.no_grad():
             y = ops.join_bn_relu_eval([x.cuda() for x in xs], mods)
     finally:
-        lib.ct_bn_eval_fwd, lib.ct_bn_eval_group_fwd, ops.BN_GROUP_LAUNCH = single, group, switch
-    assert calls == ["one"] * len(Cs), calls
+        lib.ct_bn_eval_group_fwd, ops.BN_GROUP_LAUNCH = group, switch
+    assert calls == [1] * len(Cs), calls
     _check(y, ref, bound, "join of %d norms, one launch each" % len(Cs))
     assert torch.equal(ops.amax_of(y).view(-1), y.abs().amax(dim=(0, 2)))

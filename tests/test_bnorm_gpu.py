@@ -1,5 +1,7 @@
-"""GPU parity of the fused training-mode BatchNorm1d + ReLU (ct_bn_relu_fwd / _bwd) against torch's own
+"""GPU parity of the fused training-mode BatchNorm1d + ReLU (ct_bn_group_fwd / _bwd) against torch's own
 F.batch_norm + relu evaluated in float64 on the CPU: output, running statistics, and all three gradients."""
+import ctypes
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -98,10 +100,110 @@ def test_abi_argument_checks():
     assert lib.ct_bn_relu_supported(1, 4, 1) == 0                # one value per channel has no variance
     buf = torch.zeros(1 << 16, device="cuda")
     p = buf.data_ptr()
-    assert lib.ct_bn_relu_fwd(p, 0, p, p, p, None, None, None, 0, p, 0, p, p, 2, 8, 64, 1e-5, 0.1, 1, None) == -1           # one running buffer only
-    assert lib.ct_bn_relu_fwd(p, 8 * 64 - 4, p, p, None, None, None, None, 0, p, 0, p, p, 2, 8, 64, 1e-5, 0.1, 1, None) == -1  # batch stride < C*N
-    assert lib.ct_bn_relu_fwd(p, 0, p, p, None, None, None, None, 0, p, 0, p, p, 1, 8, 1, 1e-5, 0.1, 1, None) == -1         # B*N < 2
-    assert lib.ct_bn_relu_fwd(None, 0, p, p, None, None, None, None, 0, p, 0, p, p, 2, 8, 64, 1e-5, 0.1, 1, None) == -1
+
+    def call(B=2, N=64, **fields):
+        it = _lib.BnFwdItem(**{**dict(x=p, weight=p, bias=p, y=p, save_mean=p, save_rstd=p, C=8, eps=1e-5, momentum=0.1, relu=1),
+                               **fields})
+        return lib.ct_bn_group_fwd(ctypes.addressof(it), 1, B, N, None)
+
+    assert call(running_mean=p) == -1                            # one running buffer only
+    assert call(x_batch_stride=8 * 64 - 4) == -1                 # batch stride < C*N
+    assert call(B=1, N=1) == -1                                  # B*N < 2
+    assert call(x=None) == -1
+    items = (_lib.BnFwdItem * 9)()
+    for e in items:
+        e.x = e.weight = e.bias = e.y = e.save_mean = e.save_rstd = p
+        e.C, e.eps, e.momentum, e.relu = 8, 1e-5, 0.1, 1
+    addr = ctypes.addressof(items)
+    assert lib.ct_bn_group_fwd(addr, 0, 2, 64, None) == -1
+    assert lib.ct_bn_group_fwd(addr, 9, 2, 64, None) == -1
+    assert lib.ct_bn_group_fwd(None, 1, 2, 64, None) == -1
+    torch.cuda.synchronize()
+    assert float(buf.abs().max()) == 0.0                         # nothing was launched
+
+
+def _exchange_phases(_lib, lib, n, runs, B, N, fwd_fields, bwd_fields, Ct):
+    """The four exchange phases (world = 1: `gathered` is `local`) over a table of n norms, launched as `runs` = [(first, run)];
+    every output goes to a fresh buffer pre-filled with NaN.  Returns the buffers by name."""
+    nan = lambda *shape: torch.full(shape, float("nan"), device="cuda")
+    Cs = [f["C"] for f in fwd_fields]
+    o = dict(local=nan(2 * Ct + 1), count=nan(1), sums=nan(2 * Ct), sums_copy=nan(2 * Ct))
+    for name in ("y", "gx"):
+        o[name] = [nan(B, C, N) for C in Cs]
+    for name in ("save_mean", "save_rstd", "amax_y", "amax_gx"):
+        o[name] = [nan(C) for C in Cs]
+    fwd, bwd = (_lib.BnFwdItem * n)(), (_lib.BnBwdItem * n)()
+    for i in range(n):
+        for k, v in fwd_fields[i].items():
+            setattr(fwd[i], k, v)
+        fwd[i].y, fwd[i].save_mean, fwd[i].save_rstd, fwd[i].amax_out = (o[k][i].data_ptr() for k in ("y", "save_mean", "save_rstd", "amax_y"))
+        for k, v in bwd_fields[i].items():
+            setattr(bwd[i], k, v)
+        bwd[i].save_mean, bwd[i].save_rstd, bwd[i].gx, bwd[i].amax_out = (o[k][i].data_ptr() for k in ("save_mean", "save_rstd", "gx", "amax_gx"))
+    fa, ba = ctypes.addressof(fwd), ctypes.addressof(bwd)
+    for first, run in runs:
+        assert lib.ct_bn_group_stats_fwd(fa, n, first, run, B, N, o["local"].data_ptr(), None) == 0
+    for first, run in runs:
+        assert lib.ct_bn_group_apply_fwd(fa, n, first, run, B, N, o["local"].data_ptr(), 1, o["count"].data_ptr(), None) == 0
+    for first, run in runs:
+        assert lib.ct_bn_group_reduce_bwd(ba, n, first, run, B, N, o["sums"].data_ptr(), o["sums_copy"].data_ptr(), None) == 0
+    for first, run in runs:
+        assert lib.ct_bn_group_apply_bwd(ba, n, first, run, B, N, o["sums"].data_ptr(), o["count"].data_ptr(), None) == 0
+    torch.cuda.synchronize()
+    return o, (fwd, bwd)
+
+
+# one shape per kernel family of bn_*_launch_table: register-resident, scalar loop (N % 4 != 0), float4 loop (B*N > 32768)
+@pytest.mark.parametrize("B,N", [(2, 260), (2, 259), (2, 16388)])
+def test_exchange_phases_launch_a_run_of_the_table(B, N):
+    """The range arguments of the four exchange phases: three norms launched as one run of three and as three runs of one
+    write the same bits everywhere (the buffer layout belongs to the table, not to the launch), the whole-group result is
+    torch's batch norm, and bad ranges are refused before anything is launched."""
+    from cloud_transformers_amd import _lib
+    lib = _lib.load()
+    torch.manual_seed(N)
+    Cs = (3, 8, 5)
+    Ct, n = sum(Cs), len(Cs)
+    xs = [torch.randn(B, C, N, device="cuda") * 2 for C in Cs]
+    ws = [torch.rand(C, device="cuda") + 0.5 for C in Cs]
+    bs = [torch.randn(C, device="cuda") for C in Cs]
+    gys = [torch.randn(B, C, N, device="cuda") for C in Cs]
+    fwd_fields = [dict(x=x.data_ptr(), weight=w.data_ptr(), bias=b.data_ptr(), C=C, eps=1e-5, momentum=0.1, relu=1)
+                  for x, w, b, C in zip(xs, ws, bs, Cs)]
+    bwd_fields = [dict(x=x.data_ptr(), weight=w.data_ptr(), bias=b.data_ptr(), gy=gy.data_ptr(), C=C, relu=1)
+                  for x, w, b, gy, C in zip(xs, ws, bs, gys, Cs)]
+    whole, _ = _exchange_phases(_lib, lib, n, [(0, 3)], B, N, fwd_fields, bwd_fields, Ct)
+    single, (fwd, bwd) = _exchange_phases(_lib, lib, n, [(0, 1), (1, 1), (2, 1)], B, N, fwd_fields, bwd_fields, Ct)
+    for name in ("local", "count", "sums", "sums_copy"):
+        assert not bool(torch.isnan(whole[name]).any()), name
+        assert torch.equal(whole[name], single[name]), name
+    for name in ("y", "save_mean", "save_rstd", "gx", "amax_y", "amax_gx"):
+        for a, b in zip(whole[name], single[name]):
+            assert not bool(torch.isnan(a).any()), name
+            assert torch.equal(a, b), name
+    assert float(whole["count"]) == B * N and torch.equal(whole["sums"], whole["sums_copy"])
+    for i, (x, w, b, gy) in enumerate(zip(xs, ws, bs, gys)):
+        xr = x.clone().requires_grad_(True)
+        want = torch.relu(F.batch_norm(xr, None, None, w, b, True, 0.1, 1e-5))
+        want.backward(gy)
+        ey, egx = float((whole["y"][i] - want.detach()).abs().max()), float((whole["gx"][i] - xr.grad).abs().max())
+        print("B%d N%d norm %d: max |y - torch| %.3e, max |gx - torch| %.3e" % (B, N, i, ey, egx))
+        assert ey < 1e-5 and egx < 1e-5
+        assert torch.equal(whole["amax_y"][i], whole["y"][i].abs().amax(dim=(0, 2)))
+        assert torch.equal(whole["amax_gx"][i], whole["gx"][i].abs().amax(dim=(0, 2)))
+    # bad ranges: refused by every phase, nothing launched
+    probe = {k: (v.clone() if torch.is_tensor(v) else [t.clone() for t in v]) for k, v in single.items()}
+    fa, ba = ctypes.addressof(fwd), ctypes.addressof(bwd)
+    lp, cp, sp, scp = (single[k].data_ptr() for k in ("local", "count", "sums", "sums_copy"))
+    for first, run in ((1, 3), (3, 1), (0, 0), (0, 9), (-1, 1)):
+        assert lib.ct_bn_group_stats_fwd(fa, n, first, run, B, N, lp, None) == -1
+        assert lib.ct_bn_group_apply_fwd(fa, n, first, run, B, N, lp, 1, cp, None) == -1
+        assert lib.ct_bn_group_reduce_bwd(ba, n, first, run, B, N, sp, scp, None) == -1
+        assert lib.ct_bn_group_apply_bwd(ba, n, first, run, B, N, sp, cp, None) == -1
+    torch.cuda.synchronize()
+    for k, v in single.items():
+        for a, b in zip([v] if torch.is_tensor(v) else v, [probe[k]] if torch.is_tensor(v) else probe[k]):
+            assert torch.equal(a, b), k
 
 
 def test_split_bn_equals_the_two_modules_on_split_views():

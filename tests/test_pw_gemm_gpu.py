@@ -2,6 +2,8 @@
 operands: the three operand arrangements, ragged sizes, operand magnitudes from 1e-7 to 1e6, exact integer data (layout),
 non-finite propagation, determinism of the chunked weight gradient, and the autograd layer on top
 (layers/multihead_ct.py:31-33: nn.Conv1d(k=1))."""
+import ctypes
+
 import pytest
 import torch
 
@@ -149,7 +151,7 @@ def test_pointwise_layer_against_float64_conv1d(bias):
 
 
 def test_batchnorm_kernels_leave_the_channel_maxima_of_what_they_write():
-    """ct_bn_relu_fwd_amax / _bwd_amax: max |y| (after ReLU and skip) and max |g_x| per channel, bit for bit the maxima of the
+    """amax_out of ct_bn_group_fwd / _bwd: max |y| (after ReLU and skip) and max |g_x| per channel, bit for bit the maxima of the
     tensors they wrote — the operand scale of the pointwise GEMM that reads them next, without a pass over them."""
     _needs_split16()
     from cloud_transformers_amd import ops
@@ -259,23 +261,22 @@ def test_syncbn_apply_kernels_leave_the_channel_maxima():
     w, b = torch.rand(C, device="cuda") + 0.5, torch.randn(C, device="cuda")
     st = torch.cuda.current_stream().cuda_stream
     local = torch.empty(2 * C + 1, device="cuda")
-    _lib.check(lib.ct_bn_stats_fwd(x.data_ptr(), 0, local.data_ptr(), local.data_ptr() + 4 * C, local.data_ptr() + 8 * C, B, C, N, st), "stats")
     y, mean, rstd, count, am = torch.empty_like(x), torch.empty(C, device="cuda"), torch.empty(C, device="cuda"), torch.empty(1, device="cuda"), \
         torch.empty(C, device="cuda")
-    _lib.check(lib.ct_bn_apply_fwd_amax(x.data_ptr(), 0, w.data_ptr(), b.data_ptr(), local.data_ptr(), local.data_ptr() + 4 * C,
-                                        local.data_ptr() + 8 * C, 1, 2 * C + 1, None, None, None, None, 0, y.data_ptr(), 0, mean.data_ptr(),
-                                        rstd.data_ptr(), count.data_ptr(), am.data_ptr(), B, C, N, 1e-5, 0.1, 1, st), "apply_fwd")
+    fwd = _lib.BnFwdItem(x=x.data_ptr(), weight=w.data_ptr(), bias=b.data_ptr(), y=y.data_ptr(), save_mean=mean.data_ptr(),
+                         save_rstd=rstd.data_ptr(), amax_out=am.data_ptr(), C=C, eps=1e-5, momentum=0.1, relu=1)
+    _lib.check(lib.ct_bn_group_stats_fwd(ctypes.addressof(fwd), 1, 0, 1, B, N, local.data_ptr(), st), "stats")
+    _lib.check(lib.ct_bn_group_apply_fwd(ctypes.addressof(fwd), 1, 0, 1, B, N, local.data_ptr(), 1, count.data_ptr(), st), "apply_fwd")
     assert torch.equal(am, y.abs().amax(dim=(0, 2)))
     want = torch.relu(torch.nn.functional.batch_norm(x, None, None, w, b, True, 0.1, 1e-5))
     assert float((y - want).abs().max()) < 1e-5
     gy = torch.randn_like(x)
     sums = torch.empty(2 * C, device="cuda")
-    _lib.check(lib.ct_bn_reduce_bwd(x.data_ptr(), 0, w.data_ptr(), b.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gy.data_ptr(), 0,
-                                    sums.data_ptr(), sums.data_ptr() + 4 * C, B, C, N, 1, st), "reduce")
     gx, gam = torch.empty_like(x), torch.empty(C, device="cuda")
-    _lib.check(lib.ct_bn_apply_bwd_amax(x.data_ptr(), 0, w.data_ptr(), b.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gy.data_ptr(), 0,
-                                        sums.data_ptr(), sums.data_ptr() + 4 * C, count.data_ptr(), gx.data_ptr(), 0, gam.data_ptr(),
-                                        B, C, N, 1, st), "apply_bwd")
+    bwd = _lib.BnBwdItem(x=x.data_ptr(), weight=w.data_ptr(), bias=b.data_ptr(), save_mean=mean.data_ptr(), save_rstd=rstd.data_ptr(),
+                         gy=gy.data_ptr(), gx=gx.data_ptr(), amax_out=gam.data_ptr(), C=C, relu=1)
+    _lib.check(lib.ct_bn_group_reduce_bwd(ctypes.addressof(bwd), 1, 0, 1, B, N, sums.data_ptr(), None, st), "reduce")
+    _lib.check(lib.ct_bn_group_apply_bwd(ctypes.addressof(bwd), 1, 0, 1, B, N, sums.data_ptr(), count.data_ptr(), st), "apply_bwd")
     assert torch.equal(gam, gx.abs().amax(dim=(0, 2)))
 
 

@@ -1,4 +1,4 @@
-"""Training-mode BatchNorm1d + ReLU, forward + backward as one HIP graph: the fused ct_bn_relu kernels against torch's
+"""Training-mode BatchNorm1d + ReLU, forward + backward as one HIP graph: the fused ct_bn_group_fwd / _bwd kernels (a table of one norm) against torch's
 BatchNorm1d (MIOpen) + ReLU at the blocks' shapes — register-resident channels (B*N <= 32768) and the loop kernels."""
 import os
 import sys

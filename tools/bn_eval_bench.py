@@ -2,7 +2,7 @@
 
     python tools/bn_eval_bench.py [--part kernel|model|all] [--rounds 3] [--iters 20]
 
-(a) kernel: eval BatchNorm1d + ReLU (+ the skip connection) as one ct_bn_eval_fwd launch against torch's modules, at
+(a) kernel: eval BatchNorm1d + ReLU (+ the skip connection) as one ct_bn_eval_group_fwd launch (a table of one norm) against torch's modules, at
     tools/bn_bench.py's shapes and at a key norm's (B6 C48 N8192, cut over several workgroups); each replayed from a HIP
     graph and timed with device events after a warm-up.  The fused pass moves read x + write y (+ read residual): its
     bytes per second are printed as a share of the chip's measured float4 copy rate (6.29 TB/s).

@@ -1,6 +1,7 @@
 """Training BatchNorm forward / backward at B8 N4096 for the channel counts of the blocks: the one-workgroup-per-channel kernels
-(ct_bn_relu_fwd / _bwd) against the split statistics + apply kernels (ct_bn_stats_fwd + ct_bn_apply_fwd, ct_bn_reduce_bwd +
-ct_bn_apply_bwd, as the SyncBatchNorm path uses them with world = 1); us per call, HIP events."""
+(ct_bn_group_fwd / _bwd on a table of one norm) against the split statistics + apply kernels (ct_bn_group_stats_fwd +
+ct_bn_group_apply_fwd, ct_bn_group_reduce_bwd + ct_bn_group_apply_bwd on the same table, as the SyncBatchNorm path uses them,
+with world = 1); us per call, HIP events."""
 import os, sys, ctypes
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
@@ -16,7 +17,6 @@ def t(fn, iters=50):
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / iters * 1e3
 B, N = 8, 4096
-f = ctypes.c_float
 for C in (32, 48, 64, 128, 256, 512, 768, 1024):
     x = torch.randn(B, C, N, device="cuda"); y = torch.empty_like(x); gy = torch.randn_like(x); gx = torch.empty_like(x)
     w = torch.rand(C, device="cuda") + 0.5; b = torch.randn(C, device="cuda")
@@ -24,18 +24,20 @@ for C in (32, 48, 64, 128, 256, 512, 768, 1024):
     mean = torch.empty(C, device="cuda"); rstd = torch.empty(C, device="cuda")
     gw = torch.empty(C, device="cuda"); gb = torch.empty(C, device="cuda")
     loc = torch.empty(2 * C + 1, device="cuda"); cnt = torch.empty(1, device="cuda")
-    sg = torch.empty(C, device="cuda"); sgx = torch.empty(C, device="cuda")
-    one_f = lambda: _lib.check(lib.ct_bn_relu_fwd(_ptr(x), 0, _ptr(w), _ptr(b), _ptr(rm), _ptr(rv), _ptr(nbt), None, 0, _ptr(y), 0, _ptr(mean), _ptr(rstd),
-                                                  B, C, N, f(1e-5), f(0.1), 1, _stream()), "f")
-    one_b = lambda: _lib.check(lib.ct_bn_relu_bwd(_ptr(x), 0, _ptr(w), _ptr(b), _ptr(mean), _ptr(rstd), _ptr(gy), 0, _ptr(gx), 0, _ptr(gw), _ptr(gb),
-                                                  B, C, N, 1, _stream()), "b")
+    sums = torch.empty(2 * C, device="cuda")
+    fi = _lib.BnFwdItem(x=_ptr(x), weight=_ptr(w), bias=_ptr(b), running_mean=_ptr(rm), running_var=_ptr(rv), num_batches_tracked=_ptr(nbt),
+                        y=_ptr(y), save_mean=_ptr(mean), save_rstd=_ptr(rstd), C=C, eps=1e-5, momentum=0.1, relu=1)
+    bi = _lib.BnBwdItem(x=_ptr(x), weight=_ptr(w), bias=_ptr(b), save_mean=_ptr(mean), save_rstd=_ptr(rstd), gy=_ptr(gy), gx=_ptr(gx),
+                        g_weight=_ptr(gw), g_bias=_ptr(gb), C=C, relu=1)
+    fa, ba = ctypes.addressof(fi), ctypes.addressof(bi)
+    one_f = lambda: _lib.check(lib.ct_bn_group_fwd(fa, 1, B, N, _stream()), "f")
+    one_b = lambda: _lib.check(lib.ct_bn_group_bwd(ba, 1, B, N, _stream()), "b")
     def split_f():
-        _lib.check(lib.ct_bn_stats_fwd(_ptr(x), 0, loc.data_ptr(), loc.data_ptr() + 4 * C, loc.data_ptr() + 8 * C, B, C, N, _stream()), "s")
-        _lib.check(lib.ct_bn_apply_fwd(_ptr(x), 0, _ptr(w), _ptr(b), loc.data_ptr(), loc.data_ptr() + 4 * C, loc.data_ptr() + 8 * C, 1, 2 * C + 1,
-                                       _ptr(rm), _ptr(rv), _ptr(nbt), None, 0, _ptr(y), 0, _ptr(mean), _ptr(rstd), _ptr(cnt), B, C, N, f(1e-5), f(0.1), 1, _stream()), "a")
+        _lib.check(lib.ct_bn_group_stats_fwd(fa, 1, 0, 1, B, N, _ptr(loc), _stream()), "s")
+        _lib.check(lib.ct_bn_group_apply_fwd(fa, 1, 0, 1, B, N, _ptr(loc), 1, _ptr(cnt), _stream()), "a")
     def split_b():
-        _lib.check(lib.ct_bn_reduce_bwd(_ptr(x), 0, _ptr(w), _ptr(b), _ptr(mean), _ptr(rstd), _ptr(gy), 0, _ptr(sg), _ptr(sgx), B, C, N, 1, _stream()), "r")
-        _lib.check(lib.ct_bn_apply_bwd(_ptr(x), 0, _ptr(w), _ptr(b), _ptr(mean), _ptr(rstd), _ptr(gy), 0, _ptr(sg), _ptr(sgx), _ptr(cnt), _ptr(gx), 0, B, C, N, 1, _stream()), "ab")
+        _lib.check(lib.ct_bn_group_reduce_bwd(ba, 1, 0, 1, B, N, _ptr(sums), None, _stream()), "r")
+        _lib.check(lib.ct_bn_group_apply_bwd(ba, 1, 0, 1, B, N, _ptr(sums), _ptr(cnt), _stream()), "ab")
     of, ob = t(one_f), t(one_b)
     y1 = y.clone(); gx1 = gx.clone()
     sf, sb = t(split_f), t(split_b)
