@@ -18,7 +18,10 @@ package's layers and checkpoints stay interchangeable.
   train_segmentation_kpconv.py).  `shapenet_completion` (the `completion` task; `data.category_path`, `data.partial_path`,
   `data.gt_path`, `data.n_renders`, `data.input_size`, `data.gt_size` as configs/inpainting.yaml has them) reads the
   ShapeNetCompletion .pcd files (data/completion.py) and prepares every batch on the device; one validation per epoch
-  (train_completion.py, train_inpainter.py).  The image_point variant stays out of scope.
+  (train_completion.py, train_inpainter.py).  `scanobjectnn_device` (the `classification_scanobjectnn` task; `data.path`,
+  `data.path_val`, `data.batch_size_val`, optional `data.subsample`) keeps the ScanObjectNN split on the device and gathers
+  every batch there (data/scanobjectnn.py), validates every `train.val_step` epochs with the reference's accuracies and keeps
+  the `best` / `macc_best` checkpoints (train_classification.py).  The image_point variant stays out of scope.
 """
 import copy
 import datetime
@@ -179,9 +182,16 @@ class SyntheticClouds(torch.utils.data.Dataset):
 def make_dataset(cfg, task, n_classes, length=64, channels=3, train=True):
     """The dataset `data.kind` of the config names: "synthetic" (default), "scanobjectnn" or "s3dis" (data/datasets.py);
     "s3dis_kpconv" gives the (train, validation) Areas of train_kpconv.load_kpconv_areas (`train=False`: no train Areas);
-    "shapenet_completion" the TRAIN (`train=False`: VAL) subset of data/completion.py's ShapeNetDataLoader."""
+    "shapenet_completion" the TRAIN (`train=False`: VAL) subset of data/completion.py's ShapeNetDataLoader;
+    "scanobjectnn_device" the ScanObjectNN of `data.path` (`train=False`: `data.path_val`) with its items left to the device."""
     data = cfg["data"]
     kind = str(data.get("kind", "synthetic")).lower()
+    if kind == "scanobjectnn_device":
+        assert task == "classification_scanobjectnn", "data.kind scanobjectnn_device is the classification_scanobjectnn task"
+        from .data import datasets as D
+        # (augmentation and subsampling happen on the device: the host object only reads, centres and normalises)
+        return D.ScanObjectNN(data["path"] if train else data["path_val"], train=False, subsample=None,
+                              center=data.get("center", True), normalize=data.get("normalize", True))
     if kind == "shapenet_completion":
         assert task == "completion", "ShapeNet completion items are (partial cloud, complete cloud): the completion task"
         from .data.completion import DatasetSubset, shapenet_loader
@@ -201,7 +211,8 @@ def make_dataset(cfg, task, n_classes, length=64, channels=3, train=True):
         assert task == "segmentation", "S3DIS blocks are (points, labels): the segmentation task"
         return D.Indoor3DSemSeg(data["path"], data["num_points"], train=train, aug=bool(data.get("aug", train)),
                                 test_area=data.get("test_area", "Area_5"), data_precent=float(data.get("data_precent", 1.0)))
-    raise ValueError("data.kind must be synthetic, scanobjectnn, s3dis, s3dis_kpconv or shapenet_completion (got %r)" % kind)
+    raise ValueError("data.kind must be synthetic, scanobjectnn, scanobjectnn_device, s3dis, s3dis_kpconv or shapenet_completion "
+                     "(got %r)" % kind)
 
 
 class Trainer:
@@ -216,7 +227,12 @@ class Trainer:
     validation every `train.val_step` epochs and after the last, `generator_epoch_{e}.t7` / `g_opt_epoch_{e}.t7` every
     `train.save_each_epoch` epochs; `dataset` may be the (train, validation) Areas — train_kpconv.py).  With `data.kind:
     shapenet_completion` the completion task's batches are prepared on the device (data/completion.py CompletionBatches)
-    and `fit` validates once per epoch (`validate`)."""
+    and `fit` validates once per epoch (`validate`).  "classification_scanobjectnn" (selected by `data.kind:
+    scanobjectnn_device` too; `dataset` may be a data.datasets.ScanObjectNN or a data.scanobjectnn.DeviceScanObjectNN):
+    loss = (1 - seg_weight) * CE(out[0], label) + seg_weight * BCE-with-logits(out[1][:, 0, 0], mask) of train_classification.py:
+    201-204 (the model's output is indexed, so the reference's three-output classifier and two-output models both fit),
+    batches gathered on the device (data/scanobjectnn.py ScanBatches; `n_classes` sizes the per-class accuracies), validation
+    every `train.val_step` epochs, `generator_epoch_{e}.t7` every `train.save_each_epoch` epochs (train_classification.py)."""
 
     def __init__(self, cfg, task, n_classes, device=None, dist=None, exp_name="exp", dataset_length=64, make_dirs=True,
                  channels=3, dataset=None):
@@ -225,7 +241,11 @@ class Trainer:
             from .train_kpconv import kpconv_config
             task, self.cfg = "segmentation_kpconv", kpconv_config(cfg)
             cfg = self.cfg
-        self.task, self.dist = task, dist
+        if task == "classification_scanobjectnn" or str(cfg["data"].get("kind", "")).lower() == "scanobjectnn_device":
+            from .train_classification import classification_config
+            task, self.cfg = "classification_scanobjectnn", classification_config(cfg)
+            cfg = self.cfg
+        self.task, self.dist, self.n_classes = task, dist, n_classes
         self.rank = dist.get_rank() if parallel._active(dist) else 0
         self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         model_cfg = dict(cfg["model"])
@@ -274,7 +294,11 @@ class Trainer:
         data = dataset if dataset is not None else make_dataset(cfg, task, n_classes, length=dataset_length, channels=channels)
         self.kp, self.clip, self.val_records = None, None, []
         self.shapenet, self.val_loader, self.best_val = str(cfg["data"].get("kind", "")).lower() == "shapenet_completion", None, None
-        if self.shapenet:
+        self.scan, self.best_acc, self.best_macc = task == "classification_scanobjectnn", float("-inf"), float("-inf")
+        if self.scan:
+            self.sampler = None                          # (ScanBatches holds torch's DistributedSampler itself)
+            self.loader = self._scan_batches(data, train=True)
+        elif self.shapenet:
             from .data.completion import CompletionBatches
             assert task == "completion", "data.kind shapenet_completion is the completion task"
             self.sampler = torch.utils.data.distributed.DistributedSampler(data) if parallel._active(dist) else None
@@ -296,7 +320,27 @@ class Trainer:
         self.ce, self.bce = nn.CrossEntropyLoss(), nn.BCEWithLogitsLoss()
         self.iters = 0
 
+    def _scan_batches(self, data, train):
+        """ScanBatches over `data` (a host ScanObjectNN is uploaded first) with the config's sizes, this rank's shard."""
+        from .data.scanobjectnn import DeviceScanObjectNN, ScanBatches
+        d = self.cfg["data"]
+        ds = data if isinstance(data, DeviceScanObjectNN) else DeviceScanObjectNN(data, self.device)
+        active = parallel._active(self.dist)
+        return ScanBatches(ds, d["batch_size"] if train else d["batch_size_val"], train=train, seed=int(d["seed"]) + (0 if train else 7919), rank=self.rank,
+                           world=self.dist.get_world_size() if active else 1, drop_last=bool(d.get("drop_last", False)) and train,
+                           subsample=d.get("subsample"), sigma=float(d["jitter_sigma"]), clip=float(d["jitter_clip"]))
+
+    def _scan_losses(self, batch):
+        """(loss, loss_cls, loss_seg, model output) of train_classification.py:199-204."""
+        pcd, label, mask = batch
+        out = self.model(pcd)
+        w = float(self.cfg["train"]["seg_weight"])
+        cls_loss, seg_loss = self.ce(out[0], label), self.bce(out[1][:, 0, 0], mask)
+        return (1 - w) * cls_loss + w * seg_loss, cls_loss, seg_loss, out
+
     def _loss(self, batch):
+        if self.task == "classification_scanobjectnn":
+            return self._scan_losses(batch)[0]
         if self.task == "segmentation_kpconv":
             from .train_kpconv import masked_cross_entropy
             points, mask, features, labels = batch
@@ -385,14 +429,68 @@ class Trainer:
         self.val_records.append(rec)
         return [rec]
 
+    def _validate_scan(self, epoch, dataset=None):
+        """train_classification.py:286-374: eval mode, no grad, `data.path_val` in batches of `data.batch_size_val`; the three
+        losses averaged over the batches and the ranks, the accuracies from ClassificationMeter's counts all-reduced over the
+        ranks (counts and sums stay on the device until the two reads at the end).  As in the reference the shards are padded
+        to equal length, so with several ranks a few clouds count twice.  `best` / `macc_best`: a strictly higher cls_acc /
+        m_acc than any validation before (the first one always is, unless m_acc is NaN: a class absent from the split)."""
+        import json
+        from .data.scanobjectnn import ClassificationMeter
+        if self.val_loader is None or dataset is not None:
+            data = dataset if dataset is not None else make_dataset(self.cfg, self.task, self.n_classes, train=False)
+            self.val_loader = self._scan_batches(data, train=False)
+        model = self.model
+        was_training = model.training
+        model.eval()
+        self.val_loader.set_epoch(epoch if isinstance(epoch, int) else 0)
+        meter = ClassificationMeter(self.n_classes)
+        sums = torch.zeros(4, dtype=torch.float64, device=self.device)            # loss, loss_cls, loss_seg, batches
+        with torch.no_grad():
+            for batch in self.val_loader:
+                loss, cls_loss, seg_loss, out = self._scan_losses(batch)
+                sums += torch.stack([loss, cls_loss, seg_loss, torch.ones_like(loss)]).double()
+                meter.update(out[0], out[1], batch[1], batch[2])
+        model.train(was_training)
+        if parallel._active(self.dist):
+            self.dist.all_reduce(sums)
+            meter.reduce(self.dist)
+        s = sums.tolist()
+        n = max(s[3], 1.0)
+        rec = {"epoch": epoch, "iters": self.iters, "batches": int(s[3]), "loss": s[0] / n, "loss_cls": s[1] / n, "loss_seg": s[2] / n}
+        rec.update(meter.result())
+        rec["best"], rec["macc_best"] = bool(rec["cls_acc"] > self.best_acc), bool(rec["m_acc"] > self.best_macc)
+        if rec["best"]:
+            self.best_acc = rec["cls_acc"]
+        if rec["macc_best"]:
+            self.best_macc = rec["m_acc"]
+        if self.rank == 0:
+            step = epoch if isinstance(epoch, int) else self.iters
+            for k in ("loss", "loss_cls", "loss_seg", "cls_acc", "seg_acc", "m_acc"):
+                self.writer.add_scalar("val/" + k, rec[k], global_step=step)
+            if self.exp_dir is not None:
+                with open(str(Path(self.exp_dir) / "classification_val.jsonl"), "a") as f:
+                    f.write(json.dumps(rec) + "\n")
+                for flag in ("best", "macc_best"):
+                    if rec[flag]:
+                        parallel.save_exp_parallel([self.model, self.optimizer], ["generator", "g_opt"], exp_path=self.exp_dir,
+                                                   epoch=0, epoch_name=flag)
+        self.val_records.append(rec)
+        return [rec]
+
     def validate(self, num_votes=None, epoch=None):
         """segmentation_kpconv: one validation of `num_votes` vote passes (train_kpconv.KPConvData.validate) on the unwrapped
         model; the records go to the writer and, on rank 0, to <exp>/kpconv_val.jsonl.  Returns them.
         completion (`num_votes` is not used): one pass over the VAL subset (`_validate_completion`), its record appended to
-        <exp>/completion_val.jsonl and, on a new minimum of the loss, `generator_best_0.t7` / `g_opt_best_0.t7` saved."""
+        <exp>/completion_val.jsonl and, on a new minimum of the loss, `generator_best_0.t7` / `g_opt_best_0.t7` saved.
+        classification_scanobjectnn (`num_votes` is not used): one pass over `data.path_val` (`_validate_scan`), its record
+        (losses, cls_acc, seg_acc, m_acc, class_acc) appended to <exp>/classification_val.jsonl; `generator_best_0.t7` /
+        `g_opt_best_0.t7` saved on a new best cls_acc, `generator_macc_best_0.t7` / `g_opt_macc_best_0.t7` on a new best m_acc."""
         import json
         if self.task == "completion":
             return self._validate_completion(epoch)
+        if self.task == "classification_scanobjectnn":
+            return self._validate_scan(epoch)
         records = self.kp.validate(parallel._plain_module(self.model), num_votes, epoch)
         if self.rank == 0:
             for rec in records:
@@ -532,6 +630,8 @@ class Trainer:
         for epoch in range(tr["num_epochs"]):
             if self.sampler is not None:
                 self.sampler.set_epoch(epoch)
+            if self.scan:
+                self.loader.set_epoch(epoch)
             self.model.train()
             end = time.time()
             for batch in self.loader:
@@ -570,6 +670,13 @@ class Trainer:
             if self.shapenet:
                 flush()
                 self.validate(epoch=epoch)                # train_inpainter.py:253-311: once per epoch
+            if self.scan:
+                # train_classification.py:281-286: checkpoints and validation by the 0-based epoch
+                flush()
+                if epoch > 0 and epoch % int(tr["save_each_epoch"]) == 0:
+                    self.save(epoch=epoch)
+                if epoch % int(tr["val_step"]) == 0:
+                    self.validate(epoch=epoch)
         flush()
         if self.kp is not None:
             self.validate(int(tr["final_votes"]), "Last")

@@ -36,7 +36,8 @@ extern "C" {
  * 3: the item table is the only norm interface.  Removed: the positional forms ct_bn_relu_fwd / _bwd (and _amax), ct_bn_stats_fwd,
  * ct_bn_apply_fwd / _bwd (and _amax), ct_bn_reduce_bwd, ct_bn_eval_fwd, ct_adain_fwd / _bwd (and _amax) — a single norm is a table
  * with n = 1 — and ct_bn_group_reduce_bwd_copy, whose sums_copy is now a nullable argument of ct_bn_group_reduce_bwd.  Changed:
- * the four exchange phases ct_bn_group_{stats,apply}_fwd / {reduce,apply}_bwd take the whole table plus the run of items to launch. */
+ * the four exchange phases ct_bn_group_{stats,apply}_fwd / {reduce,apply}_bwd take the whole table plus the run of items to launch.
+ * (ct_scan_items was added under version 3 without a bump: an additive symbol, which the loader's missing-symbol scan checks.) */
 #define CT_ABI_VERSION 3
 
 /* status codes */
@@ -670,6 +671,34 @@ int ct_kp_items(const int64_t* qidx, const int64_t* count, const int64_t* perm, 
  * ---------------------------------------------------------------------- */
 int ct_completion_items(const float* partial, const int64_t* perm, const float* u_dup, const float* sphere, float scale,
                         int B, int n_in, int64_t gt, float* part, float* noise, int32_t* count, ct_stream_t s);
+
+/* ------------------------------------------------------------------------
+ * Batch assembly of the ScanObjectNN classification items (datasets/scanobjectnn.py:102-122: jitter,
+ * rotation about y, subsample; the collate and the permute of train_classification.py:195), one
+ * launch, every random draw passed in.  Added under CT_ABI_VERSION 3 (additive, as ct_kp_items and
+ * ct_completion_items).
+ *
+ * The split stays on the device: data f32[M,P,3] (centred and normalised on the host), mask u8[M,P]
+ * (0 background, 1 object), label i64[M]; M >= 1.  A batch is B rows (1 <= B <= 65535) of N slots
+ * (1 <= N <= P <= 16384): item i64[B] names the cloud of each row (repeats allowed); perm i64[B,P]
+ * (nullable) is the argsort of plain random keys, whose first N entries are a draw of N points
+ * without replacement (np.random.choice(P, N, replace=False)), NULL: slot n takes point n.
+ * Augmentation, both or neither (CT_EINVAL otherwise): rot f32[B,2] = (cos, sin) of the cloud's
+ * angle, jit f32[B,N,3] standard normal draws; sigma (finite) and clip (> 0): host floats.  The draws
+ * are finite by construction; what the clip does to a NaN draw is not specified.
+ * Per slot (b, n), each operation one fp32 rounding, in this order:
+ *   g = clamp(item[b], 0, M-1); src = perm ? clamp(perm[b,n], 0, P-1) : n; p = data[g,src];
+ *   without augmentation q = p is the output; with it d_i = min(max(sigma * jit[b,n,i], -clip), clip),
+ *   q_i = p_i + d_i (jitter before rotation), then x' = (q.x * c) - (q.z * s), y' = q.y,
+ *   z' = (q.x * s) + (q.z * c): q @ [[c,0,s],[0,1,0],[-s,0,c]].
+ * Outputs: out_points f32[B,3,N] (the model's layout: [B,3,1,N] is a view of it), out_mask f32[B,N]
+ * = mask[g,src], out_label i64[B] = label[g].  The clamps are guards; valid inputs never need them.
+ * Null pointers (other than perm, rot, jit), half an augmentation and sizes outside the limits ->
+ * CT_EINVAL before anything touches the device.
+ * ---------------------------------------------------------------------- */
+int ct_scan_items(const float* data, const uint8_t* mask, const int64_t* label, int64_t M, int P, const int64_t* item,
+                  const int64_t* perm, const float* rot, const float* jit, float sigma, float clip, int B, int N,
+                  float* out_points, float* out_mask, int64_t* out_label, ct_stream_t s);
 
 #ifdef __cplusplus
 }
