@@ -341,17 +341,34 @@ RASTER_TICKETS = os.environ.get("CLOUDCT_TICKETS", "1") != "0"      # "0": the t
 _tickets = {}
 
 
+def _capturing(device):
+    """Whether the current stream of `device` is recording a HIP graph.  Asked only where a per-stream state buffer is
+    missing from its cache (raster_tickets, grid_occupancy_ratio, mhct_core_workspace): a buffer made DURING a capture
+    lives in that graph's private pool and its zero-fill is a node of that graph alone, so it must not outlive the launch it
+    was made for — cached, every later graph on the stream would use it without an init node of its own (uninitialised if
+    it is replayed before the first one, or if that capture never finished), and the first graph would re-zero state other
+    launches depend on at every replay."""
+    with _on(device):
+        return torch.cuda.is_current_stream_capturing()
+
+
 def raster_tickets(device, force=False):
     """The arrival tickets of the backward raster passes (include/cloudct.h: ct_slice_bwd_tk / ct_splat_bwd_tk) for the
     CURRENT stream of `device`: a zeroed CT_TICKETS_BYTES buffer kept for the life of the process.  The kernels leave it zero,
     so it is initialised once; launches that share a buffer must be ordered, hence one buffer per stream (the heads of a
-    union block run side by side on their own streams, and autograd replays every backward on its forward's stream)."""
+    union block run side by side on their own streams, and autograd replays every backward on its forward's stream).
+    On a capturing stream that has no buffer yet the launch gets one of its own (_capturing above): allocated in the graph's
+    pool, zeroed by a node of the graph, not cached — the caller keeps the tensor until its launch is enqueued.  A stream
+    that ran the op eagerly before the capture (harness._capture warms up on its capture stream) keeps its cached buffer
+    and the graph gains no node."""
     if not RASTER_TICKETS and not force:
         return None
     key = (device.index, _stream(device))
     t = _tickets.get(key)
     if t is None:
-        t = _tickets[key] = torch.zeros(_lib.TICKETS_BYTES // 4, device=device, dtype=torch.int32)
+        t = torch.zeros(_lib.TICKETS_BYTES // 4, device=device, dtype=torch.int32)
+        if not _capturing(device):
+            _tickets[key] = t
     return t
 
 
@@ -388,9 +405,10 @@ class SplatKeysFn(torch.autograd.Function):
         Wa = _lib.int_array(W)
         ws_bytes = lib.ct_splat_bwd_workspace_bytes(B, H, C, N, dim, Wa, _lib.REDUCE[reduce])
         ws = torch.empty(ws_bytes, device=feat.device, dtype=torch.uint8) if ws_bytes else None
+        tk = raster_tickets(feat.device)
         with _on(feat.device):
             _lib.check(lib.ct_splat_bwd_tk(_ptr(keys), _ptr(feat), _ptr(padt), pad_code, _ptr(grid), _ptr(g_grid),
-                                           _ptr(g_feat), None, _ptr(g_keys), _ptr(ws), ws_bytes, _ptr(raster_tickets(feat.device)),
+                                           _ptr(g_feat), None, _ptr(g_keys), _ptr(ws), ws_bytes, _ptr(tk),
                                            B, H, C, N, dim, Wa, _lib.REDUCE[reduce], _stream()), "ct_splat_bwd_tk")
         return g_keys, g_feat, None, None, None, None
 
@@ -428,9 +446,10 @@ class SliceKeysFn(torch.autograd.Function):
         Wa = _lib.int_array(W)
         ws_bytes = lib.ct_slice_bwd_workspace_bytes(B, H, C, N, dim, Wa)
         ws = torch.empty(ws_bytes, device=grid.device, dtype=torch.uint8) if ws_bytes else None
+        tk = raster_tickets(grid.device)
         with _on(grid.device):
             _lib.check(lib.ct_slice_bwd_tk(_ptr(keys), _ptr(grid), _ptr(padt), pad_code, _ptr(g_out),
-                                           _ptr(g_grid), _ptr(g_keys), _ptr(ws), ws_bytes, _ptr(raster_tickets(grid.device)),
+                                           _ptr(g_grid), _ptr(g_keys), _ptr(ws), ws_bytes, _ptr(tk),
                                            B, H, C, N, dim, Wa, _stream()),
                        "ct_slice_bwd_tk")
         return g_keys, g_grid, None, None, None
@@ -1738,7 +1757,9 @@ def grid_occupancy_ratio(grid, denominator):
     key = (grid.device.index, _stream(grid.device))
     ws = _occ_ws.get(key)
     if ws is None:          # zeroed once; the kernel hands its ticket back as zero; one workspace per stream (ordered launches)
-        ws = _occ_ws[key] = torch.zeros(_lib.OCC_WORKSPACE_BYTES // 8, device=grid.device, dtype=torch.int64)
+        ws = torch.zeros(_lib.OCC_WORKSPACE_BYTES // 8, device=grid.device, dtype=torch.int64)
+        if not _capturing(grid.device):          # (made during a capture: this launch's alone, raster_tickets)
+            _occ_ws[key] = ws
     out = torch.empty((), device=grid.device, dtype=torch.float32)
     inv = occupancy_scale(denominator)
     lib = _lib.load()
@@ -1776,13 +1797,23 @@ _core_ws = {}
 def mhct_core_workspace(device, B, H, C, N, W):
     """The forward's exchange workspace for a shape, allocated and initialised (counters zeroed) ONCE per device, STREAM and
     shape: every launch leaves the counters zeroed, and launches on one stream are ordered, so the buffer is reused — two
-    blocks of one shape running side by side on two streams (the heads of a union block, user code) get a buffer each."""
+    blocks of one shape running side by side on two streams (the heads of a union block, user code) get a buffer each.
+    On a capturing stream that has none yet the launch gets a workspace of its own, zeroed by a node of the graph and
+    not cached (raster_tickets): the graph is then complete by itself, and its replays re-initialise nobody else's counters
+    or status word."""
     key = (device.index, _stream(device), B, H, C, N, tuple(W))
     ws = _core_ws.get(key)
     if ws is None:
         lib = _lib.load()
         Wa = _lib.int_array(W)
         n = lib.ct_mhct_core_workspace_bytes(B, H, C, N, len(W), Wa)
+        if _capturing(device):
+            # this launch's alone, zeroed as a whole by a fill kernel of the graph (what ct_mhct_core_workspace_init sets is
+            # all zeros).  Not the init call's memset: with it the occupancy count of a replay on fresh data came out as a
+            # mix of that replay's workgroups and the one's before it (the launch-wide done counter behind the planes'
+            # counters did not start at zero once the buffer's memory had been reused inside the graph) —
+            # tests/test_graph_replay_gpu.py::test_mhct_core_clusters
+            return torch.zeros(n, device=device, dtype=torch.uint8)
         ws = torch.empty(n, device=device, dtype=torch.uint8)
         with _on(device):
             _lib.check(lib.ct_mhct_core_workspace_init(_ptr(ws), n, B, H, C, N, len(W), Wa, _stream()), "ct_mhct_core_workspace_init")
@@ -1794,7 +1825,10 @@ def mhct_core_check(raise_on_fault=True):
     """Did a cluster of any ct_mhct_core_fwd launch so far give up waiting for its partners (include/cloudct.h: status word of
     the workspace)?  Reads the status of every cached workspace — one small copy each, AFTER synchronising: call it at points
     that wait for the device anyway (harness.fit's logging flush).  A workspace whose word is set is re-initialised; with
-    `raise_on_fault` the first such workspace raises (the affected launch wrote NaN where its results would have gone)."""
+    `raise_on_fault` the first such workspace raises (the affected launch wrote NaN where its results would have gone).
+    It sees the CACHED workspaces only, the ones created by eager launches: a graph captured on a stream without one owns
+    the workspaces of its launches (mhct_core_workspace) and re-initialises them at every replay, so a give-up inside such a
+    graph shows only as the NaNs the kernel writes."""
     lib = _lib.load()
     bad = []
     for key, ws in list(_core_ws.items()):
@@ -1875,10 +1909,11 @@ class MhctCoreFn(torch.autograd.Function):
             return g_keys, g_feat, None, g_w, g_b, None, None
         nws = lib.ct_mhct_core_bwd_workspace_bytes(B, H, C, N, dim, Wa)
         ws = torch.empty(nws, device=dev, dtype=torch.uint8)
+        tk = raster_tickets(dev)
         with _on(dev):
             _lib.check(lib.ct_mhct_core_bwd_tk(_ptr(keys), _ptr(feat), _ptr(padt), pad_code, _ptr(weight), _ptr(z), _ptr(y),
                                                _ptr(g_out), _ptr(g_feat), _ptr(g_keys), _ptr(g_w), _ptr(g_b), _ptr(ws), nws,
-                                               _ptr(raster_tickets(dev)), B, H, C, N, dim, Wa, _stream()), "ct_mhct_core_bwd_tk")
+                                               _ptr(tk), B, H, C, N, dim, Wa, _stream()), "ct_mhct_core_bwd_tk")
         return g_keys, g_feat, None, g_w, g_b, None, None
 
 

@@ -25,12 +25,8 @@ def test_ratio_equals_count_float_div(shape):
     assert torch.equal(ops.grid_occupancy_ratio(zo, K), want)
 
 
-def test_ratio_replays_from_a_graph():
+def _replays(z, K):
     from cloud_transformers_amd import ops
-    z = torch.relu(torch.randn(8, 64, 64, 64, device="cuda"))
-    K = 8 * 64
-    ops.grid_occupancy_ratio(z, K)                                     # (workspace created outside the capture)
-    torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
         out = ops.grid_occupancy_ratio(z, K)
@@ -39,3 +35,28 @@ def test_ratio_replays_from_a_graph():
         g.replay()
         torch.cuda.synchronize()
         assert torch.equal(out, (z.abs() > 1e-9).sum().float() / K)
+
+
+def test_ratio_replays_from_a_graph():
+    from cloud_transformers_amd import ops
+    z = torch.relu(torch.randn(8, 64, 64, 64, device="cuda"))
+    K = 8 * 64
+    # (this creates the workspace of the CURRENT stream; torch.cuda.graph captures on a stream of its own, which has none: the
+    #  captured launch gets a workspace from the graph's pool, zeroed by a node of the graph — ops.grid_occupancy_ratio)
+    ops.grid_occupancy_ratio(z, K)
+    torch.cuda.synchronize()
+    _replays(z, K)
+
+
+def test_ratio_replays_from_a_graph_captured_first(monkeypatch):
+    """No eager launch before the capture and an empty workspace cache: the graph owns its workspace, nothing made during the
+    capture is cached, and the eager launch behind the replays makes its stream's own."""
+    from cloud_transformers_amd import ops
+    monkeypatch.setattr(ops, "_occ_ws", {})
+    z = torch.relu(torch.randn(8, 64, 64, 64, device="cuda"))
+    K = 8 * 64
+    torch.cuda.synchronize()
+    _replays(z, K)
+    assert ops._occ_ws == {}
+    assert torch.equal(ops.grid_occupancy_ratio(z, K), (z.abs() > 1e-9).sum().float() / K)
+    assert len(ops._occ_ws) == 1
