@@ -21,7 +21,8 @@ LIB_PATH = os.environ.get("CLOUDCT_LIB") or os.path.join(LIB_DIR, "libcloudct.so
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 
 HIP_SOURCES = ["ct_raster.hip", "ct_mhct.hip", "ct_lattice.hip", "ct_gconv.hip", "ct_chamfer.hip", "ct_emd.hip",
-               "ct_adain.hip", "ct_bnorm.hip", "ct_pwgemm.hip", "ct_nbr.hip", "ct_kpitems.hip", "ct_completion.hip", "ct_scanitems.hip"]
+               "ct_adain.hip", "ct_bnorm.hip", "ct_pwgemm.hip", "ct_nbr.hip", "ct_kpitems.hip", "ct_completion.hip", "ct_scanitems.hip",
+               "ct_blockitems.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared",
                # index/weight math must round exactly like the reference's fp32 op sequence
                "-ffp-contract=off"]
@@ -84,6 +85,8 @@ NBR_MAX_CELLS = 1 << 26    # ct_nbr_* grids
 COMPLETION_N_MAX = 16384   # ct_completion_items: rows of one partial cloud
 COMPLETION_GT_MAX = 1 << 24
 SCAN_P_MAX = 16384         # ct_scan_items: points of one stored cloud
+BLOCK_P_MAX = 16384        # ct_block_items: points of one stored block
+CONFUSION_C_MAX = 64       # ct_seg_confusion: classes
 
 _lock = threading.Lock()
 _lib = None
@@ -304,6 +307,8 @@ SIGNATURES = {
     "ct_kp_items": (_i, [_vp] * 10 + [ctypes.c_int64, _fp, _fp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ct_completion_items": (_i, [_vp, _vp, _vp, _vp, _f, _i, _i, ctypes.c_int64, _vp, _vp, _vp, _vp]),
     "ct_scan_items": (_i, [_vp, _vp, _vp, ctypes.c_int64, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _vp, _vp, _vp]),
+    "ct_block_items": (_i, [_vp, _vp, ctypes.c_int64, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _i, _vp, _vp, _vp]),
+    "ct_seg_confusion": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
 }
 
 

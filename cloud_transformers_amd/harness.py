@@ -21,7 +21,11 @@ package's layers and checkpoints stay interchangeable.
   (train_completion.py, train_inpainter.py).  `scanobjectnn_device` (the `classification_scanobjectnn` task; `data.path`,
   `data.path_val`, `data.batch_size_val`, optional `data.subsample`) keeps the ScanObjectNN split on the device and gathers
   every batch there (data/scanobjectnn.py), validates every `train.val_step` epochs with the reference's accuracies and keeps
-  the `best` / `macc_best` checkpoints (train_classification.py).  The image_point variant stays out of scope.
+  the `best` / `macc_best` checkpoints (train_classification.py).  `s3dis_device` (the `segmentation_blocks` task; `data.path`,
+  `data.num_points`, `data.test_area`, `data.data_percent`, `data.aug`, `data.batch_size_val` as configs/s3dis.yaml has them)
+  keeps the 1x1 m blocks on the device, assembles and augments every batch in one launch (data/s3dis_blocks.py), fills the
+  train and validation confusion matrices on the device and appends every validation to <exp>/segmentation_val.jsonl
+  (train_segmentation.py).  The image_point variant stays out of scope.
 """
 import copy
 import datetime
@@ -183,9 +187,16 @@ def make_dataset(cfg, task, n_classes, length=64, channels=3, train=True):
     """The dataset `data.kind` of the config names: "synthetic" (default), "scanobjectnn" or "s3dis" (data/datasets.py);
     "s3dis_kpconv" gives the (train, validation) Areas of train_kpconv.load_kpconv_areas (`train=False`: no train Areas);
     "shapenet_completion" the TRAIN (`train=False`: VAL) subset of data/completion.py's ShapeNetDataLoader;
-    "scanobjectnn_device" the ScanObjectNN of `data.path` (`train=False`: `data.path_val`) with its items left to the device."""
+    "scanobjectnn_device" the ScanObjectNN of `data.path` (`train=False`: `data.path_val`) with its items left to the device;
+    "s3dis_device" the Indoor3DSemSeg of `data.path` (`train=False`: the blocks of `data.test_area`), its items left to the device."""
     data = cfg["data"]
     kind = str(data.get("kind", "synthetic")).lower()
+    if kind == "s3dis_device":
+        assert task == "segmentation_blocks", "data.kind s3dis_device is the segmentation_blocks task"
+        from .data import datasets as D
+        # (shuffle and augmentation happen on the device: the host object only reads the shards and splits them by Area)
+        return D.Indoor3DSemSeg(data["path"], data["num_points"], train=train, aug=False, test_area=data.get("test_area", "Area_5"),
+                                data_precent=float(data.get("data_percent", 1.0)))
     if kind == "scanobjectnn_device":
         assert task == "classification_scanobjectnn", "data.kind scanobjectnn_device is the classification_scanobjectnn task"
         from .data import datasets as D
@@ -211,7 +222,7 @@ def make_dataset(cfg, task, n_classes, length=64, channels=3, train=True):
         assert task == "segmentation", "S3DIS blocks are (points, labels): the segmentation task"
         return D.Indoor3DSemSeg(data["path"], data["num_points"], train=train, aug=bool(data.get("aug", train)),
                                 test_area=data.get("test_area", "Area_5"), data_precent=float(data.get("data_precent", 1.0)))
-    raise ValueError("data.kind must be synthetic, scanobjectnn, scanobjectnn_device, s3dis, s3dis_kpconv or shapenet_completion "
+    raise ValueError("data.kind must be synthetic, scanobjectnn, scanobjectnn_device, s3dis, s3dis_device, s3dis_kpconv or shapenet_completion "
                      "(got %r)" % kind)
 
 
@@ -232,7 +243,12 @@ class Trainer:
     loss = (1 - seg_weight) * CE(out[0], label) + seg_weight * BCE-with-logits(out[1][:, 0, 0], mask) of train_classification.py:
     201-204 (the model's output is indexed, so the reference's three-output classifier and two-output models both fit),
     batches gathered on the device (data/scanobjectnn.py ScanBatches; `n_classes` sizes the per-class accuracies), validation
-    every `train.val_step` epochs, `generator_epoch_{e}.t7` every `train.save_each_epoch` epochs (train_classification.py)."""
+    every `train.val_step` epochs, `generator_epoch_{e}.t7` every `train.save_each_epoch` epochs (train_classification.py).
+    "segmentation_blocks" (selected by `data.kind: s3dis_device` too; `dataset` may be a data.datasets.Indoor3DSemSeg or a
+    data.s3dis_blocks.DeviceS3DISBlocks): loss = CE(pred[:, :, 0], labels) on batches assembled on the device (data/s3dis_blocks.py
+    BlockBatches), a train confusion matrix updated every step on the device and reported per epoch (`train_records`),
+    validation every `train.val_step` epochs (<exp>/segmentation_val.jsonl), `generator_iter_{n}.t7` every `train.save_each`
+    iterations and `generator_epoch_{e}.t7` every `train.save_each_epoch` epochs (train_segmentation.py)."""
 
     def __init__(self, cfg, task, n_classes, device=None, dist=None, exp_name="exp", dataset_length=64, make_dirs=True,
                  channels=3, dataset=None):
@@ -244,6 +260,10 @@ class Trainer:
         if task == "classification_scanobjectnn" or str(cfg["data"].get("kind", "")).lower() == "scanobjectnn_device":
             from .train_classification import classification_config
             task, self.cfg = "classification_scanobjectnn", classification_config(cfg)
+            cfg = self.cfg
+        if task == "segmentation_blocks" or str(cfg["data"].get("kind", "")).lower() == "s3dis_device":
+            from .train_segmentation import segmentation_config
+            task, self.cfg = "segmentation_blocks", segmentation_config(cfg)
             cfg = self.cfg
         self.task, self.dist, self.n_classes = task, dist, n_classes
         self.rank = dist.get_rank() if parallel._active(dist) else 0
@@ -295,7 +315,14 @@ class Trainer:
         self.kp, self.clip, self.val_records = None, None, []
         self.shapenet, self.val_loader, self.best_val = str(cfg["data"].get("kind", "")).lower() == "shapenet_completion", None, None
         self.scan, self.best_acc, self.best_macc = task == "classification_scanobjectnn", float("-inf"), float("-inf")
-        if self.scan:
+        self.blocks, self.train_meter, self.train_records, self._pred = task == "segmentation_blocks", None, [], None
+        self._graph_preds = {}
+        if self.blocks:
+            from .data.s3dis_blocks import SegmentationMeter
+            self.sampler = None                          # (BlockBatches holds torch's DistributedSampler itself)
+            self.loader = self._block_batches(data, train=True)
+            self.train_meter = SegmentationMeter(n_classes)
+        elif self.scan:
             self.sampler = None                          # (ScanBatches holds torch's DistributedSampler itself)
             self.loader = self._scan_batches(data, train=True)
         elif self.shapenet:
@@ -338,7 +365,32 @@ class Trainer:
         cls_loss, seg_loss = self.ce(out[0], label), self.bce(out[1][:, 0, 0], mask)
         return (1 - w) * cls_loss + w * seg_loss, cls_loss, seg_loss, out
 
+    def _block_batches(self, data, train):
+        """BlockBatches over `data` (a host Indoor3DSemSeg is uploaded first) with the config's sizes, this rank's shard."""
+        from .data.s3dis_blocks import BlockBatches, DeviceS3DISBlocks
+        d = self.cfg["data"]
+        ds = data if isinstance(data, DeviceS3DISBlocks) else DeviceS3DISBlocks(data, self.device)
+        active = parallel._active(self.dist)
+        return BlockBatches(ds, d["batch_size"] if train else d["batch_size_val"], num_points=d["num_points"], train=train,
+                            aug=bool(d["aug"]) and train, seed=int(d["seed"]) + (0 if train else 7919), rank=self.rank,
+                            world=self.dist.get_world_size() if active else 1, drop_last=bool(d.get("drop_last", False)) and train,
+                            data_percent=float(d["data_percent"]), sigma=float(d["jitter_sigma"]), clip=float(d["jitter_clip"]),
+                            cstd=float(d["color_jitter_std"]), ratio=float(d["color_shift_ratio"]), hue_max=float(d["hue_max"]),
+                            sat_max=float(d["saturation_max"]))
+
+    def _block_pred(self, pcd):
+        out = self.model(pcd)
+        return out[0] if isinstance(out, (tuple, list)) else out                      # the reference returns (pred, lattice stats)
+
     def _loss(self, batch):
+        if self.task == "segmentation_blocks":
+            pcd, labels = batch
+            pred = self._block_pred(pcd)
+            # kept for the train confusion (the step's, or a graph's static one) — detached: a tensor with a grad_fn held across
+            # steps keeps the autograd graph and its AccumulateGrad nodes alive, pinned to the stream of the first step, and a
+            # later capture on another stream then breaks
+            self._pred = pred.detach()
+            return self.ce(pred[:, :, 0], labels)
         if self.task == "classification_scanobjectnn":
             return self._scan_losses(batch)[0]
         if self.task == "segmentation_kpconv":
@@ -478,6 +530,61 @@ class Trainer:
         self.val_records.append(rec)
         return [rec]
 
+    def _validate_blocks(self, epoch, dataset=None):
+        """train_segmentation.py:244-288: eval mode, no grad, the blocks of `data.test_area` in batches of `data.batch_size_val`
+        (shuffled points, no augmentation); the loss averaged over the batches and the ranks, the confusion matrix filled on the
+        device (SegmentationMeter) and all-reduced over the ranks, `return_metrics_dict`'s numbers from it (sums and counts stay
+        on the device until the two reads at the end).  As in the reference the shards are padded to equal length, so with
+        several ranks a few blocks count twice."""
+        import json
+        from .data.s3dis_blocks import SegmentationMeter
+        if self.val_loader is None or dataset is not None:
+            data = dataset if dataset is not None else make_dataset(self.cfg, self.task, self.n_classes, train=False)
+            self.val_loader = self._block_batches(data, train=False)
+        model = self.model
+        was_training = model.training
+        model.eval()
+        self.val_loader.set_epoch(epoch if isinstance(epoch, int) else 0)
+        meter = SegmentationMeter(self.n_classes)
+        sums = torch.zeros(2, dtype=torch.float64, device=self.device)            # loss, batches
+        with torch.no_grad():
+            for pcd, labels in self.val_loader:
+                pred = self._block_pred(pcd)
+                loss = self.ce(pred[:, :, 0], labels)
+                sums += torch.stack([loss, torch.ones_like(loss)]).double()
+                meter.update(pred, labels)
+        model.train(was_training)
+        if parallel._active(self.dist):
+            self.dist.all_reduce(sums)
+            meter.reduce(self.dist)
+        s = sums.tolist()
+        rec = {"epoch": epoch, "iters": self.iters, "batches": int(s[1]), "loss": s[0] / max(s[1], 1.0)}
+        rec.update(meter.result())
+        if self.rank == 0:
+            step = epoch if isinstance(epoch, int) else self.iters
+            for k, v in rec.items():
+                if k not in ("epoch", "iters", "batches"):
+                    self.writer.add_scalar("val/" + k, v, global_step=step)
+            if self.exp_dir is not None:
+                with open(str(Path(self.exp_dir) / "segmentation_val.jsonl"), "a") as f:
+                    f.write(json.dumps(rec) + "\n")
+        self.val_records.append(rec)
+        return [rec]
+
+    def _report_train_confusion(self, epoch):
+        """The epoch's train metrics (train_segmentation.py:236-237) from the confusion matrix the steps filled; it starts anew."""
+        if self.train_meter.conf is None:
+            return
+        if parallel._active(self.dist):
+            self.train_meter.reduce(self.dist)
+        rec = dict(self.train_meter.result(), epoch=epoch, iters=self.iters)
+        self.train_meter.reset()
+        if self.rank == 0:
+            for k, v in rec.items():
+                if k not in ("epoch", "iters"):
+                    self.writer.add_scalar("train/" + k, v, global_step=epoch)
+        self.train_records.append(rec)
+
     def validate(self, num_votes=None, epoch=None):
         """segmentation_kpconv: one validation of `num_votes` vote passes (train_kpconv.KPConvData.validate) on the unwrapped
         model; the records go to the writer and, on rank 0, to <exp>/kpconv_val.jsonl.  Returns them.
@@ -485,8 +592,12 @@ class Trainer:
         <exp>/completion_val.jsonl and, on a new minimum of the loss, `generator_best_0.t7` / `g_opt_best_0.t7` saved.
         classification_scanobjectnn (`num_votes` is not used): one pass over `data.path_val` (`_validate_scan`), its record
         (losses, cls_acc, seg_acc, m_acc, class_acc) appended to <exp>/classification_val.jsonl; `generator_best_0.t7` /
-        `g_opt_best_0.t7` saved on a new best cls_acc, `generator_macc_best_0.t7` / `g_opt_macc_best_0.t7` on a new best m_acc."""
+        `g_opt_best_0.t7` saved on a new best cls_acc, `generator_macc_best_0.t7` / `g_opt_macc_best_0.t7` on a new best m_acc.
+        segmentation_blocks (`num_votes` is not used): one pass over the blocks of `data.test_area` (`_validate_blocks`), its record
+        (loss, overall_acc, mean_class_acc, iou_<name>, mean_iou) appended to <exp>/segmentation_val.jsonl."""
         import json
+        if self.task == "segmentation_blocks":
+            return self._validate_blocks(epoch)
         if self.task == "completion":
             return self._validate_completion(epoch)
         if self.task == "classification_scanobjectnn":
@@ -511,6 +622,8 @@ class Trainer:
     # -- one training step -------------------------------------------------------------------------------------------
     def _eager_step(self, batch):
         loss = self._loss(batch)
+        if self.blocks:
+            self.train_meter.update(self._pred, batch[1])
         loss.backward()
         self._clip()
         self.optimizer.step()
@@ -564,6 +677,8 @@ class Trainer:
             rec, failure = None, None
             try:
                 rec = self._capture(batch)
+                if self.blocks:
+                    self._graph_preds[key] = self._pred       # the graph's static prediction: read after every replay
             except RuntimeError as ex:
                 # only what a refused CAPTURE raises (HIP's stream-capture errors, e.g. the process group's watchdog touching an
                 # event of the capturing stream); a genuine error inside the model or the loss is not swallowed as "capture failed"
@@ -593,6 +708,8 @@ class Trainer:
         for dst, src in zip(static, batch):
             dst.copy_(src, non_blocking=True)
         graph.replay()
+        if self.blocks:
+            self.train_meter.update(self._graph_preds[key], static[1])
         for p, g in zip((p for p in self.model.parameters() if p.requires_grad), grads):
             p.grad = g
         self._clip()
@@ -613,7 +730,7 @@ class Trainer:
         tr = self.cfg["train"]
         use_graph = bool(tr.get("hip_graph", False) if hip_graph is None else hip_graph)
         log_each = int(tr.get("log_each", 10) if log_each is None else log_each)
-        self._graphs = {}
+        self._graphs, self._graph_preds = {}, {}
         history, pending = [], []
 
         def flush():
@@ -630,7 +747,7 @@ class Trainer:
         for epoch in range(tr["num_epochs"]):
             if self.sampler is not None:
                 self.sampler.set_epoch(epoch)
-            if self.scan:
+            if self.scan or self.blocks:
                 self.loader.set_epoch(epoch)
             self.model.train()
             end = time.time()
@@ -670,6 +787,14 @@ class Trainer:
             if self.shapenet:
                 flush()
                 self.validate(epoch=epoch)                # train_inpainter.py:253-311: once per epoch
+            if self.blocks:
+                # train_segmentation.py:236-244: the train metrics, then checkpoints and validation by the 0-based epoch
+                flush()
+                self._report_train_confusion(epoch)
+                if epoch > 0 and epoch % int(tr["save_each_epoch"]) == 0:
+                    self.save(epoch=epoch)
+                if epoch % int(tr["val_step"]) == 0:
+                    self.validate(epoch=epoch)
             if self.scan:
                 # train_classification.py:281-286: checkpoints and validation by the 0-based epoch
                 flush()

@@ -37,7 +37,8 @@ extern "C" {
  * ct_bn_apply_fwd / _bwd (and _amax), ct_bn_reduce_bwd, ct_bn_eval_fwd, ct_adain_fwd / _bwd (and _amax) — a single norm is a table
  * with n = 1 — and ct_bn_group_reduce_bwd_copy, whose sums_copy is now a nullable argument of ct_bn_group_reduce_bwd.  Changed:
  * the four exchange phases ct_bn_group_{stats,apply}_fwd / {reduce,apply}_bwd take the whole table plus the run of items to launch.
- * (ct_scan_items was added under version 3 without a bump: an additive symbol, which the loader's missing-symbol scan checks.) */
+ * (ct_scan_items was added under version 3 without a bump: an additive symbol, which the loader's missing-symbol scan checks;
+ * ct_block_items and ct_seg_confusion the same way.) */
 #define CT_ABI_VERSION 3
 
 /* status codes */
@@ -699,6 +700,72 @@ int ct_completion_items(const float* partial, const int64_t* perm, const float* 
 int ct_scan_items(const float* data, const uint8_t* mask, const int64_t* label, int64_t M, int P, const int64_t* item,
                   const int64_t* perm, const float* rot, const float* jit, float sigma, float clip, int B, int N,
                   float* out_points, float* out_mask, int64_t* out_label, ct_stream_t s);
+
+/* ------------------------------------------------------------------------
+ * Batch assembly of the S3DIS 1x1 m block items (datasets/s3dis_v2.py:537-560: shuffle, rotation
+ * about z, anisotropic scale, mirror in x, jitter, auto-contrast, colour translation, colour jitter,
+ * hue / saturation translation; the collate and the permute of train_segmentation.py:180), one
+ * launch, every random draw passed in.  Added under CT_ABI_VERSION 3 (additive, as ct_scan_items).
+ * It does not allocate, does not synchronise and runs on the stream s.
+ *
+ * The split stays on the device: data f32[M,P,6] (x, y, z, r, g, b: columns 0..5 of the stored
+ * [M,4096,9] blocks, colours in [0,1]), label u8[M,P]; M >= 1.  A batch is B rows (1 <= B <= 65535)
+ * of N slots (1 <= N <= P <= 16384); the pool of a row is its block's first N points
+ * (s3dis_v2.py:537).  item i64[B] names the block of each row (repeats allowed); perm i64[B,N]
+ * (nullable) is a permutation of 0..N-1 per row, NULL: slot n takes point n.
+ * Augmentation, all three or none (CT_EINVAL otherwise): aug f32[B,16], jit f32[B,N,3] and cjit
+ * f32[B,N,3] (standard normal draws); sigma, cstd (finite) and clip (> 0): host floats.
+ *   aug[b,0], aug[b,1]   c, s: cos and sin of the angle about z
+ *   aug[b,2..4]          per-axis scale; the x entry carries the mirror's sign
+ *   aug[b,5]             w, the auto-contrast's blend factor; negative: the stage is skipped
+ *   aug[b,6..8]          colour shift, already (u - 0.5) * 2 * ratio
+ *   aug[b,9]             colour translation applied (0 or 1)
+ *   aug[b,10]            colour jitter applied (0 or 1)
+ *   aug[b,11]            hue shift
+ *   aug[b,12]            saturation factor
+ *   aug[b,13..15]        zero
+ * Per slot (b, n), each operation one fp32 rounding, in this order:
+ *   g = clamp(item[b], 0, M-1); src = perm ? clamp(perm[b,n], 0, N-1) : n; (x, y, z, rgb) = data[g,src].
+ *   Without augmentation that row is the output.  With it:
+ *   1. x' = (x * c) - (y * s), y' = (x * s) + (y * c);
+ *   2. p_i = p_i * aug[b,2+i];
+ *   3. p_i = p_i + min(max(sigma * jit[b,n,i], -clip), clip);
+ *   4. when w >= 0, per channel: lo, hi = min, max of the channel over data[g,0..N-1] (exact; -0 sorts
+ *      below +0); when hi != lo: st = (rgb - lo) * (1 / (hi - lo)), rgb = ((1 - w) * rgb) + (w * st).
+ *      A channel with hi == lo is left as it is — a deviation: the reference divides by zero there and
+ *      fills the channel with NaN;
+ *   5. when aug[b,9] != 0: rgb = min(max(aug[b,6+i] + rgb, 0), 1);
+ *   6. when aug[b,10] != 0: rgb = min(max((cjit[b,n,i] * cstd) + rgb, 0), 1);
+ *   7. (r, g, b) = rgb * 255; mx, mn = max, min of the three; span = mx - mn; grey = span == 0;
+ *      rc = (mx - r) / span (gc, bc alike); h = r == mx ? bc - gc : g == mx ? (2 + rc) - bc :
+ *      (4 + gc) - rc, 0 when grey; sat = span / (mx == 0 ? 1 : mx), 0 when grey; h = rem1(h / 6) with
+ *      rem1(t) = np.remainder(t, 1) = t - trunc(t), + 1 when that is negative;
+ *      h = rem1((aug[b,11] + h) + 1); sat = min(max(aug[b,12] * sat, 0), 1);
+ *      h6 = h * 6; sector = trunc(h6); f = h6 - sector; p = mx * (1 - sat), q = mx * (1 - (sat * f)),
+ *      t = mx * (1 - (sat * (1 - f))); sector mod 6 picks (mx,t,p) (q,mx,p) (p,mx,t) (p,q,mx) (t,p,mx)
+ *      (mx,p,q); sat == 0: (mx,mx,mx);
+ *   8. rgb = trunc(min(max(value, 0), 255)) / 255 (the reference's 8-bit levels; the clamp is a guard).
+ * The draws are finite by construction; what the stages do to a NaN or infinite value is not specified.
+ * Outputs: out f32[B,6,N] (the model's layout: [B,6,1,N] is a view of it), out_label i64[B,N] =
+ * label[g,src].  The clamps of g and src are guards; valid inputs never need them.
+ * Null pointers (other than perm, aug, jit, cjit), a partial augmentation, clip <= 0 and sizes outside
+ * the limits -> CT_EINVAL before anything touches the device.
+ * ---------------------------------------------------------------------- */
+int ct_block_items(const float* data, const uint8_t* label, int64_t M, int P, const int64_t* item, const int64_t* perm,
+                   const float* aug, const float* jit, const float* cjit, float sigma, float clip, float cstd, int B, int N,
+                   float* out, int64_t* out_label, ct_stream_t s);
+
+/* ------------------------------------------------------------------------
+ * The confusion matrix of a segmentation batch (train_segmentation.py:198-205 without the copy of
+ * the predictions to the host), one launch, one pass over pred.  Added under CT_ABI_VERSION 3
+ * (additive).
+ * pred f32[B,C,N] (1 <= C <= 64, B * N < 2^31), labels i64[B,N]; conf i64[C*C], rows truth, columns
+ * prediction: conf[t*C + p] += the number of points with label t and prediction p.  It ADDS: the
+ * caller zeroes conf.  The prediction of a point is the first index of the maximum over C, a NaN
+ * counting as the maximum (np.argmax).  Points whose label is outside 0..C-1 are not counted.
+ * Integer counts only: the result does not depend on the order of the workgroups.
+ * ---------------------------------------------------------------------- */
+int ct_seg_confusion(const float* pred, const int64_t* labels, int B, int C, int N, int64_t* conf, ct_stream_t s);
 
 #ifdef __cplusplus
 }
