@@ -186,6 +186,51 @@ __device__ __forceinline__ void pt2_from_keys(float kx, float ky, const GridW<2>
 }
 
 // ---------------------------------------------------------------------------
+// Tile staging: channel rows of a grid tile (G floats each; G % 4 == 0 and 16-byte aligned rows: the hot dispatch) -> one 16-byte
+// LDS word per cell.  A lane takes ITEMS of 4 consecutive cells: one 16-byte load from each of the word's four rows, then four
+// 16-byte LDS writes (the 4 x 4 transpose happens in registers).  All loads of a batch — kStageItems items per lane, 32 dwords:
+// the whole tile of a 512-thread workgroup at the headline shape — are issued before the first write waits for one of them; their
+// addresses are clamped and unconditional, only the writes are predicated.  (One cell per lane and step — four dword loads, a wait
+// for all of them, one write, the branch back — was a chain of dependent trips to memory with 16 bytes per lane in flight, eight
+// of them for a 64 KiB tile: profiles/tile_staging_ab.txt.)
+// ---------------------------------------------------------------------------
+constexpr int kStageItems = 2;
+
+// the loads of a batch are complete values here: keeps the compiler from sinking an item's loads behind the writes of the one before
+#define CT_STAGE_PIN(r) asm volatile("" : "+v"((r).x), "+v"((r).y), "+v"((r).z), "+v"((r).w))
+
+// channel-interleaved tile: T4[q * G + cell] = {row 4q, row 4q + 1, row 4q + 2, row 4q + 3}[cell] for the nq four-row groups at `gin`
+__device__ __forceinline__ void stage_tile_ci(float4* T4, const float* gin, int nq, int G) {
+  const int G4 = G >> 2, n = nq * G4, step = (int)blockDim.x;
+  for (int j0 = threadIdx.x; j0 < n; j0 += kStageItems * step) {
+    float4 r[kStageItems][4];
+#pragma unroll
+    for (int u = 0; u < kStageItems; ++u) {
+      const int j = min(j0 + u * step, n - 1);
+      const int q = j / G4;
+      const float* p = gin + (size_t)(q * 4) * G + ((j - q * G4) << 2);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) r[u][k] = ld_stream4(p + (size_t)k * G);
+    }
+#pragma unroll
+    for (int u = 0; u < kStageItems; ++u)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) CT_STAGE_PIN(r[u][k]);
+#pragma unroll
+    for (int u = 0; u < kStageItems; ++u) {
+      const int j = j0 + u * step;
+      if (j < n) {
+        float4* d = T4 + ((size_t)j << 2);       // q * G + 4 * (j - q * G4)
+        d[0] = make_float4(r[u][0].x, r[u][1].x, r[u][2].x, r[u][3].x);
+        d[1] = make_float4(r[u][0].y, r[u][1].y, r[u][2].y, r[u][3].y);
+        d[2] = make_float4(r[u][0].z, r[u][1].z, r[u][2].z, r[u][3].z);
+        d[3] = make_float4(r[u][0].w, r[u][1].w, r[u][2].w, r[u][3].w);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // KF: Slice backward, fused.  One 512-thread workgroup per (b, h) plane (two per CU), thread = QPT quads of 4
 //   consecutive points (N <= 4 * QPT * blockDim).
 //   LDS: conv chunk [CC/4][G] x float4 (channel-interleaved) | int accumulators [CC][G] | base-cell counts [G]
@@ -321,14 +366,8 @@ __global__ void __launch_bounds__(NTB, CT_FUSED_WAVES) slice_bwd_fused_kernel(Ra
     const int cc = min(CC, a.C - c0);            // multiple of 4
     const float* gin = a.tile_in + (bh * a.C + c0) * (size_t)G;
     float* gout = a.tile_out + (((size_t)seg * a.B * a.H + bh) * a.C + c0) * (size_t)G;
-    // stage the conv chunk channel-interleaved (4 coalesced dword loads -> one conflict-free ds_write_b128)
-    if (GATHER) {
-      for (int t = tid; t < (cc >> 2) * G; t += blockDim.x) {
-        const int cq = t / G, cell = t - cq * G;
-        const float* p = gin + (size_t)(cq * 4) * G + cell;
-        T4[t] = make_float4(ld_stream(p), ld_stream(p + G), ld_stream(p + 2 * (size_t)G), ld_stream(p + 3 * (size_t)G));
-      }
-    }
+    // stage the conv chunk channel-interleaved
+    if (GATHER) stage_tile_ci(T4, gin, cc >> 2, G);
     if (chunk == cgi)
       for (int t = tid; t < (cc * G) >> 2; t += blockDim.x) ((int4*)acc)[t] = make_int4(0, 0, 0, 0);
     __syncthreads();
@@ -593,6 +632,58 @@ constexpr int kTieFixWords = 8;      // behind the 3 * kTieGroups words: splat_b
 __device__ __forceinline__ void plane_sum_bits(int* word, unsigned v, int sign) {
   const int t = wave_sum_i32((int)v);
   if ((threadIdx.x & 63) == 0 && t) atomicAdd(word, sign * t);
+}
+
+// The {z, z, g, g} pair tile of Splat(max) backward, staged like stage_tile_ci: ZG[p * G + cell] = {z(2p), z(2p + 1), g_z(2p),
+// g_z(2p + 1)}[cell] for the np channel pairs at `zin` / `gin`.  An empty cell (z = 0: nothing beat the zero floor) is staged as
+// kNoMatch, a bit pattern no product of finite inputs has, so that the winner test in the point loop is one compare.
+// COUNT: the thread's tie counters take the item's non-zero cells — nz: all of them, nzp: per four-channel group of the chunk
+// (16-bit fields, see nmp in splat_bwd_plane_pass), xzp: the sum of their cotangents' bit patterns (CT_TIE_FIX).  Integer sums:
+// which lane counts which cell does not matter.
+template <bool COUNT>
+__device__ __forceinline__ void stage_tile_pairs(float4* ZG, const float* zin, const float* gin, int np, int G, int& nz,
+                                                 unsigned long long& nzp, unsigned& xzp) {
+  const int G4 = G >> 2, n = np * G4, step = (int)blockDim.x;
+  for (int j0 = threadIdx.x; j0 < n; j0 += kStageItems * step) {
+    float4 r[kStageItems][4];        // z(2p), z(2p + 1), g_z(2p), g_z(2p + 1) at the item's 4 cells
+#pragma unroll
+    for (int u = 0; u < kStageItems; ++u) {
+      const int j = min(j0 + u * step, n - 1);
+      const int cp = j / G4;
+      const size_t o = (size_t)(cp * 2) * G + ((j - cp * G4) << 2);
+      r[u][0] = ld_stream4(zin + o);
+      r[u][1] = ld_stream4(zin + o + G);
+      r[u][2] = ld_stream4(gin + o);
+      r[u][3] = ld_stream4(gin + o + G);
+    }
+#pragma unroll
+    for (int u = 0; u < kStageItems; ++u)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) CT_STAGE_PIN(r[u][k]);
+#pragma unroll
+    for (int u = 0; u < kStageItems; ++u) {
+      const int j = j0 + u * step;
+      if (j < n) {
+        const unsigned z0[4] = {__float_as_uint(r[u][0].x), __float_as_uint(r[u][0].y), __float_as_uint(r[u][0].z), __float_as_uint(r[u][0].w)};
+        const unsigned z1[4] = {__float_as_uint(r[u][1].x), __float_as_uint(r[u][1].y), __float_as_uint(r[u][1].z), __float_as_uint(r[u][1].w)};
+        const float g0[4] = {r[u][2].x, r[u][2].y, r[u][2].z, r[u][2].w}, g1[4] = {r[u][3].x, r[u][3].y, r[u][3].z, r[u][3].w};
+        float4* d = ZG + ((size_t)j << 2);       // cp * G + 4 * (j - cp * G4)
+        int nzt = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          d[k] = make_float4(__uint_as_float(z0[k] ? z0[k] : kNoMatch), __uint_as_float(z1[k] ? z1[k] : kNoMatch), g0[k], g1[k]);
+          if (COUNT) {
+            nzt += (z0[k] != 0u) + (z1[k] != 0u);
+            if (CT_TIE_FIX) xzp += (z0[k] ? __float_as_uint(g0[k]) : 0u) + (z1[k] ? __float_as_uint(g1[k]) : 0u);
+          }
+        }
+        if (COUNT) {
+          nz += nzt;
+          nzp += (unsigned long long)(unsigned)nzt << (16 * (((j / G4) >> 1) & 3));
+        }
+      }
+    }
+  }
 }
 
 // DELTA (with CLAIMS): the redo of ONE four-channel group after an optimistic pass — its g_feat rows are rewritten with the
@@ -938,20 +1029,12 @@ __device__ __forceinline__ void splat_bwd_plane_pass(const RasterArgs& a, const 
     __syncthreads();                              // readers of the previous chunk (or pass) are done
     unsigned long long nzp = 0ull;
     unsigned xzp = 0u;
-    for (int t = tid; t < (cc >> 1) * G; t += blockDim.x) {
-      const int cp = t / G, cell = t - cp * G;
-      const size_t o = (size_t)(cp * 2) * G + cell;
-      // an empty cell (z = 0: nothing beat the zero floor) is staged as kNoMatch, a bit pattern no product of finite
-      // inputs has, so that the winner test in the loop is one compare
-      const unsigned z0 = __float_as_uint(ld_stream(zin + o)), z1 = __float_as_uint(ld_stream(zin + o + G));
-      const float g0 = ld_stream(gin + o), g1 = ld_stream(gin + o + G);
-      ZG[t] = make_float4(__uint_as_float(z0 ? z0 : kNoMatch), __uint_as_float(z1 ? z1 : kNoMatch), g0, g1);
-      if (!CLAIMS) {
-        const int nzt = (z0 != 0u) + (z1 != 0u);
-        nz += nzt;
-        nzp += (unsigned long long)(unsigned)nzt << (16 * ((cp >> 1) & 3));      // per four-channel group of the chunk (packed: see nmp)
-        if (CT_TIE_FIX) xzp += (z0 ? __float_as_uint(g0) : 0u) + (z1 ? __float_as_uint(g1) : 0u);
-      }
+    stage_tile_pairs<!CLAIMS>(ZG, zin, gin, cc >> 1, G, nz, nzp, xzp);
+    // the first quad's keys are requested in front of the barrier (a thread without a quad reads the plane's last one)
+    float4 tx0, ty0;
+    if constexpr (QPT > 0) {
+      tx0 = *(const float4*)(keyx + (min(tid, nq - 1) << 2));
+      ty0 = *(const float4*)(keyy + (min(tid, nq - 1) << 2));
     }
     if (!CLAIMS && grp != nullptr) {
 #pragma unroll
@@ -972,8 +1055,8 @@ __device__ __forceinline__ void splat_bwd_plane_pass(const RasterArgs& a, const 
         const int q = tid + u * (int)blockDim.x;
         if (q < nq) {
           const int n0 = q << 2;
-          const float4 tx = *(const float4*)(keyx + n0);
-          const float4 ty = *(const float4*)(keyy + n0);
+          const float4 tx = u == 0 ? tx0 : *(const float4*)(keyx + n0);
+          const float4 ty = u == 0 ? ty0 : *(const float4*)(keyy + n0);
           const float kx[4] = {tx.x, tx.y, tx.z, tx.w}, ky[4] = {ty.x, ty.y, ty.z, ty.w};
           splat_bwd_quad<HAS_PAD, CLAIMS, WT>(a, g, ZG, bh, b, c0, cc, n0, R, kx, ky, gs_reg[u], nm, nmp, xmp, per_group);
         }
@@ -1115,12 +1198,11 @@ __global__ void __launch_bounds__(NTB, 4) splat_max_bwd_hot_kernel(RasterArgs a,
         staged = false;
         CT_TIE_COUNT(5, 1);
         __syncthreads();
-        for (int t = tid; t < 2 * G; t += blockDim.x) {
-          const int cp = t / G, cell = t - cp * G;
-          const size_t o = (size_t)(cp * 2) * G + cell;
-          const unsigned z0 = __float_as_uint(ld_stream(zin + o)), z1 = __float_as_uint(ld_stream(zin + o + G));
-          ZG[t] = make_float4(__uint_as_float(z0 ? z0 : kNoMatch), __uint_as_float(z1 ? z1 : kNoMatch), ld_stream(gin + o),
-                              ld_stream(gin + o + G));
+        {
+          int nz_unused = 0;
+          unsigned long long nzp_unused = 0ull;
+          unsigned xzp_unused = 0u;
+          stage_tile_pairs<false>(ZG, zin, gin, 2, G, nz_unused, nzp_unused, xzp_unused);
         }
         __syncthreads();
         const float* keyx = a.pos.keys + (bh * 2 + 0) * R.Nr + R.so;
@@ -1247,23 +1329,24 @@ __global__ void __launch_bounds__(kHotThreads, 4) gather_ci_kernel(RasterArgs a,
   const int tid = threadIdx.x;
   const int off[4] = {0, W1, 1, W1 + 1};
   const float* gin = a.tile_in + (bh * a.C + c0) * (size_t)G;
-  for (int t = tid; t < (cc >> 2) * G; t += blockDim.x) {
-    const int cq = t / G, cell = t - cq * G;
-    const float* p = gin + (size_t)(cq * 4) * G + cell;
-    T4[t] = make_float4(ld_stream(p), ld_stream(p + G), ld_stream(p + 2 * (size_t)G), ld_stream(p + 3 * (size_t)G));
-  }
-  __syncthreads();
+  stage_tile_ci(T4, gin, cc >> 2, G);
   const int nq = N >> 2;
   const int per = (nq + a.nsplit - 1) / a.nsplit;
   const int q_beg = sp * per, q_end = min(nq, q_beg + per);
+  // the first quad's keys are requested in front of the barrier (a thread without a quad reads the plane's last one)
+  float4 tx = *(const float4*)(a.pos.keys + (bh * 2 + 0) * N + (min(q_beg + tid, nq - 1) << 2));
+  float4 ty = *(const float4*)(a.pos.keys + (bh * 2 + 1) * N + (min(q_beg + tid, nq - 1) << 2));
+  __syncthreads();
   float* dst = a.dst + (bh * a.C + c0) * (size_t)N;
   for (int q = q_beg + tid; q < q_end; q += blockDim.x) {
     const int n0 = q << 2;
     float cw[4][4], pv[4];
     int base[4];
     {
-      const float4 tx = *(const float4*)(a.pos.keys + (bh * 2 + 0) * N + n0);
-      const float4 ty = *(const float4*)(a.pos.keys + (bh * 2 + 1) * N + n0);
+      if (q != q_beg + tid) {
+        tx = *(const float4*)(a.pos.keys + (bh * 2 + 0) * N + n0);
+        ty = *(const float4*)(a.pos.keys + (bh * 2 + 1) * N + n0);
+      }
       const float kx[4] = {tx.x, tx.y, tx.z, tx.w}, ky[4] = {ty.x, ty.y, ty.z, ty.w};
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -1322,11 +1405,7 @@ __global__ void __launch_bounds__(kHotThreads, 4) splat_sum_bwd_kernel(RasterArg
   const int tid = threadIdx.x;
   const int off[4] = {0, W1, 1, W1 + 1};
   const float* gin = a.tile_in + bh * C * (size_t)G;
-  for (int t = tid; t < (C >> 2) * G; t += blockDim.x) {
-    const int cq = t / G, cell = t - cq * G;
-    const float* p = gin + (size_t)(cq * 4) * G + cell;
-    T4[t] = make_float4(ld_stream(p), ld_stream(p + G), ld_stream(p + 2 * (size_t)G), ld_stream(p + 3 * (size_t)G));
-  }
+  stage_tile_ci(T4, gin, C >> 2, G);
   __syncthreads();
   const int nq = N >> 2;
   const int per = (nq + a.nsplit - 1) / a.nsplit;

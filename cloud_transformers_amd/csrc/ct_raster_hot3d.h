@@ -135,11 +135,7 @@ __global__ void __launch_bounds__(NTB, 4) slice_bwd_fused3_kernel(RasterArgs a, 
     const int cc = min(CC, a.C - c0);
     const float* gin = a.tile_in + (bh * a.C + c0) * (size_t)G;
     float* gout = a.tile_out + (((size_t)seg * a.B * a.H + bh) * a.C + c0) * (size_t)G;
-    for (int t = tid; t < (cc >> 2) * G; t += blockDim.x) {
-      const int cq = t / G, cell = t - cq * G;
-      const float* p = gin + (size_t)(cq * 4) * G + cell;
-      T4[t] = make_float4(ld_stream(p), ld_stream(p + G), ld_stream(p + 2 * (size_t)G), ld_stream(p + 3 * (size_t)G));
-    }
+    stage_tile_ci(T4, gin, cc >> 2, G);
     if (chunk == cgi)
       for (int t = tid; t < (cc * G) >> 2; t += blockDim.x) ((int4*)acc)[t] = make_int4(0, 0, 0, 0);
     __syncthreads();
@@ -691,16 +687,9 @@ __device__ __forceinline__ void splat_bwd_plane_pass3(const RasterArgs& a, const
     const float* zin = a.tile_in + (bh * a.C + c0) * (size_t)G;
     const float* gin = a.tile_in2 + (bh * a.C + c0) * (size_t)G;
     __syncthreads();
-    for (int t = tid; t < (cc >> 1) * G; t += blockDim.x) {
-      const int cp = t / G, cell = t - cp * G;
-      const size_t o = (size_t)(cp * 2) * G + cell;
-      const unsigned z0 = __float_as_uint(ld_stream(zin + o)), z1 = __float_as_uint(ld_stream(zin + o + G));
-      const float g0 = ld_stream(gin + o), g1 = ld_stream(gin + o + G);
-      ZG[t] = make_float4(__uint_as_float(z0 ? z0 : kNoMatch), __uint_as_float(z1 ? z1 : kNoMatch), g0, g1);
-      if (!CLAIMS) {
-        nz += (z0 != 0u) + (z1 != 0u);
-        if (CT_TIE_FIX) xz += (z0 ? __float_as_uint(g0) : 0u) + (z1 ? __float_as_uint(g1) : 0u);
-      }
+    {
+      unsigned long long nzp_unused = 0ull;      // (no per-group counters in 3D)
+      stage_tile_pairs<!CLAIMS>(ZG, zin, gin, cc >> 1, G, nz, nzp_unused, xz);
     }
     __syncthreads();
     if constexpr (QPT > 0) {
@@ -860,11 +849,7 @@ __global__ void __launch_bounds__(kHotThreads, 4) gather_ci3_kernel(RasterArgs a
   int off[8];
   corner_offsets3(g, off);
   const float* gin = a.tile_in + (bh * a.C + c0) * (size_t)G;
-  for (int t = tid; t < (cc >> 2) * G; t += blockDim.x) {
-    const int cq = t / G, cell = t - cq * G;
-    const float* p = gin + (size_t)(cq * 4) * G + cell;
-    T4[t] = make_float4(ld_stream(p), ld_stream(p + G), ld_stream(p + 2 * (size_t)G), ld_stream(p + 3 * (size_t)G));
-  }
+  stage_tile_ci(T4, gin, cc >> 2, G);
   __syncthreads();
   const int nq = N >> 2;
   const int per = (nq + a.nsplit - 1) / a.nsplit;
