@@ -22,7 +22,7 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 
 HIP_SOURCES = ["ct_raster.hip", "ct_mhct.hip", "ct_lattice.hip", "ct_gconv.hip", "ct_chamfer.hip", "ct_emd.hip",
                "ct_adain.hip", "ct_bnorm.hip", "ct_pwgemm.hip", "ct_nbr.hip", "ct_kpitems.hip", "ct_completion.hip", "ct_scanitems.hip",
-               "ct_blockitems.hip"]
+               "ct_blockitems.hip", "ct_kpplan.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared",
                # index/weight math must round exactly like the reference's fp32 op sequence
                "-ffp-contract=off"]
@@ -82,6 +82,7 @@ DEBUG_FORCE_SORTED_SEG = 64
 DEBUG_NO_WIDE = 128
 NBR_K_MAX = 16384          # ct_nbr_radius: keys a query keeps in LDS
 NBR_MAX_CELLS = 1 << 26    # ct_nbr_* grids
+KP_PLAN_CLOUDS_MAX = 65535 # ct_kp_plan: clouds of one index table
 COMPLETION_N_MAX = 16384   # ct_completion_items: rows of one partial cloud
 COMPLETION_GT_MAX = 1 << 24
 SCAN_P_MAX = 16384         # ct_scan_items: points of one stored cloud
@@ -304,6 +305,11 @@ SIGNATURES = {
     "ct_nbr_index_build": (_i, [_vp, ctypes.c_int64, _fp, _f, _ip, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ct_nbr_radius": (_i, [_vp, _vp, _fp, _f, _ip, _vp, _i, _f, _i, _vp, _vp, _vp, _vp]),
     "ct_nbr_nearest": (_i, [_vp, _vp, _fp, _f, _ip, _vp, ctypes.c_int64, _vp, _vp, _vp]),
+    "ct_nbr_table_bytes": (_sz, [_i]),
+    "ct_nbr_table_set": (_i, [_vp, _i, _i, _vp, _vp, _fp, _f, _ip, ctypes.c_int64, ctypes.c_int64]),
+    "ct_nbr_radius_multi": (_i, [_vp, _i, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp]),
+    "ct_kp_plan_workspace_bytes": (_sz, [_i, ctypes.c_int64]),
+    "ct_kp_plan": (_i, [_vp, _i, ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_double, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ct_kp_items": (_i, [_vp] * 10 + [ctypes.c_int64, _fp, _fp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ct_completion_items": (_i, [_vp, _vp, _vp, _vp, _f, _i, _i, ctypes.c_int64, _vp, _vp, _vp, _vp]),
     "ct_scan_items": (_i, [_vp, _vp, _vp, ctypes.c_int64, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _vp, _vp, _vp]),

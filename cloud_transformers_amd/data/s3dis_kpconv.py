@@ -131,12 +131,18 @@ def scene_seg_features(input_features_dim, pc, color, height):
 class SphereSampler:
     """Spheres of `in_radius` picked by the potential field of S3DISSeg (s3dis_closer.py:239-276), items laid out as its
     __getitem__ (:302-361), B at a time.  State on `device`: the subsampled clouds, their GridIndex and the potentials
-    (`potentials[c]`, f32; `min_potentials` f32[clouds]).  `last_picks` keeps (cloud, point, pick point f32[3]) of every pick of
-    the last `plan` (or `sample`) call, in order, so that a test can replay the potential updates."""
+    (`potentials[c]`, f32, views of one concatenated buffer; `min_potentials` f32[clouds]) and the `GridIndexTable` of the
+    clouds.  `last_picks` keeps (cloud, point, pick point f32[3]) of every pick of the last `plan` (or `sample`) call, in
+    order, so that a test can replay the potential updates; after a device plan it is read back from the plan's tensors the
+    first time someone asks, and not before.
+
+    `plan` is one `ct_kp_plan` call (include/cloudct.h): no value comes back to the host while the picks are made, nor in
+    `items`.  CLOUDCT_KP_PLAN=0 selects the torch loop it replaced (`_plan_torch`): the same bits and the same draws."""
 
     def __init__(self, areas, num_points, in_radius=2.0, input_features_dim=4, color_drop=0.2, device="cuda", generator=None,
                  cell=None):
-        from ..neighbors import GridIndex
+        from .. import _lib
+        from ..neighbors import GridIndex, GridIndexTable
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("SphereSampler needs a HIP device; there is no CPU fallback")
@@ -157,12 +163,27 @@ class SphereSampler:
         self._all_colors = torch.from_numpy(np.concatenate([np.asarray(a.sub_colors, np.float32) for a in areas])).to(dev)
         self._all_labels = torch.from_numpy(np.concatenate([np.asarray(a.sub_labels) for a in areas]).astype(np.int64)).to(dev)
         # s3dis_closer.py:241-245: uniform potentials in [0, 1e-3)
-        self.potentials = [torch.rand(n, generator=self.gen, device=dev) * 1e-3 for n in sizes]
+        self._all_potentials = torch.cat([torch.rand(n, generator=self.gen, device=dev) * 1e-3 for n in sizes])
+        self.potentials = list(torch.split(self._all_potentials, sizes))
         self.min_potentials = torch.stack([p.min() for p in self.potentials])
+        self.table = GridIndexTable(self.indices, [0] + [int(v) for v in np.cumsum(sizes)[:-1]])
+        self._plan_ws = torch.empty(_lib.load().ct_kp_plan_workspace_bytes(len(sizes), max(sizes)), dtype=torch.uint8, device=dev)
+        self._device_plan = None
         self._mean = torch.tensor(COLOR_MEAN, dtype=torch.float32, device=dev)
         self._std = torch.tensor(COLOR_STD, dtype=torch.float32, device=dev)
         self.last_picks = []
         self.last_augment = (None, None, None)
+
+    @property
+    def last_picks(self):
+        if self._last_picks is None:
+            cloud, point, picks = self._device_plan
+            self._last_picks = [(c, point[i], picks[i]) for i, c in enumerate(cloud.tolist())]     # the one read
+        return self._last_picks
+
+    @last_picks.setter
+    def last_picks(self, value):
+        self._last_picks = value
 
     def _pick(self):
         """One item (s3dis_closer.py:247-276): pick, sorted radius query cut to num_points, Tukey update of the potentials."""
@@ -182,8 +203,29 @@ class SphereSampler:
         return ci, pick
 
     def plan(self, n):
-        """n picks by the potential field (`_pick`, advancing the potentials): (cloud i64[n], pick points f32[n, 3]), on the
-        device; `last_picks` gets them in order."""
+        """n picks by the potential field (advancing the potentials): (cloud i64[n], pick points f32[n, 3]), on the device;
+        `last_picks` gets them in order.  Draws n times randn(3), as `_pick` does, all before the one `ct_kp_plan` call."""
+        from .. import _lib
+        from ..ops import _on, _stream
+        n = int(n)
+        if n < 1 or os.environ.get("CLOUDCT_KP_PLAN", "1") == "0":
+            return self._plan_torch(n)
+        dev, r = self.device, self.in_radius
+        noise = torch.stack([torch.randn(3, generator=self.gen, device=dev) for _ in range(n)]) * (r / 10)
+        cloud = torch.empty(n, dtype=torch.int64, device=dev)
+        point = torch.empty(n, dtype=torch.int64, device=dev)
+        picks = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        with _on(dev):
+            _lib.check(_lib.load().ct_kp_plan(self.table.table.data_ptr(), self.table.n_clouds, self.table.max_points,
+                                              self._all_points.data_ptr(), self._all_potentials.data_ptr(),
+                                              self.min_potentials.data_ptr(), noise.data_ptr(), r, self.num_points, n,
+                                              cloud.data_ptr(), point.data_ptr(), picks.data_ptr(), self._plan_ws.data_ptr(),
+                                              self._plan_ws.numel(), _stream(dev)), "ct_kp_plan")
+        self._device_plan, self._last_picks = (cloud, point, picks), None
+        return cloud, picks
+
+    def _plan_torch(self, n):
+        """`plan` as the loop of `_pick` it was before ct_kp_plan: one device-to-host read per pick with several clouds."""
         self.last_picks = []
         cloud, picks = [], []
         for _ in range(int(n)):
@@ -193,8 +235,8 @@ class SphereSampler:
         return torch.tensor(cloud, dtype=torch.int64, device=self.device), torch.stack(picks)
 
     def items(self, cloud, picks, augment=None, generator=None):
-        """The items of picks (cloud i64[B], pick points f32[B, 3]), the 6-tuple of `sample`: one radius query per distinct cloud,
-        then the batch assembly `ct_kp_items`.  Draws, from `generator` (default: the sampler's own): the slot keys
+        """The items of picks (cloud i64[B], pick points f32[B, 3]), the 6-tuple of `sample`: one table-driven radius query for
+        the whole batch, then the batch assembly `ct_kp_items`.  Draws, from `generator` (default: the sampler's own): the slot keys
         rand(B, N), the padding rand(B, N), the colour drop rand(B); with `augment` (an `Augment`), then the angles, scales
         and mirrors rand(B, 3) each and the jitter randn(B, N, 3).  `last_augment` keeps the (R, s, j) of the last call."""
         gen = self.gen if generator is None else generator
@@ -202,17 +244,7 @@ class SphereSampler:
         cloud = cloud.to(dev)
         picks = picks.to(dev, torch.float32).contiguous()
         B = picks.shape[0]
-        idx = torch.empty(B, N, dtype=torch.int64, device=dev)
-        count = torch.empty(B, dtype=torch.int64, device=dev)
-        host_cloud = cloud.tolist()
-        for ci in sorted(set(host_cloud)):
-            rows = [b for b, c in enumerate(host_cloud) if c == ci]
-            sel = torch.tensor(rows, dtype=torch.int64, device=dev) if len(rows) < B else None
-            q_idx, _, q_count = self.indices[ci].query_radius(picks if sel is None else picks[sel], self.in_radius, N)
-            if sel is None:
-                idx, count = q_idx, q_count
-            else:
-                idx[sel], count[sel] = q_idx, q_count
+        idx, _, count = self.table.query_radius(cloud.long(), picks, self.in_radius, N)
         nvalid = torch.clamp(count, max=N)
         live = torch.arange(N, device=dev)[None, :] < nvalid[:, None]
         # a random permutation of the valid slots (:333-335); the argsort stays in torch, which decides the order of ties

@@ -134,3 +134,58 @@ class GridIndex:
                 _lib.check(lib.ct_nbr_nearest(self.cell_start.data_ptr(), self.sorted.data_ptr(), self._origin_c, self.h, self._dims_c,
                                               q[a:].data_ptr(), n, idx[a:].data_ptr(), d2[a:].data_ptr(), st), "ct_nbr_nearest")
         return idx, d2
+
+
+class GridIndexTable:
+    """The grids of several `GridIndex`es in one device-resident table (include/cloudct.h `ct_nbr_table_*`), so that a query
+    takes each centre's cloud from a device tensor and nothing is read back to choose an index.  `offsets[c]` is cloud c's
+    first row in the concatenated clouds (default: the clouds back to back).  The table keeps the indices alive; it is
+    filled on the host and uploaded once, here."""
+
+    def __init__(self, indices, offsets=None):
+        self.indices = list(indices)
+        n = len(self.indices)
+        if n < 1:
+            raise ValueError("GridIndexTable needs at least one GridIndex")
+        self.device = self.indices[0].device
+        if any(ix.device != self.device for ix in self.indices):
+            raise ValueError("GridIndexTable: every GridIndex must be on %s" % self.device)
+        if offsets is None:
+            offsets = [0] + list(np.cumsum([ix.M for ix in self.indices])[:-1])
+        self.offsets = [int(o) for o in offsets]
+        if len(self.offsets) != n:
+            raise ValueError("GridIndexTable: one offset per GridIndex")
+        self.n_clouds = n
+        self.max_points = max(ix.M for ix in self.indices)
+        lib = _lib.load()
+        host = torch.zeros(lib.ct_nbr_table_bytes(n), dtype=torch.uint8)
+        for i, (ix, off) in enumerate(zip(self.indices, self.offsets)):
+            _lib.check(lib.ct_nbr_table_set(host.data_ptr(), n, i, ix.cell_start.data_ptr(), ix.sorted.data_ptr(), ix._origin_c, ix.h,
+                                            ix._dims_c, ix.M, off), "ct_nbr_table_set")
+        self.table = host.to(self.device)
+
+    def query_radius(self, cloud, centres, r, k):
+        """`GridIndex.query_radius` of centre q in cloud[q] (i64[Q], on the device), all Q in one launch: the same
+        (idx i64[Q,k], d2 f32[Q,k], count i64[Q])."""
+        c = self.indices[0]._query_tensor(centres, "centres")
+        _dev(cloud)
+        if cloud.device != self.device or cloud.dtype != torch.int64 or cloud.dim() != 1 or cloud.shape[0] != c.shape[0]:
+            raise ValueError("query_radius: cloud must be int64 [Q] on %s" % self.device)
+        cloud = cloud.contiguous()
+        k = int(k)
+        if not 1 <= k <= _lib.NBR_K_MAX:
+            raise ValueError("query_radius: k must be in [1, %d]" % _lib.NBR_K_MAX)
+        if not float(r) >= 0:
+            raise ValueError("query_radius: r must be >= 0")
+        Q = c.shape[0]
+        dev = self.device
+        idx = torch.empty(Q, k, dtype=torch.int64, device=dev)
+        d2 = torch.empty(Q, k, dtype=torch.float32, device=dev)
+        count = torch.empty(Q, dtype=torch.int64, device=dev)
+        if Q == 0:
+            return idx, d2, count
+        with _on(dev):
+            _lib.check(_lib.load().ct_nbr_radius_multi(self.table.data_ptr(), self.n_clouds, cloud.data_ptr(), c.data_ptr(), Q, float(r),
+                                                       k, idx.data_ptr(), d2.data_ptr(), count.data_ptr(), _stream(dev)),
+                       "ct_nbr_radius_multi")
+        return idx, d2, count

@@ -38,7 +38,8 @@ extern "C" {
  * with n = 1 — and ct_bn_group_reduce_bwd_copy, whose sums_copy is now a nullable argument of ct_bn_group_reduce_bwd.  Changed:
  * the four exchange phases ct_bn_group_{stats,apply}_fwd / {reduce,apply}_bwd take the whole table plus the run of items to launch.
  * (ct_scan_items was added under version 3 without a bump: an additive symbol, which the loader's missing-symbol scan checks;
- * ct_block_items and ct_seg_confusion the same way.) */
+ * ct_block_items and ct_seg_confusion the same way; then the index table ct_nbr_table_bytes / ct_nbr_table_set /
+ * ct_nbr_radius_multi and the device plan ct_kp_plan / ct_kp_plan_workspace_bytes.) */
 #define CT_ABI_VERSION 3
 
 /* status codes */
@@ -622,6 +623,62 @@ int ct_nbr_radius(const int32_t* cell_start, const float* sorted, const float* o
                   const float* centres, int Q, float r, int K, int64_t* idx, float* d2, int64_t* count, ct_stream_t s);
 int ct_nbr_nearest(const int32_t* cell_start, const float* sorted, const float* origin, float h, const int* dims,
                    const float* queries, int64_t Q, int64_t* idx, float* d2, ct_stream_t s);
+
+/* ------------------------------------------------------------------------
+ * The index table: the grids of several clouds in device memory, so that a query can take its
+ * cloud from a device tensor.  Added under CT_ABI_VERSION 3 (additive, as ct_nbr_*).
+ *
+ * One record per cloud; the record layout is private to the library.  ct_nbr_table_bytes: the
+ * size of a table of n_clouds records (0 = n_clouds < 1).  ct_nbr_table_set writes record i
+ * (0 <= i < n_clouds) into a HOST buffer of that size (8-byte aligned) from the cloud's index
+ * (cell_start, sorted, origin, h, dims as ct_nbr_radius takes them, with the same checks: the
+ * grid's bounds, sorted 16-byte aligned), its point count M (1 <= M < 2^31) and offset >= 0, the
+ * cloud's first row in the concatenated sub-clouds; CT_EINVAL otherwise.  The caller uploads the
+ * filled buffer once (8-byte aligned on the device) and keeps the indices alive.
+ * ct_nbr_radius_multi: ct_nbr_radius with the grid of centre q taken from record cloud[q]
+ * (cloud i64[Q], device; clamped into [0, n_clouds - 1] as a guard): the same workgroup, the
+ * same (d2, index) order, the same outputs idx i64[Q,K], d2 f32[Q,K], count i64[Q].
+ * ---------------------------------------------------------------------- */
+size_t ct_nbr_table_bytes(int n_clouds);
+int ct_nbr_table_set(void* host_table, int n_clouds, int i, const int32_t* cell_start, const float* sorted, const float* origin,
+                     float h, const int* dims, int64_t M, int64_t offset);
+int ct_nbr_radius_multi(const void* table, int n_clouds, const int64_t* cloud, const float* centres, int Q, float r, int K,
+                        int64_t* idx, float* d2, int64_t* count, ct_stream_t s);
+
+/* ------------------------------------------------------------------------
+ * The epoch plan of the S3DIS KPConv sampler (datasets/s3dis_closer.py:247-276): n picks by the
+ * potential field, enqueued by one call; the host reads nothing back.  Added under CT_ABI_VERSION 3
+ * (additive, as ct_nbr_table_*).
+ *
+ * Inputs (device): table (ct_nbr_table_*, n_clouds records, 1 <= n_clouds <= 65535), points
+ * f32[total,3] (the concatenated sub-clouds the records' offsets index), noise f32[n,3] (already
+ * scaled).  Updated: potentials f32[total] (cloud c's are potentials[offset_c .. offset_c + M_c)),
+ * min_potentials f32[n_clouds].  Outputs: cloud i64[n], point i64[n], picks f32[n,3].  Host values:
+ * r >= 0 (a double: the query gets (float)r), 1 <= K <= 16384, n >= 1, max_points = the largest
+ * M_c (it sizes the reduction's grid and the workspace only: the kernels take every M_c from the
+ * table).  All arithmetic is fp32, one rounding per operation, no contraction.
+ *
+ * On entry, for every cloud c: min_potentials[c] = min(potentials of c) and arg_c = the lowest
+ * index holding it, recomputed from the buffers (nothing is cached between calls).  Then for
+ * i = 0 .. n-1, in order:
+ *   cloud[i] = the lowest c among the minima of min_potentials; point[i] = arg_c of that cloud;
+ *   picks[i] = points[offset_c + point[i]] + noise[i], one add per component;
+ *   (idx, d2, count) = ct_nbr_radius_multi at picks[i] in cloud[i] with (float)r and K;
+ *   for each of the first min(count, K) entries: t = 1 - d2 * inv, pot[idx] = pot[idx] + t*t, with
+ *     inv = 1.0f / (float)(r*r), r*r formed in double (torch: tensor / Python number);
+ *   min_potentials[c] = min(potentials of c), arg_c = its lowest index.
+ * Potentials must not be NaN (a NaN never wins a minimum).  cloud ids and point indices are clamped
+ * into range as a guard; valid inputs never need it.
+ *
+ * Launches: one begin kernel, then per pick one query workgroup and one multi-workgroup reduction
+ * whose last-arriving workgroup writes the next pick; kernel boundaries order the picks.
+ * Workspace: ct_kp_plan_workspace_bytes (0 = bad arguments), 8-byte aligned, contents irrelevant
+ * on entry; too small or null -> CT_EWORKSPACE.
+ * ---------------------------------------------------------------------- */
+size_t ct_kp_plan_workspace_bytes(int n_clouds, int64_t max_points);
+int ct_kp_plan(const void* table, int n_clouds, int64_t max_points, const float* points, float* potentials,
+               float* min_potentials, const float* noise, double r, int K, int n, int64_t* cloud, int64_t* point, float* picks,
+               void* workspace, size_t workspace_bytes, ct_stream_t s);
 
 /* ------------------------------------------------------------------------
  * Batch assembly of the S3DIS KPConv items (datasets/s3dis_closer.py:319-361) with the optional

@@ -8,7 +8,9 @@ Rows:
   before ct_kp_items (restated here; with augmentation, the rotation, scale and jitter added in torch) against one
   ct_kp_items launch, without and with augmentation (the slot keys' argsort is in both);
 - SphereSampler.sample(6), beside the 2.0 ms recorded before ct_kp_items (profiles/r7_kpconv_data_bench.txt);
-- one epoch plan of 2000 picks (SphereSampler.plan);
+- one epoch plan of 2000 picks: SphereSampler.plan (one ct_kp_plan call) and the torch loop it replaced (_plan_torch), alternating
+  in this run from the same sampler state and seed, three repeats each (the mean and the [min, max] spread), on the one cloud
+  and on five Area-like clouds in the proportions of the S3DIS training Areas (together ~2.5 x the one cloud);
 - one training step (masked cross-entropy, clip_grad_norm 10, Adam) of model_zoo/s3dis/segmenter_pad.py's structure
   (defined here: 12 MultiHeadUnion blocks, model_dim 512) at B6 N8192 through harness.Trainer, eager and graphed, on one
   fixed batch and with the data side (items of an epoch plan, augmented) in the loop."""
@@ -95,6 +97,29 @@ def kernel_assembly(smp, idx, count, picks, cloud, gen, aug=None):
                     COLOR_MEAN, COLOR_STD, smp.input_features_dim, R, s, j)
 
 
+def plan_pair(smp, n, repeats=3):
+    """(device plan ms, torch loop ms, equal): `plan(n)` and `_plan_torch(n)` alternating, each from the same potentials and the
+    same generator state; per side the mean and the [min, max] over the repeats, after one warm-up each."""
+    import time
+    state = (smp._all_potentials.clone(), smp.min_potentials.clone(), smp.gen.get_state())
+    times, outs = {"device": [], "torch": []}, {}
+    for rep in range(repeats + 1):
+        for name, fn in (("device", smp.plan), ("torch", smp._plan_torch)):
+            smp._all_potentials.copy_(state[0])
+            smp.min_potentials.copy_(state[1])
+            smp.gen.set_state(state[2])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn(n)
+            torch.cuda.synchronize()
+            if rep:
+                times[name].append((time.perf_counter() - t0) * 1e3)
+            outs[name] = (out[0], out[1], smp._all_potentials.clone())
+    equal = all(torch.equal(a, b) for a, b in zip(outs["device"], outs["torch"]))
+    row = lambda t: [round(sum(t) / len(t), 1), round(min(t), 1), round(max(t), 1)]        # noqa: E731
+    return row(times["device"]), row(times["torch"]), equal
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=1_000_000, help="target size of the subsampled cloud")
@@ -133,7 +158,26 @@ def main():
     res["sample6_N8192_ms"] = round(gpu_ms(lambda: smp.sample(6), args.iters), 3)
     res["sample6_N8192_aug_ms"] = round(gpu_ms(lambda: smp.sample(6, Augment()), args.iters), 3)
     res["sample6_N8192_recorded_before_ms"] = 2.0
-    res["plan2000_ms"] = round(gpu_ms(lambda: smp.plan(2000), 2, warmup=1), 1)
+    dev_ms, torch_ms, same = plan_pair(smp, 2000)
+    res["plan2000_ms"], res["plan2000_spread_ms"] = dev_ms[0], dev_ms[1:]
+    res["plan2000_torch_ms"], res["plan2000_torch_spread_ms"] = torch_ms[0], torch_ms[1:]
+    res["plan2000_equal"] = same
+    five = []
+    for k, share in enumerate((0.57, 0.61, 0.24, 0.55, 0.53)):
+        side5 = float(np.sqrt(args.points * share / 625.0 / 2.6))
+        raw5 = area_like(int(args.points * share * 2.5), 10 + k, (1.6 * side5, side5, 3.5))
+        rng5 = np.random.default_rng(20 + k)
+        c5 = rng5.integers(0, 256, (raw5.shape[0], 3)).astype(np.float32)
+        l5 = rng5.integers(0, 13, raw5.shape[0]).astype(np.int32)
+        p5, sc5, sl5 = grid_subsampling(raw5, features=c5, labels=l5[:, None], sampleDl=0.04)
+        five.append(Area("Area_bench_%d" % k, raw5, c5, l5, p5, sc5 / np.float32(255), sl5[:, 0]))
+    smp5 = SphereSampler(five, 8192, in_radius=2.0, input_features_dim=4, generator=torch.Generator(device="cuda").manual_seed(0))
+    res["five_clouds_sub_points"] = [int(a.sub_points.shape[0]) for a in five]
+    dev_ms, torch_ms, same = plan_pair(smp5, 2000)
+    res["plan2000_five_clouds_ms"], res["plan2000_five_clouds_spread_ms"] = dev_ms[0], dev_ms[1:]
+    res["plan2000_five_clouds_torch_ms"], res["plan2000_five_clouds_torch_spread_ms"] = torch_ms[0], torch_ms[1:]
+    res["plan2000_five_clouds_equal"] = same
+    del smp5, five
 
     if not args.no_step:
         from cloud_transformers_amd import harness
