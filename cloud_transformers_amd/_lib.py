@@ -22,7 +22,7 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 
 HIP_SOURCES = ["ct_raster.hip", "ct_mhct.hip", "ct_lattice.hip", "ct_gconv.hip", "ct_chamfer.hip", "ct_emd.hip",
                "ct_adain.hip", "ct_bnorm.hip", "ct_pwgemm.hip", "ct_nbr.hip", "ct_kpitems.hip", "ct_completion.hip", "ct_scanitems.hip",
-               "ct_blockitems.hip", "ct_kpplan.hip"]
+               "ct_blockitems.hip", "ct_kpplan.hip", "ct_imageitems.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared",
                # index/weight math must round exactly like the reference's fp32 op sequence
                "-ffp-contract=off"]
@@ -88,6 +88,12 @@ COMPLETION_GT_MAX = 1 << 24
 SCAN_P_MAX = 16384         # ct_scan_items: points of one stored cloud
 BLOCK_P_MAX = 16384        # ct_block_items: points of one stored block
 CONFUSION_C_MAX = 64       # ct_seg_confusion: classes
+IMAGE_TAPS_MAX = 64        # ct_image_items: taps of one output pixel per axis (CT_IMAGE_TAPS_MAX)
+IMAGE_W_MAX = 2048         # ct_image_items: source width
+IMAGE_SIZE_MAX = 4096      # ct_image_items: source height, output height and width
+IMAGE_STAGE_BYTES = 36 * 1024   # ct_image_items: LDS for one band's horizontally resampled rows
+IMAGE_P_MAX = 1 << 16      # ct_image_items: points of one stored cloud
+IMAGE_N_MAX = 1 << 20      # ct_image_items: slots of one output cloud
 
 _lock = threading.Lock()
 _lib = None
@@ -315,6 +321,8 @@ SIGNATURES = {
     "ct_scan_items": (_i, [_vp, _vp, _vp, ctypes.c_int64, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _vp, _vp, _vp]),
     "ct_block_items": (_i, [_vp, _vp, ctypes.c_int64, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _i, _vp, _vp, _vp]),
     "ct_seg_confusion": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "ct_image_items": (_i, [_vp, ctypes.c_int64, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _fp, _fp, _vp, _vp, _vp, _i, _vp, _vp, _vp,
+                            _i, _i, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -25,7 +25,11 @@ package's layers and checkpoints stay interchangeable.
   `data.num_points`, `data.test_area`, `data.data_percent`, `data.aug`, `data.batch_size_val` as configs/s3dis.yaml has them)
   keeps the 1x1 m blocks on the device, assembles and augments every batch in one launch (data/s3dis_blocks.py), fills the
   train and validation confusion matrices on the device and appends every validation to <exp>/segmentation_val.jsonl
-  (train_segmentation.py).  The image_point variant stays out of scope.
+  (train_segmentation.py).  `what3d_device` (the `reconstruction` task; `data.path`, `data.im_size`, `data.gt_size`,
+  `data.batch_size_val` as configs/reconstruction.yaml has them, optional `data.cache_dir`) keeps the decoded renderings and
+  the clouds of a What3D split on the device, resizes, normalises and resamples every batch in one launch
+  (data/image_point.py), trains on the EMD, validates every epoch (<exp>/reconstruction_val.jsonl, the `best` checkpoints) and
+  scores F1 on the test split (train_reconstruction.py; train_image_reconstruction.py, eval_reconstruction_f1.py).
 """
 import copy
 import datetime
@@ -49,11 +53,16 @@ def worker_init_fn(worker_id):
 
 
 def get_model(model_file, params_dict, exp_dir=None):
-    """Instantiate `Model(**params_dict)` from a model python file; keep a copy beside the experiment."""
+    """Instantiate `Model(**params_dict)` from a model python file; keep a copy beside the experiment.  A model file that
+    imports `torchvision.models` for its `resnet50` (model_zoo/image_reconstruction/reconstructor.py) builds without
+    torchvision too: while the file executes, and only when `import torchvision` fails, layers/resnet.py's stand-in pair sits in
+    sys.modules; it is removed afterwards."""
+    from .layers.resnet import stand_in_for_torchvision
     env = {"__name__": "model_file"}
-    with open(str(model_file), "r") as f:
-        exec(compile(f.read(), str(model_file), "exec"), env)
-    model = env["Model"](**params_dict)
+    with stand_in_for_torchvision():
+        with open(str(model_file), "r") as f:
+            exec(compile(f.read(), str(model_file), "exec"), env)
+        model = env["Model"](**params_dict)
     if exp_dir is not None:
         assert Path(exp_dir).exists()
         shutil.copy2(str(model_file), str(exp_dir))
@@ -188,9 +197,17 @@ def make_dataset(cfg, task, n_classes, length=64, channels=3, train=True):
     "s3dis_kpconv" gives the (train, validation) Areas of train_kpconv.load_kpconv_areas (`train=False`: no train Areas);
     "shapenet_completion" the TRAIN (`train=False`: VAL) subset of data/completion.py's ShapeNetDataLoader;
     "scanobjectnn_device" the ScanObjectNN of `data.path` (`train=False`: `data.path_val`) with its items left to the device;
-    "s3dis_device" the Indoor3DSemSeg of `data.path` (`train=False`: the blocks of `data.test_area`), its items left to the device."""
+    "s3dis_device" the Indoor3DSemSeg of `data.path` (`train=False`: the blocks of `data.test_area`), its items left to the device;
+    "what3d_device" the ImageToPoint of `data.path`, split 'train' (`train=False`: 'val'; `train="test"`: 'test' with
+    `data.eval_points` points), its items left to the device."""
     data = cfg["data"]
     kind = str(data.get("kind", "synthetic")).lower()
+    if kind == "what3d_device":
+        assert task == "reconstruction", "data.kind what3d_device is the reconstruction task"
+        from .data.image_point import ImageToPoint
+        split = "test" if train == "test" else ("train" if train else "val")
+        return ImageToPoint(data["path"], split=split, im_size=data["im_size"],
+                            points=data["eval_points"] if split == "test" else data["gt_size"])
     if kind == "s3dis_device":
         assert task == "segmentation_blocks", "data.kind s3dis_device is the segmentation_blocks task"
         from .data import datasets as D
@@ -222,8 +239,8 @@ def make_dataset(cfg, task, n_classes, length=64, channels=3, train=True):
         assert task == "segmentation", "S3DIS blocks are (points, labels): the segmentation task"
         return D.Indoor3DSemSeg(data["path"], data["num_points"], train=train, aug=bool(data.get("aug", train)),
                                 test_area=data.get("test_area", "Area_5"), data_precent=float(data.get("data_precent", 1.0)))
-    raise ValueError("data.kind must be synthetic, scanobjectnn, scanobjectnn_device, s3dis, s3dis_device, s3dis_kpconv or shapenet_completion "
-                     "(got %r)" % kind)
+    raise ValueError("data.kind must be synthetic, scanobjectnn, scanobjectnn_device, s3dis, s3dis_device, s3dis_kpconv, shapenet_completion "
+                     "or what3d_device (got %r)" % kind)
 
 
 class Trainer:
@@ -248,7 +265,14 @@ class Trainer:
     data.s3dis_blocks.DeviceS3DISBlocks): loss = CE(pred[:, :, 0], labels) on batches assembled on the device (data/s3dis_blocks.py
     BlockBatches), a train confusion matrix updated every step on the device and reported per epoch (`train_records`),
     validation every `train.val_step` epochs (<exp>/segmentation_val.jsonl), `generator_iter_{n}.t7` every `train.save_each`
-    iterations and `generator_epoch_{e}.t7` every `train.save_each_epoch` epochs (train_segmentation.py)."""
+    iterations and `generator_epoch_{e}.t7` every `train.save_each_epoch` epochs (train_segmentation.py).
+    "reconstruction" (selected by `data.kind: what3d_device` too; `dataset` may be a data.image_point.ImageToPoint or a
+    data.image_point.DeviceImageToPoint; `n_classes` is not used): noise = sphere_noise(B, gt_size), rec = model(noise, img)[0],
+    loss = mean sqrt(EMD(rec, gt, train.emd_eps, train.emd_iters)) on batches assembled on the device (data/image_point.py
+    ImageBatches); loss_chamfer_adj is computed without gradient and logged (`last_chamfer`); the scheduler steps per iteration,
+    `generator_iter_{n}.t7` every `train.save_each` iterations; a validation every epoch (<exp>/reconstruction_val.jsonl,
+    `generator_epoch_{e}.t7` every `train.save_each_epoch` epochs, `generator_best_0.t7` on a new minimum of the EMD —
+    train_reconstruction.py, train_image_reconstruction.py)."""
 
     def __init__(self, cfg, task, n_classes, device=None, dist=None, exp_name="exp", dataset_length=64, make_dirs=True,
                  channels=3, dataset=None):
@@ -264,6 +288,10 @@ class Trainer:
         if task == "segmentation_blocks" or str(cfg["data"].get("kind", "")).lower() == "s3dis_device":
             from .train_segmentation import segmentation_config
             task, self.cfg = "segmentation_blocks", segmentation_config(cfg)
+            cfg = self.cfg
+        if task == "reconstruction" or str(cfg["data"].get("kind", "")).lower() == "what3d_device":
+            from .train_reconstruction import reconstruction_config
+            task, self.cfg = "reconstruction", reconstruction_config(cfg)
             cfg = self.cfg
         self.task, self.dist, self.n_classes = task, dist, n_classes
         self.rank = dist.get_rank() if parallel._active(dist) else 0
@@ -317,7 +345,12 @@ class Trainer:
         self.scan, self.best_acc, self.best_macc = task == "classification_scanobjectnn", float("-inf"), float("-inf")
         self.blocks, self.train_meter, self.train_records, self._pred = task == "segmentation_blocks", None, [], None
         self._graph_preds = {}
-        if self.blocks:
+        self.recon, self.last_chamfer, self._noise_gen = task == "reconstruction", None, None
+        if self.recon:
+            self.sampler = None                          # (ImageBatches holds torch's DistributedSampler itself)
+            self.loader = self._image_batches(data, train=True)
+            self._noise_gen = torch.Generator(device=self.device).manual_seed(int(cfg["data"]["seed"]) * 1000003 + 15485863 + self.rank)
+        elif self.blocks:
             from .data.s3dis_blocks import SegmentationMeter
             self.sampler = None                          # (BlockBatches holds torch's DistributedSampler itself)
             self.loader = self._block_batches(data, train=True)
@@ -378,11 +411,39 @@ class Trainer:
                             cstd=float(d["color_jitter_std"]), ratio=float(d["color_shift_ratio"]), hue_max=float(d["hue_max"]),
                             sat_max=float(d["saturation_max"]))
 
+    def _image_batches(self, data, train, points=None):
+        """ImageBatches over `data` (a host ImageToPoint is decoded and uploaded first) with the config's sizes, this rank's shard."""
+        from .data.image_point import DeviceImageToPoint, ImageBatches
+        d = self.cfg["data"]
+        ds = data if isinstance(data, DeviceImageToPoint) else DeviceImageToPoint(data, self.device, cache_dir=d.get("cache_dir"))
+        active = parallel._active(self.dist)
+        return ImageBatches(ds, d["batch_size"] if train else d["batch_size_val"], train=train, seed=int(d["seed"]) + (0 if train else 7919),
+                            rank=self.rank, world=self.dist.get_world_size() if active else 1,
+                            drop_last=bool(d.get("drop_last", False)) and train, points=points)
+
+    def _reconstruct(self, img, pcd_gt, eps, iters, n_noise=None):
+        """(sqrt-EMD loss, rec [B, 3, 1, N], gt [B, 3, 1, n]) of train_image_reconstruction.py:166-175 for a device batch."""
+        from .emd import emdModule
+        from .metrics import sphere_noise
+        gt = pcd_gt[:, :, None]
+        noise = sphere_noise(gt.shape[0], gt.shape[-1] if n_noise is None else n_noise, gt.device, generator=self._noise_gen)
+        out = self.model(noise, img)
+        rec = out[0] if isinstance(out, (tuple, list)) else out
+        dist, _ = emdModule()(rec[:, :, 0].permute(0, 2, 1), gt[:, :, 0].permute(0, 2, 1), eps, iters)
+        return torch.sqrt(dist).mean(1).mean(), rec, gt
+
     def _block_pred(self, pcd):
         out = self.model(pcd)
         return out[0] if isinstance(out, (tuple, list)) else out                      # the reference returns (pred, lattice stats)
 
     def _loss(self, batch):
+        if self.task == "reconstruction":
+            from .chamfer import loss_chamfer_adj
+            tr = self.cfg["train"]
+            loss, rec, gt = self._reconstruct(batch[0], batch[1], float(tr["emd_eps"]), int(tr["emd_iters"]))
+            with torch.no_grad():
+                self.last_chamfer = loss_chamfer_adj(rec.detach(), gt)
+            return loss
         if self.task == "segmentation_blocks":
             pcd, labels = batch
             pred = self._block_pred(pcd)
@@ -474,6 +535,49 @@ class Trainer:
                 self.writer.add_scalar("val/val_" + k, rec[k], global_step=step)
             if self.exp_dir is not None:
                 with open(str(Path(self.exp_dir) / "completion_val.jsonl"), "a") as f:
+                    f.write(json.dumps(rec) + "\n")
+                if best:
+                    parallel.save_exp_parallel([self.model, self.optimizer], ["generator", "g_opt"], exp_path=self.exp_dir,
+                                               epoch=0, epoch_name="best")
+        self.val_records.append(rec)
+        return [rec]
+
+    def _validate_reconstruction(self, epoch, dataset=None):
+        """train_image_reconstruction.py:225-268: eval mode, no grad, the 'val' split in batches of `data.batch_size_val`; per
+        batch sqrt(EMD(rec, gt, val_emd_eps, val_emd_iters)).mean(1).mean() and loss_chamfer_adj, averaged over the batches and
+        the ranks (sums and the count stay on the device until the one read at the end); `best`: a new minimum of the EMD."""
+        import json
+        from .chamfer import loss_chamfer_adj
+        tr = self.cfg["train"]
+        if self.val_loader is None or dataset is not None:
+            data = dataset if dataset is not None else make_dataset(self.cfg, self.task, self.n_classes, train=False)
+            self.val_loader = self._image_batches(data, train=False)
+        model = self.model
+        was_training = model.training
+        model.eval()
+        self.val_loader.set_epoch(epoch if isinstance(epoch, int) else 0)
+        sums = torch.zeros(3, dtype=torch.float64, device=self.device)            # loss_emd, loss_chamfer, batches
+        with torch.no_grad():
+            for img, pcd in self.val_loader:
+                l_emd, rec, gt = self._reconstruct(img, pcd, float(tr["val_emd_eps"]), int(tr["val_emd_iters"]))
+                l_cd = loss_chamfer_adj(rec, gt)
+                sums += torch.stack([l_emd, l_cd, torch.ones_like(l_cd)]).double()
+        model.train(was_training)
+        if parallel._active(self.dist):
+            self.dist.all_reduce(sums)
+        s = sums.tolist()
+        n = max(s[2], 1.0)
+        rec = {"epoch": epoch, "iters": self.iters, "batches": int(s[2]), "loss_emd": s[0] / n, "loss_chamfer": s[1] / n}
+        best = self.best_val is None or rec["loss_emd"] < self.best_val
+        rec["best"] = bool(best)
+        if best:
+            self.best_val = rec["loss_emd"]
+        if self.rank == 0:
+            step = epoch if isinstance(epoch, int) else self.iters
+            for k in ("loss_emd", "loss_chamfer"):
+                self.writer.add_scalar("val/val_" + k, rec[k], global_step=step)
+            if self.exp_dir is not None:
+                with open(str(Path(self.exp_dir) / "reconstruction_val.jsonl"), "a") as f:
                     f.write(json.dumps(rec) + "\n")
                 if best:
                     parallel.save_exp_parallel([self.model, self.optimizer], ["generator", "g_opt"], exp_path=self.exp_dir,
@@ -594,8 +698,12 @@ class Trainer:
         (losses, cls_acc, seg_acc, m_acc, class_acc) appended to <exp>/classification_val.jsonl; `generator_best_0.t7` /
         `g_opt_best_0.t7` saved on a new best cls_acc, `generator_macc_best_0.t7` / `g_opt_macc_best_0.t7` on a new best m_acc.
         segmentation_blocks (`num_votes` is not used): one pass over the blocks of `data.test_area` (`_validate_blocks`), its record
-        (loss, overall_acc, mean_class_acc, iou_<name>, mean_iou) appended to <exp>/segmentation_val.jsonl."""
+        (loss, overall_acc, mean_class_acc, iou_<name>, mean_iou) appended to <exp>/segmentation_val.jsonl.
+        reconstruction (`num_votes` is not used): one pass over the 'val' split (`_validate_reconstruction`), its record (loss_emd,
+        loss_chamfer) appended to <exp>/reconstruction_val.jsonl; `generator_best_0.t7` / `g_opt_best_0.t7` on a new minimum."""
         import json
+        if self.task == "reconstruction":
+            return self._validate_reconstruction(epoch)
         if self.task == "segmentation_blocks":
             return self._validate_blocks(epoch)
         if self.task == "completion":
@@ -730,8 +838,11 @@ class Trainer:
         tr = self.cfg["train"]
         use_graph = bool(tr.get("hip_graph", False) if hip_graph is None else hip_graph)
         log_each = int(tr.get("log_each", 10) if log_each is None else log_each)
+        if use_graph and self.recon:
+            raise ValueError("the reconstruction task draws its sphere noise inside the step from a generator of its own: "
+                             "train.hip_graph is not available for it")
         self._graphs, self._graph_preds = {}, {}
-        history, pending = [], []
+        history, pending, pending_chamfer = [], [], []
 
         def flush():
             if self.device.type == "cuda":
@@ -743,11 +854,16 @@ class Trainer:
                     history.append(v)
                     self.writer.add_scalar("train/loss", v, global_step=it)
             pending.clear()
+            if pending_chamfer and self.rank == 0:
+                stamps, vals = zip(*pending_chamfer)
+                for it, v in zip(stamps, torch.stack(vals).tolist()):
+                    self.writer.add_scalar("train/loss_chamfer", v, global_step=it)
+            pending_chamfer.clear()
 
         for epoch in range(tr["num_epochs"]):
             if self.sampler is not None:
                 self.sampler.set_epoch(epoch)
-            if self.scan or self.blocks:
+            if self.scan or self.blocks or self.recon:
                 self.loader.set_epoch(epoch)
             self.model.train()
             end = time.time()
@@ -763,6 +879,9 @@ class Trainer:
                     self.scheduler.step()
                 reduced = parallel.reduce_loss_dict(self.dist, {"loss": loss})
                 pending.append((self.iters, reduced["loss"].detach().reshape(())))
+                if self.recon and self.last_chamfer is not None:
+                    chamfer = parallel.reduce_loss_dict(self.dist, {"loss_chamfer": self.last_chamfer})["loss_chamfer"]
+                    pending_chamfer.append((self.iters, chamfer.detach().reshape(())))
                 self.iters += 1
                 if self.iters % log_each == 0:
                     flush()
@@ -795,6 +914,12 @@ class Trainer:
                     self.save(epoch=epoch)
                 if epoch % int(tr["val_step"]) == 0:
                     self.validate(epoch=epoch)
+            if self.recon:
+                # train_image_reconstruction.py:225-268: a validation every epoch, checkpoints by the 0-based epoch
+                flush()
+                self.validate(epoch=epoch)
+                if epoch % int(tr["save_each_epoch"]) == 0:
+                    self.save(epoch=epoch)
             if self.scan:
                 # train_classification.py:281-286: checkpoints and validation by the 0-based epoch
                 flush()

@@ -39,7 +39,7 @@ extern "C" {
  * the four exchange phases ct_bn_group_{stats,apply}_fwd / {reduce,apply}_bwd take the whole table plus the run of items to launch.
  * (ct_scan_items was added under version 3 without a bump: an additive symbol, which the loader's missing-symbol scan checks;
  * ct_block_items and ct_seg_confusion the same way; then the index table ct_nbr_table_bytes / ct_nbr_table_set /
- * ct_nbr_radius_multi and the device plan ct_kp_plan / ct_kp_plan_workspace_bytes.) */
+ * ct_nbr_radius_multi and the device plan ct_kp_plan / ct_kp_plan_workspace_bytes; then ct_image_items.) */
 #define CT_ABI_VERSION 3
 
 /* status codes */
@@ -823,6 +823,52 @@ int ct_block_items(const float* data, const uint8_t* label, int64_t M, int P, co
  * Integer counts only: the result does not depend on the order of the workgroups.
  * ---------------------------------------------------------------------- */
 int ct_seg_confusion(const float* pred, const int64_t* labels, int B, int C, int N, int64_t* conf, ct_stream_t s);
+
+/* ------------------------------------------------------------------------
+ * Batch assembly of the What3D single-view reconstruction items (datasets/image_point.py:128-150:
+ * Resize, ToTensor, Normalize of the rendering, resample_pcd of the cloud; the collate), one launch,
+ * every random draw passed in.  Added under CT_ABI_VERSION 3 (additive, as ct_scan_items).
+ * It does not allocate, does not synchronise and runs on the stream s.
+ *
+ * The split stays on the device: images u8[M,H,W,3] (RGB, interleaved; the pointer 4-byte aligned),
+ * points f32[T,3] (all clouds concatenated), offsets i64[M+1] (cloud g is points[offsets[g] ..
+ * offsets[g+1]), 1 .. p_cap points), class_id i64[M]; M >= 1.  A batch is B rows (1 <= B <= 65535);
+ * item i64[B] names the object of each row (repeats allowed), g = clamp(item[b], 0, M-1).
+ *
+ * Image: out_img f32[B,3,OH,OW] is Pillow's 8-bit resize((OW, OH), BILINEAR) of images[g], then
+ * ToTensor and Normalize.  The resample is Pillow's integer arithmetic, horizontal pass first into
+ * 8-bit intermediates, the vertical pass on those; its coefficients come in as four tables built
+ * once per (H, W, OH, OW) in float64 (data/image_point.py resize_tables):
+ *   kx i32[OW,ksx], bx i32[OW,2] = (xmin, taps); ky i32[OH,ksy], by i32[OH,2] = (ymin, taps);
+ *   per axis with scale = in / out, fs = max(scale, 1), support = fs: ks = 2 * ceil(support) + 1,
+ *   center = (i + 0.5) * scale, min = max(int(center - support + 0.5), 0),
+ *   taps = min(int(center + support + 0.5), in) - min, w[x] = max(0, 1 - |(x + min - center + 0.5) / fs|)
+ *   divided by their sum when it is not zero, k[x] = int(0.5 + w[x] * 2^22) (entries past taps: 0).
+ *   byte = clamp((2^21 + sum_x pixel[min + x] * k[x]) >> 22, 0, 255) in 32-bit integers.
+ * Float stage, each operation one fp32 rounding, IEEE division:
+ *   v = ((float)byte / 255.0f - mean[c]) / std[c]; mean, std: HOST arrays of three finite floats, std != 0.
+ * Limits: 1 <= H, OH, OW <= 4096, 1 <= W <= 2048, 1 <= ksx, ksy <= 64 (CT_IMAGE_TAPS_MAX), and one
+ * output row's source rows after the horizontal pass, min(H, ksy) * 3 * OW bytes, within the 36 KiB
+ * of LDS the kernel stages them in.  The table entries are clamped to the image; the clamps are
+ * guards, valid tables never need them.
+ *
+ * Points: out_pcd f32[B,3,n] (1 <= n <= 2^20) is resample_pcd(cloud g, n) transposed, on the draws
+ * perm i64[B,p_cap] (the argsort of plain random keys; 1 <= p_cap <= 65536, p_cap >= every cloud's
+ * length) and u_dup f32[B,n] in [0, 1).  With P the cloud's length: slot j < min(n, P) takes the
+ * j-th entry of perm[b] that is below P, in order (an order-preserving compaction: a uniform
+ * permutation of p_cap restricted this way is a uniform permutation of P); slot j >= P takes point
+ * min((int)(u_dup[b,j] * (float)P), P - 1) (one fp32 multiply; a NaN draw gives point 0).
+ * out_class i64[B] = class_id[g].
+ * Null pointers, a misaligned images pointer, sizes outside the limits, more taps than
+ * CT_IMAGE_TAPS_MAX and an output row that does not fit the LDS budget -> CT_EINVAL before anything
+ * touches the device.
+ * ---------------------------------------------------------------------- */
+#define CT_IMAGE_TAPS_MAX 64
+int ct_image_items(const uint8_t* images, int64_t M, int H, int W, int OH, int OW, const int32_t* kx, const int32_t* bx,
+                   int ksx, const int32_t* ky, const int32_t* by, int ksy, const float* mean, const float* std,
+                   const float* points, const int64_t* offsets, const int64_t* class_id, int p_cap, const int64_t* item,
+                   const int64_t* perm, const float* u_dup, int B, int n, float* out_img, float* out_pcd, int64_t* out_class,
+                   ct_stream_t s);
 
 #ifdef __cplusplus
 }
