@@ -22,7 +22,7 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 
 HIP_SOURCES = ["ct_raster.hip", "ct_mhct.hip", "ct_lattice.hip", "ct_gconv.hip", "ct_chamfer.hip", "ct_emd.hip",
                "ct_adain.hip", "ct_bnorm.hip", "ct_pwgemm.hip", "ct_nbr.hip", "ct_kpitems.hip", "ct_completion.hip", "ct_scanitems.hip",
-               "ct_blockitems.hip", "ct_kpplan.hip", "ct_imageitems.hip"]
+               "ct_blockitems.hip", "ct_kpplan.hip", "ct_imageitems.hip", "ct_voxel.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared",
                # index/weight math must round exactly like the reference's fp32 op sequence
                "-ffp-contract=off"]
@@ -94,6 +94,8 @@ IMAGE_SIZE_MAX = 4096      # ct_image_items: source height, output height and wi
 IMAGE_STAGE_BYTES = 36 * 1024   # ct_image_items: LDS for one band's horizontally resampled rows
 IMAGE_P_MAX = 1 << 16      # ct_image_items: points of one stored cloud
 IMAGE_N_MAX = 1 << 20      # ct_image_items: slots of one output cloud
+VOXEL_GRID_BYTES = 40      # ct_voxel_keys: the grid record (f32 origin[3], i32 status, i64 nx, ny, nz)
+VOXEL_MAX_CELLS = 1 << 62  # ct_voxel_keys: cells of the grid, exclusive
 
 _lock = threading.Lock()
 _lib = None
@@ -323,6 +325,11 @@ SIGNATURES = {
     "ct_seg_confusion": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "ct_image_items": (_i, [_vp, ctypes.c_int64, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _fp, _fp, _vp, _vp, _vp, _i, _vp, _vp, _vp,
                             _i, _i, _vp, _vp, _vp, _vp]),
+    "ct_voxel_bounds_workspace_bytes": (_sz, [ctypes.c_int64]),
+    "ct_voxel_bounds": (_i, [_vp, ctypes.c_int64, _vp, _vp, _sz, _vp]),
+    "ct_voxel_keys": (_i, [_vp, ctypes.c_int64, _f, _vp, _vp, _vp, _vp]),
+    "ct_voxel_reduce_workspace_bytes": (_sz, [ctypes.c_int64]),
+    "ct_voxel_reduce": (_i, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

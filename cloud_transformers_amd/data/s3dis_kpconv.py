@@ -2,7 +2,8 @@
 datasets/s3dis_closer_utils.py:252-333) with its neighbour work on the GPU (cloud_transformers_amd.neighbors.GridIndex).
 
 - `load_areas`: the Stanford3dDataset_v1.2 text layout -> one cloud per Area, grid-subsampled on the host
-  (data.subsampling.grid_subsampling), cached as .npz arrays (s3dis_closer.py:132-201).
+  (data.subsampling.grid_subsampling) or, given a device, there (grid_subsampling_device: the same arrays), cached as
+  .npz arrays (s3dis_closer.py:132-201).
 - `SphereSampler`: the potential-field sphere picking and the item layout of S3DISSeg (s3dis_closer.py:239-276,302-361),
   batched, on the device (`plan` picks, `items` assembles them in one `ct_kp_items` launch, optionally augmented by
   `Augment`: the training transforms of s3dis_closer_utils.py:38-149).  Same semantics, not the reference's numpy random stream.
@@ -18,7 +19,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from .subsampling import grid_subsampling
+from .subsampling import grid_subsampling, grid_subsampling_device
 
 LABEL_TO_NAMES = {0: "ceiling", 1: "floor", 2: "wall", 3: "beam", 4: "column", 5: "window", 6: "door", 7: "chair", 8: "table",
                   9: "bookcase", 10: "sofa", 11: "board", 12: "clutter"}
@@ -76,9 +77,19 @@ def _read_area(folder):
     return np.concatenate(pts), np.concatenate(cols), np.concatenate(labs)
 
 
-def load_areas(data_root, areas, sampleDl=0.04, cache_dir=None):
+def _subsample_area(points, colors, labels, sampleDl, device):
+    """The Area's grid subsampling: on `device` when one is given (the raw cloud is uploaded whole; one that does not
+    fit raises), unless CLOUDCT_GRID_SUBSAMPLE=host; on the host otherwise.  The same arrays either way."""
+    if device is None or os.environ.get("CLOUDCT_GRID_SUBSAMPLE", "device") == "host":
+        return grid_subsampling(points, features=colors, labels=labels[:, None], sampleDl=sampleDl)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)      # noqa: E731
+    return tuple(t.cpu().numpy() for t in grid_subsampling_device(up(points), up(colors), up(labels[:, None]), sampleDl=sampleDl))
+
+
+def load_areas(data_root, areas, sampleDl=0.04, cache_dir=None, device=None):
     """Areas (names 'Area_k' or numbers k) of `data_root` — the Stanford3dDataset_v1.2 folder or its parent — as `Area`s.
-    With `cache_dir`, each Area's arrays are kept in <cache_dir>/<Area>_<sampleDl:.3f>.npz and read back from there."""
+    With `cache_dir`, each Area's arrays are kept in <cache_dir>/<Area>_<sampleDl:.3f>.npz and read back from there.
+    With a HIP `device`, the subsampling runs there (`_subsample_area`); arrays and cache files do not depend on it."""
     root = data_root
     if os.path.isdir(os.path.join(data_root, "Stanford3dDataset_v1.2")):
         root = os.path.join(data_root, "Stanford3dDataset_v1.2")
@@ -92,7 +103,7 @@ def load_areas(data_root, areas, sampleDl=0.04, cache_dir=None):
             continue
         points, colors, labels = _read_area(os.path.join(root, name))
         if sampleDl > 0:
-            sub_points, sub_colors, sub_labels = grid_subsampling(points, features=colors, labels=labels[:, None], sampleDl=sampleDl)
+            sub_points, sub_colors, sub_labels = _subsample_area(points, colors, labels, sampleDl, device)
             sub_colors = sub_colors / np.float32(255.0)
             sub_labels = np.squeeze(sub_labels, axis=1)
         else:

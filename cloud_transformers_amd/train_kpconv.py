@@ -37,13 +37,13 @@ def kpconv_config(cfg):
     return cfg
 
 
-def load_kpconv_areas(cfg, train=True):
+def load_kpconv_areas(cfg, train=True, device=None):
     """(train Areas or None, validation Areas) of `data.path`: `data.test_area` validates, the other Areas 1-6 train;
-    subsampled at `data.sampleDl` and cached under <data.path>/processed."""
+    subsampled at `data.sampleDl` (on `device` when one is given: the same arrays) and cached under <data.path>/processed."""
     from .data.s3dis_kpconv import load_areas
     data = kpconv_config(cfg)["data"]
     test = str(data["test_area"])
-    kw = dict(sampleDl=float(data["sampleDl"]), cache_dir=os.path.join(str(data["path"]), "processed"))
+    kw = dict(sampleDl=float(data["sampleDl"]), cache_dir=os.path.join(str(data["path"]), "processed"), device=device)
     val = load_areas(data["path"], [test], **kw)
     return (load_areas(data["path"], [a for a in ALL_AREAS if a != test], **kw) if train else None), val
 
@@ -175,7 +175,7 @@ def main(argv=None):
                                 device_id=torch.device("cuda", local))
     try:
         cfg = kpconv_config(harness.load_config(args.config))
-        areas = load_kpconv_areas(cfg, train=not args.eval)
+        areas = load_kpconv_areas(cfg, train=not args.eval, device=torch.device("cuda", torch.cuda.current_device()))
         tr = harness.Trainer(cfg, "segmentation_kpconv", int(cfg["data"]["num_classes"]), dist=dist, exp_name=args.exp_name,
                              dataset=areas)
         if args.eval:

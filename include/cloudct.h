@@ -39,7 +39,8 @@ extern "C" {
  * the four exchange phases ct_bn_group_{stats,apply}_fwd / {reduce,apply}_bwd take the whole table plus the run of items to launch.
  * (ct_scan_items was added under version 3 without a bump: an additive symbol, which the loader's missing-symbol scan checks;
  * ct_block_items and ct_seg_confusion the same way; then the index table ct_nbr_table_bytes / ct_nbr_table_set /
- * ct_nbr_radius_multi and the device plan ct_kp_plan / ct_kp_plan_workspace_bytes; then ct_image_items.) */
+ * ct_nbr_radius_multi and the device plan ct_kp_plan / ct_kp_plan_workspace_bytes; then ct_image_items; then the voxel-grid
+ * subsampling ct_voxel_bounds / ct_voxel_keys / ct_voxel_reduce and their workspace queries.) */
 #define CT_ABI_VERSION 3
 
 /* status codes */
@@ -869,6 +870,54 @@ int ct_image_items(const uint8_t* images, int64_t M, int H, int W, int OH, int O
                    const float* points, const int64_t* offsets, const int64_t* class_id, int p_cap, const int64_t* item,
                    const int64_t* perm, const float* u_dup, int B, int n, float* out_img, float* out_pcd, int64_t* out_class,
                    ct_stream_t s);
+
+/* ------------------------------------------------------------------------
+ * Barycentre voxel-grid subsampling of KPConv on the device
+ * (cpp_wrappers/cpp_subsampling/grid_subsampling/grid_subsampling.cpp:4-104, called by
+ * datasets/s3dis_closer.py:13-31): the twin of ct_grid_subsample (cloudct_host.h), with the same
+ * rows in the same order with the same bits.  Added under CT_ABI_VERSION 3 (additive, as
+ * ct_image_items).  Neither call allocates or synchronises; both run on the stream s.
+ *
+ * ct_voxel_bounds: points f32[N,3] (device, 1 <= N < 2^31) -> bounds f32[6] (device): the per-axis
+ * minimum lo[3] then maximum hi[3]; a NaN anywhere makes all six NaN.  Two launches (partial bounds
+ * of up to 1024 workgroups, then their fold).  Workspace: ct_voxel_bounds_workspace_bytes(N) (host
+ * arithmetic; 0 = bad N), 4-byte aligned; null, misaligned or too small -> CT_EWORKSPACE.
+ *
+ * ct_voxel_keys: points as above, dl > 0 and finite, bounds f32[6] (device) as ct_voxel_bounds
+ * writes them (any exact reduction will do; a NaN point must give a NaN bound).  All fp32, one rounding per operation, true divisions, no contraction:
+ *   inv = 1 / dl (on the host); org[a] = floor(lo[a] * inv) * dl; n[a] = floor((hi[a] - org[a]) / dl) + 1;
+ *   i[a] = floor((p[a] - org[a]) / dl); key = ix + nx * iy + nx * ny * iz in 64 bits.
+ * Outputs (device): grid, 40 bytes, 8-byte aligned, read by the host in one copy:
+ *   f32 origin[3]; i32 status (0, or 1: a bound is not finite); i64 nx, ny, nz (each cut to 2^62 + 1:
+ *   the caller refuses nx * ny * nz >= 2^62, below which no key wraps);
+ * keys i64[N] = key ^ 2^63: signed ascending order of these IS unsigned ascending order of the
+ * keys, the order of the host file's size_t keys — also for a point one rounding below the
+ * origin (floor(lo * inv) may round up), whose index -1 wraps there and here alike.
+ *
+ * ct_voxel_reduce: keys_sorted i64[N] and order i64[N], the STABLE ascending sort of keys and its
+ * permutation; points as above, features f32[N,fdim] and classes i32[N,ldim] (null when the dim
+ * is 0).  Each run of equal keys is one output row, rows in ascending key order:
+ *   out_points f32[.,3] = sum * (float)(1.0 / (double)count), out_features f32[.,fdim] =
+ *   sum / (float)count, each sum from 0.0f over the run's points IN INPUT ORDER (the loads may
+ *   come in any order; the additions of one (row, column) do not), out_classes i32[.,ldim] = the
+ *   per-column maximum; inverse i64[N] (nullable) = each input point's row; counts i64[.]
+ *   (nullable) = points per row; M i64[1] (device, 8-byte aligned) = the number of rows.
+ * The row arrays are sized for N rows; rows past M are not written.  order entries are clamped to
+ * [0, N - 1] as a guard; a permutation never needs it.
+ * Workspace: ct_voxel_reduce_workspace_bytes(N) (host arithmetic; 0 = bad N), 4-byte aligned,
+ * contents irrelevant on entry; null or too small -> CT_EWORKSPACE.  Null pointers, N outside
+ * [1, 2^31), negative dims, dl <= 0 -> CT_EINVAL before anything touches the device.
+ * Launches: two scan kernels and a row kernel over N, then one wave per run (a fixed grid of
+ * one-wave workgroups looping over rows; a run is never split, so the longest run bounds the time).
+ * ---------------------------------------------------------------------- */
+size_t ct_voxel_bounds_workspace_bytes(int64_t N);
+int ct_voxel_bounds(const float* points, int64_t N, float* bounds, void* workspace, size_t workspace_bytes, ct_stream_t s);
+int ct_voxel_keys(const float* points, int64_t N, float dl, const float* bounds, void* grid, int64_t* keys, ct_stream_t s);
+size_t ct_voxel_reduce_workspace_bytes(int64_t N);
+int ct_voxel_reduce(const int64_t* keys_sorted, const int64_t* order, const float* points, const float* features,
+                    const int32_t* classes, int64_t N, int fdim, int ldim, float* out_points, float* out_features,
+                    int32_t* out_classes, int64_t* inverse, int64_t* counts, int64_t* M, void* workspace, size_t workspace_bytes,
+                    ct_stream_t s);
 
 #ifdef __cplusplus
 }

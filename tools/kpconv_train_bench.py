@@ -4,6 +4,8 @@ room, grid-subsampled at 0.04):
     python tools/kpconv_train_bench.py [--points 1000000] [--iters 20] [--step-iters 10] [--no-step]
 
 Rows:
+- the raw cloud's grid subsampling through the host library and on the device, whole and in parts (`subsample_*`:
+  tools/kpconv_data_bench.py `subsample_rows`);
 - the batch assembly of 6 items at N = 8192 from the same ball query results: the torch sequence SphereSampler.sample used
   before ct_kp_items (restated here; with augmentation, the rotation, scale and jitter added in torch) against one
   ct_kp_items launch, without and with augmentation (the slot keys' argsort is in both);
@@ -127,7 +129,7 @@ def main():
     ap.add_argument("--step-iters", type=int, default=10)
     ap.add_argument("--no-step", action="store_true", help="skip the training-step rows")
     args = ap.parse_args()
-    from kpconv_data_bench import area_like, gpu_ms
+    from kpconv_data_bench import area_like, gpu_ms, subsample_rows
     from cloud_transformers_amd.data.s3dis_kpconv import Area, Augment, SphereSampler
     from cloud_transformers_amd.data.subsampling import grid_subsampling
 
@@ -140,6 +142,7 @@ def main():
     sp, sc, sl = grid_subsampling(raw, features=cols, labels=labs[:, None], sampleDl=0.04)
     area = Area("Area_bench", raw, cols, labs, sp, sc / np.float32(255), sl[:, 0])
     res = {"sub_points": int(sp.shape[0]), "B": 6, "N": 8192}
+    res.update(subsample_rows(raw, cols, labs, 0.04, max(2, args.iters // 4)))      # the raw cloud through both subsampling paths
     gen = torch.Generator(device="cuda").manual_seed(0)
     smp = SphereSampler([area], 8192, in_radius=2.0, input_features_dim=4, generator=gen)
 
