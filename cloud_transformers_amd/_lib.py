@@ -85,6 +85,8 @@ NBR_MAX_CELLS = 1 << 26    # ct_nbr_* grids
 KP_PLAN_CLOUDS_MAX = 65535 # ct_kp_plan: clouds of one index table
 COMPLETION_N_MAX = 16384   # ct_completion_items: rows of one partial cloud
 COMPLETION_GT_MAX = 1 << 24
+GATHER_CAP_MAX = 1 << 16   # ct_completion_gather: points of one stored cloud (p_cap, g_cap)
+GATHER_OUT_MAX = 1 << 16   # ct_completion_gather: slots of one gt cloud (n_out); n_in is within COMPLETION_N_MAX
 SCAN_P_MAX = 16384         # ct_scan_items: points of one stored cloud
 BLOCK_P_MAX = 16384        # ct_block_items: points of one stored block
 CONFUSION_C_MAX = 64       # ct_seg_confusion: classes
@@ -320,6 +322,7 @@ SIGNATURES = {
     "ct_kp_plan": (_i, [_vp, _i, ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_double, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ct_kp_items": (_i, [_vp] * 10 + [ctypes.c_int64, _fp, _fp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ct_completion_items": (_i, [_vp, _vp, _vp, _vp, _f, _i, _i, ctypes.c_int64, _vp, _vp, _vp, _vp]),
+    "ct_completion_gather": (_i, [_vp, _vp, _vp, _vp, ctypes.c_int64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp, _vp]),
     "ct_scan_items": (_i, [_vp, _vp, _vp, ctypes.c_int64, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _vp, _vp, _vp]),
     "ct_block_items": (_i, [_vp, _vp, ctypes.c_int64, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _i, _vp, _vp, _vp]),
     "ct_seg_confusion": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),

@@ -9,8 +9,17 @@ train_inpainter.py:175-185): the loader on the host, the per-batch preparation o
   the draws; nothing is read back to the host, `count` stays on the device.
 - `partial_postproces`: the reference's name, signature and return layout on top of it.
 - `CompletionBatches`: a DataLoader over such a dataset -> the device triples `harness.Trainer`'s `completion` loss takes.
+- `decode_split`, `DeviceShapeNetCompletion`: every file of a subset read once (an `.npz` cache keyed by paths, sizes and
+  mtimes), the clouds concatenated and uploaded once.
+- `completion_gather_from_draws`: the raw `ct_completion_gather` launch (include/cloudct.h) on explicit draws: the rendering
+  choice, both RandomSamplePoints, RandomMirrorPoints and the collate of B items; a pure function.
+- `completion_gather`: the draws of one batch from one generator on the device, then the launch; no host synchronisation.
+- `DeviceCompletionBatches`: one iteration = one epoch of the same triples as `CompletionBatches`, in the order of torch's
+  own `DistributedSampler`, with no file read and no host-to-device copy of points per step.
 """
+import hashlib
 import json
+import os
 import random
 from enum import Enum, unique
 
@@ -320,4 +329,258 @@ class CompletionBatches(object):
             part, noise, _ = completion_items(data["partial_cloud"].to(self.device, non_blocking=True), gt.shape[1], scale=2.0,
                                               generator=self.generator)
             self.last_ids = (taxonomy_ids, model_ids)
+            yield noise, part, gt
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the split on the device
+def _split_paths(dataset):
+    """Every file of a completion Dataset's file list in storage order: per model its renderings, then its gt cloud."""
+    R = int(dataset.options["n_renderings"])
+    paths = []
+    for sample in dataset.file_list:
+        partial = sample["partial_cloud_path"]
+        partial = list(partial) if isinstance(partial, (list, tuple)) else [partial]
+        if len(partial) != R:
+            raise ValueError("model %s lists %d renderings, the dataset's n_renderings is %d" % (sample["model_id"], len(partial), R))
+        paths.extend(str(p) for p in partial)
+        paths.append(str(sample["gtcloud_path"]))
+    return paths, R
+
+
+def _split_cache_key(dataset):
+    """(file tag, key): the key is a sha1 over the files' relative paths, sizes and mtimes (ns) and the ids, so a touched,
+    resized, added or removed file changes it (as image_point._cache_key); the tag, a sha1 over the paths alone, names the
+    cache file, so a rebuilt subset replaces its own stale file."""
+    paths, R = _split_paths(dataset)
+    root = os.path.commonpath([os.path.dirname(os.path.abspath(p)) for p in paths]) if paths else ""
+    rel = [os.path.relpath(os.path.abspath(p), root) for p in paths]
+    rows = []
+    for p, r in zip(paths, rel):
+        st = os.stat(p)
+        rows.append([r, st.st_size, st.st_mtime_ns])
+    ids = [[str(s["taxonomy_id"]), str(s["model_id"])] for s in dataset.file_list]
+    tag = hashlib.sha1(json.dumps([R, rel]).encode()).hexdigest()[:16]
+    return tag, hashlib.sha1(json.dumps([R, rows, ids]).encode()).hexdigest()
+
+
+def decode_split(dataset, cache_dir=None):
+    """{"partial_points" f32[Pt, 3], "partial_offsets" i64[M * R + 1] (cloud m * R + r is rendering r of model m), "gt_points"
+    f32[Gt, 3], "gt_offsets" i64[M + 1], "taxonomy_ids", "model_ids" (lists), "R", "key", "cached"} of a completion `Dataset`:
+    every file of its `file_list` read once with `read_pcd`.  With `cache_dir` the arrays are kept uncompressed in
+    <cache_dir>/shapenet_completion_<tag>.npz and read back from there while `_split_cache_key` matches."""
+    paths, R = _split_paths(dataset)
+    M = len(dataset.file_list)
+    if M < 1:
+        raise ValueError("the completion dataset lists no models")
+    tag, key = _split_cache_key(dataset)
+    cache = os.path.join(str(cache_dir), "shapenet_completion_%s.npz" % tag) if cache_dir else None
+    if cache and os.path.exists(cache):
+        with np.load(cache, allow_pickle=False) as z:
+            if str(z["key"]) == key:
+                return {"partial_points": z["partial_points"], "partial_offsets": z["partial_offsets"], "gt_points": z["gt_points"],
+                        "gt_offsets": z["gt_offsets"], "taxonomy_ids": z["taxonomy_ids"].tolist(), "model_ids": z["model_ids"].tolist(),
+                        "R": R, "key": key, "cached": True}
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
+        clouds = list(pool.map(read_pcd, paths))
+    partial = [clouds[m * (R + 1) + r] for m in range(M) for r in range(R)]
+    gt = [clouds[m * (R + 1) + R] for m in range(M)]
+    offsets = lambda cs: np.concatenate([[0], np.cumsum([c.shape[0] for c in cs])]).astype(np.int64)      # noqa: E731
+    out = {"partial_points": np.concatenate(partial).astype(np.float32).reshape(-1, 3), "partial_offsets": offsets(partial),
+           "gt_points": np.concatenate(gt).astype(np.float32).reshape(-1, 3), "gt_offsets": offsets(gt),
+           "taxonomy_ids": [s["taxonomy_id"] for s in dataset.file_list], "model_ids": [s["model_id"] for s in dataset.file_list],
+           "R": R, "key": key, "cached": False}
+    if cache:
+        os.makedirs(str(cache_dir), exist_ok=True)
+        tmp = cache + ".%d.tmp.npz" % os.getpid()
+        np.savez(tmp, partial_points=out["partial_points"], partial_offsets=out["partial_offsets"], gt_points=out["gt_points"],
+                 gt_offsets=out["gt_offsets"], taxonomy_ids=np.asarray(out["taxonomy_ids"]), model_ids=np.asarray(out["model_ids"]),
+                 key=np.array(key))
+        os.replace(tmp, cache)
+    return out
+
+
+def _sample_sizes(dataset):
+    """(n_in, n_out or None) of the dataset's Compose chain: the RandomSamplePoints of 'partial_cloud' and of 'gtcloud'."""
+    n_in = n_out = None
+    for transform, objects in getattr(dataset.transforms, "transformers", []):
+        if isinstance(transform, RandomSamplePoints):
+            if "partial_cloud" in objects:
+                n_in = int(transform.n_points)
+            if "gtcloud" in objects:
+                n_out = int(transform.n_points)
+    if n_in is None:
+        raise ValueError("the dataset's transforms hold no RandomSamplePoints of 'partial_cloud': the input size is unknown")
+    return n_in, n_out
+
+
+class DeviceShapeNetCompletion(object):
+    """A completion `Dataset` on `device`, uploaded once, in fp32 as read: `partial_points` f32[Pt, 3] and `partial_offsets`
+    i64[M * R + 1] (cloud m * R + r is rendering r of model m), `gt_points` f32[Gt, 3] and `gt_offsets` i64[M + 1]
+    (`*_offsets_host`: the numpy copies); `M` models of `R` renderings, `p_cap` / `g_cap` the longest partial / gt cloud, `n_in`
+    / `n_out` the rows of a batch's partial / gt clouds (the dataset's RandomSamplePoints), `sampled_gt` False where gt is not
+    resampled (the TEST subset: every gt cloud must then hold `n_out` rows, else ValueError: the device path cannot report a
+    ragged batch without a read-back); `taxonomy_ids`, `model_ids` host lists.  `cache_dir`: see `decode_split`."""
+
+    def __init__(self, dataset, device, cache_dir=None):
+        dec = decode_split(dataset, cache_dir)
+        n_in, n_out = _sample_sizes(dataset)
+        self.dataset, self.from_cache = dataset, bool(dec["cached"])
+        self._upload(dec["partial_points"], dec["partial_offsets"], dec["gt_points"], dec["gt_offsets"], dec["R"], n_in, n_out, device,
+                     n_out is not None, dec["taxonomy_ids"], dec["model_ids"])
+
+    @classmethod
+    def from_arrays(cls, partial_points, partial_offsets, gt_points, gt_offsets, R, n_in, n_out, device, sampled_gt=True,
+                    taxonomy_ids=None, model_ids=None):
+        """The device split of arrays already in memory.  `n_out` may be None when `sampled_gt` is False: the common length."""
+        self = cls.__new__(cls)
+        self.dataset, self.from_cache = None, False
+        self._upload(partial_points, partial_offsets, gt_points, gt_offsets, R, n_in, n_out, device, sampled_gt, taxonomy_ids, model_ids)
+        return self
+
+    def _upload(self, partial_points, partial_offsets, gt_points, gt_offsets, R, n_in, n_out, device, sampled_gt, taxonomy_ids, model_ids):
+        from .. import _lib
+        self.device = torch.device(device)
+        self.R, self.sampled_gt = int(R), bool(sampled_gt)
+        self.partial_offsets_host = np.ascontiguousarray(partial_offsets, dtype=np.int64)
+        self.gt_offsets_host = np.ascontiguousarray(gt_offsets, dtype=np.int64)
+        partial_points = np.ascontiguousarray(partial_points, dtype=np.float32)
+        gt_points = np.ascontiguousarray(gt_points, dtype=np.float32)
+        self.M = M = self.gt_offsets_host.shape[0] - 1
+        if self.R < 1 or M < 1 or self.gt_offsets_host.ndim != 1 or self.partial_offsets_host.shape != (M * self.R + 1,):
+            raise ValueError("gt_offsets are [M + 1], partial_offsets [M * R + 1], M >= 1, R >= 1; got %s and %s with R %d"
+                             % (self.gt_offsets_host.shape, self.partial_offsets_host.shape, self.R))
+        p_len, g_len = np.diff(self.partial_offsets_host), np.diff(self.gt_offsets_host)
+        for name, off, lens, pts in (("partial", self.partial_offsets_host, p_len, partial_points), ("gt", self.gt_offsets_host, g_len, gt_points)):
+            if off[0] != 0 or lens.min() < 1 or tuple(pts.shape) != (int(off[-1]), 3):
+                raise ValueError("%s_offsets start at 0 over clouds of at least one point, %s_points are f32[offsets[-1], 3]" % (name, name))
+        self.p_cap, self.g_cap = int(p_len.max()), int(g_len.max())
+        if not self.sampled_gt:
+            n_out = int(g_len[0]) if n_out is None else int(n_out)
+            if (g_len != n_out).any():
+                k = int(np.flatnonzero(g_len != n_out)[0])
+                raise ValueError("gt is not resampled and model %d holds %d points where %d are expected: a batch of the device "
+                                 "path holds clouds of one length" % (k, int(g_len[k]), n_out))
+        if n_out is None:
+            raise ValueError("n_out is needed where gt is resampled (sampled_gt)")
+        self.n_in, self.n_out = int(n_in), int(n_out)
+        if (max(self.p_cap, self.g_cap) > _lib.GATHER_CAP_MAX or not 1 <= self.n_in <= _lib.COMPLETION_N_MAX
+                or not 1 <= self.n_out <= _lib.GATHER_OUT_MAX):
+            raise ValueError("clouds of at most %d points, n_in within 1 .. %d, n_out within 1 .. %d (ct_completion_gather, "
+                             "include/cloudct.h); got p_cap %d, g_cap %d, n_in %d, n_out %d"
+                             % (_lib.GATHER_CAP_MAX, _lib.COMPLETION_N_MAX, _lib.GATHER_OUT_MAX, self.p_cap, self.g_cap, self.n_in, self.n_out))
+        self.taxonomy_ids = list(taxonomy_ids) if taxonomy_ids is not None else [None] * M
+        self.model_ids = list(model_ids) if model_ids is not None else list(range(M))
+        arrays = (partial_points, self.partial_offsets_host, gt_points, self.gt_offsets_host)
+        self.nbytes = int(sum(a.nbytes for a in arrays))
+        if self.device.type == "cuda":
+            free, total = torch.cuda.mem_get_info(self.device)
+            if self.nbytes > free:
+                raise MemoryError("the resident completion split needs %d bytes (partial %d, gt %d, offsets %d) and %s has %d of %d "
+                                  "bytes free" % (self.nbytes, partial_points.nbytes, gt_points.nbytes,
+                                                  self.partial_offsets_host.nbytes + self.gt_offsets_host.nbytes, self.device, free, total))
+        up = lambda a: torch.from_numpy(a).to(self.device)      # noqa: E731
+        self.partial_points, self.partial_offsets, self.gt_points, self.gt_offsets = (up(a) for a in arrays)
+
+    def __len__(self):
+        return self.M
+
+
+def completion_gather_from_draws(ds, item, rendering, perm_in, perm_gt, u_mirror, gt_scale=2.0):
+    """ct_completion_gather (include/cloudct.h) on explicit draws: item i64[B] (models), rendering i64[B] in [0, R), perm_in
+    i64[B, p_cap] (a permutation of p_cap per row), perm_gt i64[B, g_cap] or None (gt copied in order), u_mirror f32[B] or None
+    (no mirror) -> (partial f32[B, n_in, 3] unscaled, gt f32[B, n_out, 3] times gt_scale).  A pure function of its arguments."""
+    from .. import _lib
+    from ..ops import _dev, _on, _stream
+    given = [t for t in (item, rendering, perm_in, perm_gt, u_mirror) if t is not None]
+    _dev(ds.partial_points, *given)
+    dev = ds.partial_points.device
+    if item.dim() != 1 or item.dtype != torch.int64 or item.shape[0] < 1:
+        raise TypeError("completion_gather: item is int64 [B], B >= 1")
+    B = item.shape[0]
+    if rendering.dtype != torch.int64 or tuple(rendering.shape) != (B,):
+        raise ValueError("completion_gather: rendering is int64 [B] = [%d]; got %s %s" % (B, rendering.dtype, tuple(rendering.shape)))
+    if perm_in.dtype != torch.int64 or tuple(perm_in.shape) != (B, ds.p_cap):
+        raise ValueError("completion_gather: perm_in is int64 [B, p_cap] = [%d, %d]; got %s %s" % (B, ds.p_cap, perm_in.dtype, tuple(perm_in.shape)))
+    if perm_gt is not None and (perm_gt.dtype != torch.int64 or tuple(perm_gt.shape) != (B, ds.g_cap)):
+        raise ValueError("completion_gather: perm_gt is int64 [B, g_cap] = [%d, %d] or None; got %s %s" % (B, ds.g_cap, perm_gt.dtype, tuple(perm_gt.shape)))
+    if u_mirror is not None and (u_mirror.dtype != torch.float32 or tuple(u_mirror.shape) != (B,)):
+        raise ValueError("completion_gather: u_mirror is float32 [B] = [%d] or None; got %s %s" % (B, u_mirror.dtype, tuple(u_mirror.shape)))
+    item, rendering, perm_in = item.contiguous(), rendering.contiguous(), perm_in.contiguous()
+    perm_gt = None if perm_gt is None else perm_gt.contiguous()
+    u_mirror = None if u_mirror is None else u_mirror.contiguous()
+    partial = torch.empty(B, ds.n_in, 3, dtype=torch.float32, device=dev)
+    gt = torch.empty(B, ds.n_out, 3, dtype=torch.float32, device=dev)
+    with _on(dev):
+        _lib.check(_lib.load().ct_completion_gather(
+            ds.partial_points.data_ptr(), ds.partial_offsets.data_ptr(), ds.gt_points.data_ptr(), ds.gt_offsets.data_ptr(), ds.M, ds.R,
+            ds.p_cap, ds.g_cap, item.data_ptr(), rendering.data_ptr(), perm_in.data_ptr(), None if perm_gt is None else perm_gt.data_ptr(),
+            None if u_mirror is None else u_mirror.data_ptr(), float(gt_scale), B, ds.n_in, ds.n_out, partial.data_ptr(), gt.data_ptr(),
+            _stream(dev)), "ct_completion_gather")
+    return partial, gt
+
+
+def completion_gather_draws(ds, B, train, generator=None):
+    """The draws of one batch of B items from `generator` on the split's device, in this order: `rendering` randint(0, R) [B]
+    when training (else zeros: rendering 0), the permutation keys rand(B, p_cap) (their argsort is `perm_in`), the keys
+    rand(B, g_cap) (`perm_gt`; only when `ds.sampled_gt`, else None), `u_mirror` rand(B) (only when training, else None).
+    -> (rendering i64[B], perm_in i64[B, p_cap], perm_gt, u_mirror)."""
+    dev = ds.partial_points.device
+    if train:
+        rendering = torch.randint(0, ds.R, (B,), device=dev, generator=generator)
+    else:
+        rendering = torch.zeros(B, dtype=torch.int64, device=dev)
+    perm_in = torch.argsort(torch.rand(B, ds.p_cap, device=dev, generator=generator), dim=1)
+    perm_gt = torch.argsort(torch.rand(B, ds.g_cap, device=dev, generator=generator), dim=1) if ds.sampled_gt else None
+    u_mirror = torch.rand(B, device=dev, generator=generator) if train else None
+    return rendering, perm_in, perm_gt, u_mirror
+
+
+def completion_gather(ds, item, train, generator=None, gt_scale=2.0):
+    """(partial f32[B, n_in, 3], gt f32[B, n_out, 3]) of the models `item` i64[B] (on the device): what the host `Dataset`'s
+    items give after `collate_fn` — a rendering drawn per item when training, the partial cloud cut to a random n_in rows or
+    padded with zero rows, gt resampled to n_out rows (where the subset resamples it), both mirrored by one draw when training —
+    with gt times `gt_scale`.  The draws are `completion_gather_draws`'.  No host synchronisation."""
+    with torch.no_grad():
+        return completion_gather_from_draws(ds, item, *completion_gather_draws(ds, item.shape[0], train, generator), gt_scale=gt_scale)
+
+
+class DeviceCompletionBatches(object):
+    """One iteration is one epoch of the device triples `CompletionBatches` yields, (noise f32[B, 4, n_out], part f32[B, n_in, 3],
+    gt f32[B, n_out, 3]), of a DeviceShapeNetCompletion: `completion_gather(..., gt_scale=2)` followed by `completion_items(partial,
+    n_out, scale=2)`, both on draws of one device generator seeded by `seed` and the rank (first the gather's, then the items').
+    The epoch's order is `torch.utils.data.distributed.DistributedSampler(range(len(ds)), world, rank, shuffle=train, seed=seed)`
+    after `set_epoch`, uploaded once per epoch; `drop_last` drops a ragged last batch as a DataLoader does.  `last_ids` holds the
+    (taxonomy ids, model ids) of the batch just yielded, from the host's copy of the order."""
+
+    def __init__(self, ds, batch_size, train=False, seed=0, rank=0, world=1, drop_last=False):
+        from torch.utils.data.distributed import DistributedSampler
+        self.ds, self.batch_size, self.train, self.drop_last = ds, int(batch_size), bool(train), bool(drop_last)
+        self.sampler = DistributedSampler(range(len(ds)), num_replicas=int(world), rank=int(rank), shuffle=self.train, seed=int(seed))
+        self.generator = None
+        if ds.device.type == "cuda":
+            self.generator = torch.Generator(device=ds.device).manual_seed(int(seed) * 1000003 + int(rank))
+        self.last_ids = None
+
+    def __len__(self):
+        n = len(self.sampler)
+        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+
+    def set_epoch(self, epoch):
+        self.sampler.set_epoch(int(epoch))
+
+    def epoch_order(self):
+        """The model indices of this rank's epoch, batch after batch (host list)."""
+        order = list(self.sampler)
+        return order[:len(self) * self.batch_size]
+
+    def __iter__(self):
+        host = self.epoch_order()
+        order = torch.tensor(host, dtype=torch.int64).to(self.ds.device, non_blocking=True)
+        for k in range(len(self)):
+            sl = slice(k * self.batch_size, (k + 1) * self.batch_size)
+            partial, gt = completion_gather(self.ds, order[sl], self.train, self.generator, gt_scale=2.0)
+            part, noise, _ = completion_items(partial, self.ds.n_out, scale=2.0, generator=self.generator)
+            self.last_ids = ([self.ds.taxonomy_ids[i] for i in host[sl]], [self.ds.model_ids[i] for i in host[sl]])
             yield noise, part, gt

@@ -18,7 +18,9 @@ package's layers and checkpoints stay interchangeable.
   train_segmentation_kpconv.py).  `shapenet_completion` (the `completion` task; `data.category_path`, `data.partial_path`,
   `data.gt_path`, `data.n_renders`, `data.input_size`, `data.gt_size` as configs/inpainting.yaml has them) reads the
   ShapeNetCompletion .pcd files (data/completion.py) and prepares every batch on the device; one validation per epoch
-  (train_completion.py, train_inpainter.py).  `scanobjectnn_device` (the `classification_scanobjectnn` task; `data.path`,
+  (train_completion.py, train_inpainter.py).  `shapenet_completion_device` (the same keys, optional `data.cache_dir`) reads every
+  file of a subset once, keeps the clouds on the device and gathers, samples and mirrors every batch there in one launch
+  (data/completion.py DeviceCompletionBatches).  `scanobjectnn_device` (the `classification_scanobjectnn` task; `data.path`,
   `data.path_val`, `data.batch_size_val`, optional `data.subsample`) keeps the ScanObjectNN split on the device and gathers
   every batch there (data/scanobjectnn.py), validates every `train.val_step` epochs with the reference's accuracies and keeps
   the `best` / `macc_best` checkpoints (train_classification.py).  `s3dis_device` (the `segmentation_blocks` task; `data.path`,
@@ -195,7 +197,8 @@ class SyntheticClouds(torch.utils.data.Dataset):
 def make_dataset(cfg, task, n_classes, length=64, channels=3, train=True):
     """The dataset `data.kind` of the config names: "synthetic" (default), "scanobjectnn" or "s3dis" (data/datasets.py);
     "s3dis_kpconv" gives the (train, validation) Areas of train_kpconv.load_kpconv_areas (`train=False`: no train Areas);
-    "shapenet_completion" the TRAIN (`train=False`: VAL) subset of data/completion.py's ShapeNetDataLoader;
+    "shapenet_completion" and "shapenet_completion_device" the TRAIN (`train=False`: VAL) subset of data/completion.py's
+    ShapeNetDataLoader (the second leaves its items to the device);
     "scanobjectnn_device" the ScanObjectNN of `data.path` (`train=False`: `data.path_val`) with its items left to the device;
     "s3dis_device" the Indoor3DSemSeg of `data.path` (`train=False`: the blocks of `data.test_area`), its items left to the device;
     "what3d_device" the ImageToPoint of `data.path`, split 'train' (`train=False`: 'val'; `train="test"`: 'test' with
@@ -220,7 +223,7 @@ def make_dataset(cfg, task, n_classes, length=64, channels=3, train=True):
         # (augmentation and subsampling happen on the device: the host object only reads, centres and normalises)
         return D.ScanObjectNN(data["path"] if train else data["path_val"], train=False, subsample=None,
                               center=data.get("center", True), normalize=data.get("normalize", True))
-    if kind == "shapenet_completion":
+    if kind in ("shapenet_completion", "shapenet_completion_device"):
         assert task == "completion", "ShapeNet completion items are (partial cloud, complete cloud): the completion task"
         from .data.completion import DatasetSubset, shapenet_loader
         return shapenet_loader(data).get_dataset(DatasetSubset.TRAIN if train else DatasetSubset.VAL)
@@ -239,8 +242,8 @@ def make_dataset(cfg, task, n_classes, length=64, channels=3, train=True):
         assert task == "segmentation", "S3DIS blocks are (points, labels): the segmentation task"
         return D.Indoor3DSemSeg(data["path"], data["num_points"], train=train, aug=bool(data.get("aug", train)),
                                 test_area=data.get("test_area", "Area_5"), data_precent=float(data.get("data_precent", 1.0)))
-    raise ValueError("data.kind must be synthetic, scanobjectnn, scanobjectnn_device, s3dis, s3dis_device, s3dis_kpconv, shapenet_completion "
-                     "or what3d_device (got %r)" % kind)
+    raise ValueError("data.kind must be synthetic, scanobjectnn, scanobjectnn_device, s3dis, s3dis_device, s3dis_kpconv, shapenet_completion, "
+                     "shapenet_completion_device or what3d_device (got %r)" % kind)
 
 
 class Trainer:
@@ -255,7 +258,9 @@ class Trainer:
     validation every `train.val_step` epochs and after the last, `generator_epoch_{e}.t7` / `g_opt_epoch_{e}.t7` every
     `train.save_each_epoch` epochs; `dataset` may be the (train, validation) Areas — train_kpconv.py).  With `data.kind:
     shapenet_completion` the completion task's batches are prepared on the device (data/completion.py CompletionBatches)
-    and `fit` validates once per epoch (`validate`).  "classification_scanobjectnn" (selected by `data.kind:
+    and `fit` validates once per epoch (`validate`); with `data.kind: shapenet_completion_device` the subset stays on the device
+    and the items are gathered there too (DeviceCompletionBatches; `dataset` may be a completion Dataset or a
+    DeviceShapeNetCompletion).  "classification_scanobjectnn" (selected by `data.kind:
     scanobjectnn_device` too; `dataset` may be a data.datasets.ScanObjectNN or a data.scanobjectnn.DeviceScanObjectNN):
     loss = (1 - seg_weight) * CE(out[0], label) + seg_weight * BCE-with-logits(out[1][:, 0, 0], mask) of train_classification.py:
     201-204 (the model's output is indexed, so the reference's three-output classifier and two-output models both fit),
@@ -341,7 +346,9 @@ class Trainer:
         # `dataset`: any torch Dataset whose items have the task's layout; else what `data.kind` of the config names
         data = dataset if dataset is not None else make_dataset(cfg, task, n_classes, length=dataset_length, channels=channels)
         self.kp, self.clip, self.val_records = None, None, []
-        self.shapenet, self.val_loader, self.best_val = str(cfg["data"].get("kind", "")).lower() == "shapenet_completion", None, None
+        kind = str(cfg["data"].get("kind", "")).lower()
+        self.shapenet_device = kind == "shapenet_completion_device"
+        self.shapenet, self.val_loader, self.best_val = kind == "shapenet_completion" or self.shapenet_device, None, None
         self.scan, self.best_acc, self.best_macc = task == "classification_scanobjectnn", float("-inf"), float("-inf")
         self.blocks, self.train_meter, self.train_records, self._pred = task == "segmentation_blocks", None, [], None
         self._graph_preds = {}
@@ -358,6 +365,10 @@ class Trainer:
         elif self.scan:
             self.sampler = None                          # (ScanBatches holds torch's DistributedSampler itself)
             self.loader = self._scan_batches(data, train=True)
+        elif self.shapenet_device:
+            assert task == "completion", "data.kind shapenet_completion_device is the completion task"
+            self.sampler = None                          # (DeviceCompletionBatches holds torch's DistributedSampler itself)
+            self.loader = self._completion_batches(data, train=True)
         elif self.shapenet:
             from .data.completion import CompletionBatches
             assert task == "completion", "data.kind shapenet_completion is the completion task"
@@ -379,6 +390,16 @@ class Trainer:
                                                       worker_init_fn=worker_init_fn)
         self.ce, self.bce = nn.CrossEntropyLoss(), nn.BCEWithLogitsLoss()
         self.iters = 0
+
+    def _completion_batches(self, data, train):
+        """DeviceCompletionBatches over `data` (a host completion Dataset is read and uploaded first), this rank's shard."""
+        from .data.completion import DeviceCompletionBatches, DeviceShapeNetCompletion
+        d = self.cfg["data"]
+        ds = data if isinstance(data, DeviceShapeNetCompletion) else DeviceShapeNetCompletion(data, self.device, cache_dir=d.get("cache_dir"))
+        active = parallel._active(self.dist)
+        return DeviceCompletionBatches(ds, d["batch_size"] if train else d.get("batch_size_val", d["batch_size"]), train=train,
+                                       seed=int(d.get("seed", 0)) + (0 if train else 7919), rank=self.rank,
+                                       world=self.dist.get_world_size() if active else 1, drop_last=bool(d.get("drop_last", True)) and train)
 
     def _scan_batches(self, data, train):
         """ScanBatches over `data` (a host ScanObjectNN is uploaded first) with the config's sizes, this rank's shard."""
@@ -496,7 +517,10 @@ class Trainer:
         from .data.completion import CompletionBatches
         from .emd import emdModule
         cfg, tr = self.cfg, self.cfg["train"]
-        if self.val_loader is None or dataset is not None:
+        if self.shapenet_device and (self.val_loader is None or dataset is not None):
+            self.val_loader = self._completion_batches(dataset if dataset is not None else make_dataset(cfg, "completion", None, train=False),
+                                                       train=False)
+        elif self.val_loader is None or dataset is not None:
             data = dataset if dataset is not None else make_dataset(cfg, "completion", None, train=False)
             smp = torch.utils.data.distributed.DistributedSampler(data, shuffle=False) if parallel._active(self.dist) else None
             self.val_loader = CompletionBatches(data, cfg["data"].get("batch_size_val", cfg["data"]["batch_size"]), self.device,
@@ -863,7 +887,7 @@ class Trainer:
         for epoch in range(tr["num_epochs"]):
             if self.sampler is not None:
                 self.sampler.set_epoch(epoch)
-            if self.scan or self.blocks or self.recon:
+            if self.scan or self.blocks or self.recon or self.shapenet_device:
                 self.loader.set_epoch(epoch)
             self.model.train()
             end = time.time()

@@ -1,5 +1,6 @@
 """Training and evaluation of the ShapeNet completion protocol (train_inpainter.py, eval_inpainting.py) on the device: the
-`completion` task of `harness.Trainer` on `data.kind: shapenet_completion`.
+`completion` task of `harness.Trainer` on `data.kind: shapenet_completion` or, with the subset kept on the device and the items
+gathered there, `data.kind: shapenet_completion_device` (optional `data.cache_dir` keeps the decoded clouds between runs).
 
     python -m cloud_transformers_amd.train_completion EXP -c configs/inpainting.yaml [--gpus N] [--eval]
 
@@ -36,17 +37,31 @@ def completion_config(cfg):
     return cfg
 
 
-def evaluate(model, cfg, device, exp_dir=None, generator=None, verbose=True):
+def _resident_items(resident, generator):
+    """The TEST subset of a DeviceShapeNetCompletion in batches of one, shaped as the host loader's batches: rendering 0, the
+    partial cloud sampled, gt as stored (data/completion.py completion_gather with gt_scale 1)."""
+    from .data.completion import completion_gather
+    for i in range(len(resident)):
+        item = torch.full((1,), i, dtype=torch.int64, device=resident.device)
+        partial, gt = completion_gather(resident, item, False, generator, gt_scale=1.0)
+        yield [resident.taxonomy_ids[i]], [resident.model_ids[i]], {"partial_cloud": partial, "gtcloud": gt}
+
+
+def evaluate(model, cfg, device, exp_dir=None, generator=None, verbose=True, resident=None):
     """test_net of eval_inpainting.py:132-230 -> {"names": metric names, "taxonomies": {id: {"count", "avg"}}, "overall":
     {"count", "avg"}, "dense_loss": mean dense Chamfer x 1000}; printed as the reference prints it and, with `exp_dir`,
-    written to <exp_dir>/completion_test.json."""
+    written to <exp_dir>/completion_test.json.  `resident`: the TEST subset as a DeviceShapeNetCompletion, read instead of
+    the files."""
     from .data.completion import DatasetSubset, collate_fn, completion_items, shapenet_loader
     from .metrics import AverageMeter, ChamferDistance, Metrics
-    ds = shapenet_loader(cfg["data"]).get_dataset(DatasetSubset.TEST)
-    loader = torch.utils.data.DataLoader(ds, batch_size=1, num_workers=int(cfg["data"].get("num_workers", 0)), collate_fn=collate_fn,
-                                         shuffle=False)
     if generator is None:
         generator = torch.Generator(device=device).manual_seed(int(cfg["data"].get("seed", 0)) * 1000003 + 104729)
+    if resident is not None:
+        loader = _resident_items(resident, generator)
+    else:
+        ds = shapenet_loader(cfg["data"]).get_dataset(DatasetSubset.TEST)
+        loader = torch.utils.data.DataLoader(ds, batch_size=1, num_workers=int(cfg["data"].get("num_workers", 0)), collate_fn=collate_fn,
+                                             shuffle=False)
     was_training = model.training
     model.eval()
     chamfer_dist = ChamferDistance()
@@ -117,7 +132,8 @@ def main(argv=None):
             from .data.completion import DatasetSubset, shapenet_loader
             tr = harness.Trainer(cfg, "completion", n_in, dist=dist, exp_name=args.exp_name,
                                  dataset=shapenet_loader(cfg["data"]).get_dataset(DatasetSubset.TEST))
-            return evaluate(parallel._plain_module(tr.model), cfg, tr.device, exp_dir=tr.exp_dir)
+            resident = tr.loader.ds if tr.shapenet_device else None
+            return evaluate(parallel._plain_module(tr.model), cfg, tr.device, exp_dir=tr.exp_dir, resident=resident)
         tr = harness.Trainer(cfg, "completion", n_in, dist=dist, exp_name=args.exp_name)
         tr.fit()
         return tr.val_records

@@ -40,7 +40,8 @@ extern "C" {
  * (ct_scan_items was added under version 3 without a bump: an additive symbol, which the loader's missing-symbol scan checks;
  * ct_block_items and ct_seg_confusion the same way; then the index table ct_nbr_table_bytes / ct_nbr_table_set /
  * ct_nbr_radius_multi and the device plan ct_kp_plan / ct_kp_plan_workspace_bytes; then ct_image_items; then the voxel-grid
- * subsampling ct_voxel_bounds / ct_voxel_keys / ct_voxel_reduce and their workspace queries.) */
+ * subsampling ct_voxel_bounds / ct_voxel_keys / ct_voxel_reduce and their workspace queries; then the resident ShapeNet
+ * completion gather ct_completion_gather.) */
 #define CT_ABI_VERSION 3
 
 /* status codes */
@@ -730,6 +731,46 @@ int ct_kp_items(const int64_t* qidx, const int64_t* count, const int64_t* perm, 
  * ---------------------------------------------------------------------- */
 int ct_completion_items(const float* partial, const int64_t* perm, const float* u_dup, const float* sphere, float scale,
                         int B, int n_in, int64_t gt, float* part, float* noise, int32_t* count, ct_stream_t s);
+
+/* ------------------------------------------------------------------------
+ * The ShapeNet completion items themselves, gathered from a split that stays on the device
+ * (datasets/grnet_completion.py:371-397 Dataset.__getitem__, :107-135 Compose with :246-258
+ * RandomSamplePoints and :297-314 RandomMirrorPoints, :351-368 collate_fn), one launch, every random
+ * draw passed in.  Added under CT_ABI_VERSION 3 (additive, as ct_image_items).  It does not
+ * allocate, does not synchronise and runs on the stream s.  ct_completion_items takes its
+ * out_partial as it is.
+ *
+ * The split (device): partial_points f32[Pt,3] and partial_offsets i64[M*R+1] (cloud m*R + r is
+ * rendering r of model m, 0 .. p_cap points), gt_points f32[Gt,3] and gt_offsets i64[M+1] (0 ..
+ * g_cap points); M >= 1 models, R >= 1 renderings of each, M * R below 2^63.
+ * A batch is B rows (1 <= B <= 65535): item i64[B] names the model (repeats allowed), m =
+ * clamp(item[b], 0, M-1); rendering i64[B] the rendering, r = clamp(rendering[b], 0, R-1) (the
+ * clamps are guards).  The partial cloud of row b is m*R + r, its gt cloud is m.
+ *
+ * Partial sampling (RandomSamplePoints): perm_in i64[B,p_cap] is a permutation of 0..p_cap-1 per
+ * row (the argsort of plain random keys).  With P the partial cloud's length (cut to p_cap): slot
+ * j < min(n_in, P) of out_partial[b] takes the j-th entry of perm_in[b] that is below P, in order
+ * (the order-preserving compaction of ct_image_items: a uniform permutation of p_cap restricted
+ * this way is a uniform permutation of P, here cut to n_in); slots j >= P are rows of +0.
+ * gt sampling: the same rule with perm_gt i64[B,g_cap], g_cap and n_out into out_gt[b]; with
+ * perm_gt null the first min(n_out, G) rows of the cloud are copied in order, the rest are +0.
+ * Entries of a perm outside 0..length-1 are never followed; when it is not a permutation, slots
+ * below min(n, length) may be left unwritten, nothing is read or written out of bounds.
+ * Mirror (RandomMirrorPoints): u = u_mirror[b] (f32[B]); sx = -1 iff u <= 0.5; sz = -1 iff
+ * u <= 0.25 or 0.5 < u <= 0.75 (a NaN draw mirrors nothing); every gathered row of both clouds
+ * becomes (sx * x, y, sz * z), a sign flip (so a zero coordinate may become -0).  u_mirror null:
+ * no mirror.
+ * Scale: out_gt = gt_scale * (mirrored row), one fp32 multiply (train_inpainter.py:178's 2 *);
+ * out_partial is not scaled.  Outputs: out_partial f32[B,n_in,3], out_gt f32[B,n_out,3].
+ * Limits: 1 <= n_in <= 16384, 1 <= n_out <= 65536, 1 <= p_cap, g_cap <= 65536, gt_scale finite
+ * and non-zero.  Null required pointers and sizes outside the limits -> CT_EINVAL before anything
+ * touches the device.
+ * ---------------------------------------------------------------------- */
+int ct_completion_gather(const float* partial_points, const int64_t* partial_offsets, const float* gt_points,
+                         const int64_t* gt_offsets, int64_t M, int R, int p_cap, int g_cap, const int64_t* item,
+                         const int64_t* rendering, const int64_t* perm_in, const int64_t* perm_gt /* nullable */,
+                         const float* u_mirror /* nullable */, float gt_scale, int B, int n_in, int n_out, float* out_partial,
+                         float* out_gt, ct_stream_t s);
 
 /* ------------------------------------------------------------------------
  * Batch assembly of the ScanObjectNN classification items (datasets/scanobjectnn.py:102-122: jitter,

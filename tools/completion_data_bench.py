@@ -6,11 +6,20 @@ rows, draw the sphere noise, label and concatenate, resample; then stack and cop
 
 Per shape (B 2 and B 32 at n_in 2048, gt 16384): `completion_items` eager (the draws, the argsort and the one launch, from
 device-resident loader output) and replayed from a HIP graph; `ct_completion_items` alone, 20 launches per graph replay, with
-the bytes it has to move per second of that time; the host procedure including its three host-to-device copies."""
+the bytes it has to move per second of that time; the host procedure including its three host-to-device copies.
+
+Then the items themselves (key "resident"), on a synthetic ShapeNetCompletion-like tree of binary .pcd files written to a
+temporary directory (--models models of 8 renderings of 1200 .. 3600 points, gt clouds of 16384) and kept on the device as a
+`DeviceShapeNetCompletion`; per shape, all in this one run: `completion_gather` eager and replayed from a HIP graph;
+`ct_completion_gather` alone, 20 launches per graph replay; a whole `DeviceCompletionBatches` batch (the gather, the items'
+draws and `ct_completion_items`); and the host path for the same batch size: the `Dataset` items (two file reads and the numpy
+transforms each), `collate_fn` and the two host-to-device copies with the `2 *`, in this process without workers, the files
+in the page cache."""
 import argparse
 import json
 import os
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -52,9 +61,105 @@ def host_procedure(partial, gtcloud, dev):
     return noise, enc, gt
 
 
+def write_binary_pcd(path, xyz):
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    n = xyz.shape[0]
+    head = ("# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z\nSIZE 4 4 4\nTYPE F F F\nCOUNT 1 1 1\nWIDTH %d\n"
+            "HEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %d\nDATA binary\n" % (n, n))
+    with open(path, "wb") as f:
+        f.write(head.encode("ascii"))
+        f.write(np.ascontiguousarray(xyz, dtype="<f4").tobytes())
+
+
+def synthetic_tree(root, models, renders, gt_size, seed=0):
+    """A train subset of `models` models in two taxonomies; returns the `data` keys of the reference config for it."""
+    rng = np.random.default_rng(seed)
+    ids = ["m%04d" % k for k in range(models)]
+    cats = [{"taxonomy_id": "02691156", "taxonomy_name": "a", "train": ids[::2], "val": [], "test": []},
+            {"taxonomy_id": "03001627", "taxonomy_name": "b", "train": ids[1::2], "val": [], "test": []}]
+    with open(os.path.join(root, "ShapeNet.json"), "w") as f:
+        json.dump(cats, f)
+    for c in cats:
+        for m in c["train"]:
+            gt = (rng.random((gt_size, 3), dtype=np.float32) - 0.5)
+            write_binary_pcd(os.path.join(root, "train", "complete", c["taxonomy_id"], m + ".pcd"), gt)
+            for r in range(renders):
+                write_binary_pcd(os.path.join(root, "train", "partial", c["taxonomy_id"], m, "%02d.pcd" % r),
+                                 gt[rng.permutation(gt_size)[:int(rng.integers(1200, 3601))]])
+    return {"category_path": os.path.join(root, "ShapeNet.json"), "partial_path": os.path.join(root, "%s", "partial", "%s", "%s", "%02d.pcd"),
+            "gt_path": os.path.join(root, "%s", "complete", "%s", "%s.pcd"), "n_renders": renders, "input_size": 2048, "gt_size": gt_size}
+
+
+def resident_rows(args, dev, n_in, gt):
+    from cloud_transformers_amd.data import completion as C
+    out = {}
+    with tempfile.TemporaryDirectory() as root:
+        host_ds = C.shapenet_loader(synthetic_tree(root, args.models, 8, gt)).get_dataset(C.DatasetSubset.TRAIN)
+        t0 = time.perf_counter()
+        ds = C.DeviceShapeNetCompletion(host_ds, dev)
+        torch.cuda.synchronize()
+        out["split"] = {"models": ds.M, "renderings": ds.R, "p_cap": ds.p_cap, "g_cap": ds.g_cap, "resident_bytes": ds.nbytes,
+                        "decode_and_upload_s": round(time.perf_counter() - t0, 3)}
+        for B in (2, 32):
+            gen = torch.Generator(device=dev).manual_seed(B)
+            item = torch.randint(0, ds.M, (B,), device=dev, generator=gen)
+            row = {}
+            row["completion_gather_eager_ms"] = round(gpu_ms(lambda: C.completion_gather(ds, item, True, gen), args.iters), 4)
+            graph = torch.cuda.CUDAGraph()
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                C.completion_gather(ds, item, True)
+            torch.cuda.current_stream().wait_stream(side)
+            with torch.cuda.graph(graph):
+                outs = C.completion_gather(ds, item, True)
+            row["completion_gather_graph_replay_ms"] = round(gpu_ms(graph.replay, args.iters), 4)
+            assert bool(torch.isfinite(outs[1]).all())
+            draws = C.completion_gather_draws(ds, B, True, gen)
+            reps = 20
+            kgraph = torch.cuda.CUDAGraph()
+            C.completion_gather_from_draws(ds, item, *draws)
+            torch.cuda.synchronize()
+            with torch.cuda.graph(kgraph):
+                for _ in range(reps):
+                    C.completion_gather_from_draws(ds, item, *draws)
+            k_ms = gpu_ms(kgraph.replay, max(args.iters // 4, 10)) / reps
+            moved = B * ((ds.p_cap + ds.g_cap) * 8 + 2 * (n_in + gt) * 12)         # both permutations once, every output row read and written
+            row["kernel_alone_ms"] = round(k_ms, 5)
+            row["kernel_bytes_in_and_out"] = moved
+            row["kernel_GB_per_s"] = round(moved / (k_ms * 1e-3) / 1e9, 1)
+            row["workgroups_per_row"] = min(-(-max(ds.p_cap, n_in) // 1024), 32) + min(-(-max(ds.g_cap, gt) // 1024), 32)
+            batches = C.DeviceCompletionBatches(ds, B, train=True, seed=1)
+            state = {"it": iter(batches), "epoch": 0}
+
+            def device_batch():
+                try:
+                    return next(state["it"])
+                except StopIteration:
+                    state["epoch"] += 1
+                    batches.set_epoch(state["epoch"])
+                    state["it"] = iter(batches)
+                    return next(state["it"])
+
+            row["device_batch_ms"] = round(gpu_ms(device_batch, args.iters), 4)
+            order = np.random.default_rng(B).integers(0, len(host_ds), size=(64, B))
+            step = {"k": 0}
+
+            def host_batch():
+                idx = order[step["k"] % len(order)]
+                step["k"] += 1
+                _, _, data = C.collate_fn([host_ds[int(i)] for i in idx])
+                return 2 * data["gtcloud"].to(dev, non_blocking=True), data["partial_cloud"].to(dev, non_blocking=True)
+
+            row["host_items_collate_copies_ms"] = round(gpu_ms(host_batch, max(args.iters // 10, 5), warmup=2), 3)
+            out["B%d" % B] = row
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--models", type=int, default=64, help="models of the synthetic resident split")
     args = ap.parse_args()
     from cloud_transformers_amd.data.completion import completion_draws, completion_items, completion_items_from_draws
     dev = torch.device("cuda", 0)
@@ -96,6 +201,7 @@ def main():
         host_iters = max(args.iters // 10, 5)
         row["host_procedure_with_copies_ms"] = round(gpu_ms(lambda: host_procedure(partial, gtcloud, dev), host_iters, warmup=2), 3)
         res["B%d" % B] = row
+    res["resident"] = resident_rows(args, dev, n_in, gt)
     print(json.dumps(res))
 
 
