@@ -4,5 +4,6 @@ Python + PyTorch-ROCm host code over hand-written HIP kernels (libcloudct.so,
 C ABI in include/cloudct.h).  No CPU fallback: ops raise on non-HIP tensors.
 """
 from . import _lib  # noqa: F401
+from .determinism import set_deterministic, is_deterministic, deterministic  # noqa: F401
 
-__all__ = ["_lib"]
+__all__ = ["_lib", "set_deterministic", "is_deterministic", "deterministic"]

@@ -67,6 +67,7 @@ class AdainBwdItem(ctypes.Structure):
 ABI_VERSION = 3      # CT_ABI_VERSION of include/cloudct.h
 BN_GROUP_MAX = 8
 CT_OK = 0
+CT_EPRECOND = -4
 REDUCE = {"max": 0, "sum": 1}
 PAD_NONE, PAD_F32, PAD_I32 = 0, 1, 2
 BWD_ACCUMULATE_KEYS = 1
@@ -228,6 +229,9 @@ _fp = ctypes.POINTER(ctypes.c_float)
 SIGNATURES = {
     "ct_abi_version": (_i, []),
     "ct_strerror": (ctypes.c_char_p, [_i]),
+    "ct_set_deterministic": (None, [_i]),
+    "ct_get_deterministic": (_i, []),
+    "ct_deterministic_override": (None, [_i]),
     "ct_positions_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _ip, _vp]),
     "ct_positions_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _ip, _vp]),
     "ct_splat_fwd": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _ip, _i, _vp]),

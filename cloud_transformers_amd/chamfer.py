@@ -14,6 +14,7 @@ from torch import nn
 from torch.autograd import Function
 
 from . import _lib
+from . import determinism as _det
 from .ops import _dev, _ptr, _stream, _on
 
 
@@ -54,6 +55,7 @@ class ChamferWithIndicesFunction(Function):
         gradxyz1 = torch.empty_like(xyz1)
         gradxyz2 = torch.empty_like(xyz2)
         lib = _lib.load()
+        _det.push(lib)          # deterministic mode: the ordered form of the kernel (one wave per destination row)
         with _on(xyz1.device):
             _lib.check(lib.ct_chamfer_bwd(_ptr(xyz1), _ptr(xyz2), _ptr(graddist1), _ptr(graddist2),
                                           _ptr(idx1), _ptr(idx2), _ptr(gradxyz1), _ptr(gradxyz2),

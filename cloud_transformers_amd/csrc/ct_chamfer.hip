@@ -147,6 +147,72 @@ __global__ void nn_grad_kernel(const float* __restrict__ a, const float* __restr
   atomicAdd(&g_b[ib + 2], -dz);
 }
 
+// Deterministic form (ct_set_deterministic): every destination row of cloud `a` is written once, by the lane that owns it.
+//   g_a[i] = 2 g_dist_a[i] (a_i - b_idx_a[i])                                  its own term first,
+//          + sum over j with idx_b[j] == i, ascending j, of -(2 g_dist_b[j] (b_j - a_i))   then its sources in index order
+// — the very terms nn_grad_kernel adds with atomics in arrival order.  A wave owns kDetDst consecutive destinations (lane d
+// keeps the sum of i0 + d) and scans idx_b 64 entries at a time: O(n m / (64 kDetDst)) coalesced integer loads per cloud, no
+// sort.  The matches of a block are added lane by lane, lowest j first, each by the lane of its destination.
+// kDetDst = 8 where that still leaves a few waves per CU (B2 n = m = 16384: 350 -> 112 us against one destination per wave),
+// 1 for a small destination cloud, whose few rows take many sources each and would otherwise queue up in one wave.
+constexpr int kDetWaves = 4;
+template <int kDetDst>
+__global__ void __launch_bounds__(64 * kDetWaves)
+nn_grad_det_kernel(const float* __restrict__ a, const float* __restrict__ bpts, const float* __restrict__ g_dist_a,
+                   const float* __restrict__ g_dist_b, const int* __restrict__ idx_a, const int* __restrict__ idx_b,
+                   float* __restrict__ g_a, int n, int m) {
+  const int b = blockIdx.y;
+  const int lane = threadIdx.x & 63;
+  const int i0 = (blockIdx.x * kDetWaves + (threadIdx.x >> 6)) * kDetDst;      // wave-uniform
+  if (i0 >= n) return;
+  const float* ap = a + (size_t)b * n * 3;
+  const float* bp = bpts + (size_t)b * m * 3;
+  const int* ib = idx_b + (size_t)b * m;
+  const float* gb = g_dist_b + (size_t)b * m;
+  const int i = i0 + lane;
+  const bool own = lane < kDetDst && i < n;
+  float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+  if (own) {
+    const int j = idx_a[(size_t)b * n + i];
+    const float g = g_dist_a[(size_t)b * n + i] * 2.0f;
+    sx = g * (ap[(size_t)i * 3 + 0] - bp[(size_t)j * 3 + 0]);
+    sy = g * (ap[(size_t)i * 3 + 1] - bp[(size_t)j * 3 + 1]);
+    sz = g * (ap[(size_t)i * 3 + 2] - bp[(size_t)j * 3 + 2]);
+  }
+  for (int j0 = 0; j0 < m; j0 += 64) {
+    const int j = j0 + lane;
+    const int d = (j < m ? ib[j] : -1) - i0;          // which of the wave's destinations this source feeds, if any
+    const bool hit = j < m && d >= 0 && d < kDetDst;  // (idx_b < n: i0 + d is a row of the cloud)
+    unsigned long long mask = __ballot(hit);
+    if (mask == 0ull) continue;
+    float tx = 0.0f, ty = 0.0f, tz = 0.0f;
+    if (hit) {
+      const float g = gb[j] * 2.0f;
+      const size_t ia = (size_t)(i0 + d) * 3;
+      tx = -(g * (bp[(size_t)j * 3 + 0] - ap[ia + 0]));
+      ty = -(g * (bp[(size_t)j * 3 + 1] - ap[ia + 1]));
+      tz = -(g * (bp[(size_t)j * 3 + 2] - ap[ia + 2]));
+    }
+    while (mask) {
+      const int l = __ffsll((long long)mask) - 1;
+      mask &= mask - 1;
+      const int dd = __shfl(d, l);
+      const float vx = __shfl(tx, l), vy = __shfl(ty, l), vz = __shfl(tz, l);
+      if (lane == dd) {
+        sx += vx;
+        sy += vy;
+        sz += vz;
+      }
+    }
+  }
+  if (own) {
+    const size_t ia = ((size_t)b * n + i) * 3;
+    g_a[ia + 0] = sx;
+    g_a[ia + 1] = sy;
+    g_a[ia + 2] = sz;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -174,6 +240,23 @@ int ct_chamfer_bwd(const float* xyz1, const float* xyz2, const float* g_dist1, c
   if (!xyz1 || !xyz2 || !g_dist1 || !g_dist2 || !idx1 || !idx2 || !g_xyz1 || !g_xyz2 || B <= 0 || n <= 0 || m <= 0 || B > 65535)
     return CT_EINVAL;
   hipStream_t st = (hipStream_t)s;
+  if (ct_get_deterministic()) {      // ordered form: every row written once by the lane that owns it, nothing to clear
+    CT_CLEAR_ERROR();
+    auto launch = [&](const float* a, const float* b, const float* ga, const float* gb, const int32_t* ia, const int32_t* ib,
+                      float* out, int na, int nb) {
+      if ((long long)B * na >= 8 * 1024) {        // >= 1024 waves of eight rows
+        constexpr int per = kDetWaves * 8;        // destination rows per workgroup
+        hipLaunchKernelGGL(nn_grad_det_kernel<8>, dim3((na + per - 1) / per, B), dim3(64 * kDetWaves), 0, st, a, b, ga, gb, ia, ib, out, na, nb);
+      } else {
+        hipLaunchKernelGGL(nn_grad_det_kernel<1>, dim3((na + kDetWaves - 1) / kDetWaves, B), dim3(64 * kDetWaves), 0, st, a, b, ga, gb, ia, ib,
+                           out, na, nb);
+      }
+    };
+    launch(xyz1, xyz2, g_dist1, g_dist2, idx1, idx2, g_xyz1, n, m);
+    launch(xyz2, xyz1, g_dist2, g_dist1, idx2, idx1, g_xyz2, m, n);
+    CT_CHECK_LAUNCH();
+    return CT_OK;
+  }
   if (hipMemsetAsync(g_xyz1, 0, (size_t)B * n * 3 * 4, st) != hipSuccess) return CT_ELAUNCH;
   if (hipMemsetAsync(g_xyz2, 0, (size_t)B * m * 3 * 4, st) != hipSuccess) return CT_ELAUNCH;
   CT_CLEAR_ERROR();

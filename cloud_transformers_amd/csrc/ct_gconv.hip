@@ -2229,6 +2229,7 @@ int launch_wrw_ring(GconvArgs a, int dim, const float* g_y, float* g_w, float* g
   WrwRingPlan p;
   if (!plan_wrw_ring(a, dim, p)) return CT_EINVAL;
   if (ws && ws_bytes < wrw_ring_workspace(a, p)) return CT_EWORKSPACE;
+  if (!ws && ct_get_deterministic()) return CT_EPRECOND;      // deterministic mode: the atomic form needs the caller's consent
   note(ws ? "wrw_ring_ws" : "wrw_ring_atomics");
   if (ws) note("wrw_reduce");
   if (!ws && hipMemsetAsync(g_w, 0, (size_t)a.groups * a.Cout * a.Cin * a.taps * 4, st) != hipSuccess) return CT_ELAUNCH;
@@ -2321,6 +2322,7 @@ int launch_wrw_tiles(GconvArgs a, int dim, const float* g_y, float* g_w, hipStre
   const size_t red_bytes = (size_t)(kThreads / 64) * 3 * 256 * 4;
   if (!plan_tiles(a, dim, (size_t)16 * 4, 1024 + red_bytes, 16, /*plane == 4 (mod 32): 16-byte aligned for the DMA*/ 4,
                   kLdsBudgetWrw)) return CT_EINVAL;       // (before anything is written: a refused call leaves g_w as it was)
+  if (ct_get_deterministic()) return CT_EPRECOND;         // float atomics only: refused in deterministic mode (include/cloudct.h)
   note("wrw_tiles");
   if (hipMemsetAsync(g_w, 0, (size_t)groups * a.Cout * a.Cin * a.taps * 4, st) != hipSuccess) return CT_ELAUNCH;
   const int gstride_max = ((a.TD * a.TH * a.W + 3) & ~3) | 1;

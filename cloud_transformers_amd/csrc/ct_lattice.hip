@@ -521,6 +521,7 @@ static int lattice_bwd_impl(const float* xyz, const float* residual, const float
   if ((scales != nullptr) != (g_scales != nullptr) || (kscale != nullptr) != (g_kscale != nullptr)) return CT_EINVAL;
   hipStream_t st = (hipStream_t)s;
   if (workspace && workspace_bytes < ct_lattice_bwd_workspace_bytes(B, H, N)) return CT_EWORKSPACE;
+  if (!workspace && ct_get_deterministic()) return CT_EPRECOND;      // the parameter sums would go through float atomics
   float* parts = (float*)workspace;
   const int nbx = (N + 256 * kBwdPts - 1) / (256 * kBwdPts);
   CT_CLEAR_ERROR();

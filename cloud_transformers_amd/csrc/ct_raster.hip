@@ -1293,6 +1293,9 @@ __global__ void zero_slots_kernel(float* tiles, size_t stride, size_t rows) {
 // ---------------------------------------------------------------------------
 std::atomic<unsigned> t_dbg_flags{0};
 std::atomic<int> t_dbg_nseg{0};          // ct_debug_set_nseg: point segments of the hot Splat(max) backward (0: automatic)
+std::atomic<int> t_deterministic{0};     // ct_set_deterministic: read by every translation unit through ct_get_deterministic()
+thread_local int t_det_override = -1;    // ct_deterministic_override: 0 / 1 for the calling thread's entry points, -1 none
+inline bool det_now() { return t_det_override >= 0 ? t_det_override != 0 : t_deterministic.load(std::memory_order_relaxed) != 0; }
 std::mutex t_last_mu;
 char t_last[256] = "";
 
@@ -1306,6 +1309,7 @@ struct Switches {
   int nseg;            // point segments of the hot Splat(max) backward: ct_debug_set_nseg, else CLOUDCT_SPLAT_BWD_NSEG (0: automatic)
   int sorted;          // CLOUDCT_SORTED (-1: not set; 0 turns the sorted forms off)
   bool wide;           // CLOUDCT_WIDE (0 turns the WIDE launches off)
+  bool det;            // ct_set_deterministic: Splat(max) backward under the lowest-index rule, ordered g_keys
   bool has(unsigned f) const { return (flags & f) != 0; }
   bool hot() const { return !has(CT_DEBUG_NO_HOT); }
 };
@@ -1316,7 +1320,8 @@ Switches read_switches() {
   };
   static const int sorted = env("CLOUDCT_SORTED", -1), wide = env("CLOUDCT_WIDE", 1), nseg = env("CLOUDCT_SPLAT_BWD_NSEG", 0);
   const int dbg = t_dbg_nseg.load(std::memory_order_relaxed);
-  return {t_dbg_flags.load(std::memory_order_relaxed), dbg ? dbg : nseg, sorted, wide != 0};
+  return {t_dbg_flags.load(std::memory_order_relaxed), dbg ? dbg : nseg, sorted, wide != 0,
+          det_now()};
 }
 
 // ---------------------------------------------------------------------------
@@ -1514,6 +1519,9 @@ int run_scatter(const Switches sw, RasterArgs a, const int* W, bool sum, hipStre
       }
     }
   } else {
+    // a scatter-ADD here is global float atomics in arrival order (the max form's atomic max does not depend on the order):
+    // no ordered form, refused in deterministic mode (include/cloudct.h) before anything is written
+    if (sum && sw.det) return CT_EPRECOND;
     if (hipMemsetAsync(a.tile_out, 0, (size_t)a.B * a.H * a.C * g.G * 4, st) != hipSuccess) return CT_ELAUNCH;
     if (sum) CT_LAUNCH((scatter_kernel<DIM, FROM_KEYS, true, false>), grid, p.threads, 0, st, a, g);
     else CT_LAUNCH((scatter_kernel<DIM, FROM_KEYS, false, false>), grid, p.threads, 0, st, a, g);
@@ -2357,7 +2365,9 @@ int run_gather_gw(RasterArgs a, const int* W, hipStream_t st) {
   a.nchunks = p.nchunks;
   a.nsplit = pick_nsplit(a.B, a.H, 1, a.N);
   a.ncg = 1;
-  while ((long long)a.B * a.H * a.nsplit * a.ncg < 512 && a.ncg * 2 <= p.nchunks) a.ncg *= 2;
+  // deterministic mode (ct_set_deterministic): no chunk groups — a thread adds the chunks of its own points in order, never atomic_gpos
+  const bool det = det_now();
+  while (!det && (long long)a.B * a.H * a.nsplit * a.ncg < 512 && a.ncg * 2 <= p.nchunks) a.ncg *= 2;
   a.atomic_gpos = a.ncg > 1;
   if (a.atomic_gpos && hipMemsetAsync(a.g_pos, 0, gpos_bytes<DIM, FROM_KEYS>(a), st) != hipSuccess) return CT_ELAUNCH;
   int threads = round_threads((a.N + a.nsplit - 1) / a.nsplit);
@@ -2420,9 +2430,21 @@ int launch_splat_max_bwd(RasterArgs a, const GridW<DIM>& g, const Plan& p, bool 
   return CT_OK;
 }
 
+#include "ct_raster_det.h"
+
 template <int DIM, bool FROM_KEYS>
 int run_splat_max_bwd(const Switches sw, RasterArgs a, const int* W, void* ws, size_t ws_bytes, hipStream_t st) {
   GridW<DIM> g = make_grid<DIM>(W);
+  if (sw.det) {
+    // one rule on every shape: the banded kernels where a test forces them (they follow it already), else the two-phase claim
+    if constexpr (FROM_KEYS) {
+      if (sw.has(CT_DEBUG_FORCE_BAND)) {
+        const int r = run_band_splat_bwd<DIM>(sw, a, g, st);
+        if (r != CT_EINVAL) return r;
+      }
+    }
+    return run_splat_max_bwd_det<DIM, FROM_KEYS>(a, g, ws, ws_bytes, st);
+  }
   if constexpr (FROM_KEYS) {
     if (sw.has(CT_DEBUG_FORCE_BAND)) {
       const int r = run_band_splat_bwd<DIM>(sw, a, g, st);
@@ -2791,6 +2813,11 @@ static size_t splat_bwd_workspace_generic(int B, int H, int C, int N, int dim, c
 size_t ct_splat_bwd_workspace_bytes(int B, int H, int C, int N, int dim, const int* W, int reduce) {
   if (!valid_common(B, H, C, N, dim, W) || reduce != CT_REDUCE_MAX0) return 0;
   size_t n = splat_bwd_workspace_generic(B, H, C, N, dim, W);
+  if (det_now()) {      // sized by the mode (include/cloudct.h)
+    size_t G = 1;
+    for (int j = 0; j < dim; ++j) G *= W[j];
+    n = std::max(n, splat_bwd_det_plan(B, H, C, N, dim, (int)G).workspace());
+  }
   const size_t hot = dim == 2 ? splat_bwd_hot_workspace(B, H, C, N, make_grid<2>(W)) : splat_bwd_hot_workspace(B, H, C, N, make_grid<3>(W));
   return std::max(n, hot);
 }
@@ -2820,6 +2847,10 @@ int ct_splat_bwd_ex(const float* keys, const float* feat, const void* pad, int p
 }
 
 void ct_debug_set_flags(unsigned flags) { t_dbg_flags = flags; }
+
+void ct_set_deterministic(int on) { t_deterministic.store(on ? 1 : 0, std::memory_order_relaxed); }
+int ct_get_deterministic(void) { return det_now() ? 1 : 0; }
+void ct_deterministic_override(int on) { t_det_override = on < 0 ? -1 : (on ? 1 : 0); }
 
 const char* ct_debug_last_launch(void) {
   static thread_local char copy[256];
@@ -2868,6 +2899,7 @@ int ct_splat_bwd_tk_segments(int B, int H, int C, int N, int dim, const int* W) 
   long long G = 1;
   for (int j = 0; j < dim; ++j) G *= W[j];
   if (!hot_shape_ok(sw, B, H, C, N, (int)G, 0) || (long long)B * H > CT_TICKETS_BYTES / 8) return 1;
+  if (sw.det && !sw.has(CT_DEBUG_FORCE_BAND)) return 1;      // deterministic mode: a plane's points are not segmented
   if (sw.has(CT_DEBUG_FORCE_BAND) && C == 4 && ((G / W[0]) & 3) == 0 && W[0] >= 4) return 2;
   HotPlan sp;
   const int nseg = splat_bwd_segments_plan(sw, B, H, C, N, (int)G, dim, sp);

@@ -5,7 +5,8 @@ package's layers and checkpoints stay interchangeable.
 
 * config: the reference's YAML schema — `experiment.{root,writer_root}`, `data.{batch_size,num_points,...}`,
   `model.generator` (a python file defining `Model`; the remaining `model.*` keys are its kwargs),
-  `train.{optimizer,scheduler,num_epochs,save_each,...}`, optional `restore.{generator,optimizer,new_lr}`.
+  `train.{optimizer,scheduler,num_epochs,save_each,...}`, optional `restore.{generator,optimizer,new_lr}`; `train.deterministic:
+  true` (this package's own key) runs `fit` in deterministic mode (determinism.py): equal seeds, equal gradients.
 * checkpoints: `<exp>/<name>_<epoch_name>_<n>.t7` holding a plain `state_dict()` (train_util.py:74-80); parameter names of
   this package's modules equal the reference's, so released weights load with `strict=True`; `restore_exp_fix` drops the
   `module.` prefix DistributedDataParallel adds (train_util.py:98-117).
@@ -858,7 +859,17 @@ class Trainer:
         torchrun users set it themselves; the price is that a hung collective then hangs the job instead of aborting it.  A capture that
         fails falls back to eager steps on one device and RAISES under DistributedDataParallel — the ranks agree on it first).  Losses stay on the
         device and are read back every `log_each` steps (default `train.log_each`, else 10) in ONE transfer — no host
-        synchronisation per step (the reference reads the loss every step: train_segmentation.py:180-186)."""
+        synchronisation per step (the reference reads the loss every step: train_segmentation.py:180-186).
+
+        `train.deterministic: true` runs the whole fit in deterministic mode (determinism.py: run-to-run equal gradients from
+        the library's kernels, all five tasks); the seeds are set as without it and nothing else changes."""
+        if self.cfg["train"].get("deterministic", False):
+            from . import determinism
+            with determinism.deterministic(True):
+                return self._fit(max_iters, hip_graph, log_each)
+        return self._fit(max_iters, hip_graph, log_each)
+
+    def _fit(self, max_iters, hip_graph, log_each):
         tr = self.cfg["train"]
         use_graph = bool(tr.get("hip_graph", False) if hip_graph is None else hip_graph)
         log_each = int(tr.get("log_each", 10) if log_each is None else log_each)

@@ -14,6 +14,7 @@ import torch
 from torch import nn
 
 from .. import _lib
+from .. import determinism as _det
 from ..ops import _ptr, _stream, _on
 
 
@@ -56,8 +57,14 @@ class GroupedConvFn(torch.autograd.Function):
                 g_b = torch.empty(groups * Cout, device=x.device, dtype=torch.float32) if has_bias else None
                 ws_bytes = lib.ct_gconv_bwd_weight_workspace_bytes(B, groups, Cin, Cout, dim, Wa)
                 ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8) if ws_bytes else None
-                _lib.check(lib.ct_gconv_bwd_weight(_ptr(x), _ptr(g_y), _ptr(g_w), _ptr(g_b), _ptr(ws), ws_bytes,
-                                                   B, groups, Cin, Cout, dim, Wa, _stream()), "ct_gconv_bwd_weight")
+                _det.push(lib)
+                # refused in the mode where only a kernel that sums with float atomics takes the shape: the tile form (rows that
+                # are not a multiple of 4 floats, or rings beyond LDS), or the ring kernel when the query asked for no workspace
+                what = "ct_gconv_bwd_weight (%s -> %s channels per group on %s: only a kernel with float atomics takes this shape)" % (
+                    Cin, Cout, "x".join(str(w) for w in W))
+                rc = _det.call(lib, "ct_gconv_bwd_weight", what, _ptr(x), _ptr(g_y), _ptr(g_w), _ptr(g_b), _ptr(ws), ws_bytes,
+                               B, groups, Cin, Cout, dim, Wa, _stream())
+                _lib.check(rc, "ct_gconv_bwd_weight")
         return g_x, g_w, g_b, None
 
 

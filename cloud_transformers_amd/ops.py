@@ -11,6 +11,7 @@ import os
 import torch
 
 from . import _lib
+from . import determinism as _det
 
 
 def sizes_of(tensor_size, dim):
@@ -337,6 +338,8 @@ class PositionsFn(torch.autograd.Function):
 # ---------------------------------------------------------------------------
 # fused (keys-based) Splat / Slice — the hot path
 # ---------------------------------------------------------------------------
+# what the mode refuses of the raster entry points (include/cloudct.h): the wording of determinism.refuse's message
+_BIG_GRID_ADD = "a scatter-add onto a grid whose single-channel tile exceeds a CU's LDS: global float atomics only"
 RASTER_TICKETS = os.environ.get("CLOUDCT_TICKETS", "1") != "0"      # "0": the two-launch form (A/B, debugging)
 _tickets = {}
 
@@ -384,9 +387,10 @@ class SplatKeysFn(torch.autograd.Function):
         padt, pad_code = _pad_args(pad, B, N)
         grid = torch.empty(B, HC, *W, device=feat.device, dtype=torch.float32)
         lib = _lib.load()
+        _det.push(lib)          # (reduce="sum" onto a grid beyond a CU's LDS has float atomics only: refused in the mode)
         with _on(feat.device):
-            _lib.check(lib.ct_splat_fwd(_ptr(keys), _ptr(feat), _ptr(padt), pad_code, _ptr(grid),
-                                        B, H, C, N, dim, _lib.int_array(W), _lib.REDUCE[reduce], _stream()),
+            _lib.check(_det.call(lib, "ct_splat_fwd", "ct_splat_fwd (%s)" % _BIG_GRID_ADD, _ptr(keys), _ptr(feat), _ptr(padt), pad_code,
+                                 _ptr(grid), B, H, C, N, dim, _lib.int_array(W), _lib.REDUCE[reduce], _stream()),
                        "ct_splat_fwd")
         ctx.save_for_backward(keys, feat, padt, grid if reduce == "max" else None)
         ctx.meta = (W, H, C, reduce, pad_code)
@@ -402,6 +406,7 @@ class SplatKeysFn(torch.autograd.Function):
         g_feat = torch.empty_like(feat)
         g_keys = torch.empty_like(keys)
         lib = _lib.load()
+        _det.push(lib)          # (the query below is sized by the mode)
         Wa = _lib.int_array(W)
         ws_bytes = lib.ct_splat_bwd_workspace_bytes(B, H, C, N, dim, Wa, _lib.REDUCE[reduce])
         ws = torch.empty(ws_bytes, device=feat.device, dtype=torch.uint8) if ws_bytes else None
@@ -443,14 +448,15 @@ class SliceKeysFn(torch.autograd.Function):
         g_grid = torch.empty_like(grid)
         g_keys = torch.empty_like(keys)
         lib = _lib.load()
+        _det.push(lib)          # (off the hot shapes the key cotangents of the chunk groups are summed with atomics outside the mode)
         Wa = _lib.int_array(W)
         ws_bytes = lib.ct_slice_bwd_workspace_bytes(B, H, C, N, dim, Wa)
         ws = torch.empty(ws_bytes, device=grid.device, dtype=torch.uint8) if ws_bytes else None
         tk = raster_tickets(grid.device)
         with _on(grid.device):
-            _lib.check(lib.ct_slice_bwd_tk(_ptr(keys), _ptr(grid), _ptr(padt), pad_code, _ptr(g_out),
-                                           _ptr(g_grid), _ptr(g_keys), _ptr(ws), ws_bytes, _ptr(tk),
-                                           B, H, C, N, dim, Wa, _stream()),
+            _lib.check(_det.call(lib, "ct_slice_bwd_tk", "ct_slice_bwd_tk (%s)" % _BIG_GRID_ADD, _ptr(keys), _ptr(grid), _ptr(padt), pad_code,
+                                 _ptr(g_out), _ptr(g_grid), _ptr(g_keys), _ptr(ws), ws_bytes, _ptr(tk),
+                                 B, H, C, N, dim, Wa, _stream()),
                        "ct_slice_bwd_tk")
         return g_keys, g_grid, None, None, None
 
@@ -477,9 +483,10 @@ class SplatLcFn(torch.autograd.Function):
         padt, pad_code = _pad_args(pad, B, N)
         grid = torch.empty(B, HC, *W, device=feat.device, dtype=torch.float32)
         lib = _lib.load()
+        _det.push(lib)
         with _on(feat.device):
-            _lib.check(lib.ct_splat_lc_fwd(_ptr(lc), _ptr(idx), _ptr(feat), _ptr(padt), pad_code, _ptr(grid),
-                                           B, H, C, N, dim, _lib.int_array(W), _lib.REDUCE[reduce], _stream()),
+            _lib.check(_det.call(lib, "ct_splat_lc_fwd", "ct_splat_lc_fwd (%s)" % _BIG_GRID_ADD, _ptr(lc), _ptr(idx), _ptr(feat), _ptr(padt),
+                                 pad_code, _ptr(grid), B, H, C, N, dim, _lib.int_array(W), _lib.REDUCE[reduce], _stream()),
                        "ct_splat_lc_fwd")
         ctx.save_for_backward(lc, idx, feat, padt, grid if reduce == "max" else None)
         ctx.meta = (W, H, C, reduce, pad_code)
@@ -495,6 +502,7 @@ class SplatLcFn(torch.autograd.Function):
         g_feat = torch.empty_like(feat)
         g_lc = torch.empty_like(lc)
         lib = _lib.load()
+        _det.push(lib)          # (the query below is sized by the mode)
         Wa = _lib.int_array(W)
         ws_bytes = lib.ct_splat_bwd_workspace_bytes(B, H, C, N, dim, Wa, _lib.REDUCE[reduce])
         ws = torch.empty(ws_bytes, device=feat.device, dtype=torch.uint8) if ws_bytes else None
@@ -537,9 +545,10 @@ class SliceLcFn(torch.autograd.Function):
         g_grid = torch.empty_like(grid)
         g_lc = torch.empty_like(lc)
         lib = _lib.load()
+        _det.push(lib)
         with _on(grid.device):
-            _lib.check(lib.ct_slice_lc_bwd(_ptr(lc), _ptr(idx), _ptr(grid), _ptr(padt), pad_code, _ptr(g_out),
-                                           _ptr(g_grid), _ptr(g_lc), B, H, C, N, dim, _lib.int_array(W), _stream()),
+            _lib.check(_det.call(lib, "ct_slice_lc_bwd", "ct_slice_lc_bwd (%s)" % _BIG_GRID_ADD, _ptr(lc), _ptr(idx), _ptr(grid), _ptr(padt),
+                                 pad_code, _ptr(g_out), _ptr(g_grid), _ptr(g_lc), B, H, C, N, dim, _lib.int_array(W), _stream()),
                        "ct_slice_lc_bwd")
         return g_lc, None, g_grid, None, None, None
 
@@ -593,6 +602,7 @@ class LatticeFn(torch.autograd.Function):
         g_scales = torch.empty_like(scales) if scales is not None else None
         g_ks = torch.empty_like(ks) if ks is not None else None
         lib = _lib.load()
+        _det.push(lib)          # (the workspace is always passed: the parameter sums are ordered in either mode)
         with _on(xyz.device):
             ws_bytes = lib.ct_lattice_bwd_workspace_bytes(B, H, N)
             ws = torch.empty(ws_bytes, device=xyz.device, dtype=torch.uint8)
@@ -662,6 +672,7 @@ class LatticeSo3Fn(torch.autograd.Function):
         g_scales = torch.empty_like(scales) if scales is not None else None
         g_ks = torch.empty_like(ks) if ks is not None else None
         lib = _lib.load()
+        _det.push(lib)          # (the workspace is always passed: the parameter sums are ordered in either mode)
         with _on(xyz.device):
             ws_bytes = lib.ct_lattice_bwd_workspace_bytes(B, H, N)
             ws = torch.empty(ws_bytes, device=xyz.device, dtype=torch.uint8)
@@ -1869,7 +1880,9 @@ class MhctCoreFn(torch.autograd.Function):
         lib = _lib.load()
         Wa = _lib.int_array(W)
         # one workgroup per plane recomputes z and conv(z) in the backward where all five tiles fit a CU: nothing to save
-        recompute = bool(need_grad and FUSED_CORE_BWD and B * H >= 64 and lib.ct_mhct_core_bwd_fused_supported(B, H, C, N, dim, Wa))
+        # (off in deterministic mode: its Splat step keeps the first-claim tie rule)
+        recompute = bool(need_grad and FUSED_CORE_BWD and not _det.is_deterministic() and B * H >= 64
+                         and lib.ct_mhct_core_bwd_fused_supported(B, H, C, N, dim, Wa))
         out = torch.empty(B, HC, N, device=dev, dtype=torch.float32)
         z = torch.empty(B, HC, *W, device=dev, dtype=torch.float32) if need_grad and not recompute else None
         y = torch.empty(B, HC, *W, device=dev, dtype=torch.float32) if need_grad and not recompute else None
@@ -1899,6 +1912,8 @@ class MhctCoreFn(torch.autograd.Function):
         g_b = torch.empty(HC, device=dev, dtype=torch.float32) if has_bias else None
         lib = _lib.load()
         Wa = _lib.int_array(W)
+        if _det.push(lib) and z is None:
+            _det.refuse("ct_mhct_core_bwd_fused")      # (the forward ran outside the mode and saved no grids)
         if z is None:                 # LDS-resident backward: recomputes the grids from the points
             nws = lib.ct_mhct_core_bwd_fused_workspace_bytes(B, H, C, N, dim, Wa)
             ws = torch.empty(nws, device=dev, dtype=torch.uint8)

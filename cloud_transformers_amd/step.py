@@ -7,6 +7,7 @@ so a whole step can be captured into a HIP graph and replayed.
 import torch
 
 from . import _lib
+from . import determinism as _det
 from .ops import _ptr, _stream, sizes_of
 
 
@@ -35,6 +36,8 @@ class SplatSliceStep:
         self.g_keys_buf = torch.empty_like(self.keys)        # Slice's key cotangent
         self.g_keys_out = self.g_keys_buf                    # + Splat's: added in place ...
         self.lib = _lib.load()
+        # the mode the step was planned under (workspaces, the second key tensor); run() sets the library's switch to it again
+        self.deterministic = _det.push(self.lib)
         self.Wa = _lib.int_array(self.W)
         self.red = _lib.REDUCE[reduce]
         nws = self.lib.ct_splat_bwd_ex_workspace_bytes(self.B, self.H, self.C, self.N, dim, self.Wa, self.red,
@@ -135,6 +138,7 @@ class SplatSliceStep:
         return tags
 
     def run(self):
+        self.lib.ct_set_deterministic(1 if self.deterministic else 0)      # the mode the workspaces were planned under
         self.plane_sort()
         self.splat_fwd()
         self.slice_fwd()

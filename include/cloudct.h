@@ -4,7 +4,9 @@
  *
  * Every entry point is `extern "C"`, takes plain device pointers + sizes and a
  * HIP stream (passed as void* so that this header needs no HIP include), never
- * allocates, never synchronises the device, keeps no global state and returns
+ * allocates, never synchronises the device, keeps no global state — but for the
+ * process-wide deterministic switch ct_set_deterministic and the ct_debug_* test
+ * hooks below, host-side atomics that no kernel reads — and returns
  * an int status: CT_OK (0) or a negative CT_E* code (ct_strerror() names it).
  * All tensors are fp32, contiguous, channels-first with the point index N
  * fastest — the reference's layout (layers/cloud_transform.py:140,156).  Work is
@@ -41,7 +43,7 @@ extern "C" {
  * ct_block_items and ct_seg_confusion the same way; then the index table ct_nbr_table_bytes / ct_nbr_table_set /
  * ct_nbr_radius_multi and the device plan ct_kp_plan / ct_kp_plan_workspace_bytes; then ct_image_items; then the voxel-grid
  * subsampling ct_voxel_bounds / ct_voxel_keys / ct_voxel_reduce and their workspace queries; then the resident ShapeNet
- * completion gather ct_completion_gather.) */
+ * completion gather ct_completion_gather; then the deterministic switch ct_set_deterministic / ct_get_deterministic / ct_deterministic_override.) */
 #define CT_ABI_VERSION 3
 
 /* status codes */
@@ -68,6 +70,43 @@ int ct_abi_version(void);
 const char* ct_strerror(int status);
 
 /* ------------------------------------------------------------------------
+ * Deterministic mode.  Process-wide host state, atomic: set on one thread, read ONCE per call by the entry points on any
+ * thread (autograd runs the backward entry points on threads of its own, so the state cannot be thread-local), never read
+ * by a kernel.  Off by default; the default path is unchanged by it.  Added under CT_ABI_VERSION 3 (additive symbols).
+ * While it is on, equal inputs give bit-equal outputs from run to run:
+ *   - Splat(max) backward (ct_splat_bwd, _ex, _tk, ct_splat_lc_bwd and the Splat step of ct_mhct_core_bwd / _tk): the winner
+ *     of a (cell, channel) is the LOWEST POINT INDEX among the contributions whose product is positive and bit-equal to z
+ *     (the lowest corner of that point if two of its corners name the cell) — on every shape, by a two-phase claim
+ *     (csrc/ct_raster_det.h: splat_max_bwd_det_kernel); point segments are not used and g_keys is summed in a fixed order
+ *     (one workgroup per plane, or per-group partials in the workspace added in group order).  The launch tag carries
+ *     "splat_max_bwd_det".  CT_DEBUG_FORCE_BAND still selects the banded kernels, which follow the same rule.
+ *     The workspace queries ct_splat_bwd_workspace_bytes / _ex_ are sized BY THE MODE: they read the switch, and a query and
+ *     a launch must be made under the same setting (the partial g_keys of the channel-chunk groups differ between the
+ *     modes).  Grids whose single-channel tile exceeds a CU's LDS (4 G bytes: 256^2) keep the claim words in the workspace:
+ *     CT_EWORKSPACE without it; without the partials' share one workgroup walks all chunks of its plane.
+ *   - the generic corner-cotangent pass behind ct_slice_lc_bwd, ct_slice_bwd / ct_slice_bwd_keys off the hot shapes and
+ *     Splat(sum) backward: a plane's channel chunks are not dealt to groups of workgroups (whose g_keys / g_local_coord sums
+ *     went through float atomics); a thread adds the chunks of its own points in order.
+ *   - the scatter-ADD onto a grid whose single-channel tile exceeds a CU's LDS (256^2, 36^3: the `scatter_global_atomics` form
+ *     behind ct_splat_fwd with CT_REDUCE_SUM, ct_slice_bwd* / ct_slice_lc_bwd / ct_slice_bwd_grid where the banded kernels do
+ *     not take the call) is global float atomics in arrival order and has no ordered form: CT_EPRECOND in the mode, before
+ *     anything is written.  (The same grids' scatter-MAX is an atomic max, which no order changes.)
+ *   - ct_chamfer_bwd: every destination row written once: its own term first, then its sources in ascending index.
+ *   - ct_gconv_bwd_weight and ct_lattice_bwd: CT_EPRECOND for a NULL workspace where the shape would take float atomics
+ *     (the ring kernel without a workspace; the lattice parameter sums), and for the tile form of rows that are not a
+ *     multiple of 4 floats, which has atomics only.
+ * Every other entry point computes the same bits in either mode on finite values within the fixed-point range of the scatter-adds
+ * (DESIGN.md §4.11 has the table and its exceptions).
+ * ct_deterministic_override(on): on = 0 / 1 sets the mode for the entry points the CALLING THREAD invokes, whatever the
+ * process-wide switch says, on < 0 ends the override — how a caller runs ONE refused call in its ordinary form (torch's
+ * warn_only) without switching other threads' calls, which sit between their workspace query and their launch, to the
+ * other mode.  ct_get_deterministic() returns the mode in effect for the calling thread.
+ * ---------------------------------------------------------------------- */
+void ct_set_deterministic(int on);
+int ct_get_deterministic(void);
+void ct_deterministic_override(int on);
+
+/* ------------------------------------------------------------------------
  * DifferentiablePositions  (layers/cloud_transform.py:72-121,
  *                           layers/utils.py:100-186 bi/tri-linear corners)
  * keys f32[B,H*dim,N] -> local_coord f32[B,H,V,N], flat_idx i64[B,H,V,N]
@@ -91,7 +130,8 @@ int ct_positions_bwd(const float* keys, const float* g_local_coord, float* g_key
  *   the tied contributions receives it — as in torch_scatter, whose CPU and CUDA
  *   paths differ in WHICH one.  Here: a single chance tie in a plane is awarded
  *   to the lowest point index; with more ties (duplicated points) the winner is
- *   unspecified.  HISTORY.md §2 has the rule per kernel family.)
+ *   unspecified — unless ct_set_deterministic(1): then always the lowest point index.
+ *   HISTORY.md §2 has the rule per kernel family.)
  *   DEVIATION, deliberate: a candidate whose product is exactly +-0 (a point exactly on a cell boundary: one corner weight is 0;
  *   or a feature that is exactly 0, e.g. under a padding mask) aimed at a cell whose maximum stays at the zero floor receives
  *   NOTHING here.  torch_scatter.scatter_max records it as the arg-max (0 == 0) and routes the cell's cotangent to it.  Values
