@@ -60,6 +60,33 @@ struct PwArgs {
 #endif
 };
 
+// NORM instantiation (CT_PW_FWD only): the eval-mode BatchNorm1d (+ ReLU, + skip) that follows the projection, applied to the
+// fp32 value the epilogue holds instead of in a pass of its own (ct_bn_eval_group_fwd: ct_bnorm.hip).  Up to kPwNormMax norms
+// cover the output rows [0, M) in order, each with its own output tensor; an item's rows end where the next one's begin, at
+// any row (not at a tile, wave-block or MFMA-block boundary).
+constexpr int kPwNormMax = 8;          // = kBnMaxItems of ct_bnorm.hip
+struct PwNormItem {
+  const float* weight; const float* bias; const float* mean; const float* var;
+  const float* residual;               // nullable
+  float* y;
+  long long ybs, rbs;                  // batch strides of y / residual in floats
+  int row0, relu;                      // the item's first output row
+  float eps;
+};
+struct PwNormArgs : PwArgs {
+  PwNormItem item[kPwNormMax];
+  int n_items;
+  float* amax_out;                     // nullable: slot blockIdx.x = max |.| of what this workgroup stored
+};
+// what the epilogue needs of one row of the tile, staged in LDS once per workgroup
+struct PwNormRow {
+  float mu, rs, w, be;
+  float* y;                            // the row of THIS cloud: y + z * ybs + c * N
+  const float* res;                    // likewise, or null
+  int relu, pad[3];
+};
+static_assert(sizeof(PwNormRow) == 48, "one row record = three 16-byte LDS reads");
+
 // power of two s with s * amax in [2^13, 2^14); 1 for an all-zero or non-finite tensor (inf / nan then flow through h)
 __device__ __forceinline__ int pw_scale_exp(unsigned amax_bits) {
   const float m = __uint_as_float(amax_bits);
@@ -236,9 +263,10 @@ __device__ __forceinline__ pw_h8 pw_frag(const _Float16* img, int row, int sw, i
   }
 }
 
-template <bool A_KMAJOR, bool B_KMAJOR, bool ADD = false>
-__global__ void __launch_bounds__(kPwThreads, 4) pw_gemm_kernel(PwArgs a) {
+template <bool A_KMAJOR, bool B_KMAJOR, bool ADD = false, bool NORM = false>
+__global__ void __launch_bounds__(kPwThreads, 4) pw_gemm_kernel(std::conditional_t<NORM, PwNormArgs, PwArgs> aa) {
   extern __shared__ __attribute__((aligned(16))) _Float16 pw_lds[];
+  const PwArgs& a = aa;
   // blocks that share an XCD (id % 8) take consecutive tiles: the M tiles of one [K, 128] operand panel run side by side on
   // one L2 (bijective form of the remap, cdna_hip_programming.md §5)
   const int nwg = gridDim.x, xcd = blockIdx.x & 7, q = nwg >> 3, rr = nwg & 7;
@@ -466,6 +494,79 @@ __global__ void __launch_bounds__(kPwThreads, 4) pw_gemm_kernel(PwArgs a) {
         const float ia = ldexpf(1.f, -etab[lr]);
         if (row < a.M && col < a.N) C[(size_t)row * a.ldc + col] = acc[i][e] * ia * ib + dv[i][e];
       }
+    return;
+  }
+  if constexpr (NORM) {
+    // The per-row side of the affine, once per workgroup: the tile's first 128 threads each find their row's item (the items
+    // are compared in order: at most seven comparisons), read its four parameters of the row's channel and leave a record in
+    // the first stage (dead since the K loop's last barrier; the scale exponents lie behind the stages).  A lane holding
+    // the parameters of its 32 rows itself would need 128 registers for them beside the 32 accumulators and the 32
+    // residual values: past the 128 of this kernel's occupancy.  A record is read back as three 16-byte broadcasts.
+    PwNormRow* rows = (PwNormRow*)pw_lds;
+    if (t < kPwTile && m0 + t < a.M) {
+      const int row = m0 + t;
+      PwNormItem it = aa.item[0];
+#pragma unroll
+      for (int i = 1; i < kPwNormMax; ++i)
+        if (i < aa.n_items && row >= aa.item[i].row0) it = aa.item[i];
+      const int c = row - it.row0;
+      PwNormRow rec;
+      rec.mu = it.mean[c]; rec.rs = 1.0f / sqrtf(it.var[c] + it.eps); rec.w = it.weight[c]; rec.be = it.bias[c];
+      rec.y = it.y + z * it.ybs + (long long)c * a.N;
+      rec.res = it.residual ? it.residual + z * it.rbs + (long long)c * a.N : nullptr;
+      rec.relu = it.relu; rec.pad[0] = rec.pad[1] = rec.pad[2] = 0;
+      rows[t] = rec;
+    }
+    __syncthreads();
+    // bn_eval_one's operation sequence on the value the plain epilogue would have stored (ct_bnorm.hip): the same bits as
+    // ct_pw_gemm_rs followed by ct_bn_eval_group_fwd.  Per 32-row MFMA block: the skip connection's 16 values of this lane
+    // requested together, then the block's stores (all 32 at once, as the addend above, do not fit beside the row records'
+    // pointers in 128 registers).
+    float am = 0.f;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      float dv[16];
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int lr = 64 * wm + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
+        const float* rp = rows[lr].res;
+        dv[e] = (m0 + lr < a.M && col < a.N && rp) ? rp[col] : 0.f;
+      }
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int lr = 64 * wm + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
+        const float ia = ldexpf(1.f, -etab[lr]);
+        if (m0 + lr < a.M && col < a.N) {
+          const PwNormRow& R = rows[lr];
+          const float v = acc[i][e] * ia * ib;
+          float o = ((v - R.mu) * R.rs) * R.w + R.be;
+          if (R.relu) o = fmaxf(o, 0.0f);
+          if (R.res) o += dv[e];
+          R.y[col] = o;
+          am = fmaxf(am, fabsf(o));
+        }
+      }
+    }
+    // max |o| of the tile as stored: one partial maximum per workgroup (no atomics, nothing to zero), folded by the GEMM
+    // that reads the outputs next
+    if (aa.amax_out) {
+      // over the wave by ds_swizzle (xor of the lane within 32) and two readlanes: __shfl_xor would share its lane-address
+      // registers with the fold of the operand maxima at the kernel's start, and the compiler then keeps (spills) them
+      // across the whole K loop
+#define PW_SWZ_MAX(o) am = fmaxf(am, __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(am), ((o) << 10) | 0x1f)))
+      PW_SWZ_MAX(16); PW_SWZ_MAX(8); PW_SWZ_MAX(4); PW_SWZ_MAX(2); PW_SWZ_MAX(1);
+#undef PW_SWZ_MAX
+      am = fmaxf(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(am), 0)),
+                 __int_as_float(__builtin_amdgcn_readlane(__float_as_int(am), 32)));
+      float* red = (float*)(rows + kPwTile);
+      if (lane == 0) red[w] = am;
+      __syncthreads();
+      if (t == 0) {
+#pragma unroll
+        for (int i = 1; i < 8; ++i) am = fmaxf(am, red[i]);
+        aa.amax_out[blockIdx.x] = am;
+      }
+    }
     return;
   }
 #pragma unroll
@@ -701,9 +802,9 @@ static bool pw_plan(int mode, int B, int Co, int Ci, int N, PwPlan& p) {
 // (A second, persistent 128 x 256 kernel lived here through round 4: faster stand-alone on wide weight gradients and at K >= 1024,
 // nothing inside the training steps — 17.2 / 15.2 / 32.6 vs 17.2 / 15.1 / 31.6 ms, profiles/r4_model_steps.txt — and dispatched
 // nowhere by default.  Out of the build since round 5: tools/dev/experiments/ct_pwgemm2.h.)
-template <bool AK, bool BK, bool ADD = false>
-static int pw_launch(const PwArgs& a, int blocks, hipStream_t st) {
-  auto k = pw_gemm_kernel<AK, BK, ADD>;
+template <bool AK, bool BK, bool ADD = false, bool NORM = false>
+static int pw_launch(const std::conditional_t<NORM, PwNormArgs, PwArgs>& a, int blocks, hipStream_t st) {
+  auto k = pw_gemm_kernel<AK, BK, ADD, NORM>;
   static bool attr = false;
   if (!attr) {
     if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, kPwLdsBytes) != hipSuccess) return CT_ELAUNCH;
@@ -844,6 +945,56 @@ int ct_pw_gemm_rs_add(int mode, const float* a, const float* b, float* out, cons
     hipLaunchKernelGGL(pw_reduce_kernel, dim3((n4 + 31) / 32), dim3(256), 0, st, (const float*)workspace, out, n4, p.Z);
     CT_CHECK_LAUNCH();
   }
+  return CT_OK;
+}
+
+// partial maxima ct_pw_gemm_rs_norm writes (one per workgroup = output tile), 0 when there would be more than ct_pw_gemm folds
+int ct_pw_gemm_norm_amax_len(int B, int Co, int N) {
+  if (B < 1 || Co < 1 || N < 1) return 0;
+  const long long n = (long long)((Co + kPwTile - 1) / kPwTile) * ((N + kPwTile - 1) / kPwTile) * B;
+  return n <= kPwAmaxMax ? (int)n : 0;
+}
+
+// CT_PW_FWD with the eval-mode norms of the output rows in the epilogue: include/cloudct.h
+int ct_pw_gemm_rs_norm(const float* w, const float* x, const ct_bn_fwd_item* items, int n, float* amax_out, const float* amax_a,
+                       int n_amax_a, int rows_a, const float* amax_b, int n_amax_b, void* workspace, size_t workspace_bytes, int B,
+                       int Co, int Ci, int N, ct_stream_t s) {
+  (void)workspace; (void)workspace_bytes;      // the forward arrangement needs none
+  PwPlan p;
+  if (!w || !x || !items || n < 1 || n > kPwNormMax) return CT_EINVAL;
+  if (!pw_plan(CT_PW_FWD, B, Co, Ci, N, p)) return CT_EINVAL;
+  if ((amax_a && (n_amax_a < 1 || n_amax_a > kPwAmaxMax)) || (amax_b && (n_amax_b < 1 || n_amax_b > kPwAmaxMax))) return CT_EINVAL;
+  if (rows_a != 0 && (!amax_a || rows_a != Co || n_amax_a % rows_a != 0)) return CT_EINVAL;
+  if (((uintptr_t)w | (uintptr_t)x) & 15) return CT_EINVAL;
+  if (amax_out && ct_pw_gemm_norm_amax_len(B, Co, N) == 0) return CT_EINVAL;
+  PwNormArgs g{};
+  long long row0 = 0;
+  for (int i = 0; i < n; ++i) {
+    const ct_bn_fwd_item& it = items[i];
+    if (it.C < 1 || !it.weight || !it.bias || !it.y || !it.running_mean || !it.running_var || !(it.eps >= 0.0f) || it.amax_out)
+      return CT_EINVAL;
+    // a batch stride: 0 (= contiguous, C*N) or at least C*N, as ct_bn_eval_group_fwd; rows are written / read where they
+    // are 16-byte addressable only (N % 4 == 0 holds: pw_plan)
+    const long long dense = (long long)it.C * N;
+    const long long ybs = it.y_batch_stride ? it.y_batch_stride : dense, rbs = it.residual_batch_stride ? it.residual_batch_stride : dense;
+    if (ybs < dense || rbs < dense || ((ybs | rbs) & 3) || (((uintptr_t)it.y | (uintptr_t)it.residual) & 15)) return CT_EINVAL;
+    g.item[i] = PwNormItem{it.weight, it.bias, it.running_mean, it.running_var, it.residual, it.y, ybs, rbs, (int)row0, it.relu, it.eps};
+    row0 += it.C;
+    if (row0 > Co) return CT_EINVAL;
+  }
+  if (row0 != Co) return CT_EINVAL;
+  CT_CLEAR_ERROR();
+  g.n_items = n; g.amax_out = amax_out;
+  g.A = w; g.B = x; g.amax_a = amax_a; g.amax_b = amax_b; g.n_amax_a = n_amax_a; g.n_amax_b = n_amax_b;
+  g.rows_a = rows_a; g.rows_b = 0;
+#ifdef PW_STAMP
+  g.dbg = g_pw_dbg;
+#endif
+  g.M = p.M; g.N = p.N; g.K = p.K; g.tilesM = p.tilesM; g.tilesN = p.tilesN; g.ksplit = p.ksplit; g.Kc = p.Kc; g.Z = p.Z;
+  g.lda = Ci; g.a_bs = 0; g.ldb = N; g.b_bs = (long long)Ci * N; g.C = nullptr; g.ldc = N; g.c_zs = 0;
+  const int rc = pw_launch<true, false, false, true>(g, p.tilesM * p.tilesN * p.Z, (hipStream_t)s);
+  if (rc != CT_OK) return rc;
+  CT_CHECK_LAUNCH();
   return CT_OK;
 }
 

@@ -62,11 +62,23 @@ def run_after(module_list, input, residual=None):
     nn.ReLU runs as the fused ct_bn_relu kernels when the shape qualifies (ops.bn_relu_eligible), the skip connection
     added in the same pass when that pair ends the stack (an nn.SyncBatchNorm too: ops exchanges the group's statistics
     over its process group); the same pair in eval mode runs as ct_bn_eval_group_fwd where autograd records nothing
-    (ops.bn_eval_eligible) — an eval forward with gradients and every other layer go through their own forward."""
+    (ops.bn_eval_eligible), and a bias-free PointwiseConv1d in front of such a pair takes the pair into its GEMM's epilogue
+    (ops.pw_norm_eligible: ct_pw_gemm_rs_norm) — an eval forward with gradients and every other layer go through their own
+    forward."""
     layers = list(module_list)
     i = 0
     while i < len(layers):
         layer = layers[i]
+        if i + 2 < len(layers) and type(layer) is PointwiseConv1d and type(layers[i + 2]) is nn.ReLU and not layers[i + 1].training:
+            # projection -> eval norm -> ReLU (the union block's `after`): the norm in the GEMM's epilogue
+            res = residual if (i + 3 == len(layers) and residual is not None and residual.dtype == input.dtype and input.dim() == 3
+                               and residual.shape == (input.size(0), layer.out_channels, input.size(2))) else None
+            if ops.pw_norm_eligible(layer, [layers[i + 1]], input, residual=res):
+                input = ops.pw_bn_eval(input, layer, layers[i + 1], relu=True, residual=res)
+                if res is not None:
+                    residual = None
+                i += 3
+                continue
         pair = i + 1 < len(layers) and type(layers[i + 1]) is nn.ReLU
         fuse_res = (pair and i + 2 == len(layers) and residual is not None and residual.shape == input.shape
                     and residual.dtype == input.dtype)
@@ -143,6 +155,16 @@ class _MHCTCore(nn.Module):
         k_part, v_part = torch.split(key_values, [Ck, Cv], dim=1)   # backward: one cat
         return self.key_bn(k_part), self.values_bn(v_part)
 
+    def _keys_values(self, input):
+        """(key_bn(y[:, :3H]), values_bn(y[:, 3H:])) of y = keys_values_pred(input): in eval mode without gradients the two
+        norms run in the projection GEMM's epilogue where the kernel takes the shape (ops.pw_norm_eligible), else the
+        projection and _norm_keys_values."""
+        kvp = self.keys_values_pred
+        if (len(kvp) == 1 and type(kvp[0]) is PointwiseConv1d and not self.key_bn.training
+                and ops.pw_norm_eligible(kvp[0], [self.key_bn, self.values_bn], input, mode=None)):
+            return ops.split_pw_bn_eval(input, kvp[0], self.key_bn, self.values_bn)
+        return self._norm_keys_values(kvp(input))
+
     def _core(self, lattice, values, pts_padd=None):
         """(sliced features, occupancy) = Slice(conv(Splat(values))) at the lattice (multihead_ct.py:99-107).  The grids whose
         two tiles fit a CU run as ONE kernel that keeps them in LDS (ops.mhct_core: 32^2 / 16^2 with 16 features per head,
@@ -196,7 +218,7 @@ class MultiHead(_MHCTCore):
         if isinstance(orig_pcd, tuple):
             orig_pcd, pts_padd = orig_pcd
         if kv is None:
-            keys_res, values = self._norm_keys_values(self.keys_values_pred(input))
+            keys_res, values = self._keys_values(input)
         else:
             keys_res, values = kv
         keys, lattice, kstats = self._lattice(orig_pcd, keys_res)
@@ -230,8 +252,7 @@ class MultiHeadPool(_MHCTCore):
 
     def forward(self, input, orig_pcd, return_lattice=False):
         H = self.heads
-        key_values = self.keys_values_pred(input)
-        keys_res, values = self._norm_keys_values(key_values)
+        keys_res, values = self._keys_values(input)
         keys, lattice, kstats = self._lattice(orig_pcd, keys_res)
         z = self.splat.forward_keys(lattice, values)
         occ = self._occupancy(z, keys.size(0))

@@ -1651,13 +1651,20 @@ def union_keys_values_eval_eligible(x, convs, key_bns, values_bns):
 
 def union_keys_values_eval(x, convs, key_bns, values_bns):
     """[(key_bn_i(y_i[:, :Ck]), values_bn_i(y_i[:, Ck:])) with y_i = conv_i(x)] for the heads of a union block in eval mode:
-    ONE stacked projection GEMM, then the 2n norms on its channel ranges in one launch (2n <= BN_GROUP_MAX); the caller
-    checked union_keys_values_eval_eligible."""
+    ONE stacked projection GEMM with the 2n norms in its epilogue (PW_NORM, 2n <= BN_GROUP_MAX and a product the forward
+    kernel takes), else that GEMM and then the norms on its channel ranges in one launch; the caller checked
+    union_keys_values_eval_eligible."""
     x = _f32c(x)
     _dev(x)
     B, _, N = x.shape
     Wc = torch.cat([conv.weight.detach()[:, :, 0] for conv in convs], dim=0)        # [sum Co, Cin]
     Ct = Wc.size(0)
+    bns = [bn for kb, vb in zip(key_bns, values_bns) for bn in (kb, vb)]
+    if _pw_norm_takes(Ct, Wc.size(1), N, len(bns), PW_FWD):
+        # the 2n norms in the stacked GEMM's epilogue: the [B, sum Co, N] tensor is never written
+        outs = [torch.empty(B, bn.num_features, N, device=x.device, dtype=torch.float32) for bn in bns]
+        pw_gemm_norm(Wc, x, [_bn_eval_item(bn, None, 0, _ptr(o), 0, False) for bn, o in zip(bns, outs)])
+        return [(outs[2 * i], outs[2 * i + 1]) for i in range(len(convs))]
     y = pw_forward(Wc, x)[0]                                                        # [B, sum Co, N]
     items, outs, c0 = [], [], 0
     for kb, vb in zip(key_bns, values_bns):
@@ -1670,6 +1677,95 @@ def union_keys_values_eval(x, convs, key_bns, values_bns):
     with _on(x.device):
         _bn_eval_group(items, B, N)
     return [(outs[2 * i], outs[2 * i + 1]) for i in range(len(convs))]
+
+
+# ---------------------------------------------------------------------------
+# eval-mode norms in the epilogue of the pointwise GEMM that produces their input (ct_pw_gemm_rs_norm)
+# ---------------------------------------------------------------------------
+# Consulted only where BN_EVAL already routes to the eval kernels; the results carry the bits of the GEMM followed by
+# ct_bn_eval_group_fwd.  "0": the two launches (A/B runs).
+PW_NORM = os.environ.get("CLOUDCT_PW_NORM", "1") != "0"
+
+
+def _pw_norm_takes(Co, Ci, N, n, mode=None):
+    """The switches, a table of 1..BN_GROUP_MAX norms and a product ct_pw_gemm takes (`mode` as pw_eligible: PW_FWD where
+    the unfused path would otherwise run the library GEMM, so that the switch never changes which GEMM computes a value)."""
+    return PW_NORM and BN_EVAL and 1 <= n <= _lib.BN_GROUP_MAX and pw_eligible(Co, Ci, N, mode)
+
+
+def pw_norm_eligible(conv, bns, x, residual=None, mode=PW_FWD):
+    """True when `conv` (a bias-free 1x1 nn.Conv1d) followed by the eval-mode norms `bns` on consecutive channel ranges of its
+    output can run as ONE ct_pw_gemm_rs_norm call: x CUDA fp32 [B,Ci,N] contiguous and 16-byte aligned, at most BN_GROUP_MAX
+    norms that cover the output channels, each one ct_bn_eval_* takes, a product ct_pw_gemm takes, and nothing for autograd
+    to record (bn_eval_eligible's rule)."""
+    if not (PW_NORM and BN_EVAL and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()
+            and x.data_ptr() % 16 == 0 and all(type(bn) in _BN_TYPES for bn in bns)):
+        return False
+    if not (isinstance(conv, torch.nn.Conv1d) and conv.kernel_size == (1,) and conv.stride == (1,) and conv.padding == (0,)
+            and conv.dilation == (1,) and conv.groups == 1 and conv.bias is None and conv.in_channels == x.size(1)
+            and conv.weight.dtype == torch.float32 and conv.weight.device == x.device
+            and conv.out_channels == sum(bn.num_features for bn in bns)):
+        return False
+    if residual is not None and not (residual.is_cuda and residual.dtype == torch.float32 and residual.dim() == 3):
+        return False
+    B, Ci, N = x.shape
+    if not _pw_norm_takes(conv.out_channels, Ci, N, len(bns), mode):
+        return False
+    watched = [x, conv.weight, residual]
+    for bn in bns:
+        if not (_bn_eval_norm_ok(bn, B, bn.num_features, N) and bn.weight.device == x.device):
+            return False
+        watched += [bn.weight, bn.bias]
+    return _records_nothing(*watched)
+
+
+def pw_gemm_norm(W, x, items, want_amax=False):
+    """ct_pw_gemm_rs_norm: W [Co,Ci] x[b] with the eval norms `items` (_bn_eval_item dicts without an input, in the order of
+    the output rows they cover) applied in the epilogue; the operand maxima exactly as pw_forward takes them.  want_amax:
+    -> the partial maxima of everything stored (1-D: partials of one maximum, as ops.amax), or None where a GEMM could not
+    fold that many."""
+    lib = _lib.load()
+    W, x = _f32c(W), _f32c(x)
+    _dev(W, x)
+    Co, Ci = W.shape
+    B, _, N = x.shape
+    am_w = prep_weight(W, False)[0][0]
+    am_x = amax_of(x)
+    n_out = lib.ct_pw_gemm_norm_amax_len(B, Co, N) if want_amax else 0
+    slots = torch.empty(n_out, device=x.device, dtype=torch.float32) if n_out else None
+    arr = _bn_fwd_table(items)
+    with _on(x.device):
+        _lib.check(lib.ct_pw_gemm_rs_norm(_ptr(W), _ptr(x), _at(arr, 0), len(items), _ptr(slots), _ptr(am_w), am_w.numel(),
+                                          _rows_of(am_w, Co), _ptr(am_x), am_x.numel(), None, 0, B, Co, Ci, N, _stream()),
+                   "ct_pw_gemm_rs_norm")
+    return slots
+
+
+def pw_bn_eval(x, conv, bn, relu=True, residual=None):
+    """relu?(bn(conv(x))) [+ residual] in one launch; the caller checked pw_norm_eligible(conv, [bn], x, residual).  The
+    result carries the partial maxima of its values for the pointwise GEMM that reads it next."""
+    B, _, N = x.shape
+    C = bn.num_features
+    y = torch.empty(B, C, N, device=x.device, dtype=torch.float32)
+    rbs = 0
+    if residual is not None:
+        rbs = _batch_stride(residual, C, N)
+        if rbs is None:
+            residual, rbs = _f32c(residual), 0
+    slots = pw_gemm_norm(conv.weight.detach()[:, :, 0], x, [_bn_eval_item(bn, None, 0, _ptr(y), 0, relu, _ptr(residual), rbs)],
+                         want_amax=True)
+    if slots is not None:
+        y._ct_amax = (slots, y._version)        # (1-D on purpose: tag_amax would read [n / C, C] as per-channel maxima)
+    return y
+
+
+def split_pw_bn_eval(x, conv, bn_a, bn_b):
+    """(bn_a(y[:, :Ca]), bn_b(y[:, Ca:])) with y = conv(x), in one launch; the caller checked
+    pw_norm_eligible(conv, [bn_a, bn_b], x)."""
+    B, _, N = x.shape
+    outs = [torch.empty(B, bn.num_features, N, device=x.device, dtype=torch.float32) for bn in (bn_a, bn_b)]
+    pw_gemm_norm(conv.weight.detach()[:, :, 0], x, [_bn_eval_item(bn, None, 0, _ptr(o), 0, False) for bn, o in zip((bn_a, bn_b), outs)])
+    return outs[0], outs[1]
 
 
 # ---------------------------------------------------------------------------

@@ -629,6 +629,32 @@ int ct_pw_gemm_rs(int mode, const float* a, const float* b, float* out, const fl
 int ct_pw_gemm_rs_add(int mode, const float* a, const float* b, float* out, const float* addend, const float* amax_a, int n_amax_a,
                       int rows_a, const float* amax_b, int n_amax_b, int rows_b, void* workspace, size_t workspace_bytes, int B,
                       int Co, int Ci, int N, ct_stream_t s);
+/* CT_PW_FWD with the eval-mode BatchNorm1d (+ ReLU, + skip) that follows the projection applied in the GEMM's epilogue — the
+ * inference path's `keys_values_pred` -> key_bn / values_bn of every head and the union block's `after` (PointwiseConv1d ->
+ * BatchNorm1d -> ReLU, + the skip connection: layers/multihead_ct.py:149-153,198), where a norm launch of its own would read
+ * back the tensor the GEMM has just written:
+ *   y_i[b] = relu?( bn_i( (W x[b])[rows of item i] ) ) [+ residual_i[b]],   i = 0 .. n-1,  1 <= n <= 8
+ * The items cover the output rows [0, Co) in order (sum of C = Co; an item's rows may begin at any row) and follow the
+ * ct_bn_fwd_item contract ct_bn_eval_group_fwd reads: weight, bias, running_mean, running_var f32[C] (all required, read-only),
+ * eps >= 0, relu, y with y_batch_stride, residual (nullable) with residual_batch_stride (0 = contiguous, else >= C*N); x of an
+ * item is ignored and should be NULL, its amax_out must be NULL.  y and residual must be 16-byte addressable (aligned bases,
+ * strides % 4 == 0; N % 4 == 0 as for every ct_pw_gemm); y does not overlap x or a residual.  w, x, the operand maxima and
+ * rows_a as ct_pw_gemm_rs (the activation keeps one scale); the workspace arguments are unused.
+ * Bit equality: every stored value goes through the operation sequence of ct_pw_gemm_rs's epilogue and then
+ * ct_bn_eval_group_fwd's ( v = acc * 2^-ea * 2^-eb;  ((v - mean) * (1 / sqrt(var + eps))) * weight + bias;  max(., 0);
+ * + residual ), so each y_i holds exactly the bits of ct_pw_gemm_rs into a scratch tensor followed by ct_bn_eval_group_fwd
+ * with the same items.
+ * amax_out f32[ct_pw_gemm_norm_amax_len(B, Co, N)] (nullable): one partial maximum per workgroup, max |y| over its output tile
+ * as stored (after ReLU and skip) — partials of ONE maximum in the sense of ct_amax_f32 (rows_* = 0 for the GEMM that reads
+ * the outputs next), written without atomics, nothing to zero.  ct_pw_gemm_norm_amax_len returns 0 when there would be more
+ * partials than a GEMM folds (32768): pass NULL then.
+ * CT_EINVAL: n outside 1..8, sum of C != Co, a missing y / weight / bias / running statistic, a negative eps, a per-item
+ * amax_out, a refused or misaligned stride or pointer, amax_out where the length is 0, and whatever ct_pw_gemm_rs refuses.
+ * Added under CT_ABI_VERSION 3 (additive: the loader's missing-symbol scan checks it). */
+int ct_pw_gemm_norm_amax_len(int B, int Co, int N);
+int ct_pw_gemm_rs_norm(const float* w, const float* x, const ct_bn_fwd_item* items, int n, float* amax_out, const float* amax_a,
+                       int n_amax_a, int rows_a, const float* amax_b, int n_amax_b, void* workspace, size_t workspace_bytes, int B,
+                       int Co, int Ci, int N, ct_stream_t s);
 
 /* ------------------------------------------------------------------------
  * Neighbour search of the S3DIS KPConv protocol over a uniform grid (replaces the CPU

@@ -1,6 +1,6 @@
 """Eval-mode BatchNorm on the fused kernels (ct_bn_eval_*), at kernel and at model level:
 
-    python tools/bn_eval_bench.py [--part kernel|model|all] [--rounds 3] [--iters 20]
+    python tools/bn_eval_bench.py [--part kernel|model|after|pw_norm|all] [--rounds 3] [--iters 20]
 
 (a) kernel: eval BatchNorm1d + ReLU (+ the skip connection) as one ct_bn_eval_group_fwd launch (a table of one norm) against torch's modules, at
     tools/bn_bench.py's shapes and at a key norm's (B6 C48 N8192, cut over several workgroups); each replayed from a HIP
@@ -10,7 +10,12 @@
     (12 MultiHeadUnion blocks, model_dim 512; random weights, synthetic clouds), eager and replayed from a HIP graph, in
     fresh child processes that alternate CLOUDCT_BN_EVAL=1 / 0.  Only public API is used, so the same file runs on a
     revision without the eval kernels, where both settings are the module path and the rows give that revision's
-    run-to-run spread."""
+    run-to-run spread.
+(c) after: a union block's `after` at B8 N4096, 512 output channels — projection, eval BatchNorm1d, ReLU and the skip
+    connection as ONE ct_pw_gemm_rs_norm launch against the GEMM followed by ct_bn_eval_group_fwd (ops.PW_NORM flipped in
+    process: the same two kernels either way), graphed; the bytes the fusion removes are one write and one read of the
+    [B, 512, N] tensor.
+(d) pw_norm: the forwards of (b) in fresh child processes that alternate CLOUDCT_PW_NORM=1 / 0."""
 import argparse
 import json
 import os
@@ -88,6 +93,38 @@ def kernel_part(iters):
                   f"({100 * rate / COPY_RATE:5.1f} % of the float4 copy rate)")
 
 
+def after_part(iters):
+    import torch
+    from torch import nn
+    from cloud_transformers_amd import ops
+    from cloud_transformers_amd.layers.multihead_ct import run_after
+    from cloud_transformers_amd.layers.pointwise import PointwiseConv1d
+    print("(c) union `after` (projection + eval BatchNorm1d + ReLU + skip), B8 N4096, 512 output channels, graphed, us per call")
+    B, Co, N = 8, 512, 4096
+    for Ci in (128, 512, 768):                           # the concatenation widths of the segmenter's three block kinds
+        torch.manual_seed(Ci)
+        after = nn.Sequential(PointwiseConv1d(Ci, Co, kernel_size=1, bias=False), nn.BatchNorm1d(Co), nn.ReLU(inplace=True)).cuda().eval()
+        with torch.no_grad():
+            after[1].running_mean.uniform_(-0.2, 0.2)
+            after[1].running_var.uniform_(0.5, 1.5)
+            x = ops.bn_eval(torch.randn(B, Ci, N, device="cuda"), nn.BatchNorm1d(Ci).cuda().eval())      # carries its maxima, as a join's output
+            res = torch.randn(B, Co, N, device="cuda")
+            row = {}
+            for flag in (True, False):
+                ops.PW_NORM = flag
+                try:
+                    assert ops.pw_norm_eligible(after[0], [after[1]], x, residual=res) == flag
+                    row[flag] = timed(graphed(lambda: run_after(after, x, res)), iters)
+                    out = run_after(after, x, res)
+                finally:
+                    ops.PW_NORM = True
+                row[flag, "out"] = out
+            assert torch.equal(row[True, "out"], row[False, "out"])
+        saved = 2 * B * Co * N * 4
+        print(f"Ci{Ci:4d}: fused {row[True] * 1e3:7.1f} us | GEMM + ct_bn_eval_group_fwd {row[False] * 1e3:7.1f} us "
+              f"({row[False] / row[True]:4.2f}x; {saved / 1e6:.0f} MB less traffic = {saved / COPY_RATE * 1e6:.1f} us at the copy rate)")
+
+
 def build_model(name):
     import torch
     from torch import nn
@@ -140,31 +177,31 @@ def model_child(name, iters):
     with torch.no_grad():
         eager = timed(lambda: net(*args), iters)
         graph = timed(graphed(lambda: net(*args)), iters)
-    print(json.dumps({"model": name, "bn_eval": os.environ.get("CLOUDCT_BN_EVAL", "1"), "eager_ms": round(eager, 3),
-                      "graph_ms": round(graph, 3)}), flush=True)
+    print(json.dumps({"model": name, "bn_eval": os.environ.get("CLOUDCT_BN_EVAL", "1"), "pw_norm": os.environ.get("CLOUDCT_PW_NORM", "1"),
+                      "eager_ms": round(eager, 3), "graph_ms": round(graph, 3)}), flush=True)
 
 
-def model_part(rounds, iters):
-    print("(b) eval + no-grad forward, ms (fresh process per row, CLOUDCT_BN_EVAL alternating)")
+def model_part(rounds, iters, switch="CLOUDCT_BN_EVAL"):
+    print("(%s) eval + no-grad forward, ms (fresh process per row, %s alternating)" % ("b" if switch == "CLOUDCT_BN_EVAL" else "d", switch))
     for name in ("segmenter", "segmenter_pad"):
         rows = {"1": [], "0": []}
         for _ in range(rounds):
             for flag in ("1", "0"):
-                env = dict(os.environ, CLOUDCT_BN_EVAL=flag)
+                env = dict(os.environ, **{switch: flag})
                 out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, "--iters", str(iters)], env=env,
                                      check=True, capture_output=True, text=True, timeout=600).stdout
                 row = json.loads([line for line in out.splitlines() if line.startswith("{")][-1])
                 rows[flag].append(row)
-                print(f"{name:13s} CLOUDCT_BN_EVAL={flag}: eager {row['eager_ms']:8.3f}  graph {row['graph_ms']:8.3f}", flush=True)
+                print(f"{name:13s} {switch}={flag}: eager {row['eager_ms']:8.3f}  graph {row['graph_ms']:8.3f}", flush=True)
         for flag in ("1", "0"):
             for key in ("eager_ms", "graph_ms"):
                 v = sorted(r[key] for r in rows[flag])
-                print(f"{name:13s} CLOUDCT_BN_EVAL={flag} {key[:-3]:5s}: min {v[0]:8.3f}  median {v[len(v) // 2]:8.3f}  max {v[-1]:8.3f}")
+                print(f"{name:13s} {switch}={flag} {key[:-3]:5s}: min {v[0]:8.3f}  median {v[len(v) // 2]:8.3f}  max {v[-1]:8.3f}")
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=["kernel", "model", "all"], default="all")
+    ap.add_argument("--part", choices=["kernel", "model", "after", "pw_norm", "all"], default="all")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
@@ -175,6 +212,10 @@ def main():
         kernel_part(a.iters)
     if a.part in ("model", "all"):
         model_part(a.rounds, a.iters)
+    if a.part in ("after", "all"):
+        after_part(a.iters)
+    if a.part in ("pw_norm", "all"):
+        model_part(a.rounds, a.iters, switch="CLOUDCT_PW_NORM")
 
 
 if __name__ == "__main__":
