@@ -302,6 +302,10 @@ SIGNATURES = {
     "ct_mhct_core_status": (_i, [_vp, _sz, _i, _i, _i, _i, _i, _ip, ctypes.POINTER(ctypes.c_int), _vp]),
     "ct_chamfer_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "ct_chamfer_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "ct_chamfer_fwd_counts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "ct_chamfer_bwd_counts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "ct_rows_compact": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    "ct_chamfer_metrics": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _vp]),
     "ct_emd_workspace_bytes": (_sz, [_i, _i]),
     "ct_emd_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _f, _i, _vp]),
     "ct_emd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),

@@ -7,7 +7,10 @@ moves every cloud to the host and asks open3d's KD-tree for the nearest-neighbou
 distances, one cloud at a time; here both directions of the nearest-neighbour
 search for the whole batch are one ct_chamfer_fwd launch (the same kernel the
 Chamfer loss uses), the threshold counts stay on the device, and there is a single
-device->host copy of the [B, 3] result.
+device->host copy of the [B, 3] result.  `cloud_metrics`, `compact_nonzero`, `Metrics.get_batch`
+and `TableMeter` are the batched form of the completion benchmark's per-sample pair: clouds of
+different lengths in one launch (ct_chamfer_fwd_counts), the threshold counts and means in a
+second (ct_chamfer_metrics), sums per taxonomy on the device and one copy at the end.
 
 open3d returns Euclidean (not squared) distances in float64; the kernel returns
 squared float32 distances, so the comparison is `sqrt(d2) < th` in float32.  Only a
@@ -42,6 +45,45 @@ def fscore_batch(gt, pr, th=0.01):
     s = recall + precision
     fscore = torch.where(s > 0, 2 * recall * precision / s.clamp_min(1e-30), torch.zeros_like(s))
     return torch.stack([fscore, precision, recall], dim=1)
+
+
+def compact_nonzero(xyz):
+    """xyz f32[B,n,3] on the device -> (compacted f32[B,n,3], count i32[B]): per cloud, the rows whose coordinates do not sum
+    to zero, in order, then zero rows — the `xyz[torch.sum(xyz, dim=2).ne(0)]` of ChamferDistance(ignore_zeros=True)
+    (grdnet_utils.py:19-21) for every cloud of a batch (ct_rows_compact).  No host synchronisation."""
+    from . import _lib
+    from .ops import _dev, _on, _stream
+    _dev(xyz)
+    if xyz.dim() != 3 or xyz.size(2) != 3 or xyz.size(0) < 1 or xyz.size(1) < 1:
+        raise ValueError("compact_nonzero: xyz is [B, n, 3] with B, n >= 1; got %s" % (tuple(xyz.shape),))
+    xyz = xyz.detach().contiguous().float()
+    out = torch.empty_like(xyz)
+    count = torch.empty(xyz.size(0), dtype=torch.int32, device=xyz.device)
+    with _on(xyz.device):
+        _lib.check(_lib.load().ct_rows_compact(xyz.data_ptr(), out.data_ptr(), count.data_ptr(), xyz.size(0), xyz.size(1),
+                                               _stream(xyz.device)), "ct_rows_compact")
+    return out, count
+
+
+def cloud_metrics(gt, pr, th=0.01, gt_count=None, pr_count=None):
+    """gt f32[B,n,3], pr f32[B,m,3] whose cloud b has gt_count[b] / pr_count[b] rows (int32 [B] on the device; None: all) ->
+    table f32[B,4] = (fscore, precision, recall, chamfer) on the device: `fscore_batch(gt, pr, th)`'s three columns and
+    mean(dist1) + mean(dist2) over the valid rows, per cloud.  One ct_chamfer_fwd_counts and one ct_chamfer_metrics launch, no
+    read-back.  A cloud with a zero count: (0, 0, 0, NaN)."""
+    from . import _lib
+    from .chamfer import chamfer_with_counts
+    from .ops import _dev, _on, _ptr, _stream
+    _dev(gt, pr)
+    with torch.no_grad():
+        d1, d2, _, _ = chamfer_with_counts(gt.detach().contiguous().float(), pr.detach().contiguous().float(), gt_count, pr_count)
+        B, n, m = d1.size(0), d1.size(1), d2.size(1)
+        table = torch.empty(B, 4, dtype=torch.float32, device=d1.device)
+        c1 = None if gt_count is None else gt_count.contiguous()
+        c2 = None if pr_count is None else pr_count.contiguous()
+        with _on(d1.device):
+            _lib.check(_lib.load().ct_chamfer_metrics(d1.data_ptr(), d2.data_ptr(), _ptr(c1), _ptr(c2), float(th), None,
+                                                      table.data_ptr(), B, n, m, _stream(d1.device)), "ct_chamfer_metrics")
+    return table
 
 
 def calculate_fscore(gt, pr, th=0.01):
@@ -145,6 +187,25 @@ class AverageMeter(object):
         return self._read(lambda c: c.mean(), idx)
 
 
+class TableMeter(object):
+    """Sums of value rows per table row, kept on the device: `update(rows i64[k] on the device, values [k, n_cols])` adds
+    with index_add_ in float64 and counts the rows; `result()` is the single device-to-host copy ->
+    (counts int64 [n_rows], sums float64 [n_rows, n_cols]) as numpy arrays."""
+
+    def __init__(self, n_rows, n_cols, device):
+        self.n_rows, self.n_cols = int(n_rows), int(n_cols)
+        self._acc = torch.zeros(self.n_rows, self.n_cols + 1, dtype=torch.float64, device=device)      # last column: the count
+
+    def update(self, rows, values):
+        values = values.to(torch.float64).reshape(-1, self.n_cols)
+        ones = torch.ones(values.size(0), 1, dtype=torch.float64, device=values.device)
+        self._acc.index_add_(0, rows, torch.cat([values, ones], dim=1))
+
+    def result(self):
+        host = self._acc.cpu().numpy()
+        return host[:, -1].round().astype("int64"), host[:, :-1]
+
+
 class Metrics(object):
     """The completion benchmark's metric pair: F-Score@0.01 and Chamfer distance x1000
     (grdnet_utils.py:68-129).  `Metrics.get(pred [1,n,3], gt [1,m,3]) -> [fscore, cd1000]`."""
@@ -172,6 +233,22 @@ class Metrics(object):
     @classmethod
     def _get_chamfer_distance(cls, pred, gt):
         return cls._chamfer(pred, gt).item() * 1000
+
+    @classmethod
+    def get_batch(cls, pred, gt, th=0.01, with_dense=False):
+        """`get`'s pair for every cloud of a batch, on the device: pred [B,n,3], gt [B,m,3] -> f32[B,2] = (F-Score@th,
+        Chamfer distance x 1000), without a read-back.  As in `get`, the F-score is of the clouds as given and the Chamfer
+        distance of the clouds without their zero-sum rows (`compact_nonzero`): two nearest-neighbour passes per batch.
+        `with_dense`: a third column, mean(dist1) + mean(dist2) x 1000 of the clouds as given (ChamferDistance()(pred, gt) per
+        cloud), from the first pass."""
+        given = cloud_metrics(pred, gt, th)                               # cloud 1 = pred, as _get_f_score calls fscore_batch
+        p, p_count = compact_nonzero(pred)
+        g, g_count = compact_nonzero(gt)
+        kept = cloud_metrics(p, g, th, p_count, g_count)
+        cols = [given[:, 0], kept[:, 3] * 1000]
+        if with_dense:
+            cols.append(given[:, 3] * 1000)
+        return torch.stack(cols, dim=1)
 
     def __init__(self, metric_name, values):
         assert metric_name in self.NAMES, "Invalid metric name to compare."

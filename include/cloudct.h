@@ -43,7 +43,9 @@ extern "C" {
  * ct_block_items and ct_seg_confusion the same way; then the index table ct_nbr_table_bytes / ct_nbr_table_set /
  * ct_nbr_radius_multi and the device plan ct_kp_plan / ct_kp_plan_workspace_bytes; then ct_image_items; then the voxel-grid
  * subsampling ct_voxel_bounds / ct_voxel_keys / ct_voxel_reduce and their workspace queries; then the resident ShapeNet
- * completion gather ct_completion_gather; then the deterministic switch ct_set_deterministic / ct_get_deterministic / ct_deterministic_override.) */
+ * completion gather ct_completion_gather; then the deterministic switch ct_set_deterministic / ct_get_deterministic / ct_deterministic_override;
+ * then Chamfer with per-cloud counts and the metric table: ct_chamfer_fwd_counts / ct_chamfer_bwd_counts / ct_rows_compact /
+ * ct_chamfer_metrics.) */
 #define CT_ABI_VERSION 3
 
 /* status codes */
@@ -91,7 +93,8 @@ const char* ct_strerror(int status);
  *     behind ct_splat_fwd with CT_REDUCE_SUM, ct_slice_bwd* / ct_slice_lc_bwd / ct_slice_bwd_grid where the banded kernels do
  *     not take the call) is global float atomics in arrival order and has no ordered form: CT_EPRECOND in the mode, before
  *     anything is written.  (The same grids' scatter-MAX is an atomic max, which no order changes.)
- *   - ct_chamfer_bwd: every destination row written once: its own term first, then its sources in ascending index.
+ *   - ct_chamfer_bwd, ct_chamfer_bwd_counts: every destination row written once: its own term first, then its sources in
+ *     ascending index.
  *   - ct_gconv_bwd_weight and ct_lattice_bwd: CT_EPRECOND for a NULL workspace where the shape would take float atomics
  *     (the ring kernel without a workspace; the lattice parameter sums), and for the tile form of rows that are not a
  *     multiple of 4 floats, which has atomics only.
@@ -545,6 +548,48 @@ int ct_chamfer_fwd(const float* xyz1, const float* xyz2, float* dist1, float* di
 int ct_chamfer_bwd(const float* xyz1, const float* xyz2, const float* g_dist1, const float* g_dist2,
                    const int32_t* idx1, const int32_t* idx2, float* g_xyz1, float* g_xyz2,
                    int B, int n, int m, ct_stream_t s);
+
+/* ------------------------------------------------------------------------
+ * Chamfer distance of clouds of different lengths in one batch, and the metric table of an evaluation on top of it
+ * (utils/grdnet_utils.py:9-23 `ChamferDistance(ignore_zeros)`, whose boolean index works at B == 1 only, and :105-129
+ * `Metrics._get_f_score / _get_chamfer_distance`; eval_inpainting.py:187-226, the per-sample loop they are called from).
+ * Added under CT_ABI_VERSION 3 (additive symbols).  All five return CT_EINVAL for a null required pointer, B <= 0, n <= 0,
+ * m <= 0 or B > 65535; they enqueue on the stream s, allocate nothing and read nothing back to the host.
+ *
+ * ct_chamfer_fwd_counts: cnt1, cnt2 i32[B] in device memory, either may be null ("all n" / "all m").  Cloud b of set 1 is
+ *   the rows [0, cnt1[b]) of xyz1[b]; rows at or beyond a count are never read, as queries or as targets (they may hold
+ *   anything, NaN included).  Rows [0, cnt) of every output carry exactly the bits ct_chamfer_fwd returns for that pair of
+ *   clouds alone (B = 1, n = cnt1[b], m = cnt2[b]): the same distance expression, the lowest index on ties.  Rows at or
+ *   beyond the count get dist = 0, idx = -1, and so does every row of a cloud whose target cloud is empty; no output
+ *   element is left unwritten.  A count outside [0, n] is clamped into it.
+ * ct_chamfer_bwd_counts: ct_chamfer_bwd with the same two counts.  Rows at or beyond the count contribute nothing and
+ *   receive an exact +0.0.  Under ct_set_deterministic(1): the ordered form, per-cloud n and m, the bits of ct_chamfer_bwd
+ *   on each pair alone.
+ * ct_rows_compact: x f32[B,n,3] -> y f32[B,n,3], count i32[B].  Per cloud, the rows with (x + y) + z != 0.0f in their
+ *   input order (`torch.sum(xyz, dim=2).ne(0)` of grdnet_utils.py:20-21: a row such as (1, -1, 0) is dropped too, a NaN
+ *   row is kept), then zero rows; count[b] = the number kept.  Out of place: y must not overlap x (x == y: CT_EINVAL).
+ *   No atomics, so the result is the same on every run.
+ * ct_chamfer_metrics: dist1 f32[B,n], dist2 f32[B,m] (squared, as ct_chamfer_fwd* writes them), counts as above, either
+ *   may be null -> stats f64[B,2,3] (may be null), table f32[B,4].  stats[b][k] = (hits, sum d, sum (double)sqrtf(d)) over
+ *   rows [0, cnt_k), hits = the number of rows with sqrtf(d) < th in float32, both sums accumulated in float64.
+ *   table[b] = (fscore, precision, recall, chamfer) in calculate_fscore's convention (utils/f1_metric.py:14-28) with cloud
+ *   1 as its `gt` and cloud 2 as its `pr`: precision = (float)hits1 * (1.0f / (float)cnt1), recall = (float)hits2 *
+ *   (1.0f / (float)cnt2) (the rounding of torch's float32 mean of the 0/1 flags, which multiplies the sum by the reciprocal
+ *   of the length: the columns equal metrics.fscore_batch's bit for bit; a plain division differs from it in the last bit
+ *   for some pairs, 15 / 129 for one), fscore = 2 * recall * precision / (recall + precision) in float32, 0 when recall +
+ *   precision == 0, and
+ *   chamfer = (float)(sum d1 / cnt1 + sum d2 / cnt2).  If either count is 0: fscore = precision = recall = 0 (what
+ *   calculate_fscore returns for an empty cloud) and chamfer = NaN (the mean of nothing).  One workgroup per cloud, a fixed
+ *   reduction order: bit-equal from run to run.
+ * ---------------------------------------------------------------------- */
+int ct_chamfer_fwd_counts(const float* xyz1, const float* xyz2, const int32_t* cnt1, const int32_t* cnt2, float* dist1,
+                          float* dist2, int32_t* idx1, int32_t* idx2, int B, int n, int m, ct_stream_t s);
+int ct_chamfer_bwd_counts(const float* xyz1, const float* xyz2, const int32_t* cnt1, const int32_t* cnt2, const float* g_dist1,
+                          const float* g_dist2, const int32_t* idx1, const int32_t* idx2, float* g_xyz1, float* g_xyz2,
+                          int B, int n, int m, ct_stream_t s);
+int ct_rows_compact(const float* x, float* y, int32_t* count, int B, int n, ct_stream_t s);
+int ct_chamfer_metrics(const float* dist1, const float* dist2, const int32_t* cnt1, const int32_t* cnt2, float th, double* stats,
+                       float* table, int B, int n, int m, ct_stream_t s);
 
 /* ------------------------------------------------------------------------
  * Approximate EMD by auction (emd_linear/emd.cpp:28-31 `forward`, `backward`;
