@@ -46,6 +46,15 @@ class BnBwdItem(ctypes.Structure):
                 ("relu", ctypes.c_int)]
 
 
+class BnEvalBwdItem(ctypes.Structure):
+    """ct_bn_eval_bwd_item (include/cloudct.h)."""
+    _fields_ = [("x", ctypes.c_void_p), ("x_batch_stride", ctypes.c_longlong), ("weight", ctypes.c_void_p), ("bias", ctypes.c_void_p),
+                ("running_mean", ctypes.c_void_p), ("running_var", ctypes.c_void_p), ("gy", ctypes.c_void_p),
+                ("gy_batch_stride", ctypes.c_longlong), ("gx", ctypes.c_void_p), ("gx_batch_stride", ctypes.c_longlong),
+                ("g_weight", ctypes.c_void_p), ("g_bias", ctypes.c_void_p), ("amax_out", ctypes.c_void_p), ("C", ctypes.c_int),
+                ("eps", ctypes.c_float), ("relu", ctypes.c_int)]
+
+
 class AdainFwdItem(ctypes.Structure):
     """ct_adain_fwd_item (include/cloudct.h)."""
     _fields_ = [("x", ctypes.c_void_p), ("x_batch_stride", ctypes.c_longlong), ("gamma_beta", ctypes.c_void_p),
@@ -281,6 +290,7 @@ SIGNATURES = {
     "ct_bn_group_apply_bwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ct_bn_eval_supported": (_i, [_i, _i, _i]),
     "ct_bn_eval_group_fwd": (_i, [_vp, _i, _i, _i, _vp]),
+    "ct_bn_eval_group_bwd": (_i, [_vp, _i, _i, _i, _vp]),
     "ct_gconv_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _ip, _vp]),
     "ct_gconv_bwd_data": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _ip, _vp]),
     "ct_gconv_supported": (_i, [_i, _i, _i, _i, _i, _ip]),

@@ -927,3 +927,185 @@ extern "C" int ct_bn_eval_group_fwd(const ct_bn_fwd_item* items, int n, int B, i
   CT_CHECK_LAUNCH();
   return CT_OK;
 }
+
+// ---- backward of the eval-mode norm: frozen statistics with gradients ----
+// With rs = 1 / sqrt(running_var_c + eps), xh = (x - running_mean_c) * rs and o = xh * weight_c + bias_c (bn_eval_one's
+// expression, contraction off, so `o > 0` is exactly "the forward stored a positive value"):
+//   g' = (relu && !(o > 0)) ? 0 : gy,   gx = g' * (weight_c * rs),   g_bias_c = sum g',   g_weight_c = sum g' * xh
+// The statistics are constants, so gx does not wait for the sums: ONE pass reads x and gy, writes gx and carries the two
+// sums and max |gx| along (the training backward needs the sums before it can write the first gx).
+//
+// Decomposition, per item: an item that asks for neither the sums nor the maxima is a pure stream and is cut over
+// workgroups the way the forward cuts a channel without maxima (towards kEvalBwdTargetWgs workgroups).  An item that asks for either keeps ONE workgroup per
+// channel, as the training backward does: a thread adds its elements in loop order, the waves fold by shuffles, the
+// workgroup folds the waves' values from LDS in wave order (block_sum / block_max) — no float atomics, no partials in
+// memory (this ABI passes no workspace), and an order fixed by (B, N) and the item's own addressability alone.  That is why
+// the float4 / scalar choice is made per ITEM here and not per launch: a norm gives the same bits alone and inside a table,
+// whatever the alignment of its neighbours.
+struct BnEvalBwdItem {
+  const float* x;
+  const float* weight;
+  const float* bias;
+  const float* mean;
+  const float* var;
+  const float* gy;
+  float* gx;         // nullable: the input needs no gradient
+  float* g_weight;   // nullable together with g_bias: the affine parameters are frozen
+  float* g_bias;
+  float* amax_out;   // nullable: max |gx| per channel
+  long long xbs, gybs, gxbs;
+  int C, relu, split, vec;
+  float eps;
+};
+struct BnEvalBwdTable {
+  int n, B, N;
+  int wstart[kBnMaxItems + 1];   // first workgroup of every item (C * split workgroups each)
+  BnEvalBwdItem item[kBnMaxItems];
+};
+
+// workgroups a launch of pure streams is cut towards: one round of 2 resident per CU x 256 CUs.  (Half the forward's target:
+// three tensors per element; at 512 channels B8 N4096 the forward's cut in two measured 41.8 us against 37.4 us uncut.)
+constexpr int kEvalBwdTargetWgs = 512;
+
+// one element: masks gy, adds to the two sums, returns gx
+__device__ __forceinline__ float bn_eval_bwd_one(float x, float gy, float mu, float rs, float w, float be, float gfw, int relu,
+                                                 float& g, float& gxh) {
+  const float xh = (x - mu) * rs;
+  const float o = xh * w + be;
+  g = (relu && !(o > 0.0f)) ? 0.0f : gy;
+  gxh = g * xh;
+  return g * gfw;
+}
+
+template <bool VEC>
+__device__ __forceinline__ void bn_eval_bwd_body(const BnEvalBwdItem& a, int B, int N, int c, int part, float (*red)[kWaves]) {
+  const unsigned total = (unsigned)chan_items<VEC>(B, N);
+  const unsigned run = (total + (unsigned)a.split - 1u) / (unsigned)a.split;
+  const unsigned lo = (unsigned)part * run;
+  const unsigned hi = lo + run < total ? lo + run : total;
+  const float mu = a.mean[c], rs = 1.0f / sqrtf(a.var[c] + a.eps), w = a.weight[c], be = a.bias[c];
+  const float gfw = w * rs;
+  const float* __restrict__ x = a.x;
+  const float* __restrict__ gy = a.gy;
+  float* __restrict__ gx = a.gx;
+  float s[2] = {0.f, 0.f};
+  float am = 0.f;
+  for (unsigned base = lo + threadIdx.x; base < hi; base += kEvalUnroll * kThreads) {
+    if (VEC) {
+      float4 v[kEvalUnroll], g[kEvalUnroll];
+#pragma unroll
+      for (int k = 0; k < kEvalUnroll; ++k) {
+        const unsigned e = base + k * kThreads;
+        if (e < hi) {
+          v[k] = *reinterpret_cast<const float4*>(x + item_offset<true>((int)e, N, c, a.xbs));
+          g[k] = *reinterpret_cast<const float4*>(gy + item_offset<true>((int)e, N, c, a.gybs));
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < kEvalUnroll; ++k) {
+        const unsigned e = base + k * kThreads;
+        if (e < hi) {
+          float g0, g1, g2, g3, h0, h1, h2, h3;
+          float4 o;
+          o.x = bn_eval_bwd_one(v[k].x, g[k].x, mu, rs, w, be, gfw, a.relu, g0, h0);
+          o.y = bn_eval_bwd_one(v[k].y, g[k].y, mu, rs, w, be, gfw, a.relu, g1, h1);
+          o.z = bn_eval_bwd_one(v[k].z, g[k].z, mu, rs, w, be, gfw, a.relu, g2, h2);
+          o.w = bn_eval_bwd_one(v[k].w, g[k].w, mu, rs, w, be, gfw, a.relu, g3, h3);
+          s[0] += (g0 + g1) + (g2 + g3);
+          s[1] += (h0 + h1) + (h2 + h3);
+          if (gx) *reinterpret_cast<float4*>(gx + item_offset<true>((int)e, N, c, a.gxbs)) = o;
+          am = fmaxf(fmaxf(am, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+        }
+      }
+    } else {
+      float v[kEvalUnroll], g[kEvalUnroll];
+#pragma unroll
+      for (int k = 0; k < kEvalUnroll; ++k) {
+        const unsigned e = base + k * kThreads;
+        if (e < hi) {
+          v[k] = x[item_offset<false>((int)e, N, c, a.xbs)];
+          g[k] = gy[item_offset<false>((int)e, N, c, a.gybs)];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < kEvalUnroll; ++k) {
+        const unsigned e = base + k * kThreads;
+        if (e < hi) {
+          float g0, h0;
+          const float o = bn_eval_bwd_one(v[k], g[k], mu, rs, w, be, gfw, a.relu, g0, h0);
+          s[0] += g0;
+          s[1] += h0;
+          if (gx) gx[item_offset<false>((int)e, N, c, a.gxbs)] = o;
+          am = fmaxf(am, fabsf(o));
+        }
+      }
+    }
+  }
+  // (both uniform over the workgroup; either implies split == 1: this workgroup passed over the whole channel)
+  if (a.g_weight) {
+    block_sum<2>(s, red);
+    if (threadIdx.x == 0) {
+      a.g_bias[c] = s[0];
+      a.g_weight[c] = s[1];
+    }
+  }
+  if (a.amax_out) {
+    am = block_max(am, red);
+    if (threadIdx.x == 0) a.amax_out[c] = am;
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) bn_eval_bwd_kernel(BnEvalBwdTable t) {
+  __shared__ float red[2][kWaves];
+  int wg = blockIdx.x, i = 0;
+  while (i + 1 < t.n && wg >= t.wstart[i + 1]) ++i;
+  wg -= t.wstart[i];
+  const BnEvalBwdItem& a = t.item[i];
+  const int c = wg / a.split, part = wg - c * a.split;
+  if (a.vec) bn_eval_bwd_body<true>(a, t.B, t.N, c, part, red);
+  else bn_eval_bwd_body<false>(a, t.B, t.N, c, part, red);
+}
+
+extern "C" int ct_bn_eval_group_bwd(const ct_bn_eval_bwd_item* items, int n, int B, int N, ct_stream_t s) {
+  if (!items || n < 1 || n > kBnMaxItems) return CT_EINVAL;
+  BnEvalBwdTable t{};
+  t.n = n; t.B = B; t.N = N;
+  long long Ct = 0;
+  for (int i = 0; i < n; ++i) {
+    const ct_bn_eval_bwd_item& it = items[i];
+    if (!it.x || !it.weight || !it.bias || !it.running_mean || !it.running_var || !it.gy || !(it.eps >= 0.0f)) return CT_EINVAL;
+    if ((it.g_weight == nullptr) != (it.g_bias == nullptr)) return CT_EINVAL;
+    if (!it.gx && !it.g_weight) return CT_EINVAL;                 // nothing asked for
+    if (!eval_shape_ok(B, it.C, N)) return CT_EINVAL;
+    BnEvalBwdItem& a = t.item[i];
+    a = BnEvalBwdItem{it.x, it.weight, it.bias, it.running_mean, it.running_var, it.gy, it.gx, it.g_weight, it.g_bias, it.amax_out,
+                      0, 0, 0, it.C, it.relu, 1, 0, it.eps};
+    if (!stride_ok(it.x_batch_stride, it.C, N, a.xbs) || !stride_ok(it.gy_batch_stride, it.C, N, a.gybs) ||
+        !stride_ok(it.gx_batch_stride, it.C, N, a.gxbs))
+      return CT_EINVAL;
+    a.vec = (N & 3) == 0 && ((a.xbs | a.gybs | a.gxbs) & 3) == 0 &&
+            ((((uintptr_t)a.x) | ((uintptr_t)a.gy) | ((uintptr_t)a.gx)) & 15) == 0;
+    Ct += it.C;
+  }
+  // pure streams are cut as the forward cuts them, towards kEvalBwdTargetWgs workgroups, never below kEvalMinPerThread a thread
+  long long split = (kEvalBwdTargetWgs + Ct - 1) / Ct;
+  long long w0 = 0;
+  for (int i = 0; i < n; ++i) {
+    BnEvalBwdItem& a = t.item[i];
+    const long long per = a.vec ? (long long)B * (N >> 2) : (long long)B * N;
+    long long cut = split;
+    const long long most = per / ((long long)kThreads * kEvalMinPerThread);
+    if (cut > most) cut = most;
+    if (cut < 1 || a.g_weight || a.amax_out) cut = 1;
+    a.split = (int)cut;
+    t.wstart[i] = (int)w0;
+    w0 += (long long)a.C * a.split;
+    if (w0 > 0x7fffffffLL) return CT_EINVAL;
+  }
+  t.wstart[n] = (int)w0;
+  hipStream_t stream = (hipStream_t)s;
+  CT_CLEAR_ERROR();
+  hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3((unsigned)w0), dim3(kThreads), 0, stream, t);
+  CT_CHECK_LAUNCH();
+  return CT_OK;
+}

@@ -7,6 +7,9 @@ package's layers and checkpoints stay interchangeable.
   `model.generator` (a python file defining `Model`; the remaining `model.*` keys are its kwargs),
   `train.{optimizer,scheduler,num_epochs,save_each,...}`, optional `restore.{generator,optimizer,new_lr}`; `train.deterministic:
   true` (this package's own key) runs `fit` in deterministic mode (determinism.py): equal seeds, equal gradients.
+  `train.freeze_norms: true` (optionally `train.freeze_norm_affine: true`; this package's own keys) fine-tunes on frozen
+  norm statistics (norms.py `freeze_norms`, applied after the data-parallel wrap): the running statistics never move, no
+  statistics are exchanged between ranks, validation and checkpoints are unchanged.
 * checkpoints: `<exp>/<name>_<epoch_name>_<n>.t7` holding a plain `state_dict()` (train_util.py:74-80); parameter names of
   this package's modules equal the reference's, so released weights load with `strict=True`; `restore_exp_fix` drops the
   `module.` prefix DistributedDataParallel adds (train_util.py:98-117).
@@ -318,6 +321,17 @@ class Trainer:
         if "restore" in cfg and "generator" in cfg["restore"]:
             restore_exp_fix([model], [cfg["restore"]["generator"]], device=self.device, verbose=self.rank == 0)
         self._stream = None
+        tr = cfg["train"]
+        freeze, freeze_affine = bool(tr.get("freeze_norms", False)), bool(tr.get("freeze_norm_affine", False))
+        if freeze_affine and not freeze:
+            raise ValueError("train.freeze_norm_affine needs train.freeze_norms: true")
+        if freeze and freeze_affine and parallel._active(dist):
+            # DistributedDataParallel fixes the set of parameters it reduces when it is built: the norms' weight and bias stop
+            # taking gradients before the wrap (the conversion to SyncBatchNorm keeps the Parameter objects and their flags)
+            for m in model.modules():
+                if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.affine:
+                    m.weight.requires_grad_(False)
+                    m.bias.requires_grad_(False)
         if parallel._active(dist):
             if self.device.type == "cuda":
                 # DDP's gradient hooks (and its bucketed all-reduce) run on the stream the wrapper was BUILT on: the training
@@ -329,8 +343,12 @@ class Trainer:
                     model = parallel.data_parallel(model, self.device.index)
             else:
                 model = parallel.data_parallel(model, None)
+        if freeze:
+            # after the conversion to SyncBatchNorm (which builds new modules and would drop the marks) and the wrap: every norm
+            # in eval mode on its stored statistics, also through fit's model.train() — no statistics, no exchange of them
+            from .norms import freeze_norms
+            freeze_norms(model, affine=freeze_affine)
         self.model = model
-        tr = cfg["train"]
         if "scale_lr" in tr:      # the learnable residual scales of the AdaIN blocks get their own rate
             named = list(model.named_parameters())
             params = [{"params": [p for n, p in named if not n.endswith("scale")]},

@@ -63,8 +63,9 @@ def run_after(module_list, input, residual=None):
     added in the same pass when that pair ends the stack (an nn.SyncBatchNorm too: ops exchanges the group's statistics
     over its process group); the same pair in eval mode runs as ct_bn_eval_group_fwd where autograd records nothing
     (ops.bn_eval_eligible), and a bias-free PointwiseConv1d in front of such a pair takes the pair into its GEMM's epilogue
-    (ops.pw_norm_eligible: ct_pw_gemm_rs_norm) — an eval forward with gradients and every other layer go through their own
-    forward."""
+    (ops.pw_norm_eligible: ct_pw_gemm_rs_norm); an eval pair whose norm freeze_norms marked runs as ops.bn_frozen where
+    gradients are recorded (the projection in front of it through its own function) — an unmarked eval forward with
+    gradients and every other layer go through their own forward."""
     layers = list(module_list)
     i = 0
     while i < len(layers):
@@ -84,6 +85,13 @@ def run_after(module_list, input, residual=None):
                     and residual.dtype == input.dtype)
         if pair and not layer.training and ops.bn_eval_eligible(layer, input, residual=residual if fuse_res else None):
             input = ops.bn_eval(input, layer, relu=True, residual=residual if fuse_res else None)
+            if fuse_res:
+                residual = None
+            i += 2
+        elif (pair and not layer.training and ops.bn_frozen_eligible(layer, input, residual=residual if fuse_res else None)
+              and ops.records_gradients(input, layer.weight, layer.bias, residual if fuse_res else None)):
+            # a norm marked by freeze_norms, with gradients: the same forward launch and ct_bn_eval_group_bwd
+            input = ops.bn_frozen(input, layer, relu=True, residual=residual if fuse_res else None)
             if fuse_res:
                 residual = None
             i += 2
@@ -142,8 +150,8 @@ class _MHCTCore(nn.Module):
 
     def _norm_keys_values(self, key_values):
         """key_bn on the first 3H channels, values_bn on the rest (multihead_ct.py:89-91): fused kernels on the slices
-        where they lie when both norms qualify (training: ops.split_bn; eval without gradients: ops.split_bn_eval), the
-        modules on split views otherwise."""
+        where they lie when both norms qualify (training: ops.split_bn; eval without gradients: ops.split_bn_eval; frozen
+        with gradients: ops.split_bn_frozen), the modules on split views otherwise."""
         Ck = self.heads * 3
         Cv = key_values.size(1) - Ck
         if (ops.bn_relu_eligible(self.key_bn, key_values, Ck) and ops.bn_relu_eligible(self.values_bn, key_values, Cv)
@@ -152,6 +160,11 @@ class _MHCTCore(nn.Module):
         if (not self.key_bn.training and ops.bn_eval_eligible(self.key_bn, key_values, Ck)
                 and ops.bn_eval_eligible(self.values_bn, key_values, Cv)):
             return ops.split_bn_eval(key_values, self.key_bn, self.values_bn)
+        if (not self.key_bn.training and not self.values_bn.training and ops.bn_frozen_eligible(self.key_bn, key_values, Ck)
+                and ops.bn_frozen_eligible(self.values_bn, key_values, Cv)
+                and ops.records_gradients(key_values, self.key_bn.weight, self.key_bn.bias, self.values_bn.weight,
+                                          self.values_bn.bias)):
+            return ops.split_bn_frozen(key_values, self.key_bn, self.values_bn)      # marked by freeze_norms, with gradients
         k_part, v_part = torch.split(key_values, [Ck, Cv], dim=1)   # backward: one cat
         return self.key_bn(k_part), self.values_bn(v_part)
 
@@ -395,6 +408,17 @@ class MultiHeadUnion(_UnionBase):
                       tensor_size=w, tensor_dim=d, heads=h, scales=scales)
             for f, w, d, h in zip(features_dims, tensor_sizes, tensor_dims, heads)])
 
+    def _shortcut(self, x):
+        """shortcut(x); a projected shortcut whose norm freeze_norms marked runs that norm as ops.bn_frozen (no ReLU) where
+        gradients are recorded."""
+        sc = self.shortcut
+        if len(sc) == 2 and isinstance(sc[1], nn.modules.batchnorm._BatchNorm) and not sc[1].training and ops.norm_frozen(sc[1]):
+            y = sc[0](x)
+            if ops.bn_frozen_eligible(sc[1], y) and ops.records_gradients(y, sc[1].weight, sc[1].bias):
+                return ops.bn_frozen(y, sc[1], relu=False)
+            return sc[1](y)
+        return sc(x)
+
     def forward(self, x, orig_pcd):
         x = self.prenorm(x)
         pres, stats = [], []
@@ -411,8 +435,15 @@ class MultiHeadUnion(_UnionBase):
                 residual, kvs = self.shortcut(x), ops.union_keys_values(x, convs, kbs, vbs)
         elif ops.union_keys_values_eval_eligible(x, convs, kbs, vbs):      # eval, nothing recorded: same stacking, forward only
             residual, kvs = self.shortcut(x), ops.union_keys_values_eval(x, convs, kbs, vbs)
+        elif (not any(bn.training for bn in kbs + vbs) and ops.union_keys_values_frozen_eligible(x, convs, kbs, vbs)
+              and ops.records_gradients(x, *[c.weight for c in convs], *[p for bn in kbs + vbs for p in (bn.weight, bn.bias)])):
+            # norms marked by freeze_norms, with gradients: the training path's stacking on the stored statistics
+            if SKIP_IN_DGRAD and len(self.shortcut) == 0 and x.requires_grad and torch.is_grad_enabled():
+                residual, kvs = ops.union_keys_values_frozen(x, convs, kbs, vbs, passthrough=True)
+            else:
+                residual, kvs = self._shortcut(x), ops.union_keys_values_frozen(x, convs, kbs, vbs)
         else:
-            residual, kvs = self.shortcut(x), None
+            residual, kvs = self._shortcut(x), None
         for r, s, _ in _run_heads([(lambda a=a, i=i: a._forward_pre(x, orig_pcd, None if kvs is None else kvs[i]))
                                    for i, a in enumerate(self.attentions)], x):
             pres.append(r)
@@ -425,6 +456,10 @@ class MultiHeadUnion(_UnionBase):
         elif len(pres) > 1 and all(len(n) == 2 and type(n[1]) is nn.ReLU and not n[0].training and ops.bn_eval_eligible(n[0], p)
                                    for n, p in zip(norms, pres)):
             joined = ops.join_bn_relu_eval(pres, [n[0] for n in norms])
+        elif (len(pres) > 1 and all(len(n) == 2 and type(n[1]) is nn.ReLU and not n[0].training and ops.bn_frozen_eligible(n[0], p)
+                                    for n, p in zip(norms, pres))
+              and ops.records_gradients(*pres, *[p for n in norms for p in (n[0].weight, n[0].bias)])):
+            joined = ops.join_bn_relu_frozen(pres, [n[0] for n in norms])      # marked by freeze_norms, with gradients
         else:
             joined = torch.cat([run_after(n, p) for n, p in zip(norms, pres)], dim=1)
         return run_after(self.after, joined, residual), stats

@@ -1517,7 +1517,8 @@ def bn_relu(x, bn, relu=True, residual=None):
 # eval-mode BatchNorm1d / SyncBatchNorm (+ ReLU, + skip): a per-channel affine on the stored statistics (ct_bn_eval_*)
 # ---------------------------------------------------------------------------
 # Forward only, on purpose: plain functions that save nothing, taken only where autograd would record nothing.  An eval
-# forward WITH gradients keeps the modules' own path.  "0": every eval norm through its module (A/B runs).
+# forward WITH gradients keeps the modules' own path (norms marked by freeze_norms: the frozen section below).  "0": every
+# eval norm through its module (A/B runs).
 BN_EVAL = os.environ.get("CLOUDCT_BN_EVAL", "1") != "0"
 _bn_eval_supported = {}
 
@@ -1676,6 +1677,375 @@ def union_keys_values_eval(x, convs, key_bns, values_bns):
     assert c0 == Ct, "key_bn + values_bn must cover the projections"
     with _on(x.device):
         _bn_eval_group(items, B, N)
+    return [(outs[2 * i], outs[2 * i + 1]) for i in range(len(convs))]
+
+
+# ---------------------------------------------------------------------------
+# frozen norms: eval-mode statistics in a forward that records gradients (ct_bn_eval_group_fwd / ct_bn_eval_group_bwd)
+# ---------------------------------------------------------------------------
+# Only norms marked by cloud_transformers_amd.freeze_norms take these (an unmarked eval norm with gradients keeps its
+# module's path).  The forwards are the eval functions' launches — same items, same maxima tags — and save the norm's
+# INPUT (x, or the stacked GEMM output), never y: the backward recomputes the ReLU mask from it.  "0": marked norms through
+# their modules (A/B runs).
+BN_FROZEN = os.environ.get("CLOUDCT_BN_FROZEN", "1") != "0"
+
+
+def norm_frozen(bn):
+    """True for a norm marked by freeze_norms (norms.py)."""
+    return bool(getattr(bn, "_ct_frozen", False))
+
+
+def records_gradients(*tensors):
+    """True when autograd would record an op on `tensors` (None entries skipped): the other half of a frozen norm's routing
+    rule — where nothing is recorded the eval functions above take the norm, marked or not."""
+    return not _records_nothing(*tensors)
+
+
+def bn_frozen_eligible(bn, x, channels=None, residual=None):
+    """bn_eval_eligible without its "nothing to record" clause, for a norm that freeze_norms marked: an nn.BatchNorm1d /
+    nn.SyncBatchNorm (exactly) in eval mode, affine, with running statistics; x CUDA fp32 [B,C,N] contiguous and 16-byte
+    aligned; a shape ct_bn_eval_supported takes."""
+    if not (BN_FROZEN and norm_frozen(bn) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()
+            and x.data_ptr() % 16 == 0):
+        return False
+    if residual is not None and not (residual.is_cuda and residual.dtype == torch.float32 and residual.dim() == 3):
+        return False
+    C = x.size(1) if channels is None else channels
+    return _bn_eval_norm_ok(bn, x.size(0), C, x.size(2)) and bn.weight.device == x.device
+
+
+def union_keys_values_frozen_eligible(x, convs, key_bns, values_bns):
+    """union_keys_values_eval_eligible without its "nothing to record" clause, every norm marked by freeze_norms."""
+    if not (BN_FROZEN and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()
+            and x.data_ptr() % 16 == 0 and len(convs) > 1):
+        return False
+    for conv, kb, vb in zip(convs, key_bns, values_bns):
+        if not (isinstance(conv, torch.nn.Conv1d) and conv.kernel_size == (1,) and conv.stride == (1,) and conv.padding == (0,)
+                and conv.dilation == (1,) and conv.groups == 1 and conv.bias is None and conv.in_channels == x.size(1)
+                and conv.out_channels == kb.num_features + vb.num_features and conv.weight.dtype == torch.float32
+                and conv.weight.device == x.device):
+            return False
+        for bn in (kb, vb):
+            if not (norm_frozen(bn) and _bn_eval_norm_ok(bn, x.size(0), bn.num_features, x.size(2))
+                    and bn.weight.device == x.device):
+                return False
+    return True
+
+
+def _bn_eval_bwd_table(items):
+    """ct_bn_eval_bwd_item array.  items: dicts with x (data_ptr), xbs, C, w, b, rm, rv, eps, relu, gy (ptr), gybs, gx (ptr or
+    None), gxbs and, optionally, gw / gb (tensors: both or neither) and amax (ptr)."""
+    arr = (_lib.BnEvalBwdItem * len(items))()
+    for e, it in zip(arr, items):
+        e.x, e.x_batch_stride, e.weight, e.bias = it["x"], it["xbs"], _ptr(it["w"]), _ptr(it["b"])
+        e.running_mean, e.running_var, e.gy, e.gy_batch_stride = _ptr(it["rm"]), _ptr(it["rv"]), it["gy"], it["gybs"]
+        e.gx, e.gx_batch_stride, e.g_weight, e.g_bias = it["gx"], it["gxbs"], _ptr(it.get("gw")), _ptr(it.get("gb"))
+        e.amax_out, e.C, e.eps, e.relu = it.get("amax"), it["C"], float(it["eps"]), int(it["relu"])
+    return arr
+
+
+def _bn_eval_group_bwd(items, B, N):
+    """Backward of _bn_eval_group over the same runs (ct_bn_eval_group_bwd); items: _bn_eval_bwd_table dicts.  An item that
+    asks for nothing (no gx, no sums) is left out."""
+    items = [it for it in items if it["gx"] is not None or it.get("gw") is not None]
+    if not items:
+        return
+    lib = _lib.load()
+    arr = _bn_eval_bwd_table(items)
+    for first, run in _bn_runs(len(items)):
+        _lib.check(lib.ct_bn_eval_group_bwd(_at(arr, first), run, B, N, _stream()), "ct_bn_eval_group_bwd")
+
+
+def _frozen_sums(C, device, need):
+    """(g_weight, g_bias) buffers of a frozen norm, or (None, None) when neither parameter takes a gradient."""
+    if not need:
+        return None, None
+    return torch.empty(C, device=device, dtype=torch.float32), torch.empty(C, device=device, dtype=torch.float32)
+
+
+def _cotangent(gy, B, C, N, device):
+    """(tensor, batch stride) of a cotangent the kernels can read where it lies; None -> zeros."""
+    if gy is None:
+        gy = torch.zeros(B, C, N, device=device, dtype=torch.float32)
+    gybs = _batch_stride(gy, C, N)
+    if gybs is None:
+        gy, gybs = _f32c(gy), 0
+    return gy, gybs
+
+
+class BnFrozenFn(torch.autograd.Function):
+    """relu?(bn(x)) [+ residual] on the norm's running statistics, with gradients: bn_eval's launch forward,
+    ct_bn_eval_group_bwd backward.  The running statistics are read, never written."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, eps, relu, residual):
+        _dev(x, weight, bias, residual)
+        x, weight, bias = _f32c(x), _f32c(weight), _f32c(bias)
+        running_mean, running_var = _f32c(running_mean), _f32c(running_var)
+        B, C, N = x.shape
+        y = torch.empty_like(x)
+        rbs = 0
+        if residual is not None:
+            rbs = _batch_stride(residual, C, N)
+            if rbs is None:
+                residual, rbs = _f32c(residual), 0
+        slots = _amax_slots(C, x.device)
+        with _on(x.device):
+            _bn_eval_group([dict(x=_ptr(x), xbs=0, C=C, w=weight, b=bias, rm=running_mean, rv=running_var, eps=float(eps),
+                                 relu=int(bool(relu)), res=_ptr(residual), rbs=rbs, y=_ptr(y), ybs=0, amax=_ptr(slots))], B, N)
+        tag_amax(y, slots)
+        ctx.save_for_backward(x, weight, bias, running_mean, running_var)
+        ctx.eps, ctx.relu, ctx.has_residual = float(eps), int(bool(relu)), residual is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, weight, bias, rm, rv = ctx.saved_tensors
+        B, C, N = x.shape
+        need_x, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        gy, gybs = _cotangent(gy, B, C, N, x.device)
+        gx = torch.empty_like(x) if need_x else None
+        slots = _amax_slots(C, x.device) if need_x else None
+        g_w, g_b = _frozen_sums(C, x.device, need_p)
+        with _on(x.device):
+            _bn_eval_group_bwd([dict(x=_ptr(x), xbs=0, C=C, w=weight, b=bias, rm=rm, rv=rv, eps=ctx.eps, relu=ctx.relu, gy=_ptr(gy),
+                                     gybs=gybs, gx=_ptr(gx), gxbs=0, gw=g_w, gb=g_b, amax=_ptr(slots))], B, N)
+        if gx is not None:
+            tag_amax(gx, slots)
+        return (gx, g_w if ctx.needs_input_grad[1] else None, g_b if ctx.needs_input_grad[2] else None, None, None, None, None,
+                gy if ctx.has_residual and ctx.needs_input_grad[7] else None)
+
+
+def bn_frozen(x, bn, relu=True, residual=None):
+    """relu?(bn(x)) [+ residual] of a frozen norm with gradients; the caller checked bn_frozen_eligible(bn, x,
+    residual=residual)."""
+    return BnFrozenFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, relu, residual)
+
+
+class SplitBnFrozenFn(torch.autograd.Function):
+    """(bn_a(x[:, :Ca]), bn_b(x[:, Ca:])) of two frozen norms: split_bn_eval's launch forward; the backward writes both input
+    cotangents into the halves of ONE [B,C,N] tensor (SplitBnFn's layout)."""
+
+    @staticmethod
+    def forward(ctx, x, wa, ba, rma, rva, epsa, wb, bb, rmb, rvb, epsb):
+        _dev(x, wa, wb)
+        x = _f32c(x)
+        B, C, N = x.shape
+        Ca = wa.numel()
+        assert wb.numel() == C - Ca
+        items, outs, saved = [], [], []
+        for c0, w, b, rm, rv, eps in ((0, wa, ba, rma, rva, epsa), (Ca, wb, bb, rmb, rvb, epsb)):
+            w, b, rm, rv = _f32c(w), _f32c(b), _f32c(rm), _f32c(rv)
+            y = torch.empty(B, w.numel(), N, device=x.device, dtype=torch.float32)
+            items.append(dict(x=_ptr(x) + c0 * N * 4, xbs=C * N, C=w.numel(), w=w, b=b, rm=rm, rv=rv, eps=float(eps), relu=0,
+                              res=None, rbs=0, y=_ptr(y), ybs=0, amax=None))
+            outs.append(y)
+            saved += [w, b, rm, rv]
+        with _on(x.device):
+            _bn_eval_group(items, B, N)
+        ctx.save_for_backward(x, *saved)
+        ctx.eps = (float(epsa), float(epsb))
+        return outs[0], outs[1]
+
+    @staticmethod
+    def backward(ctx, ga, gb):
+        x = ctx.saved_tensors[0]
+        saved = ctx.saved_tensors[1:]
+        B, C, N = x.shape
+        need_x = ctx.needs_input_grad[0]
+        gx = torch.empty_like(x) if need_x else None
+        items, grads, c0 = [], [gx], 0
+        for i, gy in enumerate((ga, gb)):
+            w, b, rm, rv = saved[i * 4:(i + 1) * 4]
+            Cs = w.numel()
+            gy, gybs = _cotangent(gy, B, Cs, N, x.device)
+            need_w, need_b = ctx.needs_input_grad[1 + 5 * i], ctx.needs_input_grad[2 + 5 * i]
+            g_w, g_b = _frozen_sums(Cs, x.device, need_w or need_b)
+            items.append(dict(x=_ptr(x) + c0 * N * 4, xbs=C * N, C=Cs, w=w, b=b, rm=rm, rv=rv, eps=ctx.eps[i], relu=0, gy=_ptr(gy),
+                              gybs=gybs, gx=None if gx is None else _ptr(gx) + c0 * N * 4, gxbs=C * N, gw=g_w, gb=g_b, keep=gy))
+            grads += [g_w if need_w else None, g_b if need_b else None, None, None, None]
+            c0 += Cs
+        with _on(x.device):
+            _bn_eval_group_bwd(items, B, N)
+        return tuple(grads)
+
+
+def split_bn_frozen(x, bn_a, bn_b):
+    """(bn_a(x[:, :Ca]), bn_b(x[:, Ca:])) of two frozen norms with gradients; the caller checked bn_frozen_eligible for both
+    (each against its own slice's channels)."""
+    return SplitBnFrozenFn.apply(x, bn_a.weight, bn_a.bias, bn_a.running_mean, bn_a.running_var, bn_a.eps,
+                                 bn_b.weight, bn_b.bias, bn_b.running_mean, bn_b.running_var, bn_b.eps)
+
+
+class JoinBnReluFrozenFn(torch.autograd.Function):
+    """cat([relu(bn_i(x_i)) for i], dim=1) of frozen norms: join_bn_relu_eval's launch forward; every norm's backward reads
+    its range of the cotangent where it lies.  Arguments: n, then per head (x, weight, bias, running_mean, running_var, eps)."""
+
+    PER_HEAD = 6
+
+    @staticmethod
+    def forward(ctx, n, *args):
+        P = JoinBnReluFrozenFn.PER_HEAD
+        heads = [args[i * P:(i + 1) * P] for i in range(n)]
+        xs = [_f32c(h[0]) for h in heads]
+        _dev(*xs)
+        B, _, N = xs[0].shape
+        Ct = sum(x.size(1) for x in xs)
+        y = torch.empty(B, Ct, N, device=xs[0].device, dtype=torch.float32)
+        slots = _amax_slots(Ct, y.device)
+        items, saved, c0 = [], [], 0
+        for x, (_, w, b, rm, rv, eps) in zip(xs, heads):
+            C = x.size(1)
+            w, b, rm, rv = _f32c(w), _f32c(b), _f32c(rm), _f32c(rv)
+            items.append(dict(x=_ptr(x), xbs=0, C=C, w=w, b=b, rm=rm, rv=rv, eps=float(eps), relu=1, res=None, rbs=0,
+                              y=_ptr(y) + c0 * N * 4, ybs=Ct * N, amax=None if slots is None else _ptr(slots) + 4 * c0))
+            saved += [x, w, b, rm, rv]
+            c0 += C
+        with _on(y.device):
+            _bn_eval_group(items, B, N)
+        tag_amax(y, slots)
+        ctx.save_for_backward(*saved)
+        ctx.n = n
+        ctx.eps = [float(h[5]) for h in heads]
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        P = JoinBnReluFrozenFn.PER_HEAD
+        saved = ctx.saved_tensors
+        B, Ct, N = gy.shape
+        gybs = _batch_stride(gy, Ct, N)
+        if gybs is None:
+            gy, gybs = _f32c(gy), Ct * N
+        items, grads, tags, c0 = [], [None], [], 0
+        for i in range(ctx.n):
+            x, w, b, rm, rv = saved[i * 5:(i + 1) * 5]
+            C = x.size(1)
+            need_x, need_w, need_b = ctx.needs_input_grad[1 + P * i:4 + P * i]
+            gx = torch.empty_like(x) if need_x else None
+            slots = _amax_slots(C, x.device) if need_x else None
+            g_w, g_b = _frozen_sums(C, x.device, need_w or need_b)
+            items.append(dict(x=_ptr(x), xbs=0, C=C, w=w, b=b, rm=rm, rv=rv, eps=ctx.eps[i], relu=1, gy=_ptr(gy) + c0 * N * 4,
+                              gybs=gybs, gx=_ptr(gx), gxbs=0, gw=g_w, gb=g_b, amax=_ptr(slots)))
+            tags.append((gx, slots))
+            grads += [gx, g_w if need_w else None, g_b if need_b else None, None, None, None]
+            c0 += C
+        with _on(gy.device):
+            _bn_eval_group_bwd(items, B, N)
+        for gx, slots in tags:
+            if gx is not None:
+                tag_amax(gx, slots)
+        return tuple(grads)
+
+
+def join_bn_relu_frozen(xs, bns):
+    """cat([relu(bn(x)) for x, bn in zip(xs, bns)], dim=1) of frozen norms with gradients; the caller checked
+    bn_frozen_eligible for every pair."""
+    args = []
+    for x, bn in zip(xs, bns):
+        args += [x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps]
+    return JoinBnReluFrozenFn.apply(len(xs), *args)
+
+
+class UnionKeysValuesFrozenFn(torch.autograd.Function):
+    """UnionKeysValuesFn for frozen norms: ONE stacked forward GEMM, the 2n norms on its channel ranges in one eval launch;
+    backward: the norms' input cotangents into the ranges of ONE tensor with its maxima slots (ct_bn_eval_group_bwd), one data
+    gradient GEMM (the identity shortcut's cotangent in its epilogue) and one weight gradient GEMM.  No statistics, so no
+    collective under SyncBatchNorm.  Arguments: n (< 0: passthrough, as UnionKeysValuesFn), x, then per head: weight [Co,Cin,1],
+    key_bn (w, b, rm, rv, eps), values_bn (same 5)."""
+
+    PER_HEAD = 11
+
+    @staticmethod
+    def forward(ctx, n, x, *args):
+        ctx.passthrough = n < 0
+        n = abs(n)
+        P = UnionKeysValuesFrozenFn.PER_HEAD
+        heads = [args[i * P:(i + 1) * P] for i in range(n)]
+        x_in = x
+        x = _f32c(x)
+        _dev(x)
+        B, Cin, N = x.shape
+        Wc = torch.cat([h[0][:, :, 0] for h in heads], dim=0)               # [sum Co, Cin]
+        Ct = Wc.size(0)
+        y, am_w, am_x, Wt = pw_forward(Wc, x, ctx.needs_input_grad[1])      # [B, sum Co, N]
+        outs, items, saved, meta, c0 = [], [], [], [], 0
+        for h in heads:
+            for (w, b, rm, rv, eps) in (h[1:6], h[6:11]):
+                w, b, rm, rv = _f32c(w), _f32c(b), _f32c(rm), _f32c(rv)
+                C = w.numel()
+                o = torch.empty(B, C, N, device=x.device, dtype=torch.float32)
+                items.append(dict(x=_ptr(y) + c0 * N * 4, xbs=Ct * N, C=C, w=w, b=b, rm=rm, rv=rv, eps=float(eps), relu=0,
+                                  res=None, rbs=0, y=_ptr(o), ybs=0, amax=None))
+                outs.append(o)
+                saved += [w, b, rm, rv]
+                meta.append((c0, C, float(eps)))
+                c0 += C
+        assert c0 == Ct, "key_bn + values_bn must cover the projections"
+        with _on(x.device):
+            _bn_eval_group(items, B, N)
+        ctx.save_for_backward(x, y, Wc, *saved)
+        ctx.am = (am_w, am_x, Wt)
+        ctx.meta = meta
+        ctx.couts = [h[0].size(0) for h in heads]
+        if ctx.passthrough:
+            return (x_in,) + tuple(outs)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        P = UnionKeysValuesFrozenFn.PER_HEAD
+        g_skip = None
+        if ctx.passthrough:
+            g_skip, gouts = gouts[0], gouts[1:]
+        x, y, Wc = ctx.saved_tensors[:3]
+        saved = ctx.saved_tensors[3:]
+        B, Cin, N = x.shape
+        Ct = Wc.size(0)
+        need_x = ctx.needs_input_grad[1]
+        need_W = any(ctx.needs_input_grad[2 + P * h] for h in range(len(ctx.couts)))
+        g_y = torch.empty_like(y) if (need_x or need_W) else None
+        slots = _amax_slots(Ct, x.device) if g_y is not None else None
+        items, sums = [], []
+        for i, (c0, C, eps) in enumerate(ctx.meta):
+            w, b, rm, rv = saved[i * 4:(i + 1) * 4]
+            gy, gybs = _cotangent(gouts[i], B, C, N, x.device)
+            at = 2 + P * (i // 2) + 1 + 5 * (i % 2)                        # this norm's weight among the inputs
+            need_w, need_b = ctx.needs_input_grad[at], ctx.needs_input_grad[at + 1]
+            g_w, g_b = _frozen_sums(C, x.device, need_w or need_b)
+            sums.append((g_w if need_w else None, g_b if need_b else None))
+            items.append(dict(x=_ptr(y) + c0 * N * 4, xbs=Ct * N, C=C, w=w, b=b, rm=rm, rv=rv, eps=eps, relu=0, gy=_ptr(gy),
+                              gybs=gybs, gx=None if g_y is None else _ptr(g_y) + c0 * N * 4, gxbs=Ct * N, gw=g_w, gb=g_b, keep=gy,
+                              amax=None if slots is None else _ptr(slots) + 4 * c0))
+        with _on(x.device):
+            _bn_eval_group_bwd(items, B, N)
+        g_x = g_Wc = None
+        if g_y is not None:
+            g_x, g_Wc = pw_backward(Wc, x, g_y, ctx.am[0], ctx.am[1], need_x, need_W,
+                                    am_g=None if slots is None else slots.view(-1, g_y.shape[1]), Wt=ctx.am[2],
+                                    add_gx=g_skip if need_x else None)      # g_Wc [sum Co, Cin]
+        elif need_x:
+            g_x = g_skip
+        grads, r0 = [None, g_x], 0
+        for hi, Co in enumerate(ctx.couts):
+            (gwk, gbk), (gwv, gbv) = sums[2 * hi], sums[2 * hi + 1]
+            g_W = g_Wc[r0:r0 + Co].unsqueeze(-1) if (g_Wc is not None and ctx.needs_input_grad[2 + P * hi]) else None
+            grads += [g_W, gwk, gbk, None, None, None, gwv, gbv, None, None, None]
+            r0 += Co
+        return tuple(grads)
+
+
+def union_keys_values_frozen(x, convs, key_bns, values_bns, passthrough=False):
+    """union_keys_values for frozen norms with gradients (UnionKeysValuesFrozenFn); the caller checked
+    union_keys_values_frozen_eligible.  passthrough as union_keys_values."""
+    args = []
+    for conv, kb, vb in zip(convs, key_bns, values_bns):
+        args.append(conv.weight)
+        for bn in (kb, vb):
+            args += [bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps]
+    outs = UnionKeysValuesFrozenFn.apply(-len(convs) if passthrough else len(convs), x, *args)
+    if passthrough:
+        return outs[0], [(outs[1 + 2 * i], outs[2 + 2 * i]) for i in range(len(convs))]
     return [(outs[2 * i], outs[2 * i + 1]) for i in range(len(convs))]
 
 

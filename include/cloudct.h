@@ -45,7 +45,7 @@ extern "C" {
  * subsampling ct_voxel_bounds / ct_voxel_keys / ct_voxel_reduce and their workspace queries; then the resident ShapeNet
  * completion gather ct_completion_gather; then the deterministic switch ct_set_deterministic / ct_get_deterministic / ct_deterministic_override;
  * then Chamfer with per-cloud counts and the metric table: ct_chamfer_fwd_counts / ct_chamfer_bwd_counts / ct_rows_compact /
- * ct_chamfer_metrics.) */
+ * ct_chamfer_metrics; then the backward of the eval-mode norm, ct_bn_eval_group_bwd.) */
 #define CT_ABI_VERSION 3
 
 /* status codes */
@@ -404,6 +404,32 @@ int ct_bn_group_apply_bwd(const ct_bn_bwd_item* items, int n, int first, int run
  * momentum and num_batches_tracked are ignored and may be null.  Added under CT_ABI_VERSION 2 (additive). */
 int ct_bn_eval_supported(int B, int C, int N);
 int ct_bn_eval_group_fwd(const ct_bn_fwd_item* items, int n, int B, int N, ct_stream_t s);
+/* Backward of ct_bn_eval_group_fwd: a norm whose statistics are frozen, in a forward that records gradients.  1 <= n <= 8
+ * norms over the same (B, N) in one launch.  Per element, contraction off, with rs = 1.0f / sqrtf(running_var[c] + eps) and
+ * xh = (x - running_mean[c]) * rs:
+ *   o = xh * weight[c] + bias[c]            (the forward's expression: with relu != 0 an element passes only if the forward
+ *                                            stored a positive value for it)
+ *   g' = (relu && !(o > 0)) ? 0 : gy,   gx = g' * (weight[c] * rs),   g_bias[c] = sum g',   g_weight[c] = sum g' * xh
+ * The cotangent of the forward's residual is gy itself and needs no kernel work.  x, gy, gx and their batch strides as
+ * ct_bn_eval_group_fwd's x and y (0 = contiguous; a channel slice of a wider tensor is read, a channel range of one cotangent
+ * tensor written, where it lies); gx overlaps neither x nor gy.  Rows of an item that are 16-byte addressable (N % 4 == 0,
+ * strides % 4 == 0, aligned bases) move as float4, all others float by float — decided per item, so a norm gives the same
+ * bits alone and inside a table.  g_weight and g_bias f32[C] are given both or neither (neither: the affine parameters are
+ * frozen); gx may be null (the input needs no gradient); a call asks for at least one of gx and the pair.  amax_out f32[C]
+ * (nullable): max |gx| per channel as stored, the contract of ct_bn_group_bwd's (with a null gx: of the values it would have
+ * stored).  weight, bias, running_mean, running_var, x and gy are always required and read-only.  No workspace, no
+ * allocation, no float atomics: an item that asks for the sums or the maxima keeps one workgroup per channel and adds in an
+ * order fixed by (B, N) and its own addressability, so results are bit-equal from run to run; an item that asks for neither
+ * is cut over workgroups as the forward is.  CT_EINVAL, before anything is launched, for a null required pointer, n outside
+ * [1, 8], a batch stride that is neither 0 nor >= C*N, eps < 0 (or NaN), C < 1, B*N outside [1, 2^31), or only one of
+ * g_weight / g_bias.  Added under CT_ABI_VERSION 3 (additive: the loader's missing-symbol scan checks it). */
+typedef struct {
+  const float* x; long long x_batch_stride; const float* weight; const float* bias;
+  const float* running_mean; const float* running_var;
+  const float* gy; long long gy_batch_stride; float* gx; long long gx_batch_stride;
+  float* g_weight; float* g_bias; float* amax_out; int C; float eps; int relu;
+} ct_bn_eval_bwd_item;
+int ct_bn_eval_group_bwd(const ct_bn_eval_bwd_item* items, int n, int B, int N, ct_stream_t s);
 
 /* ------------------------------------------------------------------------
  * Adaptive instance normalisation of the AdaIN blocks (AdaIn1dUpd: layers/utils.py:82-97 =
