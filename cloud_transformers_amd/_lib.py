@@ -329,6 +329,10 @@ SIGNATURES = {
     "ct_pw_gemm_rs_add": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _sz, _i, _i, _i, _i, _vp]),
     "ct_pw_gemm_norm_amax_len": (_i, [_i, _i, _i]),
     "ct_pw_gemm_rs_norm": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "ct_slice_fwd_norm_amax_len": (_i, [_i, _i, _i, _i, _i, _ip]),
+    "ct_slice_fwd_norm": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _ip, _vp]),
+    "ct_mhct_core_fwd_norm_amax_len": (_i, [_i, _i, _i, _i, _i, _ip]),
+    "ct_mhct_core_fwd_norm": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _ip, _vp]),
     "ct_amax_rows_f32": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "ct_pw_prep_weight_rs": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "ct_nbr_index_workspace_bytes": (_sz, [ctypes.c_int64, _ip]),

@@ -149,6 +149,49 @@ __device__ __forceinline__ void st_stream4(float* p, float4 v) {
 }
 __device__ __forceinline__ float ld_stream(const float* p) { return __builtin_nontemporal_load(p); }
 
+// ---- the NORM epilogue of the Slice write-outs (ct_slice_fwd_norm: ct_raster.hip; ct_mhct_core_fwd_norm: ct_mhct.hip) ----
+// Eval-mode BatchNorm (+ ReLU) on the value a gather would have stored.  A workgroup leaves one record per channel of its
+// chunk in LDS — (mean, 1 / sqrt(var + eps), weight, bias), computed once — and applies bn_eval_one's operation sequence
+// (ct_bnorm.hip; contraction is off for the whole library, and the mean is subtracted first: no folded scale / shift) at its
+// stores: the bits of the plain gather followed by ct_bn_eval_group_fwd.
+__device__ __forceinline__ float4 ct_norm_record(float mean, float var, float eps, float weight, float bias) {
+  return make_float4(mean, 1.0f / sqrtf(var + eps), weight, bias);
+}
+// A record read back from LDS: the channel is the same for every lane of the wave, so the four values move to scalar registers —
+// the epilogue then costs the gather kernels no vector registers beside their own (held in vector registers the records of a
+// four-channel group pushed gather_ci_kernel past its 128: 20-36 bytes of scratch).
+__device__ __forceinline__ float ct_uniform(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
+__device__ __forceinline__ float4 ct_norm_uniform(const float4 r) {
+  return make_float4(ct_uniform(r.x), ct_uniform(r.y), ct_uniform(r.z), ct_uniform(r.w));
+}
+__device__ __forceinline__ float ct_norm_one(float v, const float4 r, int relu) {
+  const float o = ((v - r.x) * r.y) * r.z + r.w;
+  return relu ? fmaxf(o, 0.0f) : o;
+}
+// four values of one channel (r: its record, through ct_norm_uniform); am = max(am, |stored values|)
+__device__ __forceinline__ float4 ct_norm_four(float4 v, const float4 r, int relu, float& am) {
+  float4 o;
+  o.x = ct_norm_one(v.x, r, relu); o.y = ct_norm_one(v.y, r, relu); o.z = ct_norm_one(v.z, r, relu); o.w = ct_norm_one(v.w, r, relu);
+  am = fmaxf(fmaxf(am, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+  return o;
+}
+// max of `am` over the workgroup -> *slot, the workgroup's own partial maximum (a plain store: no atomics, nothing to zero; a
+// workgroup without points stores 0).  `red`: 16 floats of LDS nobody reads any more once every thread has arrived here.
+// Called by all threads of the workgroup; slot is block-uniform (null: no maxima asked for).
+__device__ __forceinline__ void ct_norm_fold_amax(float am, float* red, float* slot) {
+  if (slot == nullptr) return;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) am = fmaxf(am, __shfl_xor(am, o, 64));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = am;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int nw = (int)(blockDim.x + 63) >> 6;
+    for (int i = 1; i < nw; ++i) am = fmaxf(am, red[i]);
+    *slot = am;
+  }
+}
+
 // Launch tags (test hooks, host state): every entry point that picks among kernel families calls note_reset() on entry and
 // note("family") for each kernel it launches; ct_debug_last_launch() returns the tags joined with '+'.  Defined once, in
 // ct_raster.hip (the library is linked from one object per source); internal to the library.

@@ -62,6 +62,17 @@ struct CoreArgs {
   int planes, xcd_map;
   int spin_limit;        // polls before a workgroup gives up on its partners (kSpinLimit; tests shorten it)
   int fault;             // test hook: the last workgroup of plane 0 arrives late (its partners time out)
+  // NORM (ct_mhct_core_fwd_norm): the eval-mode norm of channel h*C + c in the Slice write-out.  `out` is then the first row of a
+  // [B, Ct, N] tensor's channel range — the row of (cloud b, channel c) at out + b*out_bstride + c*N — and amax receives one
+  // partial maximum of |stored value| per workgroup (null: none)
+  size_t out_bstride;
+  const float* norm_weight;
+  const float* norm_bias;
+  const float* norm_mean;
+  const float* norm_var;
+  float* amax;
+  float norm_eps;
+  int norm_relu;
 };
 
 template <int DIM, int WT, int C>
@@ -291,7 +302,12 @@ __device__ __forceinline__ void core_conv_block(const float* Zin, const float* w
 }
 
 // grid = (planes * S)
-template <int DIM, int WT, int C, bool HAS_PAD>
+// NORM (ct_mhct_core_fwd_norm): the Slice write-out applies the eval-mode norm of the output channel to the value it would have
+// stored (ct_common.h: the bits of the plain kernel followed by ct_bn_eval_group_fwd), at the strides of a wider output tensor;
+// the 16 records of a block of output channels lie in the filter bank's LDS, which is dead between a block's convolution and
+// the next one's; one partial maximum per workgroup.  A timed-out cluster still writes NaN, un-normed (a ReLU would turn the
+// marker into 0), and NaN into its slot of the maxima.
+template <int DIM, int WT, int C, bool HAS_PAD, bool NORM = false>
 __global__ void __launch_bounds__(kCoreThreads) mhct_core_fwd_kernel(CoreArgs a) {
   using Gm = CoreGeom<DIM, WT, C>;
   constexpr int V = Gm::V, G = Gm::G, PLANE = Gm::PLANE, HS = Gm::HS, KB = Gm::KB;
@@ -472,7 +488,10 @@ __global__ void __launch_bounds__(kCoreThreads) mhct_core_fwd_kernel(CoreArgs a)
       if (a.y_save != nullptr && sn == 0)
         for (int t = tid; t < (16 * G) >> 2; t += kCoreThreads) *(float4*)(a.y_save + (bh * C + co0) * (size_t)G + ((size_t)t << 2)) = bad;
       for (int c = 0; c < 16; ++c)
-        for (int qd = qa0 + tid; qd < qa1; qd += kCoreThreads) *(float4*)(a.out + (bh * C + co0 + c) * (size_t)N + ((size_t)qd << 2)) = bad;
+        for (int qd = qa0 + tid; qd < qa1; qd += kCoreThreads) {
+          if constexpr (NORM) *(float4*)(a.out + (size_t)b * a.out_bstride + ((size_t)h * C + co0 + c) * (size_t)N + ((size_t)qd << 2)) = bad;
+          else *(float4*)(a.out + (bh * C + co0 + c) * (size_t)N + ((size_t)qd << 2)) = bad;
+        }
     }
   }
   if (!aborted && (a.z_save != nullptr || a.occ != nullptr)) {
@@ -495,17 +514,27 @@ __global__ void __launch_bounds__(kCoreThreads) mhct_core_fwd_kernel(CoreArgs a)
   // ---- B + C per block of 16 output channels
   const int nmt = aborted ? 0 : (C / 16) / a.SC;
   const float* wh = a.w + (size_t)h * C * C * Gm::TAPS;
+  float am = 0.0f;                               // NORM: max |stored value| of this thread
+  const float4* rec = (const float4*)WS;         // NORM: the records of the block's 16 output channels
   for (int mi = 0; mi < nmt; ++mi) {
     const int co0 = (sc * nmt + mi) * 16;
     core_conv_block<DIM, WT, C, false>(Zf, wh, co0, a.bias != nullptr ? a.bias + (size_t)h * C + co0 : nullptr, WS, Y4,
                                        (a.y_save != nullptr && sn == 0) ? a.y_save + (bh * C + co0) * (size_t)G : nullptr);
+    if constexpr (NORM) {
+      // (the bank is consumed: the block's last barrier is behind us; the next block's first one follows the gather)
+      if (tid < 16) {
+        const int c = h * C + co0 + tid;
+        ((float4*)WS)[tid] = ct_norm_record(a.norm_mean[c], a.norm_var[c], a.norm_eps, a.norm_weight[c], a.norm_bias[c]);
+      }
+      __syncthreads();
+    }
 
     CT_STAMP(5 + 2 * mi);
     // ---- C: gather this block's 16 channels for the workgroup's point range
     {
       const int per = (nq + a.SN - 1) / a.SN;
       const int q0 = sn * per, q1 = min(nq, q0 + per);
-      float* dst = a.out + (bh * C + co0) * (size_t)N;
+      float* dst = NORM ? a.out + (size_t)b * a.out_bstride + ((size_t)h * C + co0) * (size_t)N : a.out + (bh * C + co0) * (size_t)N;
       for (int qd = q0 + tid; qd < ((CT_CORE_ABL & 4) ? 0 : q1); qd += kCoreThreads) {
         const int n0 = qd << 2;
         float kk[DIM][4];
@@ -549,12 +578,22 @@ __global__ void __launch_bounds__(kCoreThreads) mhct_core_fwd_kernel(CoreArgs a)
             asm volatile("" : "+v"(o[0][i]), "+v"(o[1][i]), "+v"(o[2][i]), "+v"(o[3][i]));
           }
 #pragma unroll
-          for (int cj = 0; cj < 4; ++cj)
-            st_stream4(dst + (size_t)(cq * 4 + cj) * N + n0, make_float4(o[cj][0], o[cj][1], o[cj][2], o[cj][3]));
+          for (int cj = 0; cj < 4; ++cj) {
+            float4 ov = make_float4(o[cj][0], o[cj][1], o[cj][2], o[cj][3]);
+            // (the record moves to scalar registers here, not at the head of the group: this kernel's scalar registers are
+            //  full, and sixteen more held across the gather spill into vector registers — 2D 70-77 -> 78-84 of them)
+            if constexpr (NORM) ov = ct_norm_four(ov, ct_norm_uniform(rec[cq * 4 + cj]), a.norm_relu, am);
+            st_stream4(dst + (size_t)(cq * 4 + cj) * N + n0, ov);
+          }
         }
       }
     }
     CT_STAMP(6 + 2 * mi);
+  }
+  if constexpr (NORM) {
+    // the workgroup's partial maximum (slot = its index in the launch); the fold overlays the dead bank behind the records
+    ct_norm_fold_amax(am, WS + 64, a.amax != nullptr ? a.amax + blockIdx.x : nullptr);
+    if (aborted && a.amax != nullptr && tid == 0) a.amax[blockIdx.x] = __builtin_nanf("");
   }
   // ---- occupancy: sum over all workgroups, written (and the words zeroed for the next launch) by the last one to arrive.
   //      Relaxed device-scope atomics — they execute at the memory side, in this lane's program order: the sum's add has
@@ -1078,23 +1117,54 @@ size_t core_ws_layout(int planes, int S, int C, int G, size_t& flags_off, size_t
 #endif
 }
 
-template <int DIM, int WT, int C>
+template <int DIM, int WT, int C, bool NORM>
 int launch_core(CoreArgs a, hipStream_t st) {
   using Gm = CoreGeom<DIM, WT, C>;
   const dim3 grid(a.planes * a.S);
   if (a.pad_dtype != CT_PAD_NONE) {
-    auto k = mhct_core_fwd_kernel<DIM, WT, C, true>;
+    auto k = mhct_core_fwd_kernel<DIM, WT, C, true, NORM>;
     if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Gm::LDS_BYTES) != hipSuccess) return CT_ELAUNCH;
     CT_CLEAR_ERROR();
     hipLaunchKernelGGL(k, grid, dim3(kCoreThreads), Gm::LDS_BYTES, st, a);
   } else {
-    auto k = mhct_core_fwd_kernel<DIM, WT, C, false>;
+    auto k = mhct_core_fwd_kernel<DIM, WT, C, false, NORM>;
     if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Gm::LDS_BYTES) != hipSuccess) return CT_ELAUNCH;
     CT_CLEAR_ERROR();
     hipLaunchKernelGGL(k, grid, dim3(kCoreThreads), Gm::LDS_BYTES, st, a);
   }
   CT_CHECK_LAUNCH();
   return CT_OK;
+}
+
+// ct_mhct_core_fwd and ct_mhct_core_fwd_norm: `out` is the plain output, or the norm's y with its stride, parameters and maxima
+// already in `a`
+template <bool NORM>
+int core_fwd(CoreArgs a, const float* keys, const float* feat, const void* pad, int pad_dtype, const float* conv_w, const float* conv_b,
+             float* out, float* z_save, float* y_save, int64_t* occ_count, void* workspace, size_t workspace_bytes, int B, int H,
+             int C, int N, int dim, const int* W, hipStream_t st) {
+  a.keys = keys; a.feat = feat; a.pad = pad; a.pad_dtype = pad_dtype; a.w = conv_w; a.bias = conv_b;
+  a.out = out; a.z_save = z_save; a.y_save = y_save; a.occ = (long long*)occ_count;
+  a.B = B; a.H = H; a.N = N; a.planes = B * H;
+  core_split(a.planes, C, N, kCoreShapes[core_shape_index(C, dim, W)].cu_div, a.S, a.SC, a.SN);
+  a.xcd_map = (a.planes % 8 == 0) ? 1 : 0;
+  {
+    const unsigned dbg = g_core_flags.load(std::memory_order_relaxed);
+    a.fault = (dbg & 2u) ? 1 : 0;                  // ct_debug_set_core bit 1: fault injection (tests of the abort path)
+    a.spin_limit = a.fault ? 256 : kSpinLimit;
+  }
+  int G = 1;
+  for (int j = 0; j < dim; ++j) G *= W[j];
+  size_t fo, so;
+  const size_t need = core_ws_layout(a.planes, a.S, C, G, fo, so);
+  if (!workspace || workspace_bytes < need) return CT_EWORKSPACE;
+  a.xch = (float*)workspace;
+  a.flags = (unsigned*)((char*)workspace + fo);
+  a.status = (int*)((char*)workspace + so);
+  a.stamps = (unsigned long long*)((char*)workspace + so + 16);
+  const int idx = core_shape_index(C, dim, W);
+  if (idx == 0) return launch_core<2, 32, 16, NORM>(a, st);
+  if (idx == 1) return launch_core<2, 16, 16, NORM>(a, st);
+  return launch_core<3, 8, 32, NORM>(a, st);
 }
 
 }  // namespace
@@ -1124,31 +1194,40 @@ int ct_mhct_core_fwd(const float* keys, const float* feat, const void* pad, int 
   if (!keys || !feat || !conv_w || !out || !ct_mhct_core_supported(B, H, C, N, dim, W)) return CT_EINVAL;
   if (pad_dtype != CT_PAD_NONE && !pad) return CT_EINVAL;
   if (((((uintptr_t)keys) | ((uintptr_t)feat) | ((uintptr_t)out) | ((uintptr_t)z_save) | ((uintptr_t)y_save)) & 15) != 0) return CT_EINVAL;
-  hipStream_t st = (hipStream_t)s;
-  CoreArgs a;
-  a.keys = keys; a.feat = feat; a.pad = pad; a.pad_dtype = pad_dtype; a.w = conv_w; a.bias = conv_b;
-  a.out = out; a.z_save = z_save; a.y_save = y_save; a.occ = (long long*)occ_count;
-  a.B = B; a.H = H; a.N = N; a.planes = B * H;
-  core_split(a.planes, C, N, kCoreShapes[core_shape_index(C, dim, W)].cu_div, a.S, a.SC, a.SN);
-  a.xcd_map = (a.planes % 8 == 0) ? 1 : 0;
-  {
-    const unsigned dbg = g_core_flags.load(std::memory_order_relaxed);
-    a.fault = (dbg & 2u) ? 1 : 0;                  // ct_debug_set_core bit 1: fault injection (tests of the abort path)
-    a.spin_limit = a.fault ? 256 : kSpinLimit;
-  }
-  int G = 1;
-  for (int j = 0; j < dim; ++j) G *= W[j];
-  size_t fo, so;
-  const size_t need = core_ws_layout(a.planes, a.S, C, G, fo, so);
-  if (!workspace || workspace_bytes < need) return CT_EWORKSPACE;
-  a.xch = (float*)workspace;
-  a.flags = (unsigned*)((char*)workspace + fo);
-  a.status = (int*)((char*)workspace + so);
-  a.stamps = (unsigned long long*)((char*)workspace + so + 16);
-  const int idx = core_shape_index(C, dim, W);
-  if (idx == 0) return launch_core<2, 32, 16>(a, st);
-  if (idx == 1) return launch_core<2, 16, 16>(a, st);
-  return launch_core<3, 8, 32>(a, st);
+  return core_fwd<false>(CoreArgs{}, keys, feat, pad, pad_dtype, conv_w, conv_b, out, z_save, y_save, occ_count, workspace,
+                         workspace_bytes, B, H, C, N, dim, W, (hipStream_t)s);
+}
+
+// partial maxima ct_mhct_core_fwd_norm writes: one per workgroup (planes x cluster size under the current ct_debug_set_core
+// flags); 0 where a GEMM could not fold that many or the shape is not built
+int ct_mhct_core_fwd_norm_amax_len(int B, int H, int C, int N, int dim, const int* W) {
+  if (!ct_mhct_core_supported(B, H, C, N, dim, W)) return 0;
+  int S, SC, SN;
+  core_split(B * H, C, N, kCoreShapes[core_shape_index(C, dim, W)].cu_div, S, SC, SN);
+  const long long n = (long long)B * H * S;
+  return n <= 32768 ? (int)n : 0;
+}
+
+// ct_mhct_core_fwd with the eval-mode norm of the sliced value in the store: include/cloudct.h
+int ct_mhct_core_fwd_norm(const float* keys, const float* feat, const void* pad, int pad_dtype, const float* conv_w,
+                          const float* conv_b, const ct_bn_fwd_item* norm, float* amax_out, float* z_save, float* y_save,
+                          int64_t* occ_count, void* workspace, size_t workspace_bytes, int B, int H, int C, int N, int dim,
+                          const int* W, ct_stream_t s) {
+  if (!keys || !feat || !conv_w || !norm || !ct_mhct_core_supported(B, H, C, N, dim, W)) return CT_EINVAL;
+  if (pad_dtype != CT_PAD_NONE && !pad) return CT_EINVAL;
+  if (!norm->y || !norm->weight || !norm->bias || !norm->running_mean || !norm->running_var || !(norm->eps >= 0.0f)) return CT_EINVAL;
+  if (norm->residual || norm->amax_out || (long long)norm->C != (long long)H * C) return CT_EINVAL;
+  const long long dense = (long long)H * C * N;
+  const long long ybs = norm->y_batch_stride ? norm->y_batch_stride : dense;
+  if (ybs < dense || (ybs & 3) != 0) return CT_EINVAL;      // (rows move as float4)
+  if (((((uintptr_t)keys) | ((uintptr_t)feat) | ((uintptr_t)norm->y) | ((uintptr_t)z_save) | ((uintptr_t)y_save)) & 15) != 0) return CT_EINVAL;
+  if (amax_out && (((uintptr_t)amax_out & 3) != 0 || ct_mhct_core_fwd_norm_amax_len(B, H, C, N, dim, W) == 0)) return CT_EINVAL;
+  CoreArgs a{};
+  a.out_bstride = (size_t)ybs;
+  a.norm_weight = norm->weight; a.norm_bias = norm->bias; a.norm_mean = norm->running_mean; a.norm_var = norm->running_var;
+  a.norm_eps = norm->eps; a.norm_relu = norm->relu; a.amax = amax_out;
+  return core_fwd<true>(a, keys, feat, pad, pad_dtype, conv_w, conv_b, norm->y, z_save, y_save, occ_count, workspace, workspace_bytes,
+                        B, H, C, N, dim, W, (hipStream_t)s);
 }
 
 size_t ct_mhct_core_bwd_workspace_bytes(int B, int H, int C, int N, int dim, const int* W) {

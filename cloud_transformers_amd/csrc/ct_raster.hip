@@ -679,8 +679,11 @@ __global__ void __launch_bounds__(1024, CT_FXREG_WAVES) scatter_add_fx_reg_kerne
 //   Slice forward; also the g_feat half of Splat(sum) backward.
 //   grid = (nchunks * nsplit, H, B)
 // ---------------------------------------------------------------------------
-template <int DIM, bool FROM_KEYS, bool LDS_TILE>
-__global__ void __launch_bounds__(1024, DIM == 2 ? 8 : 4) gather_kernel(RasterArgs a, GridW<DIM> g) {
+//   NORM (ct_slice_fwd_norm): the eval-mode norm of channel h*C + c applied to the value in the store, rows at the strides of
+//   a wider output tensor, one partial maximum per workgroup (ct_raster_args.h); the parameter records lie behind the tile
+//   (from the start of LDS where the tile stays in memory).
+template <int DIM, bool FROM_KEYS, bool LDS_TILE, bool NORM = false>
+__global__ void __launch_bounds__(1024, DIM == 2 ? 8 : 4) gather_kernel(GatherArgs<NORM> a, GridW<DIM> g) {
   constexpr int V = 1 << DIM;
   extern __shared__ __align__(16) float lds[];
   const BlockXHB blk = block_xhb();
@@ -691,13 +694,19 @@ __global__ void __launch_bounds__(1024, DIM == 2 ? 8 : 4) gather_kernel(RasterAr
   const int cc = min(a.CC, a.C - c0);
   const float* gin = a.tile_in + (bh * a.C + c0) * (size_t)g.G;
   const float* T = LDS_TILE ? lds : gin;
+  float4* rec = (float4*)(lds + (LDS_TILE ? (((size_t)a.CC * g.G + 3) & ~(size_t)3) : 0));
+  if constexpr (NORM) {
+    norm_stage_records(rec, a, h * a.C + c0, cc);
+    if (!LDS_TILE) __syncthreads();
+  }
   if (LDS_TILE) {
     stage_tile(lds, gin, cc * g.G);
     __syncthreads();
   }
   const int per = (a.N + a.nsplit - 1) / a.nsplit;
   const int n_beg = sp * per, n_end = min(a.N, n_beg + per);
-  float* dst = a.dst + (bh * a.C + c0) * (size_t)a.N;
+  float* dst = gather_dst<NORM>(a, b, h, c0, a.N);
+  float am = 0.0f;
   for (int n = n_beg + threadIdx.x; n < n_end; n += blockDim.x) {
     Corners<DIM> c;
     PointPos<DIM, FROM_KEYS> pp;
@@ -710,9 +719,14 @@ __global__ void __launch_bounds__(1024, DIM == 2 ? 8 : 4) gather_kernel(RasterAr
 #pragma unroll
       for (int v = 1; v < V; ++v) acc += Tc[c.cell[v]] * c.w[v];
       if (has_pad) acc = acc * p;
+      if constexpr (NORM) {
+        acc = norm_one(acc, rec[ch], a.norm_relu);
+        am = fmaxf(am, fabsf(acc));
+      }
       dst[(size_t)ch * a.N + n] = acc;
     }
   }
+  if constexpr (NORM) norm_store_amax(am, lds, a.amax);
 }
 
 // ---------------------------------------------------------------------------
@@ -870,8 +884,10 @@ __global__ void __launch_bounds__(1024, DIM == 2 ? 8 : 4) splat_max_bwd_kernel(R
 // ---------------------------------------------------------------------------
 enum { QM_GATHER = 0, QM_GATHER_GW = 1, QM_SPLAT_MAX_BWD = 2 };
 
-template <int DIM, int MODE, int CG, int THREADS, bool STATS, bool HAS_PAD>
-__global__ void __launch_bounds__(THREADS, THREADS == 1024 ? 4 : CT_QUAD_WAVES) quad_kernel(RasterArgs a, GridW<DIM> g) {
+//   NORM (QM_GATHER only, one chunk per workgroup): the NORM epilogue of gather_kernel, records behind the tile.
+template <int DIM, int MODE, int CG, int THREADS, bool STATS, bool HAS_PAD, bool NORM = false>
+__global__ void __launch_bounds__(THREADS, THREADS == 1024 ? 4 : CT_QUAD_WAVES) quad_kernel(GatherArgs<NORM> a, GridW<DIM> g) {
+  static_assert(!NORM || (MODE == QM_GATHER && !STATS), "the norm epilogue belongs to the pure gather");
   constexpr int V = 1 << DIM;
   constexpr bool kSrc = MODE != QM_GATHER;          // reads a point-sized input
   constexpr bool kDst = MODE != QM_GATHER_GW;       // writes a point-sized output
@@ -887,6 +903,8 @@ __global__ void __launch_bounds__(THREADS, THREADS == 1024 ? 4 : CT_QUAD_WAVES) 
   const int per = (nq + a.nsplit - 1) / a.nsplit;
   const int q_beg = sp * per, q_end = min(nq, q_beg + per);
   bool first = true;
+  float am = 0.0f;                                    // NORM: max |stored value| of this thread
+  float4* rec = (float4*)(lds + (size_t)a.CC * g.G);  // NORM: the chunk's parameter records (G % 4 == 0: 16-byte aligned)
   for (int chunk = cgi; chunk < a.nchunks; chunk += a.ncg) {
     const int c0 = chunk * a.CC;
     const int cc = min(a.CC, a.C - c0);
@@ -905,9 +923,12 @@ __global__ void __launch_bounds__(THREADS, THREADS == 1024 ? 4 : CT_QUAD_WAVES) 
     }
     stage_tile(T, a.tile_in + toff, cc * g.G);
     if (MODE == QM_SPLAT_MAX_BWD) stage_tile(T2, a.tile_in2 + toff, cc * g.G);
+    if constexpr (NORM) norm_stage_records(rec, a, h * a.C + c0, cc);
     __syncthreads();
     const float* src = kSrc ? a.src + (bh * a.C + c0) * (size_t)a.N : nullptr;
-    float* dst = kDst ? a.dst + (bh * a.C + c0) * (size_t)a.N : nullptr;
+    float* dst;
+    if constexpr (NORM) dst = gather_dst<true>(a, b, h, c0, a.N);
+    else dst = kDst ? a.dst + (bh * a.C + c0) * (size_t)a.N : nullptr;
     for (int q = q_beg + (int)threadIdx.x; q < q_end; q += blockDim.x) {
       const int n0 = q << 2;
       // corner weights and base cell of the 4 points (per-axis terms are recomputed
@@ -1052,8 +1073,13 @@ __global__ void __launch_bounds__(THREADS, THREADS == 1024 ? 4 : CT_QUAD_WAVES) 
         if (kDst) {
 #pragma unroll
           for (int cj = 0; cj < CG; ++cj)
-            if (cg0 + cj < cc)
-              *(float4*)(dst + (size_t)(cg0 + cj) * a.N + n0) = make_float4(fv[cj][0], fv[cj][1], fv[cj][2], fv[cj][3]);
+            if (cg0 + cj < cc) {
+              if constexpr (NORM)
+                *(float4*)(dst + (size_t)(cg0 + cj) * a.N + n0) =
+                    norm_four(make_float4(fv[cj][0], fv[cj][1], fv[cj][2], fv[cj][3]), rec[cg0 + cj], a.norm_relu, am);
+              else
+                *(float4*)(dst + (size_t)(cg0 + cj) * a.N + n0) = make_float4(fv[cj][0], fv[cj][1], fv[cj][2], fv[cj][3]);
+            }
         }
       }
       if (kGw) {
@@ -1135,6 +1161,7 @@ __global__ void __launch_bounds__(THREADS, THREADS == 1024 ? 4 : CT_QUAD_WAVES) 
     }
     first = false;
   }
+  if constexpr (NORM) norm_store_amax(am, lds, a.amax);
 }
 
 #include "ct_raster_hot.h"
@@ -1776,30 +1803,75 @@ LaunchForm launch_form(const Switches sw, size_t lds, int nq, HotForms forms) {
   return f;
 }
 
-// Slice forward / gather with the channel-interleaved tile.  CT_EINVAL: not eligible.
+// The pure gather (Slice forward, the g_feat half of Splat(sum) backward): which family takes a shape and how the launch is cut.
+// Pure arithmetic on the shape, the switches and the low bits of the pointers involved — run_gather launches from it, and
+// ct_slice_fwd_norm_amax_len counts the launch's workgroups (one partial maximum each) from the same description.
+enum GatherFamily { kGatherHot, kGatherQuad, kGatherGeneric };
+struct GatherPlan {
+  GatherFamily family;
+  int CC, nchunks, nsplit, threads;
+  size_t lds;          // the tile's bytes (a NORM launch adds its parameter records behind them)
+  bool lds_tile;
+  long long workgroups(int B, int H) const { return (long long)B * H * nchunks * nsplit; }
+};
+
+// hot_bits: keys | dst | tile_in (the channel-interleaved kernels' rows); quad_bits: those and whatever else the caller's
+// RasterArgs carries for the quad form (quad_ok)
 template <int DIM>
-int run_gather_hot(const Switches sw, RasterArgs a, const GridW<DIM>& g, hipStream_t st) {
-  const uintptr_t bits = (uintptr_t)a.pos.keys | (uintptr_t)a.dst | (uintptr_t)a.tile_in;
-  if (!hot_shape_ok(sw, a, g.G, bits)) return CT_EINVAL;
+GatherPlan gather_plan(const Switches sw, int B, int H, int C, int N, int G, bool from_keys, uintptr_t hot_bits, uintptr_t quad_bits) {
+  GatherPlan gp;
   HotPlan hp;
-  if (!hot_chunks(a.C, (size_t)g.G * 4, 0, hp)) return CT_EINVAL;
-  if constexpr (DIM == 3) {
-    // few planes: thinner chunks give more workgroups (the tile is staged once per chunk either way)
-    while ((long long)a.B * a.H * hp.nchunks < 256 && hp.CC > 4) {
-      hp.CC = ((hp.CC / 2) + 3) & ~3;
-      hp.nchunks = (a.C + hp.CC - 1) / hp.CC;
-      hp.lds = (size_t)hp.CC * g.G * 4;
+  if (from_keys && hot_shape_ok(sw, B, H, C, N, G, hot_bits) && hot_chunks(C, (size_t)G * 4, 0, hp)) {
+    if constexpr (DIM == 3) {
+      // few planes: thinner chunks give more workgroups (the tile is staged once per chunk either way)
+      while ((long long)B * H * hp.nchunks < 256 && hp.CC > 4) {
+        hp.CC = ((hp.CC / 2) + 3) & ~3;
+        hp.nchunks = (C + hp.CC - 1) / hp.CC;
+        hp.lds = (size_t)hp.CC * G * 4;
+      }
     }
+    gp.family = kGatherHot;
+    gp.CC = hp.CC; gp.nchunks = hp.nchunks; gp.lds = hp.lds; gp.lds_tile = true;
+    gp.nsplit = pick_nsplit(B, H, hp.nchunks, N, DIM);
+    gp.threads = hot_threads(((N >> 2) + gp.nsplit - 1) / gp.nsplit);
+    return gp;
   }
-  a.CC = hp.CC; a.nchunks = hp.nchunks; a.ncg = hp.nchunks;
-  a.nsplit = pick_nsplit(a.B, a.H, hp.nchunks, a.N, DIM);
-  const int nq = ((a.N >> 2) + a.nsplit - 1) / a.nsplit;
-  dim3 grid(hp.nchunks * a.nsplit, a.H, a.B);
+  const Plan p = make_plan(B, H, C, N, G, 1);
+  gp.CC = p.CC; gp.nchunks = p.nchunks; gp.lds = p.lds_bytes; gp.lds_tile = p.lds_tile;
+  gp.nsplit = pick_nsplit(B, H, p.nchunks, N, DIM);
+  // (3D exceeds the register budget of the quad form: generic kernel)
+  if (DIM == 2 && from_keys && p.lds_tile && (N & 3) == 0 && (quad_bits & 15) == 0 && (G & 3) == 0) {
+    gp.family = kGatherQuad;
+    gp.threads = quad_threads(N, gp.nsplit);
+  } else {
+    gp.family = kGatherGeneric;
+    gp.threads = round_threads((N + gp.nsplit - 1) / gp.nsplit);
+  }
+  return gp;
+}
+
+// LDS of a NORM launch: the tile, the chunk's parameter records (16 bytes a channel) behind it, and never less than the 16
+// words the fold of the partial maximum overlays on the tile
+constexpr int kNormAmaxMax = 32768;       // partial maxima a GEMM folds per operand (ct_pwgemm.hip: kPwAmaxMax)
+constexpr int kNormGlobalMaxC = 4096;     // channels per head where the tile stays in memory: the records of all of them take LDS
+size_t norm_lds(size_t tile_bytes, int CC) {
+  const size_t n = ((tile_bytes + 15) & ~(size_t)15) + (size_t)CC * 16;
+  return n < 64 ? 64 : n;
+}
+// a NORM launch names itself by its family's tag and this suffix — a modifier of every gather family, not a family of its own
+// (tests/test_slice_norm_gpu.py pins it per family)
+constexpr const char* kNormTag = "norm";
+
+// Slice forward / gather with the channel-interleaved tile
+template <int DIM, bool NORM>
+int run_gather_hot(const GatherPlan& gp, const GatherArgs<NORM>& a, const GridW<DIM>& g, hipStream_t st) {
+  dim3 grid(gp.nchunks * a.nsplit, a.H, a.B);
+  const size_t lds = NORM ? norm_lds(gp.lds, gp.CC) : gp.lds;
   const int r = with_hot_extent<DIM, false>(a, g, [&](auto pad, auto wt) {
     constexpr bool PAD = decltype(pad)::value;
     constexpr int WT = decltype(wt)::value;
-    if constexpr (DIM == 2) CT_LAUNCH((gather_ci_kernel<PAD, WT>), grid, hot_threads(nq), hp.lds, st, a, g);
-    else CT_LAUNCH((gather_ci3_kernel<PAD, WT>), grid, hot_threads(nq), hp.lds, st, a, g);
+    if constexpr (DIM == 2) CT_LAUNCH((gather_ci_kernel<PAD, WT, NORM>), grid, gp.threads, lds, st, a, g);
+    else CT_LAUNCH((gather_ci3_kernel<PAD, WT, NORM>), grid, gp.threads, lds, st, a, g);
     return CT_OK;
   });
   if (r != CT_OK) return r;
@@ -2326,29 +2398,52 @@ __global__ void __launch_bounds__(256) add_inplace_kernel(float* y, const float*
   if (i < n) y[i] += x[i];
 }
 
-template <int DIM, bool FROM_KEYS>
-int run_gather(const Switches sw, RasterArgs a, const int* W, hipStream_t st) {
+// NORM (ct_slice_fwd_norm; keys form only): the same plan — the output's batch stride enters the alignment tests beside its
+// pointer — and the family's NORM instantiation; the tag is the family's, then kNormTag
+template <int DIM, bool FROM_KEYS, bool NORM = false>
+int run_gather(const Switches sw, GatherArgs<NORM> a, const int* W, hipStream_t st) {
+  static_assert(FROM_KEYS || !NORM, "the norm epilogue is built for the keys form");
   GridW<DIM> g = make_grid<DIM>(W);
-  Plan p = make_plan(a.B, a.H, a.C, a.N, g.G, 1);
-  a.CC = p.CC;
-  a.nchunks = p.nchunks;
-  a.nsplit = pick_nsplit(a.B, a.H, p.nchunks, a.N, DIM);
-  int threads = round_threads((a.N + a.nsplit - 1) / a.nsplit);
-  dim3 grid(p.nchunks * a.nsplit, a.H, a.B);
+  uintptr_t hot_bits = (uintptr_t)a.pos.keys | (uintptr_t)a.dst | (uintptr_t)a.tile_in;
+  if constexpr (NORM) hot_bits |= (uintptr_t)(a.dst_bstride << 2);
+  const uintptr_t quad_bits = hot_bits | (uintptr_t)a.src | (uintptr_t)a.g_pos | (uintptr_t)a.tile_in2;
+  const GatherPlan gp = gather_plan<DIM>(sw, a.B, a.H, a.C, a.N, g.G, FROM_KEYS, hot_bits, quad_bits);
+  a.CC = gp.CC;
+  a.nchunks = gp.nchunks;
+  a.nsplit = gp.nsplit;
+  dim3 grid(gp.nchunks * a.nsplit, a.H, a.B);
   if constexpr (FROM_KEYS) {
-    const int r = run_gather_hot<DIM>(sw, a, g, st);
-    if (r != CT_EINVAL) return r;
-  }
-  if constexpr (DIM == 2) {   // 3D exceeds the register budget of the quad form: generic kernel
-    if (quad_ok(a, FROM_KEYS, p.lds_tile) && (g.G & 3) == 0) {
-      note("gather_quad");
-      a.ncg = p.nchunks;   // one chunk per workgroup
-      return launch_quad<2, QM_GATHER, CT_QUAD_CG, CT_QUAD_THREADS, false>(grid, quad_threads(a.N, a.nsplit), p.lds_bytes, st, a, g);
+    if (gp.family == kGatherHot) {
+      a.ncg = gp.nchunks;
+      const int r = run_gather_hot<DIM, NORM>(gp, a, g, st);
+      if (r == CT_OK && NORM) note(kNormTag);
+      return r;
     }
   }
-  if (p.lds_tile) CT_LAUNCH((gather_kernel<DIM, FROM_KEYS, true>), grid, threads, p.lds_bytes, st, a, g);
-  else CT_LAUNCH((gather_kernel<DIM, FROM_KEYS, false>), grid, threads, 0, st, a, g);
+  if constexpr (DIM == 2 && FROM_KEYS) {
+    if (gp.family == kGatherQuad) {
+      note("gather_quad");
+      a.ncg = gp.nchunks;   // one chunk per workgroup
+      if constexpr (NORM) {
+        const size_t lds = norm_lds(gp.lds, gp.CC);
+        if (a.pad_dtype != CT_PAD_NONE) CT_LAUNCH((quad_kernel<2, QM_GATHER, CT_QUAD_CG, CT_QUAD_THREADS, false, true, true>), grid, gp.threads, lds, st, a, g);
+        else CT_LAUNCH((quad_kernel<2, QM_GATHER, CT_QUAD_CG, CT_QUAD_THREADS, false, false, true>), grid, gp.threads, lds, st, a, g);
+        note(kNormTag);
+        return CT_OK;
+      } else {
+        return launch_quad<2, QM_GATHER, CT_QUAD_CG, CT_QUAD_THREADS, false>(grid, gp.threads, gp.lds, st, a, g);
+      }
+    }
+  }
+  if constexpr (NORM) {
+    if (gp.lds_tile) CT_LAUNCH((gather_kernel<DIM, FROM_KEYS, true, true>), grid, gp.threads, norm_lds(gp.lds, gp.CC), st, a, g);
+    else CT_LAUNCH((gather_kernel<DIM, FROM_KEYS, false, true>), grid, gp.threads, norm_lds(0, gp.CC), st, a, g);
+  } else {
+    if (gp.lds_tile) CT_LAUNCH((gather_kernel<DIM, FROM_KEYS, true>), grid, gp.threads, gp.lds, st, a, g);
+    else CT_LAUNCH((gather_kernel<DIM, FROM_KEYS, false>), grid, gp.threads, 0, st, a, g);
+  }
   note("gather_generic");
+  if (NORM) note(kNormTag);
   return CT_OK;
 }
 
@@ -3040,6 +3135,47 @@ int ct_grid_occupancy_ratio(const float* grid, int64_t n, float inv_denominator,
                      (unsigned long long*)workspace);
   CT_CHECK_LAUNCH();
   return CT_OK;
+}
+
+// (The norm entry points stand LAST in this file on purpose: a template is instantiated in the order of its first use, so the NORM
+//  kernels follow every kernel the file had before in the code object instead of sitting between the forward and the backward ones.)
+// partial maxima ct_slice_fwd_norm writes: one per workgroup of the launch run_gather plans for 16-byte aligned tensors under
+// the current switches; 0 where a GEMM could not fold that many (or the shape is refused)
+int ct_slice_fwd_norm_amax_len(int B, int H, int C, int N, int dim, const int* W) {
+  if (!valid_common(B, H, C, N, dim, W)) return 0;
+  const Switches sw = read_switches();
+  long long G = 1;
+  for (int j = 0; j < dim; ++j) G *= W[j];
+  const GatherPlan gp = dim == 2 ? gather_plan<2>(sw, B, H, C, N, (int)G, true, 0, 0) : gather_plan<3>(sw, B, H, C, N, (int)G, true, 0, 0);
+  if (!gp.lds_tile && C > kNormGlobalMaxC) return 0;
+  const long long n = gp.workgroups(B, H);
+  return n <= kNormAmaxMax ? (int)n : 0;
+}
+
+// Slice forward with the eval-mode norm of the sliced value in the store: include/cloudct.h
+int ct_slice_fwd_norm(const float* keys, const float* grid, const void* pad, int pad_dtype, const ct_bn_fwd_item* norm,
+                      float* amax_out, int B, int H, int C, int N, int dim, const int* W, ct_stream_t s) {
+  if (!keys || !grid || !norm || !valid_common(B, H, C, N, dim, W) || !valid_pad(pad, pad_dtype)) return CT_EINVAL;
+  if (!norm->y || !norm->weight || !norm->bias || !norm->running_mean || !norm->running_var || !(norm->eps >= 0.0f)) return CT_EINVAL;
+  if (norm->residual || norm->amax_out || (long long)norm->C != (long long)H * C) return CT_EINVAL;
+  const long long dense = (long long)H * C * N;
+  const long long ybs = norm->y_batch_stride ? norm->y_batch_stride : dense;
+  if (ybs < dense) return CT_EINVAL;
+  const uintptr_t bits = (uintptr_t)keys | (uintptr_t)grid | (uintptr_t)norm->y | (uintptr_t)(ybs << 2);
+  if (amax_out && ((bits & 15) != 0 || ((uintptr_t)amax_out & 3) != 0 || ct_slice_fwd_norm_amax_len(B, H, C, N, dim, W) == 0))
+    return CT_EINVAL;
+  long long G = 1;
+  for (int j = 0; j < dim; ++j) G *= W[j];
+  if ((size_t)G * 4 > (size_t)kBigLdsBytes && C > kNormGlobalMaxC) return CT_EINVAL;      // (the tile stays in memory: the records of ALL channels in LDS)
+  note_reset();
+  const Switches sw = read_switches();
+  RasterNormArgs a{};
+  static_cast<RasterArgs&>(a) = base_args(B, H, C, N, pad, pad_dtype);
+  a.pos = PosSrc{keys, nullptr, nullptr};
+  a.tile_in = grid; a.dst = norm->y; a.dst_bstride = (size_t)ybs;
+  a.norm_weight = norm->weight; a.norm_bias = norm->bias; a.norm_mean = norm->running_mean; a.norm_var = norm->running_var;
+  a.norm_eps = norm->eps; a.norm_relu = norm->relu; a.amax = amax_out;
+  return dim == 2 ? run_gather<2, true, true>(sw, a, W, (hipStream_t)s) : run_gather<3, true, true>(sw, a, W, (hipStream_t)s);
 }
 
 }  // extern "C"

@@ -49,6 +49,51 @@ struct RasterArgs {
   size_t sorted_stride;
 };
 
+// The argument block of the NORM gathers (ct_slice_fwd_norm): RasterArgs with, at its end, what the eval-mode norm of the sliced
+// value in the store needs.  dst is then the first row of a [B, Ct, N] tensor's channel range: the row of (cloud b, channel c =
+// h*C + channel in head) lies at dst + b*dst_bstride + c*N; the norm's parameters are indexed by c.  amax: one partial maximum
+// of |stored value| per workgroup (null: none).
+// An extension, not more fields of RasterArgs itself: every raster kernel takes RasterArgs by value, and with these 64 bytes in
+// it six backward kernels that never read them came out of the compiler with other register counts (slice_bwd_fused_kernel<true,
+// 0, 1>: 70 -> 75 vector registers, 7 -> 6 waves per SIMD; the padded band_slice_bwd kernels: 32 bytes of scratch).  The plain
+// kernels keep their (RasterArgs, GridW) signature and their code.
+struct RasterNormArgs : RasterArgs {
+  size_t dst_bstride;
+  const float* norm_weight;
+  const float* norm_bias;
+  const float* norm_mean;
+  const float* norm_var;
+  float* amax;
+  float norm_eps;
+  int norm_relu;
+};
+template <bool NORM>
+using GatherArgs = typename std::conditional<NORM, RasterNormArgs, RasterArgs>::type;
+
+// the first output row of channel c0 of plane (b, h): of the dense [B, H*C, N] tensor, or (NORM) at the output's own batch stride
+template <bool NORM>
+__device__ __forceinline__ float* gather_dst(const GatherArgs<NORM>& a, int b, int h, int c0, int N) {
+  if constexpr (NORM) return a.dst + (size_t)b * a.dst_bstride + ((size_t)h * a.C + c0) * (size_t)N;
+  else return a.dst + (((size_t)b * a.H + h) * a.C + c0) * (size_t)N;
+}
+
+// ---- the NORM epilogue over RasterNormArgs (the arithmetic and the fold: ct_common.h) ----
+// the records of channels [c_first, c_first + cc) of the norm, one thread each
+__device__ __forceinline__ void norm_stage_records(float4* rec, const RasterNormArgs& a, int c_first, int cc) {
+  for (int i = threadIdx.x; i < cc; i += blockDim.x) {
+    const int c = c_first + i;
+    rec[i] = ct_norm_record(a.norm_mean[c], a.norm_var[c], a.norm_eps, a.norm_weight[c], a.norm_bias[c]);
+  }
+}
+// (rec: a record in LDS; the channel is wave-uniform)
+__device__ __forceinline__ float norm_one(float v, const float4 rec, int relu) { return ct_norm_one(v, ct_norm_uniform(rec), relu); }
+__device__ __forceinline__ float4 norm_four(float4 v, const float4 rec, int relu, float& am) { return ct_norm_four(v, ct_norm_uniform(rec), relu, am); }
+// the workgroup's slot of amax_out is its linear index in the launch: every slot of the launch's length has exactly one owner
+__device__ __forceinline__ void norm_store_amax(float am, float* red, float* amax_out) {
+  ct_norm_fold_amax(am, red, amax_out == nullptr ? nullptr
+                                                 : amax_out + (blockIdx.x + (size_t)gridDim.x * (blockIdx.y + (size_t)gridDim.y * blockIdx.z)));
+}
+
 // Workgroup -> (x, head, cloud) of a grid (X, H, B) whose X workgroups per (b, h) plane share that plane's keys (and, for
 // the scatter / gather pairs, its feature rows or its tile).  The launch order is x-fastest and consecutive workgroups go to
 // the 8 XCDs in turn (observed; speed only), so a plane's workgroups are given linear ids congruent mod 8: one XCD, one

@@ -1313,8 +1313,10 @@ __global__ void __launch_bounds__(NTB, 4) splat_max_bwd_hot_kernel(RasterArgs a,
 // KG: Slice forward (and the g_feat half of Splat(sum) backward) with the channel-interleaved tile:
 //   one ds_read_b128 per (point, corner, 4 channels).   grid = (nchunks * nsplit, H, B)
 // ---------------------------------------------------------------------------
-template <bool HAS_PAD, int WT>
-__global__ void __launch_bounds__(kHotThreads, 4) gather_ci_kernel(RasterArgs a, GridW<2> g_arg) {
+//   NORM (ct_slice_fwd_norm): the eval-mode norm of channel h*C + c applied to the value in the store, rows at the strides of
+//   a wider output tensor, one partial maximum per workgroup (ct_raster_args.h); the parameter records lie behind the tile.
+template <bool HAS_PAD, int WT, bool NORM = false>
+__global__ void __launch_bounds__(kHotThreads, 4) gather_ci_kernel(GatherArgs<NORM> a, GridW<2> g_arg) {
   const GridW<2> g = grid2_of<WT>(g_arg);
   extern __shared__ __align__(16) float lds[];
   const int G = WT ? WT * WT : g.G, W1 = WT ? WT : g.W[1], N = a.N;
@@ -1330,6 +1332,9 @@ __global__ void __launch_bounds__(kHotThreads, 4) gather_ci_kernel(RasterArgs a,
   const int off[4] = {0, W1, 1, W1 + 1};
   const float* gin = a.tile_in + (bh * a.C + c0) * (size_t)G;
   stage_tile_ci(T4, gin, cc >> 2, G);
+  const float4* rec = T4 + (size_t)(a.CC >> 2) * G;
+  if constexpr (NORM) norm_stage_records(T4 + (size_t)(a.CC >> 2) * G, a, h * a.C + c0, cc);
+  float am = 0.0f;
   const int nq = N >> 2;
   const int per = (nq + a.nsplit - 1) / a.nsplit;
   const int q_beg = sp * per, q_end = min(nq, q_beg + per);
@@ -1337,7 +1342,7 @@ __global__ void __launch_bounds__(kHotThreads, 4) gather_ci_kernel(RasterArgs a,
   float4 tx = *(const float4*)(a.pos.keys + (bh * 2 + 0) * N + (min(q_beg + tid, nq - 1) << 2));
   float4 ty = *(const float4*)(a.pos.keys + (bh * 2 + 1) * N + (min(q_beg + tid, nq - 1) << 2));
   __syncthreads();
-  float* dst = a.dst + (bh * a.C + c0) * (size_t)N;
+  float* dst = gather_dst<NORM>(a, b, h, c0, N);
   for (int q = q_beg + tid; q < q_end; q += blockDim.x) {
     const int n0 = q << 2;
     float cw[4][4], pv[4];
@@ -1360,6 +1365,12 @@ __global__ void __launch_bounds__(kHotThreads, 4) gather_ci_kernel(RasterArgs a,
     }
     for (int cq = 0; cq < (cc >> 2); ++cq) {
       const float4* Tq = T4 + (size_t)cq * G;
+      // NORM: the four channels' records, in scalar registers before the gather's vector registers fill up
+      float4 nr[4];
+      if constexpr (NORM) {
+#pragma unroll
+        for (int cj = 0; cj < 4; ++cj) nr[cj] = ct_norm_uniform(rec[cq * 4 + cj]);
+      }
       float o[4][4];       // [channel][point]
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -1381,10 +1392,14 @@ __global__ void __launch_bounds__(kHotThreads, 4) gather_ci_kernel(RasterArgs a,
         o[3][i] = HAS_PAD ? s3 * pv[i] : s3;
       }
 #pragma unroll
-      for (int cj = 0; cj < 4; ++cj)
-        st_stream4(dst + (size_t)(cq * 4 + cj) * N + n0, make_float4(o[cj][0], o[cj][1], o[cj][2], o[cj][3]));
+      for (int cj = 0; cj < 4; ++cj) {
+        float4 ov = make_float4(o[cj][0], o[cj][1], o[cj][2], o[cj][3]);
+        if constexpr (NORM) ov = ct_norm_four(ov, nr[cj], a.norm_relu, am);
+        st_stream4(dst + (size_t)(cq * 4 + cj) * N + n0, ov);
+      }
     }
   }
+  if constexpr (NORM) norm_store_amax(am, lds, a.amax);
 }
 
 // ---------------------------------------------------------------------------

@@ -833,8 +833,9 @@ CT_KERNARG_IS_ARGS_AND_GRID((splat_max_bwd_hot3_kernel<true, 0, 16, kHotWideThre
 // ---------------------------------------------------------------------------
 // KG3: Slice forward / gather with the channel-interleaved tile.  grid = (nchunks * nsplit, H, B)
 // ---------------------------------------------------------------------------
-template <bool HAS_PAD, int W3 = 0>
-__global__ void __launch_bounds__(kHotThreads, 4) gather_ci3_kernel(RasterArgs a, GridW<3> g_arg) {
+//   NORM: as gather_ci_kernel's.
+template <bool HAS_PAD, int W3 = 0, bool NORM = false>
+__global__ void __launch_bounds__(kHotThreads, 4) gather_ci3_kernel(GatherArgs<NORM> a, GridW<3> g_arg) {
   const GridW<3> g = grid3_of<W3>(g_arg);
   extern __shared__ __align__(16) float lds[];
   const int G = g.G, N = a.N;
@@ -850,11 +851,14 @@ __global__ void __launch_bounds__(kHotThreads, 4) gather_ci3_kernel(RasterArgs a
   corner_offsets3(g, off);
   const float* gin = a.tile_in + (bh * a.C + c0) * (size_t)G;
   stage_tile_ci(T4, gin, cc >> 2, G);
+  const float4* rec = T4 + (size_t)(a.CC >> 2) * G;
+  if constexpr (NORM) norm_stage_records(T4 + (size_t)(a.CC >> 2) * G, a, h * a.C + c0, cc);
+  float am = 0.0f;
   __syncthreads();
   const int nq = N >> 2;
   const int per = (nq + a.nsplit - 1) / a.nsplit;
   const int q_beg = sp * per, q_end = min(nq, q_beg + per);
-  float* dst = a.dst + (bh * a.C + c0) * (size_t)N;
+  float* dst = gather_dst<NORM>(a, b, h, c0, N);
   for (int q = q_beg + tid; q < q_end; q += blockDim.x) {
     const int n0 = q << 2;
     float k[3][4], pv[4];
@@ -863,6 +867,11 @@ __global__ void __launch_bounds__(kHotThreads, 4) gather_ci3_kernel(RasterArgs a
     for (int i = 0; i < 4; ++i) pv[i] = HAS_PAD ? ct_load_pad(a.pad, a.pad_dtype, (size_t)b * N + n0 + i) : 1.0f;
     for (int cq = 0; cq < (cc >> 2); ++cq) {
       const float4* Tq = T4 + (size_t)cq * G;
+      float4 nr[4];        // NORM: the four channels' records, in scalar registers (see gather_ci_kernel)
+      if constexpr (NORM) {
+#pragma unroll
+        for (int cj = 0; cj < 4; ++cj) nr[cj] = ct_norm_uniform(rec[cq * 4 + cj]);
+      }
       float o[4][4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -890,8 +899,12 @@ __global__ void __launch_bounds__(kHotThreads, 4) gather_ci3_kernel(RasterArgs a
         __builtin_amdgcn_sched_barrier(0);
       }
 #pragma unroll
-      for (int cj = 0; cj < 4; ++cj)
-        st_stream4(dst + (size_t)(cq * 4 + cj) * N + n0, make_float4(o[cj][0], o[cj][1], o[cj][2], o[cj][3]));
+      for (int cj = 0; cj < 4; ++cj) {
+        float4 ov = make_float4(o[cj][0], o[cj][1], o[cj][2], o[cj][3]);
+        if constexpr (NORM) ov = ct_norm_four(ov, nr[cj], a.norm_relu, am);
+        st_stream4(dst + (size_t)(cq * 4 + cj) * N + n0, ov);
+      }
     }
   }
+  if constexpr (NORM) norm_store_amax(am, lds, a.amax);
 }

@@ -178,27 +178,53 @@ class _MHCTCore(nn.Module):
             return ops.split_pw_bn_eval(input, kvp[0], self.key_bn, self.values_bn)
         return self._norm_keys_values(kvp(input))
 
-    def _core(self, lattice, values, pts_padd=None):
-        """(sliced features, occupancy) = Slice(conv(Splat(values))) at the lattice (multihead_ct.py:99-107).  The grids whose
-        two tiles fit a CU run as ONE kernel that keeps them in LDS (ops.mhct_core: 32^2 / 16^2 with 16 features per head,
-        8^3 with 32 — measured 1.15-1.7x the three-kernel chain on the forward, tools/core_bench.py); every other grid goes
-        through Splat -> grouped conv -> Slice."""
-        B = lattice.size(0)
+    def _takes_core(self, B, N, dtype, is_cuda):
+        """Does the plane-resident kernel (ops.mhct_core) take this block's Splat -> conv -> Slice at batch B, N points?"""
         conv = self.conv[0] if len(self.conv) == 1 else None
-        if (ops.FUSED_CORE and conv is not None and isinstance(conv, (GroupedConv2d, GroupedConv3d)) and lattice.is_cuda
-                and values.dtype == torch.float32 and lattice.dtype == torch.float32 and lattice.size(2) % 4 == 0
+        return (ops.FUSED_CORE and conv is not None and isinstance(conv, (GroupedConv2d, GroupedConv3d)) and is_cuda
+                and dtype == torch.float32 and N % 4 == 0
                 and tuple(conv.kernel_size) == (3,) * self.tensor_dim and tuple(conv.stride) == (1,) * self.tensor_dim
                 and tuple(conv.padding) == (1,) * self.tensor_dim and tuple(conv.dilation) == (1,) * self.tensor_dim
                 and conv.padding_mode == "zeros" and conv.groups == self.heads and conv.in_channels == conv.out_channels
                 and conv.weight.dtype == torch.float32
-                and ops.mhct_core_supported(B, self.heads, self.in_feature_dim, lattice.size(2), ops.sizes_of(self.tensor_size, self.tensor_dim))):
-            pre, count = ops.mhct_core(lattice, values, pts_padd, conv.weight, conv.bias, self.tensor_size, self.heads, self.tensor_dim)
+                and ops.mhct_core_supported(B, self.heads, self.in_feature_dim, N, ops.sizes_of(self.tensor_size, self.tensor_dim)))
+
+    def _core(self, lattice, values, pts_padd=None, target=None):
+        """(sliced features, occupancy) = Slice(conv(Splat(values))) at the lattice (multihead_ct.py:99-107).  The grids whose
+        two tiles fit a CU run as ONE kernel that keeps them in LDS (ops.mhct_core: 32^2 / 16^2 with 16 features per head,
+        8^3 with 32 — measured 1.15-1.7x the three-kernel chain on the forward, tools/core_bench.py); every other grid goes
+        through Splat -> grouped conv -> Slice.  `target` (an ops.NormTarget, optional): the eval-mode norm + ReLU that follows
+        the sliced features, applied in the write-out of whichever kernel produces them where it qualifies
+        (ops.slice_norm_eligible) — the first result is then the normed tensor and target.out is set; else target is untouched."""
+        B = lattice.size(0)
+        if self._takes_core(B, lattice.size(2), values.dtype, lattice.is_cuda) and lattice.dtype == torch.float32:
+            conv = self.conv[0]
+            if target is not None and ops.slice_norm_eligible(target.bn, lattice, values, conv.weight, conv.bias):
+                pre, count = ops.mhct_core_norm(lattice, values, pts_padd, conv.weight, conv.bias, self.tensor_size, self.heads,
+                                                self.tensor_dim, target)
+            else:
+                pre, count = ops.mhct_core(lattice, values, pts_padd, conv.weight, conv.bias, self.tensor_size, self.heads, self.tensor_dim)
             with torch.no_grad():
                 occ = count * ops.occupancy_scale(B * self.in_feature_dim * self.heads)      # (one launch: int64 x float scalar -> float32)
             return pre, occ
         z = self.splat.forward_keys(lattice, values, pts_padd)
         occ = self._occupancy(z, B)
-        return self.slice.forward_keys(lattice, self.conv(z), pts_padd), occ
+        grid = self.conv(z)
+        if target is not None and ops.slice_norm_eligible(target.bn, lattice, grid):
+            return ops.slice_keys_norm(lattice, grid, pts_padd, self.tensor_size, self.heads, self.tensor_dim, target), occ
+        return self.slice.forward_keys(lattice, grid, pts_padd), occ
+
+    def _norm_plan(self, x, N):
+        """How the `after` pair of this head could ride its Slice write-out at N points: ("core" | "slice", partial maxima the
+        launch would write), or None where it cannot (ops.slice_norm_plannable; the AdaIN blocks never ask)."""
+        after = getattr(self, "after", None)
+        if not (after is not None and len(after) == 2 and type(after[1]) is nn.ReLU and ops.slice_norm_plannable(after[0], x, N)
+                and ops._records_nothing(x, *self.parameters())):
+            return None
+        B, W = x.size(0), ops.sizes_of(self.tensor_size, self.tensor_dim)
+        if self._takes_core(B, N, x.dtype, x.is_cuda):
+            return "core", ops.mhct_core_norm_amax_len(B, self.heads, self.in_feature_dim, N, W)
+        return "slice", ops.slice_norm_amax_len(B, self.heads, self.in_feature_dim, N, W)
 
     def _occupancy(self, z, batch):
         with torch.no_grad():
@@ -224,9 +250,10 @@ class MultiHead(_MHCTCore):
         # keys start as the pure rigid transform of xyz (multihead_ct.py:79-80)
         nn.init.zeros_(self.key_bn.weight)
 
-    def _forward_pre(self, input, orig_pcd, kv=None):
+    def _forward_pre(self, input, orig_pcd, kv=None, target=None):
         """Everything up to (not including) `after`: (sliced features, stats, lattice).  `kv` = (keys_res, values) when the
-        union block computed the projection and its norms for all heads at once."""
+        union block computed the projection and its norms for all heads at once.  `target`: see _core — where it is taken
+        (target.out is set) the first result already went through `after`."""
         pts_padd = None
         if isinstance(orig_pcd, tuple):
             orig_pcd, pts_padd = orig_pcd
@@ -235,14 +262,18 @@ class MultiHead(_MHCTCore):
         else:
             keys_res, values = kv
         keys, lattice, kstats = self._lattice(orig_pcd, keys_res)
-        pre, occ = self._core(lattice, values, pts_padd)
+        pre, occ = self._core(lattice, values, pts_padd, target)
         with torch.no_grad():
             stats = (occ, kstats[0], kstats[1], None)       # mean / variance of the keys, reduced by the lattice kernel
         return pre, stats, lattice
 
     def forward(self, input, orig_pcd, return_lattice=False):
-        pre, stats, lattice = self._forward_pre(input, orig_pcd)
-        result = run_after(self.after, pre)
+        # eval mode, nothing recorded, ops.SLICE_NORM: the `after` pair in the Slice (or core) write-out
+        target = None
+        if ops.SLICE_NORM and input.dim() == 3 and self._norm_plan(input, input.size(2)) is not None:
+            target = ops.NormTarget(self.after[0])
+        pre, stats, lattice = self._forward_pre(input, orig_pcd, target=target)
+        result = pre if (target is not None and target.out is not None) else run_after(self.after, pre)
         if return_lattice:
             result = result, lattice
         return result, stats
@@ -419,6 +450,48 @@ class MultiHeadUnion(_UnionBase):
             return sc[1](y)
         return sc(x)
 
+    def _slice_norm_targets(self, x):
+        """ops.SLICE_NORM, eval mode, nothing for autograd to record: one ops.NormTarget per head, or None where today's join
+        stays.  The concatenation and ONE 1-D maxima buffer are allocated here, on the current stream, before the heads fork: every
+        head's Slice (or core) launch then writes relu(bn(.)) into its channel range and its run of partial maxima — partials of
+        one maximum, which is what the projection that reads the concatenation folds."""
+        if not (len(self.attentions) > 1 and x.dim() == 3):
+            return None
+        B, _, N = x.shape
+        plans = [a._norm_plan(x, N) for a in self.attentions]
+        if any(p is None for p in plans):
+            return None
+        Ct = sum(a.after[0].num_features for a in self.attentions)
+        joined = torch.empty(B, Ct, N, device=x.device, dtype=torch.float32)
+        total = sum(n for _, n in plans)
+        # no maxima where a launch cannot leave them or a GEMM could not fold that many: the consumer runs ct_amax_f32 (same scale)
+        amax = (torch.empty(total, device=x.device, dtype=torch.float32)
+                if all(n > 0 for _, n in plans) and total <= ops.PW_AMAX_MAX else None)
+        targets, c0, a0 = [], 0, 0
+        for a, (_, n) in zip(self.attentions, plans):
+            targets.append(ops.NormTarget(a.after[0], y=joined, c0=c0, amax=amax, a0=a0))
+            c0 += a.after[0].num_features
+            a0 += n
+        return targets
+
+    def _slice_norm_join(self, targets, pres):
+        """The concatenation the targets' launches filled.  A head whose launch did not qualify after all (its result came back
+        un-normed) is normed into its channel range by one ct_bn_eval_group_fwd over just those heads; the maxima tag is then
+        left off (that head's run of partials was never written)."""
+        joined, amax = targets[0].y, targets[0].amax
+        B, Ct, N = joined.shape
+        left = [(t, p) for t, p in zip(targets, pres) if t.out is None]
+        if left:
+            if all(ops.bn_eval_eligible(t.bn, p) for t, p in left):
+                ops._bn_eval_group([ops._bn_eval_item(t.bn, p.data_ptr(), 0, joined.data_ptr() + t.c0 * N * 4, Ct * N, True)
+                                    for t, p in left], B, N)
+            else:
+                for t, p in left:
+                    joined[:, t.c0:t.c0 + p.size(1)].copy_(run_after(nn.Sequential(t.bn, nn.ReLU()), p))
+        elif amax is not None:
+            joined._ct_amax = (amax, joined._version)       # (1-D, set directly: ops.tag_amax would read [n / C, C] as per-channel maxima)
+        return joined
+
     def forward(self, x, orig_pcd):
         x = self.prenorm(x)
         pres, stats = [], []
@@ -444,10 +517,14 @@ class MultiHeadUnion(_UnionBase):
                 residual, kvs = self._shortcut(x), ops.union_keys_values_frozen(x, convs, kbs, vbs)
         else:
             residual, kvs = self._shortcut(x), None
-        for r, s, _ in _run_heads([(lambda a=a, i=i: a._forward_pre(x, orig_pcd, None if kvs is None else kvs[i]))
+        targets = self._slice_norm_targets(x) if ops.SLICE_NORM else None
+        for r, s, _ in _run_heads([(lambda a=a, i=i: a._forward_pre(x, orig_pcd, None if kvs is None else kvs[i],
+                                                                    target=None if targets is None else targets[i]))
                                    for i, a in enumerate(self.attentions)], x):
             pres.append(r)
             stats.append(s)
+        if targets is not None:
+            return run_after(self.after, self._slice_norm_join(targets, pres), residual), stats
         # the heads' BatchNorm + ReLU write straight into their channel ranges of the concatenation when they qualify
         norms = [a.after for a in self.attentions]
         if (len(pres) > 1 and all(len(n) == 2 and type(n[1]) is nn.ReLU and ops.bn_relu_eligible(n[0], p)

@@ -2402,3 +2402,134 @@ def mhct_core(keys, features, pts_padding, weight, bias, tensor_size, heads, dim
     """(sliced features, occupancy count) of one MHCT core; raises unless mhct_core_supported(...)."""
     W = sizes_of(tensor_size, dim)
     return MhctCoreFn.apply(keys, features, pts_padding, weight, bias, W, heads)
+
+
+# ---------------------------------------------------------------------------
+# eval-mode head norms in the Slice write-out (ct_slice_fwd_norm / ct_mhct_core_fwd_norm)
+# ---------------------------------------------------------------------------
+# The heads' `after` pair (BatchNorm1d -> ReLU on the Slice output) applied in the store of the kernel that produces the value:
+# the sliced features are never written un-normed, and a union block in eval mode launches no norm kernel at all.  The results
+# carry the bits of Slice (or the core) followed by ct_bn_eval_group_fwd.  Opt-in — "1" turns it on — and consulted only where
+# BN_EVAL already routes to the eval kernels: forward only, nothing for autograd to record.
+SLICE_NORM = os.environ.get("CLOUDCT_SLICE_NORM", "0") == "1"
+
+
+class NormTarget:
+    """Where the normed Slice output of one head goes: relu?(bn(.)) into channels [c0, c0 + bn.num_features) of `y` [B, Ct, N]
+    (None: a dense tensor of its own) and its partial maxima into the 1-D buffer `amax` from slot a0 on (None with a `y`: no
+    maxima; without a `y` the op allocates them and tags the result).  The op that takes the target sets `out` to the result."""
+    __slots__ = ("bn", "relu", "y", "c0", "amax", "a0", "out")
+
+    def __init__(self, bn, relu=True, y=None, c0=0, amax=None, a0=0):
+        self.bn, self.relu, self.y, self.c0, self.amax, self.a0, self.out = bn, relu, y, c0, amax, a0, None
+
+
+def slice_norm_plannable(bn, x, N):
+    """The part of slice_norm_eligible a block can check before its heads run (the union block sizes one maxima buffer for all
+    of them first): the switches, an eval-mode norm ct_bn_eval_* takes on clouds of N % 4 == 0 points, a CUDA fp32 input."""
+    return bool(SLICE_NORM and BN_EVAL and x.is_cuda and x.dtype == torch.float32 and N % 4 == 0 and not bn.training
+                and _bn_eval_norm_ok(bn, x.size(0), bn.num_features, N) and bn.weight.device == x.device)
+
+
+def slice_norm_eligible(bn, keys, grid, *more):
+    """True when relu?(bn(Slice(keys, grid))) can run as ONE ct_slice_fwd_norm (grid: the convolved grid [B, H*C, *W]) or
+    ct_mhct_core_fwd_norm (grid: the values [B, H*C, N]; `more`: the filter bank and its bias) call: ops.SLICE_NORM, and
+    bn_eval_eligible's rule — an nn.BatchNorm1d / nn.SyncBatchNorm (exactly) in eval mode, affine, with running statistics over the
+    H*C channels, fp32, and nothing for autograd to record — on CUDA fp32 contiguous tensors that are 16-byte aligned, N % 4 == 0."""
+    if not (SLICE_NORM and BN_EVAL and keys.dim() == 3 and keys.size(2) % 4 == 0 and grid.dim() >= 3):
+        return False
+    for t in (keys, grid) + more:
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0):
+            return False
+    return (not bn.training and _bn_eval_norm_ok(bn, keys.size(0), grid.size(1), keys.size(2)) and bn.weight.device == keys.device
+            and _records_nothing(keys, grid, bn.weight, bn.bias, *more))
+
+
+def slice_norm_amax_len(B, H, C, N, W):
+    """Partial maxima ct_slice_fwd_norm writes for the shape (under the current debug flags); 0: none can be asked for."""
+    if PW_GEMM != "split16":
+        return 0
+    return int(_lib.load().ct_slice_fwd_norm_amax_len(B, H, C, N, len(W), _lib.int_array(W)))
+
+
+def mhct_core_norm_amax_len(B, H, C, N, W):
+    """The same for ct_mhct_core_fwd_norm."""
+    if PW_GEMM != "split16":
+        return 0
+    return int(_lib.load().ct_mhct_core_fwd_norm_amax_len(B, H, C, N, len(W), _lib.int_array(W)))
+
+
+def _norm_target_args(target, B, HC, N, n_len, device):
+    """(the [B, HC, N] result view, its ct_bn_fwd_item, the maxima pointer, the op's own maxima buffer or None)."""
+    bn = target.bn
+    assert bn.num_features == HC
+    if target.y is None:
+        y = view = torch.empty(B, HC, N, device=device, dtype=torch.float32)
+        ybs, y_ptr = 0, _ptr(y)
+        own = torch.empty(n_len, device=device, dtype=torch.float32) if n_len else None
+        am_ptr = _ptr(own)
+    else:
+        y, own = target.y, None
+        assert y.dim() == 3 and y.is_contiguous() and y.size(0) == B and y.size(2) == N and target.c0 + HC <= y.size(1)
+        view = y[:, target.c0:target.c0 + HC]
+        ybs, y_ptr = y.size(1) * N, _ptr(y) + target.c0 * N * 4
+        am_ptr = None
+        if target.amax is not None and n_len:
+            assert target.a0 + n_len <= target.amax.numel()
+            am_ptr = _ptr(target.amax) + 4 * target.a0
+    item = _bn_eval_item(bn, None, 0, y_ptr, ybs, target.relu)
+    return view, item, am_ptr, own
+
+
+def _norm_target_done(target, view, own):
+    if own is not None:
+        view._ct_amax = (own, view._version)        # (1-D on purpose: partials of ONE maximum, as pw_bn_eval's)
+    target.out = view
+    return view
+
+
+def slice_keys_norm(keys, grid, pts_padding, tensor_size, heads, dim, target):
+    """relu?(bn(Slice(keys, grid))) in one launch (ct_slice_fwd_norm) into `target` (a NormTarget); the caller checked
+    slice_norm_eligible(target.bn, keys, grid).  Returns the result (a channel range of target.y, or a dense tensor that carries
+    the partial maxima of its values for the pointwise GEMM that reads it next)."""
+    W = sizes_of(tensor_size, dim)
+    _dev(keys, grid, pts_padding)
+    keys, grid = _f32c(keys), _f32c(grid)
+    B, HC = grid.shape[:2]
+    N = keys.shape[-1]
+    assert HC % heads == 0 and keys.shape == (B, heads * dim, N) and list(grid.shape[2:]) == list(W)
+    C = HC // heads
+    padt, pad_code = _pad_args(pts_padding, B, N)
+    view, item, am_ptr, own = _norm_target_args(target, B, HC, N, slice_norm_amax_len(B, heads, C, N, W), grid.device)
+    arr = _bn_fwd_table([item])
+    lib = _lib.load()
+    with _on(grid.device):
+        _lib.check(lib.ct_slice_fwd_norm(_ptr(keys), _ptr(grid), _ptr(padt), pad_code, _at(arr, 0), am_ptr,
+                                         B, heads, C, N, dim, _lib.int_array(W), _stream()), "ct_slice_fwd_norm")
+    return _norm_target_done(target, view, own)
+
+
+def mhct_core_norm(keys, features, pts_padding, weight, bias, tensor_size, heads, dim, target):
+    """(relu?(bn(sliced features)), occupancy count) of one MHCT core in one launch (ct_mhct_core_fwd_norm) into `target`; the
+    caller checked mhct_core_supported(...) and slice_norm_eligible(target.bn, keys, features, weight, bias).  Forward only:
+    nothing is saved.  The launch runs on the workspace mhct_core's launches of this shape and stream use, so a cluster that
+    gave up waiting shows where theirs do: mhct_core_check reads (and re-initialises) that workspace's status word."""
+    W = sizes_of(tensor_size, dim)
+    _dev(keys, features, pts_padding, weight, bias)
+    keys, features, weight = _f32c(keys), _f32c(features), _f32c(weight)
+    bias = _f32c(bias) if bias is not None else None
+    B, HC, N = features.shape
+    C = HC // heads
+    assert keys.shape == (B, heads * dim, N) and weight.shape[0] == HC and weight.shape[1] == C
+    padt, pad_code = _pad_args(pts_padding, B, N)
+    dev = features.device
+    view, item, am_ptr, own = _norm_target_args(target, B, HC, N, mhct_core_norm_amax_len(B, heads, C, N, W), dev)
+    arr = _bn_fwd_table([item])
+    occ = torch.empty((), device=dev, dtype=torch.int64)
+    ws = mhct_core_workspace(dev, B, heads, C, N, W)
+    lib = _lib.load()
+    with _on(dev):
+        _lib.check(lib.ct_mhct_core_fwd_norm(_ptr(keys), _ptr(features), _ptr(padt), pad_code, _ptr(weight), _ptr(bias), _at(arr, 0),
+                                             am_ptr, None, None, _ptr(occ), _ptr(ws), ws.numel(), B, heads, C, N, dim,
+                                             _lib.int_array(W), _stream()), "ct_mhct_core_fwd_norm")
+    return _norm_target_done(target, view, own), occ

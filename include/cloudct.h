@@ -726,6 +726,47 @@ int ct_pw_gemm_norm_amax_len(int B, int Co, int N);
 int ct_pw_gemm_rs_norm(const float* w, const float* x, const ct_bn_fwd_item* items, int n, float* amax_out, const float* amax_a,
                        int n_amax_a, int rows_a, const float* amax_b, int n_amax_b, void* workspace, size_t workspace_bytes, int B,
                        int Co, int Ci, int N, ct_stream_t s);
+/* Slice forward with the eval-mode BatchNorm1d (+ ReLU) that follows it applied in the gather's store — the heads' `after`
+ * pairs on the Slice output (layers/multihead_ct.py:67-68,107: `self.after(self.slice(...))` = slice -> BatchNorm1d -> ReLU, and
+ * the union block's concatenation of the heads' results, :196), where a norm launch of its own would read back the tensor Slice
+ * has just written:
+ *   y[b, h*C + c, n] = relu?( bn( Slice(keys, grid)[b, h*C + c, n] ) )
+ * keys, grid, pad, the sizes and W as ct_slice_fwd.  `norm` is ONE ct_bn_fwd_item with C == H*C; read of it: y with
+ * y_batch_stride in floats (0 = dense, else >= H*C*N: the head writes its channel range of a wider [B, Ct, N] tensor, the row of
+ * (cloud b, channel c) at y + b*y_batch_stride + c*N), weight, bias, running_mean, running_var f32[H*C] (all required,
+ * read-only), eps >= 0 and relu; x is ignored; residual and the item's own amax_out must be NULL.
+ * Bit equality: the value ct_slice_fwd would have stored (after the pad multiply) goes through ct_bn_eval_group_fwd's operation
+ * sequence ( ((v - mean) * (1 / sqrt(var + eps))) * weight + bias; max(., 0) ), so y holds exactly the bits of ct_slice_fwd into
+ * a dense scratch tensor followed by ct_bn_eval_group_fwd with the same item.
+ * Dispatch: the kernel family ct_slice_fwd takes for the shape, the switches and the debug flags, with y and its stride in the
+ * alignment tests where `out` stands; ct_debug_last_launch names it as the family's tag followed by "+norm".
+ * amax_out f32[ct_slice_fwd_norm_amax_len(B, H, C, N, dim, W)] (nullable): one partial maximum per workgroup, max |y| over what
+ * it stored — partials of ONE maximum in the sense of ct_amax_f32, as ct_pw_gemm_rs_norm leaves them: plain stores, nothing to
+ * zero, every slot written by the launch.  The length is that of the launch planned for 16-byte aligned tensors and strides
+ * under the current switches and debug flags (query and launch share the plan); 0 where there would be more partials than a GEMM
+ * folds (32768) or the shape is refused: pass NULL then.
+ * CT_EINVAL, before anything is launched: a null required pointer, norm->C != H*C, eps < 0 or NaN, a stride below H*C*N, a
+ * residual or per-item amax_out, amax_out where the length is 0 or keys, grid, y or the stride are not 16-byte aligned, a grid
+ * whose single-channel tile exceeds a CU's LDS with more than 4096 channels per head, and whatever ct_slice_fwd refuses.
+ * Added under CT_ABI_VERSION 3 (additive: the loader's missing-symbol scan checks it). */
+int ct_slice_fwd_norm_amax_len(int B, int H, int C, int N, int dim, const int* W);
+int ct_slice_fwd_norm(const float* keys, const float* grid, const void* pad, int pad_dtype, const ct_bn_fwd_item* norm,
+                      float* amax_out, int B, int H, int C, int N, int dim, const int* W, ct_stream_t s);
+/* The same for the plane-resident core (layers/multihead_ct.py:99-107 with the `after` pair of :67-68 in its Slice write-out):
+ * ct_mhct_core_fwd's arguments with `out` replaced by (norm, amax_out), the item read as above (y_batch_stride % 4 == 0: the
+ * rows move as float4), C the features per head.  Every output element holds exactly the bits of ct_mhct_core_fwd into a dense
+ * scratch tensor followed by ct_bn_eval_group_fwd with the same item; z_save, y_save, occ_count and the workspace (clusters,
+ * status word, ct_debug_set_core) behave as ct_mhct_core_fwd's.  A cluster that gives up waiting still writes NaN where its
+ * results would have gone — un-normed: a ReLU would turn the marker into 0 — and NaN into its partial maximum.
+ * amax_out f32[ct_mhct_core_fwd_norm_amax_len(...)] (nullable): one partial maximum per workgroup (planes x cluster size under
+ * the current ct_debug_set_core flags), as above; 0 beyond 32768 partials or where ct_mhct_core_supported is 0.
+ * CT_EINVAL as above (every pointer must be 16-byte aligned here, as for ct_mhct_core_fwd) and whatever ct_mhct_core_fwd
+ * refuses; CT_EWORKSPACE as ct_mhct_core_fwd.  Added under CT_ABI_VERSION 3 (additive). */
+int ct_mhct_core_fwd_norm_amax_len(int B, int H, int C, int N, int dim, const int* W);
+int ct_mhct_core_fwd_norm(const float* keys, const float* feat, const void* pad, int pad_dtype, const float* conv_w,
+                          const float* conv_b, const ct_bn_fwd_item* norm, float* amax_out, float* z_save, float* y_save,
+                          int64_t* occ_count, void* workspace, size_t workspace_bytes, int B, int H, int C, int N, int dim,
+                          const int* W, ct_stream_t s);
 
 /* ------------------------------------------------------------------------
  * Neighbour search of the S3DIS KPConv protocol over a uniform grid (replaces the CPU
