@@ -73,6 +73,12 @@ class AdainBwdItem(ctypes.Structure):
                 ("gamma_beta_batch_stride", ctypes.c_longlong)]
 
 
+class GconvNorm(ctypes.Structure):
+    """ct_gconv_norm (include/cloudct.h)."""
+    _fields_ = [("weight", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("running_mean", ctypes.c_void_p),
+                ("running_var", ctypes.c_void_p), ("eps", ctypes.c_float)]
+
+
 ABI_VERSION = 3      # CT_ABI_VERSION of include/cloudct.h
 BN_GROUP_MAX = 8
 CT_OK = 0
@@ -292,6 +298,8 @@ SIGNATURES = {
     "ct_bn_eval_group_fwd": (_i, [_vp, _i, _i, _i, _vp]),
     "ct_bn_eval_group_bwd": (_i, [_vp, _i, _i, _i, _vp]),
     "ct_gconv_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _ip, _vp]),
+    "ct_gconv_fwd_norm_supported": (_i, [_i, _i, _i, _i, _i, _ip]),
+    "ct_gconv_fwd_norm": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _ip, _vp]),
     "ct_gconv_bwd_data": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _ip, _vp]),
     "ct_gconv_supported": (_i, [_i, _i, _i, _i, _i, _ip]),
     "ct_gconv_bwd_weight_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _ip]),

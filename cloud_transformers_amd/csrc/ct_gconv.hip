@@ -21,6 +21,10 @@
 //                           engine (four-channel groups); partial sums to a workspace, added by
 //                           gconv_wrw_reduce_kernel / gconv_c4_wrw_reduce_kernel in a fixed order
 //   gconv_bwd_weight_kernel backward-weight for rows that are not a multiple of 4 floats (tile form, float atomics)
+// The quad, K-split and dense 2^d forms of the forward kernel (gconv_fwd4_kernel, gconv_fwd4k_kernel, gconv_tiny_kernel; further
+// down) also exist as a NORM template variant: ct_gconv_fwd_norm applies the eval-mode BatchNorm, the skip connection and the
+// ReLU of a grouped Res block to the values in their stores (GconvEpi below).  No atomics; the plain instantiations are the
+// code they were without the variant, and the variants' launches stand last in the file so that they also stay where they were.
 #include "ct_common.h"
 #include <atomic>
 #include <type_traits>
@@ -82,6 +86,49 @@ struct GconvArgs {
   int TZ;              // ring kernel: depth slices per unit (3D)
   int msplit;          // forward kernels: workgroups that share a tile, each taking every msplit-th 16-row block of output channels
 };
+
+// ---- the NORM write-out of the forward kernels (ct_gconv_fwd_norm) ----
+// Eval-mode BatchNorm, the skip connection (normed itself or as it is) and the ReLU of a Res block on the value the plain kernel
+// would have stored, in the registers that hold it: relu?(bn(v) + bn'?(skip)).  bn is bn_eval_one's operation sequence
+// (ct_bnorm.hip, through ct_norm_record / ct_norm_one of ct_common.h; contraction is off for the whole library), the add and the
+// maximum are one fp32 operation each: the bits of ct_gconv_fwd, ct_bn_eval_group_fwd, torch.add and torch.relu in a row.  The
+// K-split, quad and dense 2^d kernels carry it as a template variant; the plain instantiations do not see it.
+struct GconvNorm {
+  const float *weight, *bias, *mean, *var;   // f32[groups*Cout]
+  float eps;
+};
+struct GconvEpi {
+  GconvNorm n;         // the norm of the convolution's own output
+  GconvNorm sn;        // the norm of the skip connection (sn.weight == nullptr: the skip is added as it is)
+  const float* skip;   // (B, groups*Cout, D, H, W) or null
+  int relu;
+};
+
+// kernel argument of the forward kernels: GconvArgs itself for the plain instantiations (the same argument block as before the
+// variant existed), GconvArgs + the epilogue for the NORM ones
+template <bool NORM> struct FwdArgs : GconvArgs {};
+template <> struct FwdArgs<true> : GconvArgs { GconvEpi epi; };
+template <bool NORM> FwdArgs<NORM> fwd_args(const GconvArgs& a, const GconvEpi* e) {
+  FwdArgs<NORM> f;
+  static_cast<GconvArgs&>(f) = a;
+  if constexpr (NORM) f.epi = *e;
+  return f;
+}
+
+__device__ __forceinline__ float4 gconv_norm_rec(const GconvNorm& n, int c) {
+  return ct_norm_record(n.mean[c], n.var[c], n.eps, n.weight[c], n.bias[c]);
+}
+// one stored quad of channel `rec`; s: the skip connection's quad at the same index (read only where e.skip is set)
+__device__ __forceinline__ float4 gconv_epi_four(float4 v, const GconvEpi& e, const float4 rec, const float4 srec, float4 s) {
+  float4 o = make_float4(ct_norm_one(v.x, rec, 0), ct_norm_one(v.y, rec, 0), ct_norm_one(v.z, rec, 0), ct_norm_one(v.w, rec, 0));
+  if (e.skip != nullptr) {
+    if (e.sn.weight != nullptr)
+      s = make_float4(ct_norm_one(s.x, srec, 0), ct_norm_one(s.y, srec, 0), ct_norm_one(s.z, srec, 0), ct_norm_one(s.w, srec, 0));
+    o.x = o.x + s.x; o.y = o.y + s.y; o.z = o.z + s.z; o.w = o.w + s.w;
+  }
+  if (e.relu) o = make_float4(fmaxf(o.x, 0.0f), fmaxf(o.y, 0.0f), fmaxf(o.z, 0.0f), fmaxf(o.w, 0.0f));
+  return o;
+}
 
 // A-operand tile of one group and one 16-row block of output channels, laid out so that the 64
 // lanes of a wave read 64 consecutive floats: ws[((tap*KB + kb)*4 + k)*16 + m]
@@ -282,8 +329,10 @@ __global__ void __launch_bounds__(kThreadsBig) gconv_fwd_kernel(GconvArgs a) {
 // positions: results leave as 16-byte stores (the one-position form stores 4 bytes per lane).
 // grid = (nD*nH, groups, B)
 // ---------------------------------------------------------------------------
-template <int DIM>
-__global__ void __launch_bounds__(kThreadsBig) gconv_fwd4_kernel(GconvArgs a) {
+// NORM: the write-out of ct_gconv_fwd_norm.  The records of a 16-row block (and of its skip connection's norm) are computed once per
+// block by 16 (32) threads into static LDS, next to the bank; a lane reads the four of its rows back at the stores.
+template <int DIM, bool NORM = false>
+__global__ void __launch_bounds__(kThreadsBig) gconv_fwd4_kernel(FwdArgs<NORM> a) {
   constexpr int NR = DIM == 3 ? 9 : 3;               // window rows (dz, dy)
   extern __shared__ __align__(16) float lds[];
   const int tile = blockIdx.x / a.msplit, ms = blockIdx.x % a.msplit, grp = blockIdx.y, b = blockIdx.z;
@@ -301,9 +350,10 @@ __global__ void __launch_bounds__(kThreadsBig) gconv_fwd4_kernel(GconvArgs a) {
   const int nspans = (nquads + 15) >> 4;
   const int MT = (a.Cout + 15) >> 4;
   float* yg = a.y + ((size_t)b * a.groups + grp) * a.Cout * vol;
+  [[maybe_unused]] const float4* recs = nullptr;
 
   for (int mt = ms; mt < MT; mt += a.msplit) {
-    __syncthreads();                                 // xs ready / previous bank consumed
+    __syncthreads();                                 // xs ready / previous bank (and its records) consumed
     // filter bank of this 16-row block: ws[((r*KB + kb)*4 + k)*64 + m*4 + dx] = W[co = mt*16+m][ci = kb*4+k][tap = r*3+dx]
     for (int i = threadIdx.x; i < NR * KB * 256; i += blockDim.x) {
       const int dx = i & 3, m = (i >> 2) & 15, k = (i >> 6) & 3, rk = i >> 8;
@@ -314,6 +364,15 @@ __global__ void __launch_bounds__(kThreadsBig) gconv_fwd4_kernel(GconvArgs a) {
         v = a.transposed ? a.w[((size_t)(grp * a.Cin + ci) * a.Cout + co) * a.taps + (a.taps - 1 - tap)]
                          : a.w[((size_t)(grp * a.Cout + co) * a.Cin + ci) * a.taps + tap];
       ws[i] = v;
+    }
+    if constexpr (NORM) {
+      __shared__ float4 nrec[2][16];
+      if (threadIdx.x < 32) {
+        const int m = threadIdx.x & 15, co = mt * 16 + m;
+        const GconvNorm& n = threadIdx.x < 16 ? a.epi.n : a.epi.sn;
+        if (co < a.Cout && n.weight != nullptr) nrec[threadIdx.x >> 4][m] = gconv_norm_rec(n, grp * a.Cout + co);
+      }
+      recs = &nrec[0][0];
     }
     __syncthreads();
     float bias_r[4];
@@ -352,10 +411,29 @@ __global__ void __launch_bounds__(kThreadsBig) gconv_fwd4_kernel(GconvArgs a) {
       // D_j: row (output channel) = kq*4 + r, column = quad col, element j
       if (sp * 16 + col < nquads) {
         const size_t o = ((size_t)(td0 + z) * a.H + (th0 + y)) * a.W + x0;
+        if constexpr (NORM) {
+          const GconvEpi& e = a.epi;
+          const float* sg = e.skip != nullptr ? e.skip + (yg - a.y) : nullptr;
+          float4 sk[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int co = mt * 16 + kq * 4 + r;
-          if (co < a.Cout) *(float4*)(yg + (size_t)co * vol + o) = make_float4(acc[0][r], acc[1][r], acc[2][r], acc[3][r]);
+          for (int r = 0; r < 4; ++r) {
+            const int co = mt * 16 + kq * 4 + r;
+            sk[r] = make_float4(0, 0, 0, 0);
+            if (sg != nullptr && co < a.Cout) sk[r] = *(const float4*)(sg + (size_t)co * vol + o);
+          }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int co = mt * 16 + kq * 4 + r;
+            if (co < a.Cout)
+              *(float4*)(yg + (size_t)co * vol + o) = gconv_epi_four(make_float4(acc[0][r], acc[1][r], acc[2][r], acc[3][r]), e,
+                                                                     recs[kq * 4 + r], recs[16 + kq * 4 + r], sk[r]);
+          }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int co = mt * 16 + kq * 4 + r;
+            if (co < a.Cout) *(float4*)(yg + (size_t)co * vol + o) = make_float4(acc[0][r], acc[1][r], acc[2][r], acc[3][r]);
+          }
         }
       }
     }
@@ -387,8 +465,11 @@ constexpr int kKBlk = 16;       // input channels per contraction block (4 MFMA 
 // bank, the minimum for 64 lanes.
 template <int TAPS, bool TR> struct BankRow { static constexpr int RL = 16 * TAPS, CS = TR ? RL : RL + 4; };
 
-template <int DIM, int MAXI, bool TR>
-__global__ void __launch_bounds__(kThreadsBig) gconv_fwd4k_kernel(GconvArgs a, int dma_bank) {
+// NORM: the write-out of ct_gconv_fwd_norm.  The stores come once, after the last contraction block, when only the accumulators
+// are live: every lane computes the records of its own four rows there (in registers: no LDS next to the bank, whose size the
+// planner shares with the plain kernel).
+template <int DIM, int MAXI, bool TR, bool NORM = false>
+__global__ void __launch_bounds__(kThreadsBig) gconv_fwd4k_kernel(FwdArgs<NORM> a, int dma_bank) {
   constexpr int NR = DIM == 3 ? 9 : 3, TAPS = NR * 3;
   constexpr int KBB = kKBlk / 4;
   constexpr int RL = BankRow<TAPS, TR>::RL, CS = BankRow<TAPS, TR>::CS;
@@ -496,10 +577,31 @@ __global__ void __launch_bounds__(kThreadsBig) gconv_fwd4k_kernel(GconvArgs a, i
       const int xq = qi % wq, y = (qi / wq) % th, z = qi / (wq * th);
       const size_t o = ((size_t)(td0 + z) * a.H + (th0 + y)) * a.W + xq * 4;
       const int mt = ms + it_mt[u] * a.msplit;
+      if constexpr (NORM) {
+        const GconvEpi& e = a.epi;
+        const float* sg = e.skip != nullptr ? e.skip + (yg - a.y) : nullptr;
+        float4 sk[4], rec[4], srec[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int co = mt * 16 + kq * 4 + r;
-        if (co < a.Cout) *(float4*)(yg + (size_t)co * vol + o) = make_float4(acc[u][0][r], acc[u][1][r], acc[u][2][r], acc[u][3][r]);
+        for (int r = 0; r < 4; ++r) {
+          const int co = min(mt * 16 + kq * 4 + r, a.Cout - 1);    // clamped: rows past Cout are not stored
+          sk[r] = srec[r] = make_float4(0, 0, 0, 0);
+          if (sg != nullptr) sk[r] = *(const float4*)(sg + (size_t)co * vol + o);
+          rec[r] = gconv_norm_rec(e.n, grp * a.Cout + co);
+          if (e.sn.weight != nullptr) srec[r] = gconv_norm_rec(e.sn, grp * a.Cout + co);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int co = mt * 16 + kq * 4 + r;
+          if (co < a.Cout)
+            *(float4*)(yg + (size_t)co * vol + o) = gconv_epi_four(make_float4(acc[u][0][r], acc[u][1][r], acc[u][2][r], acc[u][3][r]),
+                                                                   e, rec[r], srec[r], sk[r]);
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int co = mt * 16 + kq * 4 + r;
+          if (co < a.Cout) *(float4*)(yg + (size_t)co * vol + o) = make_float4(acc[u][0][r], acc[u][1][r], acc[u][2][r], acc[u][3][r]);
+        }
       }
     }
   }
@@ -525,8 +627,10 @@ __global__ void __launch_bounds__(kThreadsBig) gconv_fwd4k_kernel(GconvArgs a, i
 // ---------------------------------------------------------------------------
 constexpr int kTinyTapStride = 28;     // 27 taps padded to whole b128 reads (2D: 9 -> 12)
 
-template <int DIM>
-__global__ void __launch_bounds__(256) gconv_tiny_kernel(GconvArgs a, int COB) {
+// NORM: the write-out of ct_gconv_fwd_norm, on the sums of the four waves' partial rows (a thread stores one quad of one channel
+// and computes that channel's record itself).
+template <int DIM, bool NORM = false>
+__global__ void __launch_bounds__(256) gconv_tiny_kernel(FwdArgs<NORM> a, int COB) {
   constexpr int P = DIM == 3 ? 8 : 4;
   constexpr int TAPS = DIM == 3 ? 27 : 9;
   constexpr int TS = DIM == 3 ? kTinyTapStride : 12;
@@ -605,7 +709,16 @@ __global__ void __launch_bounds__(256) gconv_tiny_kernel(GconvArgs a, int COB) {
       const float bv = a.bias[grp * a.Cout + co0 + co];
       s.x += bv, s.y += bv, s.z += bv, s.w += bv;
     }
-    *(float4*)(a.y + (((size_t)b * a.groups + grp) * a.Cout + co0 + co) * P + h * 4) = s;
+    const size_t o = (((size_t)b * a.groups + grp) * a.Cout + co0 + co) * P + h * 4;
+    if constexpr (NORM) {
+      const GconvEpi& e = a.epi;
+      const int c = grp * a.Cout + co0 + co;
+      float4 sk = make_float4(0, 0, 0, 0), srec = sk;
+      if (e.skip != nullptr) sk = *(const float4*)(e.skip + o);
+      if (e.sn.weight != nullptr) srec = gconv_norm_rec(e.sn, c);
+      s = gconv_epi_four(s, e, gconv_norm_rec(e.n, c), srec, sk);
+    }
+    *(float4*)(a.y + o) = s;
   }
 }
 
@@ -2003,7 +2116,15 @@ int launch_c4(GconvArgs a, int dim, hipStream_t st) {
 }
 
 // quad form of the MFMA kernel (rows of W % 4 == 0 floats, 16-byte aligned tensors)
-int launch_fwd4(GconvArgs a, int dim, hipStream_t st) {
+// The launches of the NORM variants (ct_gconv_fwd_norm) stand at the end of the file, after every other launch: a template is
+// emitted where it is first used, and there the kernels this file had before the variants keep their order in the code object.
+// Each notes the tags the plain launch of the same plan notes.
+int launch_fwd4_norm(const GconvArgs& a, const GconvEpi& e, int dim, dim3 grid, int threads, size_t lds, hipStream_t st);
+int launch_fwd4k_norm(const GconvArgs& t, const GconvEpi& e, int dim, int pass, int maxi, int dma, dim3 grid, size_t lds, hipStream_t st);
+int launch_tiny_norm(const GconvArgs& a, const GconvEpi& e, int dim, int cob, dim3 grid, size_t lds, hipStream_t st);
+
+// (e: the NORM write-out of ct_gconv_fwd_norm, the same plan and tags; plan_only: settle the plan and return before the launch)
+int launch_fwd4(GconvArgs a, int dim, hipStream_t st, const GconvEpi* e = nullptr, bool plan_only = false) {
   const int NR = dim == 3 ? 9 : 3;
   const size_t wbytes = (size_t)NR * a.KB * 256 * 4;
   // Tile budget: this kernel likes BIG tiles (one 1024-thread workgroup per CU: long MFMA runs per barrier, little
@@ -2028,15 +2149,17 @@ int launch_fwd4(GconvArgs a, int dim, hipStream_t st) {
   a.msplit = pick_msplit(a);
   dim3 grid(a.nD * a.nH * a.msplit, a.groups, a.B);
   const int threads = lds > 48 * 1024 ? kThreadsBig : kThreads;
+  if (plan_only) return CT_OK;
+  if (e != nullptr) return launch_fwd4_norm(a, *e, dim, grid, threads, lds, st);
   note(threads == kThreadsBig ? "quad_1024" : "quad_256");
   if (a.msplit > 1) note("quad_msplit");
   CT_CLEAR_ERROR();
   if (dim == 2) {
     if (set_lds_attr(gconv_fwd4_kernel<2>, lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL(gconv_fwd4_kernel<2>, grid, dim3(threads), lds, st, a);
+    hipLaunchKernelGGL(gconv_fwd4_kernel<2>, grid, dim3(threads), lds, st, fwd_args<false>(a, nullptr));
   } else {
     if (set_lds_attr(gconv_fwd4_kernel<3>, lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL(gconv_fwd4_kernel<3>, grid, dim3(threads), lds, st, a);
+    hipLaunchKernelGGL(gconv_fwd4_kernel<3>, grid, dim3(threads), lds, st, fwd_args<false>(a, nullptr));
   }
   CT_CHECK_LAUNCH();
   return CT_OK;
@@ -2044,7 +2167,7 @@ int launch_fwd4(GconvArgs a, int dim, hipStream_t st) {
 
 
 // K-split form for wide groups (> 32 input channels per group): see gconv_fwd4k_kernel
-int launch_fwd4k(GconvArgs a, int dim, hipStream_t st) {
+int launch_fwd4k(GconvArgs a, int dim, hipStream_t st, const GconvEpi* e = nullptr, bool plan_only = false) {
   const int NR = dim == 3 ? 9 : 3;
   const int MT = (a.Cout + 15) / 16;
   constexpr int kWaves = kThreadsBig / 64;
@@ -2072,6 +2195,8 @@ int launch_fwd4k(GconvArgs a, int dim, hipStream_t st) {
     const int maxi = items <= kWaves ? 1 : (items <= 2 * kWaves ? 2 : 4);
     // whole 16-channel rows at 16-byte aligned addresses move by LDS-DMA
     const int dma = (a.Cin % 16 == 0 && a.Cout % 16 == 0 && (((uintptr_t)a.w) & 15) == 0) ? 1 : 0;
+    if (plan_only) return CT_OK;
+    if (e != nullptr) return launch_fwd4k_norm(t, *e, dim, pass, maxi, dma, grid, lds, st);
     note(pass == 0 ? (dma ? "ksplit_one_dma" : "ksplit_one_elem") : (dma ? "ksplit_tiled_dma" : "ksplit_tiled_elem"));
     note(maxi == 1 ? "ksplit_items1" : maxi == 2 ? "ksplit_items2" : "ksplit_items4");
     if (msplit > 1) note("ksplit_msplit");
@@ -2079,7 +2204,7 @@ int launch_fwd4k(GconvArgs a, int dim, hipStream_t st) {
 #define CT_F4K_LAUNCH(DIMV, MAXIV, TRV)                                                                \
     do {                                                                                               \
       if (set_lds_attr(gconv_fwd4k_kernel<DIMV, MAXIV, TRV>, lds) != CT_OK) return CT_ELAUNCH;         \
-      hipLaunchKernelGGL((gconv_fwd4k_kernel<DIMV, MAXIV, TRV>), grid, dim3(kThreadsBig), lds, st, t, dma); \
+      hipLaunchKernelGGL((gconv_fwd4k_kernel<DIMV, MAXIV, TRV>), grid, dim3(kThreadsBig), lds, st, fwd_args<false>(t, nullptr), dma); \
     } while (0)
 #define CT_F4K_MAXI(DIMV, TRV) \
     do { if (maxi == 1) CT_F4K_LAUNCH(DIMV, 1, TRV); else if (maxi == 2) CT_F4K_LAUNCH(DIMV, 2, TRV); else CT_F4K_LAUNCH(DIMV, 4, TRV); } while (0)
@@ -2109,25 +2234,30 @@ int tiny_cob(const GconvArgs& a, int dim) {
   return tiny_lds(a, dim, cob) <= (size_t)kLdsBudgetMax ? cob : 0;
 }
 
-int launch_tiny(GconvArgs a, int dim, int cob, hipStream_t st) {
+int launch_tiny(GconvArgs a, int dim, int cob, hipStream_t st, const GconvEpi* e = nullptr) {
   const size_t lds = tiny_lds(a, dim, cob);
   dim3 grid((a.Cout + cob - 1) / cob, a.groups);
+  if (e != nullptr) return launch_tiny_norm(a, *e, dim, cob, grid, lds, st);
   note(dim == 2 ? "dense2d" : "dense3d");
   CT_CLEAR_ERROR();
   if (dim == 2) {
     if (set_lds_attr(gconv_tiny_kernel<2>, lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL(gconv_tiny_kernel<2>, grid, dim3(256), lds, st, a, cob);
+    hipLaunchKernelGGL(gconv_tiny_kernel<2>, grid, dim3(256), lds, st, fwd_args<false>(a, nullptr), cob);
   } else {
     if (set_lds_attr(gconv_tiny_kernel<3>, lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL(gconv_tiny_kernel<3>, grid, dim3(256), lds, st, a, cob);
+    hipLaunchKernelGGL(gconv_tiny_kernel<3>, grid, dim3(256), lds, st, fwd_args<false>(a, nullptr), cob);
   }
   CT_CHECK_LAUNCH();
   return CT_OK;
 }
 
-int launch_fwd(GconvArgs a, int dim, hipStream_t st) {
-  if (const int cob = tiny_cob(a, dim)) return launch_tiny(a, dim, cob, st);
+// e: the NORM write-out (ct_gconv_fwd_norm) on the families that carry it — dense 2^d, K-split, quad; the others return CT_EINVAL
+// before anything is launched.  plan_only (ct_gconv_fwd_norm_supported): the same walk with nothing noted and nothing launched.
+int launch_fwd(GconvArgs a, int dim, hipStream_t st, const GconvEpi* e = nullptr, bool plan_only = false) {
+  const bool norm = e != nullptr || plan_only;
+  if (const int cob = tiny_cob(a, dim)) return plan_only ? CT_OK : launch_tiny(a, dim, cob, st, e);
   const bool rows16 = (a.W & 3) == 0 && ((((uintptr_t)a.x) | ((uintptr_t)a.y)) & 15) == 0;
+  if (norm && (!rows16 || (a.Cin == 4 && a.Cout == 4))) return CT_EINVAL;     // the four-channel kernels and the one-position form
   // large four-channel volumes (the zoo's 32^3 C4 head at B8: 74 vs 93 us) take the matrix-core kernel; below ~2 M positions
   // (B2: 31 vs 30 us, 16^3: 29 vs 16) its per-slice barriers cost more than the vector ALU's extra multiply-adds
   // (debug bit 1 = never, bit 2 = always)
@@ -2139,15 +2269,16 @@ int launch_fwd(GconvArgs a, int dim, hipStream_t st) {
   if (rows16 && a.Cin == 4 && a.Cout == 4) return launch_c4(a, dim, st);
   const unsigned dbg_cin = (t_gconv_debug.load(std::memory_order_relaxed) >> 8) & 0xffu;
   if (rows16 && a.Cin >= (dbg_cin ? (int)dbg_cin : 32)) {      // wide groups (>= 32 input channels): contraction in blocks of 16
-    const int r = launch_fwd4k(a, dim, st);
+    const int r = launch_fwd4k(a, dim, st, e, plan_only);
     if (r != CT_EINVAL) return r;
   }
   if (rows16) {
     // the quad form keeps the whole filter bank of a 16-row block in LDS ([rows][KB][4][16][4] floats): with 64 input
     // channels per group in 3D that alone is 147 KiB — such shapes take the K-split form above
-    const int r = launch_fwd4(a, dim, st);
+    const int r = launch_fwd4(a, dim, st, e, plan_only);
     if (r != CT_EINVAL) return r;
   }
+  if (norm) return CT_EINVAL;
   const size_t wbytes = (size_t)a.taps * a.KB * 64 * 4;
   // short rows (W < 16: the 8^3 volumes) do better on the minimum-halo tiles, the others on the depth-first ones (measured)
   const bool ok = a.W < 16 ? (plan_tiles_min_halo(a, dim, 0, wbytes, a.KB * 4, 16, kLdsBudget) ||
@@ -2467,6 +2598,55 @@ bool wrw_plan_ok(GconvArgs a, int dim) {
   return plan_tiles(a, dim, (size_t)16 * 4, 1024 + red_bytes, 16, 4, kLdsBudgetWrw);
 }
 
+// ---- launches of the NORM variants: last on purpose (see launch_fwd4_norm's declaration) ----
+int launch_fwd4_norm(const GconvArgs& a, const GconvEpi& e, int dim, dim3 grid, int threads, size_t lds, hipStream_t st) {
+  note(threads == kThreadsBig ? "quad_1024" : "quad_256");
+  if (a.msplit > 1) note("quad_msplit");
+  CT_CLEAR_ERROR();
+  if (dim == 2) {
+    if (set_lds_attr(gconv_fwd4_kernel<2, true>, lds) != CT_OK) return CT_ELAUNCH;
+    hipLaunchKernelGGL((gconv_fwd4_kernel<2, true>), grid, dim3(threads), lds, st, fwd_args<true>(a, &e));
+  } else {
+    if (set_lds_attr(gconv_fwd4_kernel<3, true>, lds) != CT_OK) return CT_ELAUNCH;
+    hipLaunchKernelGGL((gconv_fwd4_kernel<3, true>), grid, dim3(threads), lds, st, fwd_args<true>(a, &e));
+  }
+  CT_CHECK_LAUNCH();
+  return CT_OK;
+}
+
+int launch_fwd4k_norm(const GconvArgs& t, const GconvEpi& e, int dim, int pass, int maxi, int dma, dim3 grid, size_t lds, hipStream_t st) {
+  note(pass == 0 ? (dma ? "ksplit_one_dma" : "ksplit_one_elem") : (dma ? "ksplit_tiled_dma" : "ksplit_tiled_elem"));
+  note(maxi == 1 ? "ksplit_items1" : maxi == 2 ? "ksplit_items2" : "ksplit_items4");
+  if (t.msplit > 1) note("ksplit_msplit");
+  CT_CLEAR_ERROR();
+#define CT_F4K_NORM(DIMV, MAXIV)                                                                       \
+  do {                                                                                                 \
+    if (set_lds_attr(gconv_fwd4k_kernel<DIMV, MAXIV, false, true>, lds) != CT_OK) return CT_ELAUNCH;   \
+    hipLaunchKernelGGL((gconv_fwd4k_kernel<DIMV, MAXIV, false, true>), grid, dim3(kThreadsBig), lds, st, fwd_args<true>(t, &e), dma); \
+  } while (0)
+#define CT_F4K_NORM_MAXI(DIMV) \
+  do { if (maxi == 1) CT_F4K_NORM(DIMV, 1); else if (maxi == 2) CT_F4K_NORM(DIMV, 2); else CT_F4K_NORM(DIMV, 4); } while (0)
+  if (dim == 2) CT_F4K_NORM_MAXI(2); else CT_F4K_NORM_MAXI(3);
+#undef CT_F4K_NORM_MAXI
+#undef CT_F4K_NORM
+  CT_CHECK_LAUNCH();
+  return CT_OK;
+}
+
+int launch_tiny_norm(const GconvArgs& a, const GconvEpi& e, int dim, int cob, dim3 grid, size_t lds, hipStream_t st) {
+  note(dim == 2 ? "dense2d" : "dense3d");
+  CT_CLEAR_ERROR();
+  if (dim == 2) {
+    if (set_lds_attr(gconv_tiny_kernel<2, true>, lds) != CT_OK) return CT_ELAUNCH;
+    hipLaunchKernelGGL((gconv_tiny_kernel<2, true>), grid, dim3(256), lds, st, fwd_args<true>(a, &e), cob);
+  } else {
+    if (set_lds_attr(gconv_tiny_kernel<3, true>, lds) != CT_OK) return CT_ELAUNCH;
+    hipLaunchKernelGGL((gconv_tiny_kernel<3, true>), grid, dim3(256), lds, st, fwd_args<true>(a, &e), cob);
+  }
+  CT_CHECK_LAUNCH();
+  return CT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2482,6 +2662,34 @@ int ct_gconv_fwd(const float* x, const float* w, const float* bias, float* y,
   a.x = x; a.w = w; a.bias = bias; a.y = y; a.transposed = 0;
   note_reset();
   return launch_fwd(a, dim, (hipStream_t)s);
+}
+
+int ct_gconv_fwd_norm_supported(int B, int groups, int Cin, int Cout, int dim, const int* W) {
+  GconvArgs a = {};                                                // (null tensors: on the 16-byte grid)
+  if (gconv_common(a, B, groups, Cin, Cout, dim, W) != CT_OK) return 0;
+  return launch_fwd(a, dim, nullptr, nullptr, /*plan_only=*/true) == CT_OK ? 1 : 0;
+}
+
+int ct_gconv_fwd_norm(const float* x, const float* w, const float* bias, const ct_gconv_norm* norm, const float* skip,
+                      const ct_gconv_norm* skip_norm, int relu, float* y, int B, int groups, int Cin, int Cout, int dim, const int* W,
+                      ct_stream_t s) {
+  if (!x || !w || !y || !norm || (skip_norm && !skip)) return CT_EINVAL;
+  GconvEpi e = {};
+  const ct_gconv_norm* ns[2] = {norm, skip_norm};
+  GconvNorm* ds[2] = {&e.n, &e.sn};
+  for (int i = 0; i < 2; ++i) {
+    if (!ns[i]) continue;
+    if (!ns[i]->weight || !ns[i]->bias || !ns[i]->running_mean || !ns[i]->running_var || !(ns[i]->eps >= 0.0f)) return CT_EINVAL;
+    *ds[i] = GconvNorm{ns[i]->weight, ns[i]->bias, ns[i]->running_mean, ns[i]->running_var, ns[i]->eps};
+  }
+  e.skip = skip; e.relu = relu;
+  if ((((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)y) | ((uintptr_t)skip)) & 15) return CT_EINVAL;
+  GconvArgs a = {};
+  int r = gconv_common(a, B, groups, Cin, Cout, dim, W);
+  if (r != CT_OK) return r;
+  a.x = x; a.w = w; a.bias = bias; a.y = y; a.transposed = 0;
+  note_reset();
+  return launch_fwd(a, dim, (hipStream_t)s, &e);
 }
 
 int ct_gconv_bwd_data(const float* g_y, const float* w, float* g_x,

@@ -10,6 +10,7 @@ reference's state dicts load with strict=True.
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .. import ops
 from .gconv import GroupedConv2d, GroupedConv3d
 
 # nn.Conv{2,3}d subclasses: 3^d / stride 1 / pad 1 layers run on the MFMA kernels, 1x1 skips on MIOpen
@@ -33,6 +34,9 @@ class _BasicBlockNd(nn.Module):
                                    nn.ReLU(inplace=True))
 
     def forward(self, x):
+        conv, bn = self.block[0], self.block[1]
+        if ops.gconv_norm_eligible(conv, bn, x):        # eval mode, nothing to record: the norm and the ReLU in the conv's stores
+            return ops.gconv_bn_eval(x, conv, bn, True)
         return self.block(x)
 
 
@@ -51,7 +55,20 @@ class _ResBlockNd(nn.Module):
             self.skip_con = nn.Sequential(*_conv_bn(self.nd, in_planes, out_planes, 1, groups))
 
     def forward(self, x):
-        return F.relu(self.res_branch(x) + self.skip_con(x), inplace=True)
+        conv1, bn1, _, conv2, bn2 = self.res_branch
+        if not ops.gconv_norm_eligible(conv1, bn1, x):
+            return F.relu(self.res_branch(x) + self.skip_con(x), inplace=True)
+        # eval mode with nothing for autograd to record: two convolution launches that norm, add the skip and clip in their stores
+        # (ops.gconv_bn_eval) and the skip's batched GEMM, whose norm goes into the second one
+        h = ops.gconv_bn_eval(x, conv1, bn1, True)
+        skip, skip_bn = x, None
+        if len(self.skip_con):
+            skip, skip_bn = self.skip_con[0](x), self.skip_con[1]
+        if ops.gconv_norm_eligible(conv2, bn2, h, skip, skip_bn):
+            return ops.gconv_bn_eval(h, conv2, bn2, True, skip, skip_bn)
+        if skip_bn is not None:
+            skip = skip_bn(skip)
+        return F.relu(bn2(conv2(h)) + skip, inplace=True)
 
 
 class Basic2DBlock(_BasicBlockNd):

@@ -2533,3 +2533,108 @@ def mhct_core_norm(keys, features, pts_padding, weight, bias, tensor_size, heads
                                              am_ptr, None, None, _ptr(occ), _ptr(ws), ws.numel(), B, heads, C, N, dim,
                                              _lib.int_array(W), _stream()), "ct_mhct_core_fwd_norm")
     return _norm_target_done(target, view, own), occ
+
+
+# ---------------------------------------------------------------------------
+# eval-mode norms of the grouped-conv Res blocks in the convolution's write-out (ct_gconv_fwd_norm)
+# ---------------------------------------------------------------------------
+# Res2DBlock / Res3DBlock / Basic2DBlock / Basic3DBlock (layers/grouped_conv.py) in eval mode: relu?(bn(conv(x)) + bn'?(skip)) in
+# the stores of the convolution kernel that holds the value, so a Res block costs two convolution launches and the skip GEMM and
+# no norm, add or ReLU pass.  The results carry the bits of ct_gconv_fwd, ct_bn_eval_group_fwd, torch.add and torch.relu in a row;
+# where the shape runs on a kernel without the write-out (four-channel groups, the one-position form) exactly that sequence is
+# composed instead, so those shapes leave the torch norms too.  Forward only, consulted only where BN_EVAL already routes to
+# the eval kernels.  "0": the modules' own path (A/B runs).
+GCONV_NORM = os.environ.get("CLOUDCT_GCONV_NORM", "1") != "0"
+_GCONV_BN_TYPES = (torch.nn.BatchNorm2d, torch.nn.BatchNorm3d, torch.nn.SyncBatchNorm)
+_gconv_norm_supported = {}
+
+
+def _gconv_bn_ok(bn, C, device):
+    return (type(bn) in _GCONV_BN_TYPES and not bn.training and bn.affine and bn.track_running_stats
+            and bn.running_mean is not None and bn.running_var is not None and bn.num_features == C
+            and bn.weight.dtype == torch.float32 and bn.running_mean.dtype == torch.float32
+            and bn.weight.device == device and bn.running_mean.device == device)
+
+
+def gconv_norm_eligible(conv, bn, x, skip=None, skip_bn=None):
+    """True when relu?(bn(conv(x)) + skip_bn?(skip)) can run as gconv_bn_eval: ops.BN_EVAL and ops.GCONV_NORM; `conv` a grouped 3^d
+    convolution the MFMA kernels take for x (layers.gconv._eligible: CUDA fp32, kernel 3, stride 1, padding 1); every norm an
+    nn.BatchNorm2d / nn.BatchNorm3d / nn.SyncBatchNorm (exactly) in eval mode, affine, with running statistics over the
+    convolution's output channels, fp32, on x's device; `skip` a CUDA fp32 tensor of the output's shape; and nothing for autograd
+    to record."""
+    if not (BN_EVAL and GCONV_NORM and isinstance(conv, torch.nn.modules.conv._ConvNd) and x.is_cuda and x.dim() in (4, 5)
+            and x.dim() - 2 == len(conv.kernel_size) and x.size(1) == conv.in_channels):
+        return False
+    from .layers.gconv import _eligible
+    if not _eligible(conv, x):
+        return False
+    C = conv.out_channels
+    if not _gconv_bn_ok(bn, C, x.device) or (skip_bn is not None and (skip is None or not _gconv_bn_ok(skip_bn, C, x.device))):
+        return False
+    if skip is not None and not (skip.is_cuda and skip.dtype == torch.float32 and skip.device == x.device
+                                 and tuple(skip.shape) == (x.size(0), C) + tuple(x.shape[2:])):
+        return False
+    N = 1
+    for w in x.shape[2:]:
+        N *= int(w)
+    key = (x.size(0), C, N)
+    ok = _bn_eval_supported.get(key)
+    if ok is None:
+        ok = _bn_eval_supported[key] = bool(_lib.load().ct_bn_eval_supported(*key))
+    watched = [x, conv.weight, conv.bias, bn.weight, bn.bias, skip]
+    if skip_bn is not None:
+        watched += [skip_bn.weight, skip_bn.bias]
+    return ok and _records_nothing(*watched)
+
+
+def _gconv_norm_struct(bn):
+    """(ct_gconv_norm, the tensors it points to)"""
+    keep = (_f32c(bn.weight.detach()), _f32c(bn.bias.detach()), _f32c(bn.running_mean), _f32c(bn.running_var))
+    return _lib.GconvNorm(_ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), _ptr(keep[3]), float(bn.eps)), keep
+
+
+def gconv_bn_eval(x, conv, bn, relu, skip=None, skip_bn=None):
+    """relu?(bn(conv(x)) + skip_bn?(skip)) of a grouped 3^d convolution and eval-mode norms; the caller checked
+    gconv_norm_eligible(conv, bn, x, skip, skip_bn).  One ct_gconv_fwd_norm launch where ct_gconv_fwd_norm_supported takes the
+    shape and the tensors lie on the 16-byte grid; else the sequence whose bits that launch carries: ct_gconv_fwd, one
+    ct_bn_eval_group_fwd (both norms), torch add and ReLU."""
+    _dev(x, skip)
+    x, w = _f32c(x), _f32c(conv.weight.detach())
+    b = _f32c(conv.bias.detach()) if conv.bias is not None else None
+    skip = _f32c(skip) if skip is not None else None
+    B, G = x.size(0), conv.groups
+    Cin, Cout = conv.in_channels // G, conv.out_channels // G
+    W = list(x.shape[2:])
+    nd = len(W)
+    lib = _lib.load()
+    key = (B, G, Cin, Cout, tuple(W))
+    fused = _gconv_norm_supported.get(key)
+    if fused is None:
+        fused = _gconv_norm_supported[key] = bool(lib.ct_gconv_fwd_norm_supported(B, G, Cin, Cout, nd, _lib.int_array(W)))
+    y = torch.empty(B, G * Cout, *W, device=x.device, dtype=torch.float32)
+    if fused and all(t is None or t.data_ptr() % 16 == 0 for t in (x, w, y, skip)):
+        norm, keep = _gconv_norm_struct(bn)
+        snorm, skeep = _gconv_norm_struct(skip_bn) if skip_bn is not None else (None, None)
+        with _on(x.device):
+            _lib.check(lib.ct_gconv_fwd_norm(_ptr(x), _ptr(w), _ptr(b), ctypes.addressof(norm), _ptr(skip),
+                                             ctypes.addressof(snorm) if snorm is not None else None, int(bool(relu)), _ptr(y),
+                                             B, G, Cin, Cout, nd, _lib.int_array(W), _stream()), "ct_gconv_fwd_norm")
+        return y
+    # the composed sequence: four-channel groups, the one-position form, tensors off the 16-byte grid
+    N = y[0, 0].numel()
+    C = G * Cout
+    with _on(x.device):
+        _lib.check(lib.ct_gconv_fwd(_ptr(x), _ptr(w), _ptr(b), _ptr(y), B, G, Cin, Cout, nd, _lib.int_array(W), _stream()),
+                   "ct_gconv_fwd")
+        out = torch.empty_like(y)
+        items = [_bn_eval_item(bn, _ptr(y), 0, _ptr(out), 0, relu and skip is None)]
+        t = skip
+        if skip_bn is not None:
+            t = torch.empty_like(skip)
+            items.append(_bn_eval_item(skip_bn, _ptr(skip), 0, _ptr(t), 0, False))
+        _bn_eval_group(items, B, N)
+    if t is not None:
+        out.add_(t)
+        if relu:
+            torch.relu_(out)
+    return out

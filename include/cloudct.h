@@ -488,6 +488,35 @@ int ct_gconv_bwd_weight(const float* x, const float* g_y, float* g_w, float* g_b
                         int B, int groups, int Cin, int Cout, int dim, const int* W, ct_stream_t s);
 
 /* ------------------------------------------------------------------------
+ * The forward convolution with the eval-mode BatchNorm, the skip connection and the ReLU of a grouped Res block
+ * (Res2DBlock / Res3DBlock / Basic2DBlock / Basic3DBlock in eval mode) in its write-out:
+ *   y = relu?( bn(conv(x)) + bn'?(skip) )
+ * Per output element, every operation one fp32 rounding (contraction is off for the whole library), c its channel:
+ *   v = the value ct_gconv_fwd stores (the same bits, bias included)
+ *   o = ((v - running_mean[c]) * rs[c]) * weight[c] + bias[c],   rs[c] = 1.0f / sqrtf(running_var[c] + eps)
+ *       (the operation sequence of ct_bn_eval_group_fwd; no folded scale or shift)
+ *   with skip:      t = skip_norm ? ((s - mean'[c]) * rs'[c]) * weight'[c] + bias'[c] : s;   o = o + t
+ *   with relu != 0: o = fmaxf(o, 0.0f), after the add
+ * Bit-equality contract: y holds exactly the bits of (1) ct_gconv_fwd into a scratch tensor, (2) ct_bn_eval_group_fwd on it
+ * viewed as [B, C, volume], with relu = 0 when a skip is given and the caller's relu otherwise, (3) with skip_norm the same
+ * on skip with relu = 0, (4) torch.add, (5) torch.relu.  One difference: a NaN sum is stored as 0 here (fmaxf) and as NaN by
+ * torch.relu.
+ *   norm       required; weight / bias / running_mean / running_var f32[groups*Cout], all required; eps >= 0
+ *   skip       f32[B, groups*Cout, *W] | NULL, read with the index and width of the y store;  skip_norm  NULL = added as it is
+ * Only y is written; y overlaps neither x nor skip.  No atomics: bitwise reproducible.
+ * The write-out exists on the K-split, quad and dense 2^d forward kernels; ct_gconv_fwd_norm_supported is 1 exactly where
+ * ct_gconv_fwd takes one of them for tensors on the 16-byte grid, and 0 on the four-channel kernels and the one-position form
+ * (compose the sequence above there).  The call launches the one kernel ct_gconv_fwd launches for the same arguments
+ * (ct_debug_last_launch: the same tags) and has no two-launch fallback.  CT_EINVAL before any launch: a NULL required pointer,
+ * skip_norm without skip, eps < 0 or NaN, x / w / y / skip off the 16-byte grid, a shape ct_gconv_fwd_norm_supported refuses.
+ * ---------------------------------------------------------------------- */
+typedef struct { const float* weight; const float* bias; const float* running_mean; const float* running_var; float eps; } ct_gconv_norm;
+int ct_gconv_fwd_norm_supported(int B, int groups, int Cin, int Cout, int dim, const int* W);
+int ct_gconv_fwd_norm(const float* x, const float* w, const float* bias, const ct_gconv_norm* norm,
+                      const float* skip, const ct_gconv_norm* skip_norm, int relu, float* y,
+                      int B, int groups, int Cin, int Cout, int dim, const int* W, ct_stream_t s);
+
+/* ------------------------------------------------------------------------
  * Plane-resident MHCT core: the part of a MultiHead block between its norms,
  *   out = Slice(lattice, conv(Splat(lattice, values)))                (layers/multihead_ct.py:99-107:
  *   DifferentiablePositions -> Splat (max, zero floor) -> grouped 3^dim conv with bias -> Slice;
