@@ -337,6 +337,9 @@ SIGNATURES = {
     "ct_pw_gemm_rs_add": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _sz, _i, _i, _i, _i, _vp]),
     "ct_pw_gemm_norm_amax_len": (_i, [_i, _i, _i]),
     "ct_pw_gemm_rs_norm": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "ct_set_pw_precision": (None, [_i]),
+    "ct_get_pw_precision": (_i, []),
+    "ct_pw_precision_override": (None, [_i]),
     "ct_slice_fwd_norm_amax_len": (_i, [_i, _i, _i, _i, _i, _ip]),
     "ct_slice_fwd_norm": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _ip, _vp]),
     "ct_mhct_core_fwd_norm_amax_len": (_i, [_i, _i, _i, _i, _i, _ip]),

@@ -22,7 +22,13 @@
 // cut into chunks, each chunk's partial [Co,Ci] tile goes to a slab and a second kernel adds the slabs in a fixed order
 // (deterministic).  The per-tensor maxima arrive as partial maxima (ct_amax_f32's per-block ones, or what the kernel that
 // wrote the operand left per channel) and are folded when the kernel starts.  HISTORY.md §4.9 has the measurements.
+//
+// Precision mode (ct_set_pw_precision, include/cloudct.h).  CT_PW_PRECISION_HIGH runs the TERMS = 1
+// instantiation of the same kernel: h alone (11-bit significands, TF32-class — gfx950 has no xf32 MFMA), one convert per
+// element, one MFMA per product, the two stages of A_h / B_h in 32 KiB, everything else — tile, waves, loads two K-steps ahead,
+// scales, epilogues, the weight gradient's slabs — as above.  The default mode's instantiation is untouched by it.
 #include "ct_common.h"
+#include <atomic>
 #include <cstdlib>
 #include <type_traits>
 
@@ -38,6 +44,10 @@ constexpr int kPwStageBytes = 2 * kPwStage * 2;         // two stages
 // behind the stages: the scale exponents of the tile's 128 A rows and 128 B rows / columns (kept to the epilogue) and the
 // scratch they are folded through
 constexpr int kPwLdsBytes = kPwStageBytes + (256 + 1024) * 4;
+// The one-term instantiation (CT_PW_PRECISION_HIGH) stages the h images only: A_h, B_h, 32 KiB for the two stages.
+constexpr int kPwStage1 = 2 * kPwImg;
+constexpr int kPwStageBytes1 = 2 * kPwStage1 * 2;
+constexpr int kPwLdsBytes1 = kPwStageBytes1 + (256 + 1024) * 4;
 
 struct PwArgs {
   const float* A; const float* B; float* C;
@@ -251,6 +261,37 @@ __device__ __forceinline__ void pw_write(const unsigned (&h)[4], const unsigned 
   *(uint4*)(imgL + o) = make_uint4(l[0], l[1], l[2], l[3]);
 }
 
+// One-term form: eight values -> h = f16(s x) only, one v_fma_mix per element, no l term.  The four (k, k+1) pairs of the
+// thread (KMAJOR: r[2i], r[2i+1]; else r[i], r[4+i]) as one block: every half-register write is followed by three
+// instructions of the other pairs, the last one by the wait state.
+template <bool KMAJOR>
+__device__ __forceinline__ void pw_cvt4(const float (&r)[kPwR], float s, unsigned (&h)[4]) {
+  constexpr int a = KMAJOR ? 2 : 1, b = KMAJOR ? 1 : 4;      // pair i = (r[a * i], r[a * i + b])
+  asm("v_fma_mixlo_f16 %0, %4, %12, 0\n\t"
+      "v_fma_mixlo_f16 %1, %6, %12, 0\n\t"
+      "v_fma_mixlo_f16 %2, %8, %12, 0\n\t"
+      "v_fma_mixlo_f16 %3, %10, %12, 0\n\t"
+      "v_fma_mixhi_f16 %0, %5, %12, 0\n\t"
+      "v_fma_mixhi_f16 %1, %7, %12, 0\n\t"
+      "v_fma_mixhi_f16 %2, %9, %12, 0\n\t"
+      "v_fma_mixhi_f16 %3, %11, %12, 0\n\t"
+      "s_nop 0"
+      : "=&v"(h[0]), "=&v"(h[1]), "=&v"(h[2]), "=&v"(h[3])
+      : "v"(r[0]), "v"(r[b]), "v"(r[a]), "v"(r[a + b]), "v"(r[2 * a]), "v"(r[2 * a + b]), "v"(r[3 * a]), "v"(r[3 * a + b]), "v"(s));
+}
+template <bool KMAJOR>
+__device__ __forceinline__ void pw_write1(const unsigned (&h)[4], _Float16* imgH, int wave, int t) {
+  const int o = KMAJOR ? pw_slot(t >> 2, t & 3) : ((2 * wave + ((t >> 5) & 1)) * kPwTile + 4 * (t & 31)) * 2;
+  *(uint4*)(imgH + o) = make_uint4(h[0], h[1], h[2], h[3]);
+}
+template <bool KMAJOR>
+__device__ __forceinline__ void pw_store1(float (&r)[kPwR], unsigned ok, _Float16* imgH, float s, int wave, int t) {
+  pw_mask(r, ok);
+  unsigned h[4];
+  pw_cvt4<KMAJOR>(r, s, h);
+  pw_write1<KMAJOR>(h, imgH, wave, t);
+}
+
 // fragment of the 32x32x16 MFMA for lane (row, k8 group g) of an image
 template <bool KMAJOR>
 __device__ __forceinline__ pw_h8 pw_frag(const _Float16* img, int row, int sw, int g) {
@@ -263,10 +304,16 @@ __device__ __forceinline__ pw_h8 pw_frag(const _Float16* img, int row, int sw, i
   }
 }
 
-template <bool A_KMAJOR, bool B_KMAJOR, bool ADD = false, bool NORM = false>
+// TERMS = 3: the products above.  TERMS = 1 (CT_PW_PRECISION_HIGH): h = f16(s x) alone — one convert per element, no l
+// image formed, staged or read, one MFMA per product; the same scales, fp32 accumulation and exact epilogue rescale.
+template <bool A_KMAJOR, bool B_KMAJOR, bool ADD = false, bool NORM = false, int TERMS = 3>
 __global__ void __launch_bounds__(kPwThreads, 4) pw_gemm_kernel(std::conditional_t<NORM, PwNormArgs, PwArgs> aa) {
+  static_assert(TERMS == 3 || TERMS == 1, "three f16 terms per product, or one");
   extern __shared__ __attribute__((aligned(16))) _Float16 pw_lds[];
   const PwArgs& a = aa;
+  // halves per stage, bytes of the two stages, the B_h image inside a stage
+  constexpr int kStage = TERMS == 3 ? kPwStage : kPwStage1, kStageBytes = TERMS == 3 ? kPwStageBytes : kPwStageBytes1;
+  constexpr int kImgB = TERMS == 3 ? 2 * kPwImg : kPwImg;
   // blocks that share an XCD (id % 8) take consecutive tiles: the M tiles of one [K, 128] operand panel run side by side on
   // one L2 (bijective form of the remap, cdna_hip_programming.md §5)
   const int nwg = gridDim.x, xcd = blockIdx.x & 7, q = nwg >> 3, rr = nwg & 7;
@@ -312,7 +359,7 @@ __global__ void __launch_bounds__(kPwThreads, 4) pw_gemm_kernel(std::conditional
   // its k-contiguous arrangement): the same with the row's own maximum — a channel 2^-20 below the tensor's maximum keeps
   // its 22 bits instead of sinking into f16's subnormals — and the factor comes out of the row's outputs exactly.  A
   // row-contiguous operand (x / g_y of forward and data gradient: k = channel) can only have ONE scale over k.
-  int* etab = (int*)((char*)pw_lds + kPwStageBytes);      // [128] A rows of the tile | [128] B rows (= output columns)
+  int* etab = (int*)((char*)pw_lds + kStageBytes);      // [128] A rows of the tile | [128] B rows (= output columns)
   {
     unsigned* scr = (unsigned*)(etab + 256);              // [4][128] A | [4][128] B
     const int i = t & 127, part = t >> 7;
@@ -381,8 +428,13 @@ __global__ void __launch_bounds__(kPwThreads, 4) pw_gemm_kernel(std::conditional
   oka0 = pw_load<A_KMAJOR>(ra0, la, a.lda, kbeg, kend, w, t);
   okb0 = pw_load<B_KMAJOR>(rb0, lb, a.ldb, kbeg, kend, w, t);
   fetch(std::false_type{}, 1, ra1, rb1, oka1, okb1);
-  pw_store<A_KMAJOR>(ra0, oka0, pw_lds, pw_lds + kPwImg, sa, w, t);
-  pw_store<B_KMAJOR>(rb0, okb0, pw_lds + 2 * kPwImg, pw_lds + 3 * kPwImg, sb, w, t);
+  if constexpr (TERMS == 3) {
+    pw_store<A_KMAJOR>(ra0, oka0, pw_lds, pw_lds + kPwImg, sa, w, t);
+    pw_store<B_KMAJOR>(rb0, okb0, pw_lds + 2 * kPwImg, pw_lds + 3 * kPwImg, sb, w, t);
+  } else {
+    pw_store1<A_KMAJOR>(ra0, oka0, pw_lds, sa, w, t);
+    pw_store1<B_KMAJOR>(rb0, okb0, pw_lds + kImgB, sb, w, t);
+  }
   __syncthreads();
 
   // fragment rows: 64*wm + 32*i + r (A), 32*wn + r (B); k8 group 2*ks + h
@@ -402,8 +454,8 @@ __global__ void __launch_bounds__(kPwThreads, 4) pw_gemm_kernel(std::conditional
   // K-step kt: fetch step kt+2 into (xa, xb), MFMAs on stage kt&1, split step kt+1 from (ya, yb) into the other stage
   auto kstep = [&](auto whole, int kt, float (&xa)[kPwR], float (&xb)[kPwR], unsigned& xoka, unsigned& xokb, float (&ya)[kPwR],
                    float (&yb)[kPwR], unsigned yoka, unsigned yokb) {
-    const _Float16* st = pw_lds + (kt & 1) * kPwStage;
-    _Float16* nx = pw_lds + ((kt + 1) & 1) * kPwStage;
+    const _Float16* st = pw_lds + (kt & 1) * kStage;
+    _Float16* nx = pw_lds + ((kt + 1) & 1) * kStage;
     PW_T(0);
     fetch(whole, kt + 2, xa, xb, xoka, xokb);
     __builtin_amdgcn_sched_barrier(0);               // the loads go out before the MFMAs, not after them
@@ -415,18 +467,6 @@ __global__ void __launch_bounds__(kPwThreads, 4) pw_gemm_kernel(std::conditional
       pw_mask(ya, yoka);
       pw_mask(yb, yokb);
     }
-    unsigned hA[4], lA[4], hB[4], lB[4];
-    pw_h8 ah[2], al[2], bh, bl;
-    auto frags = [&](int ks) {
-      const int g = 2 * ks + h;
-      bh = pw_frag<B_KMAJOR>(st + 2 * kPwImg, rowB, sw, g);
-      bl = pw_frag<B_KMAJOR>(st + 3 * kPwImg, rowB, sw, g);
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        ah[i] = pw_frag<A_KMAJOR>(st, rowA + 32 * i, sw, g);
-        al[i] = pw_frag<A_KMAJOR>(st + kPwImg, rowA + 32 * i, sw, g);
-      }
-    };
 #define PW_MF(x, y)                                                                   \
   do {                                                                                \
     __builtin_amdgcn_sched_barrier(0);                                                \
@@ -434,24 +474,56 @@ __global__ void __launch_bounds__(kPwThreads, 4) pw_gemm_kernel(std::conditional
     acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(x[1], y, acc[1], 0, 0, 0);        \
     __builtin_amdgcn_sched_barrier(0);                                                \
   } while (0)
-    frags(0);
-    PW_MF(ah, bh);
-    pw_unit<A_KMAJOR>(ya, 0, sa, hA, lA);
-    pw_unit<A_KMAJOR>(ya, 1, sa, hA, lA);
-    PW_MF(ah, bl);
-    pw_unit<A_KMAJOR>(ya, 2, sa, hA, lA);
-    pw_unit<A_KMAJOR>(ya, 3, sa, hA, lA);
-    pw_write<A_KMAJOR>(hA, lA, nx, nx + kPwImg, w, t);
-    PW_MF(al, bh);
-    frags(1);
-    pw_unit<B_KMAJOR>(yb, 0, sb, hB, lB);
-    pw_unit<B_KMAJOR>(yb, 1, sb, hB, lB);
-    PW_MF(ah, bh);
-    pw_unit<B_KMAJOR>(yb, 2, sb, hB, lB);
-    pw_unit<B_KMAJOR>(yb, 3, sb, hB, lB);
-    pw_write<B_KMAJOR>(hB, lB, nx + 2 * kPwImg, nx + 3 * kPwImg, w, t);     // two MFMA groups ahead of the barrier
-    PW_MF(ah, bl);
-    PW_MF(al, bh);
+    if constexpr (TERMS == 3) {
+      unsigned hA[4], lA[4], hB[4], lB[4];
+      pw_h8 ah[2], al[2], bh, bl;
+      auto frags = [&](int ks) {
+        const int g = 2 * ks + h;
+        bh = pw_frag<B_KMAJOR>(st + 2 * kPwImg, rowB, sw, g);
+        bl = pw_frag<B_KMAJOR>(st + 3 * kPwImg, rowB, sw, g);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          ah[i] = pw_frag<A_KMAJOR>(st, rowA + 32 * i, sw, g);
+          al[i] = pw_frag<A_KMAJOR>(st + kPwImg, rowA + 32 * i, sw, g);
+        }
+      };
+      frags(0);
+      PW_MF(ah, bh);
+      pw_unit<A_KMAJOR>(ya, 0, sa, hA, lA);
+      pw_unit<A_KMAJOR>(ya, 1, sa, hA, lA);
+      PW_MF(ah, bl);
+      pw_unit<A_KMAJOR>(ya, 2, sa, hA, lA);
+      pw_unit<A_KMAJOR>(ya, 3, sa, hA, lA);
+      pw_write<A_KMAJOR>(hA, lA, nx, nx + kPwImg, w, t);
+      PW_MF(al, bh);
+      frags(1);
+      pw_unit<B_KMAJOR>(yb, 0, sb, hB, lB);
+      pw_unit<B_KMAJOR>(yb, 1, sb, hB, lB);
+      PW_MF(ah, bh);
+      pw_unit<B_KMAJOR>(yb, 2, sb, hB, lB);
+      pw_unit<B_KMAJOR>(yb, 3, sb, hB, lB);
+      pw_write<B_KMAJOR>(hB, lB, nx + 2 * kPwImg, nx + 3 * kPwImg, w, t);     // two MFMA groups ahead of the barrier
+      PW_MF(ah, bl);
+      PW_MF(al, bh);
+    } else {
+      // One term: both k halves' fragments are read up front (the registers the l fragments took), the converts of step kt+1
+      // sit between the two MFMA groups and both stores are out one MFMA group ahead of the barrier.
+      unsigned hA[4], hB[4];
+      pw_h8 ah0[2], ah1[2], bh0, bh1;
+      bh0 = pw_frag<B_KMAJOR>(st + kImgB, rowB, sw, h);
+      bh1 = pw_frag<B_KMAJOR>(st + kImgB, rowB, sw, 2 + h);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        ah0[i] = pw_frag<A_KMAJOR>(st, rowA + 32 * i, sw, h);
+        ah1[i] = pw_frag<A_KMAJOR>(st, rowA + 32 * i, sw, 2 + h);
+      }
+      PW_MF(ah0, bh0);
+      pw_cvt4<A_KMAJOR>(ya, sa, hA);
+      pw_write1<A_KMAJOR>(hA, nx, w, t);
+      pw_cvt4<B_KMAJOR>(yb, sb, hB);
+      pw_write1<B_KMAJOR>(hB, nx + kImgB, w, t);
+      PW_MF(ah1, bh1);
+    }
 #undef PW_MF
     PW_T(4);
     __syncthreads();
@@ -802,16 +874,36 @@ static bool pw_plan(int mode, int B, int Co, int Ci, int N, PwPlan& p) {
 // (A second, persistent 128 x 256 kernel lived here through round 4: faster stand-alone on wide weight gradients and at K >= 1024,
 // nothing inside the training steps — 17.2 / 15.2 / 32.6 vs 17.2 / 15.1 / 31.6 ms, profiles/r4_model_steps.txt — and dispatched
 // nowhere by default.  Out of the build since round 5: tools/dev/experiments/ct_pwgemm2.h.)
-template <bool AK, bool BK, bool ADD = false, bool NORM = false>
-static int pw_launch(const std::conditional_t<NORM, PwNormArgs, PwArgs>& a, int blocks, hipStream_t st) {
-  auto k = pw_gemm_kernel<AK, BK, ADD, NORM>;
+template <bool AK, bool BK, bool ADD = false, bool NORM = false, int TERMS = 3>
+static int pw_launch_terms(const std::conditional_t<NORM, PwNormArgs, PwArgs>& a, int blocks, hipStream_t st) {
+  auto k = pw_gemm_kernel<AK, BK, ADD, NORM, TERMS>;
+  constexpr int lds = TERMS == 3 ? kPwLdsBytes : kPwLdsBytes1;
   static bool attr = false;
   if (!attr) {
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, kPwLdsBytes) != hipSuccess) return CT_ELAUNCH;
+    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return CT_ELAUNCH;
     attr = true;
   }
-  hipLaunchKernelGGL(k, dim3(blocks), dim3(kPwThreads), kPwLdsBytes, st, a);
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(kPwThreads), lds, st, a);
   return CT_OK;
+}
+// terms: what pw_terms planned for this launch
+template <bool AK, bool BK, bool ADD = false, bool NORM = false>
+static int pw_launch(const std::conditional_t<NORM, PwNormArgs, PwArgs>& a, int blocks, hipStream_t st, int terms) {
+  return terms == 1 ? pw_launch_terms<AK, BK, ADD, NORM, 1>(a, blocks, st) : pw_launch_terms<AK, BK, ADD, NORM, 3>(a, blocks, st);
+}
+
+// ct_set_pw_precision: process-wide, read once per entry point where it plans its launch; ct_pw_precision_override: the calling
+// thread's entry points only (a backward that keeps its forward's mode on whichever thread autograd runs it), -1 none
+static std::atomic<int> g_pw_precision{CT_PW_PRECISION_HIGHEST};
+static thread_local int t_pw_precision_override = -1;
+static inline int pw_precision_now() {
+  return t_pw_precision_override >= 0 ? t_pw_precision_override : g_pw_precision.load(std::memory_order_relaxed);
+}
+// MFMA terms per product of this launch.  The mode is a permission: a product the one-term kernel does not win on keeps three
+// terms (DESIGN.md §4.16 has the measurements behind the rule).  The workspace does not depend on it.
+static int pw_terms(int mode, const PwPlan& p) {
+  (void)mode; (void)p;
+  return pw_precision_now() == CT_PW_PRECISION_HIGH ? 1 : 3;
 }
 
 #ifdef PW_STAMP
@@ -820,6 +912,10 @@ extern "C" void ct_debug_pw_stamp(unsigned long long* buf) { g_pw_dbg = buf; }
 #endif
 
 extern "C" {
+
+void ct_set_pw_precision(int p) { g_pw_precision.store(p == CT_PW_PRECISION_HIGH ? CT_PW_PRECISION_HIGH : CT_PW_PRECISION_HIGHEST, std::memory_order_relaxed); }
+int ct_get_pw_precision(void) { return pw_precision_now(); }
+void ct_pw_precision_override(int p) { t_pw_precision_override = p < 0 ? -1 : (p == CT_PW_PRECISION_HIGH ? CT_PW_PRECISION_HIGH : CT_PW_PRECISION_HIGHEST); }
 
 int ct_amax_f32(const float* x, int64_t n, float* amax, ct_stream_t s) {
   if (!x || !amax || n < 1 || ((uintptr_t)x & 15)) return CT_EINVAL;
@@ -919,24 +1015,25 @@ int ct_pw_gemm_rs_add(int mode, const float* a, const float* b, float* out, cons
 #endif
   g.M = p.M; g.N = p.N; g.K = p.K; g.tilesM = p.tilesM; g.tilesN = p.tilesN; g.ksplit = p.ksplit; g.Kc = p.Kc; g.Z = p.Z;
   const int blocks = p.tilesM * p.tilesN * p.Z;
+  const int terms = pw_terms(mode, p);      // the precision mode, read once
   int rc;
   if (mode == CT_PW_FWD) {            // A = W [Co][Ci] (k contiguous), B = x[b] [Ci][N] (columns contiguous)
     g.lda = Ci; g.a_bs = 0; g.ldb = N; g.b_bs = (long long)Ci * N; g.C = out; g.ldc = N; g.c_zs = (long long)Co * N;
-    rc = addend ? pw_launch<true, false, true>(g, blocks, st) : pw_launch<true, false>(g, blocks, st);
+    rc = addend ? pw_launch<true, false, true>(g, blocks, st, terms) : pw_launch<true, false>(g, blocks, st, terms);
   } else if (mode == CT_PW_DGRAD) {   // A = W^T [Ci][Co] written to the workspace (k = co contiguous), B = g_y[b] [Co][N]
     hipLaunchKernelGGL(pw_transpose_kernel, dim3((Ci + 31) / 32, (Co + 31) / 32), dim3(256), 0, st, a, (float*)workspace, Co, Ci);
     CT_CHECK_LAUNCH();
     g.A = (const float*)workspace;
     g.lda = Co; g.a_bs = 0; g.ldb = N; g.b_bs = (long long)Co * N; g.C = out; g.ldc = N; g.c_zs = (long long)Ci * N;
-    rc = addend ? pw_launch<true, false, true>(g, blocks, st) : pw_launch<true, false>(g, blocks, st);
+    rc = addend ? pw_launch<true, false, true>(g, blocks, st, terms) : pw_launch<true, false>(g, blocks, st, terms);
   } else if (mode == CT_PW_DGRAD_T) {  // a IS W^T [Ci][Co] (ct_pw_prep_weight wrote it in the layer's forward)
     g.lda = Co; g.a_bs = 0; g.ldb = N; g.b_bs = (long long)Co * N; g.C = out; g.ldc = N; g.c_zs = (long long)Ci * N;
-    rc = addend ? pw_launch<true, false, true>(g, blocks, st) : pw_launch<true, false>(g, blocks, st);
+    rc = addend ? pw_launch<true, false, true>(g, blocks, st, terms) : pw_launch<true, false>(g, blocks, st, terms);
   } else {                            // A = g_y[b] [Co][N], B = x[b] [Ci][N]: both k (= point) contiguous
     g.lda = N; g.a_bs = (long long)Co * N; g.ldb = N; g.b_bs = (long long)Ci * N; g.ldc = Ci;
     g.C = p.ws ? (float*)workspace : out;
     g.c_zs = (long long)Co * Ci;
-    rc = pw_launch<true, true>(g, blocks, st);
+    rc = pw_launch<true, true>(g, blocks, st, terms);
   }
   if (rc != CT_OK) return rc;
   CT_CHECK_LAUNCH();
@@ -992,7 +1089,7 @@ int ct_pw_gemm_rs_norm(const float* w, const float* x, const ct_bn_fwd_item* ite
 #endif
   g.M = p.M; g.N = p.N; g.K = p.K; g.tilesM = p.tilesM; g.tilesN = p.tilesN; g.ksplit = p.ksplit; g.Kc = p.Kc; g.Z = p.Z;
   g.lda = Ci; g.a_bs = 0; g.ldb = N; g.b_bs = (long long)Ci * N; g.C = nullptr; g.ldc = N; g.c_zs = 0;
-  const int rc = pw_launch<true, false, false, true>(g, p.tilesM * p.tilesN * p.Z, (hipStream_t)s);
+  const int rc = pw_launch<true, false, false, true>(g, p.tilesM * p.tilesN * p.Z, (hipStream_t)s, pw_terms(CT_PW_FWD, p));
   if (rc != CT_OK) return rc;
   CT_CHECK_LAUNCH();
   return CT_OK;

@@ -6,7 +6,8 @@ package's layers and checkpoints stay interchangeable.
 * config: the reference's YAML schema — `experiment.{root,writer_root}`, `data.{batch_size,num_points,...}`,
   `model.generator` (a python file defining `Model`; the remaining `model.*` keys are its kwargs),
   `train.{optimizer,scheduler,num_epochs,save_each,...}`, optional `restore.{generator,optimizer,new_lr}`; `train.deterministic:
-  true` (this package's own key) runs `fit` in deterministic mode (determinism.py): equal seeds, equal gradients.
+  true` (this package's own key) runs `fit` in deterministic mode (determinism.py): equal seeds, equal gradients. `train.matmul_precision:
+  high` (likewise) runs `fit` with the pointwise GEMMs in the TF32-class mode of precision.py.
   `train.freeze_norms: true` (optionally `train.freeze_norm_affine: true`; this package's own keys) fine-tunes on frozen
   norm statistics (norms.py `freeze_norms`, applied after the data-parallel wrap): the running statistics never move, no
   statistics are exchanged between ranks, validation and checkpoints are unchanged.
@@ -880,12 +881,20 @@ class Trainer:
         synchronisation per step (the reference reads the loss every step: train_segmentation.py:180-186).
 
         `train.deterministic: true` runs the whole fit in deterministic mode (determinism.py: run-to-run equal gradients from
-        the library's kernels, all five tasks); the seeds are set as without it and nothing else changes."""
-        if self.cfg["train"].get("deterministic", False):
-            from . import determinism
-            with determinism.deterministic(True):
-                return self._fit(max_iters, hip_graph, log_each)
-        return self._fit(max_iters, hip_graph, log_each)
+        the library's kernels, all five tasks); the seeds are set as without it and nothing else changes.
+
+        `train.matmul_precision: high` (or `medium` / `highest`) runs the whole fit, the validation inside it included, with
+        the pointwise-convolution GEMMs in that mode (precision.py: one f16 MFMA term per operand, TF32-class); the previous
+        mode comes back when fit returns.  With `hip_graph` the captured kernels are those of this mode."""
+        import contextlib
+        with contextlib.ExitStack() as scopes:
+            if self.cfg["train"].get("deterministic", False):
+                from . import determinism
+                scopes.enter_context(determinism.deterministic(True))
+            if self.cfg["train"].get("matmul_precision") is not None:
+                from . import precision
+                scopes.enter_context(precision.matmul_precision(self.cfg["train"]["matmul_precision"]))
+            return self._fit(max_iters, hip_graph, log_each)
 
     def _fit(self, max_iters, hip_graph, log_each):
         tr = self.cfg["train"]

@@ -9,6 +9,8 @@ forward / data gradient and an NHWC implicit-GEMM kernel bracketed by layout tra
 (tools/conv1d_bench.py, tools/pw_gemm_bench.py).
 `PointwiseConv1d` subclasses nn.Conv1d: same parameters,
 same state-dict keys, same results.
+Under `matmul_precision("high")` (precision.py) the products run one f16 MFMA term per operand (TF32-class); the backward keeps the
+mode its forward ran in.
 """
 import torch
 import torch.nn.functional as F
@@ -22,6 +24,7 @@ class _PointwiseConvFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias):
         x = x.contiguous()
         w2 = weight[:, :, 0].contiguous()
+        ctx.pw_precision = ops._prec.code()      # the three products share the forward's precision (precision.py)
         y, am_w, am_x, wt = ops.pw_forward(w2, x, ctx.needs_input_grad[0])
         am_w = am_w if am_w is not None else (None, None)       # (row maxima, column maxima) of the weight
         ctx.save_for_backward(x, w2, am_w[0], am_w[1], am_x, wt)
@@ -34,7 +37,7 @@ class _PointwiseConvFn(torch.autograd.Function):
         g_y = g_y.contiguous()
         g_b = None
         g_x, g_w = ops.pw_backward(w2, x, g_y, None if am_wr is None else (am_wr, am_wc), am_x, ctx.needs_input_grad[0],
-                                   ctx.needs_input_grad[1], Wt=wt)
+                                   ctx.needs_input_grad[1], Wt=wt, precision=ctx.pw_precision)
         if g_w is not None:
             g_w = g_w.unsqueeze(-1)                                           # [O, I, 1]
         if ctx.has_bias and ctx.needs_input_grad[2]:

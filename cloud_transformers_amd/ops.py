@@ -12,6 +12,7 @@ import torch
 
 from . import _lib
 from . import determinism as _det
+from . import precision as _prec
 
 
 def sizes_of(tensor_size, dim):
@@ -189,11 +190,22 @@ def amax_of(t, rows=False):
     return amax_rows(t) if (rows and t.dim() == 3) else amax(t)
 
 
-def pw_gemm(mode, a, b, amax_a, amax_b, B, Co, Ci, N, addend=None):
+def pw_gemm(mode, a, b, amax_a, amax_b, B, Co, Ci, N, addend=None, precision=None):
     """ct_pw_gemm on contiguous float32 tensors: PW_FWD (a = W [Co,Ci], b = x [B,Ci,N]) -> y [B,Co,N]; PW_DGRAD (a = W,
     b = g_y [B,Co,N]) -> g_x [B,Ci,N]; PW_WGRAD (a = g_y, b = x) -> g_W [Co,Ci].  amax_* from amax().  addend (contiguous,
-    shaped as the output; not for PW_WGRAD): added in the kernel's epilogue (ct_pw_gemm_rs_add)."""
+    shaped as the output; not for PW_WGRAD): added in the kernel's epilogue (ct_pw_gemm_rs_add).  precision: None = the
+    effective mode of precision.py, pushed into the library's process-wide switch ahead of the workspace query and the launch,
+    which read it; or the library constant a forward remembered (a backward that runs in its forward's mode), which goes into
+    the library's per-thread override around them instead."""
     lib = _lib.load()
+    if precision is None:
+        _prec.push(lib)
+        return _pw_gemm(lib, mode, a, b, amax_a, amax_b, B, Co, Ci, N, addend)
+    with _prec.forced(precision, lib):
+        return _pw_gemm(lib, mode, a, b, amax_a, amax_b, B, Co, Ci, N, addend)
+
+
+def _pw_gemm(lib, mode, a, b, amax_a, amax_b, B, Co, Ci, N, addend):
     dev = b.device
     if mode == PW_FWD:
         out = torch.empty(B, Co, N, device=dev, dtype=torch.float32)
@@ -246,10 +258,12 @@ def pw_forward(W, x, need_dgrad=False):
     return pw_gemm(PW_FWD, W, x, am_w[0], am_x, B, Co, Ci, N), am_w, am_x, Wt
 
 
-def pw_backward(W, x, g_y, am_w, am_x, need_x=True, need_w=True, am_g=None, Wt=None, add_gx=None):
+def pw_backward(W, x, g_y, am_w, am_x, need_x=True, need_w=True, am_g=None, Wt=None, add_gx=None, precision=None):
     """(g_x, g_W) of pw_forward for the cotangent g_y [B,Co,N] (contiguous); am_g: g_y's maxima where the caller has them; Wt:
     the transposed weight pw_forward made (else the data gradient writes its own through its workspace); add_gx: another
-    cotangent of x (a skip connection's), added to g_x inside the data gradient's epilogue where the kernel runs it."""
+    cotangent of x (a skip connection's), added to g_x inside the data gradient's epilogue where the kernel runs it; precision:
+    the library constant of the mode the forward ran in (precision.code() read there), so that a layer's three products share
+    one precision wherever and whenever autograd runs this; None = the mode in effect now."""
     Co, Ci = W.shape
     B, _, N = x.shape
     mine_x = need_x and pw_eligible(Co, Ci, N, PW_DGRAD)
@@ -266,9 +280,9 @@ def pw_backward(W, x, g_y, am_w, am_x, need_x=True, need_w=True, am_g=None, Wt=N
     def dgrad():
         if mine_x and Wt is not None and am_w is not None:
             # W^T's rows are W's columns: their maxima give the data gradient its per-row scales
-            return pw_gemm(PW_DGRAD_T, Wt, g_y, am_w[1] if am_w[1] is not None else am_w[0], am_g, B, Co, Ci, N, addend=add_gx)
+            return pw_gemm(PW_DGRAD_T, Wt, g_y, am_w[1] if am_w[1] is not None else am_w[0], am_g, B, Co, Ci, N, addend=add_gx, precision=precision)
         if mine_x:
-            return pw_gemm(PW_DGRAD, W, g_y, am_w[0] if am_w is not None else amax(W), am_g, B, Co, Ci, N, addend=add_gx)
+            return pw_gemm(PW_DGRAD, W, g_y, am_w[0] if am_w is not None else amax(W), am_g, B, Co, Ci, N, addend=add_gx, precision=precision)
         if not need_x:
             return add_gx
         g = torch.bmm(W.t().unsqueeze(0).expand(B, -1, -1), g_y)
@@ -278,7 +292,7 @@ def pw_backward(W, x, g_y, am_w, am_x, need_x=True, need_w=True, am_g=None, Wt=N
         if mine_w:
             # both operands row-scaled where their maxima are per channel: a nearly-dead channel of g_y (or of x) keeps its
             # 22 bits in its own row of g_W (include/cloudct.h, ct_pw_gemm_rs)
-            return pw_gemm(PW_WGRAD, g_y, x, am_g, am_x if am_x is not None else amax_of(x, rows=True), B, Co, Ci, N)
+            return pw_gemm(PW_WGRAD, g_y, x, am_g, am_x if am_x is not None else amax_of(x, rows=True), B, Co, Ci, N, precision=precision)
         return torch.bmm(g_y, x.transpose(1, 2)).sum(0) if need_w else None
 
     # the two gradients are independent and neither is a whole number of rounds of the chip's workgroup slots (1024 + 672
@@ -915,6 +929,7 @@ class UnionKeysValuesAdaInFn(torch.autograd.Function):
         B, Cin, N = x.shape
         Wc = torch.cat([h[0][:, :, 0] for h in heads], dim=0)
         Ct = Wc.size(0)
+        ctx.pw_precision = _prec.code()      # the layer's three products share the forward's precision (precision.py)
         y, am_w, am_x, Wt = pw_forward(Wc, x, ctx.needs_input_grad[1])
         outs, saved, meta, items, c0 = [], [], [], [], 0
         for h in heads:
@@ -971,7 +986,7 @@ class UnionKeysValuesAdaInFn(torch.autograd.Function):
             _adain_group_bwd(items, B, N)
         g_x, g_Wc = pw_backward(Wc, x, g_y, ctx.am[0], ctx.am[1], ctx.needs_input_grad[1], True,
                                 am_g=None if slots is None else slots.view(-1, Ct), Wt=ctx.am[2],
-                                add_gx=g_skip if ctx.needs_input_grad[1] else None)
+                                add_gx=g_skip if ctx.needs_input_grad[1] else None, precision=ctx.pw_precision)
         grads, r0 = [None, g_x, None], 0
         for hi, Co in enumerate(ctx.couts):
             grads += [g_Wc[r0:r0 + Co].unsqueeze(-1), g_gbs[2 * hi], g_gbs[2 * hi + 1]]
@@ -1374,6 +1389,7 @@ class UnionKeysValuesFn(torch.autograd.Function):
         B, Cin, N = x.shape
         Wc = torch.cat([h[0][:, :, 0] for h in heads], dim=0)               # [sum Co, Cin]
         Ct = Wc.size(0)
+        ctx.pw_precision = _prec.code()      # the layer's three products share the forward's precision (precision.py)
         y, am_w, am_x, Wt = pw_forward(Wc, x, ctx.needs_input_grad[2])      # [B, sum Co, N]
         outs, items, meta, c0 = [], [], [], 0
         for h in heads:
@@ -1428,7 +1444,7 @@ class UnionKeysValuesFn(torch.autograd.Function):
             bn_grads = _bn_group_bwd(items, B, N, x.device, ctx.group, count)
         g_x, g_Wc = pw_backward(Wc, x, g_y, ctx.am[0], ctx.am[1], ctx.needs_input_grad[2], True,
                                 am_g=None if slots is None else slots.view(-1, g_y.shape[1]), Wt=ctx.am[2],
-                                add_gx=g_skip if ctx.needs_input_grad[2] else None)   # g_Wc [sum Co, Cin]
+                                add_gx=g_skip if ctx.needs_input_grad[2] else None, precision=ctx.pw_precision)   # g_Wc [sum Co, Cin]
         grads, r0 = [None, None, g_x], 0
         for hi, Co in enumerate(ctx.couts):
             (gwk, gbk), (gwv, gbv) = bn_grads[2 * hi], bn_grads[2 * hi + 1]
@@ -1968,6 +1984,7 @@ class UnionKeysValuesFrozenFn(torch.autograd.Function):
         B, Cin, N = x.shape
         Wc = torch.cat([h[0][:, :, 0] for h in heads], dim=0)               # [sum Co, Cin]
         Ct = Wc.size(0)
+        ctx.pw_precision = _prec.code()      # the layer's three products share the forward's precision (precision.py)
         y, am_w, am_x, Wt = pw_forward(Wc, x, ctx.needs_input_grad[1])      # [B, sum Co, N]
         outs, items, saved, meta, c0 = [], [], [], [], 0
         for h in heads:
@@ -2023,7 +2040,7 @@ class UnionKeysValuesFrozenFn(torch.autograd.Function):
         if g_y is not None:
             g_x, g_Wc = pw_backward(Wc, x, g_y, ctx.am[0], ctx.am[1], need_x, need_W,
                                     am_g=None if slots is None else slots.view(-1, g_y.shape[1]), Wt=ctx.am[2],
-                                    add_gx=g_skip if need_x else None)      # g_Wc [sum Co, Cin]
+                                    add_gx=g_skip if need_x else None, precision=ctx.pw_precision)      # g_Wc [sum Co, Cin]
         elif need_x:
             g_x = g_skip
         grads, r0 = [None, g_x], 0
@@ -2104,6 +2121,7 @@ def pw_gemm_norm(W, x, items, want_amax=False):
     n_out = lib.ct_pw_gemm_norm_amax_len(B, Co, N) if want_amax else 0
     slots = torch.empty(n_out, device=x.device, dtype=torch.float32) if n_out else None
     arr = _bn_fwd_table(items)
+    _prec.push(lib)          # the product's precision (precision.py), read by the entry point where it plans its launch
     with _on(x.device):
         _lib.check(lib.ct_pw_gemm_rs_norm(_ptr(W), _ptr(x), _at(arr, 0), len(items), _ptr(slots), _ptr(am_w), am_w.numel(),
                                           _rows_of(am_w, Co), _ptr(am_x), am_x.numel(), None, 0, B, Co, Ci, N, _stream()),

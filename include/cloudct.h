@@ -5,7 +5,8 @@
  * Every entry point is `extern "C"`, takes plain device pointers + sizes and a
  * HIP stream (passed as void* so that this header needs no HIP include), never
  * allocates, never synchronises the device, keeps no global state — but for the
- * process-wide deterministic switch ct_set_deterministic and the ct_debug_* test
+ * process-wide deterministic switch ct_set_deterministic, the process-wide precision
+ * mode of the pointwise GEMMs ct_set_pw_precision and the ct_debug_* test
  * hooks below, host-side atomics that no kernel reads — and returns
  * an int status: CT_OK (0) or a negative CT_E* code (ct_strerror() names it).
  * All tensors are fp32, contiguous, channels-first with the point index N
@@ -45,7 +46,8 @@ extern "C" {
  * subsampling ct_voxel_bounds / ct_voxel_keys / ct_voxel_reduce and their workspace queries; then the resident ShapeNet
  * completion gather ct_completion_gather; then the deterministic switch ct_set_deterministic / ct_get_deterministic / ct_deterministic_override;
  * then Chamfer with per-cloud counts and the metric table: ct_chamfer_fwd_counts / ct_chamfer_bwd_counts / ct_rows_compact /
- * ct_chamfer_metrics; then the backward of the eval-mode norm, ct_bn_eval_group_bwd.) */
+ * ct_chamfer_metrics; then the backward of the eval-mode norm, ct_bn_eval_group_bwd; then the precision mode of the pointwise
+ * GEMMs ct_set_pw_precision / ct_get_pw_precision / ct_pw_precision_override.) */
 #define CT_ABI_VERSION 3
 
 /* status codes */
@@ -755,6 +757,35 @@ int ct_pw_gemm_norm_amax_len(int B, int Co, int N);
 int ct_pw_gemm_rs_norm(const float* w, const float* x, const ct_bn_fwd_item* items, int n, float* amax_out, const float* amax_a,
                        int n_amax_a, int rows_a, const float* amax_b, int n_amax_b, void* workspace, size_t workspace_bytes, int B,
                        int Co, int Ci, int N, ct_stream_t s);
+/* Precision mode of the pointwise GEMMs.  Process-wide host state, atomic, never read by a kernel, as the deterministic switch:
+ * every ct_pw_gemm* entry point (ct_pw_gemm, _rs, _rs_add, _rs_norm) reads the effective value ONCE, where it plans its
+ * launch.  Added under CT_ABI_VERSION 3 (additive: the loader's missing-symbol scan checks them).
+ *   CT_PW_PRECISION_HIGHEST (the default): everything above, bit for bit.
+ *   CT_PW_PRECISION_HIGH: ONE f16 term per operand — h = f16(s x) under the same per-tensor / per-row power-of-two scale
+ *     (s M in [2^13, 2^14)), one convert per element, no l term formed or staged, one v_mfma_f32_32x32x16_f16 per product,
+ *     fp32 accumulation, the exact 1/(s_a s_b) in the epilogue.  An 11-bit significand: the precision of TF32, for which gfx950
+ *     has no matrix instruction.  All four modes (CT_PW_WGRAD keeps its slabs and their fixed-order sum: still run-to-run
+ *     bit-equal), the addend and the norm epilogues; within the mode ct_pw_gemm_rs_add and ct_pw_gemm_rs_norm keep their bit
+ *     equalities with ct_pw_gemm_rs.  Zeros, NaN and inf propagate as in the default mode.
+ *     Error bound.  For an element x with scale maximum M:  |f16(s x)/s - x| <= 2^-11 |x| + 2^-38 M  (the rounding of a normal
+ *     f16; a subnormal's 2^-25 over s >= 2^13 / M).  f16 x f16 products are exact in fp32, so with da, db these element errors
+ *     one product is off by a db + b da + da db: (2^-10 + 2^-22) |a b| from the normal parts; 2^-38 (M_a |b| + M_b |a|) from
+ *     the subnormal parts against the other operand's value, 2^-11 of that again against its normal error, and subnormal
+ *     against subnormal at most 2^-38 M_a |b| once more (an element that is not flushed has |b| >= 2^-25 / s_b, a flushed one
+ *     has |db| = |b|).  With eps_acc the fp32-accumulation allowance of the default mode (2^-21 above covers it there):
+ *       |err_ij| <= (2^-10 + 2^-22 + eps_acc) * sum_k |a_ik b_kj|  +  2^-37 * ( M_a * sum_k |b_kj|  +  M_b * sum_k |a_ik| )
+ *     M_a, M_b as in ct_pw_gemm_rs: the ROW's own maxima wherever per-row scales apply.
+ *   The mode is a permission, not an order: a product the one-term kernel does not take, or does not win on, keeps three terms.
+ *   Workspace sizes do not depend on it.  Other values of p select CT_PW_PRECISION_HIGHEST.
+ * ct_pw_precision_override(p): p = 0 / 1 sets the mode for the entry points the CALLING THREAD invokes, whatever the
+ * process-wide value says, p < 0 ends the override — how a backward runs its products in its forward's precision on
+ * whichever thread it is called.  ct_get_pw_precision() returns the value in effect for the calling thread.
+ * HIP graphs: the mode is read when a launch is recorded; a replay runs the captured kernels. */
+#define CT_PW_PRECISION_HIGHEST 0   /* three terms, 22-bit operands: the default, as before */
+#define CT_PW_PRECISION_HIGH    1   /* one f16 term per operand: 11-bit significands (TF32-class), fp32 accumulation */
+void ct_set_pw_precision(int p);     /* process-wide, atomic; other values -> HIGHEST */
+int  ct_get_pw_precision(void);      /* the effective value for the calling thread */
+void ct_pw_precision_override(int p);/* this thread's entry points only; -1: none */
 /* Slice forward with the eval-mode BatchNorm1d (+ ReLU) that follows it applied in the gather's store — the heads' `after`
  * pairs on the Slice output (layers/multihead_ct.py:67-68,107: `self.after(self.slice(...))` = slice -> BatchNorm1d -> ReLU, and
  * the union block's concatenation of the heads' results, :196), where a norm launch of its own would read back the tensor Slice
