@@ -302,6 +302,10 @@ SIGNATURES = {
     "ct_gconv_fwd_norm": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _ip, _vp]),
     "ct_gconv_bwd_data": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _ip, _vp]),
     "ct_gconv_supported": (_i, [_i, _i, _i, _i, _i, _ip]),
+    "ct_set_gconv_precision": (None, [_i]),
+    "ct_get_gconv_precision": (_i, []),
+    "ct_gconv_precision_override": (None, [_i]),
+    "ct_gconv_precision_covers": (_i, [_i, _i, _i, _i, _i, _i, _ip]),
     "ct_gconv_bwd_weight_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _ip]),
     "ct_gconv_bwd_weight": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _ip, _vp]),
     "ct_mhct_core_supported": (_i, [_i, _i, _i, _i, _i, _ip]),

@@ -25,6 +25,9 @@
 // down) also exist as a NORM template variant: ct_gconv_fwd_norm applies the eval-mode BatchNorm, the skip connection and the
 // ReLU of a grouped Res block to the values in their stores (GconvEpi below).  No atomics; the plain instantiations are the
 // code they were without the variant, and the variants' launches stand last in the file so that they also stay where they were.
+// The quad and K-split forms also exist as an F16 template variant (plain and NORM): under ct_set_gconv_precision(HIGH) the
+// operands are packed in place into 11-bit f16 images and multiplied on v_mfma_f32_16x16x16_f16 with fp32 accumulators (see
+// g16_pack_tile).  The same plans and tags; launched after the NORM variants, for the same reason.
 #include "ct_common.h"
 #include <atomic>
 #include <type_traits>
@@ -318,6 +321,75 @@ __global__ void __launch_bounds__(kThreadsBig) gconv_fwd_kernel(GconvArgs a) {
   }
 }
 
+// ---- the one-term f16 variants of the quad and K-split kernels (ct_set_gconv_precision, include/cloudct.h) ----
+// F16: the operands the workgroup has staged are packed IN PLACE into 11-bit f16 images under power-of-two scales taken from
+// the staged data itself (the input tile's largest finite magnitude; each bank row's), and one v_mfma_f32_16x16x16_f16 contracts
+// the 16 input channels that four v_mfma_f32_16x16x4_f32 did: lane (col, kq) carries the four channels kb*4 .. kb*4+3 of the
+// quad of planes kb = g*4 + kq as the k slots kq*4 .. kq*4+3 of both operands.  The packing is thread-local: the thread that
+// reads the four fp32 values of a (kb, position) or (kb, row, tap) writes their four halves into the slots of channels
+// kb*4 and kb*4+1 (dwords {i0, i1} and {i2, i3}), so the LDS footprint, the plan and the staging code are the fp32 kernel's, the
+// fragment reads are half as many, and there is no conversion in the MFMA loop.  fp32 accumulators; the exact 1/(s_w s_x)
+// is applied before the bias is added.  The default instantiations do not see any of it.
+typedef _Float16 halfx2 __attribute__((ext_vector_type(2)));
+typedef _Float16 halfx4 __attribute__((ext_vector_type(4)));
+typedef unsigned uintx2 __attribute__((ext_vector_type(2)));
+
+// magnitude bits of a finite value; 0 for inf / nan (they pass through the image as they are and do not set the scale)
+__device__ __forceinline__ unsigned g16_mag(float v) {
+  const unsigned b = __float_as_uint(v) & 0x7fffffffu;
+  return b < 0x7f800000u ? b : 0u;
+}
+__device__ __forceinline__ unsigned g16_mag4(unsigned m, const float4 v) {
+  return max(max(m, g16_mag(v.x)), max(max(g16_mag(v.y), g16_mag(v.z)), g16_mag(v.w)));
+}
+__device__ __forceinline__ unsigned g16_wave_max(unsigned m) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
+  return m;
+}
+// e with 2^e * m in [2^13, 2^14); 0 for m == 0 (an all-zero tile or row: the image is zeros under any scale)
+__device__ __forceinline__ int g16_exp(unsigned mag_bits) {
+  if (mag_bits == 0u) return 0;
+  int e;
+  (void)frexpf(__uint_as_float(mag_bits), &e);
+  return min(14 - e, 126);   // 2^126 and its inverse are finite; the two scales are undone one after the other
+}
+// two values -> one dword of two f16 (round to nearest even)
+__device__ __forceinline__ unsigned g16_pack(float lo, float hi) {
+  const halfx2 h = {(_Float16)lo, (_Float16)hi};
+  return __builtin_bit_cast(unsigned, h);
+}
+__device__ __forceinline__ halfx4 g16_frag(unsigned lo, unsigned hi) {
+  const uintx2 u = {lo, hi};
+  return __builtin_bit_cast(halfx4, u);
+}
+// The largest finite magnitude of the staged tile xs[4*nkb][plane] -> its scale exponent (the same value in every thread), then
+// the tile packed in place: dword (kb*4, pos) = halves of channels kb*4, kb*4+1, dword (kb*4+1, pos) = those of kb*4+2, kb*4+3.
+// Called by the whole workgroup between two barriers of its own; part: 16 words of LDS.
+__device__ __forceinline__ int g16_pack_tile(float* xs, int nkb, int plane, unsigned* part, int lane, int wave, int nwaves) {
+  unsigned m = 0u;
+  const int n4 = (nkb * 4 * plane) >> 2;
+  for (int i = threadIdx.x; i < n4; i += blockDim.x) m = g16_mag4(m, ((const float4*)xs)[i]);
+  m = g16_wave_max(m);
+  if (lane == 0) part[wave] = m;
+  __syncthreads();
+  m = part[lane < nwaves ? lane : 0];
+  const int ex = g16_exp(g16_wave_max(m));
+  const float sx = ldexpf(1.0f, ex);
+  const int p4 = plane >> 2;
+  for (int i = threadIdx.x; i < nkb * p4; i += blockDim.x) {
+    const int kb = i / p4, q = i - kb * p4;
+    float* base = xs + (size_t)kb * 4 * plane + q * 4;
+    const float4 c0 = *(const float4*)base, c1 = *(const float4*)(base + plane);
+    const float4 c2 = *(const float4*)(base + 2 * plane), c3 = *(const float4*)(base + 3 * plane);
+    *(uint4*)base = make_uint4(g16_pack(c0.x * sx, c1.x * sx), g16_pack(c0.y * sx, c1.y * sx),
+                               g16_pack(c0.z * sx, c1.z * sx), g16_pack(c0.w * sx, c1.w * sx));
+    *(uint4*)(base + plane) = make_uint4(g16_pack(c2.x * sx, c3.x * sx), g16_pack(c2.y * sx, c3.y * sx),
+                                         g16_pack(c2.z * sx, c3.z * sx), g16_pack(c2.w * sx, c3.w * sx));
+  }
+  return ex;
+}
+
 // ---------------------------------------------------------------------------
 // Forward / backward-data on the matrix cores, rows of W % 4 == 0 floats ("quad" form of gconv_fwd_kernel).
 // A wave walks spans of 16 quads = 64 positions; lane (col, kq) owns the quad `col` of the span (4 consecutive x
@@ -331,7 +403,9 @@ __global__ void __launch_bounds__(kThreadsBig) gconv_fwd_kernel(GconvArgs a) {
 // ---------------------------------------------------------------------------
 // NORM: the write-out of ct_gconv_fwd_norm.  The records of a 16-row block (and of its skip connection's norm) are computed once per
 // block by 16 (32) threads into static LDS, next to the bank; a lane reads the four of its rows back at the stores.
-template <int DIM, bool NORM = false>
+// F16: the one-term variant (see g16_pack_tile above).  The tile is packed once, each 16-row block's bank after it is staged, under
+// the row's own scale; a 16-channel group of planes whose quad kb = g*4 + kq lies past KB contributes zero operands.
+template <int DIM, bool NORM = false, bool F16 = false>
 __global__ void __launch_bounds__(kThreadsBig) gconv_fwd4_kernel(FwdArgs<NORM> a) {
   constexpr int NR = DIM == 3 ? 9 : 3;               // window rows (dz, dy)
   extern __shared__ __align__(16) float lds[];
@@ -344,6 +418,15 @@ __global__ void __launch_bounds__(kThreadsBig) gconv_fwd4_kernel(FwdArgs<NORM> a
   const size_t vol = (size_t)a.D * a.H * a.W;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwaves = blockDim.x >> 6;
   stage_halo_tile<DIM>(xs, a.x + ((size_t)b * a.groups + grp) * a.Cin * vol, a, KB * 4, td0, th0, lane, wave, nwaves);
+  [[maybe_unused]] float inv_x = 1.0f;               // F16: 1 / the tile's scale
+  [[maybe_unused]] int* wexp = nullptr;              // F16: the scale exponents of the block's 16 bank rows
+  if constexpr (F16) {
+    __shared__ unsigned part[16];
+    __shared__ int wexp_s[16];
+    wexp = wexp_s;
+    __syncthreads();                                 // the tile is in LDS
+    inv_x = ldexpf(1.0f, -g16_pack_tile(xs, KB, a.plane, part, lane, wave, nwaves));
+  }
   const int col = lane & 15, kq = lane >> 4;
   const int wq = a.W >> 2;
   const int nquads = td * th * wq;
@@ -375,11 +458,39 @@ __global__ void __launch_bounds__(kThreadsBig) gconv_fwd4_kernel(FwdArgs<NORM> a
       recs = &nrec[0][0];
     }
     __syncthreads();
+    if constexpr (F16) {
+      // row m's largest finite magnitude over the staged bank -> its scale exponent (one wave per row), then the bank packed in
+      // place under it: entry (r, kb, m) = the four float4 {dx 0..2, pad} of k = 0..3 -> 16 bytes {dx0, dx1} x {i0 i1, i2 i3} in
+      // the slot of k = 0 and 8 bytes {dx2} in the slot of k = 1
+      for (int m = wave; m < 16; m += nwaves) {
+        unsigned mx = 0u;
+        for (int i = lane; i < NR * KB * 4; i += 64) mx = g16_mag4(mx, *(const float4*)(ws + (size_t)i * 64 + m * 4));
+        mx = g16_wave_max(mx);
+        if (lane == 0) wexp[m] = g16_exp(mx);
+      }
+      __syncthreads();
+      for (int i = threadIdx.x; i < NR * KB * 16; i += blockDim.x) {
+        const int m = i & 15, rk = i >> 4;
+        float* base = ws + (size_t)rk * 256 + m * 4;
+        const float sw = ldexpf(1.0f, wexp[m]);
+        const float4 c0 = *(const float4*)base, c1 = *(const float4*)(base + 64);
+        const float4 c2 = *(const float4*)(base + 128), c3 = *(const float4*)(base + 192);
+        *(uint4*)base = make_uint4(g16_pack(c0.x * sw, c1.x * sw), g16_pack(c2.x * sw, c3.x * sw),
+                                   g16_pack(c0.y * sw, c1.y * sw), g16_pack(c2.y * sw, c3.y * sw));
+        *(uint2*)(base + 64) = make_uint2(g16_pack(c0.z * sw, c1.z * sw), g16_pack(c2.z * sw, c3.z * sw));
+      }
+      __syncthreads();
+    }
     float bias_r[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int co = mt * 16 + kq * 4 + r;
       bias_r[r] = (a.bias != nullptr && co < a.Cout) ? a.bias[grp * a.Cout + co] : 0.0f;
+    }
+    [[maybe_unused]] float inv_w[4];
+    if constexpr (F16) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) inv_w[r] = ldexpf(1.0f, -wexp[kq * 4 + r]);
     }
     for (int sp = wave; sp < nspans; sp += nwaves) {
       const int q = min(sp * 16 + col, nquads - 1);   // clamped: inactive lanes read valid LDS
@@ -391,7 +502,42 @@ __global__ void __launch_bounds__(kThreadsBig) gconv_fwd4_kernel(FwdArgs<NORM> a
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) acc[j][r] = bias_r[r];
+        for (int r = 0; r < 4; ++r) acc[j][r] = F16 ? 0.0f : bias_r[r];
+      if constexpr (F16) {
+        const int G = (KB + 3) >> 2;
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+          const int roff = ((r / 3) * a.Hs + (r % 3)) * a.W;
+          for (int g = 0; g < G; ++g) {
+            const int kb = g * 4 + kq, kbc = min(kb, KB - 1);      // quads past KB: a valid address, zero operands
+            const float* wb = ws + (size_t)(r * KB + kbc) * 256 + col * 4;
+            uint4 a01 = *(const uint4*)__builtin_assume_aligned(wb, 16);
+            uint2 a2 = *(const uint2*)__builtin_assume_aligned(wb + 64, 8);
+            const float* rp = xs + (size_t)kbc * 4 * a.plane + off + roff;
+            uint4 lo = *(const uint4*)__builtin_assume_aligned(rp, 16);
+            uint4 hi = *(const uint4*)__builtin_assume_aligned(rp + a.plane, 16);
+            unsigned lfl = bl ? 0u : __float_as_uint(rp[-1]), lfh = bl ? 0u : __float_as_uint(rp[a.plane - 1]);
+            unsigned rtl = br ? 0u : __float_as_uint(rp[4]), rth = br ? 0u : __float_as_uint(rp[a.plane + 4]);
+            if (kb >= KB) {
+              a01 = make_uint4(0u, 0u, 0u, 0u); a2 = make_uint2(0u, 0u);
+              lo = hi = make_uint4(0u, 0u, 0u, 0u);
+              lfl = lfh = rtl = rth = 0u;
+            }
+            const halfx4 v[6] = {g16_frag(lfl, lfh), g16_frag(lo.x, hi.x), g16_frag(lo.y, hi.y),
+                                 g16_frag(lo.z, hi.z), g16_frag(lo.w, hi.w), g16_frag(rtl, rth)};
+            const halfx4 av[3] = {g16_frag(a01.x, a01.y), g16_frag(a01.z, a01.w), g16_frag(a2.x, a2.y)};
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+              for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x16f16(av[dx], v[j + dx], acc[j], 0, 0, 0);
+          }
+        }
+        // the exact inverse scales, then the bias: what the default form holds in its accumulators here
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) acc[j][r] = acc[j][r] * inv_x * inv_w[r] + bias_r[r];
+      } else {
 #pragma unroll
       for (int r = 0; r < NR; ++r) {
         const int roff = ((r / 3) * a.Hs + (r % 3)) * a.W;
@@ -407,6 +553,7 @@ __global__ void __launch_bounds__(kThreadsBig) gconv_fwd4_kernel(FwdArgs<NORM> a
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[dx], v[j + dx], acc[j], 0, 0, 0);
         }
+      }
       }
       // D_j: row (output channel) = kq*4 + r, column = quad col, element j
       if (sp * 16 + col < nquads) {
@@ -468,7 +615,10 @@ template <int TAPS, bool TR> struct BankRow { static constexpr int RL = 16 * TAP
 // NORM: the write-out of ct_gconv_fwd_norm.  The stores come once, after the last contraction block, when only the accumulators
 // are live: every lane computes the records of its own four rows there (in registers: no LDS next to the bank, whose size the
 // planner shares with the plain kernel).
-template <int DIM, int MAXI, bool TR, bool NORM = false>
+// F16: the one-term variant (see g16_pack_tile above).  Every contraction block packs its 16 planes under the block's own tile
+// scale and its bank slice under per-(row, block) scales, runs ONE f16 MFMA where the fp32 form runs four, into accumulators of its
+// own, and folds them into the fp32 accumulators by the block's exact 1/(s_w s_x); the bias is added after the last block.
+template <int DIM, int MAXI, bool TR, bool NORM = false, bool F16 = false>
 __global__ void __launch_bounds__(kThreadsBig) gconv_fwd4k_kernel(FwdArgs<NORM> a, int dma_bank) {
   constexpr int NR = DIM == 3 ? 9 : 3, TAPS = NR * 3;
   constexpr int KBB = kKBlk / 4;
@@ -501,10 +651,17 @@ __global__ void __launch_bounds__(kThreadsBig) gconv_fwd4k_kernel(FwdArgs<NORM> 
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int co = mt * 16 + kq * 4 + r;
-      const float bv = (a.bias != nullptr && co < a.Cout && item < nitems) ? a.bias[grp * a.Cout + co] : 0.0f;
+      const float bv = (!F16 && a.bias != nullptr && co < a.Cout && item < nitems) ? a.bias[grp * a.Cout + co] : 0.0f;
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[u][j][r] = bv;
     }
+  }
+  [[maybe_unused]] int* wexp = nullptr;                // F16: the scale exponents of the block's bank rows ([nmt][16], nmt <= 64)
+  [[maybe_unused]] unsigned* part = nullptr;
+  if constexpr (F16) {
+    __shared__ unsigned part_s[16];
+    __shared__ int wexp_s[64 * 16];
+    part = part_s; wexp = wexp_s;
   }
 
   for (int k0 = 0; k0 < a.Cin; k0 += kKBlk) {
@@ -540,6 +697,34 @@ __global__ void __launch_bounds__(kThreadsBig) gconv_fwd4k_kernel(FwdArgs<NORM> 
       }
     }
     __syncthreads();
+    [[maybe_unused]] float inv_x = 1.0f;
+    if constexpr (F16) {
+      // scale exponent of every output row of the slice (one wave per row: its 16 x TAPS staged values), the tile's, then both
+      // packed in place: the four input channels kq*4 + i of a (row, tap) into the slots of i = 0 and i = 1
+      for (int rw = wave; rw < nmt * 16; rw += nwaves) {
+        unsigned mx = 0u;
+        for (int i = lane; i < RL; i += 64) {
+          const int c16 = i / TAPS, tp = i - c16 * TAPS;
+          mx = max(mx, g16_mag(TR ? ws[(size_t)((rw & ~15) + c16) * CS + (rw & 15) * TAPS + tp] : ws[(size_t)rw * CS + i]));
+        }
+        mx = g16_wave_max(mx);
+        if (lane == 0) wexp[rw] = g16_exp(mx);
+      }
+      inv_x = ldexpf(1.0f, -g16_pack_tile(xs, KBB, a.plane, part, lane, wave, nwaves));   // (its barrier publishes wexp too)
+      for (int i = threadIdx.x; i < nmt * 64 * TAPS; i += blockDim.x) {
+        const int tp = i % TAPS, t = i / TAPS;
+        // forward: t = (row rw, kq); backward-data: t = (block, kq, co)
+        const int row = TR ? (t >> 6) * 16 + (t & 15) : t >> 2;
+        float* base = TR ? ws + (size_t)((t >> 6) * 16 + ((t >> 4) & 3) * 4) * CS + (t & 15) * TAPS + tp
+                         : ws + (size_t)(t >> 2) * CS + (t & 3) * 4 * TAPS + tp;
+        constexpr int IS = TR ? CS : TAPS;             // stride between the four channels
+        const float sw = ldexpf(1.0f, wexp[row]);
+        const float c0 = base[0], c1 = base[IS], c2 = base[2 * IS], c3 = base[3 * IS];
+        base[0] = __uint_as_float(g16_pack(c0 * sw, c1 * sw));
+        base[IS] = __uint_as_float(g16_pack(c2 * sw, c3 * sw));
+      }
+      __syncthreads();
+    }
 #pragma unroll
     for (int u = 0; u < MAXI; ++u) {
       if (it_sp[u] < 0) continue;                      // wave-uniform
@@ -548,6 +733,40 @@ __global__ void __launch_bounds__(kThreadsBig) gconv_fwd4k_kernel(FwdArgs<NORM> 
       const int x0 = xq * 4;
       const bool bl = x0 == 0, br = x0 + 4 == a.W;
       const int off = (z * a.Hs + y) * a.W + x0;
+      if constexpr (F16) {
+        constexpr int IS = TR ? CS : TAPS;
+        const float* wm = ws + (size_t)it_mt[u] * 16 * CS + (TR ? kq * 4 * CS + col * TAPS + (TAPS - 1) : col * CS + kq * 4 * TAPS);
+        floatx4 blk[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) blk[j] = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+          const int roff = ((r / 3) * a.Hs + (r % 3)) * a.W;
+          const float* ap = wm + (TR ? -r * 3 : r * 3);
+          halfx4 av[3];
+#pragma unroll
+          for (int dx = 0; dx < 3; ++dx)
+            av[dx] = g16_frag(__float_as_uint(ap[TR ? -dx : dx]), __float_as_uint(ap[IS + (TR ? -dx : dx)]));
+          const float* rp = xs + (size_t)kq * 4 * a.plane + off + roff;
+          const uint4 lo = *(const uint4*)__builtin_assume_aligned(rp, 16);
+          const uint4 hi = *(const uint4*)__builtin_assume_aligned(rp + a.plane, 16);
+          const unsigned lfl = bl ? 0u : __float_as_uint(rp[-1]), lfh = bl ? 0u : __float_as_uint(rp[a.plane - 1]);
+          const unsigned rtl = br ? 0u : __float_as_uint(rp[4]), rth = br ? 0u : __float_as_uint(rp[a.plane + 4]);
+          const halfx4 v[6] = {g16_frag(lfl, lfh), g16_frag(lo.x, hi.x), g16_frag(lo.y, hi.y),
+                               g16_frag(lo.z, hi.z), g16_frag(lo.w, hi.w), g16_frag(rtl, rth)};
+#pragma unroll
+          for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) blk[j] = __builtin_amdgcn_mfma_f32_16x16x16f16(av[dx], v[j + dx], blk[j], 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float iw = ldexpf(1.0f, -wexp[it_mt[u] * 16 + kq * 4 + r]);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[u][j][r] = acc[u][j][r] + blk[j][r] * inv_x * iw;
+        }
+        continue;
+      }
       // forward: ws[co][ci][tap]; backward-data: ws[ci][co][taps - 1 - tap]
       const float* wm = ws + (size_t)it_mt[u] * 16 * CS + (TR ? kq * CS + col * TAPS + (TAPS - 1) : col * CS + kq * TAPS);
 #pragma unroll
@@ -577,6 +796,16 @@ __global__ void __launch_bounds__(kThreadsBig) gconv_fwd4k_kernel(FwdArgs<NORM> 
       const int xq = qi % wq, y = (qi / wq) % th, z = qi / (wq * th);
       const size_t o = ((size_t)(td0 + z) * a.H + (th0 + y)) * a.W + xq * 4;
       const int mt = ms + it_mt[u] * a.msplit;
+      if constexpr (F16) {
+        if (a.bias != nullptr) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float bv = a.bias[grp * a.Cout + min(mt * 16 + kq * 4 + r, a.Cout - 1)];   // rows past Cout are not stored
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[u][j][r] = acc[u][j][r] + bv;
+          }
+        }
+      }
       if constexpr (NORM) {
         const GconvEpi& e = a.epi;
         const float* sg = e.skip != nullptr ? e.skip + (yg - a.y) : nullptr;
@@ -2122,9 +2351,33 @@ int launch_c4(GconvArgs a, int dim, hipStream_t st) {
 int launch_fwd4_norm(const GconvArgs& a, const GconvEpi& e, int dim, dim3 grid, int threads, size_t lds, hipStream_t st);
 int launch_fwd4k_norm(const GconvArgs& t, const GconvEpi& e, int dim, int pass, int maxi, int dma, dim3 grid, size_t lds, hipStream_t st);
 int launch_tiny_norm(const GconvArgs& a, const GconvEpi& e, int dim, int cob, dim3 grid, size_t lds, hipStream_t st);
+// ... and after them the launches of the one-term f16 variants (plain and NORM), for the same reason
+int launch_fwd4_f16(const GconvArgs& a, const GconvEpi* e, int dim, dim3 grid, int threads, size_t lds, hipStream_t st);
+int launch_fwd4k_f16(const GconvArgs& t, const GconvEpi* e, int dim, int pass, int maxi, int dma, dim3 grid, size_t lds, hipStream_t st);
+
+// Precision mode (ct_set_gconv_precision, include/cloudct.h): process-wide, read ONCE per entry point and handed
+// down to the planner as `prec`; the calling thread's override wins.  No kernel reads it.
+std::atomic<int> g_gconv_precision{CT_GCONV_PRECISION_HIGHEST};
+thread_local int t_gconv_precision_override = -1;
+inline int gconv_precision_now() {
+  return t_gconv_precision_override >= 0 ? t_gconv_precision_override : g_gconv_precision.load(std::memory_order_relaxed);
+}
+// What the planner hands back beside the return code: whether the plan it settled on is a one-term kernel under
+// CT_GCONV_PRECISION_HIGH (ct_gconv_precision_covers)
+struct FwdTook { bool one_term = false; };
+// The quad form takes the one-term kernel from 16 input channels per group on (one full f16 MFMA group; below it most k slots
+// would carry zeros).  The K-split form takes it from four spans of 16 quads per tile on: every contraction block pays for
+// packing its planes and its bank slice, which a 4^3 volume's single span does not earn back (measured: 8^3 1.5 - 2.0x,
+// 4^3 1.05x forward and 0.90x backward-data; profiles/gconv_precision_bench.txt).
+inline bool quad_one_term(const GconvArgs& a) { return a.Cin >= 16; }
+#ifndef CT_GCONV_F16_SPANS
+#define CT_GCONV_F16_SPANS 4
+#endif
+inline bool ksplit_one_term(int nspans) { return nspans >= CT_GCONV_F16_SPANS; }
 
 // (e: the NORM write-out of ct_gconv_fwd_norm, the same plan and tags; plan_only: settle the plan and return before the launch)
-int launch_fwd4(GconvArgs a, int dim, hipStream_t st, const GconvEpi* e = nullptr, bool plan_only = false) {
+int launch_fwd4(GconvArgs a, int dim, hipStream_t st, const GconvEpi* e = nullptr, bool plan_only = false, int prec = 0,
+                FwdTook* took = nullptr) {
   const int NR = dim == 3 ? 9 : 3;
   const size_t wbytes = (size_t)NR * a.KB * 256 * 4;
   // Tile budget: this kernel likes BIG tiles (one 1024-thread workgroup per CU: long MFMA runs per barrier, little
@@ -2149,7 +2402,9 @@ int launch_fwd4(GconvArgs a, int dim, hipStream_t st, const GconvEpi* e = nullpt
   a.msplit = pick_msplit(a);
   dim3 grid(a.nD * a.nH * a.msplit, a.groups, a.B);
   const int threads = lds > 48 * 1024 ? kThreadsBig : kThreads;
+  if (took != nullptr) took->one_term = quad_one_term(a);
   if (plan_only) return CT_OK;
+  if (prec == CT_GCONV_PRECISION_HIGH && quad_one_term(a)) return launch_fwd4_f16(a, e, dim, grid, threads, lds, st);
   if (e != nullptr) return launch_fwd4_norm(a, *e, dim, grid, threads, lds, st);
   note(threads == kThreadsBig ? "quad_1024" : "quad_256");
   if (a.msplit > 1) note("quad_msplit");
@@ -2167,7 +2422,8 @@ int launch_fwd4(GconvArgs a, int dim, hipStream_t st, const GconvEpi* e = nullpt
 
 
 // K-split form for wide groups (> 32 input channels per group): see gconv_fwd4k_kernel
-int launch_fwd4k(GconvArgs a, int dim, hipStream_t st, const GconvEpi* e = nullptr, bool plan_only = false) {
+int launch_fwd4k(GconvArgs a, int dim, hipStream_t st, const GconvEpi* e = nullptr, bool plan_only = false, int prec = 0,
+                 FwdTook* took = nullptr) {
   const int NR = dim == 3 ? 9 : 3;
   const int MT = (a.Cout + 15) / 16;
   constexpr int kWaves = kThreadsBig / 64;
@@ -2195,7 +2451,10 @@ int launch_fwd4k(GconvArgs a, int dim, hipStream_t st, const GconvEpi* e = nullp
     const int maxi = items <= kWaves ? 1 : (items <= 2 * kWaves ? 2 : 4);
     // whole 16-channel rows at 16-byte aligned addresses move by LDS-DMA
     const int dma = (a.Cin % 16 == 0 && a.Cout % 16 == 0 && (((uintptr_t)a.w) & 15) == 0) ? 1 : 0;
+    const bool one_term = ksplit_one_term((nquads + 15) / 16);
+    if (took != nullptr) took->one_term = one_term;
     if (plan_only) return CT_OK;
+    if (prec == CT_GCONV_PRECISION_HIGH && one_term) return launch_fwd4k_f16(t, e, dim, pass, maxi, dma, grid, lds, st);
     if (e != nullptr) return launch_fwd4k_norm(t, *e, dim, pass, maxi, dma, grid, lds, st);
     note(pass == 0 ? (dma ? "ksplit_one_dma" : "ksplit_one_elem") : (dma ? "ksplit_tiled_dma" : "ksplit_tiled_elem"));
     note(maxi == 1 ? "ksplit_items1" : maxi == 2 ? "ksplit_items2" : "ksplit_items4");
@@ -2253,14 +2512,17 @@ int launch_tiny(GconvArgs a, int dim, int cob, hipStream_t st, const GconvEpi* e
 
 // e: the NORM write-out (ct_gconv_fwd_norm) on the families that carry it — dense 2^d, K-split, quad; the others return CT_EINVAL
 // before anything is launched.  plan_only (ct_gconv_fwd_norm_supported): the same walk with nothing noted and nothing launched.
-int launch_fwd(GconvArgs a, int dim, hipStream_t st, const GconvEpi* e = nullptr, bool plan_only = false) {
-  const bool norm = e != nullptr || plan_only;
+// prec: the precision mode the entry point read; took: see FwdTook (norm_plan: plan_only walks as ct_gconv_fwd_norm would)
+int launch_fwd(GconvArgs a, int dim, hipStream_t st, const GconvEpi* e = nullptr, bool plan_only = false, int prec = 0,
+               FwdTook* took = nullptr, bool norm_plan = true) {
+  const bool norm = e != nullptr || (plan_only && norm_plan);
   if (const int cob = tiny_cob(a, dim)) return plan_only ? CT_OK : launch_tiny(a, dim, cob, st, e);
   const bool rows16 = (a.W & 3) == 0 && ((((uintptr_t)a.x) | ((uintptr_t)a.y)) & 15) == 0;
   if (norm && (!rows16 || (a.Cin == 4 && a.Cout == 4))) return CT_EINVAL;     // the four-channel kernels and the one-position form
   // large four-channel volumes (the zoo's 32^3 C4 head at B8: 74 vs 93 us) take the matrix-core kernel; below ~2 M positions
   // (B2: 31 vs 30 us, 16^3: 29 vs 16) its per-slice barriers cost more than the vector ALU's extra multiply-adds
   // (debug bit 1 = never, bit 2 = always)
+  if (plan_only && a.Cin == 4 && a.Cout == 4) return CT_OK;      // (ct_gconv_precision_covers: the four-channel kernels keep fp32)
   if (dim == 3 && rows16 && a.Cin == 4 && a.Cout == 4 && c4_mfma3_fits(a)) {
     const unsigned dbg = t_gconv_debug.load(std::memory_order_relaxed);
     const long long positions = (long long)a.B * a.groups * a.D * a.H * a.W;
@@ -2269,16 +2531,18 @@ int launch_fwd(GconvArgs a, int dim, hipStream_t st, const GconvEpi* e = nullptr
   if (rows16 && a.Cin == 4 && a.Cout == 4) return launch_c4(a, dim, st);
   const unsigned dbg_cin = (t_gconv_debug.load(std::memory_order_relaxed) >> 8) & 0xffu;
   if (rows16 && a.Cin >= (dbg_cin ? (int)dbg_cin : 32)) {      // wide groups (>= 32 input channels): contraction in blocks of 16
-    const int r = launch_fwd4k(a, dim, st, e, plan_only);
+    const int r = launch_fwd4k(a, dim, st, e, plan_only, prec, took);
     if (r != CT_EINVAL) return r;
   }
   if (rows16) {
     // the quad form keeps the whole filter bank of a 16-row block in LDS ([rows][KB][4][16][4] floats): with 64 input
     // channels per group in 3D that alone is 147 KiB — such shapes take the K-split form above
-    const int r = launch_fwd4(a, dim, st, e, plan_only);
+    const int r = launch_fwd4(a, dim, st, e, plan_only, prec, took);
     if (r != CT_EINVAL) return r;
   }
+  if (took != nullptr) took->one_term = false;
   if (norm) return CT_EINVAL;
+  if (plan_only) return CT_OK;                                    // (ct_gconv_precision_covers: the one-position form keeps fp32)
   const size_t wbytes = (size_t)a.taps * a.KB * 64 * 4;
   // short rows (W < 16: the 8^3 volumes) do better on the minimum-halo tiles, the others on the depth-first ones (measured)
   const bool ok = a.W < 16 ? (plan_tiles_min_halo(a, dim, 0, wbytes, a.KB * 4, 16, kLdsBudget) ||
@@ -2647,9 +2911,64 @@ int launch_tiny_norm(const GconvArgs& a, const GconvEpi& e, int dim, int cob, di
   return CT_OK;
 }
 
+// ---- launches of the one-term f16 variants: after everything else (see launch_fwd4_f16's declaration).  Same plans, same tags. ----
+int launch_fwd4_f16(const GconvArgs& a, const GconvEpi* e, int dim, dim3 grid, int threads, size_t lds, hipStream_t st) {
+  note(threads == kThreadsBig ? "quad_1024" : "quad_256");
+  if (a.msplit > 1) note("quad_msplit");
+  CT_CLEAR_ERROR();
+#define CT_F4H(DIMV, NORMV)                                                                              \
+  do {                                                                                                   \
+    if (set_lds_attr(gconv_fwd4_kernel<DIMV, NORMV, true>, lds) != CT_OK) return CT_ELAUNCH;             \
+    hipLaunchKernelGGL((gconv_fwd4_kernel<DIMV, NORMV, true>), grid, dim3(threads), lds, st, fwd_args<NORMV>(a, e)); \
+  } while (0)
+  if (dim == 2) { if (e != nullptr) CT_F4H(2, true); else CT_F4H(2, false); }
+  else { if (e != nullptr) CT_F4H(3, true); else CT_F4H(3, false); }
+#undef CT_F4H
+  CT_CHECK_LAUNCH();
+  return CT_OK;
+}
+
+int launch_fwd4k_f16(const GconvArgs& t, const GconvEpi* e, int dim, int pass, int maxi, int dma, dim3 grid, size_t lds, hipStream_t st) {
+  note(pass == 0 ? (dma ? "ksplit_one_dma" : "ksplit_one_elem") : (dma ? "ksplit_tiled_dma" : "ksplit_tiled_elem"));
+  note(maxi == 1 ? "ksplit_items1" : maxi == 2 ? "ksplit_items2" : "ksplit_items4");
+  if (t.msplit > 1) note("ksplit_msplit");
+  CT_CLEAR_ERROR();
+#define CT_F4KH(DIMV, MAXIV, TRV, NORMV)                                                                 \
+  do {                                                                                                   \
+    if (set_lds_attr(gconv_fwd4k_kernel<DIMV, MAXIV, TRV, NORMV, true>, lds) != CT_OK) return CT_ELAUNCH; \
+    hipLaunchKernelGGL((gconv_fwd4k_kernel<DIMV, MAXIV, TRV, NORMV, true>), grid, dim3(kThreadsBig), lds, st, fwd_args<NORMV>(t, e), dma); \
+  } while (0)
+#define CT_F4KH_MAXI(DIMV, TRV, NORMV) \
+  do { if (maxi == 1) CT_F4KH(DIMV, 1, TRV, NORMV); else if (maxi == 2) CT_F4KH(DIMV, 2, TRV, NORMV); else CT_F4KH(DIMV, 4, TRV, NORMV); } while (0)
+  if (e != nullptr) { if (dim == 2) CT_F4KH_MAXI(2, false, true); else CT_F4KH_MAXI(3, false, true); }
+  else if (dim == 2) { if (t.transposed) CT_F4KH_MAXI(2, true, false); else CT_F4KH_MAXI(2, false, false); }
+  else { if (t.transposed) CT_F4KH_MAXI(3, true, false); else CT_F4KH_MAXI(3, false, false); }
+#undef CT_F4KH_MAXI
+#undef CT_F4KH
+  CT_CHECK_LAUNCH();
+  return CT_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+void ct_set_gconv_precision(int p) {
+  g_gconv_precision.store(p == CT_GCONV_PRECISION_HIGH ? CT_GCONV_PRECISION_HIGH : CT_GCONV_PRECISION_HIGHEST, std::memory_order_relaxed);
+}
+int ct_get_gconv_precision(void) { return gconv_precision_now(); }
+void ct_gconv_precision_override(int p) {
+  t_gconv_precision_override = p < 0 ? -1 : (p == CT_GCONV_PRECISION_HIGH ? CT_GCONV_PRECISION_HIGH : CT_GCONV_PRECISION_HIGHEST);
+}
+
+int ct_gconv_precision_covers(int pass, int B, int groups, int Cin, int Cout, int dim, const int* W) {
+  GconvArgs a = {};                                                // (null tensors: on the 16-byte grid)
+  if ((pass != 0 && pass != 1) || gconv_common(a, B, groups, pass ? Cout : Cin, pass ? Cin : Cout, dim, W) != CT_OK) return 0;
+  a.transposed = pass;
+  FwdTook took;
+  if (launch_fwd(a, dim, nullptr, nullptr, /*plan_only=*/true, CT_GCONV_PRECISION_HIGH, &took, /*norm_plan=*/false) != CT_OK) return 0;
+  return took.one_term ? 1 : 0;
+}
 
 void ct_debug_set_gconv(unsigned flags) { t_gconv_debug.store(flags, std::memory_order_relaxed); }
 
@@ -2661,7 +2980,7 @@ int ct_gconv_fwd(const float* x, const float* w, const float* bias, float* y,
   if (r != CT_OK) return r;
   a.x = x; a.w = w; a.bias = bias; a.y = y; a.transposed = 0;
   note_reset();
-  return launch_fwd(a, dim, (hipStream_t)s);
+  return launch_fwd(a, dim, (hipStream_t)s, nullptr, false, gconv_precision_now());
 }
 
 int ct_gconv_fwd_norm_supported(int B, int groups, int Cin, int Cout, int dim, const int* W) {
@@ -2689,7 +3008,7 @@ int ct_gconv_fwd_norm(const float* x, const float* w, const float* bias, const c
   if (r != CT_OK) return r;
   a.x = x; a.w = w; a.bias = bias; a.y = y; a.transposed = 0;
   note_reset();
-  return launch_fwd(a, dim, (hipStream_t)s, &e);
+  return launch_fwd(a, dim, (hipStream_t)s, &e, false, gconv_precision_now());
 }
 
 int ct_gconv_bwd_data(const float* g_y, const float* w, float* g_x,
@@ -2702,7 +3021,7 @@ int ct_gconv_bwd_data(const float* g_y, const float* w, float* g_x,
   a.x = g_y; a.w = w; a.bias = nullptr; a.y = g_x; a.transposed = 1;
   note_reset();
   note("bwd_data");                                                // the same kernels with TR / a.transposed set
-  return launch_fwd(a, dim, (hipStream_t)s);
+  return launch_fwd(a, dim, (hipStream_t)s, nullptr, false, gconv_precision_now());
 }
 
 int ct_gconv_supported(int B, int groups, int Cin, int Cout, int dim, const int* W) {

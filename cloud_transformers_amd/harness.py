@@ -7,7 +7,8 @@ package's layers and checkpoints stay interchangeable.
   `model.generator` (a python file defining `Model`; the remaining `model.*` keys are its kwargs),
   `train.{optimizer,scheduler,num_epochs,save_each,...}`, optional `restore.{generator,optimizer,new_lr}`; `train.deterministic:
   true` (this package's own key) runs `fit` in deterministic mode (determinism.py): equal seeds, equal gradients. `train.matmul_precision:
-  high` (likewise) runs `fit` with the pointwise GEMMs in the TF32-class mode of precision.py.
+  high` (likewise) runs `fit` with the pointwise GEMMs in the TF32-class mode of precision.py. `train.conv_precision: high`
+  (likewise, independent of it) does the same for the grouped 3^d convolutions.
   `train.freeze_norms: true` (optionally `train.freeze_norm_affine: true`; this package's own keys) fine-tunes on frozen
   norm statistics (norms.py `freeze_norms`, applied after the data-parallel wrap): the running statistics never move, no
   statistics are exchanged between ranks, validation and checkpoints are unchanged.
@@ -885,8 +886,13 @@ class Trainer:
 
         `train.matmul_precision: high` (or `medium` / `highest`) runs the whole fit, the validation inside it included, with
         the pointwise-convolution GEMMs in that mode (precision.py: one f16 MFMA term per operand, TF32-class); the previous
-        mode comes back when fit returns.  With `hip_graph` the captured kernels are those of this mode."""
+        mode comes back when fit returns.  With `hip_graph` the captured kernels are those of this mode.
+        `train.conv_precision` does the same for the grouped 3^d convolutions (precision.py `conv_precision`), independently;
+        a value that is not a mode's name raises ValueError here, before any device work."""
         import contextlib
+        conv_mode = self.cfg["train"].get("conv_precision")
+        if conv_mode is not None and conv_mode not in ("highest", "high", "medium"):
+            raise ValueError("train.conv_precision expects 'highest', 'high' or 'medium', got %r" % (conv_mode,))
         with contextlib.ExitStack() as scopes:
             if self.cfg["train"].get("deterministic", False):
                 from . import determinism
@@ -894,6 +900,9 @@ class Trainer:
             if self.cfg["train"].get("matmul_precision") is not None:
                 from . import precision
                 scopes.enter_context(precision.matmul_precision(self.cfg["train"]["matmul_precision"]))
+            if self.cfg["train"].get("conv_precision") is not None:
+                from . import precision
+                scopes.enter_context(precision.conv_precision(self.cfg["train"]["conv_precision"]))
             return self._fit(max_iters, hip_graph, log_each)
 
     def _fit(self, max_iters, hip_graph, log_each):

@@ -9,12 +9,15 @@ padding 1, dilation 1, zero padding, fp32 on a HIP device.  The grouped 1x1 skip
 (layers/v2v_groups.py:40-44) are one batched GEMM per (cloud, group) on the BLAS library — the library's grouped
 convolution spends ~0.4 ms per weight gradient on these few-kFLOP layers; any other configuration goes to the
 stock PyTorch/MIOpen implementation of the parent class.
+Under `conv_precision("high")` (precision.py) the forward and the data gradient run one f16 MFMA term per operand where the
+library covers the shape (TF32-class); the data gradient keeps the mode its forward ran in, the weight gradient stays fp32.
 """
 import torch
 from torch import nn
 
 from .. import _lib
 from .. import determinism as _det
+from .. import precision as _prec
 from ..ops import _ptr, _stream, _on
 
 
@@ -30,6 +33,7 @@ class GroupedConvFn(torch.autograd.Function):
         W = list(x.shape[2:])
         y = torch.empty(B, groups * Cout, *W, device=x.device, dtype=torch.float32)
         lib = _lib.load()
+        ctx.conv_precision = _prec.conv_push(lib)     # the backward-data keeps the forward's precision (precision.py)
         with _on(x.device):
             _lib.check(lib.ct_gconv_fwd(_ptr(x), _ptr(weight), _ptr(bias.contiguous()) if bias is not None else None,
                                         _ptr(y), B, groups, Cin, Cout, dim, _lib.int_array(W), _stream()),
@@ -50,8 +54,9 @@ class GroupedConvFn(torch.autograd.Function):
         with _on(x.device):
             if ctx.needs_input_grad[0]:
                 g_x = torch.empty_like(x)
-                _lib.check(lib.ct_gconv_bwd_data(_ptr(g_y), _ptr(weight), _ptr(g_x), B, groups, Cin, Cout, dim, Wa,
-                                                 _stream()), "ct_gconv_bwd_data")
+                with _prec.conv_forced(ctx.conv_precision, lib):     # on whichever thread autograd runs this
+                    _lib.check(lib.ct_gconv_bwd_data(_ptr(g_y), _ptr(weight), _ptr(g_x), B, groups, Cin, Cout, dim, Wa,
+                                                     _stream()), "ct_gconv_bwd_data")
             if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
                 g_w = torch.empty_like(weight)
                 g_b = torch.empty(groups * Cout, device=x.device, dtype=torch.float32) if has_bias else None

@@ -2625,6 +2625,7 @@ def gconv_bn_eval(x, conv, bn, relu, skip=None, skip_bn=None):
     W = list(x.shape[2:])
     nd = len(W)
     lib = _lib.load()
+    _prec.conv_push(lib)     # the convolution's precision (precision.py): an eval Res block is in one mode throughout
     key = (B, G, Cin, Cout, tuple(W))
     fused = _gconv_norm_supported.get(key)
     if fused is None:

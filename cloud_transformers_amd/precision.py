@@ -21,6 +21,19 @@ autograd runs them — a `with` scope around the forward alone still gives a con
 
 HIP graphs: the mode is read when a launch is RECORDED.  A replay runs the kernels that were captured, whatever the mode is
 by then; capture again to change it.
+
+Precision of the grouped 3^d convolutions (include/cloudct.h: ct_set_gconv_precision), the same pattern and an
+INDEPENDENT mode, like torch's two flags:
+
+    set_conv_precision("highest" | "high" | "medium" | None)
+    get_conv_precision()
+    with conv_precision("high"): ...
+
+"highest" (the default): fp32 MFMA.  "high": the quad and K-split kernels of ct_gconv_fwd / ct_gconv_bwd_data / ct_gconv_fwd_norm
+multiply one f16 term per operand (11-bit significands, fp32 accumulation); "medium" is served by the same kernels.  None follows
+torch.backends.cudnn.allow_tf32 at call time.  CLOUDCT_GCONV_PRECISION=highest|high|medium sets the initial mode; unset, or anything
+else, means "highest" — not None: torch's flag defaults to True, and a process that never asks stays exactly as it is.  A layer's
+backward-data runs in its forward's mode (`conv_forced`); the weight gradient is fp32 in every mode.
 """
 import contextlib
 import os
@@ -94,3 +107,70 @@ def forced(p, lib=None):
         yield
     finally:
         lib.ct_pw_precision_override(-1)
+
+
+# ---- the grouped convolutions' mode ----
+
+def _conv_from_env():
+    v = os.environ.get("CLOUDCT_GCONV_PRECISION")
+    return v if v in _NAMES else "highest"
+
+
+_conv_mode = _conv_from_env()
+
+
+def set_conv_precision(mode):
+    """"highest" / "high" / "medium": that mode whatever torch says; None: follow torch.backends.cudnn.allow_tf32 at call time."""
+    global _conv_mode
+    if mode is not None and not isinstance(mode, str):
+        raise TypeError("set_conv_precision expects 'highest', 'high', 'medium' or None, got %r" % (mode,))
+    if mode is not None and mode not in _NAMES:
+        raise ValueError("set_conv_precision expects 'highest', 'high', 'medium' or None, got %r" % (mode,))
+    _conv_mode = mode
+    if _lib._lib is not None:          # keep a loaded library in step (direct ABI callers; a scope that just ended)
+        conv_push(_lib._lib)
+
+
+def get_conv_mode():
+    """What set_conv_precision was given (a name or None)."""
+    return _conv_mode
+
+
+def get_conv_precision():
+    if _conv_mode is None:
+        return "high" if torch.backends.cudnn.allow_tf32 else "highest"
+    return _conv_mode
+
+
+def conv_code():
+    """The effective mode as the library's constant (CT_GCONV_PRECISION_HIGHEST / _HIGH)."""
+    return HIGHEST if get_conv_precision() == "highest" else HIGH
+
+
+@contextlib.contextmanager
+def conv_precision(mode="high"):
+    prev = _conv_mode
+    set_conv_precision(mode)
+    try:
+        yield
+    finally:
+        set_conv_precision(prev)
+
+
+def conv_push(lib=None):
+    """Set the library's switch to the effective mode; returns its constant.  Called by the ops ahead of their launches."""
+    p = conv_code()
+    (lib or _lib.load()).ct_set_gconv_precision(p)
+    return p
+
+
+@contextlib.contextmanager
+def conv_forced(p, lib=None):
+    """Mode `p` (a library constant) for the entry points THIS thread calls inside the scope, whatever the process-wide switch
+    says: how a backward-data runs in its forward's precision."""
+    lib = lib or _lib.load()
+    lib.ct_gconv_precision_override(p)
+    try:
+        yield
+    finally:
+        lib.ct_gconv_precision_override(-1)

@@ -6,7 +6,8 @@
  * HIP stream (passed as void* so that this header needs no HIP include), never
  * allocates, never synchronises the device, keeps no global state — but for the
  * process-wide deterministic switch ct_set_deterministic, the process-wide precision
- * mode of the pointwise GEMMs ct_set_pw_precision and the ct_debug_* test
+ * mode of the pointwise GEMMs ct_set_pw_precision, that of the grouped convolutions
+ * ct_set_gconv_precision and the ct_debug_* test
  * hooks below, host-side atomics that no kernel reads — and returns
  * an int status: CT_OK (0) or a negative CT_E* code (ct_strerror() names it).
  * All tensors are fp32, contiguous, channels-first with the point index N
@@ -47,7 +48,8 @@ extern "C" {
  * completion gather ct_completion_gather; then the deterministic switch ct_set_deterministic / ct_get_deterministic / ct_deterministic_override;
  * then Chamfer with per-cloud counts and the metric table: ct_chamfer_fwd_counts / ct_chamfer_bwd_counts / ct_rows_compact /
  * ct_chamfer_metrics; then the backward of the eval-mode norm, ct_bn_eval_group_bwd; then the precision mode of the pointwise
- * GEMMs ct_set_pw_precision / ct_get_pw_precision / ct_pw_precision_override.) */
+ * GEMMs ct_set_pw_precision / ct_get_pw_precision / ct_pw_precision_override; then that of the grouped convolutions,
+ * ct_set_gconv_precision / ct_get_gconv_precision / ct_gconv_precision_override / ct_gconv_precision_covers.) */
 #define CT_ABI_VERSION 3
 
 /* status codes */
@@ -517,6 +519,48 @@ int ct_gconv_fwd_norm_supported(int B, int groups, int Cin, int Cout, int dim, c
 int ct_gconv_fwd_norm(const float* x, const float* w, const float* bias, const ct_gconv_norm* norm,
                       const float* skip, const ct_gconv_norm* skip_norm, int relu, float* y,
                       int B, int groups, int Cin, int Cout, int dim, const int* W, ct_stream_t s);
+
+/* ------------------------------------------------------------------------
+ * Precision mode of the grouped convolution: the counterpart of ct_set_pw_precision for ct_gconv_fwd, ct_gconv_bwd_data and
+ * ct_gconv_fwd_norm.  Process-wide host state, atomic, never read by a kernel: each of the three entry points reads the
+ * effective value ONCE, where it plans its launch.  Added under CT_ABI_VERSION 3 (additive).  Independent of the pointwise
+ * GEMMs' mode.
+ *   CT_GCONV_PRECISION_HIGHEST (the default): everything above, bit for bit.
+ *   CT_GCONV_PRECISION_HIGH: the quad and K-split kernels (ct_gconv_precision_covers) multiply ONE f16 term per operand on
+ *     v_mfma_f32_16x16x16_f16 with fp32 accumulators: 11-bit significands, the precision of TF32, for which gfx950 has no matrix
+ *     instruction.  h = f16(s v) under power-of-two scales s with s M in [2^13, 2^14), taken inside the kernel from the operands
+ *     the workgroup has staged: M = the largest finite magnitude of the staged input tile (K-split: of the tile of each
+ *     16-channel contraction block) and of each output-channel row of the staged bank (K-split: per row and block); no
+ *     pre-pass, no workspace, the same signatures.  The accumulators are multiplied by the exact 1/s_x and 1/s_w (K-split: per
+ *     block, then added in fp32) before the bias is added; the stores, the NORM write-out and the launch tags are those of the
+ *     default mode, and within the mode ct_gconv_fwd_norm keeps its bit-equality contract with ct_gconv_fwd.  An all-zero tile
+ *     or row has s = 1 and contributes exact zeros; inf and NaN do not set a scale and pass through f16 as they are, reaching the
+ *     outputs they reach in the default mode.  No atomics: every output is written once, run-to-run bit-equal.
+ *     Error bound.  For an element v under a scale with maximum M:  |f16(s v)/s - v| <= 2^-11 |v| + 2^-38 M  (the rounding of a
+ *     normal f16; a subnormal's 2^-25 over s >= 2^13 / M).  f16 x f16 products are exact in fp32, so with dw, dx these element
+ *     errors one product is off by w dx + x dw + dw dx: (2^-10 + 2^-22) |w x| from the normal parts, 2^-38 (M_w |x| + M_x |w|) from
+ *     the subnormal parts against the other operand's value, 2^-11 of that again against its normal error, subnormal against
+ *     subnormal at most 2^-38 M_w |x| once more.  Any tile's maximum is at most the maximum M_x of the output's (batch, group)
+ *     slab, any block's row maximum at most the row's M_w.  With K = Cin 3^dim terms and eps_acc = (K + 2) 2^-24, the fp32
+ *     accumulation allowance of the default mode (the products are exact here; the K-split folds are fp32 additions like its):
+ *       |err| <= (2^-10 + 2^-22 + eps_acc) * sum |w x|  +  2^-37 * ( M_w * sum |x|  +  M_x * sum |w| )
+ *   The mode is a permission, not an order: the one-position form, the dense 2^d form, the four-channel kernels, quad shapes
+ *   below 16 input channels per group, every weight-gradient kernel and the 1x1 skip GEMM stay fp32.  Other values of p select
+ *   CT_GCONV_PRECISION_HIGHEST.
+ * ct_gconv_precision_override(p): p = 0 / 1 sets the mode for the entry points the CALLING THREAD invokes, whatever the
+ * process-wide value says, p < 0 ends the override: how a backward-data runs in its forward's precision on whichever thread it
+ * is called.  ct_get_gconv_precision() returns the value in effect for the calling thread.
+ * ct_gconv_precision_covers(pass, ...): pass 0 = ct_gconv_fwd / ct_gconv_fwd_norm, 1 = ct_gconv_bwd_data; 1 when that call takes a
+ * one-term kernel under CT_GCONV_PRECISION_HIGH for tensors on the 16-byte grid, else 0.  The host planner's answer: no device, and
+ * independent of the current mode.
+ * HIP graphs: the mode is read when a launch is recorded; a replay runs the captured kernels.
+ * ---------------------------------------------------------------------- */
+#define CT_GCONV_PRECISION_HIGHEST 0   /* fp32 MFMA: the default, as before */
+#define CT_GCONV_PRECISION_HIGH    1   /* one f16 term per operand: 11-bit significands (TF32-class), fp32 accumulation */
+void ct_set_gconv_precision(int p);      /* process-wide, atomic; other values -> HIGHEST */
+int  ct_get_gconv_precision(void);       /* the effective value for the calling thread */
+void ct_gconv_precision_override(int p); /* this thread's entry points only; -1: none */
+int  ct_gconv_precision_covers(int pass, int B, int groups, int Cin, int Cout, int dim, const int* W);
 
 /* ------------------------------------------------------------------------
  * Plane-resident MHCT core: the part of a MultiHead block between its norms,
