@@ -258,6 +258,8 @@ SIGNATURES = {
     "ct_debug_set_nseg": (None, [_i]),
     "ct_debug_last_launch": (ctypes.c_char_p, []),
     "ct_slice_fwd": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _ip, _vp]),
+    "ct_splat_slice_fwd_supported": (_i, [_i, _i, _i, _i, _i, _ip, _i, _i]),
+    "ct_splat_slice_fwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _ip, _i, _vp]),
     "ct_slice_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _ip, _vp]),
     "ct_slice_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _ip]),
     "ct_slice_bwd_ws": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _ip, _vp]),

@@ -1165,6 +1165,7 @@ __global__ void __launch_bounds__(THREADS, THREADS == 1024 ? 4 : CT_QUAD_WAVES) 
 }
 
 #include "ct_raster_hot.h"
+#include "ct_raster_fwd_fused.h"
 #include "ct_raster_hot3d.h"
 CT_KERNARG_IS_ARGS_AND_GRID((splat_max_bwd_hot_kernel<false, 32, 2>), 2);      // (defined in ct_raster_hot.h, ahead of the macro)
 CT_KERNARG_IS_ARGS_AND_GRID((splat_max_bwd_hot_kernel<true, 0, 0, kHotWideThreads>), 2);
@@ -1337,6 +1338,8 @@ struct Switches {
   int sorted;          // CLOUDCT_SORTED (-1: not set; 0 turns the sorted forms off)
   bool wide;           // CLOUDCT_WIDE (0 turns the WIDE launches off)
   bool det;            // ct_set_deterministic: Splat(max) backward under the lowest-index rule, ordered g_keys
+  int fused_fwd;       // CLOUDCT_FUSED_FWD (-1: not set; 1: the fused Splat + Slice forward on every shape it supports)
+  int fused_geom;      // CLOUDCT_FUSED_FWD_GEOM (A/B runs; 0: the default geometry, 1: whole planes, 2: chunks of eight channels)
   bool has(unsigned f) const { return (flags & f) != 0; }
   bool hot() const { return !has(CT_DEBUG_NO_HOT); }
 };
@@ -1346,9 +1349,10 @@ Switches read_switches() {
     return e ? atoi(e) : unset;
   };
   static const int sorted = env("CLOUDCT_SORTED", -1), wide = env("CLOUDCT_WIDE", 1), nseg = env("CLOUDCT_SPLAT_BWD_NSEG", 0);
+  static const int fused_fwd = env("CLOUDCT_FUSED_FWD", -1), fused_geom = env("CLOUDCT_FUSED_FWD_GEOM", 0);
   const int dbg = t_dbg_nseg.load(std::memory_order_relaxed);
   return {t_dbg_flags.load(std::memory_order_relaxed), dbg ? dbg : nseg, sorted, wide != 0,
-          det_now()};
+          det_now(), fused_fwd, fused_geom};
 }
 
 // ---------------------------------------------------------------------------
@@ -2692,6 +2696,73 @@ RasterArgs base_args(int B, int H, int C, int N, const void* pad, int pad_dtype)
   return a;
 }
 
+// ---------------------------------------------------------------------------
+// Splat(max) forward + Slice forward in one launch (ct_raster_fwd_fused.h): which shapes take it and how the launch is cut.  Pure
+// arithmetic on the shape, the switches and the low bits of the pointers involved: ct_splat_slice_fwd_supported answers from it
+// (no pointers: zero bits) and ct_splat_slice_fwd launches from it.
+//   Geometry, by measurement (profiles/fused_fwd_ab.txt): kFusedGeomPlane — one workgroup per plane with all its channels, the
+//   integer and the interleaved tile side by side in up to a whole CU's LDS; kFusedGeomChunk8 — chunks of eight channels, two
+//   co-resident workgroups per CU (as the separate scatter's launch at the headline shape).
+//   Taken without flags only where it was measured: kFusedFwdMeasuredWin and the headline's class of shapes (two or more planes
+//   per CU, 32 x 32, C16, N4096, no padding).  CT_DEBUG_FORCE_HOT (tests) and CLOUDCT_FUSED_FWD=1 take it wherever it is legal;
+//   CT_DEBUG_NO_HOT keeps it off.
+// ---------------------------------------------------------------------------
+// the family's launch tag: an entry point of its own, outside the table of the four Splat / Slice entry points' families
+// (tests/raster_families.py); tests/test_splat_slice_fused_gpu.py pins it on every parity case
+constexpr const char* kFusedFwdTag = "splat_slice_fwd_fused";
+enum FusedFwdGeom { kFusedGeomPlane = 1, kFusedGeomChunk8 = 2 };
+constexpr FusedFwdGeom kFusedFwdDefaultGeom = kFusedGeomChunk8;
+constexpr bool kFusedFwdMeasuredWin = true;
+struct FusedFwdPlan {
+  bool ok;
+  FusedFwdGeom geom;
+  int CC, nchunks, threads;
+  size_t lds;
+};
+
+FusedFwdPlan fused_fwd_plan(const Switches sw, int B, int H, int C, int N, int dim, const int* W, int reduce, int pad_dtype,
+                            uintptr_t ptr_bits) {
+  FusedFwdPlan p = {};
+  if (!valid_common(B, H, C, N, dim, W) || dim != 2 || reduce != CT_REDUCE_MAX0 || !sw.hot()) return p;
+  if (pad_dtype != CT_PAD_NONE && pad_dtype != CT_PAD_F32 && pad_dtype != CT_PAD_I32) return p;
+  const int G = W[0] * W[1];
+  if ((N & 3) != 0 || (N >> 2) > kFusedFwdThreads || (C & 3) != 0 || (G & 3) != 0 || (ptr_bits & 15) != 0) return p;
+  p.geom = sw.fused_geom == kFusedGeomPlane ? kFusedGeomPlane : sw.fused_geom == kFusedGeomChunk8 ? kFusedGeomChunk8 : kFusedFwdDefaultGeom;
+  p.CC = p.geom == kFusedGeomPlane ? C : std::min(C, 8);
+  p.nchunks = (C + p.CC - 1) / p.CC;
+  p.lds = (size_t)2 * p.CC * G * 4;
+  if (p.lds > (size_t)(p.geom == kFusedGeomPlane ? kBigLdsBytes : kHalfCuLdsBytes)) return p;
+  p.threads = round_threads(N >> 2);
+  const bool measured = kFusedFwdMeasuredWin && (long long)B * H >= 512 && W[0] == 32 && W[1] == 32 && C == 16 && N == 4096 &&
+                        pad_dtype == CT_PAD_NONE;
+  p.ok = measured || sw.has(CT_DEBUG_FORCE_HOT) || sw.fused_fwd == 1;
+  return p;
+}
+
+int run_splat_slice_fwd(const FusedFwdPlan& p, RasterArgs a, const int* W, hipStream_t st) {
+  const GridW<2> g = make_grid<2>(W);
+  a.CC = p.CC;
+  a.nchunks = p.nchunks;
+  const dim3 grid(p.nchunks, a.H, a.B);
+  // instantiated for the headline's 32 x 32 grid beside the general form (padding: the general form); the 64-register bound that lets
+  // two chunk workgroups share a CU exists for the 32 x 32 instance only (ct_raster_fwd_fused.h)
+  const int r = with_pad_extent<true, 32>(a, g, [&](auto pad, auto wt) {
+    constexpr bool PAD = decltype(pad)::value;
+    constexpr int WT = decltype(wt)::value;
+    if constexpr (WT == 32) {
+      if (p.geom == kFusedGeomChunk8) {
+        CT_LAUNCH((splat_slice_fwd_kernel<PAD, WT, 8>), grid, p.threads, p.lds, st, a, g);
+        return CT_OK;
+      }
+    }
+    CT_LAUNCH((splat_slice_fwd_kernel<PAD, WT, 4>), grid, p.threads, p.lds, st, a, g);
+    return CT_OK;
+  });
+  if (r != CT_OK) return r;
+  note(kFusedFwdTag);
+  return CT_OK;
+}
+
 template <bool FROM_KEYS>
 int splat_fwd_impl(PosSrc pos, const float* feat, const void* pad, int pad_dtype, float* grid,
                    int B, int H, int C, int N, int dim, const int* W, int reduce, hipStream_t st) {
@@ -2959,6 +3030,24 @@ int ct_slice_fwd(const float* keys, const float* grid, const void* pad, int pad_
   if (!keys) return CT_EINVAL;
   PosSrc pos = {keys, nullptr, nullptr};
   return slice_fwd_impl<true>(pos, grid, pad, pad_dtype, out, B, H, C, N, dim, W, (hipStream_t)s);
+}
+
+int ct_splat_slice_fwd_supported(int B, int H, int C, int N, int dim, const int* W, int reduce, int pad_dtype) {
+  return fused_fwd_plan(read_switches(), B, H, C, N, dim, W, reduce, pad_dtype, 0).ok ? 1 : 0;
+}
+
+int ct_splat_slice_fwd(const float* keys, const float* feat, const void* pad, int pad_dtype, float* grid, float* out,
+                       int B, int H, int C, int N, int dim, const int* W, int reduce, ct_stream_t s) {
+  if (!keys || !feat || !grid || !out || !valid_pad(pad, pad_dtype)) return CT_EINVAL;
+  const Switches sw = read_switches();
+  const uintptr_t bits = (uintptr_t)keys | (uintptr_t)feat | (uintptr_t)grid | (uintptr_t)out;
+  const FusedFwdPlan p = fused_fwd_plan(sw, B, H, C, N, dim, W, reduce, pad_dtype, bits);
+  if (!p.ok) return CT_EINVAL;
+  note_reset();
+  RasterArgs a = base_args(B, H, C, N, pad, pad_dtype);
+  a.pos = {keys, nullptr, nullptr};
+  a.src = feat; a.tile_out = grid; a.dst = out;
+  return run_splat_slice_fwd(p, a, W, (hipStream_t)s);
 }
 
 int ct_slice_bwd(const float* keys, const float* grid, const void* pad, int pad_dtype, const float* g_out,

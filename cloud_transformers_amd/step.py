@@ -4,6 +4,8 @@ This is the unit `bench.py` times and `__graft_entry__.smoke()` checks: every
 buffer is allocated once, the four ABI calls enqueue on torch's current stream,
 so a whole step can be captured into a HIP graph and replayed.
 """
+import os
+
 import torch
 
 from . import _lib
@@ -14,7 +16,8 @@ from .ops import _ptr, _stream, sizes_of
 class SplatSliceStep:
     """out = Slice(keys, Splat(keys, feat)); backward from the cotangent `cot`.
 
-    forward : z = ct_splat_fwd(keys, feat);  out = ct_slice_fwd(keys, z)
+    forward : z = ct_splat_fwd(keys, feat);  out = ct_slice_fwd(keys, z) — or both from ct_splat_slice_fwd, one launch, where
+              the library takes the shape (ct_splat_slice_fwd_supported) and CLOUDCT_FUSED_FWD is not 0: the same bits
     backward: g_z, g_keys_slice = ct_slice_bwd_tk(keys, z, cot)
               g_feat, g_keys = ct_splat_bwd_tk(keys, feat, z, g_z, add = g_keys_slice)
     The keys feed both ops, so their two key cotangents are summed (what autograd does in the module path); the
@@ -56,6 +59,11 @@ class SplatSliceStep:
         nps = self.lib.ct_plane_sort_bytes(self.B, self.H, self.N, dim, self.Wa) if plane_sort else 0
         self.sorted = torch.empty(nps, device=dev, dtype=torch.uint8) if nps else None
         self.nps = nps
+        # the forward in one launch (ct_splat_slice_fwd) where the library says so; CLOUDCT_FUSED_FWD=0 keeps the two calls (A/B runs).
+        # Decided once, here: a captured graph and the eager step of one object launch the same kernels.
+        self.fused_fwd = (os.environ.get("CLOUDCT_FUSED_FWD", "") != "0" and
+                          bool(self.lib.ct_splat_slice_fwd_supported(self.B, self.H, self.C, self.N, dim, self.Wa, self.red, 0)))
+        self._forward_tag = None
         if tickets and reduce == "max" and self.lib.ct_splat_bwd_tk_segments(self.B, self.H, self.C, self.N, dim, self.Wa) > 1:
             self.g_keys_out = torch.empty_like(self.keys)    # ... or into a second tensor where point segments pay (ct_splat_bwd_tk)
 
@@ -74,6 +82,12 @@ class SplatSliceStep:
         _lib.check(self.lib.ct_slice_fwd(_ptr(self.keys), _ptr(self.z), None, 0, _ptr(self.out),
                                          self.B, self.H, self.C, self.N, self.dim, self.Wa, _stream()),
                    "ct_slice_fwd")
+
+    def splat_slice_fwd(self):
+        """z and out in one launch: the bits of splat_fwd() followed by slice_fwd() (only where self.fused_fwd)"""
+        _lib.check(self.lib.ct_splat_slice_fwd(_ptr(self.keys), _ptr(self.feat), None, 0, _ptr(self.z), _ptr(self.out),
+                                               self.B, self.H, self.C, self.N, self.dim, self.Wa, self.red, _stream()),
+                   "ct_splat_slice_fwd")
 
     def slice_bwd_grid(self):
         _lib.check(self.lib.ct_slice_bwd_grid(_ptr(self.keys), None, 0, _ptr(self.cot), _ptr(self.g_z),
@@ -111,6 +125,7 @@ class SplatSliceStep:
         "scatter_add_sorted": "slice_bwd_sorted_kernel<false, 32, false, false",
         "splat_sum_bwd_hot": "splat_sum_bwd_kernel",
         "gather_ci": "gather_ci_kernel",
+        "splat_slice_fwd_fused": "splat_slice_fwd_kernel",
         "gather_quad": "quad_kernel<2, 0,",
         "slice_bwd_fused": "slice_bwd_fused_kernel",
         "slice_bwd_sorted": "slice_bwd_sorted_kernel<false, 32, false, true",
@@ -140,10 +155,25 @@ class SplatSliceStep:
     def run(self):
         self.lib.ct_set_deterministic(1 if self.deterministic else 0)      # the mode the workspaces were planned under
         self.plane_sort()
-        self.splat_fwd()
-        self.slice_fwd()
+        self.forward()
         self.slice_bwd()
         self.splat_bwd()
+
+    def forward(self):
+        """z and out: one launch where the fused forward takes the shape, else the two calls"""
+        record = self._forward_tag is None
+        tags = []
+        for call in ((self.splat_slice_fwd,) if self.fused_fwd else (self.splat_fwd, self.slice_fwd)):
+            call()
+            if record:
+                tags.append(self.lib.ct_debug_last_launch().decode())
+        if record:
+            self._forward_tag = "+".join(tags)
+
+    def forward_tag(self):
+        """kernel-family tags of what run()'s forward launches (recorded at the first run(); None before it).  With the fused
+        forward the per-pass timings of `PASSES` remain those of the separate kernels and no longer add up to the step."""
+        return self._forward_tag
 
     def g_keys(self):
         """d(out . cot)/d(keys) after run(): Slice's and Splat's key cotangents, already summed"""

@@ -196,6 +196,20 @@ int ct_slice_fwd(const float* keys, const float* grid, const void* pad, int pad_
 int ct_slice_bwd(const float* keys, const float* grid, const void* pad, int pad_dtype,
                  const float* g_out, float* g_grid, float* g_keys,
                  int B, int H, int C, int N, int dim, const int* W, ct_stream_t s);
+/* Splat(max) forward and Slice forward on the same keys in ONE launch: grid = ct_splat_fwd(keys, feat), out = ct_slice_fwd(keys,
+ * grid), both written, with the bits the two calls write (csrc/ct_raster_fwd_fused.h: a plane's tile stays in LDS between the two
+ * halves; `grid` is written once and not read back).  For callers that chain the two ops directly (SplatSliceStep); a block with a
+ * grouped convolution between them uses ct_mhct_core_fwd.
+ * ct_splat_slice_fwd_supported: 1 where the call takes the shape under the current switches, else 0.  Legal are dim == 2, reduce ==
+ * CT_REDUCE_MAX0, N % 4 == 0, N <= 4096, C % 4 == 0, G % 4 == 0, the tiles of a workgroup within its LDS budget, with or without a
+ * padding mask; of these it answers 1 where the kernel was measured against the two calls and won, wherever it is
+ * legal under CT_DEBUG_FORCE_HOT or CLOUDCT_FUSED_FWD=1 (read once per process), and nowhere under CT_DEBUG_NO_HOT.
+ * ct_splat_slice_fwd: CT_EINVAL, before anything is launched or written, where the query answers 0 and for a null or not 16-byte
+ * aligned keys / feat / grid / out; the launch tag is "splat_slice_fwd_fused".  Added under CT_ABI_VERSION 3 (additive symbols). */
+int ct_splat_slice_fwd_supported(int B, int H, int C, int N, int dim, const int* W, int reduce, int pad_dtype);
+int ct_splat_slice_fwd(const float* keys, const float* feat, const void* pad, int pad_dtype,
+                       float* grid, float* out, int B, int H, int C, int N, int dim, const int* W,
+                       int reduce, ct_stream_t s);
 /* ct_slice_bwd with scratch: with few (b,h) planes (the zoo's H = 16 blocks) the channel chunks of a plane are dealt to
  * several workgroups, whose partial g_keys go through `workspace` (ct_slice_bwd_workspace_bytes(...) bytes, may be 0).
  * Same results as ct_slice_bwd, which has to keep one workgroup per plane there. */
