@@ -41,7 +41,13 @@ struct EmdWs {
   int* unass_idx;    // [B,n]
   int* unass_cnt;    // [B]
   int* sync;         // [B][3]: arrivals before Assign | arrivals at the end | entries of the list being written (emd_update_multi_kernel)
+                     // ragged path (ct_emd_fwd_counts: no emd_update_multi_kernel there): [3 * b] = the rows of cloud b, see emd_extent
 };
+
+// Ragged path (RAGGED instantiations below): cloud b is the rows [0, c) of a tensor with row stride n; c is count[b] clamped into
+// [0, n] ONCE, by the init kernel, into the workspace word the dense path uses as an arrival counter — the bid and update
+// kernels read it from there (device memory, never the host), so their dense instantiations keep their arguments and their code.
+__device__ __forceinline__ int emd_extent(const EmdWs& w, int b) { return w.sync[3 * b]; }
 
 __device__ __forceinline__ int ld_coherent(const int* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -50,7 +56,8 @@ __device__ __forceinline__ float ld_coherent(const float* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__global__ void emd_init_kernel(EmdWs w, int* assignment, size_t total, int nsync) {
+template <bool RAGGED>
+__global__ void emd_init_kernel(EmdWs w, int* assignment, size_t total, int nsync, const int* count, int n) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
   assignment[i] = -1;
@@ -60,18 +67,25 @@ __global__ void emd_init_kernel(EmdWs w, int* assignment, size_t total, int nsyn
   w.max_idx[i] = -1;
   w.bid[i] = 0;
   w.bid_inc[i] = 0.0f;
-  if (i < (size_t)nsync) w.sync[i] = 0;
+  if (i < (size_t)nsync) {
+    if (RAGGED) w.sync[3 * i] = count ? min(max(count[i], 0), n) : n;      // nsync = B (<= total): the clouds' extents, see emd_extent
+    else w.sync[i] = 0;
+  }
 }
 
 // One workgroup per batch.  do_assign: GetMax + Assign for the bids of the iteration
 // that just ran (emd_cuda.cu:181-215).  do_compact: rebuild the unassigned list
 // (emd_cuda.cu:30-93).  do_dist: CalcDist (emd_cuda.cu:217-226).
+// RAGGED: the cloud is the rows [0, c), c = emd_extent (<= n, any value): the compactions stop at c — a row at or beyond it keeps
+// assignment -1 for good and must never enter the list — and CalcDist writes 0 there.  Everything else walks the list.
+template <bool RAGGED>
 __global__ void __launch_bounds__(1024)
 emd_update_kernel(EmdWs w, int* assignment, const float* xyz1, const float* xyz2, float* dist,
                   int n, int do_assign, int last, int do_compact, int do_dist) {
   __shared__ int s_scan[16];
   const int b = blockIdx.x;
   const size_t off = (size_t)b * n;
+  const int c = RAGGED ? emd_extent(w, b) : n;         // rows of this cloud (block-uniform)
   int* ass = assignment + off;
   int* ass_inv = w.ass_inv + off;
   int* bid = w.bid + off;
@@ -236,15 +250,16 @@ emd_update_kernel(EmdWs w, int* assignment, const float* xyz1, const float* xyz2
   if (do_compact) {
     // ascending list of unassigned points: a thread owns n/1024 (<= 64 per segment) consecutive points, keeps their
     // flags as a bit mask, and one block-wide exclusive scan of the per-thread counts places its entries
+    // (RAGGED: ceil(c / 1024) points per thread, the last threads' runs cut at c; a full segment still has exactly 64)
     int base = 0;
-    for (int seg = 0; seg < n; seg += 65536) {
-      const int per = min(n - seg, 65536) >> 10;        // n % 1024 == 0
+    for (int seg = 0; seg < c; seg += 65536) {
+      const int per = RAGGED ? (min(c - seg, 65536) + 1023) >> 10 : min(n - seg, 65536) >> 10;        // dense: n % 1024 == 0
       const int j0 = seg + (int)threadIdx.x * per;
       unsigned long long mask = 0ull;
       for (int u0 = 0; u0 < per; u0 += kUpR) {
         int a[kUpR];
 #pragma unroll
-        for (int u = 0; u < kUpR; ++u) a[u] = (u0 + u < per) ? ld_coherent(&ass[j0 + u0 + u]) : 0;
+        for (int u = 0; u < kUpR; ++u) a[u] = (u0 + u < per && (!RAGGED || j0 + u0 + u < c)) ? ld_coherent(&ass[j0 + u0 + u]) : 0;
 #pragma unroll
         for (int u = 0; u < kUpR; ++u)
           if (a[u] == -1) mask |= 1ull << (u0 + u);
@@ -261,9 +276,9 @@ emd_update_kernel(EmdWs w, int* assignment, const float* xyz1, const float* xyz2
       __syncthreads();
       int wave_off = 0, total = 0;
       for (int q = 0; q < (int)(blockDim.x >> 6); ++q) {
-        const int c = s_scan[q];
-        if (q < wave) wave_off += c;
-        total += c;
+        const int cq = s_scan[q];
+        if (q < wave) wave_off += cq;
+        total += cq;
       }
       int pos = base + wave_off + v - cnt;
       while (mask) {
@@ -281,6 +296,7 @@ emd_update_kernel(EmdWs w, int* assignment, const float* xyz1, const float* xyz2
     const float* p1 = xyz1 + off * 3;
     const float* p2 = xyz2 + off * 3;
     for (int j = threadIdx.x; j < n; j += blockDim.x) {
+      if (RAGGED && j >= c) { dist[off + j] = 0.0f; continue; }
       const int k = ld_coherent(&ass[j]);
       const float dx = p1[j * 3 + 0] - p2[k * 3 + 0];
       const float dy = p1[j * 3 + 1] - p2[k * 3 + 1];
@@ -457,7 +473,14 @@ __device__ __forceinline__ void top2_push(Top2& t, float d, int idx) {
   t.best = fmaxf(t.best, d);
 }
 
-// grid = (blocks per batch, B).  n % 1024 == 0 (checked by ct_emd_fwd), so every tile is full.
+// grid = (blocks per batch, B).  Dense: n % 1024 == 0 (checked by ct_emd_fwd), so every tile is full.
+// RAGGED (ct_emd_fwd_counts; 1024-target tiles only): the targets are the rows [0, c), c = emd_extent, ceil(c / KTILE) tiles; the
+// slots of the last tile at or beyond c are not loaded but staged as the sentinel {0, 0, 0, price = +inf}.  Its value
+// 3 - sqrt(d2) - inf is -inf: `d > best` is false against the initial -1e9, the median of (best, better, -inf) leaves `better`
+// alone (-1e9 with a single real target, as in the sequential scan) and the maximum leaves `best` alone, so it is never best or
+// second best and never feeds the threshold.  In the candidate filter tt = cthr - inf = -inf, tt * |tt| = -inf < d2: dropped
+// without its sqrt; with the filter off (cthr = inf) tt is NaN, the comparison is false and the slot takes the slow path, where
+// the -inf above does nothing.  Bidders come from the list, which holds rows below c only.
 // Late iterations have a handful of bidders and are pure latency: the next tile's global loads are in flight
 // while the current one is scanned (registers -> the other LDS buffer, one barrier per tile), a bidder gets up
 // to all 256 lanes, and the scan is unrolled by 4 so that four ds_read_b128 and four sqrt chains overlap.
@@ -468,7 +491,7 @@ __device__ __forceinline__ void top2_push(Top2& t, float d, int idx) {
 // 4096-target tiles two deep on half as many workgroups: 4 steps instead of 16 (50 iterations at B2 n = 16384: 3.48 -> 3.34 ms
 // on uniform clouds, 2.69 -> 2.49 ms on a blob against a sphere shell).  Measured and dropped: the targets packed with their
 // prices as one float4 array (one 16-byte load per target instead of four dwords: +10 us per launch), rotated tile orders.
-template <int KTILE, int KDEPTH>
+template <int KTILE, int KDEPTH, bool RAGGED>
 __global__ void __launch_bounds__(kBidThreads)
 emd_bid_kernel(EmdWs w, const float* __restrict__ xyz1, const float* __restrict__ xyz2, int n, float eps, int u_min, int u_max) {
   constexpr int kTile = KTILE, kDepth = KDEPTH;
@@ -499,7 +522,7 @@ emd_bid_kernel(EmdWs w, const float* __restrict__ xyz1, const float* __restrict_
   int T = kBidThreads / groups;                                 // lanes per bidder (pair)
   T = T < 1 ? 1 : (T > 256 ? 256 : T);                         // (a tile holds 1024 targets: 4 per lane and step at most)
   T = 1 << (31 - __clz(T));                                     // power of two: a bidder is a lane group of a wave, or whole waves
-  // nblk >= n/128 >= U/128  =>  per_blk <= 128  =>  T >= 4
+  // nblk >= n/128 >= U/128  =>  per_blk <= 128  =>  T >= 4   (RAGGED: nblk = ceil(n / 64) and U <= c <= n)
   const int slot = threadIdx.x / T, sub = threadIdx.x % T;
   const bool active = two ? 2 * slot < mine : slot < mine;
   int j = -1, jb = -1;                                          // (jb: the pair's second bidder, -1 when the count is odd)
@@ -519,9 +542,14 @@ emd_bid_kernel(EmdWs w, const float* __restrict__ xyz1, const float* __restrict_
   }
   // software pipeline: tile t is scanned from LDS while tiles t+2 .. t+1+kDepth are in flight to registers
   float4 stage[kDepth][kPer];
+  const int c = RAGGED ? emd_extent(w, b) : n;                  // targets of this cloud (U > 0 => c > 0)
   auto fetch = [&](int t, float4 (&st)[kPer]) {
 #pragma unroll
     for (int e = 0; e < kPer; ++e) {
+      if (RAGGED && t * kTile + e * kBidThreads + (int)threadIdx.x >= c) {      // predicated: nothing at or beyond c is read
+        st[e] = make_float4(0.0f, 0.0f, 0.0f, __builtin_inff());
+        continue;
+      }
       const size_t k = off + (size_t)t * kTile + e * kBidThreads + threadIdx.x;
       const float* p = xyz2 + k * 3;
       st[e] = make_float4(p[0], p[1], p[2], w.price[k]);
@@ -531,7 +559,7 @@ emd_bid_kernel(EmdWs w, const float* __restrict__ xyz1, const float* __restrict_
 #pragma unroll
     for (int e = 0; e < kPer; ++e) tile[buf][e * kBidThreads + threadIdx.x] = st[e];
   };
-  const int ntiles = n / kTile;
+  const int ntiles = RAGGED ? (c + kTile - 1) / kTile : n / kTile;
 #pragma unroll
   for (int r = 0; r < kDepth; ++r)
     if (r < ntiles) fetch(r, stage[r]);
@@ -702,11 +730,20 @@ emd_bid_kernel(EmdWs w, const float* __restrict__ xyz1, const float* __restrict_
   }
 }
 
+// RAGGED: a row at or beyond its cloud's count gets +0.0 by a plain store — its g_dist (NaN, perhaps) and assignment are not read.
+template <bool RAGGED>
 __global__ void emd_grad_kernel(const float* xyz1, const float* xyz2, const float* g_dist, const int* assignment,
-                                float* g_xyz1, int n, size_t total) {
+                                float* g_xyz1, int n, size_t total, const int* count) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
   const size_t b = i / n;
+  if (RAGGED) {
+    if (count && (int)(i - b * n) >= min(max(count[b], 0), n)) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) g_xyz1[i * 3 + c] = 0.0f;
+      return;
+    }
+  }
   const int k = assignment[i];
   const float g = g_dist[i] * 2.0f;
 #pragma unroll
@@ -724,6 +761,21 @@ int emd_cu_count() {
             ? prop.multiProcessorCount : 256;
   }
   return n;
+}
+EmdWs emd_carve(void* workspace, int B, int n) {
+  char* p = (char*)workspace;
+  const size_t seg = align256((size_t)B * n * 4);
+  EmdWs w;
+  w.price = (float*)p; p += seg;
+  w.bid_inc = (float*)p; p += seg;
+  w.max_inc = (float*)p; p += seg;
+  w.ass_inv = (int*)p; p += seg;
+  w.bid = (int*)p; p += seg;
+  w.max_idx = (int*)p; p += seg;
+  w.unass_idx = (int*)p; p += seg;
+  w.unass_cnt = (int*)p; p += align256((size_t)B * 4);
+  w.sync = (int*)p;
+  return w;
 }
 int g_emd_single_update = -1;         // test hook (ct_debug_set_emd; env CLOUDCT_EMD_SINGLE_UPDATE read once): the update on one workgroup per batch
 
@@ -743,26 +795,16 @@ int ct_emd_fwd(const float* xyz1, const float* xyz2, float* dist, int32_t* assig
   if (n % 1024 != 0 || B > 512) return CT_EPRECOND;
   if (workspace_bytes < ct_emd_workspace_bytes(B, n)) return CT_EWORKSPACE;
   hipStream_t st = (hipStream_t)s;
-  char* p = (char*)workspace;
-  const size_t seg = align256((size_t)B * n * 4);
-  EmdWs w;
-  w.price = (float*)p; p += seg;
-  w.bid_inc = (float*)p; p += seg;
-  w.max_inc = (float*)p; p += seg;
-  w.ass_inv = (int*)p; p += seg;
-  w.bid = (int*)p; p += seg;
-  w.max_idx = (int*)p; p += seg;
-  w.unass_idx = (int*)p; p += seg;
-  w.unass_cnt = (int*)p; p += align256((size_t)B * 4);
-  w.sync = (int*)p;
+  const EmdWs w = emd_carve(workspace, B, n);
   const size_t total = (size_t)B * n;
   CT_CLEAR_ERROR();
-  hipLaunchKernelGGL(emd_init_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w, (int*)assignment, total, 3 * B);
-  hipLaunchKernelGGL(emd_update_kernel, dim3(B), dim3(1024), 0, st, w, (int*)assignment, xyz1, xyz2, dist, n, 0, 0, 1, 0);
+  hipLaunchKernelGGL(emd_init_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w, (int*)assignment, total, 3 * B,
+                     (const int*)nullptr, n);
+  hipLaunchKernelGGL(emd_update_kernel<false>, dim3(B), dim3(1024), 0, st, w, (int*)assignment, xyz1, xyz2, dist, n, 0, 0, 1, 0);
   const dim3 bid_grid(n / 64, B);
   constexpr int kBigTile = 4096;
   const bool big_ok = n % kBigTile == 0 && n >= 2 * kBigTile &&
-                      hipFuncSetAttribute((const void*)emd_bid_kernel<kBigTile, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                      hipFuncSetAttribute((const void*)emd_bid_kernel<kBigTile, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                           2 * kBigTile * (int)sizeof(float4)) == hipSuccess;
   // the per-batch update on several workgroups (emd_update_multi_kernel): every list entry needs a thread's register slot and
   // every workgroup of the grid must be resident for their meeting
@@ -780,19 +822,45 @@ int ct_emd_fwd(const float* xyz1, const float* xyz2, float* dist, int32_t* assig
     // tiles); a collapsed cloud — the completion network's output early in training — keeps 6000-8000 bidding to the end,
     // where the big tiles on half the workgroups cost 9.87 vs 8.78 ms.
     if (big_ok && it >= kEmdBigFrom) {
-      hipLaunchKernelGGL((emd_bid_kernel<kBigTile, 2>), dim3(n / 128, B), dim3(kBidThreads), 2 * kBigTile * sizeof(float4), st, w, xyz1, xyz2, n, eps,
+      hipLaunchKernelGGL((emd_bid_kernel<kBigTile, 2, false>), dim3(n / 128, B), dim3(kBidThreads), 2 * kBigTile * sizeof(float4), st, w, xyz1, xyz2, n, eps,
                          0, kEmdBigMaxU);
-      hipLaunchKernelGGL((emd_bid_kernel<kTile, 4>), bid_grid, dim3(kBidThreads), 2 * kTile * sizeof(float4), st, w, xyz1, xyz2, n, eps,
+      hipLaunchKernelGGL((emd_bid_kernel<kTile, 4, false>), bid_grid, dim3(kBidThreads), 2 * kTile * sizeof(float4), st, w, xyz1, xyz2, n, eps,
                          kEmdBigMaxU + 1, 0x7fffffff);
     } else {
-      hipLaunchKernelGGL((emd_bid_kernel<kTile, 4>), bid_grid, dim3(kBidThreads), 2 * kTile * sizeof(float4), st, w, xyz1, xyz2, n, eps,
+      hipLaunchKernelGGL((emd_bid_kernel<kTile, 4, false>), bid_grid, dim3(kBidThreads), 2 * kTile * sizeof(float4), st, w, xyz1, xyz2, n, eps,
                          0, 0x7fffffff);
     }
     if (multi_g > 1 && !last)
       hipLaunchKernelGGL(emd_update_multi_kernel, dim3(multi_g, B), dim3(1024), 0, st, w, (int*)assignment, n, multi_gen++);
     else
-      hipLaunchKernelGGL(emd_update_kernel, dim3(B), dim3(1024), 0, st, w, (int*)assignment, xyz1, xyz2, dist, n,
+      hipLaunchKernelGGL(emd_update_kernel<false>, dim3(B), dim3(1024), 0, st, w, (int*)assignment, xyz1, xyz2, dist, n,
                          1, last, last ? 0 : 1, last);
+  }
+  CT_CHECK_LAUNCH();
+  return CT_OK;
+}
+
+// Any n, per-cloud counts read on the device (cloudct.h): the RAGGED instantiations, 1024-target tiles and the single-workgroup
+// update in every iteration.  Nothing depends on the counts' values on the host: same launches for every count.
+int ct_emd_fwd_counts(const float* xyz1, const float* xyz2, const int32_t* count, float* dist, int32_t* assignment, void* workspace,
+                      size_t workspace_bytes, int B, int n, float eps, int iters, ct_stream_t s) {
+  if (!xyz1 || !xyz2 || !dist || !assignment || !workspace || B <= 0 || n <= 0 || iters < 1) return CT_EINVAL;
+  if (B > 512) return CT_EPRECOND;
+  if (workspace_bytes < ct_emd_workspace_bytes(B, n)) return CT_EWORKSPACE;
+  hipStream_t st = (hipStream_t)s;
+  const EmdWs w = emd_carve(workspace, B, n);
+  const size_t total = (size_t)B * n;
+  CT_CLEAR_ERROR();
+  hipLaunchKernelGGL(emd_init_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w, (int*)assignment, total, B,
+                     (const int*)count, n);
+  hipLaunchKernelGGL(emd_update_kernel<true>, dim3(B), dim3(1024), 0, st, w, (int*)assignment, xyz1, xyz2, dist, n, 0, 0, 1, 0);
+  const dim3 bid_grid((unsigned)(((size_t)n + 63) / 64), B);   // >= n / 64 workgroups per cloud: at most 64 bidders each
+  for (int it = 0; it < iters; ++it) {
+    const int last = it == iters - 1;
+    hipLaunchKernelGGL((emd_bid_kernel<kTile, 4, true>), bid_grid, dim3(kBidThreads), 2 * kTile * sizeof(float4), st, w, xyz1, xyz2, n, eps,
+                       0, 0x7fffffff);
+    hipLaunchKernelGGL(emd_update_kernel<true>, dim3(B), dim3(1024), 0, st, w, (int*)assignment, xyz1, xyz2, dist, n,
+                       1, last, last ? 0 : 1, last);
   }
   CT_CHECK_LAUNCH();
   return CT_OK;
@@ -805,8 +873,19 @@ int ct_emd_bwd(const float* xyz1, const float* xyz2, const float* g_dist, const 
   if (!xyz1 || !xyz2 || !g_dist || !assignment || !g_xyz1 || B <= 0 || n <= 0) return CT_EINVAL;
   const size_t total = (size_t)B * n;
   CT_CLEAR_ERROR();
-  hipLaunchKernelGGL(emd_grad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)s,
-                     xyz1, xyz2, g_dist, (const int*)assignment, g_xyz1, n, total);
+  hipLaunchKernelGGL(emd_grad_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)s,
+                     xyz1, xyz2, g_dist, (const int*)assignment, g_xyz1, n, total, (const int*)nullptr);
+  CT_CHECK_LAUNCH();
+  return CT_OK;
+}
+
+int ct_emd_bwd_counts(const float* xyz1, const float* xyz2, const int32_t* count, const float* g_dist, const int32_t* assignment,
+                      float* g_xyz1, int B, int n, ct_stream_t s) {
+  if (!xyz1 || !xyz2 || !g_dist || !assignment || !g_xyz1 || B <= 0 || n <= 0) return CT_EINVAL;
+  const size_t total = (size_t)B * n;
+  CT_CLEAR_ERROR();
+  hipLaunchKernelGGL(emd_grad_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)s,
+                     xyz1, xyz2, g_dist, (const int*)assignment, g_xyz1, n, total, (const int*)count);
   CT_CHECK_LAUNCH();
   return CT_OK;
 }

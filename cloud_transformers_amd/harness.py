@@ -465,13 +465,13 @@ class Trainer:
 
     def _reconstruct(self, img, pcd_gt, eps, iters, n_noise=None):
         """(sqrt-EMD loss, rec [B, 3, 1, N], gt [B, 3, 1, n]) of train_image_reconstruction.py:166-175 for a device batch."""
-        from .emd import emdModule
+        from .emd import emd_distance
         from .metrics import sphere_noise
         gt = pcd_gt[:, :, None]
         noise = sphere_noise(gt.shape[0], gt.shape[-1] if n_noise is None else n_noise, gt.device, generator=self._noise_gen)
         out = self.model(noise, img)
         rec = out[0] if isinstance(out, (tuple, list)) else out
-        dist, _ = emdModule()(rec[:, :, 0].permute(0, 2, 1), gt[:, :, 0].permute(0, 2, 1), eps, iters)
+        dist, _ = emd_distance(rec[:, :, 0].permute(0, 2, 1), gt[:, :, 0].permute(0, 2, 1), eps, iters)
         return torch.sqrt(dist).mean(1).mean(), rec, gt
 
     def _block_pred(self, pcd):
@@ -508,14 +508,14 @@ class Trainer:
             return self.ce(pred[:, :, 0], labels.to(self.device))
         if self.task == "completion":
             from .chamfer import loss_chamfer
-            from .emd import emdModule
+            from .emd import emd_distance
             noise, part, gt = batch
             out = self.model(noise.to(self.device), part.permute(0, 2, 1)[:, :, None].to(self.device))
             rec = out[0] if isinstance(out, (tuple, list)) else out                   # (B, 3, 1, N)
             gt4 = gt.permute(0, 2, 1)[:, :, None].to(self.device)
             tr = self.cfg["train"]
-            dist, _ = emdModule()(rec[:, :, 0].permute(0, 2, 1), gt4[:, :, 0].permute(0, 2, 1),
-                                  float(tr.get("emd_eps", 0.005)), int(tr.get("emd_iters", 50)))
+            dist, _ = emd_distance(rec[:, :, 0].permute(0, 2, 1), gt4[:, :, 0].permute(0, 2, 1),
+                                   float(tr.get("emd_eps", 0.005)), int(tr.get("emd_iters", 50)))
             return torch.sqrt(dist).mean(1).mean() + float(tr.get("chamfer_weight", 1.0)) * loss_chamfer(rec, gt4)
         pts, label, mask = batch
         logits, mask_pred = self.model(pts.permute(0, 2, 1)[:, :, None].to(self.device))
@@ -536,7 +536,7 @@ class Trainer:
         import json
         from .chamfer import loss_chamfer
         from .data.completion import CompletionBatches
-        from .emd import emdModule
+        from .emd import emd_distance
         cfg, tr = self.cfg, self.cfg["train"]
         if self.shapenet_device and (self.val_loader is None or dataset is not None):
             self.val_loader = self._completion_batches(dataset if dataset is not None else make_dataset(cfg, "completion", None, train=False),
@@ -559,7 +559,7 @@ class Trainer:
                 out = model(noise, part.permute(0, 2, 1)[:, :, None])
                 rec = out[0] if isinstance(out, (tuple, list)) else out
                 gt4 = gt.permute(0, 2, 1)[:, :, None]
-                dist, _ = emdModule()(rec[:, :, 0].permute(0, 2, 1), gt4[:, :, 0].permute(0, 2, 1), eps, iters)
+                dist, _ = emd_distance(rec[:, :, 0].permute(0, 2, 1), gt4[:, :, 0].permute(0, 2, 1), eps, iters)
                 l_emd = torch.sqrt(dist).mean(1).mean()
                 l_cd = loss_chamfer(rec, gt4)
                 sums += torch.stack([l_emd + w * l_cd, l_emd, l_cd, torch.ones_like(l_cd)]).double()

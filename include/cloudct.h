@@ -49,7 +49,8 @@ extern "C" {
  * then Chamfer with per-cloud counts and the metric table: ct_chamfer_fwd_counts / ct_chamfer_bwd_counts / ct_rows_compact /
  * ct_chamfer_metrics; then the backward of the eval-mode norm, ct_bn_eval_group_bwd; then the precision mode of the pointwise
  * GEMMs ct_set_pw_precision / ct_get_pw_precision / ct_pw_precision_override; then that of the grouped convolutions,
- * ct_set_gconv_precision / ct_get_gconv_precision / ct_gconv_precision_override / ct_gconv_precision_covers.) */
+ * ct_set_gconv_precision / ct_get_gconv_precision / ct_gconv_precision_override / ct_gconv_precision_covers; then the EMD auction for any cloud size and per-cloud counts,
+ * ct_emd_fwd_counts / ct_emd_bwd_counts.) */
 #define CT_ABI_VERSION 3
 
 /* status codes */
@@ -727,6 +728,35 @@ int ct_emd_fwd(const float* xyz1, const float* xyz2, float* dist, int32_t* assig
 /* g_xyz1 = 2 g_dist (x1 - x2[assignment]); no gradient to xyz2 (emd_module.py:66-70). */
 int ct_emd_bwd(const float* xyz1, const float* xyz2, const float* g_dist, const int32_t* assignment,
                float* g_xyz1, int B, int n, ct_stream_t s);
+
+/* ------------------------------------------------------------------------
+ * The auction for any cloud size and clouds of different lengths in one batch.  Added under CT_ABI_VERSION 3 (additive
+ * symbols); ct_emd_fwd / ct_emd_bwd above keep their preconditions, their results and their launches.
+ *
+ * xyz1, xyz2 f32[B,n,3]; n is the ROW STRIDE.  Cloud b is the rows [0, c_b) of BOTH tensors, c_b = count[b] clamped into
+ * [0, n] on the device; count is i32[B] in device memory, or null = every row (c_b = n).  The host never reads count: no
+ * synchronisation, the same launches for every value, so a captured graph replays with new counts in the same buffer.
+ * Any n >= 1; B <= 512 (CT_EPRECOND otherwise); iters >= 1.  The workspace is that of ct_emd_workspace_bytes(B, n).
+ *
+ * ct_emd_fwd_counts: rows [0, c_b) of dist and assignment carry the auction of oracle/emd_ref.c run on that pair of clouds
+ *   alone with its n = c_b: value = (float)(3.0 - sqrt(d2) - price) evaluated in double and rounded once, d2 by two fmaf;
+ *   the lowest target index on value ties; the highest bidder index on GetMax window ties; every remaining bidder is
+ *   force-assigned to its bid in the last iteration.  Where c_b % 1024 == 0 those rows are exactly the bits ct_emd_fwd
+ *   returns for that pair at B = 1, n = c_b.  Rows at or beyond c_b are never read, neither as bidders nor as targets (they
+ *   may hold anything, NaN included), and get dist = 0, assignment = -1; no output element is left unwritten.  c_b = 0:
+ *   nothing to do; c_b = 1: assignment[0] = 0.
+ * ct_emd_bwd_counts: g_xyz1 = 2 g_dist (x1 - x2[assignment]) on the rows below c_b; the rows at or beyond it receive an
+ *   exact +0.0 by a store, their g_dist and assignment are not read (a NaN there does not leak).
+ *
+ * CT_EINVAL for a null required pointer (everything but count), B <= 0, n <= 0 or iters < 1; CT_EPRECOND for B > 512;
+ * CT_EWORKSPACE for a short workspace — all before any launch and without touching a device.  The deterministic switch
+ * (ct_set_deterministic) neither changes nor refuses these entries, as it does not ct_emd_fwd: the auction has one outcome.
+ * Not covered: n != m, a gradient for xyz2.
+ * ---------------------------------------------------------------------- */
+int ct_emd_fwd_counts(const float* xyz1, const float* xyz2, const int32_t* count, float* dist, int32_t* assignment,
+                      void* workspace, size_t workspace_bytes, int B, int n, float eps, int iters, ct_stream_t s);
+int ct_emd_bwd_counts(const float* xyz1, const float* xyz2, const int32_t* count, const float* g_dist,
+                      const int32_t* assignment, float* g_xyz1, int B, int n, ct_stream_t s);
 
 /* ------------------------------------------------------------------------
  * Pointwise (kernel size 1) convolutions of the MHCT blocks and their gradients
