@@ -536,8 +536,9 @@ static int lattice_bwd_impl(const float* xyz, const float* residual, const float
 }
 
 int ct_so3_exp_fwd(const float* log_R, float* R, int H, float eps, ct_stream_t s) {
-  if (!log_R || !R || H < 0 || !(eps > 0.0f)) return CT_EINVAL;
-  if (H == 0) return CT_OK;
+  if (H < 0 || !(eps > 0.0f)) return CT_EINVAL;
+  if (H == 0) return CT_OK;            // no heads: nothing to read or write (an empty tensor's pointer is null)
+  if (!log_R || !R) return CT_EINVAL;
   CT_CLEAR_ERROR();
   hipLaunchKernelGGL(so3_exp_fwd_kernel, dim3((H + 63) / 64), dim3(64), 0, (hipStream_t)s, log_R, R, H, eps);
   CT_CHECK_LAUNCH();
@@ -545,8 +546,9 @@ int ct_so3_exp_fwd(const float* log_R, float* R, int H, float eps, ct_stream_t s
 }
 
 int ct_so3_exp_bwd(const float* log_R, const float* g_R, float* g_log_R, int H, float eps, ct_stream_t s) {
-  if (!log_R || !g_R || !g_log_R || H < 0 || !(eps > 0.0f)) return CT_EINVAL;
+  if (H < 0 || !(eps > 0.0f)) return CT_EINVAL;
   if (H == 0) return CT_OK;
+  if (!log_R || !g_R || !g_log_R) return CT_EINVAL;
   CT_CLEAR_ERROR();
   hipLaunchKernelGGL(so3_exp_bwd_kernel, dim3((H + 63) / 64), dim3(64), 0, (hipStream_t)s, log_R, g_R, g_log_R, H, eps);
   CT_CHECK_LAUNCH();

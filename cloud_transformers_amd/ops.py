@@ -630,7 +630,10 @@ class LatticeFn(torch.autograd.Function):
 
 def lattice(xyz, residual, R, shift, scales, kscale, dim, with_stats=False):
     """(keys, tanh(keys)) of an MHCT block; R = so3_exponential_map(log_R) [H,3,3].  with_stats: also a
-    non-differentiable f32[2] = (mean, unbiased variance) of the keys, reduced inside the same launch."""
+    non-differentiable f32[2] = (mean, unbiased variance) of the keys, reduced inside the same launch.  The variance is
+    one-pass, (sum k^2 - n mean^2) / (n - 1) from float32 workgroup partials: accurate to
+    3 m 2^-24 mean(k^2) n / (n - 1) with m = dim * (points per workgroup / 256) + 20, that is relative to mean(k^2), not to the
+    variance (tests/test_lattice_cases_gpu.py: _check_stats)."""
     return LatticeFn.apply(xyz, residual, R, shift, scales, kscale, dim, with_stats)
 
 
@@ -699,7 +702,8 @@ class LatticeSo3Fn(torch.autograd.Function):
 
 def lattice_so3(xyz, residual, log_R, shift, scales, kscale, dim, eps=1e-4, with_stats=False):
     """(keys, tanh(keys)[, key statistics]) of an MHCT block from the transformer's so3 parameters log_R [H,3]
-    (layers/utils.py:25-34,53-61; eps: pytorch3d's so3_exponential_map default)."""
+    (layers/utils.py:25-34,53-61; eps: pytorch3d's so3_exponential_map default).  The reported variance is one-pass from float32
+    workgroup partials, accurate to the bound that ops.lattice states: relative to mean(k^2), not to the variance."""
     return LatticeSo3Fn.apply(xyz, residual, log_R, shift, scales, kscale, dim, eps, with_stats)
 
 

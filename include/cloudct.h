@@ -344,7 +344,8 @@ int ct_lattice_so3_bwd(const float* xyz, const float* residual, const float* log
 /* so3 exponential map of the per-head rotation parameters — the third-party call of the transformers
  * (pytorch3d.transforms.so3.so3_exponential_map, layers/utils.py:6,29,56; eps = 1e-4 there):
  *   theta = sqrt(max(|v|^2, eps));  R = I + (sin theta / theta) K + ((1 - cos theta) / theta^2) K^2,  K = hat(v)
- * log_R f32[H,3] -> R f32[H,3,3];  backward: g_R f32[H,3,3] -> g_log_R f32[H,3] (overwritten). */
+ * log_R f32[H,3] -> R f32[H,3,3];  backward: g_R f32[H,3,3] -> g_log_R f32[H,3] (overwritten).
+ * H = 0 is CT_OK with nothing read or written (the pointers may be NULL then: an empty tensor has none). */
 int ct_so3_exp_fwd(const float* log_R, float* R, int H, float eps, ct_stream_t s);
 int ct_so3_exp_bwd(const float* log_R, const float* g_R, float* g_log_R, int H, float eps, ct_stream_t s);
 
