@@ -1171,6 +1171,7 @@ CT_KERNARG_IS_ARGS_AND_GRID((splat_max_bwd_hot_kernel<false, 32, 2>), 2);      /
 CT_KERNARG_IS_ARGS_AND_GRID((splat_max_bwd_hot_kernel<true, 0, 0, kHotWideThreads>), 2);
 #include "ct_raster_band.h"
 #include "ct_raster_sorted.h"
+#include "ct_raster_bwd_fused.h"
 #include "ct_raster_sorted3d.h"
 
 // ---------------------------------------------------------------------------
@@ -1340,6 +1341,7 @@ struct Switches {
   bool det;            // ct_set_deterministic: Splat(max) backward under the lowest-index rule, ordered g_keys
   int fused_fwd;       // CLOUDCT_FUSED_FWD (-1: not set; 1: the fused Splat + Slice forward on every shape it supports)
   int fused_geom;      // CLOUDCT_FUSED_FWD_GEOM (A/B runs; 0: the default geometry, 1: whole planes, 2: chunks of eight channels)
+  int fused_bwd;       // CLOUDCT_FUSED_BWD (-1: not set; 1: the fused Slice + Splat(max) backward on every shape it supports)
   bool has(unsigned f) const { return (flags & f) != 0; }
   bool hot() const { return !has(CT_DEBUG_NO_HOT); }
 };
@@ -1350,9 +1352,10 @@ Switches read_switches() {
   };
   static const int sorted = env("CLOUDCT_SORTED", -1), wide = env("CLOUDCT_WIDE", 1), nseg = env("CLOUDCT_SPLAT_BWD_NSEG", 0);
   static const int fused_fwd = env("CLOUDCT_FUSED_FWD", -1), fused_geom = env("CLOUDCT_FUSED_FWD_GEOM", 0);
+  static const int fused_bwd = env("CLOUDCT_FUSED_BWD", -1);
   const int dbg = t_dbg_nseg.load(std::memory_order_relaxed);
   return {t_dbg_flags.load(std::memory_order_relaxed), dbg ? dbg : nseg, sorted, wide != 0,
-          det_now(), fused_fwd, fused_geom};
+          det_now(), fused_fwd, fused_geom, fused_bwd};
 }
 
 // ---------------------------------------------------------------------------
@@ -2763,6 +2766,60 @@ int run_splat_slice_fwd(const FusedFwdPlan& p, RasterArgs a, const int* W, hipSt
   return CT_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Slice backward + Splat(max) backward in one launch (ct_raster_bwd_fused.h): which shapes take it.  Pure arithmetic on the shape,
+// the switches and the low bits of the pointers involved: ct_slice_splat_bwd_supported answers from it (no pointers: zero bits) and
+// ct_slice_splat_bwd launches from it.
+//   Legal: what the sorted Slice backward takes as ONE workgroup per plane (sorted_plane_ok's layout conditions), a grid of at most
+//   kSortThreads cells (a thread converts one accumulator word in place), C <= 256 (the tied groups' mask), reduce = max, outside the
+//   deterministic mode (whose lowest-index tie rule the claims do not implement).
+//   Taken without flags only where it was measured and won (kFusedBwdMeasuredWin, profiles/fused_bwd_ab.txt): the headline's class
+//   of shapes.  CT_DEBUG_FORCE_HOT (tests) and CLOUDCT_FUSED_BWD=1 take it wherever it is legal; CT_DEBUG_NO_HOT and
+//   CT_DEBUG_NO_SORTED keep it off.
+// ---------------------------------------------------------------------------
+constexpr const char* kFusedBwdTag = "slice_splat_bwd_fused";
+constexpr bool kFusedBwdMeasuredWin = true;
+// a padding mask is NOT served: the HAS_PAD instance spills in its group loop (37 registers, 152 bytes of scratch per lane:
+// profiles/fused_bwd_ab.txt) — the query answers 0 for it and the kernel is not instantiated with one
+constexpr bool kFusedBwdServesPad = false;
+struct FusedBwdPlan {
+  bool ok;
+  size_t lds;
+};
+
+FusedBwdPlan fused_bwd_plan(const Switches sw, int B, int H, int C, int N, int dim, const int* W, int reduce, int pad_dtype,
+                            uintptr_t ptr_bits) {
+  FusedBwdPlan p = {};
+  if (!valid_common(B, H, C, N, dim, W) || dim != 2 || reduce != CT_REDUCE_MAX0 || !sw.hot() || sw.det) return p;
+  if (sw.has(CT_DEBUG_NO_SORTED) || sw.fused_bwd == 0) return p;
+  if (pad_dtype != CT_PAD_NONE && !kFusedBwdServesPad) return p;
+  const long long G = (long long)W[0] * W[1];
+  if (N > 4096 || (N & 3) != 0 || (C & 3) != 0 || C > 256 || (G & 3) != 0 || G > kSortThreads || (ptr_bits & 15) != 0) return p;
+  if (N / 4 + (3 * (int)G) / 4 > kMaxItems) return p;
+  p.lds = sort_lds((int)G, N, C).total;
+  if (p.lds > (size_t)kBigLdsBytes) return p;
+  const bool measured = kFusedBwdMeasuredWin && (long long)B * H >= 512 && W[0] == 32 && W[1] == 32 && C == 16 && N == 4096 &&
+                        pad_dtype == CT_PAD_NONE;
+  p.ok = measured || sw.has(CT_DEBUG_FORCE_HOT) || sw.fused_bwd == 1;
+  return p;
+}
+
+int run_slice_splat_bwd(const FusedBwdPlan& p, RasterArgs a, const int* W, hipStream_t st) {
+  const GridW<2> g = make_grid<2>(W);
+  a.CC = 4; a.nchunks = a.C >> 2;
+  a.ncg = 1; a.nseg = 1; a.Nrow = 0;
+  const dim3 wgrid(1, a.H, a.B);
+  if (a.pad_dtype == CT_PAD_NONE && W[0] == 32 && W[1] == 32 && a.N == 4096 && a.C == 16) {
+    CT_LAUNCH((slice_splat_bwd_kernel<false, 32, 4096, 16>), wgrid, kSortThreads, p.lds, st, a, g);
+  } else if (W[0] == 32 && W[1] == 32) {
+    CT_LAUNCH((slice_splat_bwd_kernel<false, 32>), wgrid, kSortThreads, p.lds, st, a, g);
+  } else {
+    CT_LAUNCH((slice_splat_bwd_kernel<false, 0>), wgrid, kSortThreads, p.lds, st, a, g);
+  }
+  note(kFusedBwdTag);
+  return CT_OK;
+}
+
 template <bool FROM_KEYS>
 int splat_fwd_impl(PosSrc pos, const float* feat, const void* pad, int pad_dtype, float* grid,
                    int B, int H, int C, int N, int dim, const int* W, int reduce, hipStream_t st) {
@@ -3048,6 +3105,28 @@ int ct_splat_slice_fwd(const float* keys, const float* feat, const void* pad, in
   a.pos = {keys, nullptr, nullptr};
   a.src = feat; a.tile_out = grid; a.dst = out;
   return run_splat_slice_fwd(p, a, W, (hipStream_t)s);
+}
+
+int ct_slice_splat_bwd_supported(int B, int H, int C, int N, int dim, const int* W, int reduce, int pad_dtype) {
+  return fused_bwd_plan(read_switches(), B, H, C, N, dim, W, reduce, pad_dtype, 0).ok ? 1 : 0;
+}
+
+int ct_slice_splat_bwd(const float* keys, const float* feat, const void* pad, int pad_dtype, const float* grid, const float* g_out,
+                       float* g_grid, float* g_feat, float* g_keys_slice, float* g_keys,
+                       int B, int H, int C, int N, int dim, const int* W, int reduce, ct_stream_t s) {
+  if (!keys || !feat || !grid || !g_out || !g_grid || !g_feat || !g_keys || !valid_pad(pad, pad_dtype)) return CT_EINVAL;
+  if (g_keys == keys || g_keys == feat || g_keys == grid || g_keys == g_out || g_keys == g_keys_slice) return CT_EINVAL;
+  const Switches sw = read_switches();
+  const uintptr_t bits = (uintptr_t)keys | (uintptr_t)feat | (uintptr_t)grid | (uintptr_t)g_out | (uintptr_t)g_grid |
+                         (uintptr_t)g_feat | (uintptr_t)g_keys_slice | (uintptr_t)g_keys;
+  const FusedBwdPlan p = fused_bwd_plan(sw, B, H, C, N, dim, W, reduce, pad_dtype, bits);
+  if (!p.ok) return CT_EINVAL;
+  note_reset();
+  RasterArgs a = base_args(B, H, C, N, pad, pad_dtype);
+  a.pos = {keys, nullptr, nullptr};
+  a.src = g_out; a.tile_in = grid; a.tile_in2 = feat;      // (tile_in2 carries the point-sized features here: ct_raster_bwd_fused.h)
+  a.tile_out = g_grid; a.dst = g_feat; a.g_pos = g_keys; a.fold_gpos = g_keys_slice;
+  return run_slice_splat_bwd(p, a, W, (hipStream_t)s);
 }
 
 int ct_slice_bwd(const float* keys, const float* grid, const void* pad, int pad_dtype, const float* g_out,

@@ -64,6 +64,11 @@ class SplatSliceStep:
         self.fused_fwd = (os.environ.get("CLOUDCT_FUSED_FWD", "") != "0" and
                           bool(self.lib.ct_splat_slice_fwd_supported(self.B, self.H, self.C, self.N, dim, self.Wa, self.red, 0)))
         self._forward_tag = None
+        # the backward in one launch (ct_slice_splat_bwd) on the same terms; CLOUDCT_FUSED_BWD=0 keeps the two calls.  A plane-sort
+        # record is an input of the two calls only: a step that carries one keeps them.
+        self.fused_bwd = (os.environ.get("CLOUDCT_FUSED_BWD", "") != "0" and self.sorted is None and
+                          bool(self.lib.ct_slice_splat_bwd_supported(self.B, self.H, self.C, self.N, dim, self.Wa, self.red, 0)))
+        self._backward_tag = None
         if tickets and reduce == "max" and self.lib.ct_splat_bwd_tk_segments(self.B, self.H, self.C, self.N, dim, self.Wa) > 1:
             self.g_keys_out = torch.empty_like(self.keys)    # ... or into a second tensor where point segments pay (ct_splat_bwd_tk)
 
@@ -114,6 +119,16 @@ class SplatSliceStep:
                                             _stream()),
                    "ct_splat_bwd_tk")
 
+    def slice_splat_bwd(self):
+        """g_z, g_feat and the summed g_keys in one launch: the bits of slice_bwd() followed by splat_bwd() (only where
+        self.fused_bwd); Slice's key cotangent alone still lands in g_keys_buf where g_keys_out is a tensor of its own"""
+        own = self.g_keys_out is not self.g_keys_buf
+        _lib.check(self.lib.ct_slice_splat_bwd(_ptr(self.keys), _ptr(self.feat), None, 0, _ptr(self.z), _ptr(self.cot),
+                                               _ptr(self.g_z), _ptr(self.g_feat), _ptr(self.g_keys_buf) if own else None,
+                                               _ptr(self.g_keys_out), self.B, self.H, self.C, self.N, self.dim, self.Wa,
+                                               self.red, _stream()),
+                   "ct_slice_splat_bwd")
+
     # one entry per ABI call
     PASSES = ("splat_fwd", "slice_fwd", "slice_bwd", "splat_bwd")
 
@@ -132,6 +147,7 @@ class SplatSliceStep:
         "slice_bwd_presorted": "slice_bwd_sorted_kernel<false, 32, true, true",
         "splat_max_bwd_hot": "splat_max_bwd_hot_kernel",
         "splat_max_bwd_whole_head": "quad_kernel<2, 2, 4, 1024,",
+        "slice_splat_bwd_fused": "slice_splat_bwd_kernel",
     }
 
     # the four kernels of the headline workload (B8 N4096 H64 C16 32^2 max) by their FULL instantiated names, as rocprofv3 prints
@@ -156,8 +172,7 @@ class SplatSliceStep:
         self.lib.ct_set_deterministic(1 if self.deterministic else 0)      # the mode the workspaces were planned under
         self.plane_sort()
         self.forward()
-        self.slice_bwd()
-        self.splat_bwd()
+        self.backward()
 
     def forward(self):
         """z and out: one launch where the fused forward takes the shape, else the two calls"""
@@ -174,6 +189,21 @@ class SplatSliceStep:
         """kernel-family tags of what run()'s forward launches (recorded at the first run(); None before it).  With the fused
         forward the per-pass timings of `PASSES` remain those of the separate kernels and no longer add up to the step."""
         return self._forward_tag
+
+    def backward(self):
+        """g_z, g_feat, g_keys: one launch where the fused backward takes the shape, else the two calls"""
+        record = self._backward_tag is None
+        tags = []
+        for call in ((self.slice_splat_bwd,) if self.fused_bwd else (self.slice_bwd, self.splat_bwd)):
+            call()
+            if record:
+                tags.append(self.lib.ct_debug_last_launch().decode())
+        if record:
+            self._backward_tag = "+".join(tags)
+
+    def backward_tag(self):
+        """kernel-family tags of what run()'s backward launches (recorded at the first run(); None before it)"""
+        return self._backward_tag
 
     def g_keys(self):
         """d(out . cot)/d(keys) after run(): Slice's and Splat's key cotangents, already summed"""

@@ -211,6 +211,27 @@ int ct_splat_slice_fwd_supported(int B, int H, int C, int N, int dim, const int*
 int ct_splat_slice_fwd(const float* keys, const float* feat, const void* pad, int pad_dtype,
                        float* grid, float* out, int B, int H, int C, int N, int dim, const int* W,
                        int reduce, ct_stream_t s);
+/* Slice backward and Splat(max) backward on the same keys in ONE launch (csrc/ct_raster_bwd_fused.h): what
+ *   ct_slice_bwd_tk(keys, grid, g_out) -> g_grid, g_keys_slice   followed by
+ *   ct_splat_bwd_tk(keys, feat, grid, g_grid, add = g_keys_slice) -> g_feat, g_keys
+ * write, with their bits: g_grid is stored once and not read back, grid and the keys are read once, and Slice's key cotangent
+ * never leaves the workgroup (g_keys_slice may be NULL; given, it receives that cotangent alone).  For callers that chain the two
+ * ops directly (SplatSliceStep).
+ * ct_slice_splat_bwd_supported: 1 where the call takes the shape under the current switches, else 0.  Legal are dim == 2, reduce ==
+ * CT_REDUCE_MAX0, N % 4 == 0, N <= 4096, C % 4 == 0, C <= 256, a grid of G % 4 == 0 and G <= 1024 cells, one workgroup per plane
+ * within the sorted kernels' LDS budget, NO padding mask (pad_dtype != CT_PAD_NONE: 0 — that instance of the kernel spills in its
+ * loop and is not built), outside the deterministic mode (ct_set_deterministic(1): 0); of these it answers 1 where the kernel was measured against the two calls and won, wherever it is legal
+ * under CT_DEBUG_FORCE_HOT or CLOUDCT_FUSED_BWD=1 (read once per process), and nowhere under CT_DEBUG_NO_HOT, CT_DEBUG_NO_SORTED or
+ * CLOUDCT_FUSED_BWD=0.
+ * ct_slice_splat_bwd: CT_EINVAL, before anything is launched or written, where the query answers 0, for a null or not 16-byte
+ * aligned pointer (g_keys_slice excepted: NULL is legal) and for g_keys aliasing an input or g_keys_slice; no host
+ * synchronisation, no state left behind (graph-safe); the launch tag is "slice_splat_bwd_fused".  Added under CT_ABI_VERSION 3
+ * (additive symbols). */
+int ct_slice_splat_bwd_supported(int B, int H, int C, int N, int dim, const int* W, int reduce, int pad_dtype);
+int ct_slice_splat_bwd(const float* keys, const float* feat, const void* pad, int pad_dtype,
+                       const float* grid, const float* g_out,
+                       float* g_grid, float* g_feat, float* g_keys_slice /* may be NULL */, float* g_keys,
+                       int B, int H, int C, int N, int dim, const int* W, int reduce, ct_stream_t s);
 /* ct_slice_bwd with scratch: with few (b,h) planes (the zoo's H = 16 blocks) the channel chunks of a plane are dealt to
  * several workgroups, whose partial g_keys go through `workspace` (ct_slice_bwd_workspace_bytes(...) bytes, may be 0).
  * Same results as ct_slice_bwd, which has to keep one workgroup per plane there. */

@@ -8,6 +8,7 @@ namespace ctdev {
 #include "ct_raster_hot.h"
 #include "ct_raster_hot3d.h"
 #include "ct_raster_sorted.h"
+#include "ct_raster_bwd_fused.h"
 #include "ct_raster_sorted3d.h"
 }
 #ifndef CT_ONE_ARGS
