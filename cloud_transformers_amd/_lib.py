@@ -97,6 +97,7 @@ DEBUG_FORCE_SORTED = 32
 DEBUG_FORCE_SORTED_SEG = 64
 DEBUG_NO_WIDE = 128
 NBR_K_MAX = 16384          # ct_nbr_radius: keys a query keeps in LDS
+NBR_KNN_K_MAX = 64         # ct_nbr_knn: one list slot per lane of the query's wavefront
 NBR_MAX_CELLS = 1 << 26    # ct_nbr_* grids
 KP_PLAN_CLOUDS_MAX = 65535 # ct_kp_plan: clouds of one index table
 COMPLETION_N_MAX = 16384   # ct_completion_items: rows of one partial cloud
@@ -363,6 +364,9 @@ SIGNATURES = {
     "ct_nbr_table_bytes": (_sz, [_i]),
     "ct_nbr_table_set": (_i, [_vp, _i, _i, _vp, _vp, _fp, _f, _ip, ctypes.c_int64, ctypes.c_int64]),
     "ct_nbr_radius_multi": (_i, [_vp, _i, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp]),
+    "ct_nbr_knn": (_i, [_vp, _vp, _fp, _f, _ip, _vp, ctypes.c_int64, _i, _vp, _vp, _vp]),
+    "ct_nbr_knn_multi": (_i, [_vp, _i, _vp, _vp, ctypes.c_int64, _i, _vp, _vp, _vp]),
+    "ct_nbr_interp": (_i, [_vp, _vp, ctypes.c_int64, _i, _vp, ctypes.c_int64, _i, _f, _vp, _vp]),
     "ct_kp_plan_workspace_bytes": (_sz, [_i, ctypes.c_int64]),
     "ct_kp_plan": (_i, [_vp, _i, ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_double, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ct_kp_items": (_i, [_vp] * 10 + [ctypes.c_int64, _fp, _fp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -12,6 +12,7 @@
 // float32 test decides membership, never the cell geometry.  Points outside the grid box are counted in the nearest
 // edge cell; both queries treat the edge cells as reaching to infinity and stay exact for them.
 #include "ct_nbr_query.h"
+#include "ct_nbr_knn.h"
 
 namespace {
 
@@ -259,6 +260,49 @@ int ct_nbr_nearest(const int32_t* cell_start, const float* sorted, const float* 
   CT_CLEAR_ERROR();
   hipLaunchKernelGGL(nbr_nearest_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, (const float4*)sorted, cell_start,
                      make_grid(origin, h, dims), queries, (long long)Q, idx, d2);
+  CT_CHECK_LAUNCH();
+  return CT_OK;
+}
+
+int ct_nbr_knn(const int32_t* cell_start, const float* sorted, const float* origin, float h, const int* dims,
+               const float* queries, int64_t Q, int K, int64_t* idx, float* d2, ct_stream_t s) {
+  long long ncells = 0;
+  if (!cell_start || !sorted || !aligned16(sorted) || !queries || !idx || !d2 || Q < 1 || Q > kNearestMaxQ || K < 1 ||
+      K > kKnnKMax || !grid_ok(origin, h, dims, &ncells))
+    return CT_EINVAL;
+  hipStream_t st = (hipStream_t)s;
+  CT_CLEAR_ERROR();
+  const NbrDirectSource src{(const float4*)sorted, cell_start, make_grid(origin, h, dims), queries};
+  hipLaunchKernelGGL(nbr_knn_kernel<NbrDirectSource>, dim3((unsigned)((Q + kKnnWaves - 1) / kKnnWaves)), dim3(kKnnThreads), 0, st,
+                     src, (long long)Q, K, idx, d2);
+  CT_CHECK_LAUNCH();
+  return CT_OK;
+}
+
+int ct_nbr_knn_multi(const void* table, int n_clouds, const int64_t* cloud, const float* queries, int64_t Q, int K,
+                     int64_t* idx, float* d2, ct_stream_t s) {
+  if (!table || ((uintptr_t)table & 7) != 0 || n_clouds < 1 || !cloud || !queries || !idx || !d2 || Q < 1 || Q > kNearestMaxQ ||
+      K < 1 || K > kKnnKMax)
+    return CT_EINVAL;
+  hipStream_t st = (hipStream_t)s;
+  CT_CLEAR_ERROR();
+  const NbrTableSource src{(const NbrRecord*)table, n_clouds, cloud, queries};
+  hipLaunchKernelGGL(nbr_knn_kernel<NbrTableSource>, dim3((unsigned)((Q + kKnnWaves - 1) / kKnnWaves)), dim3(kKnnThreads), 0, st,
+                     src, (long long)Q, K, idx, d2);
+  CT_CHECK_LAUNCH();
+  return CT_OK;
+}
+
+int ct_nbr_interp(const int64_t* idx, const float* d2, int64_t Q, int K, const float* values, int64_t M, int C, float eps,
+                  float* out, ct_stream_t s) {
+  if (!idx || !d2 || !values || !out || Q < 1 || Q > kNearestMaxQ || K < 1 || K > kKnnKMax || M < 1 || C < 1 || !(eps >= 0.0f))
+    return CT_EINVAL;
+  hipStream_t st = (hipStream_t)s;
+  CT_CLEAR_ERROR();
+  const long long items = (long long)Q * ((C + kInterpCols - 1) / kInterpCols);
+  const long long blocks = (items + 255) / 256;
+  hipLaunchKernelGGL(nbr_interp_kernel, dim3((unsigned)(blocks < kInterpMaxBlocks ? blocks : kInterpMaxBlocks)), dim3(256), 0, st,
+                     idx, d2, (long long)Q, K, values, C, eps, out);
   CT_CHECK_LAUNCH();
   return CT_OK;
 }

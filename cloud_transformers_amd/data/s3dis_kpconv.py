@@ -483,12 +483,33 @@ class VoteEvaluator:
             self._proj = proj
         return self._proj
 
-    def full_ious(self):
-        """s3dis_metrics: IoUs at full resolution, every raw point taking the vote of its nearest subsampled point."""
+    def full_ious(self, k=1):
+        """s3dis_metrics: IoUs at full resolution, every raw point taking the vote of its nearest subsampled point (k = 1,
+        the reference's projection and the default).  With k > 1 every raw point takes the argmax of the inverse-distance
+        interpolation of the vote logits over its k nearest subsampled points (GridIndex.interpolate) instead."""
+        k = int(k)
+        if k != 1:
+            return self._full_ious_knn(k)
         logits = self.vote_logits()
         conf = torch.zeros(self.C, self.C, dtype=torch.int64, device=self.device)
         for a, off, proj in zip(self.areas, self.offsets.tolist(), self.projections()):
             pred = torch.argmax(logits[:, off + proj], dim=0)
+            truth = torch.from_numpy(np.asarray(a.labels).astype(np.int64)).to(self.device)
+            conf += _confusion(truth, pred, self.C)
+        iou = iou_from_confusions(conf)
+        return iou.cpu().numpy(), float(iou.mean())
+
+    def _full_ious_knn(self, k):
+        from .. import _lib
+        from ..neighbors import GridIndex
+        if not 1 <= k <= _lib.NBR_KNN_K_MAX:
+            raise ValueError("full_ious: k must be in [1, %d]" % _lib.NBR_KNN_K_MAX)
+        logits = self.vote_logits()
+        conf = torch.zeros(self.C, self.C, dtype=torch.int64, device=self.device)
+        for a, off, size in zip(self.areas, self.offsets.tolist(), self.sizes):
+            index = GridIndex(torch.from_numpy(np.ascontiguousarray(a.sub_points, np.float32)).to(self.device))
+            raw = torch.from_numpy(np.ascontiguousarray(a.points, np.float32)).to(self.device)
+            pred = torch.argmax(index.interpolate(logits[:, off:off + size].t().contiguous(), raw, k), dim=1)
             truth = torch.from_numpy(np.asarray(a.labels).astype(np.int64)).to(self.device)
             conf += _confusion(truth, pred, self.C)
         iou = iou_from_confusions(conf)

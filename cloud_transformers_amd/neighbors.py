@@ -14,7 +14,28 @@ from .ops import _dev, _on, _stream
 
 # default cell: aim at ~6 points per occupied cell (4-8 is the target band)
 _TARGET_PER_CELL = 6.0
-NEAREST_CHUNK = 1 << 24      # queries per ct_nbr_nearest launch
+NEAREST_CHUNK = 1 << 24      # queries per ct_nbr_nearest / ct_nbr_knn launch
+
+
+def _knn_k(k):
+    k = int(k)
+    if not 1 <= k <= _lib.NBR_KNN_K_MAX:
+        raise ValueError("query_knn: k must be in [1, %d]" % _lib.NBR_KNN_K_MAX)
+    return k
+
+
+def _knn_tensor(x, device, name, dtype, what, ok):
+    """The k-nearest methods' argument check: ValueError for a wrong dtype or shape, then for a tensor that is not on `device`
+    (a CPU tensor included)."""
+    if not torch.is_tensor(x) or x.dtype != dtype or not ok(x):
+        raise ValueError("%s must be %s" % (name, what))
+    if not x.is_cuda or x.device != device:
+        raise ValueError("%s must be on %s; there is no CPU fallback" % (name, device))
+    return x.contiguous()
+
+
+def _knn_queries(x, device):
+    return _knn_tensor(x, device, "queries", torch.float32, "float32 [Q, 3]", lambda t: t.dim() == 2 and t.shape[1] == 3)
 
 
 def _dims_for(lo, hi, h):
@@ -135,6 +156,56 @@ class GridIndex:
                                               q[a:].data_ptr(), n, idx[a:].data_ptr(), d2[a:].data_ptr(), st), "ct_nbr_nearest")
         return idx, d2
 
+    def query_knn(self, queries, k):
+        """KDTree.query(queries, k), 1 <= k <= 64: (idx i64[Q,k], d2 f32[Q,k]), the k nearest points by (d2, index)
+        ascending (the order of `query_radius`, the tie rule of `nearest`); a cloud of fewer than k points leaves -1 / +inf
+        in the tail, and so does a query with a non-finite coordinate in every slot.  Any query position is exact; one
+        wavefront per query, launched in chunks of NEAREST_CHUNK queries (no workspace).  For finite queries k = 1 gives `nearest`'s bits."""
+        k = _knn_k(k)
+        q = _knn_queries(queries, self.device)
+        Q = q.shape[0]
+        dev = self.device
+        idx = torch.empty(Q, k, dtype=torch.int64, device=dev)
+        d2 = torch.empty(Q, k, dtype=torch.float32, device=dev)
+        lib = _lib.load()
+        with _on(dev):
+            st = _stream(dev)
+            for a in range(0, Q, NEAREST_CHUNK):
+                n = min(NEAREST_CHUNK, Q - a)
+                _lib.check(lib.ct_nbr_knn(self.cell_start.data_ptr(), self.sorted.data_ptr(), self._origin_c, self.h, self._dims_c,
+                                          q[a:].data_ptr(), n, k, idx[a:].data_ptr(), d2[a:].data_ptr(), st), "ct_nbr_knn")
+        return idx, d2
+
+    def interpolate(self, values, queries, k=3, eps=1e-8):
+        """Inverse-distance interpolation of `values` f32[M,C] (one row per indexed point) at `queries`: f32[Q,C], the mean of
+        each query's k nearest rows weighted by 1 / (d2 + eps).  `query_knn` followed by ct_nbr_interp, in float32 in the
+        order include/cloudct.h states; the gathered rows [Q,k,C] are never formed.  A query with a non-finite
+        coordinate has no neighbour and gets NaN."""
+        k = _knn_k(k)
+        eps = float(eps)
+        if not eps >= 0:
+            raise ValueError("interpolate: eps must be >= 0")
+        values = _knn_tensor(values, self.device, "values", torch.float32, "float32 [%d, C] with C >= 1" % self.M,
+                             lambda t: t.dim() == 2 and t.shape[0] == self.M and t.shape[1] >= 1)
+        idx, d2 = self.query_knn(queries, k)
+        return _interp(idx, d2, values, eps)
+
+
+def _interp(idx, d2, values, eps):
+    """ct_nbr_interp over a finished table, in chunks of NEAREST_CHUNK queries."""
+    Q, k = idx.shape
+    M, C = values.shape
+    dev = values.device
+    out = torch.empty(Q, C, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    with _on(dev):
+        st = _stream(dev)
+        for a in range(0, Q, NEAREST_CHUNK):
+            n = min(NEAREST_CHUNK, Q - a)
+            _lib.check(lib.ct_nbr_interp(idx[a:].data_ptr(), d2[a:].data_ptr(), n, k, values.data_ptr(), M, C, eps,
+                                         out[a:].data_ptr(), st), "ct_nbr_interp")
+    return out
+
 
 class GridIndexTable:
     """The grids of several `GridIndex`es in one device-resident table (include/cloudct.h `ct_nbr_table_*`), so that a query
@@ -189,3 +260,22 @@ class GridIndexTable:
                                                        k, idx.data_ptr(), d2.data_ptr(), count.data_ptr(), _stream(dev)),
                        "ct_nbr_radius_multi")
         return idx, d2, count
+
+    def query_knn(self, cloud, queries, k):
+        """`GridIndex.query_knn` of query q in cloud[q] (i64[Q], on the device; ids outside the table are clamped into it):
+        the same (idx i64[Q,k], d2 f32[Q,k]), idx counting inside the query's own cloud."""
+        k = _knn_k(k)
+        q = _knn_queries(queries, self.device)
+        cloud = _knn_tensor(cloud, self.device, "cloud", torch.int64, "int64 [Q]", lambda t: t.dim() == 1 and t.shape[0] == q.shape[0])
+        Q = q.shape[0]
+        dev = self.device
+        idx = torch.empty(Q, k, dtype=torch.int64, device=dev)
+        d2 = torch.empty(Q, k, dtype=torch.float32, device=dev)
+        lib = _lib.load()
+        with _on(dev):
+            st = _stream(dev)
+            for a in range(0, Q, NEAREST_CHUNK):
+                n = min(NEAREST_CHUNK, Q - a)
+                _lib.check(lib.ct_nbr_knn_multi(self.table.data_ptr(), self.n_clouds, cloud[a:].data_ptr(), q[a:].data_ptr(), n, k,
+                                                idx[a:].data_ptr(), d2[a:].data_ptr(), st), "ct_nbr_knn_multi")
+        return idx, d2

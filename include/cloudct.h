@@ -50,7 +50,8 @@ extern "C" {
  * ct_chamfer_metrics; then the backward of the eval-mode norm, ct_bn_eval_group_bwd; then the precision mode of the pointwise
  * GEMMs ct_set_pw_precision / ct_get_pw_precision / ct_pw_precision_override; then that of the grouped convolutions,
  * ct_set_gconv_precision / ct_get_gconv_precision / ct_gconv_precision_override / ct_gconv_precision_covers; then the EMD auction for any cloud size and per-cloud counts,
- * ct_emd_fwd_counts / ct_emd_bwd_counts.) */
+ * ct_emd_fwd_counts / ct_emd_bwd_counts; then the k-nearest query and its interpolation, ct_nbr_knn / ct_nbr_knn_multi /
+ * ct_nbr_interp.) */
 #define CT_ABI_VERSION 3
 
 /* status codes */
@@ -994,6 +995,47 @@ int ct_nbr_table_set(void* host_table, int n_clouds, int i, const int32_t* cell_
                      float h, const int* dims, int64_t M, int64_t offset);
 int ct_nbr_radius_multi(const void* table, int n_clouds, const int64_t* cloud, const float* centres, int Q, float r, int K,
                         int64_t* idx, float* d2, int64_t* count, ct_stream_t s);
+
+/* ------------------------------------------------------------------------
+ * The exact k-nearest query (KDTree.query(X, k), 1 <= k <= CT_NBR_KNN_K_MAX) over the same index,
+ * and inverse-distance interpolation over its result.  Added under CT_ABI_VERSION 3 (additive, as
+ * ct_nbr_table_*).
+ *
+ * ct_nbr_knn: for each of Q queries f32[Q,3], idx i64[Q,K] / d2 f32[Q,K] = the K nearest points
+ * by (d2, index) ascending: d2 ascends, and among equal d2 the lower index goes first (the order
+ * of ct_nbr_radius, the tie rule of ct_nbr_nearest).  A cloud of fewer than K points fills the tail
+ * with -1 / +inf.  Queries may lie anywhere, the outside of the grid's box included; the result is
+ * exact, and for every query with finite coordinates K = 1 gives ct_nbr_nearest's idx and d2 bit
+ * for bit (at a +-inf coordinate ct_nbr_nearest keeps the lowest index it visits, with d2 = +inf).
+ * One wavefront per query: the
+ * shells of cells of ct_nbr_nearest, each run of cells read 64 records at a time, the K best kept
+ * in the wave's registers; the walk stops once the K-th d2 is below the squared gap to the nearest
+ * unvisited cell (less ct_nbr_nearest's slack) or no unvisited cell remains, so it is bounded by
+ * the grid's dimensions for every input.  A query with a non-finite coordinate ends through the
+ * second condition and gets -1 / +inf in every slot.  One launch per call, 1 <= Q < 2^31 (larger
+ * sets go in several calls), no workspace, no allocation.
+ * ct_nbr_knn_multi: ct_nbr_knn with the grid of query q taken from record cloud[q] of a
+ * ct_nbr_table_* table (cloud i64[Q], device; clamped into [0, n_clouds - 1] as a guard), as
+ * ct_nbr_radius_multi relates to ct_nbr_radius.  idx counts inside the query's own cloud.
+ * ct_nbr_interp: from such a table idx i64[Q,K] / d2 f32[Q,K] and values f32[M,C], out f32[Q,C] in
+ * fp32 with true divisions and no contraction, in this order (numpy float32 gives the same bits):
+ *   w_j = 1.0f / (d2_j + eps) for the slots with idx_j >= 0 (the others are skipped throughout);
+ *   s = ((w_0 + w_1) + ...) in slot order;
+ *   out[c] = ((w_0 / s) * values[idx_0][c] + (w_1 / s) * values[idx_1][c]) + ... in slot order.
+ * values[idx] (Q * K * C elements) is never formed.  A row without a slot to use is NaN.  An idx
+ * value at or above M is the caller's error: there is no device check.
+ *
+ * CT_EINVAL before any launch: a null pointer, K outside [1, 64], Q < 1 or Q >= 2^31, a grid
+ * outside the bounds of ct_nbr_index_build, `sorted` not 16-byte aligned, a table not 8-byte
+ * aligned or n_clouds < 1; for ct_nbr_interp C < 1, M < 1, or eps negative or NaN.
+ * ---------------------------------------------------------------------- */
+#define CT_NBR_KNN_K_MAX 64
+int ct_nbr_knn(const int32_t* cell_start, const float* sorted, const float* origin, float h, const int* dims,
+               const float* queries, int64_t Q, int K, int64_t* idx, float* d2, ct_stream_t s);
+int ct_nbr_knn_multi(const void* table, int n_clouds, const int64_t* cloud, const float* queries, int64_t Q, int K,
+                     int64_t* idx, float* d2, ct_stream_t s);
+int ct_nbr_interp(const int64_t* idx, const float* d2, int64_t Q, int K, const float* values, int64_t M, int C,
+                  float eps, float* out, ct_stream_t s);
 
 /* ------------------------------------------------------------------------
  * The epoch plan of the S3DIS KPConv sampler (datasets/s3dis_closer.py:247-276): n picks by the
