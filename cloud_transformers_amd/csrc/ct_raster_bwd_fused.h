@@ -12,8 +12,17 @@
 // It serves callers that run ct_slice_bwd_tk and ct_splat_bwd_tk(add = Slice's key cotangent) on one key tensor with nothing in
 // between (SplatSliceStep.run()).  The arithmetic of either half is the stand-alone kernel's, in its order: the bits of
 // slice_bwd_sorted_kernel and splat_max_bwd_hot_kernel with one workgroup per plane (tests/test_slice_splat_bwd_fused_gpu.py).
-// Measured on the headline step (profiles/fused_bwd_ab.txt).  Not served: padding masks (that instance spills in
-// its group loop), the deterministic mode, a plane-sort record as input, N > 4096, grids of more than 1024 cells, 3D, reduce=sum.
+// What the group loop does NOT do (profiles/fused_bwd_loop_ab.txt): recompute a point's corner set-up from the keys — the base
+// cells are parked behind the sort (16 bits each, over the dead first-item marks), (w1x, w1y) are the entry's weights in LDS,
+// w0 = 1 - w1, the clamp mask of the g_keys store is the rank's flags: the keys are read once per plane (the rare tied-group
+// redo reads them again); touch scratch or wait for vector memory on its behalf — the five streams (g_out, feat, z cells in,
+// g_z, g_feat out) go through wave-uniform buffer descriptors with a scalar row offset and one shared 32-bit lane offset, so the
+// only vmcnt waits in the loop are the staging of g_out / z cells and the first use of feat in the Splat body (the headline
+// instance: no scratch at all).  Measured and not kept: matches and non-zero cells counted per wave by ballot and popcount
+// instead of per lane — fewer vector instructions, a slower step.
+// Measured on the headline step (profiles/fused_bwd_ab.txt, fused_bwd_loop_ab.txt).  Not served: padding masks
+// (that instance is not built), the deterministic mode, a plane-sort record as input, N > 4096, grids of more than 1024 cells,
+// 3D, reduce=sum.
 // Ties: per four-channel group, non-zero cells against matches; a tied group is redone behind the loop with single-winner claims
 // (first come between threads, the lower index inside a thread's quad: as the stand-alone kernel's group redo).  The stand-alone
 // kernel's repair of a single tie by value (lowest point index) is not built in: a chance tie costs one group's redo here.
@@ -36,6 +45,33 @@
 //   workgroup stored, splat_bwd_quad<.., CLAIMS, DELTA>); then the key cotangents.
 //   grid = (1, H, B)
 // ---------------------------------------------------------------------------
+// A stream of the plane behind a buffer descriptor: raw buffer, 32-bit byte offsets (a scalar row + the lane's), range-checked
+// against the plane's bytes.  Built from wave-uniform values only.
+typedef unsigned ct_u4 __attribute__((ext_vector_type(4)));
+struct StreamBuf {
+  __amdgpu_buffer_rsrc_t r;
+};
+constexpr int kBufNt = 2;      // the non-temporal bit of a buffer access (the `nt` of ld_stream4 / st_stream4)
+__device__ __forceinline__ StreamBuf stream_buf(const float* base, unsigned bytes) {
+  StreamBuf b;
+  b.r = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
+  return b;
+}
+__device__ __forceinline__ float4 buf_ld_stream4(const StreamBuf& b, unsigned voff, unsigned soff) {
+  const ct_u4 v = __builtin_amdgcn_raw_buffer_load_b128(b.r, (int)voff, (int)soff, kBufNt);
+  return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+}
+__device__ __forceinline__ float buf_ld_stream(const StreamBuf& b, unsigned voff, unsigned soff) {
+  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(b.r, (int)voff, (int)soff, kBufNt));
+}
+__device__ __forceinline__ void buf_st_stream4(const StreamBuf& b, unsigned voff, unsigned soff, float4 v) {
+  const ct_u4 t = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
+  __builtin_amdgcn_raw_buffer_store_b128(t, b.r, (int)voff, (int)soff, kBufNt);
+}
+__device__ __forceinline__ void buf_st_stream(const StreamBuf& b, unsigned voff, unsigned soff, float v) {
+  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), b.r, (int)voff, (int)soff, kBufNt);
+}
+
 template <bool HAS_PAD, int WT, int NT = 0, int CT = 0>
 __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArgs a_arg, GridW<2> g_arg) {
   const GridW<2> g = grid2_of<WT>(g_arg);
@@ -65,17 +101,25 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
   float gq[4][4];           // [channel][point] of the thread's quad: g_out of the group being staged
   float fq[4][4];           // the same of feat: requested during the group's items, consumed (and overwritten by g_feat) behind them
   float cvq[4];
-  const float* const src0 = a.src + bh * C * (size_t)N;
-  const float* const fea0 = feat + bh * C * (size_t)N;
-  const float* const cnv0 = a.tile_in + bh * C * (size_t)G;
-  const unsigned ln0 = (unsigned)n0, lc0 = (unsigned)(tid < G ? tid : 0);
+  // The plane's five streams go through buffer descriptors built from kernel arguments and block indices alone (wave-uniform:
+  // scalar registers), a channel row is the scalar offset, and the lanes share ONE 32-bit offset: the byte offset of the thread's
+  // quad in a point row (a quarter of it: of its cell in a grid row).  No per-lane 64-bit address is left for the compiler to keep
+  // across the group loop.  The accesses keep the non-temporal hint of ld_stream4 / st_stream4.
+  const unsigned ln0 = (unsigned)n0;
+  const unsigned pt_row = (unsigned)N * 4u, cell_row = (unsigned)G * 4u;      // bytes
+  const StreamBuf b_src = stream_buf(a.src + bh * C * (size_t)N, (unsigned)C * pt_row);
+  const StreamBuf b_fea = stream_buf(feat + bh * C * (size_t)N, (unsigned)C * pt_row);
+  const StreamBuf b_dst = stream_buf(a.dst + bh * C * (size_t)N, (unsigned)C * pt_row);
+  const StreamBuf b_cnv = stream_buf(a.tile_in + bh * C * (size_t)G, (unsigned)C * cell_row);
+  const StreamBuf b_gz = stream_buf(a.tile_out + bh * C * (size_t)G, (unsigned)C * cell_row);
+  const unsigned vo_pt = ln0 * 4u, vo_cell = tid < G ? (unsigned)tid * 4u : 0u;
   auto request1 = [&](int grp, int cj) {
-    const float4 t = ld_stream4(src0 + (size_t)(grp * 4 + cj) * N + ln0);
+    const float4 t = buf_ld_stream4(b_src, vo_pt, (unsigned)(grp * 4 + cj) * pt_row);
     gq[cj][0] = t.x; gq[cj][1] = t.y; gq[cj][2] = t.z; gq[cj][3] = t.w;
-    cvq[cj] = ld_stream(cnv0 + (size_t)(grp * 4 + cj) * G + lc0);
+    cvq[cj] = buf_ld_stream(b_cnv, vo_cell, (unsigned)(grp * 4 + cj) * cell_row);
   };
   auto request_feat1 = [&](int grp, int cj) {
-    const float4 t = ld_stream4(fea0 + (size_t)(grp * 4 + cj) * N + ln0);
+    const float4 t = buf_ld_stream4(b_fea, vo_pt, (unsigned)(grp * 4 + cj) * pt_row);
     fq[cj][0] = t.x; fq[cj][1] = t.y; fq[cj][2] = t.z; fq[cj][3] = t.w;
   };
   PlaneKeys PK;
@@ -90,6 +134,10 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
     for (int cj = 0; cj < 4; ++cj) request1(0, cj);
   });
   // (sort_plane's last barrier is behind its last use of the scan scratch; the first group's barriers order these stores)
+  // The quad's base cells, 16 bits each (G <= 1024), parked in point order over the first-item marks: their last readers are in
+  // front of sort_plane's last barrier, and a thread reads back only the word it wrote.
+  uint2* const s_cell = (uint2*)(lds_raw + L.mark);
+  s_cell[tid] = make_uint2((unsigned)PK.base[0] | (unsigned)PK.base[1] << 16, (unsigned)PK.base[2] | (unsigned)PK.base[3] << 16);
   for (int i = tid; i < G; i += kSortThreads) ((int4*)acc)[i] = make_int4(0, 0, 0, 0);
   if (tid == 0) Sg[N] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   if (tid < 4) s_tie[tid] = 0;
@@ -103,14 +151,15 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
   float gs[4][2];           // Splat's key cotangent of the quad's points
 #pragma unroll
   for (int i = 0; i < 4; ++i) gs[i][0] = gs[i][1] = 0.0f;
+  // the two items' cells in one register (G <= 1024; -1: no item), unpacked per group
+  unsigned cell01 = ((unsigned)S.cell[0] & 0xffffu) | (unsigned)S.cell[1] << 16;
   unsigned long long tied = 0ull;      // block-uniform: bit i — group i has more matches than non-zero cells
-
-  const float* const key0 = a.pos.keys + bh * 2 * (size_t)N;       // wave-uniform base, 32-bit lane offsets (as src0)
 
   auto group = [&](const int grp, auto more) {
     const int ch0 = grp * 4;
     // (opaque per group, as the items' offsets below: the unpacked positions would otherwise be kept across the loop, in scratch)
-    asm volatile("" : "+v"(S.rk01), "+v"(S.rk23));
+    asm volatile("" : "+v"(S.rk01), "+v"(S.rk23), "+v"(cell01));
+    const int cell[2] = {(int)(short)(cell01 & 0xffffu), (int)cell01 >> 16};
 #pragma unroll
     for (int cj = 0; cj < 4; ++cj) {
       float m = 0.0f;
@@ -149,8 +198,9 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
     // the item body of slice_bwd_sorted_kernel; the first item carries the requests of this group's feat rows
     auto item = [&](auto U) {
       constexpr int u = decltype(U)::value;
-      const int Y = S.cell[u] < 0 ? 0 : S.cell[u];
-      asm volatile("" : "+v"(S.ent8[u][0]), "+v"(S.ent8[u][1]));
+      int Y = cell[u] < 0 ? 0 : cell[u];
+      // (opaque per group, the cell too: its accumulator byte offset was otherwise kept beside its tile offset, in scratch)
+      asm volatile("" : "+v"(S.ent8[u][0]), "+v"(S.ent8[u][1]), "+v"(Y));
       float4 cv[4];
 #pragma unroll
       for (int v = 0; v < 4; ++v) cv[v] = T4[Y + off[v]];
@@ -186,7 +236,7 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
         asm volatile("" : "+v"(gsx[u][j]), "+v"(gsy[u][j]));
         CT_SB;
       }
-      if (S.cell[u] >= 0) {
+      if (cell[u] >= 0) {
         const ct_f2 iq01 = {iq[0], iq[1]}, iq23 = {iq[2], iq[3]};
         int* Tc = acc + Y;
 #pragma unroll
@@ -201,14 +251,12 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
       CT_SB;
     };
     item(std::integral_constant<int, 0>{});
-    if (S.cell[1] >= 0) item(std::integral_constant<int, 1>{});
+    if (cell[1] >= 0) item(std::integral_constant<int, 1>{});
     if (any_float) {
 #pragma unroll 1
       for (int cj = 0; cj < 4; ++cj)
         if (iq[cj] == 0.0f) scatter_float_channel<HAS_PAD>(a, g, bh, b, ch0 + cj, (float*)(acc + cj * G), 1, 0);
     }
-    // the quad's keys: from the cache (the sort read them), a group at a time — eight registers the items do not carry
-    const float4 tx = *(const float4*)(key0 + ln0), ty = *(const float4*)(key0 + N + ln0);
     __syncthreads();
 
     // ---- convert: thread = cell.  Its four accumulator words -> g_z (slice_bwd_sorted_kernel's arithmetic per word), its z word, the
@@ -219,7 +267,6 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
     float gv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (tid < G) {
       zc = T4[tid];
-      float* gout = a.tile_out + (bh * C + ch0) * (size_t)G + tid;
 #pragma unroll
       for (int cj = 0; cj < 4; ++cj) {
         float q, iqd;
@@ -227,7 +274,7 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
         fx_quantum(__uint_as_float(s_max[ch0 + cj]) * Kf, q, iqd, fixed);
         const int r = acc[cj * G + tid];
         gv[cj] = fixed ? (float)r * q : __int_as_float(r);
-        __builtin_nontemporal_store(gv[cj], gout + (size_t)cj * G);
+        buf_st_stream(b_gz, vo_cell, (unsigned)(ch0 + cj) * cell_row, gv[cj]);
       }
     }
     const unsigned zw[4] = {__float_as_uint(zc.x), __float_as_uint(zc.y), __float_as_uint(zc.z), __float_as_uint(zc.w)};
@@ -248,14 +295,19 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
     // ---- Splat(max) backward, the optimistic pass of splat_bwd_quad<HAS_PAD, false, WT> on the thread's quad and these channels ----
     int nm = 0;
     if (has) {
-      float kx[4] = {tx.x, tx.y, tx.z, tx.w}, ky[4] = {ty.x, ty.y, ty.z, ty.w};
+      // The points' set-up is the sort's, not recomputed from the keys: the base cells parked behind the sort, (w1x, w1y) from the
+      // entry's weights, w0 = 1 - w1 (bit for bit, as the items), the corner products in pt2_from_keys' order.
+      const uint2 bc = s_cell[tid];
+      const unsigned rk[4] = {S.rk01 & kRankMask, (S.rk01 >> 16) & kRankMask, S.rk23 & kRankMask, (S.rk23 >> 16) & kRankMask};
+      const int pbase[4] = {(int)(bc.x & 0xffffu), (int)(bc.x >> 16), (int)(bc.y & 0xffffu), (int)(bc.y >> 16)};
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         if constexpr (decltype(more)::value) request1(grp + 1, i);      // one channel of the next group's g_out per point
-        // (opaque per group: the corner set-up of all four points would otherwise be kept across the group loop)
-        asm volatile("" : "+v"(kx[i]), "+v"(ky[i]));
+        const float2 w1 = AB[rk[i]];
         Pt2 p;
-        pt2_from_keys(kx[i], ky[i], g, W1, p);
+        p.w1x = w1.x; p.w1y = w1.y; p.w0x = 1.0f - w1.x; p.w0y = 1.0f - w1.y;
+        p.base = pbase[i];
+        p.cw[0] = p.w0x * p.w0y; p.cw[1] = p.w1x * p.w0y; p.cw[2] = p.w0x * p.w1y; p.cw[3] = p.w1x * p.w1y;
         float gw[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int pr = 0; pr < 2; ++pr) {
@@ -291,7 +343,7 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
       }
 #pragma unroll
       for (int cj = 0; cj < 4; ++cj)
-        st_stream4(a.dst + (bh * C + ch0 + cj) * (size_t)N + n0, make_float4(fq[cj][0], fq[cj][1], fq[cj][2], fq[cj][3]));
+        buf_st_stream4(b_dst, vo_pt, (unsigned)(ch0 + cj) * pt_row, make_float4(fq[cj][0], fq[cj][1], fq[cj][2], fq[cj][3]));
     } else if constexpr (decltype(more)::value) {
 #pragma unroll
       for (int cj = 0; cj < 4; ++cj) request1(grp + 1, cj);      // (a thread without a quad still stages its conv cell)
@@ -304,7 +356,10 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
     const int* tw = s_tie + (grp & 1) * 2;
     if (tw[0] != tw[1]) tied |= 1ull << grp;
     if (tid < 2) s_tie[((grp & 1) ^ 1) * 2 + tid] = 0;
-    if (tid < G) ((int4*)acc)[tid] = make_int4(0, 0, 0, 0);
+    // (the zero is made per group: one kept across the loop as a 16-byte vector was spilled and reloaded here)
+    int zero;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
+    if (tid < G) ((int4*)acc)[tid] = make_int4(zero, zero, zero, zero);
   };
   int grp = 0;
   for (; grp + 1 < ngroups; ++grp) group(grp, std::true_type{});
@@ -340,6 +395,7 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
       }
       __syncthreads();
       if (has) {
+        const float* const key0 = a.pos.keys + bh * 2 * (size_t)N;
         const float4 tx = *(const float4*)(key0 + ln0), ty = *(const float4*)(key0 + N + ln0);
         const float kx[4] = {tx.x, tx.y, tx.z, tx.w}, ky[4] = {ty.x, ty.y, ty.z, ty.w};
         int nm_unused = 0;
@@ -371,10 +427,16 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
       st_stream4(a.fold_gpos + (bh * 2 + 0) * N + n0, make_float4(gk[0].x, gk[1].x, gk[2].x, gk[3].x));
       st_stream4(a.fold_gpos + (bh * 2 + 1) * N + n0, make_float4(gk[0].y, gk[1].y, gk[2].y, gk[3].y));
     }
-    // gs * mask + add: the order of splat_max_bwd_hot_kernel's store with an incoming cotangent
-    const float4 tx = *(const float4*)(key0 + ln0), ty = *(const float4*)(key0 + N + ln0);
-    float4 ox = make_float4(gs[0][0] * ct_key_mask(tx.x), gs[1][0] * ct_key_mask(tx.y), gs[2][0] * ct_key_mask(tx.z), gs[3][0] * ct_key_mask(tx.w));
-    float4 oy = make_float4(gs[0][1] * ct_key_mask(ty.x), gs[1][1] * ct_key_mask(ty.y), gs[2][1] * ct_key_mask(ty.z), gs[3][1] * ct_key_mask(ty.w));
+    // gs * mask + add: the order of splat_max_bwd_hot_kernel's store with an incoming cotangent; the mask is the rank's clamp flag
+    // (ct_key_mask's {0, 1}, taken by the sort)
+    float mx[4], my[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      mx[i] = (rw[i] & kInsideX) ? 1.0f : 0.0f;
+      my[i] = (rw[i] & kInsideY) ? 1.0f : 0.0f;
+    }
+    float4 ox = make_float4(gs[0][0] * mx[0], gs[1][0] * mx[1], gs[2][0] * mx[2], gs[3][0] * mx[3]);
+    float4 oy = make_float4(gs[0][1] * my[0], gs[1][1] * my[1], gs[2][1] * my[2], gs[3][1] * my[3]);
     ox.x += gk[0].x; ox.y += gk[1].x; ox.z += gk[2].x; ox.w += gk[3].x;
     oy.x += gk[0].y; oy.y += gk[1].y; oy.z += gk[2].y; oy.w += gk[3].y;
     *(float4*)(a.g_pos + (bh * 2 + 0) * N + n0) = ox;
