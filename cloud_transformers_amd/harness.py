@@ -372,7 +372,7 @@ class Trainer:
         self.shapenet, self.val_loader, self.best_val = kind == "shapenet_completion" or self.shapenet_device, None, None
         self.scan, self.best_acc, self.best_macc = task == "classification_scanobjectnn", float("-inf"), float("-inf")
         self.blocks, self.train_meter, self.train_records, self._pred = task == "segmentation_blocks", None, [], None
-        self._graph_preds = {}
+        self._graph_preds, self._graph_chamfers, self._val_graph = {}, {}, None
         self.recon, self.last_chamfer, self._noise_gen = task == "reconstruction", None, None
         if self.recon:
             self.sampler = None                          # (ImageBatches holds torch's DistributedSampler itself)
@@ -463,12 +463,18 @@ class Trainer:
                             rank=self.rank, world=self.dist.get_world_size() if active else 1,
                             drop_last=bool(d.get("drop_last", False)) and train, points=points)
 
-    def _reconstruct(self, img, pcd_gt, eps, iters, n_noise=None):
-        """(sqrt-EMD loss, rec [B, 3, 1, N], gt [B, 3, 1, n]) of train_image_reconstruction.py:166-175 for a device batch."""
-        from .emd import emd_distance
+    def _draw_noise(self, pcd_gt, n_noise=None):
+        """The step's sphere noise [B, 3, gt_size]: ONE draw from `_noise_gen` (the only place the harness draws from it)."""
         from .metrics import sphere_noise
+        return sphere_noise(pcd_gt.shape[0], pcd_gt.shape[-1] if n_noise is None else n_noise, pcd_gt.device, generator=self._noise_gen)
+
+    def _reconstruct(self, img, pcd_gt, eps, iters, n_noise=None, noise=None):
+        """(sqrt-EMD loss, rec [B, 3, 1, N], gt [B, 3, 1, n]) of train_image_reconstruction.py:166-175 for a device batch.
+        `noise`: the sphere noise to use (a graph's static buffer, filled from an eager draw); by default it is drawn here."""
+        from .emd import emd_distance
         gt = pcd_gt[:, :, None]
-        noise = sphere_noise(gt.shape[0], gt.shape[-1] if n_noise is None else n_noise, gt.device, generator=self._noise_gen)
+        if noise is None:
+            noise = self._draw_noise(pcd_gt, n_noise)
         out = self.model(noise, img)
         rec = out[0] if isinstance(out, (tuple, list)) else out
         dist, _ = emd_distance(rec[:, :, 0].permute(0, 2, 1), gt[:, :, 0].permute(0, 2, 1), eps, iters)
@@ -482,7 +488,8 @@ class Trainer:
         if self.task == "reconstruction":
             from .chamfer import loss_chamfer_adj
             tr = self.cfg["train"]
-            loss, rec, gt = self._reconstruct(batch[0], batch[1], float(tr["emd_eps"]), int(tr["emd_iters"]))
+            loss, rec, gt = self._reconstruct(batch[0], batch[1], float(tr["emd_eps"]), int(tr["emd_iters"]),
+                                              noise=batch[2] if len(batch) > 2 else None)      # (a graph's batch carries its noise)
             with torch.no_grad():
                 self.last_chamfer = loss_chamfer_adj(rec.detach(), gt)
             return loss
@@ -529,14 +536,63 @@ class Trainer:
             parallel.save_exp_parallel([self.model, self.optimizer], ["generator", "g_opt"], exp_path=self.exp_dir,
                                        epoch=self.iters if epoch is None else epoch, epoch_name="iter" if epoch is None else "epoch")
 
-    def _validate_completion(self, epoch, dataset=None):
+    # -- validation: the per-batch work as one function of device tensors, run eagerly or by graph replay ------------------
+    def _val_step(self, *t):
+        """One validation batch of this task: the eval-mode forward plus the task's validation loss terms, device tensors in,
+        device tensors out (the caller holds eval mode and no_grad; the meters stay with the caller).
+        reconstruction (img, cloud, noise) -> (loss_emd, loss_chamfer); completion (noise, partial, gt) -> (loss_emd,
+        loss_chamfer); segmentation_blocks (points, labels) -> (pred, loss); classification_scanobjectnn (points, label, mask)
+        -> (loss, loss_cls, loss_seg, logits, mask logits); segmentation_kpconv (points, mask, features, labels) -> (pred, loss)."""
+        tr = self.cfg["train"]
+        if self.task == "reconstruction":
+            from .chamfer import loss_chamfer_adj
+            l_emd, rec, gt = self._reconstruct(t[0], t[1], float(tr["val_emd_eps"]), int(tr["val_emd_iters"]), noise=t[2])
+            return l_emd, loss_chamfer_adj(rec, gt)
+        if self.task == "completion":
+            from .chamfer import loss_chamfer
+            from .emd import emd_distance
+            noise, part, gt = t
+            out = self.model(noise, part.permute(0, 2, 1)[:, :, None])
+            rec = out[0] if isinstance(out, (tuple, list)) else out
+            gt4 = gt.permute(0, 2, 1)[:, :, None]
+            dist, _ = emd_distance(rec[:, :, 0].permute(0, 2, 1), gt4[:, :, 0].permute(0, 2, 1),
+                                   float(tr.get("val_emd_eps", 0.004)), int(tr.get("val_emd_iters", 3000)))
+            return torch.sqrt(dist).mean(1).mean(), loss_chamfer(rec, gt4)
+        if self.task == "segmentation_blocks":
+            pred = self._block_pred(t[0])
+            return pred, self.ce(pred[:, :, 0], t[1])
+        if self.task == "classification_scanobjectnn":
+            loss, cls_loss, seg_loss, out = self._scan_losses(t)
+            return loss, cls_loss, seg_loss, out[0], out[1]
+        if self.task == "segmentation_kpconv":
+            from .train_kpconv import masked_cross_entropy
+            points, mask, features, labels = t
+            pred = parallel._plain_module(self.model)(points, mask, features)
+            return pred, masked_cross_entropy(pred, labels, mask)
+        raise ValueError("task %r has no validation step" % (self.task,))
+
+    def _val_runner(self, hip_graph=None):
+        """What a validation pass calls per batch: `_val_step` itself (the launches of today), or — with `hip_graph`, by default
+        `train.hip_graph_val` of the config — a graphs.GraphedForward over it (`_val_graph`, built on first use and kept between
+        validations: a graph per batch shape, parameter addresses and modes; a refused capture is printed once on rank 0 and
+        the step runs eagerly from then on — no rank agreement: an eval forward holds no collective).  The outputs of a replay
+        are static: the callers consume them before the next batch."""
+        use = bool(self.cfg["train"].get("hip_graph_val", False) if hip_graph is None else hip_graph)
+        if not use or self.device.type != "cuda":
+            return self._val_step
+        if self._val_graph is None:
+            from .graphs import GraphedForward
+            # (the plain module names the parameters: a data-parallel wrapper keeps its own training flag through model.eval()
+            #  of the module inside, which is what the KPConv vote passes switch)
+            self._val_graph = GraphedForward(parallel._plain_module(self.model), fn=self._val_step, fallback=True, verbose=self.rank == 0)
+        return self._val_graph
+
+    def _validate_completion(self, epoch, dataset=None, hip_graph=None):
         """train_inpainter.py:253-311: eval mode, no grad, the VAL subset in batches of `data.batch_size_val`; per batch
         sqrt(EMD(rec, gt, val_emd_eps, val_emd_iters)).mean(1).mean() and loss_chamfer, averaged over the batches and the
         ranks (sums and the count stay on the device until the one read at the end)."""
         import json
-        from .chamfer import loss_chamfer
         from .data.completion import CompletionBatches
-        from .emd import emd_distance
         cfg, tr = self.cfg, self.cfg["train"]
         if self.shapenet_device and (self.val_loader is None or dataset is not None):
             self.val_loader = self._completion_batches(dataset if dataset is not None else make_dataset(cfg, "completion", None, train=False),
@@ -547,21 +603,16 @@ class Trainer:
             self.val_loader = CompletionBatches(data, cfg["data"].get("batch_size_val", cfg["data"]["batch_size"]), self.device,
                                                 seed=int(cfg["data"].get("seed", 0)) + 7919, rank=self.rank, sampler=smp,
                                                 num_workers=int(cfg["data"].get("num_workers", 0)), worker_init_fn=worker_init_fn)
-        eps, iters = float(tr.get("val_emd_eps", 0.004)), int(tr.get("val_emd_iters", 3000))
         w = float(tr.get("chamfer_weight", 1.0))
         model = self.model
         was_training = model.training
         model.eval()
         self.val_loader.set_epoch(epoch if isinstance(epoch, int) else 0)
+        step = self._val_runner(hip_graph)
         sums = torch.zeros(4, dtype=torch.float64, device=self.device)            # loss, loss_emd, loss_chamfer, batches
         with torch.no_grad():
             for noise, part, gt in self.val_loader:
-                out = model(noise, part.permute(0, 2, 1)[:, :, None])
-                rec = out[0] if isinstance(out, (tuple, list)) else out
-                gt4 = gt.permute(0, 2, 1)[:, :, None]
-                dist, _ = emd_distance(rec[:, :, 0].permute(0, 2, 1), gt4[:, :, 0].permute(0, 2, 1), eps, iters)
-                l_emd = torch.sqrt(dist).mean(1).mean()
-                l_cd = loss_chamfer(rec, gt4)
+                l_emd, l_cd = step(noise, part, gt)
                 sums += torch.stack([l_emd + w * l_cd, l_emd, l_cd, torch.ones_like(l_cd)]).double()
         model.train(was_training)
         if parallel._active(self.dist):
@@ -587,13 +638,11 @@ class Trainer:
         self.val_records.append(rec)
         return [rec]
 
-    def _validate_reconstruction(self, epoch, dataset=None):
+    def _validate_reconstruction(self, epoch, dataset=None, hip_graph=None):
         """train_image_reconstruction.py:225-268: eval mode, no grad, the 'val' split in batches of `data.batch_size_val`; per
         batch sqrt(EMD(rec, gt, val_emd_eps, val_emd_iters)).mean(1).mean() and loss_chamfer_adj, averaged over the batches and
         the ranks (sums and the count stay on the device until the one read at the end); `best`: a new minimum of the EMD."""
         import json
-        from .chamfer import loss_chamfer_adj
-        tr = self.cfg["train"]
         if self.val_loader is None or dataset is not None:
             data = dataset if dataset is not None else make_dataset(self.cfg, self.task, self.n_classes, train=False)
             self.val_loader = self._image_batches(data, train=False)
@@ -601,11 +650,11 @@ class Trainer:
         was_training = model.training
         model.eval()
         self.val_loader.set_epoch(epoch if isinstance(epoch, int) else 0)
+        step = self._val_runner(hip_graph)
         sums = torch.zeros(3, dtype=torch.float64, device=self.device)            # loss_emd, loss_chamfer, batches
         with torch.no_grad():
             for img, pcd in self.val_loader:
-                l_emd, rec, gt = self._reconstruct(img, pcd, float(tr["val_emd_eps"]), int(tr["val_emd_iters"]))
-                l_cd = loss_chamfer_adj(rec, gt)
+                l_emd, l_cd = step(img, pcd, self._draw_noise(pcd))            # (the noise: one eager draw per batch, as ever)
                 sums += torch.stack([l_emd, l_cd, torch.ones_like(l_cd)]).double()
         model.train(was_training)
         if parallel._active(self.dist):
@@ -630,7 +679,7 @@ class Trainer:
         self.val_records.append(rec)
         return [rec]
 
-    def _validate_scan(self, epoch, dataset=None):
+    def _validate_scan(self, epoch, dataset=None, hip_graph=None):
         """train_classification.py:286-374: eval mode, no grad, `data.path_val` in batches of `data.batch_size_val`; the three
         losses averaged over the batches and the ranks, the accuracies from ClassificationMeter's counts all-reduced over the
         ranks (counts and sums stay on the device until the two reads at the end).  As in the reference the shards are padded
@@ -646,12 +695,13 @@ class Trainer:
         model.eval()
         self.val_loader.set_epoch(epoch if isinstance(epoch, int) else 0)
         meter = ClassificationMeter(self.n_classes)
+        step = self._val_runner(hip_graph)
         sums = torch.zeros(4, dtype=torch.float64, device=self.device)            # loss, loss_cls, loss_seg, batches
         with torch.no_grad():
             for batch in self.val_loader:
-                loss, cls_loss, seg_loss, out = self._scan_losses(batch)
+                loss, cls_loss, seg_loss, logits, mask_logits = step(*batch)
                 sums += torch.stack([loss, cls_loss, seg_loss, torch.ones_like(loss)]).double()
-                meter.update(out[0], out[1], batch[1], batch[2])
+                meter.update(logits, mask_logits, batch[1], batch[2])
         model.train(was_training)
         if parallel._active(self.dist):
             self.dist.all_reduce(sums)
@@ -679,7 +729,7 @@ class Trainer:
         self.val_records.append(rec)
         return [rec]
 
-    def _validate_blocks(self, epoch, dataset=None):
+    def _validate_blocks(self, epoch, dataset=None, hip_graph=None):
         """train_segmentation.py:244-288: eval mode, no grad, the blocks of `data.test_area` in batches of `data.batch_size_val`
         (shuffled points, no augmentation); the loss averaged over the batches and the ranks, the confusion matrix filled on the
         device (SegmentationMeter) and all-reduced over the ranks, `return_metrics_dict`'s numbers from it (sums and counts stay
@@ -695,11 +745,11 @@ class Trainer:
         model.eval()
         self.val_loader.set_epoch(epoch if isinstance(epoch, int) else 0)
         meter = SegmentationMeter(self.n_classes)
+        step = self._val_runner(hip_graph)
         sums = torch.zeros(2, dtype=torch.float64, device=self.device)            # loss, batches
         with torch.no_grad():
             for pcd, labels in self.val_loader:
-                pred = self._block_pred(pcd)
-                loss = self.ce(pred[:, :, 0], labels)
+                pred, loss = step(pcd, labels)
                 sums += torch.stack([loss, torch.ones_like(loss)]).double()
                 meter.update(pred, labels)
         model.train(was_training)
@@ -734,7 +784,7 @@ class Trainer:
                     self.writer.add_scalar("train/" + k, v, global_step=epoch)
         self.train_records.append(rec)
 
-    def validate(self, num_votes=None, epoch=None):
+    def validate(self, num_votes=None, epoch=None, hip_graph=None):
         """segmentation_kpconv: one validation of `num_votes` vote passes (train_kpconv.KPConvData.validate) on the unwrapped
         model; the records go to the writer and, on rank 0, to <exp>/kpconv_val.jsonl.  Returns them.
         completion (`num_votes` is not used): one pass over the VAL subset (`_validate_completion`), its record appended to
@@ -745,17 +795,22 @@ class Trainer:
         segmentation_blocks (`num_votes` is not used): one pass over the blocks of `data.test_area` (`_validate_blocks`), its record
         (loss, overall_acc, mean_class_acc, iou_<name>, mean_iou) appended to <exp>/segmentation_val.jsonl.
         reconstruction (`num_votes` is not used): one pass over the 'val' split (`_validate_reconstruction`), its record (loss_emd,
-        loss_chamfer) appended to <exp>/reconstruction_val.jsonl; `generator_best_0.t7` / `g_opt_best_0.t7` on a new minimum."""
+        loss_chamfer) appended to <exp>/reconstruction_val.jsonl; `generator_best_0.t7` / `g_opt_best_0.t7` on a new minimum.
+
+        `hip_graph` (default: `train.hip_graph_val` of the config, else False; independent of `train.hip_graph`): the per-batch
+        work — eval-mode forward plus the validation loss terms, `_val_step` — runs by replay of one HIP graph per batch shape
+        (`_val_runner`, graphs.GraphedForward); the meters and tables stay eager on the graph's static outputs.  The graphs read
+        the parameters where they live and are kept between validations: training steps in between need no new capture."""
         import json
         if self.task == "reconstruction":
-            return self._validate_reconstruction(epoch)
+            return self._validate_reconstruction(epoch, hip_graph=hip_graph)
         if self.task == "segmentation_blocks":
-            return self._validate_blocks(epoch)
+            return self._validate_blocks(epoch, hip_graph=hip_graph)
         if self.task == "completion":
-            return self._validate_completion(epoch)
+            return self._validate_completion(epoch, hip_graph=hip_graph)
         if self.task == "classification_scanobjectnn":
-            return self._validate_scan(epoch)
-        records = self.kp.validate(parallel._plain_module(self.model), num_votes, epoch)
+            return self._validate_scan(epoch, hip_graph=hip_graph)
+        records = self.kp.validate(parallel._plain_module(self.model), num_votes, epoch, step=self._val_runner(hip_graph))
         if self.rank == 0:
             for rec in records:
                 step = self.iters
@@ -793,7 +848,9 @@ class Trainer:
         gradient all-reduce and the norms' statistics exchanges: RCCL collectives are captured like kernels); the optimizer
         step stays outside.  The blocks' eager launch rate is host-bound (~250 launches per block through Python / ctypes:
         the segmenter step 30.8 ms eager vs 24.8 ms graphed, profiles/r3_tools_output.txt).  Returns the record of the
-        capture: (graph, static inputs, static loss, the gradient tensors the graph writes)."""
+        capture: (graph, static inputs, static loss, the gradient tensors the graph writes).  Reconstruction: the static inputs
+        are (image, cloud, noise) — the noise is an input of the graph, and neither the warm-up nor the capture draws from
+        `_noise_gen`; `last_chamfer` of the capture is a static output."""
         static = [t.to(self.device).clone() for t in batch]
         buffers = [b.clone() for b in self.model.buffers()]          # the warm-up passes must not count as training steps
         params = [p for p in self.model.parameters() if p.requires_grad]
@@ -826,12 +883,18 @@ class Trainer:
         captured tensors with zero_grad(), would silently stop the training."""
         key = tuple(tuple(t.shape) for t in batch)
         rec = self._graphs.get(key)
+        if self.recon and rec is not False:
+            # the step's noise: the same generator, the same call and the same one draw per step as the eager step's, drawn
+            # here, outside the graph, and handed to it as a third static input (an eager fall-back step draws its own)
+            batch = (batch[0], batch[1], self._draw_noise(batch[1]))
         if rec is None:
             rec, failure = None, None
             try:
                 rec = self._capture(batch)
                 if self.blocks:
                     self._graph_preds[key] = self._pred       # the graph's static prediction: read after every replay
+                if self.recon:
+                    self._graph_chamfers[key] = self.last_chamfer      # likewise the logged Chamfer term
             except RuntimeError as ex:
                 # only what a refused CAPTURE raises (HIP's stream-capture errors, e.g. the process group's watchdog touching an
                 # event of the capturing stream); a genuine error inside the model or the loss is not swallowed as "capture failed"
@@ -856,13 +919,15 @@ class Trainer:
                 rec = False
             self._graphs[key] = rec
         if rec is False:
-            return self._eager_step(batch)
+            return self._eager_step(batch)            # (reconstruction: a noise drawn above rides along as batch[2])
         graph, static, static_loss, grads = rec
         for dst, src in zip(static, batch):
             dst.copy_(src, non_blocking=True)
         graph.replay()
         if self.blocks:
             self.train_meter.update(self._graph_preds[key], static[1])
+        if self.recon:
+            self.last_chamfer = self._graph_chamfers[key]             # static: _fit appends a clone
         for p, g in zip((p for p in self.model.parameters() if p.requires_grad), grads):
             p.grad = g
         self._clip()
@@ -879,7 +944,9 @@ class Trainer:
         torchrun users set it themselves; the price is that a hung collective then hangs the job instead of aborting it.  A capture that
         fails falls back to eager steps on one device and RAISES under DistributedDataParallel — the ranks agree on it first).  Losses stay on the
         device and are read back every `log_each` steps (default `train.log_each`, else 10) in ONE transfer — no host
-        synchronisation per step (the reference reads the loss every step: train_segmentation.py:180-186).
+        synchronisation per step (the reference reads the loss every step: train_segmentation.py:180-186).  The reconstruction
+        task's sphere noise is an INPUT of its graph: one eager draw per step from `_noise_gen`, before the replay, in step order,
+        so a graphed and an eager run of one seed see the same noise at step k; the logged Chamfer term is a static output.
 
         `train.deterministic: true` runs the whole fit in deterministic mode (determinism.py: run-to-run equal gradients from
         the library's kernels, all five tasks); the seeds are set as without it and nothing else changes.
@@ -909,10 +976,7 @@ class Trainer:
         tr = self.cfg["train"]
         use_graph = bool(tr.get("hip_graph", False) if hip_graph is None else hip_graph)
         log_each = int(tr.get("log_each", 10) if log_each is None else log_each)
-        if use_graph and self.recon:
-            raise ValueError("the reconstruction task draws its sphere noise inside the step from a generator of its own: "
-                             "train.hip_graph is not available for it")
-        self._graphs, self._graph_preds = {}, {}
+        self._graphs, self._graph_preds, self._graph_chamfers = {}, {}, {}
         history, pending, pending_chamfer = [], [], []
 
         def flush():
@@ -952,7 +1016,9 @@ class Trainer:
                 pending.append((self.iters, reduced["loss"].detach().reshape(())))
                 if self.recon and self.last_chamfer is not None:
                     chamfer = parallel.reduce_loss_dict(self.dist, {"loss_chamfer": self.last_chamfer})["loss_chamfer"]
-                    pending_chamfer.append((self.iters, chamfer.detach().reshape(())))
+                    chamfer = chamfer.detach().reshape(())
+                    # (under hip_graph `last_chamfer` is a static output that the next replay overwrites: a clone is kept)
+                    pending_chamfer.append((self.iters, chamfer.clone() if use_graph else chamfer))
                 self.iters += 1
                 if self.iters % log_each == 0:
                     flush()
@@ -1006,9 +1072,8 @@ class Trainer:
 
 def _is_capture_error(ex):
     """Is this RuntimeError HIP refusing or invalidating a stream capture (as opposed to an error of the captured code)?"""
-    msg = str(ex).lower()
-    return any(k in msg for k in ("capture", "hipgraph", "cudagraph", "graph", "operation not permitted when stream is capturing",
-                                  "streamcapture"))
+    from .graphs import is_capture_error
+    return is_capture_error(ex)
 
 
 def load_config(path):

@@ -13,7 +13,8 @@ are HDF5 (or their .npz twins: data/datasets.py).
   (1 - seg_weight) * CE + seg_weight * BCE, the scheduler stepped per iteration, a validation every `train.val_step` epochs
   (`Trainer.validate`: <exp>/classification_val.jsonl, `generator_best_0.t7` on a new best cls_acc,
   `generator_macc_best_0.t7` on a new best m_acc), `generator_epoch_{e}.t7` every `train.save_each_epoch` epochs.
-- `--eval`: restore `restore.generator`, then one validation over `data.path_val`; its record is printed and returned.
+- `--eval`: restore `restore.generator`, then one validation over `data.path_val` (`train.hip_graph_val: true`: its per-batch
+  work by HIP-graph replay, as in the validations of a training run); its record is printed and returned.
 - `--gpus N > 1`: N ranks through `launch.spawn_ranks`, one process group over RCCL (training only)."""
 import argparse
 import copy

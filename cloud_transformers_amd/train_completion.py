@@ -76,6 +76,7 @@ def _evaluate_batched(model, cfg, device, generator, resident, k):
     ids, which are host data.  One copy at the end -> the dictionary `evaluate` returns, taxonomies in the order they first
     appear."""
     from .data.completion import DatasetSubset, collate_fn, completion_items, shapenet_loader
+    from .graphs import eval_forward
     from .metrics import Metrics, TableMeter
     if resident is not None:
         every_id = list(resident.taxonomy_ids)
@@ -91,13 +92,14 @@ def _evaluate_batched(model, cfg, device, generator, resident, k):
     meter = TableMeter(len(rows), 3, device)            # columns: F-Score, Chamfer x 1000, dense loss x 1000
     was_training = model.training
     model.eval()
+    forward = eval_forward(model, cfg)          # `train.hip_graph_val`: a HIP graph per batch shape
     with torch.no_grad():
         for taxonomy_ids, _model_ids, data in loader:
             ids = [t if isinstance(t, str) else t.item() for t in taxonomy_ids]
             gt = data["gtcloud"].to(device, non_blocking=True)
             part, noise, _ = completion_items(data["partial_cloud"].to(device, non_blocking=True), gt.shape[1], scale=2.0,
                                               generator=generator)
-            out = model(noise, part.permute(0, 2, 1)[:, :, None])
+            out = forward(noise, part.permute(0, 2, 1)[:, :, None])
             rec = out[0] if isinstance(out, (tuple, list)) else out
             dense = (rec / 2)[:, :, 0].permute(0, 2, 1).contiguous()
             row = torch.tensor([rows[t] for t in ids], dtype=torch.int64).to(device, non_blocking=True)
@@ -120,6 +122,7 @@ def evaluate(model, cfg, device, exp_dir=None, generator=None, verbose=True, res
     clouds and the metrics stay on the device until the end (`_evaluate_batched`); the model's draws then depend on the
     batch, so the table is that of another sample of the noise, not the batch-of-one table bit for bit."""
     from .data.completion import DatasetSubset, collate_fn, completion_items, shapenet_loader
+    from .graphs import eval_forward
     from .metrics import AverageMeter, ChamferDistance, Metrics
     if generator is None:
         generator = torch.Generator(device=device).manual_seed(int(cfg["data"].get("seed", 0)) * 1000003 + 104729)
@@ -136,6 +139,7 @@ def evaluate(model, cfg, device, exp_dir=None, generator=None, verbose=True, res
                                              shuffle=False)
     was_training = model.training
     model.eval()
+    forward = eval_forward(model, cfg, verbose=verbose)          # `train.hip_graph_val`: a HIP graph per batch shape
     chamfer_dist = ChamferDistance()
     test_losses, test_metrics, category_metrics = AverageMeter(["DenseLoss"]), AverageMeter(Metrics.names()), {}
     with torch.no_grad():
@@ -143,7 +147,7 @@ def evaluate(model, cfg, device, exp_dir=None, generator=None, verbose=True, res
             taxonomy_id = taxonomy_id[0] if isinstance(taxonomy_id[0], str) else taxonomy_id[0].item()
             gt = data["gtcloud"].to(device)
             part, noise, _ = completion_items(data["partial_cloud"].to(device), gt.shape[1], scale=2.0, generator=generator)
-            out = model(noise, part.permute(0, 2, 1)[:, :, None])
+            out = forward(noise, part.permute(0, 2, 1)[:, :, None])
             rec = out[0] if isinstance(out, (tuple, list)) else out
             dense = (rec / 2)[:, :, 0].permute(0, 2, 1).contiguous()
             test_losses.update([chamfer_dist(dense, gt).item() * 1000])

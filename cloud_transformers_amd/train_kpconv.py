@@ -10,7 +10,8 @@ reference hard-codes in its FakeCFG (train_segmentation_kpconv.py:84-114) are de
   seeded by `data.seed`), sharded as DistributedSampler(shuffle=False) shards indices, in batches of `data.batch_size` (the
   last partial batch is dropped); items are augmented (`Augment`) from a per-rank generator.  Validation: the same over
   the validation Area, `num_votes` passes, pass v > 0 augmented, the last partial batch kept (the reference's val loader).
-- `--eval`: restore `restore.generator` (and `restore.optimizer` when given), then one validation of 20 votes.
+- `--eval`: restore `restore.generator` (and `restore.optimizer` when given), then one validation of 20 votes
+  (`train.hip_graph_val: true`: forward and loss of every vote batch by HIP-graph replay, `VoteEvaluator.add` eager).
 - `--gpus N > 1`: N ranks through `launch.spawn_ranks`, one process group over RCCL."""
 import argparse
 import copy
@@ -107,10 +108,12 @@ class KPConvData:
             points, mask, features, labels, _, _ = self.train.items(cloud[sel], picks[sel], self.augment, generator=self.train_gen)
             yield points, mask, features, labels
 
-    def validate(self, model, num_votes, epoch):
+    def validate(self, model, num_votes, epoch, step=None):
         """validate() of s3dis_closer_train.py:70-167: the vote sums and counts restart, the running logits go on; one record
         per pass: mean loss, part / running-sub / sub / full IoUs and their means (sums, counts and the part confusion
-        summed over the ranks first)."""
+        summed over the ranks first).  `step`: (points, mask, features, labels) -> (pred, masked cross-entropy) of `model`,
+        called per batch in its place (the harness passes its validation step, eager or replayed as a HIP graph; `pred` may
+        be a graph's static output: `VoteEvaluator.add` consumes it before the next batch)."""
         from . import parallel
         ev = self.evaluator
         ev.reset_votes()
@@ -127,8 +130,12 @@ class KPConvData:
                     sel = torch.tensor(rows, dtype=torch.int64, device=self.device)
                     points, mask, features, labels, cl, inds = self.val.items(cloud[sel], picks[sel], self.augment if v > 0 else None,
                                                                               generator=self.val_gen)
-                    pred = model(points, mask, features)
-                    loss[0] += masked_cross_entropy(pred, labels, mask).double() * len(rows)
+                    if step is None:
+                        pred = model(points, mask, features)
+                        batch_loss = masked_cross_entropy(pred, labels, mask)
+                    else:
+                        pred, batch_loss = step(points, mask, features, labels)
+                    loss[0] += batch_loss.double() * len(rows)
                     loss[1] += len(rows)
                     ev.add(pred, mask, cl, inds)
                 if parallel._active(self.dist):

@@ -8,6 +8,8 @@ The config is the reference's YAML as it is (`data.path`, `data.batch_size`, `da
 defaults here: `train.emd_eps` 0.005 and `train.emd_iters` 50 for the training loss, `train.val_emd_eps` 0.004 and
 `train.val_emd_iters` 3000 for validation, `data.seed` 42, and for `--eval` `data.eval_points` 10000, `data.eval_noise` 8192
 and `train.f1_threshold` 0.01.  `data.cache_dir` (optional) keeps the decoded renderings and clouds between runs.
+`train.hip_graph: true` replays the training step and `train.hip_graph_val: true` the validation step and the `--eval`
+forwards as HIP graphs; the sphere noise is drawn eagerly before every replay and copied into the graph's input.
 
 - training: the split lives on the device and every batch is one launch (data/image_point.py ImageBatches); noise on the unit
   sphere, loss = mean sqrt(EMD(rec, gt)), loss_chamfer_adj logged; the scheduler stepped per iteration;
@@ -48,18 +50,22 @@ def evaluate(model, batches, cfg, exp_dir=None, generator=None, verbose=True):
     """eval_reconstruction_f1.py:94-126 over `batches` (an ImageBatches of the test split) -> {"names": ["f1", "precision",
     "recall"], "categories": {name: {"count", "avg"}}, "overall": {"count", "avg"}}; printed and, with `exp_dir`, written to
     <exp_dir>/reconstruction_test.json."""
+    from .graphs import eval_forward
     from .metrics import get_f1_scores_merge, sphere_noise
     ds = batches.ds
     n_noise, th = int(cfg["data"]["eval_noise"]), float(cfg["train"]["f1_threshold"])
     scores = {}
     was_training = model.training
     model.eval()
+    # `train.hip_graph_val`: the forward by graph replay; both noise draws of a batch are eager inputs of the same graph, so the
+    # first reconstruction must outlive the second replay (clone_outputs)
+    forward = eval_forward(model, cfg, clone_outputs=True, verbose=verbose)
     with torch.no_grad():
         for img, pcd_gt in batches:
             recs = []
             for _ in range(2):
                 noise = sphere_noise(img.shape[0], n_noise, img.device, generator=generator)
-                out = model(noise, img)
+                out = forward(noise, img)
                 recs.append((out[0] if isinstance(out, (tuple, list)) else out)[:, :, 0])
             f1, pr, rc = get_f1_scores_merge(pcd=recs[0], pcd_2=recs[1], pcd_gt=pcd_gt, th=th, generator=generator)
             for c, row in zip(batches.last_classes.tolist(), zip(f1, pr, rc)):
@@ -100,7 +106,8 @@ def main(argv=None):
     args = _parse(argv)
     if args.gpus > 1 and not args.eval and not launch.under_launcher():
         rest = [a for i, a in enumerate(argv) if a != "--gpus" and (i == 0 or argv[i - 1] != "--gpus") and not a.startswith("--gpus=")]
-        rc = launch.spawn_ranks(os.path.abspath(__file__), rest, args.gpus, capture=False)
+        cfg = harness.load_config(args.config)
+        rc = launch.spawn_ranks(os.path.abspath(__file__), rest, args.gpus, capture=bool(cfg.get("train", {}).get("hip_graph", False)))
         if rc != 0:
             raise SystemExit(rc)
         return []

@@ -14,7 +14,8 @@ is filled in.  The values the reference hard-codes are defaults here: `data.n_cl
   confusion matrix filled on the device every step and reported per epoch, a validation every `train.val_step` epochs
   (`Trainer.validate`: <exp>/segmentation_val.jsonl), `generator_iter_{n}.t7` every `train.save_each` iterations,
   `generator_epoch_{e}.t7` every `train.save_each_epoch` epochs.
-- `--eval`: restore `restore.generator`, then one validation over the blocks of `data.test_area`; its record is printed and
+- `--eval`: restore `restore.generator`, then one validation over the blocks of `data.test_area` (`train.hip_graph_val: true`:
+  its per-batch work by HIP-graph replay, as in the validations of a training run); its record is printed and
   returned.
 - `--gpus N > 1`: N ranks through `launch.spawn_ranks`, one process group over RCCL (training only)."""
 import argparse
