@@ -338,6 +338,10 @@ SIGNATURES = {
     "ct_emd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "ct_emd_fwd_counts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _f, _i, _vp]),
     "ct_emd_bwd_counts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "ct_emd_tail_supported": (_i, [_i, _i]),
+    "ct_emd_tail_workspace_bytes": (_sz, [_i, _i]),
+    "ct_emd_fwd_tail": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _f, _i, _i, _vp]),
+    "ct_debug_set_emd_tail": (None, [_i, _i]),
     "ct_amax_f32": (_i, [_vp, _ll, _vp, _vp]),
     "ct_amax_len": (_i, []),
     "ct_pw_prep_weight_partials": (_i, [_i, _i]),

@@ -78,12 +78,42 @@ __global__ void emd_init_kernel(EmdWs w, int* assignment, size_t total, int nsyn
 // (emd_cuda.cu:30-93).  do_dist: CalcDist (emd_cuda.cu:217-226).
 // RAGGED: the cloud is the rows [0, c), c = emd_extent (<= n, any value): the compactions stop at c — a row at or beyond it keeps
 // assignment -1 for good and must never enter the list — and CalcDist writes 0 there.  Everything else walks the list.
-template <bool RAGGED>
+// With an EmdTailArg (ct_emd_fwd_tail's launches only; the kernels of ct_emd_fwd / ct_emd_fwd_counts are instantiated without one
+// and keep their device code): a cloud whose auction the tail kernel has finished (fin[b]) is skipped, and thread 0 keeps info[b] = {the first iteration
+// that started without a bidder | iters, the bidders of the last iteration} as the list lengths come by (emd_tail_note).
+// (The state travels as a trailing parameter PACK, empty in the launches of ct_emd_fwd / ct_emd_fwd_counts: their kernels keep
+// their arguments, hidden ones included, and so their code — tools/dev/kernel_digest.py.)
+struct EmdTailArg {
+  int* fin;      // [B]
+  int* info;     // [B, 2]
+  int it, iters; // the iteration this launch belongs to (-1: the compaction before iteration 0) of how many
+};
+__device__ __forceinline__ bool emd_tail_skip(int) { return false; }
+__device__ __forceinline__ bool emd_tail_skip(int b, const EmdTailArg& ta) { return ta.it >= 0 && ta.fin[b] != 0; }
+__device__ __forceinline__ void emd_tail_last(int, int) {}
+__device__ __forceinline__ void emd_tail_last(int b, int cnt, const EmdTailArg& ta) { ta.info[2 * b + 1] = cnt; }
+__device__ __forceinline__ void emd_tail_note(int, int) {}
+__device__ __forceinline__ void emd_tail_note(int b, int cnt, const EmdTailArg& ta) {
+  if (ta.it < 0) {                                     // the compaction before iteration 0: also the state's initialisation
+    ta.fin[b] = 0;
+    ta.info[2 * b] = cnt == 0 ? 0 : ta.iters;
+    ta.info[2 * b + 1] = 0;
+  } else if (cnt == 0 && ta.info[2 * b] == ta.iters) {
+    ta.info[2 * b] = ta.it + 1;                        // the list that iteration it leaves to iteration it + 1 is empty
+  }
+}
+
+template <bool RAGGED, class... TA>
 __global__ void __launch_bounds__(1024)
 emd_update_kernel(EmdWs w, int* assignment, const float* xyz1, const float* xyz2, float* dist,
-                  int n, int do_assign, int last, int do_compact, int do_dist) {
+                  int n, int do_assign, int last, int do_compact, int do_dist, TA... ta) {
+  static_assert(sizeof...(TA) <= 1, "nothing, or one EmdTailArg");
   __shared__ int s_scan[16];
   const int b = blockIdx.x;
+  if constexpr (sizeof...(TA) > 0) {
+    if (emd_tail_skip(b, ta...)) return;               // block-uniform, before any barrier
+    if (do_assign && last && threadIdx.x == 0) emd_tail_last(b, w.unass_cnt[b], ta...);
+  }
   const size_t off = (size_t)b * n;
   const int c = RAGGED ? emd_extent(w, b) : n;         // rows of this cloud (block-uniform)
   int* ass = assignment + off;
@@ -171,7 +201,10 @@ emd_update_kernel(EmdWs w, int* assignment, const float* xyz1, const float* xyz2
         }
       }
       __syncthreads();
-      if (threadIdx.x == 0) w.unass_cnt[b] = s_new;
+      if (threadIdx.x == 0) {
+        w.unass_cnt[b] = s_new;
+        emd_tail_note(b, s_new, ta...);
+      }
     }
     __threadfence_block();
     __syncthreads();
@@ -288,7 +321,10 @@ emd_update_kernel(EmdWs w, int* assignment, const float* xyz1, const float* xyz2
       }
       base += total;
     }
-    if (threadIdx.x == 0) w.unass_cnt[b] = base;
+    if (threadIdx.x == 0) {
+      w.unass_cnt[b] = base;
+      emd_tail_note(b, base, ta...);
+    }
   }
   }   // (slow path)
 
@@ -319,8 +355,10 @@ emd_update_kernel(EmdWs w, int* assignment, const float* xyz1, const float* xyz2
 #endif
 constexpr int kMultiR = 2, kSoloR = 4, kMultiMin = CT_EMD_MULTI_MIN;      // entries per thread: shared / alone (kSoloR * 1024 >= kMultiMin)
 static_assert(kSoloR * 1024 >= kMultiMin && kSoloR >= kMultiR, "entries per thread");
+template <class... TA>
 __global__ void __launch_bounds__(1024)
-emd_update_multi_kernel(EmdWs w, int* assignment, int n, int gen) {
+emd_update_multi_kernel(EmdWs w, int* assignment, int n, int gen, TA... ta) {
+  static_assert(sizeof...(TA) <= 1, "nothing, or one EmdTailArg");
   __shared__ int s_new, s_base;
   const int b = blockIdx.y, g = blockIdx.x, G = gridDim.x;
   const size_t off = (size_t)b * n;
@@ -335,6 +373,13 @@ emd_update_multi_kernel(EmdWs w, int* assignment, int n, int gen) {
   int* arrive = w.sync + 3 * b;
   int* done = arrive + 1;
   int* newc = arrive + 2;
+  if (emd_tail_skip(b, ta...)) {                               // finished by the tail kernel: the counters advance as if all G had met
+    if (g == 0 && threadIdx.x == 0) {
+      __hip_atomic_fetch_add(arrive, G, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_add(done, G, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return;
+  }
   const int U = w.unass_cnt[b];
   const bool solo = U <= kMultiMin;                  // the same for every workgroup of the batch
   if (solo && g != 0) return;
@@ -424,6 +469,7 @@ emd_update_multi_kernel(EmdWs w, int* assignment, int n, int gen) {
   if (solo) {                                        // (the counters advance as if all G workgroups had met)
     if (threadIdx.x == 0) {
       w.unass_cnt[b] = s_new;
+      emd_tail_note(b, s_new, ta...);
       __hip_atomic_fetch_add(arrive, G, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_fetch_add(done, G, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -435,6 +481,7 @@ emd_update_multi_kernel(EmdWs w, int* assignment, int n, int gen) {
     const int d = __hip_atomic_fetch_add(done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (d == G * (gen + 1) - 1) {
       w.unass_cnt[b] = __hip_atomic_load(newc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if constexpr (sizeof...(TA) > 0) emd_tail_note(b, w.unass_cnt[b], ta...);
       __hip_atomic_store(newc, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
@@ -730,6 +777,253 @@ emd_bid_kernel(EmdWs w, const float* __restrict__ xyz1, const float* __restrict_
   }
 }
 
+// The tail of a long auction in ONE launch (ct_emd_fwd_tail).  After a few hundred iterations a cloud has a handful of bidders
+// left and never more again (a round takes W winners off the list and adds at most one evicted owner per winner), yet every
+// iteration still costs two or three grid launches.  Here one 1024-thread workgroup per cloud takes a cloud whose list holds at
+// most u_tail entries and runs ALL its remaining iterations — the forced last one and CalcDist included — then marks the cloud
+// finished (fin[b] = 1, list length 0: the bid launches that follow return at their first test, the update launches at fin).
+// With more bidders it returns without touching anything.  No workgroup waits for another; the loop is bounded by iters.
+//   * a thread keeps its R = ceil(n / 1024) targets {x, y, z, price, owner} in registers for the whole launch (target k belongs to
+//     thread k % 1024, register k / 1024): an iteration reads no target from memory and a price is updated by its owner thread;
+//   * the list lives in LDS as {x, y, z, bidder} per slot; bids, increments and winners are LDS tables indexed by slot;
+//   * Bid: NB bidders at a time, every thread scanning its R targets in ascending order for each (strict '>': the lowest index),
+//     wave butterflies (merge_top2), one barrier, and ONE wave merging the 16 wave results of the batch while the others scan
+//     the next batch (two buffers);
+//   * GetMax: a slot's thread walks the slot tables for the bids on its target: their maximum, the +-1e-6 window in double, the
+//     highest bidder index among the slots inside it;
+//   * Assign: every thread walks the winners; the owner thread of a won target swaps the owner, adds the increment and puts the
+//     evicted owner into the winner's slot.  Only a winner of a free target leaves a hole; the list is compacted when there is one.
+// Every operation is that of emd_bid_kernel / emd_update_kernel and each is order-free (see there), so the result is theirs bit
+// for bit.  Global memory inside the loop: relaxed agent-scope stores of won assignments (read back after the loop with
+// ld_coherent, as emd_update_kernel does) and plain loads of xyz1, which no kernel writes.  Prices go back when the workgroup leaves
+// (the forced iteration's price additions, which nothing reads, are not made).
+constexpr int kTailCap = 2048;          // list slots in LDS: u_tail is clamped to it
+template <int R>
+__global__ void __launch_bounds__(1024)
+emd_tail_kernel(EmdWs w, int* assignment, const float* __restrict__ xyz1, const float* __restrict__ xyz2, float* dist,
+                int* fin, int* info, int n, float eps, int it0, int iters, int u_tail, int ragged) {
+  constexpr int NB = R >= 16 ? 1 : 4;                     // bidders per batch (R = 16: 64 registers hold the targets)
+  __shared__ float4 s_pt[kTailCap];                       // the list: {x, y, z, bidder index}
+  __shared__ int s_bt[kTailCap];                          // the slot's bid: target ...
+  __shared__ float s_inc[kTailCap];                       // ... and increment
+  __shared__ int s_wt[kTailCap];                          // the target again if the slot wins it, else -1
+  __shared__ unsigned char s_q[kTailCap], s_keep[kTailCap];   // inside GetMax's window | stays in the list
+  __shared__ float s_rb[2][NB][16], s_r2[2][NB][16];
+  __shared__ int s_ri[2][NB][16];
+  __shared__ int s_new, s_holes;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (fin[b]) return;
+  int U = w.unass_cnt[b];                                 // block-uniform from here to the end
+  if (U > u_tail || U > kTailCap) return;
+  const size_t off = (size_t)b * n;
+  const int c = ragged ? emd_extent(w, b) : n;            // targets of this cloud, c <= n <= 1024 * R
+  int* ass = assignment + off;
+  float tx[R], ty[R], tz[R], tp[R];
+  constexpr bool kInvReg = R < 16;                        // R = 16: the owners stay in the workspace, touched by the owner thread alone
+  int tinv[kInvReg ? R : 1];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int k = r * 1024 + tid;
+    if (k < c) {
+      const float* p = xyz2 + (off + k) * 3;
+      tx[r] = p[0]; ty[r] = p[1]; tz[r] = p[2];
+      tp[r] = w.price[off + k];
+      if (kInvReg) tinv[r] = w.ass_inv[off + k];
+    } else {                                              // the bid kernel's sentinel: never best, never second best
+      tx[r] = 0.0f; ty[r] = 0.0f; tz[r] = 0.0f;
+      tp[r] = __builtin_inff();
+      if (kInvReg) tinv[r] = -1;
+    }
+  }
+  for (int s = tid; s < U; s += 1024) {
+    const int j = w.unass_idx[off + s];
+    const float* p = xyz1 + (off + j) * 3;
+    s_pt[s] = make_float4(p[0], p[1], p[2], __int_as_float(j));
+  }
+  if (tid == 0) { s_new = 0; s_holes = 0; }
+  __syncthreads();
+  int batch = 0;
+  for (int it = it0; it < iters; ++it) {
+    if (U == 0) {                                         // nothing bids any more: the auction is over
+      if (tid == 0 && info[2 * b] == iters) info[2 * b] = it;
+      break;
+    }
+    const bool last = it == iters - 1;
+    if (last && tid == 0) info[2 * b + 1] = U;
+    // Bid
+    for (int s0 = 0; s0 < U; s0 += NB, ++batch) {
+      const int buf = batch & 1;
+      float4 q[NB];
+      Top2 t2[NB];
+#pragma unroll
+      for (int e = 0; e < NB; ++e) {
+        q[e] = s_pt[min(s0 + e, U - 1)];                  // (a short last batch scans the last bidder again; nothing is kept of it)
+        t2[e].best = -1e9f; t2[e].better = -1e9f; t2[e].idx = 0x7fffffff;
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        float pr = tp[r];
+        asm volatile("" : "+v"(pr));                      // (keeps the price's double out of a register pair held across batches)
+#pragma unroll
+        for (int e = 0; e < NB; ++e) {
+          const float x2 = tx[r] - q[e].x, y2 = ty[r] - q[e].y, z2 = tz[r] - q[e].z;
+          const float d2 = fmaf(z2, z2, fmaf(y2, y2, x2 * x2));
+          top2_push(t2[e], (float)(3.0 - (double)sqrtf(d2) - (double)pr), r);     // (the register's number: a literal, not R index registers)
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < NB; ++e) {
+        t2[e].idx = t2[e].idx == 0x7fffffff ? 0x7fffffff : t2[e].idx * 1024 + tid;
+        for (int m = 1; m < 64; m <<= 1) {
+          Top2 o;
+          o.best = __shfl_xor(t2[e].best, m, 64);
+          o.better = __shfl_xor(t2[e].better, m, 64);
+          o.idx = __shfl_xor(t2[e].idx, m, 64);
+          t2[e] = merge_top2(t2[e], o);
+        }
+        if (lane == 0) { s_rb[buf][e][wave] = t2[e].best; s_r2[buf][e][wave] = t2[e].better; s_ri[buf][e][wave] = t2[e].idx; }
+      }
+      __syncthreads();
+      if (wave == (batch & 15)) {                         // wave-uniform: this wave merges the batch, the others go on
+        const int e = min(lane >> 4, NB - 1), qd = lane & 15;
+        Top2 v = {s_rb[buf][e][qd], s_r2[buf][e][qd], s_ri[buf][e][qd]};
+        for (int m = 1; m < 16; m <<= 1) {
+          Top2 o;
+          o.best = __shfl_xor(v.best, m, 64);
+          o.better = __shfl_xor(v.better, m, 64);
+          o.idx = __shfl_xor(v.idx, m, 64);
+          v = merge_top2(v, o);
+        }
+        if (qd == 0 && (lane >> 4) < NB && s0 + e < U) {
+          s_bt[s0 + e] = min(v.idx, c - 1);               // (NaN coordinates leave no best target: stay inside the cloud; U > 0 => c > 0)
+          s_inc[s0 + e] = v.best - v.better + eps;
+        }
+      }
+    }
+    __syncthreads();
+    // GetMax: the slots tid and tid + 1024
+    constexpr int kSlots = kTailCap / 1024;
+    int mt[kSlots];
+    bool mq[kSlots];
+#pragma unroll
+    for (int u = 0; u < kSlots; ++u) {
+      const int s = u * 1024 + tid;
+      mt[u] = -1;
+      mq[u] = false;
+      if (s < U) {
+        const int t = s_bt[s];
+        const float bi = s_inc[s];
+        float mi = bi;
+        if (!last) {                                      // (the last iteration assigns every bidder: no maximum needed)
+          for (int o = 0; o < U; ++o)
+            if (s_bt[o] == t) mi = fmaxf(mi, s_inc[o]);
+        }
+        mt[u] = t;
+        mq[u] = (double)bi - 1e-6 <= (double)mi && (double)mi <= (double)bi + 1e-6;
+        s_q[s] = mq[u] ? 1 : 0;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < kSlots; ++u) {
+      const int s = u * 1024 + tid;
+      if (s < U) {
+        const int j = __float_as_int(s_pt[s].w);
+        bool win = last || mq[u];
+        if (!last && win) {
+          for (int o = 0; o < U; ++o)
+            if (s_bt[o] == mt[u] && s_q[o] && __float_as_int(s_pt[o].w) > j) win = false;
+        }
+        s_wt[s] = win ? mt[u] : -1;
+        s_keep[s] = win ? 0 : 1;
+        // the forced assignment of the last iteration: every bidder takes its bid
+        if (last) __hip_atomic_store(&ass[j], mt[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    if (last) break;
+    __syncthreads();
+    // Assign, by the owner thread of each won target (a target has one winner: the slots touched are disjoint)
+    for (int s = 0; s < U; ++s) {
+      const int t = s_wt[s];
+      if (t >= 0 && (t & 1023) == tid) {
+        const int r = t >> 10;
+        const int j = __float_as_int(s_pt[s].w);
+        const float inc = s_inc[s];
+        int prev = -1;
+#pragma unroll
+        for (int rr = 0; rr < R; ++rr) {
+          if (rr == r) {
+            if (kInvReg) { prev = tinv[rr]; tinv[rr] = j; }
+            tp[rr] += inc;
+          }
+        }
+        if (!kInvReg) { prev = w.ass_inv[off + t]; w.ass_inv[off + t] = j; }
+        __hip_atomic_store(&ass[j], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (prev != -1) {                                 // the evicted owner bids from the winner's slot
+          const float* p = xyz1 + (off + prev) * 3;
+          s_pt[s] = make_float4(p[0], p[1], p[2], __int_as_float(prev));
+          s_keep[s] = 1;
+        } else {
+          atomicAdd(&s_holes, 1);
+        }
+      }
+    }
+    __syncthreads();
+    const int holes = s_holes;
+    if (holes > 0) {                                      // block-uniform
+      float4 ent[kSlots];
+      bool keep[kSlots];
+#pragma unroll
+      for (int u = 0; u < kSlots; ++u) {
+        const int s = u * 1024 + tid;
+        keep[u] = s < U && s_keep[s] != 0;
+        ent[u] = keep[u] ? s_pt[s] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      }
+      __syncthreads();                                    // every kept entry is in registers: the list may be rewritten
+      const unsigned long long lt = lane ? (~0ull >> (64 - lane)) : 0ull;
+#pragma unroll
+      for (int u = 0; u < kSlots; ++u) {
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(keep[u]);
+        if (m == 0ull) continue;                          // wave-uniform
+        int base = 0;
+        if (lane == 0) base = atomicAdd(&s_new, __popcll(m));
+        base = __builtin_amdgcn_readfirstlane(base);
+        if (keep[u]) s_pt[base + __popcll(m & lt)] = ent[u];
+      }
+      __syncthreads();
+      U -= holes;
+      if (tid == 0) { s_new = 0; s_holes = 0; }           // (next read behind the barriers of the next iteration's Bid)
+    }
+  }
+  // leave: every store of an assignment has been performed before anybody reads one back
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __threadfence_block();
+  __syncthreads();
+  int tq = tid;
+  asm volatile("" : "+v"(tq));                            // (addresses formed here, not carried from the loads through the loop)
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int k = r * 1024 + tq;
+    if (k < c) {
+      w.price[off + k] = tp[r];
+      if (kInvReg) w.ass_inv[off + k] = tinv[r];
+    }
+  }
+  {
+    const float* p1 = xyz1 + off * 3;
+    const float* p2 = xyz2 + off * 3;
+    for (int j = tid; j < n; j += 1024) {
+      if (j >= c) { dist[off + j] = 0.0f; continue; }
+      const int k = ld_coherent(&ass[j]);
+      const float dx = p1[j * 3 + 0] - p2[k * 3 + 0];
+      const float dy = p1[j * 3 + 1] - p2[k * 3 + 1];
+      const float dz = p1[j * 3 + 2] - p2[k * 3 + 2];
+      dist[off + j] = dx * dx + dy * dy + dz * dz;
+    }
+  }
+  if (tid == 0) { w.unass_cnt[b] = 0; fin[b] = 1; }
+}
+
 // RAGGED: a row at or beyond its cloud's count gets +0.0 by a plain store — its g_dist (NaN, perhaps) and assignment are not read.
 template <bool RAGGED>
 __global__ void emd_grad_kernel(const float* xyz1, const float* xyz2, const float* g_dist, const int* assignment,
@@ -777,7 +1071,16 @@ EmdWs emd_carve(void* workspace, int B, int n) {
   w.sync = (int*)p;
   return w;
 }
-int g_emd_single_update = -1;         // test hook (ct_debug_set_emd; env CLOUDCT_EMD_SINGLE_UPDATE read once): the update on one workgroup per batch
+// ct_emd_fwd_tail's schedule (DESIGN.md §4.20 has the measurements behind the three numbers): a cloud enters the tail kernel with
+// at most kEmdTailU bidders; the first tail launch follows iteration kEmdTailFrom (the default of the entry's tail_from), then one
+// follows every kEmdTailEvery-th iteration.  kEmdTailU = 0 is what the crossover sweep gave on an MI355X: one workgroup runs an
+// iteration of 5 - 11 bidders in 21 us (n = 2048) where the ordinary launches take 11.5 us, and the gap only widens with more
+// bidders and larger clouds (one CU does the U * n evaluations that the bid launch spreads over the chip), so by default the tail
+// launch takes a cloud once its list is EMPTY — it writes the distances and the launches that follow skip the cloud — and the hook
+// (ct_debug_set_emd_tail) opens it to longer lists.  A tail launch that declines costs ~2 us: one every 64 iterations.
+constexpr int kEmdTailU = 0, kEmdTailEvery = 64, kEmdTailFrom = 64;
+int g_emd_tail_u = kEmdTailU, g_emd_tail_every = kEmdTailEvery;      // test hook: ct_debug_set_emd_tail
+int g_emd_single_update = -1;        // test hook (ct_debug_set_emd; env CLOUDCT_EMD_SINGLE_UPDATE read once): the update on one workgroup per batch
 
 }  // namespace
 
@@ -831,7 +1134,7 @@ int ct_emd_fwd(const float* xyz1, const float* xyz2, float* dist, int32_t* assig
                          0, 0x7fffffff);
     }
     if (multi_g > 1 && !last)
-      hipLaunchKernelGGL(emd_update_multi_kernel, dim3(multi_g, B), dim3(1024), 0, st, w, (int*)assignment, n, multi_gen++);
+      hipLaunchKernelGGL(emd_update_multi_kernel<>, dim3(multi_g, B), dim3(1024), 0, st, w, (int*)assignment, n, multi_gen++);
     else
       hipLaunchKernelGGL(emd_update_kernel<false>, dim3(B), dim3(1024), 0, st, w, (int*)assignment, xyz1, xyz2, dist, n,
                          1, last, last ? 0 : 1, last);
@@ -867,6 +1170,104 @@ int ct_emd_fwd_counts(const float* xyz1, const float* xyz2, const int32_t* count
 }
 
 void ct_debug_set_emd(unsigned flags) { g_emd_single_update = (flags & 1u) ? 1 : 0; }
+
+// ---- ct_emd_fwd_tail: the same auction, its long tail in one launch per cloud (emd_tail_kernel) ----
+int ct_emd_tail_supported(int B, int n) { return B >= 1 && B <= 512 && n >= 1 && n <= 16 * 1024; }
+
+size_t ct_emd_tail_workspace_bytes(int B, int n) {
+  if (B <= 0 || n <= 0) return 0;
+  return ct_emd_workspace_bytes(B, n) + align256((size_t)B * 4) + align256((size_t)B * 8);   // + fin [B] + info [B, 2]
+}
+
+void ct_debug_set_emd_tail(int u_tail, int every) {
+  g_emd_tail_u = u_tail < 0 ? kEmdTailU : (u_tail > kTailCap ? kTailCap : u_tail);
+  g_emd_tail_every = every <= 0 ? kEmdTailEvery : every;
+}
+
+// Launches depend on (B, n, iters, tail_from, count == NULL) and the hook alone, never on the clouds: capturable.  The ordinary
+// iterations are those of ct_emd_fwd (dense: count NULL and n % 1024 == 0) or ct_emd_fwd_counts, their update launches in the
+// TAIL instantiation; after iteration tail_from, and after every g_emd_tail_every-th one from there, one tail launch.
+int ct_emd_fwd_tail(const float* xyz1, const float* xyz2, const int32_t* count, float* dist, int32_t* assignment, int32_t* info,
+                    void* workspace, size_t workspace_bytes, int B, int n, float eps, int iters, int tail_from, ct_stream_t s) {
+  if (!xyz1 || !xyz2 || !dist || !assignment || !workspace || B <= 0 || n <= 0 || iters < 1) return CT_EINVAL;
+  if (B > 512) return CT_EPRECOND;
+  if (!ct_emd_tail_supported(B, n)) return CT_EINVAL;
+  if (workspace_bytes < ct_emd_tail_workspace_bytes(B, n)) return CT_EWORKSPACE;
+  hipStream_t st = (hipStream_t)s;
+  const EmdWs w = emd_carve(workspace, B, n);
+  int* fin = (int*)((char*)workspace + ct_emd_workspace_bytes(B, n));
+  int* inf = info ? (int*)info : (int*)((char*)fin + align256((size_t)B * 4));
+  const size_t total = (size_t)B * n;
+  const bool ragged = count != nullptr || n % 1024 != 0;
+  if (tail_from < 0) tail_from = kEmdTailFrom;
+  const int u_tail = g_emd_tail_u, every = g_emd_tail_every;
+  CT_CLEAR_ERROR();
+  auto tail = [&](int it0) {
+    const dim3 g(B), t(1024);
+#define CT_EMD_TAIL_LAUNCH(R) \
+    hipLaunchKernelGGL(emd_tail_kernel<R>, g, t, 0, st, w, (int*)assignment, xyz1, xyz2, dist, fin, inf, n, eps, it0, iters, u_tail, ragged ? 1 : 0)
+    if (n <= 1024) CT_EMD_TAIL_LAUNCH(1);
+    else if (n <= 2048) CT_EMD_TAIL_LAUNCH(2);
+    else if (n <= 4096) CT_EMD_TAIL_LAUNCH(4);
+    else if (n <= 8192) CT_EMD_TAIL_LAUNCH(8);
+    else CT_EMD_TAIL_LAUNCH(16);
+#undef CT_EMD_TAIL_LAUNCH
+  };
+  auto tail_after = [&](int it) { return it < iters - 1 && it >= tail_from && (it - tail_from) % every == 0; };
+  if (ragged) {
+    hipLaunchKernelGGL(emd_init_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w, (int*)assignment, total, B,
+                       (const int*)count, n);
+    hipLaunchKernelGGL((emd_update_kernel<true, EmdTailArg>), dim3(B), dim3(1024), 0, st, w, (int*)assignment, xyz1, xyz2, dist, n, 0, 0, 1, 0,
+                       (EmdTailArg{fin, inf, -1, iters}));
+    const dim3 bid_grid((unsigned)(((size_t)n + 63) / 64), B);
+    for (int it = 0; it < iters; ++it) {
+      const int last = it == iters - 1;
+      hipLaunchKernelGGL((emd_bid_kernel<kTile, 4, true>), bid_grid, dim3(kBidThreads), 2 * kTile * sizeof(float4), st, w, xyz1, xyz2, n, eps,
+                         0, 0x7fffffff);
+      hipLaunchKernelGGL((emd_update_kernel<true, EmdTailArg>), dim3(B), dim3(1024), 0, st, w, (int*)assignment, xyz1, xyz2, dist, n,
+                         1, last, last ? 0 : 1, last, (EmdTailArg{fin, inf, it, iters}));
+      if (tail_after(it)) tail(it + 1);
+    }
+    CT_CHECK_LAUNCH();
+    return CT_OK;
+  }
+  hipLaunchKernelGGL(emd_init_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w, (int*)assignment, total, 3 * B,
+                     (const int*)nullptr, n);
+  hipLaunchKernelGGL((emd_update_kernel<false, EmdTailArg>), dim3(B), dim3(1024), 0, st, w, (int*)assignment, xyz1, xyz2, dist, n, 0, 0, 1, 0,
+                     (EmdTailArg{fin, inf, -1, iters}));
+  const dim3 bid_grid(n / 64, B);
+  constexpr int kBigTile = 4096;
+  const bool big_ok = n % kBigTile == 0 && n >= 2 * kBigTile &&
+                      hipFuncSetAttribute((const void*)emd_bid_kernel<kBigTile, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          2 * kBigTile * (int)sizeof(float4)) == hipSuccess;
+  int multi_g = (n + 1024 * kMultiR - 1) / (1024 * kMultiR), multi_gen = 0;
+  if (g_emd_single_update < 0) {
+    const char* e = getenv("CLOUDCT_EMD_SINGLE_UPDATE");
+    g_emd_single_update = (e && atoi(e) != 0) ? 1 : 0;
+  }
+  if (multi_g > 16 || (long long)B * multi_g > emd_cu_count() || g_emd_single_update) multi_g = 1;
+  for (int it = 0; it < iters; ++it) {
+    const int last = it == iters - 1;
+    if (big_ok && it >= kEmdBigFrom) {
+      hipLaunchKernelGGL((emd_bid_kernel<kBigTile, 2, false>), dim3(n / 128, B), dim3(kBidThreads), 2 * kBigTile * sizeof(float4), st, w, xyz1, xyz2, n, eps,
+                         0, kEmdBigMaxU);
+      hipLaunchKernelGGL((emd_bid_kernel<kTile, 4, false>), bid_grid, dim3(kBidThreads), 2 * kTile * sizeof(float4), st, w, xyz1, xyz2, n, eps,
+                         kEmdBigMaxU + 1, 0x7fffffff);
+    } else {
+      hipLaunchKernelGGL((emd_bid_kernel<kTile, 4, false>), bid_grid, dim3(kBidThreads), 2 * kTile * sizeof(float4), st, w, xyz1, xyz2, n, eps,
+                         0, 0x7fffffff);
+    }
+    if (multi_g > 1 && !last)
+      hipLaunchKernelGGL(emd_update_multi_kernel<EmdTailArg>, dim3(multi_g, B), dim3(1024), 0, st, w, (int*)assignment, n, multi_gen++,
+                         (EmdTailArg{fin, inf, it, iters}));
+    else
+      hipLaunchKernelGGL((emd_update_kernel<false, EmdTailArg>), dim3(B), dim3(1024), 0, st, w, (int*)assignment, xyz1, xyz2, dist, n,
+                         1, last, last ? 0 : 1, last, (EmdTailArg{fin, inf, it, iters}));
+    if (tail_after(it)) tail(it + 1);
+  }
+  CT_CHECK_LAUNCH();
+  return CT_OK;
+}
 
 int ct_emd_bwd(const float* xyz1, const float* xyz2, const float* g_dist, const int32_t* assignment,
                float* g_xyz1, int B, int n, ct_stream_t s) {

@@ -134,21 +134,76 @@ def emd_with_counts(xyz1, xyz2, eps, iters, count=None):
     return EmdWithCountsFunction.apply(xyz1, xyz2, eps, iters, count)
 
 
-def emd_distance(xyz1, xyz2, eps, iters, count=None):
+class EmdWithInfoFunction(Function):
+    """The same auction through ct_emd_fwd_tail: a cloud whose bidder list has become short enough (by default: empty — the
+    measured crossover) is finished by one workgroup in one launch, and `info` int32 [B, 2] says what
+    the auction came to: info[b, 0] the first iteration that began without a bidder (iters: none did), info[b, 1] the bidders
+    the last iteration force-assigned (0 exactly when the auction finished).  dist and assignment are those of
+    emdFunction / EmdWithCountsFunction bit for bit, and so is the gradient."""
+
+    @staticmethod
+    def forward(ctx, xyz1, xyz2, eps, iters, count, tail_from):
+        batchsize, n, _ = xyz1.size()
+        _, m, _ = xyz2.size()
+        assert n == m
+        assert xyz1.size()[0] == xyz2.size()[0]
+        assert batchsize <= 512
+        lib = _lib.load()
+        if not lib.ct_emd_tail_supported(batchsize, n):
+            raise ValueError("emd_with_info: B = %d, n = %d is not a shape of ct_emd_fwd_tail (B <= 512, n <= 16384)" % (batchsize, n))
+        count = _count_arg(count, batchsize, n, xyz1.device)
+        _dev(xyz1, xyz2, count)
+        xyz1 = xyz1.contiguous().float()
+        xyz2 = xyz2.contiguous().float()
+        dev = xyz1.device
+        dist = torch.empty(batchsize, n, device=dev, dtype=torch.float32)
+        assignment = torch.empty(batchsize, n, device=dev, dtype=torch.int32)
+        info = torch.empty(batchsize, 2, device=dev, dtype=torch.int32)
+        nws = lib.ct_emd_tail_workspace_bytes(batchsize, n)
+        ws = torch.empty(nws, device=dev, dtype=torch.uint8)
+        with _on(dev):
+            _lib.check(lib.ct_emd_fwd_tail(_ptr(xyz1), _ptr(xyz2), _ptr(count), _ptr(dist), _ptr(assignment), _ptr(info), _ptr(ws), nws,
+                                           batchsize, n, float(eps), int(iters), -1 if tail_from is None else int(tail_from),
+                                           _stream()), "ct_emd_fwd_tail")
+        ctx.save_for_backward(xyz1, xyz2, assignment)
+        ctx.count, ctx.dense = count, count is None and n % 1024 == 0
+        ctx.mark_non_differentiable(assignment, info)
+        return dist, assignment, info
+
+    @staticmethod
+    def backward(ctx, graddist, gradidx, gradinfo):
+        return EmdWithCountsFunction.backward(ctx, graddist, gradidx) + (None,)
+
+
+def emd_with_info(xyz1, xyz2, eps, iters, count=None, tail_from=None):
+    """(dist [B,n], assignment [B,n] int32, info [B,2] int32) — see EmdWithInfoFunction.  count: int32 [B] device tensor or None;
+    tail_from: the iteration after which the first tail launch is enqueued (None: the library's default).  Raises ValueError
+    where ct_emd_tail_supported declines the shape."""
+    return EmdWithInfoFunction.apply(xyz1, xyz2, eps, iters, count, tail_from)
+
+
+def emd_tail_supported(B, n):
+    return bool(_lib.load().ct_emd_tail_supported(int(B), int(n)))
+
+
+def emd_distance(xyz1, xyz2, eps, iters, count=None, tail=False):
     """The EMD call of the training loops: emdFunction — its preconditions, bits and speed — where it applies (no count, n a
-    multiple of 1024), EmdWithCountsFunction otherwise."""
+    multiple of 1024), EmdWithCountsFunction otherwise.  tail=True: the same (dist, assignment) through emd_with_info where
+    its shape is supported; the default is the call described above, launch for launch."""
+    if tail and emd_tail_supported(xyz1.size(0), xyz1.size(1)):
+        return emd_with_info(xyz1, xyz2, eps, iters, count)[:2]
     if count is None and xyz1.size(1) % 1024 == 0:
         return emdFunction.apply(xyz1, xyz2, eps, iters)
     return EmdWithCountsFunction.apply(xyz1, xyz2, eps, iters, count)
 
 
-def loss_emd_counts(pc_1, pc_2, eps, iters, count=None):
+def loss_emd_counts(pc_1, pc_2, eps, iters, count=None, tail=False):
     """The EMD loss of train_inpainter.py:189 for clouds [B, 3, 1, N] of different lengths: per cloud, the mean of sqrt(dist)
     over its count[b] rows; then the mean over the batch.  A count of None stands for every row.  The rows at or beyond a
     count are masked BEFORE the root (the root's derivative at their stored 0 is inf, and inf * 0 = NaN).  (A cloud with a
-    zero count has no mean: its term, and the loss, is NaN, as torch's mean of nothing.)"""
+    zero count has no mean: its term, and the loss, is NaN, as torch's mean of nothing.)  tail: as in emd_distance."""
     from .chamfer import _to_bn3
-    dist, _ = emd_distance(_to_bn3(pc_1), _to_bn3(pc_2), eps, iters, count)
+    dist, _ = emd_distance(_to_bn3(pc_1), _to_bn3(pc_2), eps, iters, count, tail=tail)
     if count is None:
         return torch.sqrt(dist).mean(1).mean()
     n = dist.size(1)

@@ -468,15 +468,30 @@ class Trainer:
         from .metrics import sphere_noise
         return sphere_noise(pcd_gt.shape[0], pcd_gt.shape[-1] if n_noise is None else n_noise, pcd_gt.device, generator=self._noise_gen)
 
-    def _reconstruct(self, img, pcd_gt, eps, iters, n_noise=None, noise=None):
+    def _val_emd(self, rec_bn3, gt_bn3, eps, iters):
+        """The validation EMD of a batch -> (dist [B, n], stats).  `train.val_emd_tail` (default false): the auction through
+        emd_with_info where its shape is supported — the same dist, a cloud's long tail in one launch — and stats = float64
+        [sum of info[:, 0], clouds whose auction did not finish, clouds] on the device; otherwise today's call and stats None."""
+        from .emd import emd_distance, emd_tail_supported, emd_with_info
+        if bool(self.cfg["train"].get("val_emd_tail", False)) and emd_tail_supported(rec_bn3.size(0), rec_bn3.size(1)):
+            dist, _, info = emd_with_info(rec_bn3, gt_bn3, eps, iters)
+            clouds = torch.full((), float(info.size(0)), dtype=torch.float64, device=info.device)
+            return dist, torch.stack([info[:, 0].sum().double(), (info[:, 1] > 0).sum().double(), clouds])
+        return emd_distance(rec_bn3, gt_bn3, eps, iters)[0], None
+
+    def _reconstruct(self, img, pcd_gt, eps, iters, n_noise=None, noise=None, val=False):
         """(sqrt-EMD loss, rec [B, 3, 1, N], gt [B, 3, 1, n]) of train_image_reconstruction.py:166-175 for a device batch.
-        `noise`: the sphere noise to use (a graph's static buffer, filled from an eager draw); by default it is drawn here."""
+        `noise`: the sphere noise to use (a graph's static buffer, filled from an eager draw); by default it is drawn here.
+        `val`: the validation call — the EMD through `_val_emd`, whose stats come fourth."""
         from .emd import emd_distance
         gt = pcd_gt[:, :, None]
         if noise is None:
             noise = self._draw_noise(pcd_gt, n_noise)
         out = self.model(noise, img)
         rec = out[0] if isinstance(out, (tuple, list)) else out
+        if val:
+            dist, stats = self._val_emd(rec[:, :, 0].permute(0, 2, 1), gt[:, :, 0].permute(0, 2, 1), eps, iters)
+            return torch.sqrt(dist).mean(1).mean(), rec, gt, stats
         dist, _ = emd_distance(rec[:, :, 0].permute(0, 2, 1), gt[:, :, 0].permute(0, 2, 1), eps, iters)
         return torch.sqrt(dist).mean(1).mean(), rec, gt
 
@@ -541,13 +556,13 @@ class Trainer:
         """One validation batch of this task: the eval-mode forward plus the task's validation loss terms, device tensors in,
         device tensors out (the caller holds eval mode and no_grad; the meters stay with the caller).
         reconstruction (img, cloud, noise) -> (loss_emd, loss_chamfer); completion (noise, partial, gt) -> (loss_emd,
-        loss_chamfer); segmentation_blocks (points, labels) -> (pred, loss); classification_scanobjectnn (points, label, mask)
+        loss_chamfer) — both with the stats of `_val_emd` third under `train.val_emd_tail`; segmentation_blocks (points, labels) -> (pred, loss); classification_scanobjectnn (points, label, mask)
         -> (loss, loss_cls, loss_seg, logits, mask logits); segmentation_kpconv (points, mask, features, labels) -> (pred, loss)."""
         tr = self.cfg["train"]
         if self.task == "reconstruction":
             from .chamfer import loss_chamfer_adj
-            l_emd, rec, gt = self._reconstruct(t[0], t[1], float(tr["val_emd_eps"]), int(tr["val_emd_iters"]), noise=t[2])
-            return l_emd, loss_chamfer_adj(rec, gt)
+            l_emd, rec, gt, stats = self._reconstruct(t[0], t[1], float(tr["val_emd_eps"]), int(tr["val_emd_iters"]), noise=t[2], val=True)
+            return (l_emd, loss_chamfer_adj(rec, gt)) + (() if stats is None else (stats,))
         if self.task == "completion":
             from .chamfer import loss_chamfer
             from .emd import emd_distance
@@ -555,9 +570,9 @@ class Trainer:
             out = self.model(noise, part.permute(0, 2, 1)[:, :, None])
             rec = out[0] if isinstance(out, (tuple, list)) else out
             gt4 = gt.permute(0, 2, 1)[:, :, None]
-            dist, _ = emd_distance(rec[:, :, 0].permute(0, 2, 1), gt4[:, :, 0].permute(0, 2, 1),
-                                   float(tr.get("val_emd_eps", 0.004)), int(tr.get("val_emd_iters", 3000)))
-            return torch.sqrt(dist).mean(1).mean(), loss_chamfer(rec, gt4)
+            dist, stats = self._val_emd(rec[:, :, 0].permute(0, 2, 1), gt4[:, :, 0].permute(0, 2, 1),
+                                        float(tr.get("val_emd_eps", 0.004)), int(tr.get("val_emd_iters", 3000)))
+            return (torch.sqrt(dist).mean(1).mean(), loss_chamfer(rec, gt4)) + (() if stats is None else (stats,))
         if self.task == "segmentation_blocks":
             pred = self._block_pred(t[0])
             return pred, self.ce(pred[:, :, 0], t[1])
@@ -587,6 +602,15 @@ class Trainer:
             self._val_graph = GraphedForward(parallel._plain_module(self.model), fn=self._val_step, fallback=True, verbose=self.rank == 0)
         return self._val_graph
 
+    def _tail_record(self, rec, tail):
+        """`train.val_emd_tail`: the validation record also says how the auctions ended — the mean over the clouds of the first
+        iteration without a bidder (`val_emd_iters` where there was none) and the clouds whose auction did not finish."""
+        if bool(self.cfg["train"].get("val_emd_tail", False)):
+            t = tail.tolist()
+            if t[2] > 0:
+                rec["emd_first_empty_mean"] = t[0] / t[2]
+                rec["emd_unfinished"] = int(t[1])
+
     def _validate_completion(self, epoch, dataset=None, hip_graph=None):
         """train_inpainter.py:253-311: eval mode, no grad, the VAL subset in batches of `data.batch_size_val`; per batch
         sqrt(EMD(rec, gt, val_emd_eps, val_emd_iters)).mean(1).mean() and loss_chamfer, averaged over the batches and the
@@ -610,17 +634,22 @@ class Trainer:
         self.val_loader.set_epoch(epoch if isinstance(epoch, int) else 0)
         step = self._val_runner(hip_graph)
         sums = torch.zeros(4, dtype=torch.float64, device=self.device)            # loss, loss_emd, loss_chamfer, batches
+        tail = torch.zeros(3, dtype=torch.float64, device=self.device)            # `train.val_emd_tail`: see _val_emd
         with torch.no_grad():
             for noise, part, gt in self.val_loader:
-                l_emd, l_cd = step(noise, part, gt)
+                l_emd, l_cd, *stats = step(noise, part, gt)
                 sums += torch.stack([l_emd + w * l_cd, l_emd, l_cd, torch.ones_like(l_cd)]).double()
+                if stats:
+                    tail += stats[0]
         model.train(was_training)
         if parallel._active(self.dist):
             self.dist.all_reduce(sums)
+            self.dist.all_reduce(tail)
         s = sums.tolist()
         n = max(s[3], 1.0)
         rec = {"epoch": epoch, "iters": self.iters, "batches": int(s[3]), "loss": s[0] / n, "loss_emd": s[1] / n,
                "loss_chamfer": s[2] / n}
+        self._tail_record(rec, tail)
         best = self.best_val is None or rec["loss"] < self.best_val
         rec["best"] = bool(best)
         if best:
@@ -652,16 +681,21 @@ class Trainer:
         self.val_loader.set_epoch(epoch if isinstance(epoch, int) else 0)
         step = self._val_runner(hip_graph)
         sums = torch.zeros(3, dtype=torch.float64, device=self.device)            # loss_emd, loss_chamfer, batches
+        tail = torch.zeros(3, dtype=torch.float64, device=self.device)            # `train.val_emd_tail`: see _val_emd
         with torch.no_grad():
             for img, pcd in self.val_loader:
-                l_emd, l_cd = step(img, pcd, self._draw_noise(pcd))            # (the noise: one eager draw per batch, as ever)
+                l_emd, l_cd, *stats = step(img, pcd, self._draw_noise(pcd))    # (the noise: one eager draw per batch, as ever)
                 sums += torch.stack([l_emd, l_cd, torch.ones_like(l_cd)]).double()
+                if stats:
+                    tail += stats[0]
         model.train(was_training)
         if parallel._active(self.dist):
             self.dist.all_reduce(sums)
+            self.dist.all_reduce(tail)
         s = sums.tolist()
         n = max(s[2], 1.0)
         rec = {"epoch": epoch, "iters": self.iters, "batches": int(s[2]), "loss_emd": s[0] / n, "loss_chamfer": s[1] / n}
+        self._tail_record(rec, tail)
         best = self.best_val is None or rec["loss_emd"] < self.best_val
         rec["best"] = bool(best)
         if best:

@@ -782,6 +782,38 @@ int ct_emd_bwd_counts(const float* xyz1, const float* xyz2, const int32_t* count
                       const int32_t* assignment, float* g_xyz1, int B, int n, ct_stream_t s);
 
 /* ------------------------------------------------------------------------
+ * Long auctions: the tail in one launch per cloud, and what the auction came to.  Added under CT_ABI_VERSION 3 (additive
+ * symbols); the four entries above keep their results, their launches and their workspace size.
+ *
+ * ct_emd_fwd_tail computes what ct_emd_fwd (count null and n % 1024 == 0) or ct_emd_fwd_counts (otherwise) computes, bit for
+ * bit, with another schedule: the ordinary iterations are enqueued as there; after iteration tail_from (0-based; negative = the
+ * library's default) and after every few iterations from then on, one launch gives each cloud whose bidder list has become short
+ * to ONE workgroup, which runs all remaining iterations of that cloud, the forced last one and the distances included; the
+ * launches that follow skip such a cloud.  tail_from >= iters - 1 enqueues the ordinary iterations alone.  No host
+ * synchronisation; the launches depend on (B, n, iters, tail_from, count == null) only, so a captured graph replays with other
+ * clouds and other counts in the same buffers.
+ *
+ * info, i32[B,2] in device memory or null, is written on the device: info[b,0] = the index of the first iteration at whose start
+ * cloud b had no bidder left, or iters if there was none; info[b,1] = the number of bidders of the last iteration, which it
+ * force-assigns — 0 exactly when the auction finished.  A cloud without rows has {0, 0}.
+ *
+ * ct_emd_tail_supported(B, n): 1 where ct_emd_fwd_tail takes the shape (1 <= B <= 512, 1 <= n <= 16384), else 0.
+ * ct_emd_tail_workspace_bytes(B, n): its workspace (that of ct_emd_workspace_bytes and the per-cloud state); 0 for B or n <= 0.
+ * CT_EINVAL for a null required pointer (everything but count and info), B <= 0, n <= 0, iters < 1 or a shape the query
+ * declines; CT_EPRECOND for B > 512; CT_EWORKSPACE for a short workspace — all before any launch.  ct_emd_bwd /
+ * ct_emd_bwd_counts serve this forward as they are.  The deterministic switch neither changes nor refuses it.
+ * ct_debug_set_emd_tail(u_tail, every): test hook — the longest list the tail launch takes (at most 2048; negative = default)
+ * and the number of iterations between two tail launches (<= 0 = default).  The defaults come from a measurement (DESIGN.md
+ * §4.20): on an MI355X one workgroup does not run an iteration faster than the ordinary launches at any bidder count, so by
+ * default the tail launch takes a cloud only once its list is empty (it writes the distances; later launches skip the cloud).
+ * ---------------------------------------------------------------------- */
+int ct_emd_tail_supported(int B, int n);
+size_t ct_emd_tail_workspace_bytes(int B, int n);
+int ct_emd_fwd_tail(const float* xyz1, const float* xyz2, const int32_t* count, float* dist, int32_t* assignment, int32_t* info,
+                    void* workspace, size_t workspace_bytes, int B, int n, float eps, int iters, int tail_from, ct_stream_t s);
+void ct_debug_set_emd_tail(int u_tail, int every);
+
+/* ------------------------------------------------------------------------
  * Pointwise (kernel size 1) convolutions of the MHCT blocks and their gradients
  * (layers/multihead_ct.py:31-33,62-66,89-91: nn.Conv1d(Ci, Co, 1) on [B,Ci,N]), fp32 in /
  * fp32 out on the f16 matrix pipes: operands are scaled by a per-tensor power of two

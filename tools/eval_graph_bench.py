@@ -9,6 +9,7 @@ their initial values): segmenter B8 N4096, classifier B8 N2048, segmenter_pad B6
 reconstructor (ResNet-50 encoder, twelve AdaIN blocks) B4 N8192 at 128^2.  The steps are the harness's own: a `harness.Trainer`
 without its data side (`bare_trainer`) runs `_eager_step` / `_graph_step` for (a) and `_val_step`, eagerly or through
 `_val_runner(True)` (graphs.GraphedForward), for (b); the two EMD tasks at `val_emd_iters` 3000 (the protocol) and 50.
+A row name with `_tail` appended (not in the default list) runs that EMD row with `train.val_emd_tail` on.
 
 Timing: device events around a window of steps — as many as fill `--window-ms` at the eager step's warmed-up time, at least
 `--iters`, the same count for both paths; eager and graphed windows alternate in one process after a warm-up of both (the
@@ -207,7 +208,9 @@ def window(fn, iters):
 
 def row(name, windows, iters, window_ms):
     import torch
-    emd = {"val_emd_eps": 0.004, "val_emd_iters": int(name.rsplit("_", 1)[1])} if name[-1].isdigit() else {}
+    tail = name.endswith("_tail")                    # `train.val_emd_tail` on (§4.20): val_completion_3000_tail, val_reconstruction_3000_tail
+    name = name[:-len("_tail")] if tail else name
+    emd = {"val_emd_eps": 0.004, "val_emd_iters": int(name.rsplit("_", 1)[1]), "val_emd_tail": tail} if name[-1].isdigit() else {}
     if name == "train_reconstruction":
         net, args = build("reconstructor")
         tr = bare_trainer("reconstruction", net, {"emd_eps": 0.005, "emd_iters": 50})
@@ -244,7 +247,7 @@ def row(name, windows, iters, window_ms):
     for _ in range(windows):
         got["eager"].append(window(eager, iters))
         got["graphed"].append(window(graphed, iters))
-    print(json.dumps({"row": name, "steps": iters, **{k: [round(x, 3) for x in v] for k, v in got.items()}}), flush=True)
+    print(json.dumps({"row": name + ("_tail" if tail else ""), "steps": iters, **{k: [round(x, 3) for x in v] for k, v in got.items()}}), flush=True)
 
 
 def summary(values):
