@@ -57,15 +57,27 @@ def forward_style(module_list, input, z, residual=None):
     return input if residual is None else residual + input
 
 
+# the entry points of each composition by ops.norm_route's answer (looked up per call: tests swap them in place)
+def _single(mode):
+    return {"train": ops.bn_relu, "eval": ops.bn_eval, "frozen": ops.bn_frozen}[mode]
+
+
+def _split(mode):
+    return {"train": ops.split_bn, "eval": ops.split_bn_eval, "frozen": ops.split_bn_frozen}[mode]
+
+
+def _join(mode):
+    return {"train": ops.join_bn_relu, "eval": ops.join_bn_relu_eval, "frozen": ops.join_bn_relu_frozen}[mode]
+
+
 def run_after(module_list, input, residual=None):
-    """Apply an `after` Sequential (and add `residual` to its result); a training-mode nn.BatchNorm1d directly followed by
-    nn.ReLU runs as the fused ct_bn_relu kernels when the shape qualifies (ops.bn_relu_eligible), the skip connection
-    added in the same pass when that pair ends the stack (an nn.SyncBatchNorm too: ops exchanges the group's statistics
-    over its process group); the same pair in eval mode runs as ct_bn_eval_group_fwd where autograd records nothing
-    (ops.bn_eval_eligible), and a bias-free PointwiseConv1d in front of such a pair takes the pair into its GEMM's epilogue
-    (ops.pw_norm_eligible: ct_pw_gemm_rs_norm); an eval pair whose norm freeze_norms marked runs as ops.bn_frozen where
-    gradients are recorded (the projection in front of it through its own function) — an unmarked eval forward with
-    gradients and every other layer go through their own forward."""
+    """Apply an `after` Sequential (and add `residual` to its result).  An nn.BatchNorm1d / nn.SyncBatchNorm directly followed by
+    nn.ReLU runs on the fused kernels in the mode ops.norm_route gives — training: ct_bn_group_* (under SyncBatchNorm ops
+    exchanges the statistics over the norm's process group); eval where autograd records nothing: ct_bn_eval_group_fwd; a norm
+    freeze_norms marked, with gradients: the same forward launch and ct_bn_eval_group_bwd — with the skip connection added in
+    the same pass when that pair ends the stack.  A bias-free PointwiseConv1d in front of an eval pair takes the pair into its
+    GEMM's epilogue (ops.pw_norm_eligible: ct_pw_gemm_rs_norm).  An unmarked eval forward with gradients and every other layer
+    go through their own forward."""
     layers = list(module_list)
     i = 0
     while i < len(layers):
@@ -81,23 +93,12 @@ def run_after(module_list, input, residual=None):
                 i += 3
                 continue
         pair = i + 1 < len(layers) and type(layers[i + 1]) is nn.ReLU
-        fuse_res = (pair and i + 2 == len(layers) and residual is not None and residual.shape == input.shape
-                    and residual.dtype == input.dtype)
-        if pair and not layer.training and ops.bn_eval_eligible(layer, input, residual=residual if fuse_res else None):
-            input = ops.bn_eval(input, layer, relu=True, residual=residual if fuse_res else None)
-            if fuse_res:
-                residual = None
-            i += 2
-        elif (pair and not layer.training and ops.bn_frozen_eligible(layer, input, residual=residual if fuse_res else None)
-              and ops.records_gradients(input, layer.weight, layer.bias, residual if fuse_res else None)):
-            # a norm marked by freeze_norms, with gradients: the same forward launch and ct_bn_eval_group_bwd
-            input = ops.bn_frozen(input, layer, relu=True, residual=residual if fuse_res else None)
-            if fuse_res:
-                residual = None
-            i += 2
-        elif pair and ops.bn_relu_eligible(layer, input):
-            input = ops.bn_relu(input, layer, relu=True, residual=residual if fuse_res else None)
-            if fuse_res:
+        res = residual if (pair and i + 2 == len(layers) and residual is not None and residual.shape == input.shape
+                           and residual.dtype == input.dtype) else None
+        mode = ops.norm_route([(layer, input, None)], residual=res) if pair else None
+        if mode is not None:
+            input = _single(mode)(input, layer, relu=True, residual=res)
+            if res is not None:
                 residual = None
             i += 2
         else:
@@ -150,21 +151,13 @@ class _MHCTCore(nn.Module):
 
     def _norm_keys_values(self, key_values):
         """key_bn on the first 3H channels, values_bn on the rest (multihead_ct.py:89-91): fused kernels on the slices
-        where they lie when both norms qualify (training: ops.split_bn; eval without gradients: ops.split_bn_eval; frozen
-        with gradients: ops.split_bn_frozen), the modules on split views otherwise."""
+        where they lie in the mode ops.norm_route gives both norms (training: ops.split_bn; eval without gradients:
+        ops.split_bn_eval; frozen with gradients: ops.split_bn_frozen), the modules on split views otherwise."""
         Ck = self.heads * 3
         Cv = key_values.size(1) - Ck
-        if (ops.bn_relu_eligible(self.key_bn, key_values, Ck) and ops.bn_relu_eligible(self.values_bn, key_values, Cv)
-                and ops.norms_share_group([self.key_bn, self.values_bn])):
-            return ops.split_bn(key_values, self.key_bn, self.values_bn)
-        if (not self.key_bn.training and ops.bn_eval_eligible(self.key_bn, key_values, Ck)
-                and ops.bn_eval_eligible(self.values_bn, key_values, Cv)):
-            return ops.split_bn_eval(key_values, self.key_bn, self.values_bn)
-        if (not self.key_bn.training and not self.values_bn.training and ops.bn_frozen_eligible(self.key_bn, key_values, Ck)
-                and ops.bn_frozen_eligible(self.values_bn, key_values, Cv)
-                and ops.records_gradients(key_values, self.key_bn.weight, self.key_bn.bias, self.values_bn.weight,
-                                          self.values_bn.bias)):
-            return ops.split_bn_frozen(key_values, self.key_bn, self.values_bn)      # marked by freeze_norms, with gradients
+        mode = ops.norm_route([(self.key_bn, key_values, Ck), (self.values_bn, key_values, Cv)])
+        if mode is not None:
+            return _split(mode)(key_values, self.key_bn, self.values_bn)
         k_part, v_part = torch.split(key_values, [Ck, Cv], dim=1)   # backward: one cat
         return self.key_bn(k_part), self.values_bn(v_part)
 
@@ -479,12 +472,10 @@ class MultiHeadUnion(_UnionBase):
         un-normed) is normed into its channel range by one ct_bn_eval_group_fwd over just those heads; the maxima tag is then
         left off (that head's run of partials was never written)."""
         joined, amax = targets[0].y, targets[0].amax
-        B, Ct, N = joined.shape
         left = [(t, p) for t, p in zip(targets, pres) if t.out is None]
         if left:
             if all(ops.bn_eval_eligible(t.bn, p) for t, p in left):
-                ops._bn_eval_group([ops._bn_eval_item(t.bn, p.data_ptr(), 0, joined.data_ptr() + t.c0 * N * 4, Ct * N, True)
-                                    for t, p in left], B, N)
+                ops.bn_relu_eval_into(joined, [(t.bn, p, t.c0) for t, p in left])
             else:
                 for t, p in left:
                     joined[:, t.c0:t.c0 + p.size(1)].copy_(run_after(nn.Sequential(t.bn, nn.ReLU()), p))
@@ -498,25 +489,22 @@ class MultiHeadUnion(_UnionBase):
         # the heads share x: one stacked GEMM for their keys_values_pred projections (and for its gradients)
         convs = [a.keys_values_pred[0] for a in self.attentions]
         kbs, vbs = [a.key_bn for a in self.attentions], [a.values_bn for a in self.attentions]
-        if ops.union_keys_values_eligible(x, convs, kbs, vbs):
+        mode = ops.norm_route([(bn, x, bn.num_features) for kb, vb in zip(kbs, vbs) for bn in (kb, vb)],
+                              watch=[c.weight for c in convs], convs=convs)
+        if mode is None:
+            residual, kvs = self._shortcut(x), None
+        elif mode == "eval":                                              # nothing recorded: the same stacking, forward only
+            residual, kvs = self.shortcut(x), ops.union_keys_values_eval(x, convs, kbs, vbs)
+        else:
+            # training norms, or norms marked by freeze_norms with gradients (the training path's stacking on the stored statistics)
+            union = ops.union_keys_values if mode == "train" else ops.union_keys_values_frozen
             if SKIP_IN_DGRAD and len(self.shortcut) == 0 and x.requires_grad and torch.is_grad_enabled():
                 # identity shortcut: x leaves the projections' node as an output too, so the shortcut's cotangent is added in the
                 # data gradient's epilogue (ops.UnionKeysValuesFn) — autograd's own sum was a 31 us pass per block on the
                 # segmenter's critical path (profiles/r6_skip_in_dgrad.txt)
-                residual, kvs = ops.union_keys_values(x, convs, kbs, vbs, passthrough=True)
+                residual, kvs = union(x, convs, kbs, vbs, passthrough=True)
             else:
-                residual, kvs = self.shortcut(x), ops.union_keys_values(x, convs, kbs, vbs)
-        elif ops.union_keys_values_eval_eligible(x, convs, kbs, vbs):      # eval, nothing recorded: same stacking, forward only
-            residual, kvs = self.shortcut(x), ops.union_keys_values_eval(x, convs, kbs, vbs)
-        elif (not any(bn.training for bn in kbs + vbs) and ops.union_keys_values_frozen_eligible(x, convs, kbs, vbs)
-              and ops.records_gradients(x, *[c.weight for c in convs], *[p for bn in kbs + vbs for p in (bn.weight, bn.bias)])):
-            # norms marked by freeze_norms, with gradients: the training path's stacking on the stored statistics
-            if SKIP_IN_DGRAD and len(self.shortcut) == 0 and x.requires_grad and torch.is_grad_enabled():
-                residual, kvs = ops.union_keys_values_frozen(x, convs, kbs, vbs, passthrough=True)
-            else:
-                residual, kvs = self._shortcut(x), ops.union_keys_values_frozen(x, convs, kbs, vbs)
-        else:
-            residual, kvs = self._shortcut(x), None
+                residual, kvs = (self.shortcut if mode == "train" else self._shortcut)(x), union(x, convs, kbs, vbs)
         targets = self._slice_norm_targets(x) if ops.SLICE_NORM else None
         for r, s, _ in _run_heads([(lambda a=a, i=i: a._forward_pre(x, orig_pcd, None if kvs is None else kvs[i],
                                                                     target=None if targets is None else targets[i]))
@@ -526,17 +514,14 @@ class MultiHeadUnion(_UnionBase):
         if targets is not None:
             return run_after(self.after, self._slice_norm_join(targets, pres), residual), stats
         # the heads' BatchNorm + ReLU write straight into their channel ranges of the concatenation when they qualify
+        # (training: ops.join_bn_relu; eval, nothing recorded: ops.join_bn_relu_eval; marked by freeze_norms, with gradients:
+        #  ops.join_bn_relu_frozen)
         norms = [a.after for a in self.attentions]
-        if (len(pres) > 1 and all(len(n) == 2 and type(n[1]) is nn.ReLU and ops.bn_relu_eligible(n[0], p)
-                                  for n, p in zip(norms, pres)) and ops.norms_share_group([n[0] for n in norms])):
-            joined = ops.join_bn_relu(pres, [n[0] for n in norms])
-        elif len(pres) > 1 and all(len(n) == 2 and type(n[1]) is nn.ReLU and not n[0].training and ops.bn_eval_eligible(n[0], p)
-                                   for n, p in zip(norms, pres)):
-            joined = ops.join_bn_relu_eval(pres, [n[0] for n in norms])
-        elif (len(pres) > 1 and all(len(n) == 2 and type(n[1]) is nn.ReLU and not n[0].training and ops.bn_frozen_eligible(n[0], p)
-                                    for n, p in zip(norms, pres))
-              and ops.records_gradients(*pres, *[p for n in norms for p in (n[0].weight, n[0].bias)])):
-            joined = ops.join_bn_relu_frozen(pres, [n[0] for n in norms])      # marked by freeze_norms, with gradients
+        mode = None
+        if len(pres) > 1 and all(len(n) == 2 and type(n[1]) is nn.ReLU for n in norms):
+            mode = ops.norm_route([(n[0], p, None) for n, p in zip(norms, pres)])
+        if mode is not None:
+            joined = _join(mode)(pres, [n[0] for n in norms])
         else:
             joined = torch.cat([run_after(n, p) for n, p in zip(norms, pres)], dim=1)
         return run_after(self.after, joined, residual), stats

@@ -748,6 +748,27 @@ def _batch_stride(t, C, N):
     return None
 
 
+def _residual_arg(residual, C, N):
+    """(tensor, batch stride) of a residual the kernels read where it lies, else of its contiguous copy; (None, 0) without one."""
+    if residual is None:
+        return None, 0
+    rbs = _batch_stride(residual, C, N)
+    if rbs is None:
+        residual, rbs = _f32c(residual), 0
+    return residual, rbs
+
+
+def _cotangent(gy, B, C, N, device):
+    """(tensor, batch stride) of a cotangent the kernels can read where it lies, else of its contiguous copy (stride 0 = dense);
+    None -> zeros."""
+    if gy is None:
+        gy = torch.zeros(B, C, N, device=device, dtype=torch.float32)
+    gybs = _batch_stride(gy, C, N)
+    if gybs is None:
+        gy, gybs = _f32c(gy), 0
+    return gy, gybs
+
+
 class AdaInFn(torch.autograd.Function):
     """relu?(instance_norm(x) * (gamma + 1) + beta) [+ residual], gamma_beta [B,2,C] (layers/utils.py:88-97).  x may be a
     channel slice of a wider tensor (read where it lies), and so may the cotangent."""
@@ -763,11 +784,7 @@ class AdaInFn(torch.autograd.Function):
             x, xbs = x.contiguous(), 0
         assert gamma_beta.shape == (B, 2, C)
         gamma_beta, gbbs = _gb_arg(gamma_beta, B, C)
-        rbs = 0
-        if residual is not None:
-            rbs = _batch_stride(residual, C, N)
-            if rbs is None:
-                residual, rbs = _f32c(residual), 0
+        residual, rbs = _residual_arg(residual, C, N)
         y = torch.empty(B, C, N, device=x.device, dtype=torch.float32)
         mean = torch.empty(B * C, device=x.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
@@ -787,9 +804,7 @@ class AdaInFn(torch.autograd.Function):
     def backward(ctx, gy):
         x, gamma_beta, mean, rstd = ctx.saved_tensors
         B, C, N = x.shape
-        gybs = _batch_stride(gy, C, N)
-        if gybs is None:
-            gy, gybs = _f32c(gy), 0
+        gy, gybs = _cotangent(gy, B, C, N, x.device)
         gx = torch.empty(B, C, N, device=x.device, dtype=torch.float32)
         g_gb = torch.empty(B, 2, C, device=x.device, dtype=torch.float32)
         slots = _amax_slots(B * C, x.device)
@@ -974,12 +989,7 @@ class UnionKeysValuesAdaInFn(torch.autograd.Function):
         slots = _amax_slots(B * Ct, x.device)           # [B][Ct]: every norm writes its channel range of every cloud
         for i, (c0, C) in enumerate(ctx.meta):
             gb, mean, rstd = saved[i * 3:(i + 1) * 3]
-            gy = gouts[i]
-            if gy is None:
-                gy = torch.zeros(B, C, N, device=x.device, dtype=torch.float32)
-            gybs = _batch_stride(gy, C, N)
-            if gybs is None:
-                gy, gybs = _f32c(gy), 0
+            gy, gybs = _cotangent(gouts[i], B, C, N, x.device)
             keep.append(gy)
             g_gb = torch.empty(B, 2, C, device=x.device, dtype=torch.float32)
             items.append(dict(x=_ptr(y) + c0 * N * 4, xbs=Ct * N, gb=gb, gbbs=_gb_arg(gb, B, C)[1], mean=mean, rstd=rstd, gy=_ptr(gy), gybs=gybs,
@@ -1195,561 +1205,30 @@ def _bn_group_bwd(items, B, N, device, group, count):
     return out
 
 
-class BnReluFn(torch.autograd.Function):
-    """relu?(batch_norm(x)) [+ residual] in training mode (batch statistics; running statistics and num_batches_tracked
-    updated in place by the kernel): the nn.Sequential(BatchNorm1d, ReLU) tail of the blocks' `after` stacks and the
-    union's skip connection (layers/multihead_ct.py:67-68,149-153,198).  `group`: the process group of a SyncBatchNorm."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, running_mean, running_var, nbt, eps, momentum, relu, residual, group=None):
-        _dev(x, weight, bias)
-        x, weight, bias = _f32c(x), _f32c(weight), _f32c(bias)
-        B, C, N = x.shape
-        y = torch.empty_like(x)
-        rbs = 0
-        if residual is not None:
-            rbs = _batch_stride(residual, C, N)
-            if rbs is None:
-                residual = _f32c(residual)
-                rbs = 0
-        slots = _amax_slots(C, x.device)
-        with _on(x.device):
-            stats, count = _bn_group_fwd([dict(x=_ptr(x), xbs=0, C=C, w=weight, b=bias, rm=running_mean, rv=running_var, nbt=nbt,
-                                               eps=eps, mom=momentum, relu=relu, res=_ptr(residual), rbs=rbs, y=_ptr(y), ybs=0,
-                                               amax=_ptr(slots))],
-                                         B, N, x.device, group)
-        tag_amax(y, slots)
-        mean, rstd = stats[0]
-        ctx.save_for_backward(x, weight, bias, mean, rstd, count)
-        ctx.relu = int(bool(relu))
-        ctx.has_residual = residual is not None
-        ctx.group = group
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, weight, bias, mean, rstd, count = ctx.saved_tensors
-        B, C, N = x.shape
-        gybs = _batch_stride(gy, C, N)          # a slice of the concatenation's cotangent is read where it lies
-        if gybs is None:
-            gy = _f32c(gy)
-            gybs = 0
-        gx = torch.empty_like(x)
-        slots = _amax_slots(C, x.device)
-        with _on(x.device):
-            ((g_w, g_b),) = _bn_group_bwd([dict(x=_ptr(x), xbs=0, C=C, w=weight, b=bias, mean=mean, rstd=rstd, gy=_ptr(gy),
-                                                gybs=gybs, gx=_ptr(gx), gxbs=0, relu=ctx.relu, amax=_ptr(slots))],
-                                          B, N, x.device, ctx.group, count)
-        tag_amax(gx, slots)
-        return gx, g_w, g_b, None, None, None, None, None, None, (gy if ctx.has_residual else None), None
-
-
-class SplitBnFn(torch.autograd.Function):
-    """(key_bn(x[:, :Ck]), values_bn(x[:, Ck:])) in training mode — the two BatchNorms on the halves of the
-    keys_values_pred output (layers/multihead_ct.py:89-91).  The kernels read the channel slices of x where they lie
-    (batch stride C*N) and the backward writes both input cotangents straight into the halves of ONE [B,C,N] tensor:
-    neither the contiguous copies of the slices nor the concatenation of their cotangents exist."""
-
-    @staticmethod
-    def forward(ctx, x, wk, bk, rmk, rvk, nbk, epsk, momk, wv, bv, rmv, rvv, nbv, epsv, momv, group=None):
-        _dev(x, wk, wv)
-        x = _f32c(x)
-        B, C, N = x.shape
-        Ck = wk.numel()
-        Cv = C - Ck
-        assert wv.numel() == Cv
-        items, outs = [], []
-        for c0, Cs, w, b, rm, rv, nb, eps, mom in ((0, Ck, wk, bk, rmk, rvk, nbk, epsk, momk),
-                                                   (Ck, Cv, wv, bv, rmv, rvv, nbv, epsv, momv)):
-            y = torch.empty(B, Cs, N, device=x.device, dtype=torch.float32)
-            items.append(dict(x=_ptr(x) + c0 * N * 4, xbs=C * N, C=Cs, w=_f32c(w), b=_f32c(b), rm=rm, rv=rv, nbt=nb, eps=eps,
-                              mom=mom, relu=0, res=None, rbs=0, y=_ptr(y), ybs=0))
-            outs.append(y)
-        with _on(x.device):
-            stats, count = _bn_group_fwd(items, B, N, x.device, group)
-        saved = []
-        for it, (mean, rstd) in zip(items, stats):
-            saved += [it["w"], it["b"], mean, rstd]
-        ctx.save_for_backward(x, count, *saved)
-        ctx.Ck = Ck
-        ctx.group = group
-        return outs[0], outs[1]
-
-    @staticmethod
-    def backward(ctx, gk, gv):
-        x, count, wk, bk, mk, rk, wv, bv, mv, rv = ctx.saved_tensors
-        B, C, N = x.shape
-        Ck = ctx.Ck
-        gx = torch.empty_like(x)
-        items = []
-        for c0, Cs, w, b, mean, rstd, gy in ((0, Ck, wk, bk, mk, rk, gk), (Ck, C - Ck, wv, bv, mv, rv, gv)):
-            if gy is None:
-                gy = torch.zeros(B, Cs, N, device=x.device, dtype=torch.float32)
-            gybs = _batch_stride(gy, Cs, N)
-            if gybs is None:
-                gy, gybs = _f32c(gy), 0
-            items.append(dict(x=_ptr(x) + c0 * N * 4, xbs=C * N, C=Cs, w=w, b=b, mean=mean, rstd=rstd, gy=_ptr(gy), gybs=gybs,
-                              gx=_ptr(gx) + c0 * N * 4, gxbs=C * N, relu=0, keep=gy))
-        with _on(x.device):
-            (gwk, gbk), (gwv, gbv) = _bn_group_bwd(items, B, N, x.device, ctx.group, count)
-        return gx, gwk, gbk, None, None, None, None, None, gwv, gbv, None, None, None, None, None, None
-
-
-class JoinBnReluFn(torch.autograd.Function):
-    """cat([relu(bn_i(x_i)) for i], dim=1) — the heads' `after` stacks of a union block followed by its concatenation
-    (layers/multihead_ct.py:67-68,187-196): every head's kernel writes its channel range of the result where it belongs
-    and, in backward, reads its range of the cotangent where it lies; the separate outputs and their copy never exist.
-    Arguments: n, group, then per head (x, weight, bias, running_mean, running_var, num_batches_tracked, eps, momentum)."""
-
-    @staticmethod
-    def forward(ctx, n, group, *args):
-        heads = [args[i * 8:(i + 1) * 8] for i in range(n)]
-        xs = [_f32c(h[0]) for h in heads]
-        _dev(*xs)
-        B, _, N = xs[0].shape
-        Ct = sum(x.size(1) for x in xs)
-        y = torch.empty(B, Ct, N, device=xs[0].device, dtype=torch.float32)
-        slots = _amax_slots(Ct, y.device)
-        items, c0 = [], 0
-        for x, (_, w, b, rm, rv, nbt, eps, mom) in zip(xs, heads):
-            C = x.size(1)
-            items.append(dict(x=_ptr(x), xbs=0, C=C, w=_f32c(w), b=_f32c(b), rm=rm, rv=rv, nbt=nbt, eps=eps, mom=mom, relu=1,
-                              res=None, rbs=0, y=_ptr(y) + c0 * N * 4, ybs=Ct * N,
-                              amax=None if slots is None else _ptr(slots) + 4 * c0))
-            c0 += C
-        with _on(y.device):
-            stats, count = _bn_group_fwd(items, B, N, y.device, group)
-        tag_amax(y, slots)
-        saved = []
-        for x, it, (mean, rstd) in zip(xs, items, stats):
-            saved += [x, it["w"], it["b"], mean, rstd]
-        ctx.save_for_backward(count, *saved)
-        ctx.n = n
-        ctx.group = group
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        n = ctx.n
-        count = ctx.saved_tensors[0]
-        saved = ctx.saved_tensors[1:]
-        B, Ct, N = gy.shape
-        gybs = _batch_stride(gy, Ct, N)
-        if gybs is None:
-            gy, gybs = _f32c(gy), Ct * N
-        items, gxs, c0 = [], [], 0
-        for i in range(n):
-            x, w, b, mean, rstd = saved[i * 5:(i + 1) * 5]
-            C = x.size(1)
-            gx = torch.empty_like(x)
-            gxs.append(gx)
-            slots = _amax_slots(C, gx.device)
-            items.append(dict(x=_ptr(x), xbs=0, C=C, w=w, b=b, mean=mean, rstd=rstd, gy=_ptr(gy) + c0 * N * 4, gybs=gybs,
-                              gx=_ptr(gx), gxbs=0, relu=1, amax=_ptr(slots), slots=slots))
-            c0 += C
-        with _on(gy.device):
-            wb = _bn_group_bwd(items, B, N, gy.device, ctx.group, count)
-        for gx, it in zip(gxs, items):
-            tag_amax(gx, it["slots"])
-        grads = [None, None]
-        for gx, (g_w, g_b) in zip(gxs, wb):
-            grads += [gx, g_w, g_b, None, None, None, None, None]
-        return tuple(grads)
-
-
-def join_bn_relu(xs, bns):
-    """cat([relu(bn(x)) for x, bn in zip(xs, bns)], dim=1) through JoinBnReluFn; the caller checked bn_relu_eligible for
-    every pair."""
-    args = []
-    for x, bn in zip(xs, bns):
-        args += [x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.eps, bn.momentum]
-    return JoinBnReluFn.apply(len(xs), _sync_group(bns[0]), *args)
-
-
-class UnionKeysValuesFn(torch.autograd.Function):
-    """The `keys_values_pred` projections of all heads of a union block and the key_bn / values_bn norms on their
-    outputs (layers/multihead_ct.py:31-33,89-91), as ONE GEMM with the heads' weights stacked: the heads share the input,
-    so forward is one [sum Co, Cin] x [Cin, N] product per cloud instead of one per head, the data gradient one product
-    with K = sum Co instead of one per head plus autograd's accumulation of their results, the weight gradient one
-    product.  The norms read their channel ranges of the GEMM output where they lie and write their input cotangents
-    into the ranges of ONE tensor, which is the data / weight gradient GEMMs' operand.  Under SyncBatchNorm the 2n norms
-    share ONE statistics all_gather in forward and ONE all_reduce in backward.
-    Arguments: n, group, x, then per head: weight [Co,Cin,1], key_bn (w, b, rm, rv, nbt, eps, mom), values_bn (same 7).
-    Returns (keys_res_0, values_0, keys_res_1, values_1, ...)."""
-
-    PER_HEAD = 15
-
-    @staticmethod
-    def forward(ctx, n, group, x, *args):
-        # n < 0: -n heads AND x itself as the first output (the block's identity shortcut, layers/multihead_ct.py:170-176:
-        # its cotangent comes back here and rides the data gradient's epilogue instead of a separate add over three tensors)
-        ctx.passthrough = n < 0
-        n = abs(n)
-        P = UnionKeysValuesFn.PER_HEAD
-        heads = [args[i * P:(i + 1) * P] for i in range(n)]
-        x_in = x
-        x = _f32c(x)
-        _dev(x)
-        B, Cin, N = x.shape
-        Wc = torch.cat([h[0][:, :, 0] for h in heads], dim=0)               # [sum Co, Cin]
-        Ct = Wc.size(0)
-        ctx.pw_precision = _prec.code()      # the layer's three products share the forward's precision (precision.py)
-        y, am_w, am_x, Wt = pw_forward(Wc, x, ctx.needs_input_grad[2])      # [B, sum Co, N]
-        outs, items, meta, c0 = [], [], [], 0
-        for h in heads:
-            for (w, b, rm, rv, nbt, eps, mom) in (h[1:8], h[8:15]):
-                w, b = _f32c(w), _f32c(b)
-                C = w.numel()
-                o = torch.empty(B, C, N, device=x.device, dtype=torch.float32)
-                items.append(dict(x=_ptr(y) + c0 * N * 4, xbs=Ct * N, C=C, w=w, b=b, rm=rm, rv=rv, nbt=nbt, eps=eps, mom=mom,
-                                  relu=0, res=None, rbs=0, y=_ptr(o), ybs=0))
-                outs.append(o)
-                meta.append((c0, C))
-                c0 += C
-        assert c0 == Ct, "key_bn + values_bn must cover the projections"
-        with _on(x.device):
-            stats, count = _bn_group_fwd(items, B, N, x.device, group)
-        saved = []
-        for it, (mean, rstd) in zip(items, stats):
-            saved += [it["w"], it["b"], mean, rstd]
-        ctx.save_for_backward(x, y, Wc, count, *saved)
-        ctx.am = (am_w, am_x, Wt)
-        ctx.meta = meta
-        ctx.couts = [h[0].size(0) for h in heads]
-        ctx.group = group
-        if ctx.passthrough:
-            return (x_in,) + tuple(outs)
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, *gouts):
-        g_skip = None
-        if ctx.passthrough:
-            g_skip, gouts = gouts[0], gouts[1:]
-        x, y, Wc, count = ctx.saved_tensors[:4]
-        saved = ctx.saved_tensors[4:]
-        B, Cin, N = x.shape
-        Ct = Wc.size(0)
-        g_y = torch.empty_like(y)
-        slots = _amax_slots(Ct, x.device)
-        items = []
-        for i, (c0, C) in enumerate(ctx.meta):
-            w, b, mean, rstd = saved[i * 4:(i + 1) * 4]
-            gy = gouts[i]
-            if gy is None:
-                gy = torch.zeros(B, C, N, device=x.device, dtype=torch.float32)
-            gybs = _batch_stride(gy, C, N)
-            if gybs is None:
-                gy, gybs = _f32c(gy), 0
-            items.append(dict(x=_ptr(y) + c0 * N * 4, xbs=Ct * N, C=C, w=w, b=b, mean=mean, rstd=rstd, gy=_ptr(gy), gybs=gybs,
-                              gx=_ptr(g_y) + c0 * N * 4, gxbs=Ct * N, relu=0, keep=gy,
-                              amax=None if slots is None else _ptr(slots) + 4 * c0))
-        with _on(x.device):
-            bn_grads = _bn_group_bwd(items, B, N, x.device, ctx.group, count)
-        g_x, g_Wc = pw_backward(Wc, x, g_y, ctx.am[0], ctx.am[1], ctx.needs_input_grad[2], True,
-                                am_g=None if slots is None else slots.view(-1, g_y.shape[1]), Wt=ctx.am[2],
-                                add_gx=g_skip if ctx.needs_input_grad[2] else None, precision=ctx.pw_precision)   # g_Wc [sum Co, Cin]
-        grads, r0 = [None, None, g_x], 0
-        for hi, Co in enumerate(ctx.couts):
-            (gwk, gbk), (gwv, gbv) = bn_grads[2 * hi], bn_grads[2 * hi + 1]
-            grads += [g_Wc[r0:r0 + Co].unsqueeze(-1), gwk, gbk, None, None, None, None, None, gwv, gbv, None, None, None, None, None]
-            r0 += Co
-        return tuple(grads)
-
-
-def union_keys_values(x, convs, key_bns, values_bns, passthrough=False):
-    """[(key_bn_i(y_i[:, :Ck]), values_bn_i(y_i[:, Ck:])) with y_i = conv_i(x)] for the heads of a union block through
-    UnionKeysValuesFn; the caller checked union_keys_values_eligible.  passthrough: -> (x', that list) with x' = x as an output
-    of the same node — the block's identity shortcut takes x' so that its cotangent is summed inside the data gradient."""
-    args = []
-    for conv, kb, vb in zip(convs, key_bns, values_bns):
-        args.append(conv.weight)
-        for bn in (kb, vb):
-            args += [bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.eps, bn.momentum]
-    outs = UnionKeysValuesFn.apply(-len(convs) if passthrough else len(convs), _sync_group(key_bns[0]), x, *args)
-    if passthrough:
-        return outs[0], [(outs[1 + 2 * i], outs[2 + 2 * i]) for i in range(len(convs))]
-    return [(outs[2 * i], outs[2 * i + 1]) for i in range(len(convs))]
-
-
-def union_keys_values_eligible(x, convs, key_bns, values_bns):
-    """Plain bias-free 1x1 Conv1d projections of the same input and norms the fused kernels take."""
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous() and len(convs) > 1):
-        return False
-    for conv, kb, vb in zip(convs, key_bns, values_bns):
-        if not (isinstance(conv, torch.nn.Conv1d) and conv.kernel_size == (1,) and conv.stride == (1,) and conv.padding == (0,)
-                and conv.dilation == (1,) and conv.groups == 1 and conv.bias is None and conv.in_channels == x.size(1)
-                and conv.out_channels == kb.num_features + vb.num_features):
-            return False
-        probe = (x.size(0), x.size(2))
-        for bn in (kb, vb):
-            if not (type(bn) in _BN_TYPES and bn.training and bn.affine and bn.track_running_stats
-                    and bn.momentum is not None):
-                return False
-            key = (probe[0], bn.num_features, probe[1])
-            ok = _bn_supported.get(key)
-            if ok is None:
-                ok = _bn_supported[key] = bool(_lib.load().ct_bn_relu_supported(*key))
-            if not ok:
-                return False
-    return norms_share_group(list(key_bns) + list(values_bns))
-
-
-_bn_supported = {}
+# ---------------------------------------------------------------------------
+# the three modes of a fused norm, and the norms on their stored statistics (ct_bn_eval_group_fwd / ct_bn_eval_group_bwd)
+# ---------------------------------------------------------------------------
+# train:  batch statistics, running buffers updated in place (ct_bn_group_*, above).
+# eval:   the stored statistics where autograd would record nothing — forward only, on purpose: plain functions that save
+#         nothing.  "0": every eval norm through its module (A/B runs).
+# frozen: the stored statistics in a forward that records gradients, only for norms marked by cloud_transformers_amd.freeze_norms
+#         (an unmarked eval norm with gradients keeps its module's path).  The eval functions' launches — same items, same maxima
+#         tags — which save the norm's INPUT (x, or the stacked GEMM output), never y: the backward recomputes the ReLU mask from
+#         it.  "0": marked norms through their modules (A/B runs).
+BN_EVAL = os.environ.get("CLOUDCT_BN_EVAL", "1") != "0"
+BN_FROZEN = os.environ.get("CLOUDCT_BN_FROZEN", "1") != "0"
 # nn.BatchNorm1d, and nn.SyncBatchNorm (what parallel.data_parallel / the reference's DDP recipe turns every norm into:
 # train_segmentation.py:128): same parameters and buffers, statistics exchanged over its process group
 _BN_TYPES = (torch.nn.BatchNorm1d, torch.nn.SyncBatchNorm)
 
 
-def bn_relu_eligible(bn, x, channels=None):
-    """True when `bn` (an nn.BatchNorm1d, exactly) applied to x (or, with `channels`, to a slice of that many of its
-    channels) can run as ct_bn_group_*: training mode with running statistics and a fixed momentum, affine, CUDA fp32
-    [B,C,N] contiguous, and a shape the register-resident kernels take (ct_bn_relu_supported)."""
-    C = x.size(1) if channels is None and x.dim() == 3 else channels
-    if not (type(bn) in _BN_TYPES and bn.training and bn.affine and bn.track_running_stats
-            and bn.momentum is not None and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3
-            and x.is_contiguous() and x.data_ptr() % 16 == 0 and C == bn.num_features):
-        return False
-    key = (x.size(0), C, x.size(2))
-    ok = _bn_supported.get(key)
-    if ok is None:
-        ok = _bn_supported[key] = bool(_lib.load().ct_bn_relu_supported(*key))
-    return ok
-
-
-def split_bn(x, bn_a, bn_b):
-    """(bn_a(x[:, :Ca]), bn_b(x[:, Ca:])) through SplitBnFn; the caller checked bn_relu_eligible for both modules (each
-    against its own slice's shape) and that x is contiguous."""
-    return SplitBnFn.apply(x, bn_a.weight, bn_a.bias, bn_a.running_mean, bn_a.running_var, bn_a.num_batches_tracked,
-                           bn_a.eps, bn_a.momentum,
-                           bn_b.weight, bn_b.bias, bn_b.running_mean, bn_b.running_var, bn_b.num_batches_tracked,
-                           bn_b.eps, bn_b.momentum, _sync_group(bn_a))
-
-
-def bn_relu(x, bn, relu=True, residual=None):
-    """relu?(bn(x)) [+ residual] through the fused kernels; the caller checked bn_relu_eligible(bn, x).  Updates the
-    module's running statistics and num_batches_tracked exactly as nn.BatchNorm1d.forward does in training mode."""
-    return BnReluFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.eps,
-                          bn.momentum, relu, residual, _sync_group(bn))
-
-
-# ---------------------------------------------------------------------------
-# eval-mode BatchNorm1d / SyncBatchNorm (+ ReLU, + skip): a per-channel affine on the stored statistics (ct_bn_eval_*)
-# ---------------------------------------------------------------------------
-# Forward only, on purpose: plain functions that save nothing, taken only where autograd would record nothing.  An eval
-# forward WITH gradients keeps the modules' own path (norms marked by freeze_norms: the frozen section below).  "0": every
-# eval norm through its module (A/B runs).
-BN_EVAL = os.environ.get("CLOUDCT_BN_EVAL", "1") != "0"
-_bn_eval_supported = {}
-
-
-def _records_nothing(*tensors):
-    """True when autograd would record nothing for an op on `tensors` (None entries skipped)."""
-    return not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in tensors)
-
-
-def _bn_eval_norm_ok(bn, B, C, N):
-    """An eval-mode affine norm of C channels with running statistics whose shape ct_bn_eval_* takes."""
-    if not (type(bn) in _BN_TYPES and not bn.training and bn.affine and bn.track_running_stats
-            and bn.running_mean is not None and bn.running_var is not None and C == bn.num_features
-            and bn.weight.dtype == torch.float32 and bn.running_mean.dtype == torch.float32):
-        return False
-    key = (B, C, N)
-    ok = _bn_eval_supported.get(key)
-    if ok is None:
-        ok = _bn_eval_supported[key] = bool(_lib.load().ct_bn_eval_supported(*key))
-    return ok
-
-
-def bn_eval_eligible(bn, x, channels=None, residual=None):
-    """True when `bn` applied to x (or, with `channels`, to a slice of that many of its channels) can run as
-    ct_bn_eval_group_fwd: an nn.BatchNorm1d / nn.SyncBatchNorm (exactly) in eval mode, affine, with running statistics; x CUDA
-    fp32 [B,C,N] contiguous and 16-byte aligned; a shape ct_bn_eval_supported takes; and nothing for autograd to record
-    (grad mode off, or none of x, the affine parameters and `residual` requires grad)."""
-    if not (BN_EVAL and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()
-            and x.data_ptr() % 16 == 0):
-        return False
-    if residual is not None and not (residual.is_cuda and residual.dtype == torch.float32 and residual.dim() == 3):
-        return False
-    C = x.size(1) if channels is None else channels
-    return (_bn_eval_norm_ok(bn, x.size(0), C, x.size(2)) and bn.weight.device == x.device
-            and _records_nothing(x, bn.weight, bn.bias, residual))
-
-
-def _bn_eval_item(bn, x_ptr, xbs, y_ptr, ybs, relu, res=None, rbs=0, amax=None):
-    return dict(x=x_ptr, xbs=xbs, C=bn.num_features, w=_f32c(bn.weight.detach()), b=_f32c(bn.bias.detach()),
-                rm=_f32c(bn.running_mean), rv=_f32c(bn.running_var), eps=float(bn.eps), relu=int(bool(relu)),
-                res=res, rbs=rbs, y=y_ptr, ybs=ybs, amax=amax)
-
-
 def _bn_eval_group(items, B, N):
-    """Run eval norms over the same (B, N) (ct_bn_eval_group_fwd), over the runs of _bn_runs as _bn_group_fwd.  items:
-    _bn_eval_item dicts."""
+    """Run stored-statistics norms over the same (B, N) (ct_bn_eval_group_fwd), over the runs of _bn_runs as _bn_group_fwd.
+    items: _bn_fwd_table dicts (_bn_eval_item)."""
     lib = _lib.load()
     arr = _bn_fwd_table(items)
     for first, run in _bn_runs(len(items)):
         _lib.check(lib.ct_bn_eval_group_fwd(_at(arr, first), run, B, N, _stream()), "ct_bn_eval_group_fwd")
-
-
-def bn_eval(x, bn, relu=True, residual=None):
-    """relu?(bn(x)) [+ residual] of an eval-mode norm in one pass (ct_bn_eval_group_fwd); the caller checked
-    bn_eval_eligible(bn, x, residual=residual).  Reads the running statistics, writes nothing but the result, which carries
-    its per-channel maxima for the pointwise GEMM that reads it next."""
-    _dev(x, residual)
-    x = _f32c(x)
-    B, C, N = x.shape
-    y = torch.empty_like(x)
-    rbs = 0
-    if residual is not None:
-        rbs = _batch_stride(residual, C, N)
-        if rbs is None:
-            residual, rbs = _f32c(residual), 0
-    slots = _amax_slots(C, x.device)
-    with _on(x.device):
-        _bn_eval_group([_bn_eval_item(bn, _ptr(x), 0, _ptr(y), 0, relu, _ptr(residual), rbs, _ptr(slots))], B, N)
-    return tag_amax(y, slots)
-
-
-def split_bn_eval(x, bn_a, bn_b):
-    """(bn_a(x[:, :Ca]), bn_b(x[:, Ca:])) of two eval-mode norms in one launch, the halves of x read where they lie; the
-    caller checked bn_eval_eligible for both (each against its own slice's channels)."""
-    _dev(x)
-    x = _f32c(x)
-    B, C, N = x.shape
-    Ca = bn_a.num_features
-    assert bn_b.num_features == C - Ca
-    items, outs = [], []
-    for c0, bn in ((0, bn_a), (Ca, bn_b)):
-        y = torch.empty(B, bn.num_features, N, device=x.device, dtype=torch.float32)
-        items.append(_bn_eval_item(bn, _ptr(x) + c0 * N * 4, C * N, _ptr(y), 0, False))
-        outs.append(y)
-    with _on(x.device):
-        _bn_eval_group(items, B, N)
-    return outs[0], outs[1]
-
-
-def join_bn_relu_eval(xs, bns):
-    """cat([relu(bn(x)) for x, bn in zip(xs, bns)], dim=1) of eval-mode norms: every norm writes its channel range of the
-    result where it belongs, and the result carries one maxima tag over all its channels; the caller checked
-    bn_eval_eligible for every pair."""
-    xs = [_f32c(x) for x in xs]
-    _dev(*xs)
-    B, _, N = xs[0].shape
-    Ct = sum(x.size(1) for x in xs)
-    y = torch.empty(B, Ct, N, device=xs[0].device, dtype=torch.float32)
-    slots = _amax_slots(Ct, y.device)
-    items, c0 = [], 0
-    for x, bn in zip(xs, bns):
-        items.append(_bn_eval_item(bn, _ptr(x), 0, _ptr(y) + c0 * N * 4, Ct * N, True,
-                                   amax=None if slots is None else _ptr(slots) + 4 * c0))
-        c0 += x.size(1)
-    with _on(y.device):
-        _bn_eval_group(items, B, N)
-    return tag_amax(y, slots)
-
-
-def union_keys_values_eval_eligible(x, convs, key_bns, values_bns):
-    """Plain bias-free 1x1 Conv1d projections of the same input, eval-mode norms ct_bn_eval_* takes, and nothing for
-    autograd to record."""
-    if not (BN_EVAL and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()
-            and x.data_ptr() % 16 == 0 and len(convs) > 1):
-        return False
-    watched = [x]
-    for conv, kb, vb in zip(convs, key_bns, values_bns):
-        if not (isinstance(conv, torch.nn.Conv1d) and conv.kernel_size == (1,) and conv.stride == (1,) and conv.padding == (0,)
-                and conv.dilation == (1,) and conv.groups == 1 and conv.bias is None and conv.in_channels == x.size(1)
-                and conv.out_channels == kb.num_features + vb.num_features and conv.weight.dtype == torch.float32):
-            return False
-        for bn in (kb, vb):
-            if not (_bn_eval_norm_ok(bn, x.size(0), bn.num_features, x.size(2)) and bn.weight.device == x.device):
-                return False
-            watched += [bn.weight, bn.bias]
-        if conv.weight.device != x.device:
-            return False
-        watched.append(conv.weight)
-    return _records_nothing(*watched)
-
-
-def union_keys_values_eval(x, convs, key_bns, values_bns):
-    """[(key_bn_i(y_i[:, :Ck]), values_bn_i(y_i[:, Ck:])) with y_i = conv_i(x)] for the heads of a union block in eval mode:
-    ONE stacked projection GEMM with the 2n norms in its epilogue (PW_NORM, 2n <= BN_GROUP_MAX and a product the forward
-    kernel takes), else that GEMM and then the norms on its channel ranges in one launch; the caller checked
-    union_keys_values_eval_eligible."""
-    x = _f32c(x)
-    _dev(x)
-    B, _, N = x.shape
-    Wc = torch.cat([conv.weight.detach()[:, :, 0] for conv in convs], dim=0)        # [sum Co, Cin]
-    Ct = Wc.size(0)
-    bns = [bn for kb, vb in zip(key_bns, values_bns) for bn in (kb, vb)]
-    if _pw_norm_takes(Ct, Wc.size(1), N, len(bns), PW_FWD):
-        # the 2n norms in the stacked GEMM's epilogue: the [B, sum Co, N] tensor is never written
-        outs = [torch.empty(B, bn.num_features, N, device=x.device, dtype=torch.float32) for bn in bns]
-        pw_gemm_norm(Wc, x, [_bn_eval_item(bn, None, 0, _ptr(o), 0, False) for bn, o in zip(bns, outs)])
-        return [(outs[2 * i], outs[2 * i + 1]) for i in range(len(convs))]
-    y = pw_forward(Wc, x)[0]                                                        # [B, sum Co, N]
-    items, outs, c0 = [], [], 0
-    for kb, vb in zip(key_bns, values_bns):
-        for bn in (kb, vb):
-            o = torch.empty(B, bn.num_features, N, device=x.device, dtype=torch.float32)
-            items.append(_bn_eval_item(bn, _ptr(y) + c0 * N * 4, Ct * N, _ptr(o), 0, False))
-            outs.append(o)
-            c0 += bn.num_features
-    assert c0 == Ct, "key_bn + values_bn must cover the projections"
-    with _on(x.device):
-        _bn_eval_group(items, B, N)
-    return [(outs[2 * i], outs[2 * i + 1]) for i in range(len(convs))]
-
-
-# ---------------------------------------------------------------------------
-# frozen norms: eval-mode statistics in a forward that records gradients (ct_bn_eval_group_fwd / ct_bn_eval_group_bwd)
-# ---------------------------------------------------------------------------
-# Only norms marked by cloud_transformers_amd.freeze_norms take these (an unmarked eval norm with gradients keeps its
-# module's path).  The forwards are the eval functions' launches — same items, same maxima tags — and save the norm's
-# INPUT (x, or the stacked GEMM output), never y: the backward recomputes the ReLU mask from it.  "0": marked norms through
-# their modules (A/B runs).
-BN_FROZEN = os.environ.get("CLOUDCT_BN_FROZEN", "1") != "0"
-
-
-def norm_frozen(bn):
-    """True for a norm marked by freeze_norms (norms.py)."""
-    return bool(getattr(bn, "_ct_frozen", False))
-
-
-def records_gradients(*tensors):
-    """True when autograd would record an op on `tensors` (None entries skipped): the other half of a frozen norm's routing
-    rule — where nothing is recorded the eval functions above take the norm, marked or not."""
-    return not _records_nothing(*tensors)
-
-
-def bn_frozen_eligible(bn, x, channels=None, residual=None):
-    """bn_eval_eligible without its "nothing to record" clause, for a norm that freeze_norms marked: an nn.BatchNorm1d /
-    nn.SyncBatchNorm (exactly) in eval mode, affine, with running statistics; x CUDA fp32 [B,C,N] contiguous and 16-byte
-    aligned; a shape ct_bn_eval_supported takes."""
-    if not (BN_FROZEN and norm_frozen(bn) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()
-            and x.data_ptr() % 16 == 0):
-        return False
-    if residual is not None and not (residual.is_cuda and residual.dtype == torch.float32 and residual.dim() == 3):
-        return False
-    C = x.size(1) if channels is None else channels
-    return _bn_eval_norm_ok(bn, x.size(0), C, x.size(2)) and bn.weight.device == x.device
-
-
-def union_keys_values_frozen_eligible(x, convs, key_bns, values_bns):
-    """union_keys_values_eval_eligible without its "nothing to record" clause, every norm marked by freeze_norms."""
-    if not (BN_FROZEN and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()
-            and x.data_ptr() % 16 == 0 and len(convs) > 1):
-        return False
-    for conv, kb, vb in zip(convs, key_bns, values_bns):
-        if not (isinstance(conv, torch.nn.Conv1d) and conv.kernel_size == (1,) and conv.stride == (1,) and conv.padding == (0,)
-                and conv.dilation == (1,) and conv.groups == 1 and conv.bias is None and conv.in_channels == x.size(1)
-                and conv.out_channels == kb.num_features + vb.num_features and conv.weight.dtype == torch.float32
-                and conv.weight.device == x.device):
-            return False
-        for bn in (kb, vb):
-            if not (norm_frozen(bn) and _bn_eval_norm_ok(bn, x.size(0), bn.num_features, x.size(2))
-                    and bn.weight.device == x.device):
-                return False
-    return True
 
 
 def _bn_eval_bwd_table(items):
@@ -1776,270 +1255,372 @@ def _bn_eval_group_bwd(items, B, N):
         _lib.check(lib.ct_bn_eval_group_bwd(_at(arr, first), run, B, N, _stream()), "ct_bn_eval_group_bwd")
 
 
-def _frozen_sums(C, device, need):
-    """(g_weight, g_bias) buffers of a frozen norm, or (None, None) when neither parameter takes a gradient."""
-    if not need:
-        return None, None
-    return torch.empty(C, device=device, dtype=torch.float32), torch.empty(C, device=device, dtype=torch.float32)
+def _norm_args(bn, stored, detach=False):
+    """A norm's run of a Function's arguments: (weight, bias, running_mean, running_var, num_batches_tracked, eps, momentum).
+    A norm on its stored statistics updates nothing, so it has neither counter nor momentum; `detach`: the parameters of an
+    eval function, which records nothing."""
+    w, b = (bn.weight.detach(), bn.bias.detach()) if detach else (bn.weight, bn.bias)
+    if stored:
+        return (w, b, bn.running_mean, bn.running_var, None, bn.eps, None)
+    return (w, b, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.eps, bn.momentum)
 
 
-def _cotangent(gy, B, C, N, device):
-    """(tensor, batch stride) of a cotangent the kernels can read where it lies; None -> zeros."""
-    if gy is None:
-        gy = torch.zeros(B, C, N, device=device, dtype=torch.float32)
-    gybs = _batch_stride(gy, C, N)
-    if gybs is None:
-        gy, gybs = _f32c(gy), 0
-    return gy, gybs
+_NORM_ARGS = 7
 
 
-class BnFrozenFn(torch.autograd.Function):
-    """relu?(bn(x)) [+ residual] on the norm's running statistics, with gradients: bn_eval's launch forward,
-    ct_bn_eval_group_bwd backward.  The running statistics are read, never written."""
+def _stored_item(place, norm):
+    """`place` (a norm's pointers, strides, C and relu) + what a stored-statistics launch reads of the norm (_norm_args)."""
+    w, b, rm, rv, _, eps, _ = norm
+    return dict(place, w=_f32c(w), b=_f32c(b), rm=_f32c(rm), rv=_f32c(rv), eps=float(eps))
+
+
+def _bn_eval_item(bn, x_ptr, xbs, y_ptr, ybs, relu, res=None, rbs=0, amax=None):
+    return _stored_item(dict(x=x_ptr, xbs=xbs, C=bn.num_features, relu=int(bool(relu)), res=res, rbs=rbs, y=y_ptr, ybs=ybs, amax=amax),
+                        _norm_args(bn, True, detach=True))
+
+
+def _norms_fwd(layout, norms, stored, B, N, device, group=None):
+    """Launch the norms of a composition.  layout: one dict per norm with where it reads and writes (x, xbs, C, relu, res, rbs, y,
+    ybs, amax: a composition's forward layout); norms: their _norm_args.  -> (per norm the four tensors its backward reads —
+    weight, bias and the batch mean / rstd of a training norm or the running mean / variance of a stored one —, count: see
+    _bn_group_fwd)."""
+    with _on(device):
+        if stored:
+            items = [_stored_item(place, norm) for place, norm in zip(layout, norms)]
+            _bn_eval_group(items, B, N)
+            return [(it["w"], it["b"], it["rm"], it["rv"]) for it in items], None
+        items = [dict(place, w=_f32c(w), b=_f32c(b), rm=rm, rv=rv, nbt=nbt, eps=eps, mom=mom)
+                 for place, (w, b, rm, rv, nbt, eps, mom) in zip(layout, norms)]
+        stats, count = _bn_group_fwd(items, B, N, device, group)
+    return [(it["w"], it["b"], mean, rstd) for it, (mean, rstd) in zip(items, stats)], count
+
+
+def _norms_bwd(ctx, layout, saved, needs, B, N, device, count):
+    """Backward of _norms_fwd.  layout: one dict per norm (x, xbs, C, relu, gy, gybs, gx, gxbs, amax: a composition's backward
+    layout); saved: _norms_fwd's tuples; needs: per norm whether (weight, bias) take a gradient.  -> [(g_weight, g_bias)].  A
+    training norm computes both whatever `needs` says; a stored one skips the sums nobody needs, and the launch if nothing is."""
+    with _on(device):
+        if not ctx.stored:
+            return _bn_group_bwd([dict(place, w=w, b=b, mean=mean, rstd=rstd) for place, (w, b, mean, rstd) in zip(layout, saved)],
+                                 B, N, device, ctx.group, count)
+        items, sums = [], []
+        for place, (w, b, rm, rv), eps, (need_w, need_b) in zip(layout, saved, ctx.eps, needs):
+            g_w = g_b = None
+            if need_w or need_b:
+                g_w, g_b = (torch.empty(place["C"], device=device, dtype=torch.float32) for _ in range(2))
+            items.append(dict(place, w=w, b=b, rm=rm, rv=rv, eps=eps, gw=g_w, gb=g_b))
+            sums.append((g_w if need_w else None, g_b if need_b else None))
+        _bn_eval_group_bwd(items, B, N)
+    return sums
+
+
+def _save_norms(ctx, tensors, norms, saved, count, stored, group):
+    ctx.save_for_backward(*tensors, count, *[t for s in saved for t in s])
+    ctx.stored, ctx.group, ctx.eps = stored, group, [float(norm[5]) for norm in norms]
+
+
+def _saved_norms(ctx, n):
+    """-> (the n tensors saved in front, count, _norms_fwd's tuples, needs_input_grad — all True for a training backward, which
+    computes everything)"""
+    t = ctx.saved_tensors
+    needs = ctx.needs_input_grad if ctx.stored else (True,) * len(ctx.needs_input_grad)
+    return t[:n], t[n], [t[i:i + 4] for i in range(n + 1, len(t), 4)], needs
+
+
+# -- one norm (+ ReLU, + residual) -------------------------------------------------------------------------------------------
+def _single_fwd(x, norm, relu, residual, stored, group=None):
+    """relu?(norm(x)) [+ residual].  -> (y with its per-channel maxima tag, x as read, *_norms_fwd's results)"""
+    _dev(x, norm[0], norm[1], residual)
+    x = _f32c(x)
+    B, C, N = x.shape
+    y = torch.empty_like(x)
+    residual, rbs = _residual_arg(residual, C, N)
+    slots = _amax_slots(C, x.device)
+    saved, count = _norms_fwd([dict(x=_ptr(x), xbs=0, C=C, relu=int(bool(relu)), res=_ptr(residual), rbs=rbs, y=_ptr(y), ybs=0,
+                                    amax=_ptr(slots))], [norm], stored, B, N, x.device, group)
+    return tag_amax(y, slots), x, saved, count
+
+
+class BnReluFn(torch.autograd.Function):
+    """relu?(norm(x)) [+ residual]: the nn.Sequential(BatchNorm1d, ReLU) tail of the blocks' `after` stacks and the union's skip
+    connection (layers/multihead_ct.py:67-68,149-153,198).  Training mode (ct_bn_group_*: batch statistics, running statistics
+    and num_batches_tracked updated in place by the kernel; `group`: the process group of a SyncBatchNorm) or, `stored`, the
+    running statistics with gradients (bn_eval's launch forward, ct_bn_eval_group_bwd backward; they are read, never written).
+    Arguments: stored, group, x, relu, residual, then the norm (_norm_args)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, running_mean, running_var, eps, relu, residual):
-        _dev(x, weight, bias, residual)
-        x, weight, bias = _f32c(x), _f32c(weight), _f32c(bias)
-        running_mean, running_var = _f32c(running_mean), _f32c(running_var)
-        B, C, N = x.shape
-        y = torch.empty_like(x)
-        rbs = 0
-        if residual is not None:
-            rbs = _batch_stride(residual, C, N)
-            if rbs is None:
-                residual, rbs = _f32c(residual), 0
-        slots = _amax_slots(C, x.device)
-        with _on(x.device):
-            _bn_eval_group([dict(x=_ptr(x), xbs=0, C=C, w=weight, b=bias, rm=running_mean, rv=running_var, eps=float(eps),
-                                 relu=int(bool(relu)), res=_ptr(residual), rbs=rbs, y=_ptr(y), ybs=0, amax=_ptr(slots))], B, N)
-        tag_amax(y, slots)
-        ctx.save_for_backward(x, weight, bias, running_mean, running_var)
-        ctx.eps, ctx.relu, ctx.has_residual = float(eps), int(bool(relu)), residual is not None
+    def forward(ctx, stored, group, x, relu, residual, *norm):
+        y, x, saved, count = _single_fwd(x, norm, relu, residual, stored, group)
+        _save_norms(ctx, [x], [norm], saved, count, stored, group)
+        ctx.relu, ctx.has_residual = int(bool(relu)), residual is not None
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        x, weight, bias, rm, rv = ctx.saved_tensors
+        (x,), count, saved, needs = _saved_norms(ctx, 1)
         B, C, N = x.shape
-        need_x, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        gy, gybs = _cotangent(gy, B, C, N, x.device)
-        gx = torch.empty_like(x) if need_x else None
-        slots = _amax_slots(C, x.device) if need_x else None
-        g_w, g_b = _frozen_sums(C, x.device, need_p)
-        with _on(x.device):
-            _bn_eval_group_bwd([dict(x=_ptr(x), xbs=0, C=C, w=weight, b=bias, rm=rm, rv=rv, eps=ctx.eps, relu=ctx.relu, gy=_ptr(gy),
-                                     gybs=gybs, gx=_ptr(gx), gxbs=0, gw=g_w, gb=g_b, amax=_ptr(slots))], B, N)
+        gy, gybs = _cotangent(gy, B, C, N, x.device)          # a slice of the concatenation's cotangent is read where it lies
+        gx = torch.empty_like(x) if needs[2] else None
+        slots = _amax_slots(C, x.device) if needs[2] else None
+        ((g_w, g_b),) = _norms_bwd(ctx, [dict(x=_ptr(x), xbs=0, C=C, relu=ctx.relu, gy=_ptr(gy), gybs=gybs, gx=_ptr(gx), gxbs=0,
+                                              amax=_ptr(slots))], saved, [needs[5:7]], B, N, x.device, count)
         if gx is not None:
             tag_amax(gx, slots)
-        return (gx, g_w if ctx.needs_input_grad[1] else None, g_b if ctx.needs_input_grad[2] else None, None, None, None, None,
-                gy if ctx.has_residual and ctx.needs_input_grad[7] else None)
+        return (None, None, gx, None, gy if ctx.has_residual and needs[4] else None, g_w, g_b) + (None,) * (_NORM_ARGS - 2)
+
+
+def bn_relu(x, bn, relu=True, residual=None):
+    """relu?(bn(x)) [+ residual] through the fused kernels; the caller checked bn_relu_eligible(bn, x).  Updates the
+    module's running statistics and num_batches_tracked exactly as nn.BatchNorm1d.forward does in training mode."""
+    return BnReluFn.apply(False, _sync_group(bn), x, relu, residual, *_norm_args(bn, False))
+
+
+def bn_eval(x, bn, relu=True, residual=None):
+    """relu?(bn(x)) [+ residual] of an eval-mode norm in one pass (ct_bn_eval_group_fwd); the caller checked
+    bn_eval_eligible(bn, x, residual=residual).  Reads the running statistics, writes nothing but the result, which carries
+    its per-channel maxima for the pointwise GEMM that reads it next."""
+    return _single_fwd(x, _norm_args(bn, True, detach=True), relu, residual, True)[0]
 
 
 def bn_frozen(x, bn, relu=True, residual=None):
     """relu?(bn(x)) [+ residual] of a frozen norm with gradients; the caller checked bn_frozen_eligible(bn, x,
     residual=residual)."""
-    return BnFrozenFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, relu, residual)
+    return BnReluFn.apply(True, None, x, relu, residual, *_norm_args(bn, True))
 
 
-class SplitBnFrozenFn(torch.autograd.Function):
-    """(bn_a(x[:, :Ca]), bn_b(x[:, Ca:])) of two frozen norms: split_bn_eval's launch forward; the backward writes both input
-    cotangents into the halves of ONE [B,C,N] tensor (SplitBnFn's layout)."""
+# -- norms on consecutive channel ranges of one tensor, each into a tensor of its own: the two norms on the halves of
+#    keys_values_pred's output, and the 2n norms on the stacked projection of a union block ---------------------------------
+def _ranges_fwd(src, norms, stored, group=None):
+    """The norms on their channel ranges of src [B,Ct,N], read where they lie (batch stride Ct*N): neither contiguous copies of
+    the slices nor maxima tags exist.  -> (the outputs, *_norms_fwd's results)"""
+    B, Ct, N = src.shape
+    layout, outs, c0 = [], [], 0
+    for norm in norms:
+        C = norm[0].numel()
+        o = torch.empty(B, C, N, device=src.device, dtype=torch.float32)
+        layout.append(dict(x=_ptr(src) + c0 * N * 4, xbs=Ct * N, C=C, relu=0, res=None, rbs=0, y=_ptr(o), ybs=0, amax=None))
+        outs.append(o)
+        c0 += C
+    assert c0 == Ct, "the norms must cover the channels"
+    return (outs,) + _norms_fwd(layout, norms, stored, B, N, src.device, group)
+
+
+def _ranges_bwd(ctx, src, gouts, saved, needs, need_src, with_slots, count):
+    """Backward of _ranges_fwd: every norm writes its input cotangent into its range of ONE [B,Ct,N] tensor (no concatenation
+    of cotangents) and, `with_slots`, that range's per-channel maxima into one buffer.  -> (g_src, slots, [(g_weight, g_bias)]);
+    g_src and slots are None without need_src."""
+    B, Ct, N = src.shape
+    g_src = torch.empty_like(src) if need_src else None
+    slots = _amax_slots(Ct, src.device) if (with_slots and need_src) else None
+    layout, c0 = [], 0
+    for gy, (w, _, _, _) in zip(gouts, saved):
+        C = w.numel()
+        gy, gybs = _cotangent(gy, B, C, N, src.device)
+        layout.append(dict(x=_ptr(src) + c0 * N * 4, xbs=Ct * N, C=C, relu=0, gy=_ptr(gy), gybs=gybs, keep=gy,
+                           gx=None if g_src is None else _ptr(g_src) + c0 * N * 4, gxbs=Ct * N,
+                           amax=None if slots is None else _ptr(slots) + 4 * c0))
+        c0 += C
+    return g_src, slots, _norms_bwd(ctx, layout, saved, needs, B, N, src.device, count)
+
+
+def _split_fwd(x, norm_a, norm_b, stored, group=None):
+    _dev(x, norm_a[0], norm_b[0])
+    x = _f32c(x)
+    return (x,) + _ranges_fwd(x, [norm_a, norm_b], stored, group)
+
+
+class SplitBnFn(torch.autograd.Function):
+    """(bn_a(x[:, :Ca]), bn_b(x[:, Ca:])) — the two BatchNorms on the halves of the keys_values_pred output
+    (layers/multihead_ct.py:89-91), in training mode or, `stored`, on their running statistics with gradients (_ranges_fwd /
+    _ranges_bwd).  Arguments: stored, group, x, then the two norms (_norm_args each)."""
 
     @staticmethod
-    def forward(ctx, x, wa, ba, rma, rva, epsa, wb, bb, rmb, rvb, epsb):
-        _dev(x, wa, wb)
-        x = _f32c(x)
-        B, C, N = x.shape
-        Ca = wa.numel()
-        assert wb.numel() == C - Ca
-        items, outs, saved = [], [], []
-        for c0, w, b, rm, rv, eps in ((0, wa, ba, rma, rva, epsa), (Ca, wb, bb, rmb, rvb, epsb)):
-            w, b, rm, rv = _f32c(w), _f32c(b), _f32c(rm), _f32c(rv)
-            y = torch.empty(B, w.numel(), N, device=x.device, dtype=torch.float32)
-            items.append(dict(x=_ptr(x) + c0 * N * 4, xbs=C * N, C=w.numel(), w=w, b=b, rm=rm, rv=rv, eps=float(eps), relu=0,
-                              res=None, rbs=0, y=_ptr(y), ybs=0, amax=None))
-            outs.append(y)
-            saved += [w, b, rm, rv]
-        with _on(x.device):
-            _bn_eval_group(items, B, N)
-        ctx.save_for_backward(x, *saved)
-        ctx.eps = (float(epsa), float(epsb))
+    def forward(ctx, stored, group, x, *args):
+        norms = [args[:_NORM_ARGS], args[_NORM_ARGS:]]
+        x, outs, saved, count = _split_fwd(x, norms[0], norms[1], stored, group)
+        _save_norms(ctx, [x], norms, saved, count, stored, group)
         return outs[0], outs[1]
 
     @staticmethod
-    def backward(ctx, ga, gb):
-        x = ctx.saved_tensors[0]
-        saved = ctx.saved_tensors[1:]
-        B, C, N = x.shape
-        need_x = ctx.needs_input_grad[0]
-        gx = torch.empty_like(x) if need_x else None
-        items, grads, c0 = [], [gx], 0
-        for i, gy in enumerate((ga, gb)):
-            w, b, rm, rv = saved[i * 4:(i + 1) * 4]
-            Cs = w.numel()
-            gy, gybs = _cotangent(gy, B, Cs, N, x.device)
-            need_w, need_b = ctx.needs_input_grad[1 + 5 * i], ctx.needs_input_grad[2 + 5 * i]
-            g_w, g_b = _frozen_sums(Cs, x.device, need_w or need_b)
-            items.append(dict(x=_ptr(x) + c0 * N * 4, xbs=C * N, C=Cs, w=w, b=b, rm=rm, rv=rv, eps=ctx.eps[i], relu=0, gy=_ptr(gy),
-                              gybs=gybs, gx=None if gx is None else _ptr(gx) + c0 * N * 4, gxbs=C * N, gw=g_w, gb=g_b, keep=gy))
-            grads += [g_w if need_w else None, g_b if need_b else None, None, None, None]
-            c0 += Cs
-        with _on(x.device):
-            _bn_eval_group_bwd(items, B, N)
+    def backward(ctx, *gouts):
+        (x,), count, saved, needs = _saved_norms(ctx, 1)
+        at = [3 + _NORM_ARGS * i for i in range(2)]                       # each norm's weight among the inputs
+        gx, _, sums = _ranges_bwd(ctx, x, gouts, saved, [needs[a:a + 2] for a in at], needs[2], False, count)
+        grads = [None, None, gx]
+        for g_w, g_b in sums:
+            grads += [g_w, g_b] + [None] * (_NORM_ARGS - 2)
         return tuple(grads)
+
+
+def split_bn(x, bn_a, bn_b):
+    """(bn_a(x[:, :Ca]), bn_b(x[:, Ca:])) through SplitBnFn; the caller checked bn_relu_eligible for both modules (each
+    against its own slice's shape) and that x is contiguous."""
+    return SplitBnFn.apply(False, _sync_group(bn_a), x, *_norm_args(bn_a, False), *_norm_args(bn_b, False))
+
+
+def split_bn_eval(x, bn_a, bn_b):
+    """(bn_a(x[:, :Ca]), bn_b(x[:, Ca:])) of two eval-mode norms in one launch, the halves of x read where they lie; the
+    caller checked bn_eval_eligible for both (each against its own slice's channels)."""
+    outs = _split_fwd(x, _norm_args(bn_a, True, detach=True), _norm_args(bn_b, True, detach=True), True)[1]
+    return outs[0], outs[1]
 
 
 def split_bn_frozen(x, bn_a, bn_b):
     """(bn_a(x[:, :Ca]), bn_b(x[:, Ca:])) of two frozen norms with gradients; the caller checked bn_frozen_eligible for both
     (each against its own slice's channels)."""
-    return SplitBnFrozenFn.apply(x, bn_a.weight, bn_a.bias, bn_a.running_mean, bn_a.running_var, bn_a.eps,
-                                 bn_b.weight, bn_b.bias, bn_b.running_mean, bn_b.running_var, bn_b.eps)
+    return SplitBnFn.apply(True, None, x, *_norm_args(bn_a, True), *_norm_args(bn_b, True))
 
 
-class JoinBnReluFrozenFn(torch.autograd.Function):
-    """cat([relu(bn_i(x_i)) for i], dim=1) of frozen norms: join_bn_relu_eval's launch forward; every norm's backward reads
-    its range of the cotangent where it lies.  Arguments: n, then per head (x, weight, bias, running_mean, running_var, eps)."""
+# -- n norms + ReLU written into one concatenation -----------------------------------------------------------------------------
+def _join_layout(xs, c0s, y, slots):
+    """relu(norm_i(x_i)) into the channels from c0_i on of y [B,Ct,N], every norm's maxima into the same range of `slots`."""
+    Ct, N = y.size(1), y.size(2)
+    return [dict(x=_ptr(x), xbs=0, C=x.size(1), relu=1, res=None, rbs=0, y=_ptr(y) + c0 * N * 4, ybs=Ct * N,
+                 amax=None if slots is None else _ptr(slots) + 4 * c0) for x, c0 in zip(xs, c0s)]
 
-    PER_HEAD = 6
+
+def _join_fwd(xs, norms, stored, group=None):
+    """cat([relu(norm_i(x_i)) for i], dim=1): every norm writes its channel range of the result where it belongs; the separate
+    outputs and their copy never exist.  -> (y with one maxima tag over all its channels, the x_i as read, *_norms_fwd's results)"""
+    xs = [_f32c(x) for x in xs]
+    _dev(*xs)
+    B, _, N = xs[0].shape
+    sizes = [x.size(1) for x in xs]
+    y = torch.empty(B, sum(sizes), N, device=xs[0].device, dtype=torch.float32)
+    slots = _amax_slots(sum(sizes), y.device)
+    c0s = [sum(sizes[:i]) for i in range(len(xs))]
+    saved, count = _norms_fwd(_join_layout(xs, c0s, y, slots), norms, stored, B, N, y.device, group)
+    return tag_amax(y, slots), xs, saved, count
+
+
+class JoinBnReluFn(torch.autograd.Function):
+    """cat([relu(bn_i(x_i)) for i], dim=1) — the heads' `after` stacks of a union block followed by its concatenation
+    (layers/multihead_ct.py:67-68,187-196), in training mode or, `stored`, on the running statistics with gradients; in backward
+    every norm reads its range of the cotangent where it lies.  Arguments: stored, group, then per head x and its norm
+    (_norm_args)."""
+
+    PER_HEAD = 1 + _NORM_ARGS
 
     @staticmethod
-    def forward(ctx, n, *args):
-        P = JoinBnReluFrozenFn.PER_HEAD
-        heads = [args[i * P:(i + 1) * P] for i in range(n)]
-        xs = [_f32c(h[0]) for h in heads]
-        _dev(*xs)
-        B, _, N = xs[0].shape
-        Ct = sum(x.size(1) for x in xs)
-        y = torch.empty(B, Ct, N, device=xs[0].device, dtype=torch.float32)
-        slots = _amax_slots(Ct, y.device)
-        items, saved, c0 = [], [], 0
-        for x, (_, w, b, rm, rv, eps) in zip(xs, heads):
-            C = x.size(1)
-            w, b, rm, rv = _f32c(w), _f32c(b), _f32c(rm), _f32c(rv)
-            items.append(dict(x=_ptr(x), xbs=0, C=C, w=w, b=b, rm=rm, rv=rv, eps=float(eps), relu=1, res=None, rbs=0,
-                              y=_ptr(y) + c0 * N * 4, ybs=Ct * N, amax=None if slots is None else _ptr(slots) + 4 * c0))
-            saved += [x, w, b, rm, rv]
-            c0 += C
-        with _on(y.device):
-            _bn_eval_group(items, B, N)
-        tag_amax(y, slots)
-        ctx.save_for_backward(*saved)
-        ctx.n = n
-        ctx.eps = [float(h[5]) for h in heads]
+    def forward(ctx, stored, group, *args):
+        P = JoinBnReluFn.PER_HEAD
+        heads = [args[i:i + P] for i in range(0, len(args), P)]
+        norms = [h[1:] for h in heads]
+        y, xs, saved, count = _join_fwd([h[0] for h in heads], norms, stored, group)
+        _save_norms(ctx, xs, norms, saved, count, stored, group)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        P = JoinBnReluFrozenFn.PER_HEAD
-        saved = ctx.saved_tensors
+        P = JoinBnReluFn.PER_HEAD
+        n = (len(ctx.needs_input_grad) - 2) // P
+        xs, count, saved, needs = _saved_norms(ctx, n)
         B, Ct, N = gy.shape
-        gybs = _batch_stride(gy, Ct, N)
-        if gybs is None:
-            gy, gybs = _f32c(gy), Ct * N
-        items, grads, tags, c0 = [], [None], [], 0
-        for i in range(ctx.n):
-            x, w, b, rm, rv = saved[i * 5:(i + 1) * 5]
+        gy, gybs = _cotangent(gy, B, Ct, N, gy.device)
+        layout, gxs, c0 = [], [], 0
+        for i, x in enumerate(xs):
             C = x.size(1)
-            need_x, need_w, need_b = ctx.needs_input_grad[1 + P * i:4 + P * i]
-            gx = torch.empty_like(x) if need_x else None
-            slots = _amax_slots(C, x.device) if need_x else None
-            g_w, g_b = _frozen_sums(C, x.device, need_w or need_b)
-            items.append(dict(x=_ptr(x), xbs=0, C=C, w=w, b=b, rm=rm, rv=rv, eps=ctx.eps[i], relu=1, gy=_ptr(gy) + c0 * N * 4,
-                              gybs=gybs, gx=_ptr(gx), gxbs=0, gw=g_w, gb=g_b, amax=_ptr(slots)))
-            tags.append((gx, slots))
-            grads += [gx, g_w if need_w else None, g_b if need_b else None, None, None, None]
+            gx = torch.empty_like(x) if needs[2 + P * i] else None
+            slots = _amax_slots(C, x.device) if gx is not None else None
+            layout.append(dict(x=_ptr(x), xbs=0, C=C, relu=1, gy=_ptr(gy) + c0 * N * 4, gybs=gybs or Ct * N, gx=_ptr(gx), gxbs=0,
+                               amax=_ptr(slots)))
+            gxs.append((gx, slots))
             c0 += C
-        with _on(gy.device):
-            _bn_eval_group_bwd(items, B, N)
-        for gx, slots in tags:
-            if gx is not None:
-                tag_amax(gx, slots)
+        sums = _norms_bwd(ctx, layout, saved, [needs[3 + P * i:5 + P * i] for i in range(n)], B, N, gy.device, count)
+        grads = [None, None]
+        for (gx, slots), (g_w, g_b) in zip(gxs, sums):
+            grads += [gx if gx is None else tag_amax(gx, slots), g_w, g_b] + [None] * (_NORM_ARGS - 2)
         return tuple(grads)
+
+
+def _join_args(xs, bns, stored):
+    return [a for x, bn in zip(xs, bns) for a in (x,) + _norm_args(bn, stored)]
+
+
+def join_bn_relu(xs, bns):
+    """cat([relu(bn(x)) for x, bn in zip(xs, bns)], dim=1) through JoinBnReluFn; the caller checked bn_relu_eligible for
+    every pair."""
+    return JoinBnReluFn.apply(False, _sync_group(bns[0]), *_join_args(xs, bns, False))
+
+
+def join_bn_relu_eval(xs, bns):
+    """cat([relu(bn(x)) for x, bn in zip(xs, bns)], dim=1) of eval-mode norms; the result carries one maxima tag over all its
+    channels; the caller checked bn_eval_eligible for every pair."""
+    return _join_fwd(xs, [_norm_args(bn, True, detach=True) for bn in bns], True)[0]
 
 
 def join_bn_relu_frozen(xs, bns):
     """cat([relu(bn(x)) for x, bn in zip(xs, bns)], dim=1) of frozen norms with gradients; the caller checked
     bn_frozen_eligible for every pair."""
-    args = []
-    for x, bn in zip(xs, bns):
-        args += [x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps]
-    return JoinBnReluFrozenFn.apply(len(xs), *args)
+    return JoinBnReluFn.apply(True, None, *_join_args(xs, bns, True))
 
 
-class UnionKeysValuesFrozenFn(torch.autograd.Function):
-    """UnionKeysValuesFn for frozen norms: ONE stacked forward GEMM, the 2n norms on its channel ranges in one eval launch;
-    backward: the norms' input cotangents into the ranges of ONE tensor with its maxima slots (ct_bn_eval_group_bwd), one data
-    gradient GEMM (the identity shortcut's cotangent in its epilogue) and one weight gradient GEMM.  No statistics, so no
-    collective under SyncBatchNorm.  Arguments: n (< 0: passthrough, as UnionKeysValuesFn), x, then per head: weight [Co,Cin,1],
-    key_bn (w, b, rm, rv, eps), values_bn (same 5)."""
+def bn_relu_eval_into(joined, parts):
+    """relu(bn(x)) of eval-mode norms into the channels from c0 on of an existing concatenation `joined` [B,Ct,N], for every
+    (bn, x, c0) of `parts`, in one launch; no maxima are written and `joined` gets no tag.  The caller checked
+    bn_eval_eligible(bn, x) for every pair."""
+    B, _, N = joined.shape
+    _norms_fwd(_join_layout([x for _, x, _ in parts], [c0 for _, _, c0 in parts], joined, None),
+               [_norm_args(bn, True, detach=True) for bn, _, _ in parts], True, B, N, joined.device)
 
-    PER_HEAD = 11
+
+# -- stacked projection + 2n norms ------------------------------------------------------------------------------------------
+def _union_fwd(x, weights, norms, stored, group=None, need_dgrad=False):
+    """The heads' projections as ONE [sum Co, Cin] x [Cin, N] product per cloud and the norms on the channel ranges of its output
+    (_ranges_fwd).  -> ((x as read, the product, the stacked weight), pw_forward's (am_w, am_x, Wt), outs, *_norms_fwd's results)"""
+    x = _f32c(x)
+    _dev(x)
+    Wc = torch.cat([w[:, :, 0] for w in weights], dim=0)                # [sum Co, Cin]
+    y, am_w, am_x, Wt = pw_forward(Wc, x, need_dgrad)                   # [B, sum Co, N]
+    return ((x, y, Wc), (am_w, am_x, Wt)) + _ranges_fwd(y, norms, stored, group)
+
+
+def _kv_pairs(outs, n, passthrough=False):
+    """(key, values) per head from a union Function's flat outputs; passthrough: (x', that list)."""
+    first = 1 if passthrough else 0
+    pairs = [(outs[first + 2 * i], outs[first + 2 * i + 1]) for i in range(n)]
+    return (outs[0], pairs) if passthrough else pairs
+
+
+class UnionKeysValuesFn(torch.autograd.Function):
+    """The `keys_values_pred` projections of all heads of a union block and the key_bn / values_bn norms on their
+    outputs (layers/multihead_ct.py:31-33,89-91), as ONE GEMM with the heads' weights stacked: the heads share the input,
+    so forward is one [sum Co, Cin] x [Cin, N] product per cloud instead of one per head, the data gradient one product
+    with K = sum Co instead of one per head plus autograd's accumulation of their results, the weight gradient one
+    product.  The norms read their channel ranges of the GEMM output where they lie and write their input cotangents
+    into the ranges of ONE tensor with its maxima slots, which is the data / weight gradient GEMMs' operand.  In training mode
+    the 2n norms share ONE statistics all_gather in forward and ONE all_reduce in backward under SyncBatchNorm; `stored`: on the
+    running statistics with gradients — no statistics, so no collective.
+    Arguments: stored, group, passthrough, x, then per head: weight [Co,Cin,1], key_bn, values_bn (_norm_args each).
+    Returns (keys_res_0, values_0, keys_res_1, values_1, ...)."""
+
+    PER_HEAD = 1 + 2 * _NORM_ARGS
 
     @staticmethod
-    def forward(ctx, n, x, *args):
-        ctx.passthrough = n < 0
-        n = abs(n)
-        P = UnionKeysValuesFrozenFn.PER_HEAD
-        heads = [args[i * P:(i + 1) * P] for i in range(n)]
-        x_in = x
-        x = _f32c(x)
-        _dev(x)
-        B, Cin, N = x.shape
-        Wc = torch.cat([h[0][:, :, 0] for h in heads], dim=0)               # [sum Co, Cin]
-        Ct = Wc.size(0)
+    def forward(ctx, stored, group, passthrough, x, *args):
+        # passthrough: x itself as the first output too (the block's identity shortcut, layers/multihead_ct.py:170-176:
+        # its cotangent comes back here and rides the data gradient's epilogue instead of a separate add over three tensors)
+        ctx.passthrough = passthrough
+        P = UnionKeysValuesFn.PER_HEAD
+        heads = [args[i:i + P] for i in range(0, len(args), P)]
+        norms = [h[1 + _NORM_ARGS * j:1 + _NORM_ARGS * (j + 1)] for h in heads for j in range(2)]
         ctx.pw_precision = _prec.code()      # the layer's three products share the forward's precision (precision.py)
-        y, am_w, am_x, Wt = pw_forward(Wc, x, ctx.needs_input_grad[1])      # [B, sum Co, N]
-        outs, items, saved, meta, c0 = [], [], [], [], 0
-        for h in heads:
-            for (w, b, rm, rv, eps) in (h[1:6], h[6:11]):
-                w, b, rm, rv = _f32c(w), _f32c(b), _f32c(rm), _f32c(rv)
-                C = w.numel()
-                o = torch.empty(B, C, N, device=x.device, dtype=torch.float32)
-                items.append(dict(x=_ptr(y) + c0 * N * 4, xbs=Ct * N, C=C, w=w, b=b, rm=rm, rv=rv, eps=float(eps), relu=0,
-                                  res=None, rbs=0, y=_ptr(o), ybs=0, amax=None))
-                outs.append(o)
-                saved += [w, b, rm, rv]
-                meta.append((c0, C, float(eps)))
-                c0 += C
-        assert c0 == Ct, "key_bn + values_bn must cover the projections"
-        with _on(x.device):
-            _bn_eval_group(items, B, N)
-        ctx.save_for_backward(x, y, Wc, *saved)
-        ctx.am = (am_w, am_x, Wt)
-        ctx.meta = meta
+        tensors, ctx.am, outs, saved, count = _union_fwd(x, [h[0] for h in heads], norms, stored, group, ctx.needs_input_grad[3])
+        _save_norms(ctx, tensors, norms, saved, count, stored, group)
         ctx.couts = [h[0].size(0) for h in heads]
-        if ctx.passthrough:
-            return (x_in,) + tuple(outs)
-        return tuple(outs)
+        return ((x,) if ctx.passthrough else ()) + tuple(outs)
 
     @staticmethod
     def backward(ctx, *gouts):
-        P = UnionKeysValuesFrozenFn.PER_HEAD
+        P = UnionKeysValuesFn.PER_HEAD
         g_skip = None
         if ctx.passthrough:
             g_skip, gouts = gouts[0], gouts[1:]
-        x, y, Wc = ctx.saved_tensors[:3]
-        saved = ctx.saved_tensors[3:]
-        B, Cin, N = x.shape
-        Ct = Wc.size(0)
-        need_x = ctx.needs_input_grad[1]
-        need_W = any(ctx.needs_input_grad[2 + P * h] for h in range(len(ctx.couts)))
-        g_y = torch.empty_like(y) if (need_x or need_W) else None
-        slots = _amax_slots(Ct, x.device) if g_y is not None else None
-        items, sums = [], []
-        for i, (c0, C, eps) in enumerate(ctx.meta):
-            w, b, rm, rv = saved[i * 4:(i + 1) * 4]
-            gy, gybs = _cotangent(gouts[i], B, C, N, x.device)
-            at = 2 + P * (i // 2) + 1 + 5 * (i % 2)                        # this norm's weight among the inputs
-            need_w, need_b = ctx.needs_input_grad[at], ctx.needs_input_grad[at + 1]
-            g_w, g_b = _frozen_sums(C, x.device, need_w or need_b)
-            sums.append((g_w if need_w else None, g_b if need_b else None))
-            items.append(dict(x=_ptr(y) + c0 * N * 4, xbs=Ct * N, C=C, w=w, b=b, rm=rm, rv=rv, eps=eps, relu=0, gy=_ptr(gy),
-                              gybs=gybs, gx=None if g_y is None else _ptr(g_y) + c0 * N * 4, gxbs=Ct * N, gw=g_w, gb=g_b, keep=gy,
-                              amax=None if slots is None else _ptr(slots) + 4 * c0))
-        with _on(x.device):
-            _bn_eval_group_bwd(items, B, N)
+        (x, y, Wc), count, saved, needs = _saved_norms(ctx, 3)
+        need_x = ctx.needs_input_grad[3]
+        need_W = any(needs[4 + P * h] for h in range(len(ctx.couts)))
+        at = [4 + P * (i // 2) + 1 + _NORM_ARGS * (i % 2) for i in range(len(saved))]      # each norm's weight among the inputs
+        g_y, slots, sums = _ranges_bwd(ctx, y, gouts, saved, [needs[a:a + 2] for a in at], need_x or need_W, True, count)
         g_x = g_Wc = None
         if g_y is not None:
             g_x, g_Wc = pw_backward(Wc, x, g_y, ctx.am[0], ctx.am[1], need_x, need_W,
@@ -2047,27 +1628,211 @@ class UnionKeysValuesFrozenFn(torch.autograd.Function):
                                     add_gx=g_skip if need_x else None, precision=ctx.pw_precision)      # g_Wc [sum Co, Cin]
         elif need_x:
             g_x = g_skip
-        grads, r0 = [None, g_x], 0
+        grads, r0 = [None, None, None, g_x], 0
         for hi, Co in enumerate(ctx.couts):
-            (gwk, gbk), (gwv, gbv) = sums[2 * hi], sums[2 * hi + 1]
-            g_W = g_Wc[r0:r0 + Co].unsqueeze(-1) if (g_Wc is not None and ctx.needs_input_grad[2 + P * hi]) else None
-            grads += [g_W, gwk, gbk, None, None, None, gwv, gbv, None, None, None]
+            grads.append(g_Wc[r0:r0 + Co].unsqueeze(-1) if (g_Wc is not None and needs[4 + P * hi]) else None)
+            for g_w, g_b in sums[2 * hi:2 * hi + 2]:
+                grads += [g_w, g_b] + [None] * (_NORM_ARGS - 2)
             r0 += Co
         return tuple(grads)
 
 
-def union_keys_values_frozen(x, convs, key_bns, values_bns, passthrough=False):
-    """union_keys_values for frozen norms with gradients (UnionKeysValuesFrozenFn); the caller checked
-    union_keys_values_frozen_eligible.  passthrough as union_keys_values."""
+def _union_args(convs, key_bns, values_bns, stored):
     args = []
     for conv, kb, vb in zip(convs, key_bns, values_bns):
-        args.append(conv.weight)
-        for bn in (kb, vb):
-            args += [bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps]
-    outs = UnionKeysValuesFrozenFn.apply(-len(convs) if passthrough else len(convs), x, *args)
-    if passthrough:
-        return outs[0], [(outs[1 + 2 * i], outs[2 + 2 * i]) for i in range(len(convs))]
-    return [(outs[2 * i], outs[2 * i + 1]) for i in range(len(convs))]
+        args += (conv.weight,) + _norm_args(kb, stored) + _norm_args(vb, stored)
+    return args
+
+
+def union_keys_values(x, convs, key_bns, values_bns, passthrough=False):
+    """[(key_bn_i(y_i[:, :Ck]), values_bn_i(y_i[:, Ck:])) with y_i = conv_i(x)] for the heads of a union block through
+    UnionKeysValuesFn; the caller checked union_keys_values_eligible.  passthrough: -> (x', that list) with x' = x as an output
+    of the same node — the block's identity shortcut takes x' so that its cotangent is summed inside the data gradient."""
+    return _kv_pairs(UnionKeysValuesFn.apply(False, _sync_group(key_bns[0]), passthrough, x,
+                                             *_union_args(convs, key_bns, values_bns, False)), len(convs), passthrough)
+
+
+def union_keys_values_frozen(x, convs, key_bns, values_bns, passthrough=False):
+    """union_keys_values for frozen norms with gradients; the caller checked union_keys_values_frozen_eligible."""
+    return _kv_pairs(UnionKeysValuesFn.apply(True, None, passthrough, x,
+                                             *_union_args(convs, key_bns, values_bns, True)), len(convs), passthrough)
+
+
+def union_keys_values_eval(x, convs, key_bns, values_bns):
+    """[(key_bn_i(y_i[:, :Ck]), values_bn_i(y_i[:, Ck:])) with y_i = conv_i(x)] for the heads of a union block in eval mode:
+    ONE stacked projection GEMM with the 2n norms in its epilogue (PW_NORM, 2n <= BN_GROUP_MAX and a product the forward
+    kernel takes), else that GEMM and then the norms on its channel ranges in one launch; the caller checked
+    union_keys_values_eval_eligible."""
+    bns = [bn for kb, vb in zip(key_bns, values_bns) for bn in (kb, vb)]
+    weights = [conv.weight.detach() for conv in convs]
+    B, _, N = x.shape
+    if _pw_norm_takes(sum(w.size(0) for w in weights), weights[0].size(1), N, len(bns), PW_FWD):
+        # the 2n norms in the stacked GEMM's epilogue: the [B, sum Co, N] tensor is never written
+        x = _f32c(x)
+        _dev(x)
+        outs = [torch.empty(B, bn.num_features, N, device=x.device, dtype=torch.float32) for bn in bns]
+        pw_gemm_norm(torch.cat([w[:, :, 0] for w in weights], dim=0), x,
+                     [_bn_eval_item(bn, None, 0, _ptr(o), 0, False) for bn, o in zip(bns, outs)])
+    else:
+        outs = _union_fwd(x, weights, [_norm_args(bn, True, detach=True) for bn in bns], True)[2]
+    return _kv_pairs(outs, len(convs))
+
+
+# ---------------------------------------------------------------------------
+# which norms take the fused kernels, and in which mode
+# ---------------------------------------------------------------------------
+_bn_supported = {}
+_bn_eval_supported = {}
+
+
+def _shape_ok(cache, supported, key):
+    """The library's answer to `supported`(B, C, N), asked once per shape."""
+    ok = cache.get(key)
+    if ok is None:
+        ok = cache[key] = bool(getattr(_lib.load(), supported)(*key))
+    return ok
+
+
+def _input_ok(x, aligned=True):
+    """x CUDA fp32 [B,C,N] contiguous and, with `aligned`, 16-byte aligned."""
+    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()
+            and (not aligned or x.data_ptr() % 16 == 0))
+
+
+def _residual_ok(residual):
+    """No residual, or a CUDA fp32 3-D one (_residual_arg reads it where it lies or copies it)."""
+    return residual is None or (residual.is_cuda and residual.dtype == torch.float32 and residual.dim() == 3)
+
+
+def _conv1x1_ok(conv, x, Co, weight_like_x=True):
+    """A plain bias-free 1x1 nn.Conv1d from x's channels to Co and, with `weight_like_x`, an fp32 weight on x's device."""
+    return (isinstance(conv, torch.nn.Conv1d) and conv.kernel_size == (1,) and conv.stride == (1,) and conv.padding == (0,)
+            and conv.dilation == (1,) and conv.groups == 1 and conv.bias is None and conv.in_channels == x.size(1)
+            and conv.out_channels == Co
+            and (not weight_like_x or (conv.weight.dtype == torch.float32 and conv.weight.device == x.device)))
+
+
+def _bn_train_norm_ok(bn, B, C, N):
+    """A training-mode affine norm of C channels with running statistics and a fixed momentum whose shape the register-resident
+    ct_bn_group_* kernels take."""
+    return (type(bn) in _BN_TYPES and bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None
+            and C == bn.num_features and _shape_ok(_bn_supported, "ct_bn_relu_supported", (B, C, N)))
+
+
+def _bn_eval_norm_ok(bn, B, C, N):
+    """An eval-mode affine norm of C channels with running statistics whose shape ct_bn_eval_* takes."""
+    return (type(bn) in _BN_TYPES and not bn.training and bn.affine and bn.track_running_stats
+            and bn.running_mean is not None and bn.running_var is not None and C == bn.num_features
+            and bn.weight.dtype == torch.float32 and bn.running_mean.dtype == torch.float32
+            and _shape_ok(_bn_eval_supported, "ct_bn_eval_supported", (B, C, N)))
+
+
+def _bn_train_ok(bn, x, C):
+    return _bn_train_norm_ok(bn, x.size(0), C, x.size(2))
+
+
+def _bn_stored_ok(bn, x, C):
+    return _bn_eval_norm_ok(bn, x.size(0), C, x.size(2)) and bn.weight.device == x.device
+
+
+def _channels(x, channels):
+    return x.size(1) if channels is None and x.dim() == 3 else channels
+
+
+def _records_nothing(*tensors):
+    """True when autograd would record nothing for an op on `tensors` (None entries skipped)."""
+    return not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in tensors)
+
+
+def records_gradients(*tensors):
+    """True when autograd would record an op on `tensors` (None entries skipped): the other half of a frozen norm's routing
+    rule — where nothing is recorded the eval functions take the norm, marked or not."""
+    return not _records_nothing(*tensors)
+
+
+def norm_frozen(bn):
+    """True for a norm marked by freeze_norms (norms.py)."""
+    return bool(getattr(bn, "_ct_frozen", False))
+
+
+def _affine(bns):
+    return [p for bn in bns for p in (bn.weight, bn.bias)]
+
+
+def bn_relu_eligible(bn, x, channels=None):
+    """True when `bn` (an nn.BatchNorm1d / nn.SyncBatchNorm, exactly) applied to x (or, with `channels`, to a slice of that many
+    of its channels) can run as ct_bn_group_*: training mode with running statistics and a fixed momentum, affine, CUDA fp32
+    [B,C,N] contiguous and 16-byte aligned, and a shape the register-resident kernels take (ct_bn_relu_supported)."""
+    return _input_ok(x) and _bn_train_ok(bn, x, _channels(x, channels))
+
+
+def bn_eval_eligible(bn, x, channels=None, residual=None):
+    """True when `bn` applied to x (or, with `channels`, to a slice of that many of its channels) can run as
+    ct_bn_eval_group_fwd: an nn.BatchNorm1d / nn.SyncBatchNorm (exactly) in eval mode, affine, with running statistics; x CUDA
+    fp32 [B,C,N] contiguous and 16-byte aligned; a shape ct_bn_eval_supported takes; and nothing for autograd to record
+    (grad mode off, or none of x, the affine parameters and `residual` requires grad)."""
+    return (BN_EVAL and _input_ok(x) and _residual_ok(residual) and _bn_stored_ok(bn, x, _channels(x, channels))
+            and _records_nothing(x, bn.weight, bn.bias, residual))
+
+
+def bn_frozen_eligible(bn, x, channels=None, residual=None):
+    """bn_eval_eligible without its "nothing to record" clause, for a norm that freeze_norms marked."""
+    return (BN_FROZEN and norm_frozen(bn) and _input_ok(x) and _residual_ok(residual)
+            and _bn_stored_ok(bn, x, _channels(x, channels)))
+
+
+def _union_ok(x, convs, key_bns, values_bns, norm_ok, strict=True):
+    """More than one plain bias-free 1x1 Conv1d projection of x, each covered by its two norms, every norm passing
+    norm_ok(bn, x, C).  The training form is not `strict`: it asks neither for x's alignment nor for the weights' dtype and
+    device."""
+    return (_input_ok(x, aligned=strict) and len(convs) > 1
+            and all(_conv1x1_ok(conv, x, kb.num_features + vb.num_features, weight_like_x=strict)
+                    and norm_ok(kb, x, kb.num_features) and norm_ok(vb, x, vb.num_features)
+                    for conv, kb, vb in zip(convs, key_bns, values_bns)))
+
+
+def union_keys_values_eligible(x, convs, key_bns, values_bns):
+    """Plain bias-free 1x1 Conv1d projections of the same input and training-mode norms the fused kernels take, of one type and
+    one process group."""
+    return _union_ok(x, convs, key_bns, values_bns, _bn_train_ok, strict=False) and norms_share_group(list(key_bns) + list(values_bns))
+
+
+def union_keys_values_eval_eligible(x, convs, key_bns, values_bns):
+    """Plain bias-free 1x1 Conv1d projections of the same input, eval-mode norms ct_bn_eval_* takes, and nothing for
+    autograd to record."""
+    return (BN_EVAL and _union_ok(x, convs, key_bns, values_bns, _bn_stored_ok)
+            and _records_nothing(x, *[conv.weight for conv in convs], *_affine(list(key_bns) + list(values_bns))))
+
+
+def union_keys_values_frozen_eligible(x, convs, key_bns, values_bns):
+    """union_keys_values_eval_eligible without its "nothing to record" clause, every norm marked by freeze_norms."""
+    return BN_FROZEN and _union_ok(x, convs, key_bns, values_bns, lambda bn, x, C: norm_frozen(bn) and _bn_stored_ok(bn, x, C))
+
+
+def norm_route(norms, residual=None, watch=(), convs=None):
+    """Which fused path takes a group of norms: "train", "eval", "frozen" or None (the modules).  norms: [(bn, x, channels)] —
+    one x per norm for a join, one shared x whose channel ranges the norms read for a split (channels None: all of x's); with
+    `convs` the union form: the norms are (key_bn, values_bn) per projection of the shared x.  `residual`: added by a single
+    norm's launch; `watch`: further tensors whose gradients the forward would have to record (the union's conv weights).
+    Train needs training-mode norms, eval and frozen eval-mode ones; eval needs nothing recorded, frozen the mark and something
+    recorded: at most one of the three holds, whatever the order they are asked in."""
+    bns = [bn for bn, _, _ in norms]
+    if convs is not None:
+        union = (norms[0][1], convs, bns[0::2], bns[1::2])
+        if union_keys_values_eligible(*union):
+            return "train"
+        if union_keys_values_eval_eligible(*union):
+            return "eval"
+        stored = union_keys_values_frozen_eligible(*union)
+    else:
+        if all(bn_relu_eligible(bn, x, C) for bn, x, C in norms) and norms_share_group(bns):
+            return "train"
+        if all(bn_eval_eligible(bn, x, C, residual) for bn, x, C in norms):
+            return "eval"
+        stored = all(bn_frozen_eligible(bn, x, C, residual) for bn, x, C in norms)
+    if stored and records_gradients(*[x for _, x, _ in norms], *_affine(bns), residual, *watch):
+        return "frozen"
+    return None
 
 
 # ---------------------------------------------------------------------------
@@ -2089,25 +1854,11 @@ def pw_norm_eligible(conv, bns, x, residual=None, mode=PW_FWD):
     output can run as ONE ct_pw_gemm_rs_norm call: x CUDA fp32 [B,Ci,N] contiguous and 16-byte aligned, at most BN_GROUP_MAX
     norms that cover the output channels, each one ct_bn_eval_* takes, a product ct_pw_gemm takes, and nothing for autograd
     to record (bn_eval_eligible's rule)."""
-    if not (PW_NORM and BN_EVAL and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()
-            and x.data_ptr() % 16 == 0 and all(type(bn) in _BN_TYPES for bn in bns)):
-        return False
-    if not (isinstance(conv, torch.nn.Conv1d) and conv.kernel_size == (1,) and conv.stride == (1,) and conv.padding == (0,)
-            and conv.dilation == (1,) and conv.groups == 1 and conv.bias is None and conv.in_channels == x.size(1)
-            and conv.weight.dtype == torch.float32 and conv.weight.device == x.device
-            and conv.out_channels == sum(bn.num_features for bn in bns)):
-        return False
-    if residual is not None and not (residual.is_cuda and residual.dtype == torch.float32 and residual.dim() == 3):
-        return False
-    B, Ci, N = x.shape
-    if not _pw_norm_takes(conv.out_channels, Ci, N, len(bns), mode):
-        return False
-    watched = [x, conv.weight, residual]
-    for bn in bns:
-        if not (_bn_eval_norm_ok(bn, B, bn.num_features, N) and bn.weight.device == x.device):
-            return False
-        watched += [bn.weight, bn.bias]
-    return _records_nothing(*watched)
+    return (PW_NORM and BN_EVAL and _input_ok(x) and all(type(bn) in _BN_TYPES for bn in bns)
+            and _conv1x1_ok(conv, x, sum(bn.num_features for bn in bns)) and _residual_ok(residual)
+            and _pw_norm_takes(conv.out_channels, x.size(1), x.size(2), len(bns), mode)
+            and all(_bn_stored_ok(bn, x, bn.num_features) for bn in bns)
+            and _records_nothing(x, conv.weight, residual, *_affine(bns)))
 
 
 def pw_gemm_norm(W, x, items, want_amax=False):
@@ -2139,11 +1890,7 @@ def pw_bn_eval(x, conv, bn, relu=True, residual=None):
     B, _, N = x.shape
     C = bn.num_features
     y = torch.empty(B, C, N, device=x.device, dtype=torch.float32)
-    rbs = 0
-    if residual is not None:
-        rbs = _batch_stride(residual, C, N)
-        if rbs is None:
-            residual, rbs = _f32c(residual), 0
+    residual, rbs = _residual_arg(residual, C, N)
     slots = pw_gemm_norm(conv.weight.detach()[:, :, 0], x, [_bn_eval_item(bn, None, 0, _ptr(y), 0, relu, _ptr(residual), rbs)],
                          want_amax=True)
     if slots is not None:
