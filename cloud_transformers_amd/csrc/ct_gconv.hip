@@ -24,10 +24,12 @@
 // The quad, K-split and dense 2^d forms of the forward kernel (gconv_fwd4_kernel, gconv_fwd4k_kernel, gconv_tiny_kernel; further
 // down) also exist as a NORM template variant: ct_gconv_fwd_norm applies the eval-mode BatchNorm, the skip connection and the
 // ReLU of a grouped Res block to the values in their stores (GconvEpi below).  No atomics; the plain instantiations are the
-// code they were without the variant, and the variants' launches stand last in the file so that they also stay where they were.
+// code they were without the variant.
 // The quad and K-split forms also exist as an F16 template variant (plain and NORM): under ct_set_gconv_precision(HIGH) the
 // operands are packed in place into 11-bit f16 images and multiplied on v_mfma_f32_16x16x16_f16 with fp32 accumulators (see
-// g16_pack_tile).  The same plans and tags; launched after the NORM variants, for the same reason.
+// g16_pack_tile).  The same plans and tags.
+// Where each instantiation sits in the code object is pinned by the list of instantiations after the last kernel, not
+// by the order of the launches in the host half (the planner below it: a plan is a value, one launch function per family).
 #include "ct_common.h"
 #include <atomic>
 #include <type_traits>
@@ -2194,6 +2196,39 @@ __global__ void gconv_bias_grad_kernel(const float* gy, float* gbias, int B, int
   if (threadIdx.x == 0) gbias[c] = red[0] + red[1] + red[2] + red[3];
 }
 
+// ---- every template instantiation of this file, in the order the kernels have in the code object ----
+// Every kernel here sits in the anonymous namespace, so the compiler defers its emission to the end of the translation unit: first
+// the four kernels that are no templates, in the order of their definitions above, then the implicit instantiations in the order in
+// which the translation unit first names them — and that is here, whatever order the host code below launches them in.  The order
+// was measured to matter: the plain kernels, then the NORM variants, then the one-term f16 variants
+// (tools/dev/kernel_digest.py --order prints it from an object file).  A launch of an instantiation that is not listed would
+// append it at the end.  Explicit instantiation definitions are NOT used: they are emitted eagerly, where they stand, which puts
+// the templates ahead of the four deferred non-template kernels and so changes the order this file always had.
+template <typename... K> constexpr int kernels_in_order(K...) { return sizeof...(K); }
+#define CT_F4K_123(DIMV, TRV, NORMV, F16V) \
+  gconv_fwd4k_kernel<DIMV, 1, TRV, NORMV, F16V>, gconv_fwd4k_kernel<DIMV, 2, TRV, NORMV, F16V>, gconv_fwd4k_kernel<DIMV, 4, TRV, NORMV, F16V>
+static_assert(kernels_in_order(
+    gconv_c4_mfma3_kernel<true>, gconv_c4_mfma3_kernel<false>,
+    gconv_c4_kernel<2, true>, gconv_c4_kernel<2, false>, gconv_c4_kernel<3, true>, gconv_c4_kernel<3, false>,
+    gconv_fwd4_kernel<2, false, false>, gconv_fwd4_kernel<3, false, false>,
+    CT_F4K_123(2, true, false, false), CT_F4K_123(2, false, false, false), CT_F4K_123(3, true, false, false), CT_F4K_123(3, false, false, false),
+    gconv_tiny_kernel<2, false>, gconv_tiny_kernel<3, false>, gconv_fwd_kernel<2>, gconv_fwd_kernel<3>,
+    gconv_wrw_ring_kernel<2, false, kWrwThreads>, gconv_wrw_ring_kernel<3, false, kWrwThreads>, gconv_wrw_ring_kernel<2, true, kThreads>,
+    gconv_wrw_ring_kernel<3, true, kThreads>, gconv_bwd_weight_kernel<2>, gconv_bwd_weight_kernel<3>,
+    gconv_wrw_small_kernel<2, 2>, gconv_wrw_small_kernel<2, 4>, gconv_wrw_small_kernel<2, 8>, gconv_wrw_small_kernel<2, 16>,
+    gconv_wrw_small_kernel<3, 2>, gconv_wrw_small_kernel<3, 4>, gconv_wrw_small_kernel<3, 8>, gconv_wrw_small_kernel<3, 16>,
+    gconv_wrw_mfma_kernel<2, 4>, gconv_wrw_mfma_kernel<2, 8>, gconv_wrw_mfma_kernel<2, 16>, gconv_wrw_mfma_kernel<3, 4>,
+    gconv_wrw_mfma_kernel<3, 8>, gconv_wrw_mfma_kernel<3, 16>,
+    // NORM (a forward write-out: no transposed bank)
+    gconv_fwd4_kernel<2, true, false>, gconv_fwd4_kernel<3, true, false>, CT_F4K_123(2, false, true, false), CT_F4K_123(3, false, true, false),
+    gconv_tiny_kernel<2, true>, gconv_tiny_kernel<3, true>,
+    // one-term f16, NORM and plain
+    gconv_fwd4_kernel<2, true, true>, gconv_fwd4_kernel<2, false, true>, gconv_fwd4_kernel<3, true, true>, gconv_fwd4_kernel<3, false, true>,
+    CT_F4K_123(2, false, true, true), CT_F4K_123(3, false, true, true),
+    CT_F4K_123(2, true, false, true), CT_F4K_123(2, false, false, true), CT_F4K_123(3, true, false, true), CT_F4K_123(3, false, false, true))
+    == 76, "the instantiation set of this file");
+#undef CT_F4K_123
+
 bool plan_tiles_min_halo(GconvArgs& a, int dim, size_t extra_per_pos_bytes, size_t fixed_bytes, int cin_planes,
                          int plane_mod, size_t budget) {
   // LDS per workgroup = cin_planes*plane*4 + fixed + extra_per_pos*TD*TH*W  <= budget.
@@ -2247,10 +2282,10 @@ bool plan_tiles_budget(GconvArgs& a, int dim, size_t extra_per_pos_bytes, size_t
   return false;
 }
 
-bool plan_tiles(GconvArgs& a, int dim, size_t extra_per_pos_bytes, size_t fixed_bytes, int cin_planes, int plane_mod,
-                size_t budget = kLdsBudget) {
-  return plan_tiles_budget(a, dim, extra_per_pos_bytes, fixed_bytes, cin_planes, plane_mod, budget) ||
-         plan_tiles_budget(a, dim, extra_per_pos_bytes, fixed_bytes, cin_planes, plane_mod, kLdsBudgetMax);
+// a policy (plan_tiles_min_halo or plan_tiles_budget) at the small budget, then at the large one
+template <typename Policy>
+bool plan_tiles(Policy policy, GconvArgs& a, int dim, size_t extra, size_t fixed, int cin_planes, int plane_mod, size_t budget = kLdsBudget) {
+  return policy(a, dim, extra, fixed, cin_planes, plane_mod, budget) || policy(a, dim, extra, fixed, cin_planes, plane_mod, kLdsBudgetMax);
 }
 
 int gconv_common(GconvArgs& a, int B, int groups, int Cin, int Cout, int dim, const int* W) {
@@ -2284,87 +2319,13 @@ int pick_msplit(const GconvArgs& a) {
   return m;
 }
 
-// four-channel groups in 3D with rows of 16-position blocks: the matrix-core kernel (see gconv_c4_mfma3_kernel)
-int c4_mfma3_rows(const GconvArgs& a) {
-  const int XB = a.W >> 4;
-  int TH = (kC4mCols * (kC4mThreads / 64)) / XB;              // columns of a workgroup: rows x 16-position blocks
-  return TH > a.H ? a.H : TH;
-}
-
-bool c4_mfma3_fits(const GconvArgs& a) {
-  if ((a.W & 15) != 0 || a.W > 16 * kC4mCols * (kC4mThreads / 64)) return false;
-  const int TH = c4_mfma3_rows(a);
-  if (TH < 1) return false;
-  // the kernel's static bounds: LDS-DMA pieces per wave (2) and 16-byte stores per thread (2) and slice
-  const int ppc = ((TH + 2) * a.W / 4 + 63) / 64;
-  return 4 * ppc <= 2 * (kC4mThreads / 64) && TH * a.W <= 2 * kC4mThreads;
-}
-
-int launch_c4_mfma3(GconvArgs a, hipStream_t st) {
-  const int TH = c4_mfma3_rows(a);
-  const int nH = (a.H + TH - 1) / TH;
-  // depth segments until the chip is covered (each walks two extra slices)
-  int nZ = 1;
-  while ((long long)a.B * a.groups * nH * nZ < CT_C4M_WGS && a.D / (nZ * 2) >= 4) nZ *= 2;
-  const int LZ = (a.D + nZ - 1) / nZ;
-  nZ = (a.D + LZ - 1) / LZ;
-  int CSX = (TH + 2) * a.W;
-  CSX += (16 - (CSX & 31) + 32) & 31;                         // == 16 (mod 32): the four channels' 16-float runs fall on all 32 banks twice
-  const size_t lds = ((size_t)3 * 4 * CSX + (size_t)2 * 4 * TH * a.W + 2 * kSlack) * 4;
-  dim3 grid(nH * nZ, a.groups, a.B);
-  note("c4_mfma3");
-  CT_CLEAR_ERROR();
-  if (a.transposed) {
-    if (set_lds_attr(gconv_c4_mfma3_kernel<true>, lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL(gconv_c4_mfma3_kernel<true>, grid, dim3(kC4mThreads), lds, st, a, TH, LZ, nZ, CSX);
-  } else {
-    if (set_lds_attr(gconv_c4_mfma3_kernel<false>, lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL(gconv_c4_mfma3_kernel<false>, grid, dim3(kC4mThreads), lds, st, a, TH, LZ, nZ, CSX);
-  }
-  CT_CHECK_LAUNCH();
-  return CT_OK;
-}
-
-// four-channel groups with 16-byte rows: the vector-ALU kernel
-int launch_c4(GconvArgs a, int dim, hipStream_t st) {
-  if (!plan_tiles_min_halo(a, dim, 0, 0, 4, 4, kLdsBudget) && !plan_tiles_min_halo(a, dim, 0, 0, 4, 4, kLdsBudgetMax)) return CT_EINVAL;
-  const size_t lds = (size_t)4 * a.plane * 4 + 2 * kSlack * 4;
-  dim3 grid(a.nD * a.nH, a.groups, a.B);
-  note("c4_valu");
-  CT_CLEAR_ERROR();
-#define CT_C4_LAUNCH(DIMV, TR)                                                              \
-  do {                                                                                      \
-    if (set_lds_attr(gconv_c4_kernel<DIMV, TR>, lds) != CT_OK) return CT_ELAUNCH;           \
-    hipLaunchKernelGGL((gconv_c4_kernel<DIMV, TR>), grid, dim3(kThreads), lds, st, a);      \
-  } while (0)
-  if (dim == 2) { if (a.transposed) CT_C4_LAUNCH(2, true); else CT_C4_LAUNCH(2, false); }
-  else { if (a.transposed) CT_C4_LAUNCH(3, true); else CT_C4_LAUNCH(3, false); }
-#undef CT_C4_LAUNCH
-  CT_CHECK_LAUNCH();
-  return CT_OK;
-}
-
-// quad form of the MFMA kernel (rows of W % 4 == 0 floats, 16-byte aligned tensors)
-// The launches of the NORM variants (ct_gconv_fwd_norm) stand at the end of the file, after every other launch: a template is
-// emitted where it is first used, and there the kernels this file had before the variants keep their order in the code object.
-// Each notes the tags the plain launch of the same plan notes.
-int launch_fwd4_norm(const GconvArgs& a, const GconvEpi& e, int dim, dim3 grid, int threads, size_t lds, hipStream_t st);
-int launch_fwd4k_norm(const GconvArgs& t, const GconvEpi& e, int dim, int pass, int maxi, int dma, dim3 grid, size_t lds, hipStream_t st);
-int launch_tiny_norm(const GconvArgs& a, const GconvEpi& e, int dim, int cob, dim3 grid, size_t lds, hipStream_t st);
-// ... and after them the launches of the one-term f16 variants (plain and NORM), for the same reason
-int launch_fwd4_f16(const GconvArgs& a, const GconvEpi* e, int dim, dim3 grid, int threads, size_t lds, hipStream_t st);
-int launch_fwd4k_f16(const GconvArgs& t, const GconvEpi* e, int dim, int pass, int maxi, int dma, dim3 grid, size_t lds, hipStream_t st);
-
 // Precision mode (ct_set_gconv_precision, include/cloudct.h): process-wide, read ONCE per entry point and handed
-// down to the planner as `prec`; the calling thread's override wins.  No kernel reads it.
+// to the launch as `prec`; the calling thread's override wins.  Neither the planner nor a kernel reads it.
 std::atomic<int> g_gconv_precision{CT_GCONV_PRECISION_HIGHEST};
 thread_local int t_gconv_precision_override = -1;
 inline int gconv_precision_now() {
   return t_gconv_precision_override >= 0 ? t_gconv_precision_override : g_gconv_precision.load(std::memory_order_relaxed);
 }
-// What the planner hands back beside the return code: whether the plan it settled on is a one-term kernel under
-// CT_GCONV_PRECISION_HIGH (ct_gconv_precision_covers)
-struct FwdTook { bool one_term = false; };
 // The quad form takes the one-term kernel from 16 input channels per group on (one full f16 MFMA group; below it most k slots
 // would carry zeros).  The K-split form takes it from four spans of 16 quads per tile on: every contraction block pays for
 // packing its planes and its bank slice, which a 4^3 volume's single span does not earn back (measured: 8^3 1.5 - 2.0x,
@@ -2375,56 +2336,88 @@ inline bool quad_one_term(const GconvArgs& a) { return a.Cin >= 16; }
 #endif
 inline bool ksplit_one_term(int nspans) { return nspans >= CT_GCONV_F16_SPANS; }
 
-// (e: the NORM write-out of ct_gconv_fwd_norm, the same plan and tags; plan_only: settle the plan and return before the launch)
-int launch_fwd4(GconvArgs a, int dim, hipStream_t st, const GconvEpi* e = nullptr, bool plan_only = false, int prec = 0,
-                FwdTook* took = nullptr) {
-  const int NR = dim == 3 ? 9 : 3;
-  const size_t wbytes = (size_t)NR * a.KB * 256 * 4;
-  // Tile budget: this kernel likes BIG tiles (one 1024-thread workgroup per CU: long MFMA runs per barrier, little
-  // halo) as long as one workgroup per CU exists — take the largest budget that still yields 256 of them, else the most
-  // workgroups (measured on the zoo shapes: 2D 32^2 H64 47 -> 37 us, 64^2 63 -> 43 us vs the 32 KiB tiles).
-  const size_t budgets[] = {(size_t)kLdsBudgetMax, (size_t)96 * 1024, (size_t)64 * 1024, (size_t)kLdsBudget};
-  bool ok = false;
-  GconvArgs best = a;
-  long long best_wgs = -1;
-  for (size_t budget : budgets) {
-    GconvArgs t = a;
-    const bool fits = a.W < 16 ? plan_tiles_min_halo(t, dim, 0, wbytes, a.KB * 4, 16, budget)
-                               : plan_tiles_budget(t, dim, 0, wbytes, a.KB * 4, 16, budget);
-    if (!fits) continue;
-    const long long wgs = (long long)t.nD * t.nH * a.groups * a.B;
-    if (wgs >= 256) { best = t; ok = true; break; }
-    if (wgs > best_wgs) { best = t; best_wgs = wgs; ok = true; }
-  }
-  if (!ok) return CT_EINVAL;
-  a = best;
-  const size_t lds = (size_t)a.KB * 4 * a.plane * 4 + wbytes + 2 * kSlack * 4;
-  a.msplit = pick_msplit(a);
-  dim3 grid(a.nD * a.nH * a.msplit, a.groups, a.B);
-  const int threads = lds > 48 * 1024 ? kThreadsBig : kThreads;
-  if (took != nullptr) took->one_term = quad_one_term(a);
-  if (plan_only) return CT_OK;
-  if (prec == CT_GCONV_PRECISION_HIGH && quad_one_term(a)) return launch_fwd4_f16(a, e, dim, grid, threads, lds, st);
-  if (e != nullptr) return launch_fwd4_norm(a, *e, dim, grid, threads, lds, st);
-  note(threads == kThreadsBig ? "quad_1024" : "quad_256");
-  if (a.msplit > 1) note("quad_msplit");
-  CT_CLEAR_ERROR();
-  if (dim == 2) {
-    if (set_lds_attr(gconv_fwd4_kernel<2>, lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL(gconv_fwd4_kernel<2>, grid, dim3(threads), lds, st, fwd_args<false>(a, nullptr));
-  } else {
-    if (set_lds_attr(gconv_fwd4_kernel<3>, lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL(gconv_fwd4_kernel<3>, grid, dim3(threads), lds, st, fwd_args<false>(a, nullptr));
-  }
-  CT_CHECK_LAUNCH();
-  return CT_OK;
+// ---- forward and backward-data: the plan is a value.  plan_fwd settles it from the sizes and FwdInputs alone (no tag, no HIP
+// call, no global read); the entry points launch it, the queries (ct_gconv_fwd_norm_supported, ct_gconv_precision_covers,
+// ct_gconv_supported) only look at it. ----
+enum FwdFamily { kFamDense, kFamC4Mfma3, kFamC4Valu, kFamKsplit, kFamQuad, kFamOnepos };
+
+struct FwdInputs {
+  bool xy16;          // x | y on the 16-byte grid
+  bool w16;           // w on the 16-byte grid
+  unsigned debug;     // the ct_debug_set_gconv word, read once by the entry point
+  bool need_norm;     // the caller writes out through NORM (ct_gconv_fwd_norm): only a family that carries the variant will do
+};
+
+struct FwdPlan {
+  FwdFamily family;
+  int dim;
+  GconvArgs a;                // the call's arguments with the tile fields (and msplit) settled
+  dim3 grid;
+  int threads;
+  size_t lds;
+  int cob;                    // dense 2^d: output channels per workgroup
+  int TH, LZ, nZ, CSX;        // four-channel matrix-core: rows, depth segment, segments, LDS channel stride
+  int pass, maxi, dma;        // K-split: one tile (0) or tiled (1), items per wave, bank slices by LDS-DMA
+  bool one_term;              // under CT_GCONV_PRECISION_HIGH the launch takes the one-term f16 kernel (ct_gconv_precision_covers)
+  bool has_norm;              // the family has a NORM variant
+};
+
+void settle(FwdPlan& p, FwdFamily family, int dim, const GconvArgs& a, dim3 grid, int threads, size_t lds, bool has_norm,
+            bool one_term = false) {
+  p.family = family; p.dim = dim; p.a = a; p.grid = grid; p.threads = threads; p.lds = lds;
+  p.has_norm = has_norm; p.one_term = one_term;
 }
 
+// 2^d volumes: the dense small-volume form
+size_t tiny_lds(const GconvArgs& a, int dim, int cob) {
+  const int P = dim == 3 ? 8 : 4, TS = dim == 3 ? kTinyTapStride : 12;
+  return ((size_t)cob * (a.Cin * TS + 4) + (size_t)a.B * (a.Cin * P + 4) + (size_t)4 * cob * a.B * P) * 4;
+}
 
-// K-split form for wide groups (> 32 input channels per group): see gconv_fwd4k_kernel
-int launch_fwd4k(GconvArgs a, int dim, hipStream_t st, const GconvEpi* e = nullptr, bool plan_only = false, int prec = 0,
-                 FwdTook* took = nullptr) {
-  const int NR = dim == 3 ? 9 : 3;
+bool plan_dense(const GconvArgs& a, int dim, FwdPlan& p) {
+  if (a.W != 2 || a.H != 2 || (dim == 3 && a.D != 2)) return false;
+  int cob = 64 / a.B;                                   // one lane per (output channel, cloud)
+  if (cob < 4) cob = 4;
+  if (cob > a.Cout) cob = a.Cout;
+  while (cob > 1 && tiny_lds(a, dim, cob) > (size_t)84 * 1024) cob >>= 1;      // two workgroups per CU when it can
+  if (tiny_lds(a, dim, cob) > (size_t)kLdsBudgetMax) return false;
+  p.cob = cob;
+  settle(p, kFamDense, dim, a, dim3((a.Cout + cob - 1) / cob, a.groups), 256, tiny_lds(a, dim, cob), true);
+  return true;
+}
+
+// four-channel groups in 3D with rows of 16-position blocks: the matrix-core kernel (see gconv_c4_mfma3_kernel)
+bool plan_c4_mfma3(const GconvArgs& a, int dim, FwdPlan& p) {
+  if (dim != 3 || (a.W & 15) != 0 || a.W > 16 * kC4mCols * (kC4mThreads / 64)) return false;
+  int TH = (kC4mCols * (kC4mThreads / 64)) / (a.W >> 4);      // columns of a workgroup: rows x 16-position blocks
+  if (TH > a.H) TH = a.H;
+  if (TH < 1) return false;
+  // the kernel's static bounds: LDS-DMA pieces per wave (2) and 16-byte stores per thread (2) and slice
+  const int ppc = ((TH + 2) * a.W / 4 + 63) / 64;
+  if (4 * ppc > 2 * (kC4mThreads / 64) || TH * a.W > 2 * kC4mThreads) return false;
+  const int nH = (a.H + TH - 1) / TH;
+  // depth segments until the chip is covered (each walks two extra slices)
+  int nZ = 1;
+  while ((long long)a.B * a.groups * nH * nZ < CT_C4M_WGS && a.D / (nZ * 2) >= 4) nZ *= 2;
+  const int LZ = (a.D + nZ - 1) / nZ;
+  nZ = (a.D + LZ - 1) / LZ;
+  int CSX = (TH + 2) * a.W;
+  CSX += (16 - (CSX & 31) + 32) & 31;                         // == 16 (mod 32): the four channels' 16-float runs fall on all 32 banks twice
+  p.TH = TH; p.LZ = LZ; p.nZ = nZ; p.CSX = CSX;
+  settle(p, kFamC4Mfma3, dim, a, dim3(nH * nZ, a.groups, a.B), kC4mThreads,
+         ((size_t)3 * 4 * CSX + (size_t)2 * 4 * TH * a.W + 2 * kSlack) * 4, false);
+  return true;
+}
+
+// four-channel groups with 16-byte rows: the vector-ALU kernel
+bool plan_c4_valu(GconvArgs a, int dim, FwdPlan& p) {
+  if (!plan_tiles(plan_tiles_min_halo, a, dim, 0, 0, 4, 4)) return false;
+  settle(p, kFamC4Valu, dim, a, dim3(a.nD * a.nH, a.groups, a.B), kThreads, (size_t)4 * a.plane * 4 + 2 * kSlack * 4, false);
+  return true;
+}
+
+// K-split form for wide groups (>= 32 input channels per group): see gconv_fwd4k_kernel
+bool plan_ksplit(const GconvArgs& a, int dim, bool w16, FwdPlan& p) {
   const int MT = (a.Cout + 15) / 16;
   constexpr int kWaves = kThreadsBig / 64;
   // Pass 0: the smallest split of the 16-row output blocks over workgroups (msplit) for which ONE tile covers the whole
@@ -2446,128 +2439,214 @@ int launch_fwd4k(GconvArgs a, int dim, hipStream_t st, const GconvEpi* e = nullp
     if (items > 4 * kWaves) continue;                        // thinner blocks per workgroup
     if (pass == 0 && wgs < 256 && msplit < MT && items > kWaves / 2) continue;   // cover the chip while the waves still have work
     t.msplit = msplit;
-    const size_t lds = (size_t)kKBlk * t.plane * 4 + wbytes + 2 * kSlack * 4;
-    dim3 grid(t.nD * t.nH * msplit, a.groups, a.B);
-    const int maxi = items <= kWaves ? 1 : (items <= 2 * kWaves ? 2 : 4);
+    p.pass = pass;
+    p.maxi = items <= kWaves ? 1 : (items <= 2 * kWaves ? 2 : 4);
     // whole 16-channel rows at 16-byte aligned addresses move by LDS-DMA
-    const int dma = (a.Cin % 16 == 0 && a.Cout % 16 == 0 && (((uintptr_t)a.w) & 15) == 0) ? 1 : 0;
-    const bool one_term = ksplit_one_term((nquads + 15) / 16);
-    if (took != nullptr) took->one_term = one_term;
-    if (plan_only) return CT_OK;
-    if (prec == CT_GCONV_PRECISION_HIGH && one_term) return launch_fwd4k_f16(t, e, dim, pass, maxi, dma, grid, lds, st);
-    if (e != nullptr) return launch_fwd4k_norm(t, *e, dim, pass, maxi, dma, grid, lds, st);
-    note(pass == 0 ? (dma ? "ksplit_one_dma" : "ksplit_one_elem") : (dma ? "ksplit_tiled_dma" : "ksplit_tiled_elem"));
-    note(maxi == 1 ? "ksplit_items1" : maxi == 2 ? "ksplit_items2" : "ksplit_items4");
-    if (msplit > 1) note("ksplit_msplit");
-    CT_CLEAR_ERROR();
-#define CT_F4K_LAUNCH(DIMV, MAXIV, TRV)                                                                \
-    do {                                                                                               \
-      if (set_lds_attr(gconv_fwd4k_kernel<DIMV, MAXIV, TRV>, lds) != CT_OK) return CT_ELAUNCH;         \
-      hipLaunchKernelGGL((gconv_fwd4k_kernel<DIMV, MAXIV, TRV>), grid, dim3(kThreadsBig), lds, st, fwd_args<false>(t, nullptr), dma); \
-    } while (0)
-#define CT_F4K_MAXI(DIMV, TRV) \
-    do { if (maxi == 1) CT_F4K_LAUNCH(DIMV, 1, TRV); else if (maxi == 2) CT_F4K_LAUNCH(DIMV, 2, TRV); else CT_F4K_LAUNCH(DIMV, 4, TRV); } while (0)
-    if (dim == 2) { if (a.transposed) CT_F4K_MAXI(2, true); else CT_F4K_MAXI(2, false); }
-    else { if (a.transposed) CT_F4K_MAXI(3, true); else CT_F4K_MAXI(3, false); }
-#undef CT_F4K_MAXI
-#undef CT_F4K_LAUNCH
-    CT_CHECK_LAUNCH();
-    return CT_OK;
+    p.dma = (a.Cin % 16 == 0 && a.Cout % 16 == 0 && w16) ? 1 : 0;
+    settle(p, kFamKsplit, dim, t, dim3(t.nD * t.nH * msplit, a.groups, a.B), kThreadsBig,
+           (size_t)kKBlk * t.plane * 4 + wbytes + 2 * kSlack * 4, true, ksplit_one_term((nquads + 15) / 16));
+    return true;
   }
-  return CT_EINVAL;
+  return false;
 }
 
-// 2^d volumes: the dense small-volume form
-size_t tiny_lds(const GconvArgs& a, int dim, int cob) {
-  const int P = dim == 3 ? 8 : 4, TS = dim == 3 ? kTinyTapStride : 12;
-  return ((size_t)cob * (a.Cin * TS + 4) + (size_t)a.B * (a.Cin * P + 4) + (size_t)4 * cob * a.B * P) * 4;
-}
-
-int tiny_cob(const GconvArgs& a, int dim) {
-  if (a.W != 2 || a.H != 2 || (dim == 3 && a.D != 2)) return 0;
-  if ((((uintptr_t)a.x) | ((uintptr_t)a.y)) & 15) return 0;
-  int cob = 64 / a.B;                                   // one lane per (output channel, cloud)
-  if (cob < 4) cob = 4;
-  if (cob > a.Cout) cob = a.Cout;
-  while (cob > 1 && tiny_lds(a, dim, cob) > (size_t)84 * 1024) cob >>= 1;      // two workgroups per CU when it can
-  return tiny_lds(a, dim, cob) <= (size_t)kLdsBudgetMax ? cob : 0;
-}
-
-int launch_tiny(GconvArgs a, int dim, int cob, hipStream_t st, const GconvEpi* e = nullptr) {
-  const size_t lds = tiny_lds(a, dim, cob);
-  dim3 grid((a.Cout + cob - 1) / cob, a.groups);
-  if (e != nullptr) return launch_tiny_norm(a, *e, dim, cob, grid, lds, st);
-  note(dim == 2 ? "dense2d" : "dense3d");
-  CT_CLEAR_ERROR();
-  if (dim == 2) {
-    if (set_lds_attr(gconv_tiny_kernel<2>, lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL(gconv_tiny_kernel<2>, grid, dim3(256), lds, st, fwd_args<false>(a, nullptr), cob);
-  } else {
-    if (set_lds_attr(gconv_tiny_kernel<3>, lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL(gconv_tiny_kernel<3>, grid, dim3(256), lds, st, fwd_args<false>(a, nullptr), cob);
-  }
-  CT_CHECK_LAUNCH();
-  return CT_OK;
-}
-
-// e: the NORM write-out (ct_gconv_fwd_norm) on the families that carry it — dense 2^d, K-split, quad; the others return CT_EINVAL
-// before anything is launched.  plan_only (ct_gconv_fwd_norm_supported): the same walk with nothing noted and nothing launched.
-// prec: the precision mode the entry point read; took: see FwdTook (norm_plan: plan_only walks as ct_gconv_fwd_norm would)
-int launch_fwd(GconvArgs a, int dim, hipStream_t st, const GconvEpi* e = nullptr, bool plan_only = false, int prec = 0,
-               FwdTook* took = nullptr, bool norm_plan = true) {
-  const bool norm = e != nullptr || (plan_only && norm_plan);
-  if (const int cob = tiny_cob(a, dim)) return plan_only ? CT_OK : launch_tiny(a, dim, cob, st, e);
-  const bool rows16 = (a.W & 3) == 0 && ((((uintptr_t)a.x) | ((uintptr_t)a.y)) & 15) == 0;
-  if (norm && (!rows16 || (a.Cin == 4 && a.Cout == 4))) return CT_EINVAL;     // the four-channel kernels and the one-position form
-  // large four-channel volumes (the zoo's 32^3 C4 head at B8: 74 vs 93 us) take the matrix-core kernel; below ~2 M positions
-  // (B2: 31 vs 30 us, 16^3: 29 vs 16) its per-slice barriers cost more than the vector ALU's extra multiply-adds
-  // (debug bit 1 = never, bit 2 = always)
-  if (plan_only && a.Cin == 4 && a.Cout == 4) return CT_OK;      // (ct_gconv_precision_covers: the four-channel kernels keep fp32)
-  if (dim == 3 && rows16 && a.Cin == 4 && a.Cout == 4 && c4_mfma3_fits(a)) {
-    const unsigned dbg = t_gconv_debug.load(std::memory_order_relaxed);
-    const long long positions = (long long)a.B * a.groups * a.D * a.H * a.W;
-    if (!(dbg & 2) && ((dbg & 4) || positions >= (2ll << 20))) return launch_c4_mfma3(a, st);
-  }
-  if (rows16 && a.Cin == 4 && a.Cout == 4) return launch_c4(a, dim, st);
-  const unsigned dbg_cin = (t_gconv_debug.load(std::memory_order_relaxed) >> 8) & 0xffu;
-  if (rows16 && a.Cin >= (dbg_cin ? (int)dbg_cin : 32)) {      // wide groups (>= 32 input channels): contraction in blocks of 16
-    const int r = launch_fwd4k(a, dim, st, e, plan_only, prec, took);
-    if (r != CT_EINVAL) return r;
-  }
-  if (rows16) {
-    // the quad form keeps the whole filter bank of a 16-row block in LDS ([rows][KB][4][16][4] floats): with 64 input
-    // channels per group in 3D that alone is 147 KiB — such shapes take the K-split form above
-    const int r = launch_fwd4(a, dim, st, e, plan_only, prec, took);
-    if (r != CT_EINVAL) return r;
-  }
-  if (took != nullptr) took->one_term = false;
-  if (norm) return CT_EINVAL;
-  if (plan_only) return CT_OK;                                    // (ct_gconv_precision_covers: the one-position form keeps fp32)
-  const size_t wbytes = (size_t)a.taps * a.KB * 64 * 4;
-  // short rows (W < 16: the 8^3 volumes) do better on the minimum-halo tiles, the others on the depth-first ones (measured)
-  const bool ok = a.W < 16 ? (plan_tiles_min_halo(a, dim, 0, wbytes, a.KB * 4, 16, kLdsBudget) ||
-                              plan_tiles_min_halo(a, dim, 0, wbytes, a.KB * 4, 16, kLdsBudgetMax))
-                           : plan_tiles(a, dim, 0, wbytes, a.KB * 4, 16);
-  if (!ok) return CT_EINVAL;
+// the workgroups of the quad and one-position forms, once their tiles are settled
+void settle_mfma_tiles(FwdPlan& p, FwdFamily family, int dim, GconvArgs a, size_t wbytes, bool has_norm, bool one_term) {
   const size_t lds = (size_t)a.KB * 4 * a.plane * 4 + wbytes + 2 * kSlack * 4;
   a.msplit = pick_msplit(a);
-  dim3 grid(a.nD * a.nH * a.msplit, a.groups, a.B);
-  const int threads = lds > 48 * 1024 ? kThreadsBig : kThreads;
-  note("onepos");
-  if (a.msplit > 1) note("onepos_msplit");
+  settle(p, family, dim, a, dim3(a.nD * a.nH * a.msplit, a.groups, a.B), lds > 48 * 1024 ? kThreadsBig : kThreads, lds, has_norm,
+         one_term);
+}
+
+// quad form of the MFMA kernel (rows of W % 4 == 0 floats, 16-byte aligned tensors).  It keeps the whole filter bank of a 16-row
+// block in LDS ([rows][KB][4][16][4] floats): with 64 input channels per group in 3D that alone is 147 KiB — such shapes take the
+// K-split form
+bool plan_quad(const GconvArgs& a, int dim, FwdPlan& p) {
+  const int NR = dim == 3 ? 9 : 3;
+  const size_t wbytes = (size_t)NR * a.KB * 256 * 4;
+  // Tile budget: this kernel likes BIG tiles (one 1024-thread workgroup per CU: long MFMA runs per barrier, little
+  // halo) as long as one workgroup per CU exists — take the largest budget that still yields 256 of them, else the most
+  // workgroups (measured on the zoo shapes: 2D 32^2 H64 47 -> 37 us, 64^2 63 -> 43 us vs the 32 KiB tiles).
+  const size_t budgets[] = {(size_t)kLdsBudgetMax, (size_t)96 * 1024, (size_t)64 * 1024, (size_t)kLdsBudget};
+  bool ok = false;
+  GconvArgs best = a;
+  long long best_wgs = -1;
+  for (size_t budget : budgets) {
+    GconvArgs t = a;
+    const bool fits = a.W < 16 ? plan_tiles_min_halo(t, dim, 0, wbytes, a.KB * 4, 16, budget)
+                               : plan_tiles_budget(t, dim, 0, wbytes, a.KB * 4, 16, budget);
+    if (!fits) continue;
+    const long long wgs = (long long)t.nD * t.nH * a.groups * a.B;
+    if (wgs >= 256) { best = t; ok = true; break; }
+    if (wgs > best_wgs) { best = t; best_wgs = wgs; ok = true; }
+  }
+  if (ok) settle_mfma_tiles(p, kFamQuad, dim, best, wbytes, true, quad_one_term(a));
+  return ok;
+}
+
+// one-position form: any row length, any alignment
+bool plan_onepos(GconvArgs a, int dim, FwdPlan& p) {
+  const size_t wbytes = (size_t)a.taps * a.KB * 64 * 4;
+  // short rows (W < 16: the 8^3 volumes) do better on the minimum-halo tiles, the others on the depth-first ones (measured)
+  const bool ok = a.W < 16 ? plan_tiles(plan_tiles_min_halo, a, dim, 0, wbytes, a.KB * 4, 16)
+                           : plan_tiles(plan_tiles_budget, a, dim, 0, wbytes, a.KB * 4, 16);
+  if (ok) settle_mfma_tiles(p, kFamOnepos, dim, a, wbytes, false, false);
+  return ok;
+}
+
+// The walk: the first family that takes the call
+bool walk_fwd(const GconvArgs& a, int dim, const FwdInputs& in, FwdPlan& p) {
+  if (in.xy16 && plan_dense(a, dim, p)) return true;
+  const bool rows16 = (a.W & 3) == 0 && in.xy16;
+  if (rows16 && a.Cin == 4 && a.Cout == 4) {
+    // large four-channel volumes (the zoo's 32^3 C4 head at B8: 74 vs 93 us) take the matrix-core kernel; below ~2 M positions
+    // (B2: 31 vs 30 us, 16^3: 29 vs 16) its per-slice barriers cost more than the vector ALU's extra multiply-adds
+    // (debug bit 1 = never, bit 2 = always)
+    const long long positions = (long long)a.B * a.groups * a.D * a.H * a.W;
+    if (!(in.debug & 2) && ((in.debug & 4) || positions >= (2ll << 20)) && plan_c4_mfma3(a, dim, p)) return true;
+    return plan_c4_valu(a, dim, p);                              // (a four-channel group on 16-byte rows goes nowhere else)
+  }
+  const int wide = (in.debug >> 8) & 0xffu ? (int)((in.debug >> 8) & 0xffu) : 32;      // wide groups: contraction in blocks of 16
+  if (rows16 && a.Cin >= wide && plan_ksplit(a, dim, in.w16, p)) return true;
+  if (rows16 && plan_quad(a, dim, p)) return true;
+  return plan_onepos(a, dim, p);
+}
+
+// CT_EINVAL: no family takes the call, or (need_norm) the one that does has no NORM variant: the four-channel kernels and the
+// one-position form
+int plan_fwd(const GconvArgs& a, int dim, const FwdInputs& in, FwdPlan& p) {
+  return walk_fwd(a, dim, in, p) && (p.has_norm || !in.need_norm) ? CT_OK : CT_EINVAL;
+}
+
+// ---- ... and the launches: one per family.  Each notes the family's tags once and then picks the instantiation: plain, NORM
+// (e: the write-out of ct_gconv_fwd_norm), F16 (prec == HIGH on a one-term plan) or both.  Same plan, same tags. ----
+int launch_dense(const FwdPlan& p, const GconvEpi* e, int, hipStream_t st) {
+  note(p.dim == 2 ? "dense2d" : "dense3d");
   CT_CLEAR_ERROR();
-  if (dim == 2) {
-    if (set_lds_attr(gconv_fwd_kernel<2>, lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL(gconv_fwd_kernel<2>, grid, dim3(threads), lds, st, a);
+#define CT_TINY_LAUNCH(DIMV, NORMV)                                                                                  \
+  do {                                                                                                               \
+    if (set_lds_attr(gconv_tiny_kernel<DIMV, NORMV>, p.lds) != CT_OK) return CT_ELAUNCH;                             \
+    hipLaunchKernelGGL((gconv_tiny_kernel<DIMV, NORMV>), p.grid, dim3(p.threads), p.lds, st, fwd_args<NORMV>(p.a, e), p.cob); \
+  } while (0)
+  if (p.dim == 2) { if (e != nullptr) CT_TINY_LAUNCH(2, true); else CT_TINY_LAUNCH(2, false); }
+  else { if (e != nullptr) CT_TINY_LAUNCH(3, true); else CT_TINY_LAUNCH(3, false); }
+#undef CT_TINY_LAUNCH
+  CT_CHECK_LAUNCH();
+  return CT_OK;
+}
+
+int launch_c4_mfma3(const FwdPlan& p, const GconvEpi*, int, hipStream_t st) {
+  note("c4_mfma3");
+  CT_CLEAR_ERROR();
+#define CT_C4M_LAUNCH(TRV)                                                                                           \
+  do {                                                                                                               \
+    if (set_lds_attr(gconv_c4_mfma3_kernel<TRV>, p.lds) != CT_OK) return CT_ELAUNCH;                                 \
+    hipLaunchKernelGGL(gconv_c4_mfma3_kernel<TRV>, p.grid, dim3(p.threads), p.lds, st, p.a, p.TH, p.LZ, p.nZ, p.CSX); \
+  } while (0)
+  if (p.a.transposed) CT_C4M_LAUNCH(true); else CT_C4M_LAUNCH(false);
+#undef CT_C4M_LAUNCH
+  CT_CHECK_LAUNCH();
+  return CT_OK;
+}
+
+int launch_c4_valu(const FwdPlan& p, const GconvEpi*, int, hipStream_t st) {
+  note("c4_valu");
+  CT_CLEAR_ERROR();
+#define CT_C4_LAUNCH(DIMV, TRV)                                                                   \
+  do {                                                                                            \
+    if (set_lds_attr(gconv_c4_kernel<DIMV, TRV>, p.lds) != CT_OK) return CT_ELAUNCH;              \
+    hipLaunchKernelGGL((gconv_c4_kernel<DIMV, TRV>), p.grid, dim3(p.threads), p.lds, st, p.a);    \
+  } while (0)
+  if (p.dim == 2) { if (p.a.transposed) CT_C4_LAUNCH(2, true); else CT_C4_LAUNCH(2, false); }
+  else { if (p.a.transposed) CT_C4_LAUNCH(3, true); else CT_C4_LAUNCH(3, false); }
+#undef CT_C4_LAUNCH
+  CT_CHECK_LAUNCH();
+  return CT_OK;
+}
+
+int launch_ksplit(const FwdPlan& p, const GconvEpi* e, int prec, hipStream_t st) {
+  note(p.pass == 0 ? (p.dma ? "ksplit_one_dma" : "ksplit_one_elem") : (p.dma ? "ksplit_tiled_dma" : "ksplit_tiled_elem"));
+  note(p.maxi == 1 ? "ksplit_items1" : p.maxi == 2 ? "ksplit_items2" : "ksplit_items4");
+  if (p.a.msplit > 1) note("ksplit_msplit");
+  const bool f16 = prec == CT_GCONV_PRECISION_HIGH && p.one_term;
+  CT_CLEAR_ERROR();
+#define CT_F4K_LAUNCH(DIMV, MAXIV, TRV, NORMV, F16V)                                                                 \
+  do {                                                                                                               \
+    if (set_lds_attr(gconv_fwd4k_kernel<DIMV, MAXIV, TRV, NORMV, F16V>, p.lds) != CT_OK) return CT_ELAUNCH;          \
+    hipLaunchKernelGGL((gconv_fwd4k_kernel<DIMV, MAXIV, TRV, NORMV, F16V>), p.grid, dim3(p.threads), p.lds, st,      \
+                       fwd_args<NORMV>(p.a, e), p.dma);                                                              \
+  } while (0)
+#define CT_F4K_MAXI(DIMV, ...) \
+  do { if (p.maxi == 1) CT_F4K_LAUNCH(DIMV, 1, __VA_ARGS__); else if (p.maxi == 2) CT_F4K_LAUNCH(DIMV, 2, __VA_ARGS__); else CT_F4K_LAUNCH(DIMV, 4, __VA_ARGS__); } while (0)
+#define CT_F4K_F16(DIMV, TRV, NORMV) do { if (f16) CT_F4K_MAXI(DIMV, TRV, NORMV, true); else CT_F4K_MAXI(DIMV, TRV, NORMV, false); } while (0)
+  // (NORM is a forward write-out: no transposed instantiation of it exists)
+#define CT_F4K_DIM(DIMV) \
+  do { if (e != nullptr) CT_F4K_F16(DIMV, false, true); else if (p.a.transposed) CT_F4K_F16(DIMV, true, false); else CT_F4K_F16(DIMV, false, false); } while (0)
+  if (p.dim == 2) CT_F4K_DIM(2); else CT_F4K_DIM(3);
+#undef CT_F4K_DIM
+#undef CT_F4K_F16
+#undef CT_F4K_MAXI
+#undef CT_F4K_LAUNCH
+  CT_CHECK_LAUNCH();
+  return CT_OK;
+}
+
+int launch_quad(const FwdPlan& p, const GconvEpi* e, int prec, hipStream_t st) {
+  note(p.threads == kThreadsBig ? "quad_1024" : "quad_256");
+  if (p.a.msplit > 1) note("quad_msplit");
+  const bool f16 = prec == CT_GCONV_PRECISION_HIGH && p.one_term;
+  CT_CLEAR_ERROR();
+#define CT_F4_LAUNCH(DIMV, NORMV, F16V)                                                                                        \
+  do {                                                                                                                         \
+    if (set_lds_attr(gconv_fwd4_kernel<DIMV, NORMV, F16V>, p.lds) != CT_OK) return CT_ELAUNCH;                                 \
+    hipLaunchKernelGGL((gconv_fwd4_kernel<DIMV, NORMV, F16V>), p.grid, dim3(p.threads), p.lds, st, fwd_args<NORMV>(p.a, e));   \
+  } while (0)
+#define CT_F4_F16(DIMV, NORMV) do { if (f16) CT_F4_LAUNCH(DIMV, NORMV, true); else CT_F4_LAUNCH(DIMV, NORMV, false); } while (0)
+  if (p.dim == 2) { if (e != nullptr) CT_F4_F16(2, true); else CT_F4_F16(2, false); }
+  else { if (e != nullptr) CT_F4_F16(3, true); else CT_F4_F16(3, false); }
+#undef CT_F4_F16
+#undef CT_F4_LAUNCH
+  CT_CHECK_LAUNCH();
+  return CT_OK;
+}
+
+int launch_onepos(const FwdPlan& p, const GconvEpi*, int, hipStream_t st) {
+  note("onepos");
+  if (p.a.msplit > 1) note("onepos_msplit");
+  CT_CLEAR_ERROR();
+  if (p.dim == 2) {
+    if (set_lds_attr(gconv_fwd_kernel<2>, p.lds) != CT_OK) return CT_ELAUNCH;
+    hipLaunchKernelGGL(gconv_fwd_kernel<2>, p.grid, dim3(p.threads), p.lds, st, p.a);
   } else {
-    if (set_lds_attr(gconv_fwd_kernel<3>, lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL(gconv_fwd_kernel<3>, grid, dim3(threads), lds, st, a);
+    if (set_lds_attr(gconv_fwd_kernel<3>, p.lds) != CT_OK) return CT_ELAUNCH;
+    hipLaunchKernelGGL(gconv_fwd_kernel<3>, p.grid, dim3(p.threads), p.lds, st, p.a);
   }
   CT_CHECK_LAUNCH();
   return CT_OK;
 }
 
-// backward-weight, ring kernel (rows of W % 4 == 0 floats): the plan ...
+// plan, then launch: ct_gconv_fwd, ct_gconv_fwd_norm (e) and ct_gconv_bwd_data (a.transposed)
+int run_fwd(const GconvArgs& a, int dim, const GconvEpi* e, hipStream_t st) {
+  const auto on16 = [](const void* p, const void* q) { return ((((uintptr_t)p) | ((uintptr_t)q)) & 15) == 0; };
+  const FwdInputs in = {on16(a.x, a.y), on16(a.w, nullptr), t_gconv_debug.load(std::memory_order_relaxed), e != nullptr};
+  FwdPlan p;
+  const int r = plan_fwd(a, dim, in, p);
+  if (r != CT_OK) return r;
+  constexpr decltype(&launch_dense) launch[] = {launch_dense, launch_c4_mfma3, launch_c4_valu, launch_ksplit, launch_quad, launch_onepos};
+  return launch[p.family](p, e, gconv_precision_now(), st);
+}
+
+// the queries have no tensors: they plan a call whose tensors all lie on the 16-byte grid
+FwdInputs aligned_inputs(bool need_norm) { return {true, true, t_gconv_debug.load(std::memory_order_relaxed), need_norm}; }
+
+// ct_gconv_supported: a plan exists whatever the alignment
+bool fwd_plan_ok(const GconvArgs& a, int dim) {
+  FwdPlan p;
+  return plan_dense(a, dim, p) || (a.Cin == 4 && a.Cout == 4 && (a.W & 3) == 0 && plan_c4_valu(a, dim, p)) || plan_onepos(a, dim, p);
+}
+
+// ---- backward-weight.  Every kind has a plan record; wrw_candidate below lists the kinds in launch order. ----
+// ring kernel (rows of W % 4 == 0 floats), MFMA engine on 16-channel blocks (nch 16) or vector-ALU engine on four-channel groups (4)
 struct WrwRingPlan { size_t lds; int chunks, units_per_wg; };
 
 bool plan_wrw_ring(GconvArgs& a, int dim, WrwRingPlan& p, int nch = 16) {
@@ -2614,63 +2693,6 @@ bool plan_wrw_ring(GconvArgs& a, int dim, WrwRingPlan& p, int nch = 16) {
   return true;
 }
 
-size_t wrw_ring_workspace(const GconvArgs& a, const WrwRingPlan& p) {
-  const size_t CiB = (a.Cin + 15) >> 4, CoB = (a.Cout + 15) >> 4;
-  return ((size_t)p.chunks * a.groups * CoB * CiB * a.taps * 256 + (size_t)p.chunks * a.groups * CoB * 16) * sizeof(float);
-}
-
-// ... and the launch.  `ws` (>= wrw_ring_workspace bytes) selects the two-stage reduction; NULL the atomics.
-int launch_wrw_ring(GconvArgs a, int dim, const float* g_y, float* g_w, float* g_bias, float* ws, size_t ws_bytes, hipStream_t st) {
-  WrwRingPlan p;
-  if (!plan_wrw_ring(a, dim, p)) return CT_EINVAL;
-  if (ws && ws_bytes < wrw_ring_workspace(a, p)) return CT_EWORKSPACE;
-  if (!ws && ct_get_deterministic()) return CT_EPRECOND;      // deterministic mode: the atomic form needs the caller's consent
-  note(ws ? "wrw_ring_ws" : "wrw_ring_atomics");
-  if (ws) note("wrw_reduce");
-  if (!ws && hipMemsetAsync(g_w, 0, (size_t)a.groups * a.Cout * a.Cin * a.taps * 4, st) != hipSuccess) return CT_ELAUNCH;
-  dim3 grid(p.chunks, a.groups);
-  if (dim == 2) {
-    if (set_lds_attr(gconv_wrw_ring_kernel<2, false, kWrwThreads>, p.lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL((gconv_wrw_ring_kernel<2, false, kWrwThreads>), grid, dim3(kWrwThreads), p.lds, st, a, g_y, g_w, ws, p.units_per_wg);
-  } else {
-    if (set_lds_attr(gconv_wrw_ring_kernel<3, false, kWrwThreads>, p.lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL((gconv_wrw_ring_kernel<3, false, kWrwThreads>), grid, dim3(kWrwThreads), p.lds, st, a, g_y, g_w, ws, p.units_per_wg);
-  }
-  if (ws) {
-    const size_t CiB = (a.Cin + 15) >> 4, CoB = (a.Cout + 15) >> 4;
-    const size_t n = (size_t)a.groups * CoB * CiB * a.taps * 256;
-    hipLaunchKernelGGL(gconv_wrw_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64, 4), 0, st, ws, g_w, g_bias, p.chunks,
-                       a.groups, a.Cin, a.Cout, a.taps);
-  }
-  return CT_OK;
-}
-
-// backward-weight of four-channel groups: the ring kernel with its vector-ALU engine
-bool c4_wrw_eligible(const GconvArgs& a) { return a.Cin == 4 && a.Cout == 4 && (a.W & 3) == 0; }
-
-size_t c4_wrw_workspace(const GconvArgs& a, const WrwRingPlan& p) {
-  return ((size_t)p.chunks * a.groups * 16 * a.taps + (size_t)p.chunks * a.groups * 4) * sizeof(float);
-}
-
-int launch_c4_wrw(GconvArgs a, int dim, const float* g_y, float* g_w, float* g_bias, float* ws, size_t ws_bytes, hipStream_t st) {
-  WrwRingPlan p;
-  if (!plan_wrw_ring(a, dim, p, 4)) return CT_EINVAL;
-  if (ws_bytes < c4_wrw_workspace(a, p)) return CT_EWORKSPACE;
-  note("wrw_c4_ring");
-  note("wrw_c4_reduce");
-  dim3 grid(p.chunks, a.groups);
-  if (dim == 2) {
-    if (set_lds_attr(gconv_wrw_ring_kernel<2, true, kThreads>, p.lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL((gconv_wrw_ring_kernel<2, true, kThreads>), grid, dim3(kThreads), p.lds, st, a, g_y, g_w, ws, p.units_per_wg);
-  } else {
-    if (set_lds_attr(gconv_wrw_ring_kernel<3, true, kThreads>, p.lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL((gconv_wrw_ring_kernel<3, true, kThreads>), grid, dim3(kThreads), p.lds, st, a, g_y, g_w, ws, p.units_per_wg);
-  }
-  const int n = a.groups * 16 * a.taps;
-  hipLaunchKernelGGL(gconv_c4_wrw_reduce_kernel, dim3((n + 63) / 64), dim3(64, 4), 0, st, ws, g_w, g_bias, p.chunks, a.groups, a.taps);
-  return CT_OK;
-}
-
 // four-channel 3D groups: the matrix-core weight gradient (see gconv_c4_wrw_mfma3_kernel)
 struct C4WrwPlan { int R, nwaves, nZ, LZ, SX, SG, chunks; size_t lds; };
 
@@ -2691,55 +2713,6 @@ bool plan_c4_wrw_mfma3(const GconvArgs& a, int dim, C4WrwPlan& p) {
   return p.lds <= (size_t)kLdsBudgetMax;
 }
 
-size_t c4_wrw_mfma3_workspace(const GconvArgs& a, const C4WrwPlan& p) {
-  return ((size_t)p.chunks * a.groups * 16 * a.taps + (size_t)p.chunks * a.groups * 4) * sizeof(float);
-}
-
-int launch_c4_wrw_mfma3(GconvArgs a, const C4WrwPlan& p, const float* g_y, float* g_w, float* g_bias, float* ws, size_t ws_bytes, hipStream_t st) {
-  if (ws_bytes < c4_wrw_mfma3_workspace(a, p)) return CT_EWORKSPACE;
-  note("wrw_c4_mfma3");
-  note("wrw_c4_reduce");
-  dim3 grid(p.nZ, a.groups, a.B);
-  CT_CLEAR_ERROR();
-  if (set_lds_attr(gconv_c4_wrw_mfma3_kernel, p.lds) != CT_OK) return CT_ELAUNCH;
-  hipLaunchKernelGGL(gconv_c4_wrw_mfma3_kernel, grid, dim3(p.nwaves * 64), p.lds, st, a, g_y, ws, p.R, p.LZ, p.SX, p.SG, p.chunks);
-  CT_CHECK_LAUNCH();
-  const int n = a.groups * 16 * a.taps;
-  hipLaunchKernelGGL(gconv_c4_wrw_reduce_kernel, dim3((n + 63) / 64), dim3(64, 4), 0, st, ws, g_w, g_bias, p.chunks, a.groups, a.taps);
-  CT_CHECK_LAUNCH();
-  return CT_OK;
-}
-
-// backward-weight, tile kernel (any row length): plan + launch
-int launch_wrw_tiles(GconvArgs a, int dim, const float* g_y, float* g_w, hipStream_t st) {
-  const int B = a.B, groups = a.groups;
-  // LDS: 16 input planes with halo + 16 rows of g_y + the cross-wave reduction buffer
-  const size_t red_bytes = (size_t)(kThreads / 64) * 3 * 256 * 4;
-  if (!plan_tiles(a, dim, (size_t)16 * 4, 1024 + red_bytes, 16, /*plane == 4 (mod 32): 16-byte aligned for the DMA*/ 4,
-                  kLdsBudgetWrw)) return CT_EINVAL;       // (before anything is written: a refused call leaves g_w as it was)
-  if (ct_get_deterministic()) return CT_EPRECOND;         // float atomics only: refused in deterministic mode (include/cloudct.h)
-  note("wrw_tiles");
-  if (hipMemsetAsync(g_w, 0, (size_t)groups * a.Cout * a.Cin * a.taps * 4, st) != hipSuccess) return CT_ELAUNCH;
-  const int gstride_max = ((a.TD * a.TH * a.W + 3) & ~3) | 1;
-  const size_t lds = ((size_t)16 * a.plane + (size_t)16 * gstride_max) * 4 + red_bytes + 2 * kSlack * 4;
-  const int U = B * a.nD * a.nH;
-  int chunks = (512 + groups - 1) / groups;           // ~512 workgroups in flight
-  if (chunks > U) chunks = U;
-  if (chunks < 1) chunks = 1;
-  const int units_per_wg = (U + chunks - 1) / chunks;
-  chunks = (U + units_per_wg - 1) / units_per_wg;
-  dim3 grid(chunks, groups);
-  if (dim == 2) {
-    if (set_lds_attr(gconv_bwd_weight_kernel<2>, lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL(gconv_bwd_weight_kernel<2>, grid, dim3(kThreads), lds, st, a, g_y, g_w, units_per_wg);
-  } else {
-    if (set_lds_attr(gconv_bwd_weight_kernel<3>, lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL(gconv_bwd_weight_kernel<3>, grid, dim3(kThreads), lds, st, a, g_y, g_w, units_per_wg);
-  }
-  return CT_OK;
-}
-
-// plan-only checks behind ct_gconv_supported
 // LDS of the small-volume weight gradient: the two operand tiles, or the partial filters of the row slices if larger
 size_t wrw_small_lds(const GconvArgs& a, int dim) {
   const int P = a.D * a.H * a.W;
@@ -2759,26 +2732,6 @@ bool wrw_small_eligible(const GconvArgs& a, int dim) {
   if ((long long)P * a.B > (wgs >= 256 ? 4096 : 2048)) return false;      // 8^3 B8 64->64 (256 workgroups): 327 vs 403 us ring;
                                                                           // 32->64 (128 workgroups): 326 vs 211 us
   return wrw_small_lds(a, dim) <= (size_t)kLdsBudgetMax;
-}
-
-int launch_wrw_small(GconvArgs a, int dim, const float* g_y, float* g_w, float* g_bias, hipStream_t st) {
-  const size_t lds = wrw_small_lds(a, dim);
-  dim3 grid(((a.Cin + 15) / 16) * ((a.Cout + 15) / 16), a.groups);
-  note("wrw_small_valu");
-  CT_CLEAR_ERROR();
-#define CT_WS_LAUNCH(DIMV, WTV)                                                                    \
-  do {                                                                                             \
-    if (set_lds_attr(gconv_wrw_small_kernel<DIMV, WTV>, lds) != CT_OK) return CT_ELAUNCH;          \
-    hipLaunchKernelGGL((gconv_wrw_small_kernel<DIMV, WTV>), grid, dim3(256 * kWsSplit), lds, st, a, g_y, g_w, g_bias); \
-  } while (0)
-  if (dim == 2) {
-    if (a.W == 2) CT_WS_LAUNCH(2, 2); else if (a.W == 4) CT_WS_LAUNCH(2, 4); else if (a.W == 8) CT_WS_LAUNCH(2, 8); else CT_WS_LAUNCH(2, 16);
-  } else {
-    if (a.W == 2) CT_WS_LAUNCH(3, 2); else if (a.W == 4) CT_WS_LAUNCH(3, 4); else if (a.W == 8) CT_WS_LAUNCH(3, 8); else CT_WS_LAUNCH(3, 16);
-  }
-#undef CT_WS_LAUNCH
-  CT_CHECK_LAUNCH();
-  return CT_OK;
 }
 
 // small volumes, many channels, on the matrix cores (see gconv_wrw_mfma_kernel)
@@ -2811,18 +2764,84 @@ bool plan_wrw_mfma(const GconvArgs& a, int dim, WrwMfmaPlan& p) {
   return true;
 }
 
-size_t wrw_mfma_workspace(const GconvArgs& a, const WrwMfmaPlan& p) {
-  if (p.ksplit <= 1) return 0;
+// chunk sums of 16 x 16 channel blocks (the ring and small-volume MFMA kernels) / of four-channel groups, plus their bias rows
+size_t wrw_block_workspace(const GconvArgs& a, int chunks) {
   const size_t CiB = (a.Cin + 15) >> 4, CoB = (a.Cout + 15) >> 4;
-  return ((size_t)p.ksplit * a.groups * CoB * CiB * a.taps * 256 + (size_t)p.ksplit * a.groups * CoB * 16) * sizeof(float);
+  return ((size_t)chunks * a.groups * CoB * CiB * a.taps * 256 + (size_t)chunks * a.groups * CoB * 16) * sizeof(float);
+}
+size_t wrw_c4_workspace(const GconvArgs& a, int chunks) {
+  return ((size_t)chunks * a.groups * 16 * a.taps + (size_t)chunks * a.groups * 4) * sizeof(float);
 }
 
-int launch_wrw_mfma(GconvArgs a, int dim, WrwMfmaPlan p, const float* g_y, float* g_w, float* g_bias, float* ws, size_t ws_bytes,
-                    hipStream_t st) {
-  if (p.ksplit > 1 && (!ws || ws_bytes < wrw_mfma_workspace(a, p))) p.ksplit = 1;      // no workspace: one workgroup per block
-  float* wsp = p.ksplit > 1 ? ws : nullptr;
+// One candidate of the weight gradient: the plan of its kind, what it needs beyond the sizes, and the workspace it wants.
+// ct_gconv_bwd_weight takes the first kind (in the order of WrwKind) whose candidate exists and whose needs the call meets;
+// ct_gconv_bwd_weight_workspace_bytes sizes the workspace over the same candidates; ct_gconv_supported asks whether any exists.
+enum WrwKind { kWrwSmallMfma, kWrwSmallValu, kWrwC4Mfma3, kWrwC4Ring, kWrwRing, kWrwTiles, kWrwKinds };
+
+struct WrwCand {
+  GconvArgs a;                // the call's sizes, tiled by the kind's plan
+  bool need_aligned;          // only with x | g_y on the 16-byte grid
+  bool need_ws;               // only with a workspace ...
+  bool need_ws_full;          // ... of at least ws_bytes (a kind without this flag answers a short one itself)
+  unsigned off_bits;          // ct_debug_set_gconv bits that switch the kind off
+  size_t ws_bytes;            // the workspace it wants
+  bool own_bias;              // it produces g_bias itself (the 16-channel ring: on a workspace only, hence have_ws below)
+  WrwMfmaPlan mfma;
+  C4WrwPlan c4m;
+  WrwRingPlan ring;
+};
+
+bool wrw_candidate(int kind, const GconvArgs& a, int dim, bool have_ws, WrwCand& c) {
+  c = WrwCand{};
+  c.a = a;
+  c.own_bias = kind != kWrwTiles && (kind != kWrwRing || have_ws);
+  switch (kind) {
+    case kWrwSmallMfma:       // (debug bit 0: the vector-ALU form instead; short or no workspace: one workgroup per block)
+      if (!plan_wrw_mfma(a, dim, c.mfma)) return false;
+      c.need_aligned = true; c.off_bits = 1;
+      c.ws_bytes = c.mfma.ksplit > 1 ? wrw_block_workspace(a, c.mfma.ksplit) : 0;
+      return true;
+    case kWrwSmallValu:
+      return wrw_small_eligible(a, dim);
+    case kWrwC4Mfma3:         // wherever its plan fits (161 -> 90 us at 32^3 B8, 67 -> 30 at B2, 34 -> 18 on a 5 x 7 x 16 volume;
+                              // debug bit 1 = never)
+      if (!plan_c4_wrw_mfma3(a, dim, c.c4m)) return false;
+      c.need_aligned = c.need_ws = c.need_ws_full = true; c.off_bits = 2;
+      c.ws_bytes = wrw_c4_workspace(a, c.c4m.chunks);
+      return true;
+    case kWrwC4Ring:          // takes unaligned tensors too (the ring kernel stages them element-wise, its own `vec` flag), and it
+                              // must: where this candidate exists the workspace is sized for the four-channel kinds only
+      if (a.Cin != 4 || a.Cout != 4 || (a.W & 3) != 0 || !plan_wrw_ring(c.a, dim, c.ring, 4)) return false;
+      c.need_ws = true;
+      c.ws_bytes = wrw_c4_workspace(a, c.ring.chunks);
+      return true;
+    case kWrwRing:            // with a workspace the two-stage reduction, without one float atomics
+      if ((a.W & 3) != 0 || !plan_wrw_ring(c.a, dim, c.ring)) return false;
+      c.ws_bytes = wrw_block_workspace(a, c.ring.chunks);
+      return true;
+    default: {                // kWrwTiles: any row length.  LDS: 16 input planes with halo + 16 rows of g_y + the cross-wave reduction buffer
+      const size_t red_bytes = (size_t)(kThreads / 64) * 3 * 256 * 4;
+      return plan_tiles(plan_tiles_budget, c.a, dim, (size_t)16 * 4, 1024 + red_bytes, 16,
+                            /*plane == 4 (mod 32): 16-byte aligned for the DMA*/ 4, kLdsBudgetWrw);
+    }
+  }
+}
+
+bool wrw_plan_ok(const GconvArgs& a, int dim) {
+  WrwCand c;
+  for (int kind = 0; kind < kWrwKinds; ++kind)
+    if (wrw_candidate(kind, a, dim, true, c)) return true;
+  return false;
+}
+
+// ---- ... and the launches, one per kind.  A refused call leaves g_w as it was: every check stands before the first write. ----
+int launch_wrw_mfma(const WrwCand& c, int dim, const float* g_y, float* g_w, float* g_bias, float* ws, size_t ws_bytes, hipStream_t st) {
+  const GconvArgs& a = c.a;
+  const WrwMfmaPlan& p = c.mfma;
+  const int ksplit = ws && ws_bytes >= c.ws_bytes ? p.ksplit : 1;      // no workspace: one workgroup per block
+  float* wsp = ksplit > 1 ? ws : nullptr;
   const int CiB = (a.Cin + 15) / 16, CoB = (a.Cout + 15) / 16;
-  dim3 grid(CiB * CoB * p.ksplit, a.groups);
+  dim3 grid(CiB * CoB * ksplit, a.groups);
   note(wsp ? "wrw_small_mfma_ksplit" : "wrw_small_mfma");
   if (wsp) note("wrw_reduce");
   CT_CLEAR_ERROR();
@@ -2830,7 +2849,7 @@ int launch_wrw_mfma(GconvArgs a, int dim, WrwMfmaPlan p, const float* g_y, float
   do {                                                                                              \
     if (set_lds_attr(gconv_wrw_mfma_kernel<DIMV, WTV>, p.lds) != CT_OK) return CT_ELAUNCH;          \
     hipLaunchKernelGGL((gconv_wrw_mfma_kernel<DIMV, WTV>), grid, dim3(kWmThreads), p.lds, st, a, g_y, g_w, g_bias, wsp, \
-                       p.TZ, p.XS, p.GS, p.ksplit);                                                 \
+                       p.TZ, p.XS, p.GS, ksplit);                                                   \
   } while (0)
   if (dim == 2) { if (a.W == 4) CT_WM_LAUNCH(2, 4); else if (a.W == 8) CT_WM_LAUNCH(2, 8); else CT_WM_LAUNCH(2, 16); }
   else { if (a.W == 4) CT_WM_LAUNCH(3, 4); else if (a.W == 8) CT_WM_LAUNCH(3, 8); else CT_WM_LAUNCH(3, 16); }
@@ -2838,114 +2857,117 @@ int launch_wrw_mfma(GconvArgs a, int dim, WrwMfmaPlan p, const float* g_y, float
   CT_CHECK_LAUNCH();
   if (wsp) {
     const size_t n = (size_t)a.groups * CoB * CiB * a.taps * 256;
-    hipLaunchKernelGGL(gconv_wrw_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64, 4), 0, st, wsp, g_w, g_bias, p.ksplit,
+    hipLaunchKernelGGL(gconv_wrw_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64, 4), 0, st, wsp, g_w, g_bias, ksplit,
                        a.groups, a.Cin, a.Cout, a.taps);
     CT_CHECK_LAUNCH();
   }
   return CT_OK;
 }
 
-bool fwd_plan_ok(GconvArgs a, int dim) {
-  if (tiny_cob(a, dim)) return true;
-  if (a.Cin == 4 && a.Cout == 4 && (a.W & 3) == 0 &&
-      (plan_tiles_min_halo(a, dim, 0, 0, 4, 4, kLdsBudget) || plan_tiles_min_halo(a, dim, 0, 0, 4, 4, kLdsBudgetMax))) return true;
-  const size_t wbytes = (size_t)a.taps * a.KB * 64 * 4;          // the one-position form: what the quad form falls back to
-  return plan_tiles(a, dim, 0, wbytes, a.KB * 4, 16);
+int launch_wrw_small(const WrwCand& c, int dim, const float* g_y, float* g_w, float* g_bias, float*, size_t, hipStream_t st) {
+  const GconvArgs& a = c.a;
+  const size_t lds = wrw_small_lds(a, dim);
+  dim3 grid(((a.Cin + 15) / 16) * ((a.Cout + 15) / 16), a.groups);
+  note("wrw_small_valu");
+  CT_CLEAR_ERROR();
+#define CT_WS_LAUNCH(DIMV, WTV)                                                                    \
+  do {                                                                                             \
+    if (set_lds_attr(gconv_wrw_small_kernel<DIMV, WTV>, lds) != CT_OK) return CT_ELAUNCH;          \
+    hipLaunchKernelGGL((gconv_wrw_small_kernel<DIMV, WTV>), grid, dim3(256 * kWsSplit), lds, st, a, g_y, g_w, g_bias); \
+  } while (0)
+  if (dim == 2) {
+    if (a.W == 2) CT_WS_LAUNCH(2, 2); else if (a.W == 4) CT_WS_LAUNCH(2, 4); else if (a.W == 8) CT_WS_LAUNCH(2, 8); else CT_WS_LAUNCH(2, 16);
+  } else {
+    if (a.W == 2) CT_WS_LAUNCH(3, 2); else if (a.W == 4) CT_WS_LAUNCH(3, 4); else if (a.W == 8) CT_WS_LAUNCH(3, 8); else CT_WS_LAUNCH(3, 16);
+  }
+#undef CT_WS_LAUNCH
+  CT_CHECK_LAUNCH();
+  return CT_OK;
 }
 
-bool wrw_plan_ok(GconvArgs a, int dim) {
-  WrwMfmaPlan pm;
-  if (plan_wrw_mfma(a, dim, pm) || wrw_small_eligible(a, dim)) return true;
-  WrwRingPlan p;
-  if ((a.W & 3) == 0 && plan_wrw_ring(a, dim, p, c4_wrw_eligible(a) ? 4 : 16)) return true;
+int launch_c4_wrw_mfma3(const WrwCand& c, int, const float* g_y, float* g_w, float* g_bias, float* ws, size_t, hipStream_t st) {
+  const GconvArgs& a = c.a;
+  const C4WrwPlan& p = c.c4m;
+  note("wrw_c4_mfma3");
+  note("wrw_c4_reduce");
+  dim3 grid(p.nZ, a.groups, a.B);
+  CT_CLEAR_ERROR();
+  if (set_lds_attr(gconv_c4_wrw_mfma3_kernel, p.lds) != CT_OK) return CT_ELAUNCH;
+  hipLaunchKernelGGL(gconv_c4_wrw_mfma3_kernel, grid, dim3(p.nwaves * 64), p.lds, st, a, g_y, ws, p.R, p.LZ, p.SX, p.SG, p.chunks);
+  CT_CHECK_LAUNCH();
+  const int n = a.groups * 16 * a.taps;
+  hipLaunchKernelGGL(gconv_c4_wrw_reduce_kernel, dim3((n + 63) / 64), dim3(64, 4), 0, st, ws, g_w, g_bias, p.chunks, a.groups, a.taps);
+  CT_CHECK_LAUNCH();
+  return CT_OK;
+}
+
+int launch_c4_wrw(const WrwCand& c, int dim, const float* g_y, float* g_w, float* g_bias, float* ws, size_t ws_bytes, hipStream_t st) {
+  const GconvArgs& a = c.a;
+  const WrwRingPlan& p = c.ring;
+  if (ws_bytes < c.ws_bytes) return CT_EWORKSPACE;
+  note("wrw_c4_ring");
+  note("wrw_c4_reduce");
+  dim3 grid(p.chunks, a.groups);
+  if (dim == 2) {
+    if (set_lds_attr(gconv_wrw_ring_kernel<2, true, kThreads>, p.lds) != CT_OK) return CT_ELAUNCH;
+    hipLaunchKernelGGL((gconv_wrw_ring_kernel<2, true, kThreads>), grid, dim3(kThreads), p.lds, st, a, g_y, g_w, ws, p.units_per_wg);
+  } else {
+    if (set_lds_attr(gconv_wrw_ring_kernel<3, true, kThreads>, p.lds) != CT_OK) return CT_ELAUNCH;
+    hipLaunchKernelGGL((gconv_wrw_ring_kernel<3, true, kThreads>), grid, dim3(kThreads), p.lds, st, a, g_y, g_w, ws, p.units_per_wg);
+  }
+  const int n = a.groups * 16 * a.taps;
+  hipLaunchKernelGGL(gconv_c4_wrw_reduce_kernel, dim3((n + 63) / 64), dim3(64, 4), 0, st, ws, g_w, g_bias, p.chunks, a.groups, a.taps);
+  return CT_OK;
+}
+
+// `ws` selects the two-stage reduction; NULL the atomics
+int launch_wrw_ring(const WrwCand& c, int dim, const float* g_y, float* g_w, float* g_bias, float* ws, size_t ws_bytes, hipStream_t st) {
+  const GconvArgs& a = c.a;
+  const WrwRingPlan& p = c.ring;
+  if (ws && ws_bytes < c.ws_bytes) return CT_EWORKSPACE;
+  if (!ws && ct_get_deterministic()) return CT_EPRECOND;      // deterministic mode: the atomic form needs the caller's consent
+  note(ws ? "wrw_ring_ws" : "wrw_ring_atomics");
+  if (ws) note("wrw_reduce");
+  if (!ws && hipMemsetAsync(g_w, 0, (size_t)a.groups * a.Cout * a.Cin * a.taps * 4, st) != hipSuccess) return CT_ELAUNCH;
+  dim3 grid(p.chunks, a.groups);
+  if (dim == 2) {
+    if (set_lds_attr(gconv_wrw_ring_kernel<2, false, kWrwThreads>, p.lds) != CT_OK) return CT_ELAUNCH;
+    hipLaunchKernelGGL((gconv_wrw_ring_kernel<2, false, kWrwThreads>), grid, dim3(kWrwThreads), p.lds, st, a, g_y, g_w, ws, p.units_per_wg);
+  } else {
+    if (set_lds_attr(gconv_wrw_ring_kernel<3, false, kWrwThreads>, p.lds) != CT_OK) return CT_ELAUNCH;
+    hipLaunchKernelGGL((gconv_wrw_ring_kernel<3, false, kWrwThreads>), grid, dim3(kWrwThreads), p.lds, st, a, g_y, g_w, ws, p.units_per_wg);
+  }
+  if (ws) {
+    const size_t CiB = (a.Cin + 15) >> 4, CoB = (a.Cout + 15) >> 4;
+    const size_t n = (size_t)a.groups * CoB * CiB * a.taps * 256;
+    hipLaunchKernelGGL(gconv_wrw_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64, 4), 0, st, ws, g_w, g_bias, p.chunks,
+                       a.groups, a.Cin, a.Cout, a.taps);
+  }
+  return CT_OK;
+}
+
+int launch_wrw_tiles(const WrwCand& c, int dim, const float* g_y, float* g_w, float*, float*, size_t, hipStream_t st) {
+  const GconvArgs& a = c.a;
+  if (ct_get_deterministic()) return CT_EPRECOND;         // float atomics only: refused in deterministic mode (include/cloudct.h)
+  note("wrw_tiles");
+  if (hipMemsetAsync(g_w, 0, (size_t)a.groups * a.Cout * a.Cin * a.taps * 4, st) != hipSuccess) return CT_ELAUNCH;
   const size_t red_bytes = (size_t)(kThreads / 64) * 3 * 256 * 4;
-  return plan_tiles(a, dim, (size_t)16 * 4, 1024 + red_bytes, 16, 4, kLdsBudgetWrw);
-}
-
-// ---- launches of the NORM variants: last on purpose (see launch_fwd4_norm's declaration) ----
-int launch_fwd4_norm(const GconvArgs& a, const GconvEpi& e, int dim, dim3 grid, int threads, size_t lds, hipStream_t st) {
-  note(threads == kThreadsBig ? "quad_1024" : "quad_256");
-  if (a.msplit > 1) note("quad_msplit");
-  CT_CLEAR_ERROR();
+  const int gstride_max = ((a.TD * a.TH * a.W + 3) & ~3) | 1;
+  const size_t lds = ((size_t)16 * a.plane + (size_t)16 * gstride_max) * 4 + red_bytes + 2 * kSlack * 4;
+  const int U = a.B * a.nD * a.nH;
+  int chunks = (512 + a.groups - 1) / a.groups;       // ~512 workgroups in flight
+  if (chunks > U) chunks = U;
+  if (chunks < 1) chunks = 1;
+  const int units_per_wg = (U + chunks - 1) / chunks;
+  chunks = (U + units_per_wg - 1) / units_per_wg;
+  dim3 grid(chunks, a.groups);
   if (dim == 2) {
-    if (set_lds_attr(gconv_fwd4_kernel<2, true>, lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL((gconv_fwd4_kernel<2, true>), grid, dim3(threads), lds, st, fwd_args<true>(a, &e));
+    if (set_lds_attr(gconv_bwd_weight_kernel<2>, lds) != CT_OK) return CT_ELAUNCH;
+    hipLaunchKernelGGL(gconv_bwd_weight_kernel<2>, grid, dim3(kThreads), lds, st, a, g_y, g_w, units_per_wg);
   } else {
-    if (set_lds_attr(gconv_fwd4_kernel<3, true>, lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL((gconv_fwd4_kernel<3, true>), grid, dim3(threads), lds, st, fwd_args<true>(a, &e));
+    if (set_lds_attr(gconv_bwd_weight_kernel<3>, lds) != CT_OK) return CT_ELAUNCH;
+    hipLaunchKernelGGL(gconv_bwd_weight_kernel<3>, grid, dim3(kThreads), lds, st, a, g_y, g_w, units_per_wg);
   }
-  CT_CHECK_LAUNCH();
-  return CT_OK;
-}
-
-int launch_fwd4k_norm(const GconvArgs& t, const GconvEpi& e, int dim, int pass, int maxi, int dma, dim3 grid, size_t lds, hipStream_t st) {
-  note(pass == 0 ? (dma ? "ksplit_one_dma" : "ksplit_one_elem") : (dma ? "ksplit_tiled_dma" : "ksplit_tiled_elem"));
-  note(maxi == 1 ? "ksplit_items1" : maxi == 2 ? "ksplit_items2" : "ksplit_items4");
-  if (t.msplit > 1) note("ksplit_msplit");
-  CT_CLEAR_ERROR();
-#define CT_F4K_NORM(DIMV, MAXIV)                                                                       \
-  do {                                                                                                 \
-    if (set_lds_attr(gconv_fwd4k_kernel<DIMV, MAXIV, false, true>, lds) != CT_OK) return CT_ELAUNCH;   \
-    hipLaunchKernelGGL((gconv_fwd4k_kernel<DIMV, MAXIV, false, true>), grid, dim3(kThreadsBig), lds, st, fwd_args<true>(t, &e), dma); \
-  } while (0)
-#define CT_F4K_NORM_MAXI(DIMV) \
-  do { if (maxi == 1) CT_F4K_NORM(DIMV, 1); else if (maxi == 2) CT_F4K_NORM(DIMV, 2); else CT_F4K_NORM(DIMV, 4); } while (0)
-  if (dim == 2) CT_F4K_NORM_MAXI(2); else CT_F4K_NORM_MAXI(3);
-#undef CT_F4K_NORM_MAXI
-#undef CT_F4K_NORM
-  CT_CHECK_LAUNCH();
-  return CT_OK;
-}
-
-int launch_tiny_norm(const GconvArgs& a, const GconvEpi& e, int dim, int cob, dim3 grid, size_t lds, hipStream_t st) {
-  note(dim == 2 ? "dense2d" : "dense3d");
-  CT_CLEAR_ERROR();
-  if (dim == 2) {
-    if (set_lds_attr(gconv_tiny_kernel<2, true>, lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL((gconv_tiny_kernel<2, true>), grid, dim3(256), lds, st, fwd_args<true>(a, &e), cob);
-  } else {
-    if (set_lds_attr(gconv_tiny_kernel<3, true>, lds) != CT_OK) return CT_ELAUNCH;
-    hipLaunchKernelGGL((gconv_tiny_kernel<3, true>), grid, dim3(256), lds, st, fwd_args<true>(a, &e), cob);
-  }
-  CT_CHECK_LAUNCH();
-  return CT_OK;
-}
-
-// ---- launches of the one-term f16 variants: after everything else (see launch_fwd4_f16's declaration).  Same plans, same tags. ----
-int launch_fwd4_f16(const GconvArgs& a, const GconvEpi* e, int dim, dim3 grid, int threads, size_t lds, hipStream_t st) {
-  note(threads == kThreadsBig ? "quad_1024" : "quad_256");
-  if (a.msplit > 1) note("quad_msplit");
-  CT_CLEAR_ERROR();
-#define CT_F4H(DIMV, NORMV)                                                                              \
-  do {                                                                                                   \
-    if (set_lds_attr(gconv_fwd4_kernel<DIMV, NORMV, true>, lds) != CT_OK) return CT_ELAUNCH;             \
-    hipLaunchKernelGGL((gconv_fwd4_kernel<DIMV, NORMV, true>), grid, dim3(threads), lds, st, fwd_args<NORMV>(a, e)); \
-  } while (0)
-  if (dim == 2) { if (e != nullptr) CT_F4H(2, true); else CT_F4H(2, false); }
-  else { if (e != nullptr) CT_F4H(3, true); else CT_F4H(3, false); }
-#undef CT_F4H
-  CT_CHECK_LAUNCH();
-  return CT_OK;
-}
-
-int launch_fwd4k_f16(const GconvArgs& t, const GconvEpi* e, int dim, int pass, int maxi, int dma, dim3 grid, size_t lds, hipStream_t st) {
-  note(pass == 0 ? (dma ? "ksplit_one_dma" : "ksplit_one_elem") : (dma ? "ksplit_tiled_dma" : "ksplit_tiled_elem"));
-  note(maxi == 1 ? "ksplit_items1" : maxi == 2 ? "ksplit_items2" : "ksplit_items4");
-  if (t.msplit > 1) note("ksplit_msplit");
-  CT_CLEAR_ERROR();
-#define CT_F4KH(DIMV, MAXIV, TRV, NORMV)                                                                 \
-  do {                                                                                                   \
-    if (set_lds_attr(gconv_fwd4k_kernel<DIMV, MAXIV, TRV, NORMV, true>, lds) != CT_OK) return CT_ELAUNCH; \
-    hipLaunchKernelGGL((gconv_fwd4k_kernel<DIMV, MAXIV, TRV, NORMV, true>), grid, dim3(kThreadsBig), lds, st, fwd_args<NORMV>(t, e), dma); \
-  } while (0)
-#define CT_F4KH_MAXI(DIMV, TRV, NORMV) \
-  do { if (maxi == 1) CT_F4KH(DIMV, 1, TRV, NORMV); else if (maxi == 2) CT_F4KH(DIMV, 2, TRV, NORMV); else CT_F4KH(DIMV, 4, TRV, NORMV); } while (0)
-  if (e != nullptr) { if (dim == 2) CT_F4KH_MAXI(2, false, true); else CT_F4KH_MAXI(3, false, true); }
-  else if (dim == 2) { if (t.transposed) CT_F4KH_MAXI(2, true, false); else CT_F4KH_MAXI(2, false, false); }
-  else { if (t.transposed) CT_F4KH_MAXI(3, true, false); else CT_F4KH_MAXI(3, false, false); }
-#undef CT_F4KH_MAXI
-#undef CT_F4KH
-  CT_CHECK_LAUNCH();
   return CT_OK;
 }
 
@@ -2962,12 +2984,11 @@ void ct_gconv_precision_override(int p) {
 }
 
 int ct_gconv_precision_covers(int pass, int B, int groups, int Cin, int Cout, int dim, const int* W) {
-  GconvArgs a = {};                                                // (null tensors: on the 16-byte grid)
+  GconvArgs a = {};
   if ((pass != 0 && pass != 1) || gconv_common(a, B, groups, pass ? Cout : Cin, pass ? Cin : Cout, dim, W) != CT_OK) return 0;
   a.transposed = pass;
-  FwdTook took;
-  if (launch_fwd(a, dim, nullptr, nullptr, /*plan_only=*/true, CT_GCONV_PRECISION_HIGH, &took, /*norm_plan=*/false) != CT_OK) return 0;
-  return took.one_term ? 1 : 0;
+  FwdPlan p;
+  return plan_fwd(a, dim, aligned_inputs(false), p) == CT_OK && p.one_term ? 1 : 0;
 }
 
 void ct_debug_set_gconv(unsigned flags) { t_gconv_debug.store(flags, std::memory_order_relaxed); }
@@ -2980,13 +3001,13 @@ int ct_gconv_fwd(const float* x, const float* w, const float* bias, float* y,
   if (r != CT_OK) return r;
   a.x = x; a.w = w; a.bias = bias; a.y = y; a.transposed = 0;
   note_reset();
-  return launch_fwd(a, dim, (hipStream_t)s, nullptr, false, gconv_precision_now());
+  return run_fwd(a, dim, nullptr, (hipStream_t)s);
 }
 
 int ct_gconv_fwd_norm_supported(int B, int groups, int Cin, int Cout, int dim, const int* W) {
-  GconvArgs a = {};                                                // (null tensors: on the 16-byte grid)
-  if (gconv_common(a, B, groups, Cin, Cout, dim, W) != CT_OK) return 0;
-  return launch_fwd(a, dim, nullptr, nullptr, /*plan_only=*/true) == CT_OK ? 1 : 0;
+  GconvArgs a = {};
+  FwdPlan p;
+  return gconv_common(a, B, groups, Cin, Cout, dim, W) == CT_OK && plan_fwd(a, dim, aligned_inputs(true), p) == CT_OK ? 1 : 0;
 }
 
 int ct_gconv_fwd_norm(const float* x, const float* w, const float* bias, const ct_gconv_norm* norm, const float* skip,
@@ -3008,7 +3029,7 @@ int ct_gconv_fwd_norm(const float* x, const float* w, const float* bias, const c
   if (r != CT_OK) return r;
   a.x = x; a.w = w; a.bias = bias; a.y = y; a.transposed = 0;
   note_reset();
-  return launch_fwd(a, dim, (hipStream_t)s, &e, false, gconv_precision_now());
+  return run_fwd(a, dim, &e, (hipStream_t)s);
 }
 
 int ct_gconv_bwd_data(const float* g_y, const float* w, float* g_x,
@@ -3021,7 +3042,7 @@ int ct_gconv_bwd_data(const float* g_y, const float* w, float* g_x,
   a.x = g_y; a.w = w; a.bias = nullptr; a.y = g_x; a.transposed = 1;
   note_reset();
   note("bwd_data");                                                // the same kernels with TR / a.transposed set
-  return launch_fwd(a, dim, (hipStream_t)s, nullptr, false, gconv_precision_now());
+  return run_fwd(a, dim, nullptr, (hipStream_t)s);
 }
 
 int ct_gconv_supported(int B, int groups, int Cin, int Cout, int dim, const int* W) {
@@ -3032,22 +3053,18 @@ int ct_gconv_supported(int B, int groups, int Cin, int Cout, int dim, const int*
   return fwd_plan_ok(a, dim) && fwd_plan_ok(t, dim) && wrw_plan_ok(a, dim) ? 1 : 0;
 }
 
+// the largest workspace a candidate wants; where a four-channel ring plan exists, of the four-channel kinds only (a four-channel
+// group with a workspace never reaches the others)
 size_t ct_gconv_bwd_weight_workspace_bytes(int B, int groups, int Cin, int Cout, int dim, const int* W) {
   GconvArgs a = {};
-  if (gconv_common(a, B, groups, Cin, Cout, dim, W) != CT_OK || (a.W & 3) != 0) return 0;
-  if (c4_wrw_eligible(a)) {
-    WrwRingPlan p4;
-    C4WrwPlan p4m;
-    size_t need4 = plan_wrw_ring(a, dim, p4, 4) ? c4_wrw_workspace(a, p4) : 0;
-    if (plan_c4_wrw_mfma3(a, dim, p4m) && c4_wrw_mfma3_workspace(a, p4m) > need4) need4 = c4_wrw_mfma3_workspace(a, p4m);
-    if (plan_wrw_ring(a, dim, p4, 4)) return need4;               // (no four-channel ring plan: the launch may take any form below)
-  }
-  WrwRingPlan p;
-  size_t need = plan_wrw_ring(a, dim, p) ? wrw_ring_workspace(a, p) : 0;
-  WrwMfmaPlan pm;
-  if (plan_wrw_mfma(a, dim, pm) && wrw_mfma_workspace(a, pm) > need) need = wrw_mfma_workspace(a, pm);
-  C4WrwPlan p4m;
-  if (plan_c4_wrw_mfma3(a, dim, p4m) && c4_wrw_mfma3_workspace(a, p4m) > need) need = c4_wrw_mfma3_workspace(a, p4m);
+  if (gconv_common(a, B, groups, Cin, Cout, dim, W) != CT_OK) return 0;
+  size_t want[kWrwKinds] = {};
+  WrwCand c;
+  for (int kind = 0; kind < kWrwKinds; ++kind)
+    if (wrw_candidate(kind, a, dim, true, c)) want[kind] = c.ws_bytes;
+  if (want[kWrwC4Ring]) return want[kWrwC4Mfma3] > want[kWrwC4Ring] ? want[kWrwC4Mfma3] : want[kWrwC4Ring];
+  size_t need = 0;
+  for (size_t w : want) need = w > need ? w : need;
   return need;
 }
 
@@ -3062,41 +3079,24 @@ int ct_gconv_bwd_weight(const float* x, const float* g_y, float* g_w, float* g_b
   hipStream_t st = (hipStream_t)s;
   CT_CLEAR_ERROR();
   const bool aligned = ((((uintptr_t)x) | ((uintptr_t)g_y)) & 15) == 0;
-  bool ring_bias = (a.W & 3) == 0 && workspace != nullptr;        // the ring kernels' workspace path produces g_bias itself
-  WrwMfmaPlan pm;
-  if (aligned && !(t_gconv_debug.load(std::memory_order_relaxed) & 1) && plan_wrw_mfma(a, dim, pm))
-    return launch_wrw_mfma(a, dim, pm, g_y, g_w, g_bias, (float*)workspace, workspace_bytes, st);
-  if (wrw_small_eligible(a, dim)) {
-    r = launch_wrw_small(a, dim, g_y, g_w, g_bias, st);
-    if (r != CT_OK) return r;
+  const unsigned dbg = t_gconv_debug.load(std::memory_order_relaxed);
+  constexpr decltype(&launch_wrw_ring) launch[kWrwKinds] = {launch_wrw_mfma, launch_wrw_small, launch_c4_wrw_mfma3,
+                                                            launch_c4_wrw,   launch_wrw_ring,  launch_wrw_tiles};
+  WrwCand c;
+  for (int kind = 0; kind < kWrwKinds; ++kind) {
+    if (!wrw_candidate(kind, a, dim, workspace != nullptr, c) || (c.need_aligned && !aligned) || (dbg & c.off_bits) || (c.need_ws && !workspace) ||
+        (c.need_ws_full && workspace_bytes < c.ws_bytes)) continue;
+    r = launch[kind](c, dim, g_y, g_w, g_bias, (float*)workspace, workspace_bytes, st);
+    if (r != CT_OK || kind == kWrwSmallMfma || kind == kWrwC4Mfma3) return r;      // (the two matrix-core kinds checked their launches)
+    if (g_bias && !c.own_bias) {
+      note("bias_grad");
+      const size_t vol = (size_t)a.D * a.H * a.W;
+      hipLaunchKernelGGL(gconv_bias_grad_kernel, dim3(groups * Cout), dim3(256), 0, st, g_y, g_bias, B, groups * Cout, vol);
+    }
     CT_CHECK_LAUNCH();
     return CT_OK;
   }
-  C4WrwPlan p4m;
-  // four-channel 3D groups: the matrix-core kernel wherever its plan fits (161 -> 90 us at 32^3 B8, 67 -> 30 at B2, 34 -> 18 on a
-  // 5 x 7 x 16 volume; debug bit 1 = never)
-  if (workspace && aligned && plan_c4_wrw_mfma3(a, dim, p4m) && !(t_gconv_debug.load(std::memory_order_relaxed) & 2) &&
-      workspace_bytes >= c4_wrw_mfma3_workspace(a, p4m))
-    return launch_c4_wrw_mfma3(a, p4m, g_y, g_w, g_bias, (float*)workspace, workspace_bytes, st);
-  // (the four-channel ring takes unaligned tensors too — the ring kernel stages them element-wise, its own `vec` flag — and it
-  // must: ct_gconv_bwd_weight_workspace_bytes sizes a four-channel group's workspace for the four-channel plans only)
-  r = CT_EINVAL;
-  if (workspace && c4_wrw_eligible(a)) r = launch_c4_wrw(a, dim, g_y, g_w, g_bias, (float*)workspace, workspace_bytes, st);
-  if (r == CT_EINVAL) {                                            // not a four-channel group, no workspace, or no four-channel plan
-    r = (a.W & 3) == 0 ? launch_wrw_ring(a, dim, g_y, g_w, g_bias, (float*)workspace, workspace_bytes, st) : CT_EINVAL;
-    if (r == CT_EINVAL) {                                          // rows off the 16-byte grid, or rings that do not fit LDS
-      ring_bias = false;
-      r = launch_wrw_tiles(a, dim, g_y, g_w, st);
-    }
-  }
-  if (r != CT_OK) return r;
-  if (g_bias && !ring_bias) {
-    note("bias_grad");
-    const size_t vol = (size_t)a.D * a.H * a.W;
-    hipLaunchKernelGGL(gconv_bias_grad_kernel, dim3(groups * Cout), dim3(256), 0, st, g_y, g_bias, B, groups * Cout, vol);
-  }
-  CT_CHECK_LAUNCH();
-  return CT_OK;
+  return CT_EINVAL;
 }
 
 }  // extern "C"

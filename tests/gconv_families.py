@@ -1,9 +1,10 @@
 """Every kernel family of the grouped convolution (csrc/ct_gconv.hip), one row per launch tag and variant.
 
-The host planner at the bottom of csrc/ct_gconv.hip picks the kernels of ct_gconv_fwd / ct_gconv_bwd_data / ct_gconv_bwd_weight from
-the channel counts per group, the row length modulo 4 / 8 / 16, the volume and the batch (how many workgroups exist), four LDS
-budgets, 16-byte alignment of x / y / g_y / w, the workspace and the ct_debug_set_gconv bits; each launch names itself through
-note(), which ct_debug_last_launch() returns: one tag per kernel, followed by the tags of the host-side choices that change its code
+The host planner in the second half of csrc/ct_gconv.hip (plan_fwd -> FwdPlan for ct_gconv_fwd / ct_gconv_fwd_norm /
+ct_gconv_bwd_data, wrw_candidate -> WrwCand for ct_gconv_bwd_weight) picks the kernels from the channel counts per group, the row
+length modulo 4 / 8 / 16, the volume and the batch (how many workgroups exist), four LDS budgets, 16-byte alignment of
+x / y / g_y / w, the workspace and the ct_debug_set_gconv bits; the one launch function of the family it settles on names itself
+through note(), which ct_debug_last_launch() returns: one tag per kernel, followed by the tags of the host-side choices that change its code
 path, all joined with '+'.  This module is plain data, importable without a GPU:
 
 - tests/test_gconv_families_cpu.py checks that the tags the rows name (plus UNREACHABLE) are exactly the literals passed to note()
@@ -71,7 +72,7 @@ NOPLAN_WRW = (1, 1, 3, 3, (2, 1001))      # ct_gconv_supported == 0: the weight 
                                           # planes of three 1001-float rows fits LDS); not a row: only its return code is checked
 
 ROWS = [
-    # ---- dense 2^d (tiny_cob: cob = 64 / B output channels per workgroup, at least 4, at most Cout) ----
+    # ---- dense 2^d (plan_dense: cob = 64 / B output channels per workgroup, at least 4, at most Cout) ----
     row("dense3d_ragged_channels", FWD, "dense3d", 2, 3, 40, 24, (2, 2, 2), bias=False),
     row("dense3d_cout_not_multiple_of_cob", FWD, "dense3d", 2, 3, 24, 40, (2, 2, 2)),                 # cob 32: blocks of 32 + 8
     row("dense2d", FWD, "dense2d", 3, 2, 5, 7, (2, 2)),

@@ -50,7 +50,7 @@ def test_every_launch_site_is_tagged():
     host = text[text.index("bool plan_tiles_min_halo"):]
     bodies = re.split(r"\n(?=(?:int|bool|size_t|template <typename K>\nint) \w+\()", host)
     launchers = [b for b in bodies if "hipLaunchKernelGGL" in b]
-    assert len(launchers) >= 12
+    assert len(launchers) == 13      # one per family: six forward, six weight-gradient, and ct_gconv_bwd_weight's own bias_grad
     for b in launchers:
         assert re.search(r"(?<![\w.])note\(", b), b.split("{")[0]
 

@@ -112,6 +112,24 @@ def test_the_mode_took_effect_and_only_where_covered(shape, bwd):
     assert tag1 == tag0 and tag0 != ""
 
 
+@pytest.mark.parametrize("row", ["dense3d_ragged_channels", "ksplit_one_64_8cube", "quad_16_32sq"])
+def test_every_variant_of_a_family_notes_the_plain_calls_tags(row):
+    """one launch function per family picks among plain / NORM / F16 / NORM + F16 after it has noted the tags: the four calls on a
+    shape note the same string, the row's (dense has no F16 variant: the mode changes nothing there; 8^3 has the four spans the
+    K-split one-term kernel asks for; 16 input channels per group are the quad one's threshold)"""
+    from tests import test_gconv_norm_gpu as N
+    r = next(r for r in F.ROWS if r.id == row)
+    shape = (r.B, r.G, r.Cin, r.Cout, r.W)
+    assert _covers(0, shape) == (0 if row.startswith("dense") else 1)
+    ops = inputs(shape, "plain")
+    tags = {"plain": _run(F.FWD, shape, ops, bias=r.bias)[1], "norm": N._fused(shape, "norm_relu")[1]}
+    with _high():
+        tags["high"] = _run(F.FWD, shape, ops, bias=r.bias)[1]
+        rc, tags["norm+high"], y = N._fused(shape, "normed_skip_relu")
+    assert rc == F.CT_OK and y.guards_intact()
+    assert tags == dict.fromkeys(tags, r.tag), tags
+
+
 @pytest.mark.parametrize("shape", [(2, 3, 16, 16, (32, 32)), (1, 2, 64, 64, (8, 8, 8))], ids=C.shape_id)
 def test_default_untouched_by_a_high_call(shape):
     ops = inputs(shape, "scaled")

@@ -1,4 +1,4 @@
-"""Time the MFMA grouped conv against PyTorch/MIOpen on the zoo shapes (us, fwd / fwd+bwd)."""
+"""Time the MFMA grouped conv against PyTorch/MIOpen on the zoo shapes (us, fwd / fwd+bwd); --no-ref: without the MIOpen columns."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -31,5 +31,6 @@ SHAPES = [("2D 32^2 C16 H64", GroupedConv2d, 8, 64, 16, (32, 32)), ("2D 128^2 C4
           ("2D 64^2 C16 H16", GroupedConv2d, 8, 16, 16, (64, 64)), ("2D 16^2 C16 H16", GroupedConv2d, 8, 16, 16, (16, 16)),
           ("3D 32^3 C4 H16", GroupedConv3d, 8, 16, 4, (32, 32, 32)), ("3D 16^3 C16 H16", GroupedConv3d, 8, 16, 16, (16, 16, 16)),
           ("3D 8^3 C32 H16", GroupedConv3d, 8, 16, 32, (8, 8, 8))]
+NO_REF = "--no-ref" in sys.argv      # this library's columns only (A/B runs of two builds of it)
 for name, cls, B, G, C, W in SHAPES:
-    print(name, "mfma fwd/fwd+bwd us", bench(cls, B, G, C, W, False), " miopen", bench(cls, B, G, C, W, True), flush=True)
+    print(name, "mfma fwd/fwd+bwd us", bench(cls, B, G, C, W, False), *(() if NO_REF else (" miopen", bench(cls, B, G, C, W, True))), flush=True)
