@@ -15,6 +15,11 @@
 // re-read; other rows take the strided kernel, which re-reads the row (from L2) for each pass.
 #include "ct_common.h"
 
+// Launch tags (ct_common.h): the two entry points reset the tag, the launch functions name the kernel body they picked.
+// tests/norm_families.py holds one row per tag.
+using ct_tags::note;
+using ct_tags::note_reset;
+
 namespace {
 
 constexpr int kThreads = 256;
@@ -384,8 +389,12 @@ static int adain_fwd_launch_table(AdainTable& t, bool vec, hipStream_t stream) {
   const int rows = t.rstart[t.n];
   CT_CLEAR_ERROR();
   if (vec) {
-    CT_ADAIN_DISPATCH(nv_for(t.item[0].N), adain_fwd_reg_kernel, t)
+    const int nv = nv_for(t.item[0].N);
+    note(nv == 1 ? "adain_fwd_reg1" : nv == 2 ? "adain_fwd_reg2" : nv == 4 ? "adain_fwd_reg4" : nv == 8 ? "adain_fwd_reg8"
+                                                                                                      : "adain_fwd_reg16");
+    CT_ADAIN_DISPATCH(nv, adain_fwd_reg_kernel, t)
   } else {
+    note("adain_fwd_strided");
     hipLaunchKernelGGL(adain_fwd_strided_kernel, dim3(rows), dim3(kThreads), 0, stream, t);
   }
   CT_CHECK_LAUNCH();
@@ -395,6 +404,7 @@ static int adain_fwd_launch_table(AdainTable& t, bool vec, hipStream_t stream) {
 // Up to kAdainMaxItems norms over the same (B, N) in one launch (non-empty shapes only: the caller owns the empty ones);
 // a single norm is a table with n = 1.
 extern "C" int ct_adain_group_fwd(const ct_adain_fwd_item* items, int n, int B, int N, ct_stream_t s) {
+  note_reset();
   if (!items || n < 1 || n > kAdainMaxItems || B < 1 || N < 1) return CT_EINVAL;
   AdainTable t{};
   t.n = n;
@@ -435,8 +445,12 @@ static int adain_bwd_launch_table(AdainBwdTable& t, bool vec, hipStream_t stream
   const int rows = t.rstart[t.n];
   CT_CLEAR_ERROR();
   if (vec) {
-    CT_ADAIN_DISPATCH(nv_for(t.item[0].N), adain_bwd_reg_kernel, t)
+    const int nv = nv_for(t.item[0].N);
+    note(nv == 1 ? "adain_bwd_reg1" : nv == 2 ? "adain_bwd_reg2" : nv == 4 ? "adain_bwd_reg4" : nv == 8 ? "adain_bwd_reg8"
+                                                                                                      : "adain_bwd_reg16");
+    CT_ADAIN_DISPATCH(nv, adain_bwd_reg_kernel, t)
   } else {
+    note("adain_bwd_strided");
     hipLaunchKernelGGL(adain_bwd_strided_kernel, dim3(rows), dim3(kThreads), 0, stream, t);
   }
   CT_CHECK_LAUNCH();
@@ -444,6 +458,7 @@ static int adain_bwd_launch_table(AdainBwdTable& t, bool vec, hipStream_t stream
 }
 
 extern "C" int ct_adain_group_bwd(const ct_adain_bwd_item* items, int n, int B, int N, ct_stream_t s) {
+  note_reset();
   if (!items || n < 1 || n > kAdainMaxItems || B < 1 || N < 1) return CT_EINVAL;
   AdainBwdTable t{};
   t.n = n;

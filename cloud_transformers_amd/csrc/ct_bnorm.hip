@@ -12,6 +12,11 @@
 // loop kernels below, which re-read the channel (from L2, mostly) for each pass.
 #include "ct_common.h"
 
+// Launch tags (ct_common.h): every entry point that launches resets the tag, and the launch functions name the kernel body they
+// picked (one tag per body).  tests/norm_families.py holds one row per tag.
+using ct_tags::note;
+using ct_tags::note_reset;
+
 namespace {
 
 constexpr int kThreads = 1024;
@@ -553,10 +558,14 @@ static int bn_fwd_launch_table(BnTable& t, bool vec, hipStream_t stream) {
   const int B = t.item[0].B, N = t.item[0].N, C = t.cstart[t.n];
   CT_CLEAR_ERROR();
   if (vec && reg_ok(B, N)) {
-    CT_BN_DISPATCH(nv_for((long long)B * (N >> 2)), bn_fwd_reg_kernel, t)
+    const int nv = nv_for((long long)B * (N >> 2));
+    note(nv == 1 ? "bn_fwd_reg1" : nv == 2 ? "bn_fwd_reg2" : nv == 4 ? "bn_fwd_reg4" : "bn_fwd_reg8");
+    CT_BN_DISPATCH(nv, bn_fwd_reg_kernel, t)
   } else if (vec) {
+    note("bn_fwd_loop_vec");
     hipLaunchKernelGGL(bn_fwd_loop_kernel<true>, dim3(C), dim3(kThreads), 0, stream, t);
   } else {
+    note("bn_fwd_loop_scalar");
     hipLaunchKernelGGL(bn_fwd_loop_kernel<false>, dim3(C), dim3(kThreads), 0, stream, t);
   }
   CT_CHECK_LAUNCH();
@@ -577,10 +586,14 @@ static int bn_bwd_launch_table(BnBwdTable& t, bool vec, hipStream_t stream) {
   const int B = t.item[0].B, N = t.item[0].N, C = t.cstart[t.n];
   CT_CLEAR_ERROR();
   if (vec && reg_ok(B, N)) {
-    CT_BN_DISPATCH(nv_for((long long)B * (N >> 2)), bn_bwd_reg_kernel, t)
+    const int nv = nv_for((long long)B * (N >> 2));
+    note(nv == 1 ? "bn_bwd_reg1" : nv == 2 ? "bn_bwd_reg2" : nv == 4 ? "bn_bwd_reg4" : "bn_bwd_reg8");
+    CT_BN_DISPATCH(nv, bn_bwd_reg_kernel, t)
   } else if (vec) {
+    note("bn_bwd_loop_vec");
     hipLaunchKernelGGL(bn_bwd_loop_kernel<true>, dim3(C), dim3(kThreads), 0, stream, t);
   } else {
+    note("bn_bwd_loop_scalar");
     hipLaunchKernelGGL(bn_bwd_loop_kernel<false>, dim3(C), dim3(kThreads), 0, stream, t);
   }
   CT_CHECK_LAUNCH();
@@ -589,6 +602,7 @@ static int bn_bwd_launch_table(BnBwdTable& t, bool vec, hipStream_t stream) {
 
 // Up to kBnMaxItems norms over the same (B, N) in one launch; a single norm is a table with n = 1.
 extern "C" int ct_bn_group_fwd(const ct_bn_fwd_item* items, int n, int B, int N, ct_stream_t s) {
+  note_reset();
   if (!items || n < 1 || n > kBnMaxItems) return CT_EINVAL;
   BnTable t{};
   t.n = n;
@@ -614,6 +628,7 @@ extern "C" int ct_bn_group_fwd(const ct_bn_fwd_item* items, int n, int B, int N,
 }
 
 extern "C" int ct_bn_group_bwd(const ct_bn_bwd_item* items, int n, int B, int N, ct_stream_t s) {
+  note_reset();
   if (!items || n < 1 || n > kBnMaxItems) return CT_EINVAL;
   BnBwdTable t{};
   t.n = n;
@@ -699,6 +714,7 @@ static int bn_group_fwd_table(const ct_bn_fwd_item* items, int n, int first, int
 
 extern "C" int ct_bn_group_stats_fwd(const ct_bn_fwd_item* items, int n, int first, int run, int B, int N, float* local,
                                      ct_stream_t s) {
+  note_reset();
   if (!local) return CT_EINVAL;
   BnTable t{};
   bool vec;
@@ -708,6 +724,7 @@ extern "C" int ct_bn_group_stats_fwd(const ct_bn_fwd_item* items, int n, int fir
 
 extern "C" int ct_bn_group_apply_fwd(const ct_bn_fwd_item* items, int n, int first, int run, int B, int N, const float* gathered,
                                      int world, float* count_total, ct_stream_t s) {
+  note_reset();
   if (!gathered || world < 1) return CT_EINVAL;
   BnTable t{};
   bool vec;
@@ -753,6 +770,7 @@ static int bn_group_bwd_table(const ct_bn_bwd_item* items, int n, int first, int
 // sums_copy (nullable): a second copy of this rank's sums, which stays when the collective overwrites `sums` in place
 extern "C" int ct_bn_group_reduce_bwd(const ct_bn_bwd_item* items, int n, int first, int run, int B, int N, float* sums,
                                       float* sums_copy, ct_stream_t s) {
+  note_reset();
   BnBwdTable t{};
   bool vec;
   const int rc = bn_group_bwd_table(items, n, first, run, B, N, 1, sums, sums_copy, nullptr, t, vec);
@@ -761,6 +779,7 @@ extern "C" int ct_bn_group_reduce_bwd(const ct_bn_bwd_item* items, int n, int fi
 
 extern "C" int ct_bn_group_apply_bwd(const ct_bn_bwd_item* items, int n, int first, int run, int B, int N, const float* sums,
                                      const float* count, ct_stream_t s) {
+  note_reset();
   BnBwdTable t{};
   bool vec;
   const int rc = bn_group_bwd_table(items, n, first, run, B, N, 2, const_cast<float*>(sums), nullptr, count, t, vec);
@@ -887,6 +906,7 @@ static bool eval_shape_ok(int B, int C, int N) {
 extern "C" int ct_bn_eval_supported(int B, int C, int N) { return eval_shape_ok(B, C, N) ? 1 : 0; }
 
 extern "C" int ct_bn_eval_group_fwd(const ct_bn_fwd_item* items, int n, int B, int N, ct_stream_t s) {
+  note_reset();
   if (!items || n < 1 || n > kBnMaxItems) return CT_EINVAL;
   BnEvalTable t{};
   t.n = n; t.B = B; t.N = N;
@@ -922,6 +942,7 @@ extern "C" int ct_bn_eval_group_fwd(const ct_bn_fwd_item* items, int n, int B, i
   t.wstart[n] = (int)w0;
   hipStream_t stream = (hipStream_t)s;
   CT_CLEAR_ERROR();
+  note(vec ? "bn_eval_vec" : "bn_eval_scalar");
   if (vec) hipLaunchKernelGGL(bn_eval_kernel<true>, dim3((unsigned)w0), dim3(kThreads), 0, stream, t);
   else hipLaunchKernelGGL(bn_eval_kernel<false>, dim3((unsigned)w0), dim3(kThreads), 0, stream, t);
   CT_CHECK_LAUNCH();
@@ -1067,6 +1088,7 @@ __global__ void __launch_bounds__(kThreads) bn_eval_bwd_kernel(BnEvalBwdTable t)
 }
 
 extern "C" int ct_bn_eval_group_bwd(const ct_bn_eval_bwd_item* items, int n, int B, int N, ct_stream_t s) {
+  note_reset();
   if (!items || n < 1 || n > kBnMaxItems) return CT_EINVAL;
   BnEvalBwdTable t{};
   t.n = n; t.B = B; t.N = N;
@@ -1105,6 +1127,7 @@ extern "C" int ct_bn_eval_group_bwd(const ct_bn_eval_bwd_item* items, int n, int
   t.wstart[n] = (int)w0;
   hipStream_t stream = (hipStream_t)s;
   CT_CLEAR_ERROR();
+  note("bn_eval_bwd");
   hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3((unsigned)w0), dim3(kThreads), 0, stream, t);
   CT_CHECK_LAUNCH();
   return CT_OK;
