@@ -1,7 +1,8 @@
 """YAML-driven training harness around the hot path: the reference's experiment plumbing
 (utils/train_util.py:19-134) and the skeleton of its training scripts (train_segmentation.py:64-230,
 train_classification.py) with synthetic loaders, so that a reference config + model file runs end to end on this
-package's layers and checkpoints stay interchangeable.
+package's layers and checkpoints stay interchangeable.  This module is the generic loop; what a task adds to it — its
+defaults, dataset, batches, loss, validation and end of epoch — is its class in protocols.py.
 
 * config: the reference's YAML schema — `experiment.{root,writer_root}`, `data.{batch_size,num_points,...}`,
   `model.generator` (a python file defining `Model`; the remaining `model.*` keys are its kwargs),
@@ -18,26 +19,9 @@ package's layers and checkpoints stay interchangeable.
 * data: `SyntheticClouds` produces batches of the shapes and dtypes the reference loaders yield (no files needed); with
   `data.kind` in the config (or `Trainer(dataset=...)`) the loop runs on `data/datasets.py`'s readers instead — `scanobjectnn`
   (datasets/scanobjectnn.py: `data.path` = the .h5 / .npz file) and `s3dis` (datasets/s3dis_v2.py: `data.path` = the
-  indoor3d_sem_seg_hdf5_data directory), items equal to the reference loaders' under the same seeds.  `s3dis_kpconv`
-  (`data.path` = the Stanford3dDataset_v1.2 folder) selects the `segmentation_kpconv` task: sphere items sampled on the
-  device, masked cross-entropy with gradient clipping, vote validation and per-epoch checkpoints (train_kpconv.py,
-  train_segmentation_kpconv.py).  `shapenet_completion` (the `completion` task; `data.category_path`, `data.partial_path`,
-  `data.gt_path`, `data.n_renders`, `data.input_size`, `data.gt_size` as configs/inpainting.yaml has them) reads the
-  ShapeNetCompletion .pcd files (data/completion.py) and prepares every batch on the device; one validation per epoch
-  (train_completion.py, train_inpainter.py).  `shapenet_completion_device` (the same keys, optional `data.cache_dir`) reads every
-  file of a subset once, keeps the clouds on the device and gathers, samples and mirrors every batch there in one launch
-  (data/completion.py DeviceCompletionBatches).  `scanobjectnn_device` (the `classification_scanobjectnn` task; `data.path`,
-  `data.path_val`, `data.batch_size_val`, optional `data.subsample`) keeps the ScanObjectNN split on the device and gathers
-  every batch there (data/scanobjectnn.py), validates every `train.val_step` epochs with the reference's accuracies and keeps
-  the `best` / `macc_best` checkpoints (train_classification.py).  `s3dis_device` (the `segmentation_blocks` task; `data.path`,
-  `data.num_points`, `data.test_area`, `data.data_percent`, `data.aug`, `data.batch_size_val` as configs/s3dis.yaml has them)
-  keeps the 1x1 m blocks on the device, assembles and augments every batch in one launch (data/s3dis_blocks.py), fills the
-  train and validation confusion matrices on the device and appends every validation to <exp>/segmentation_val.jsonl
-  (train_segmentation.py).  `what3d_device` (the `reconstruction` task; `data.path`, `data.im_size`, `data.gt_size`,
-  `data.batch_size_val` as configs/reconstruction.yaml has them, optional `data.cache_dir`) keeps the decoded renderings and
-  the clouds of a What3D split on the device, resizes, normalises and resamples every batch in one launch
-  (data/image_point.py), trains on the EMD, validates every epoch (<exp>/reconstruction_val.jsonl, the `best` checkpoints) and
-  scores F1 on the test split (train_reconstruction.py; train_image_reconstruction.py, eval_reconstruction_f1.py).
+  indoor3d_sem_seg_hdf5_data directory), items equal to the reference loaders' under the same seeds.  The kinds `s3dis_kpconv`,
+  `scanobjectnn_device`, `s3dis_device` and `what3d_device` select their task, `shapenet_completion` and
+  `shapenet_completion_device` belong to the `completion` task (protocols.py `PROTOCOLS`, each class's docstring).
 """
 import copy
 import datetime
@@ -49,7 +33,7 @@ from pathlib import Path
 import torch
 from torch import nn
 
-from . import parallel
+from . import parallel, protocols
 
 
 def worker_init_fn(worker_id):
@@ -208,103 +192,34 @@ def make_dataset(cfg, task, n_classes, length=64, channels=3, train=True):
     "scanobjectnn_device" the ScanObjectNN of `data.path` (`train=False`: `data.path_val`) with its items left to the device;
     "s3dis_device" the Indoor3DSemSeg of `data.path` (`train=False`: the blocks of `data.test_area`), its items left to the device;
     "what3d_device" the ImageToPoint of `data.path`, split 'train' (`train=False`: 'val'; `train="test"`: 'test' with
-    `data.eval_points` points), its items left to the device."""
-    data = cfg["data"]
-    kind = str(data.get("kind", "synthetic")).lower()
-    if kind == "what3d_device":
-        assert task == "reconstruction", "data.kind what3d_device is the reconstruction task"
-        from .data.image_point import ImageToPoint
-        split = "test" if train == "test" else ("train" if train else "val")
-        return ImageToPoint(data["path"], split=split, im_size=data["im_size"],
-                            points=data["eval_points"] if split == "test" else data["gt_size"])
-    if kind == "s3dis_device":
-        assert task == "segmentation_blocks", "data.kind s3dis_device is the segmentation_blocks task"
-        from .data import datasets as D
-        # (shuffle and augmentation happen on the device: the host object only reads the shards and splits them by Area)
-        return D.Indoor3DSemSeg(data["path"], data["num_points"], train=train, aug=False, test_area=data.get("test_area", "Area_5"),
-                                data_precent=float(data.get("data_percent", 1.0)))
-    if kind == "scanobjectnn_device":
-        assert task == "classification_scanobjectnn", "data.kind scanobjectnn_device is the classification_scanobjectnn task"
-        from .data import datasets as D
-        # (augmentation and subsampling happen on the device: the host object only reads, centres and normalises)
-        return D.ScanObjectNN(data["path"] if train else data["path_val"], train=False, subsample=None,
-                              center=data.get("center", True), normalize=data.get("normalize", True))
-    if kind in ("shapenet_completion", "shapenet_completion_device"):
-        assert task == "completion", "ShapeNet completion items are (partial cloud, complete cloud): the completion task"
-        from .data.completion import DatasetSubset, shapenet_loader
-        return shapenet_loader(data).get_dataset(DatasetSubset.TRAIN if train else DatasetSubset.VAL)
-    if kind == "s3dis_kpconv":
-        assert task == "segmentation_kpconv", "S3DIS KPConv items are (points, mask, features, labels): the segmentation_kpconv task"
-        from .train_kpconv import load_kpconv_areas
-        return load_kpconv_areas(cfg, train=train)
+    `data.eval_points` points), its items left to the device.  Every kind but "synthetic" is the `dataset` of one protocol."""
+    kind = str(cfg["data"].get("kind", "synthetic")).lower()
     if kind == "synthetic":
-        return SyntheticClouds(task, data["num_points"], n_classes, length=length, channels=channels)
-    from .data import datasets as D
-    if kind == "scanobjectnn":
-        assert task == "classification", "ScanObjectNN items are (points, label, mask): the classification task"
-        return D.ScanObjectNN(data["path"], train=train, subsample=data.get("num_points"), center=data.get("center", True),
-                              normalize=data.get("normalize", True))
-    if kind == "s3dis":
-        assert task == "segmentation", "S3DIS blocks are (points, labels): the segmentation task"
-        return D.Indoor3DSemSeg(data["path"], data["num_points"], train=train, aug=bool(data.get("aug", train)),
-                                test_area=data.get("test_area", "Area_5"), data_precent=float(data.get("data_precent", 1.0)))
-    raise ValueError("data.kind must be synthetic, scanobjectnn, scanobjectnn_device, s3dis, s3dis_device, s3dis_kpconv, shapenet_completion, "
-                     "shapenet_completion_device or what3d_device (got %r)" % kind)
+        return SyntheticClouds(task, cfg["data"]["num_points"], n_classes, length=length, channels=channels)
+    protocol = protocols.DATASETS.get(kind)
+    if protocol is None:
+        raise ValueError("data.kind must be synthetic, scanobjectnn, scanobjectnn_device, s3dis, s3dis_device, s3dis_kpconv, shapenet_completion, "
+                         "shapenet_completion_device or what3d_device (got %r)" % kind)
+    assert task == protocol.name, protocol.mismatch or "data.kind %s is the %s task" % (kind, protocol.name)
+    return protocol.dataset(cfg, train)
 
 
 class Trainer:
     """The reference scripts' loop: model file + YAML config -> DDP(+SyncBN) model, optimizer, scheduler, steps with
     loss reduction to rank 0, `.t7` checkpoints every `train.save_each` iterations.
 
-    `task`: "segmentation" (loss = CE(pred[:, :, 0], labels), train_segmentation.py:178), "classification"
-    (loss = CE(logits, label) + seg_weight * BCE-with-logits(mask), train_classification.py) or "completion"
-    (loss = mean sqrt(EMD(rec, gt, 0.005, 50)) + chamfer_weight * loss_chamfer(rec, gt), train_inpainter.py:186-192;
-    `n_classes` is then the size of the partial cloud) or "segmentation_kpconv" (selected by `data.kind: s3dis_kpconv` too:
-    loss = sum(CE * mask) / sum(mask) of model(points, mask, features), gradients clipped to `train.clip_grad_norm` (10),
-    validation every `train.val_step` epochs and after the last, `generator_epoch_{e}.t7` / `g_opt_epoch_{e}.t7` every
-    `train.save_each_epoch` epochs; `dataset` may be the (train, validation) Areas — train_kpconv.py).  With `data.kind:
-    shapenet_completion` the completion task's batches are prepared on the device (data/completion.py CompletionBatches)
-    and `fit` validates once per epoch (`validate`); with `data.kind: shapenet_completion_device` the subset stays on the device
-    and the items are gathered there too (DeviceCompletionBatches; `dataset` may be a completion Dataset or a
-    DeviceShapeNetCompletion).  "classification_scanobjectnn" (selected by `data.kind:
-    scanobjectnn_device` too; `dataset` may be a data.datasets.ScanObjectNN or a data.scanobjectnn.DeviceScanObjectNN):
-    loss = (1 - seg_weight) * CE(out[0], label) + seg_weight * BCE-with-logits(out[1][:, 0, 0], mask) of train_classification.py:
-    201-204 (the model's output is indexed, so the reference's three-output classifier and two-output models both fit),
-    batches gathered on the device (data/scanobjectnn.py ScanBatches; `n_classes` sizes the per-class accuracies), validation
-    every `train.val_step` epochs, `generator_epoch_{e}.t7` every `train.save_each_epoch` epochs (train_classification.py).
-    "segmentation_blocks" (selected by `data.kind: s3dis_device` too; `dataset` may be a data.datasets.Indoor3DSemSeg or a
-    data.s3dis_blocks.DeviceS3DISBlocks): loss = CE(pred[:, :, 0], labels) on batches assembled on the device (data/s3dis_blocks.py
-    BlockBatches), a train confusion matrix updated every step on the device and reported per epoch (`train_records`),
-    validation every `train.val_step` epochs (<exp>/segmentation_val.jsonl), `generator_iter_{n}.t7` every `train.save_each`
-    iterations and `generator_epoch_{e}.t7` every `train.save_each_epoch` epochs (train_segmentation.py).
-    "reconstruction" (selected by `data.kind: what3d_device` too; `dataset` may be a data.image_point.ImageToPoint or a
-    data.image_point.DeviceImageToPoint; `n_classes` is not used): noise = sphere_noise(B, gt_size), rec = model(noise, img)[0],
-    loss = mean sqrt(EMD(rec, gt, train.emd_eps, train.emd_iters)) on batches assembled on the device (data/image_point.py
-    ImageBatches); loss_chamfer_adj is computed without gradient and logged (`last_chamfer`); the scheduler steps per iteration,
-    `generator_iter_{n}.t7` every `train.save_each` iterations; a validation every epoch (<exp>/reconstruction_val.jsonl,
-    `generator_epoch_{e}.t7` every `train.save_each_epoch` epochs, `generator_best_0.t7` on a new minimum of the EMD —
-    train_reconstruction.py, train_image_reconstruction.py)."""
+    `task`: "segmentation", "classification", "completion", "segmentation_kpconv", "classification_scanobjectnn",
+    "segmentation_blocks" or "reconstruction"; a `data.kind` that selects a task overrides it.  The trainer holds one instance of
+    the task's class of protocols.py (`protocol`): loss, batches, validation rules, end of epoch and the state only that task has
+    are there.  Here are the model, the optimizer and scheduler, the loaders (`loader`, `val_loader`, `sampler`), the step (eager
+    or by graph replay, `_graphs`), the validation pass (`_validate`, `_val_graph`, `val_records`), `iters`, the writer and the
+    experiment directory."""
 
     def __init__(self, cfg, task, n_classes, device=None, dist=None, exp_name="exp", dataset_length=64, make_dirs=True,
                  channels=3, dataset=None):
-        self.cfg = cfg = copy.deepcopy(cfg)
-        if task == "segmentation_kpconv" or str(cfg["data"].get("kind", "")).lower() == "s3dis_kpconv":
-            from .train_kpconv import kpconv_config
-            task, self.cfg = "segmentation_kpconv", kpconv_config(cfg)
-            cfg = self.cfg
-        if task == "classification_scanobjectnn" or str(cfg["data"].get("kind", "")).lower() == "scanobjectnn_device":
-            from .train_classification import classification_config
-            task, self.cfg = "classification_scanobjectnn", classification_config(cfg)
-            cfg = self.cfg
-        if task == "segmentation_blocks" or str(cfg["data"].get("kind", "")).lower() == "s3dis_device":
-            from .train_segmentation import segmentation_config
-            task, self.cfg = "segmentation_blocks", segmentation_config(cfg)
-            cfg = self.cfg
-        if task == "reconstruction" or str(cfg["data"].get("kind", "")).lower() == "what3d_device":
-            from .train_reconstruction import reconstruction_config
-            task, self.cfg = "reconstruction", reconstruction_config(cfg)
-            cfg = self.cfg
-        self.task, self.dist, self.n_classes = task, dist, n_classes
+        protocol = protocols.pick(task, str(cfg["data"].get("kind", "")).lower())
+        self.cfg = cfg = protocol.config(cfg)
+        self.task, self.dist, self.n_classes = protocol.name, dist, n_classes
         self.rank = dist.get_rank() if parallel._active(dist) else 0
         self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         model_cfg = dict(cfg["model"])
@@ -365,185 +280,14 @@ class Trainer:
                     g["lr"] = cfg["restore"]["new_lr"]
         self.scheduler = make_scheduler(self.optimizer, tr["scheduler"]) if "scheduler" in tr else None
         # `dataset`: any torch Dataset whose items have the task's layout; else what `data.kind` of the config names
-        data = dataset if dataset is not None else make_dataset(cfg, task, n_classes, length=dataset_length, channels=channels)
-        self.kp, self.clip, self.val_records = None, None, []
-        kind = str(cfg["data"].get("kind", "")).lower()
-        self.shapenet_device = kind == "shapenet_completion_device"
-        self.shapenet, self.val_loader, self.best_val = kind == "shapenet_completion" or self.shapenet_device, None, None
-        self.scan, self.best_acc, self.best_macc = task == "classification_scanobjectnn", float("-inf"), float("-inf")
-        self.blocks, self.train_meter, self.train_records, self._pred = task == "segmentation_blocks", None, [], None
-        self._graph_preds, self._graph_chamfers, self._val_graph = {}, {}, None
-        self.recon, self.last_chamfer, self._noise_gen = task == "reconstruction", None, None
-        if self.recon:
-            self.sampler = None                          # (ImageBatches holds torch's DistributedSampler itself)
-            self.loader = self._image_batches(data, train=True)
-            self._noise_gen = torch.Generator(device=self.device).manual_seed(int(cfg["data"]["seed"]) * 1000003 + 15485863 + self.rank)
-        elif self.blocks:
-            from .data.s3dis_blocks import SegmentationMeter
-            self.sampler = None                          # (BlockBatches holds torch's DistributedSampler itself)
-            self.loader = self._block_batches(data, train=True)
-            self.train_meter = SegmentationMeter(n_classes)
-        elif self.scan:
-            self.sampler = None                          # (ScanBatches holds torch's DistributedSampler itself)
-            self.loader = self._scan_batches(data, train=True)
-        elif self.shapenet_device:
-            assert task == "completion", "data.kind shapenet_completion_device is the completion task"
-            self.sampler = None                          # (DeviceCompletionBatches holds torch's DistributedSampler itself)
-            self.loader = self._completion_batches(data, train=True)
-        elif self.shapenet:
-            from .data.completion import CompletionBatches
-            assert task == "completion", "data.kind shapenet_completion is the completion task"
-            self.sampler = torch.utils.data.distributed.DistributedSampler(data) if parallel._active(dist) else None
-            self.loader = CompletionBatches(data, cfg["data"]["batch_size"], self.device, seed=int(cfg["data"].get("seed", 0)),
-                                            rank=self.rank, shuffle=True, drop_last=bool(cfg["data"].get("drop_last", True)),
-                                            num_workers=int(cfg["data"].get("num_workers", 0)), sampler=self.sampler,
-                                            worker_init_fn=worker_init_fn)
-        elif task == "segmentation_kpconv":
-            from .train_kpconv import KPConvData
-            # one iteration over the loader is one epoch of device batches (a plan of sphere picks, sharded over the ranks)
-            self.kp = self.loader = KPConvData(cfg, self.device, dist, areas=data)
-            self.sampler, self.clip = None, float(tr["clip_grad_norm"])
-        else:
-            self.sampler = torch.utils.data.distributed.DistributedSampler(data) if parallel._active(dist) else None
-            self.loader = torch.utils.data.DataLoader(data, batch_size=cfg["data"]["batch_size"], shuffle=self.sampler is None,
-                                                      num_workers=int(cfg["data"].get("num_workers", 0)), sampler=self.sampler,
-                                                      drop_last=bool(cfg["data"].get("drop_last", True)),
-                                                      worker_init_fn=worker_init_fn)
-        self.ce, self.bce = nn.CrossEntropyLoss(), nn.BCEWithLogitsLoss()
-        self.iters = 0
-
-    def _completion_batches(self, data, train):
-        """DeviceCompletionBatches over `data` (a host completion Dataset is read and uploaded first), this rank's shard."""
-        from .data.completion import DeviceCompletionBatches, DeviceShapeNetCompletion
-        d = self.cfg["data"]
-        ds = data if isinstance(data, DeviceShapeNetCompletion) else DeviceShapeNetCompletion(data, self.device, cache_dir=d.get("cache_dir"))
-        active = parallel._active(self.dist)
-        return DeviceCompletionBatches(ds, d["batch_size"] if train else d.get("batch_size_val", d["batch_size"]), train=train,
-                                       seed=int(d.get("seed", 0)) + (0 if train else 7919), rank=self.rank,
-                                       world=self.dist.get_world_size() if active else 1, drop_last=bool(d.get("drop_last", True)) and train)
-
-    def _scan_batches(self, data, train):
-        """ScanBatches over `data` (a host ScanObjectNN is uploaded first) with the config's sizes, this rank's shard."""
-        from .data.scanobjectnn import DeviceScanObjectNN, ScanBatches
-        d = self.cfg["data"]
-        ds = data if isinstance(data, DeviceScanObjectNN) else DeviceScanObjectNN(data, self.device)
-        active = parallel._active(self.dist)
-        return ScanBatches(ds, d["batch_size"] if train else d["batch_size_val"], train=train, seed=int(d["seed"]) + (0 if train else 7919), rank=self.rank,
-                           world=self.dist.get_world_size() if active else 1, drop_last=bool(d.get("drop_last", False)) and train,
-                           subsample=d.get("subsample"), sigma=float(d["jitter_sigma"]), clip=float(d["jitter_clip"]))
-
-    def _scan_losses(self, batch):
-        """(loss, loss_cls, loss_seg, model output) of train_classification.py:199-204."""
-        pcd, label, mask = batch
-        out = self.model(pcd)
-        w = float(self.cfg["train"]["seg_weight"])
-        cls_loss, seg_loss = self.ce(out[0], label), self.bce(out[1][:, 0, 0], mask)
-        return (1 - w) * cls_loss + w * seg_loss, cls_loss, seg_loss, out
-
-    def _block_batches(self, data, train):
-        """BlockBatches over `data` (a host Indoor3DSemSeg is uploaded first) with the config's sizes, this rank's shard."""
-        from .data.s3dis_blocks import BlockBatches, DeviceS3DISBlocks
-        d = self.cfg["data"]
-        ds = data if isinstance(data, DeviceS3DISBlocks) else DeviceS3DISBlocks(data, self.device)
-        active = parallel._active(self.dist)
-        return BlockBatches(ds, d["batch_size"] if train else d["batch_size_val"], num_points=d["num_points"], train=train,
-                            aug=bool(d["aug"]) and train, seed=int(d["seed"]) + (0 if train else 7919), rank=self.rank,
-                            world=self.dist.get_world_size() if active else 1, drop_last=bool(d.get("drop_last", False)) and train,
-                            data_percent=float(d["data_percent"]), sigma=float(d["jitter_sigma"]), clip=float(d["jitter_clip"]),
-                            cstd=float(d["color_jitter_std"]), ratio=float(d["color_shift_ratio"]), hue_max=float(d["hue_max"]),
-                            sat_max=float(d["saturation_max"]))
-
-    def _image_batches(self, data, train, points=None):
-        """ImageBatches over `data` (a host ImageToPoint is decoded and uploaded first) with the config's sizes, this rank's shard."""
-        from .data.image_point import DeviceImageToPoint, ImageBatches
-        d = self.cfg["data"]
-        ds = data if isinstance(data, DeviceImageToPoint) else DeviceImageToPoint(data, self.device, cache_dir=d.get("cache_dir"))
-        active = parallel._active(self.dist)
-        return ImageBatches(ds, d["batch_size"] if train else d["batch_size_val"], train=train, seed=int(d["seed"]) + (0 if train else 7919),
-                            rank=self.rank, world=self.dist.get_world_size() if active else 1,
-                            drop_last=bool(d.get("drop_last", False)) and train, points=points)
-
-    def _draw_noise(self, pcd_gt, n_noise=None):
-        """The step's sphere noise [B, 3, gt_size]: ONE draw from `_noise_gen` (the only place the harness draws from it)."""
-        from .metrics import sphere_noise
-        return sphere_noise(pcd_gt.shape[0], pcd_gt.shape[-1] if n_noise is None else n_noise, pcd_gt.device, generator=self._noise_gen)
-
-    def _val_emd(self, rec_bn3, gt_bn3, eps, iters):
-        """The validation EMD of a batch -> (dist [B, n], stats).  `train.val_emd_tail` (default false): the auction through
-        emd_with_info where its shape is supported — the same dist, a cloud's long tail in one launch — and stats = float64
-        [sum of info[:, 0], clouds whose auction did not finish, clouds] on the device; otherwise today's call and stats None."""
-        from .emd import emd_distance, emd_tail_supported, emd_with_info
-        if bool(self.cfg["train"].get("val_emd_tail", False)) and emd_tail_supported(rec_bn3.size(0), rec_bn3.size(1)):
-            dist, _, info = emd_with_info(rec_bn3, gt_bn3, eps, iters)
-            clouds = torch.full((), float(info.size(0)), dtype=torch.float64, device=info.device)
-            return dist, torch.stack([info[:, 0].sum().double(), (info[:, 1] > 0).sum().double(), clouds])
-        return emd_distance(rec_bn3, gt_bn3, eps, iters)[0], None
-
-    def _reconstruct(self, img, pcd_gt, eps, iters, n_noise=None, noise=None, val=False):
-        """(sqrt-EMD loss, rec [B, 3, 1, N], gt [B, 3, 1, n]) of train_image_reconstruction.py:166-175 for a device batch.
-        `noise`: the sphere noise to use (a graph's static buffer, filled from an eager draw); by default it is drawn here.
-        `val`: the validation call — the EMD through `_val_emd`, whose stats come fourth."""
-        from .emd import emd_distance
-        gt = pcd_gt[:, :, None]
-        if noise is None:
-            noise = self._draw_noise(pcd_gt, n_noise)
-        out = self.model(noise, img)
-        rec = out[0] if isinstance(out, (tuple, list)) else out
-        if val:
-            dist, stats = self._val_emd(rec[:, :, 0].permute(0, 2, 1), gt[:, :, 0].permute(0, 2, 1), eps, iters)
-            return torch.sqrt(dist).mean(1).mean(), rec, gt, stats
-        dist, _ = emd_distance(rec[:, :, 0].permute(0, 2, 1), gt[:, :, 0].permute(0, 2, 1), eps, iters)
-        return torch.sqrt(dist).mean(1).mean(), rec, gt
-
-    def _block_pred(self, pcd):
-        out = self.model(pcd)
-        return out[0] if isinstance(out, (tuple, list)) else out                      # the reference returns (pred, lattice stats)
+        data = dataset if dataset is not None else make_dataset(cfg, self.task, n_classes, length=dataset_length, channels=channels)
+        self.kp, self.clip, self.sampler, self.val_loader, self.val_records = None, None, None, None, []
+        self._graphs, self._val_graph, self.iters = {}, None, 0
+        self.protocol = protocol(self)
+        self.loader = self.protocol.loader(self, data, train=True)
 
     def _loss(self, batch):
-        if self.task == "reconstruction":
-            from .chamfer import loss_chamfer_adj
-            tr = self.cfg["train"]
-            loss, rec, gt = self._reconstruct(batch[0], batch[1], float(tr["emd_eps"]), int(tr["emd_iters"]),
-                                              noise=batch[2] if len(batch) > 2 else None)      # (a graph's batch carries its noise)
-            with torch.no_grad():
-                self.last_chamfer = loss_chamfer_adj(rec.detach(), gt)
-            return loss
-        if self.task == "segmentation_blocks":
-            pcd, labels = batch
-            pred = self._block_pred(pcd)
-            # kept for the train confusion (the step's, or a graph's static one) — detached: a tensor with a grad_fn held across
-            # steps keeps the autograd graph and its AccumulateGrad nodes alive, pinned to the stream of the first step, and a
-            # later capture on another stream then breaks
-            self._pred = pred.detach()
-            return self.ce(pred[:, :, 0], labels)
-        if self.task == "classification_scanobjectnn":
-            return self._scan_losses(batch)[0]
-        if self.task == "segmentation_kpconv":
-            from .train_kpconv import masked_cross_entropy
-            points, mask, features, labels = batch
-            return masked_cross_entropy(self.model(points, mask, features), labels, mask)
-        if self.task == "segmentation":
-            pts, labels = batch
-            pcd = pts.permute(0, 2, 1)[:, :, None].to(self.device)                    # (B, channels, 1, N)
-            out = self.model(pcd)
-            pred = out[0] if isinstance(out, (tuple, list)) else out                  # the reference returns (pred, lattice stats)
-            return self.ce(pred[:, :, 0], labels.to(self.device))
-        if self.task == "completion":
-            from .chamfer import loss_chamfer
-            from .emd import emd_distance
-            noise, part, gt = batch
-            out = self.model(noise.to(self.device), part.permute(0, 2, 1)[:, :, None].to(self.device))
-            rec = out[0] if isinstance(out, (tuple, list)) else out                   # (B, 3, 1, N)
-            gt4 = gt.permute(0, 2, 1)[:, :, None].to(self.device)
-            tr = self.cfg["train"]
-            dist, _ = emd_distance(rec[:, :, 0].permute(0, 2, 1), gt4[:, :, 0].permute(0, 2, 1),
-                                   float(tr.get("emd_eps", 0.005)), int(tr.get("emd_iters", 50)))
-            return torch.sqrt(dist).mean(1).mean() + float(tr.get("chamfer_weight", 1.0)) * loss_chamfer(rec, gt4)
-        pts, label, mask = batch
-        logits, mask_pred = self.model(pts.permute(0, 2, 1)[:, :, None].to(self.device))
-        w = float(self.cfg["train"].get("seg_weight", 0.5))
-        return (self.ce(logits, label.to(self.device).long())
-                + w * self.bce(mask_pred.reshape(mask.shape[0], -1), mask.to(self.device).float()))     # (ScanObjectNN's mask is int64)
+        return self.protocol.loss(self, batch)
 
     def save(self, epoch=None):
         """`generator_iter_{iters}.t7` / `g_opt_iter_{iters}.t7`; with `epoch`, `generator_epoch_{epoch}.t7` / `g_opt_epoch_{epoch}.t7`."""
@@ -553,38 +297,9 @@ class Trainer:
 
     # -- validation: the per-batch work as one function of device tensors, run eagerly or by graph replay ------------------
     def _val_step(self, *t):
-        """One validation batch of this task: the eval-mode forward plus the task's validation loss terms, device tensors in,
-        device tensors out (the caller holds eval mode and no_grad; the meters stay with the caller).
-        reconstruction (img, cloud, noise) -> (loss_emd, loss_chamfer); completion (noise, partial, gt) -> (loss_emd,
-        loss_chamfer) — both with the stats of `_val_emd` third under `train.val_emd_tail`; segmentation_blocks (points, labels) -> (pred, loss); classification_scanobjectnn (points, label, mask)
-        -> (loss, loss_cls, loss_seg, logits, mask logits); segmentation_kpconv (points, mask, features, labels) -> (pred, loss)."""
-        tr = self.cfg["train"]
-        if self.task == "reconstruction":
-            from .chamfer import loss_chamfer_adj
-            l_emd, rec, gt, stats = self._reconstruct(t[0], t[1], float(tr["val_emd_eps"]), int(tr["val_emd_iters"]), noise=t[2], val=True)
-            return (l_emd, loss_chamfer_adj(rec, gt)) + (() if stats is None else (stats,))
-        if self.task == "completion":
-            from .chamfer import loss_chamfer
-            from .emd import emd_distance
-            noise, part, gt = t
-            out = self.model(noise, part.permute(0, 2, 1)[:, :, None])
-            rec = out[0] if isinstance(out, (tuple, list)) else out
-            gt4 = gt.permute(0, 2, 1)[:, :, None]
-            dist, stats = self._val_emd(rec[:, :, 0].permute(0, 2, 1), gt4[:, :, 0].permute(0, 2, 1),
-                                        float(tr.get("val_emd_eps", 0.004)), int(tr.get("val_emd_iters", 3000)))
-            return (torch.sqrt(dist).mean(1).mean(), loss_chamfer(rec, gt4)) + (() if stats is None else (stats,))
-        if self.task == "segmentation_blocks":
-            pred = self._block_pred(t[0])
-            return pred, self.ce(pred[:, :, 0], t[1])
-        if self.task == "classification_scanobjectnn":
-            loss, cls_loss, seg_loss, out = self._scan_losses(t)
-            return loss, cls_loss, seg_loss, out[0], out[1]
-        if self.task == "segmentation_kpconv":
-            from .train_kpconv import masked_cross_entropy
-            points, mask, features, labels = t
-            pred = parallel._plain_module(self.model)(points, mask, features)
-            return pred, masked_cross_entropy(pred, labels, mask)
-        raise ValueError("task %r has no validation step" % (self.task,))
+        """One validation batch of the task (the protocol's `val_step`): the eval-mode forward plus the task's validation loss
+        terms, device tensors in, device tensors out (the caller holds eval mode and no_grad; the meters stay with the caller)."""
+        return self.protocol.val_step(self, *t)
 
     def _val_runner(self, hip_graph=None):
         """What a validation pass calls per batch: `_val_step` itself (the launches of today), or — with `hip_graph`, by default
@@ -602,260 +317,64 @@ class Trainer:
             self._val_graph = GraphedForward(parallel._plain_module(self.model), fn=self._val_step, fallback=True, verbose=self.rank == 0)
         return self._val_graph
 
-    def _tail_record(self, rec, tail):
-        """`train.val_emd_tail`: the validation record also says how the auctions ended — the mean over the clouds of the first
-        iteration without a bidder (`val_emd_iters` where there was none) and the clouds whose auction did not finish."""
-        if bool(self.cfg["train"].get("val_emd_tail", False)):
-            t = tail.tolist()
-            if t[2] > 0:
-                rec["emd_first_empty_mean"] = t[0] / t[2]
-                rec["emd_unfinished"] = int(t[1])
-
-    def _validate_completion(self, epoch, dataset=None, hip_graph=None):
-        """train_inpainter.py:253-311: eval mode, no grad, the VAL subset in batches of `data.batch_size_val`; per batch
-        sqrt(EMD(rec, gt, val_emd_eps, val_emd_iters)).mean(1).mean() and loss_chamfer, averaged over the batches and the
-        ranks (sums and the count stay on the device until the one read at the end)."""
+    def _validate(self, epoch=None, hip_graph=None, dataset=None):
+        """One validation pass as the protocol describes it: eval mode, no grad, the validation set (`dataset`, else
+        `make_dataset(train=False)`; the loader is kept) in this rank's batches; the protocol's terms are summed per batch on the
+        device in float64 with the batch count, all-reduced and read once; its meter, reduced after them, adds its keys; the
+        record gets the protocol's best flags, goes to the writer (at `epoch` when it is an int, else at `iters`), to
+        <exp>/<val_file> and to `val_records`; every true flag saves `generator_<flag>_0.t7` / `g_opt_<flag>_0.t7`."""
         import json
-        from .data.completion import CompletionBatches
-        cfg, tr = self.cfg, self.cfg["train"]
-        if self.shapenet_device and (self.val_loader is None or dataset is not None):
-            self.val_loader = self._completion_batches(dataset if dataset is not None else make_dataset(cfg, "completion", None, train=False),
-                                                       train=False)
-        elif self.val_loader is None or dataset is not None:
-            data = dataset if dataset is not None else make_dataset(cfg, "completion", None, train=False)
-            smp = torch.utils.data.distributed.DistributedSampler(data, shuffle=False) if parallel._active(self.dist) else None
-            self.val_loader = CompletionBatches(data, cfg["data"].get("batch_size_val", cfg["data"]["batch_size"]), self.device,
-                                                seed=int(cfg["data"].get("seed", 0)) + 7919, rank=self.rank, sampler=smp,
-                                                num_workers=int(cfg["data"].get("num_workers", 0)), worker_init_fn=worker_init_fn)
-        w = float(tr.get("chamfer_weight", 1.0))
-        model = self.model
-        was_training = model.training
-        model.eval()
-        self.val_loader.set_epoch(epoch if isinstance(epoch, int) else 0)
-        step = self._val_runner(hip_graph)
-        sums = torch.zeros(4, dtype=torch.float64, device=self.device)            # loss, loss_emd, loss_chamfer, batches
-        tail = torch.zeros(3, dtype=torch.float64, device=self.device)            # `train.val_emd_tail`: see _val_emd
-        with torch.no_grad():
-            for noise, part, gt in self.val_loader:
-                l_emd, l_cd, *stats = step(noise, part, gt)
-                sums += torch.stack([l_emd + w * l_cd, l_emd, l_cd, torch.ones_like(l_cd)]).double()
-                if stats:
-                    tail += stats[0]
-        model.train(was_training)
-        if parallel._active(self.dist):
-            self.dist.all_reduce(sums)
-            self.dist.all_reduce(tail)
-        s = sums.tolist()
-        n = max(s[3], 1.0)
-        rec = {"epoch": epoch, "iters": self.iters, "batches": int(s[3]), "loss": s[0] / n, "loss_emd": s[1] / n,
-               "loss_chamfer": s[2] / n}
-        self._tail_record(rec, tail)
-        best = self.best_val is None or rec["loss"] < self.best_val
-        rec["best"] = bool(best)
-        if best:
-            self.best_val = rec["loss"]
-        if self.rank == 0:
-            step = epoch if isinstance(epoch, int) else self.iters
-            for k in ("loss", "loss_emd", "loss_chamfer"):
-                self.writer.add_scalar("val/val_" + k, rec[k], global_step=step)
-            if self.exp_dir is not None:
-                with open(str(Path(self.exp_dir) / "completion_val.jsonl"), "a") as f:
-                    f.write(json.dumps(rec) + "\n")
-                if best:
-                    parallel.save_exp_parallel([self.model, self.optimizer], ["generator", "g_opt"], exp_path=self.exp_dir,
-                                               epoch=0, epoch_name="best")
-        self.val_records.append(rec)
-        return [rec]
-
-    def _validate_reconstruction(self, epoch, dataset=None, hip_graph=None):
-        """train_image_reconstruction.py:225-268: eval mode, no grad, the 'val' split in batches of `data.batch_size_val`; per
-        batch sqrt(EMD(rec, gt, val_emd_eps, val_emd_iters)).mean(1).mean() and loss_chamfer_adj, averaged over the batches and
-        the ranks (sums and the count stay on the device until the one read at the end); `best`: a new minimum of the EMD."""
-        import json
+        p = self.protocol
         if self.val_loader is None or dataset is not None:
             data = dataset if dataset is not None else make_dataset(self.cfg, self.task, self.n_classes, train=False)
-            self.val_loader = self._image_batches(data, train=False)
+            self.val_loader = p.loader(self, data, train=False)
         model = self.model
         was_training = model.training
         model.eval()
         self.val_loader.set_epoch(epoch if isinstance(epoch, int) else 0)
         step = self._val_runner(hip_graph)
-        sums = torch.zeros(3, dtype=torch.float64, device=self.device)            # loss_emd, loss_chamfer, batches
-        tail = torch.zeros(3, dtype=torch.float64, device=self.device)            # `train.val_emd_tail`: see _val_emd
-        with torch.no_grad():
-            for img, pcd in self.val_loader:
-                l_emd, l_cd, *stats = step(img, pcd, self._draw_noise(pcd))    # (the noise: one eager draw per batch, as ever)
-                sums += torch.stack([l_emd, l_cd, torch.ones_like(l_cd)]).double()
-                if stats:
-                    tail += stats[0]
-        model.train(was_training)
-        if parallel._active(self.dist):
-            self.dist.all_reduce(sums)
-            self.dist.all_reduce(tail)
-        s = sums.tolist()
-        n = max(s[2], 1.0)
-        rec = {"epoch": epoch, "iters": self.iters, "batches": int(s[2]), "loss_emd": s[0] / n, "loss_chamfer": s[1] / n}
-        self._tail_record(rec, tail)
-        best = self.best_val is None or rec["loss_emd"] < self.best_val
-        rec["best"] = bool(best)
-        if best:
-            self.best_val = rec["loss_emd"]
-        if self.rank == 0:
-            step = epoch if isinstance(epoch, int) else self.iters
-            for k in ("loss_emd", "loss_chamfer"):
-                self.writer.add_scalar("val/val_" + k, rec[k], global_step=step)
-            if self.exp_dir is not None:
-                with open(str(Path(self.exp_dir) / "reconstruction_val.jsonl"), "a") as f:
-                    f.write(json.dumps(rec) + "\n")
-                if best:
-                    parallel.save_exp_parallel([self.model, self.optimizer], ["generator", "g_opt"], exp_path=self.exp_dir,
-                                               epoch=0, epoch_name="best")
-        self.val_records.append(rec)
-        return [rec]
-
-    def _validate_scan(self, epoch, dataset=None, hip_graph=None):
-        """train_classification.py:286-374: eval mode, no grad, `data.path_val` in batches of `data.batch_size_val`; the three
-        losses averaged over the batches and the ranks, the accuracies from ClassificationMeter's counts all-reduced over the
-        ranks (counts and sums stay on the device until the two reads at the end).  As in the reference the shards are padded
-        to equal length, so with several ranks a few clouds count twice.  `best` / `macc_best`: a strictly higher cls_acc /
-        m_acc than any validation before (the first one always is, unless m_acc is NaN: a class absent from the split)."""
-        import json
-        from .data.scanobjectnn import ClassificationMeter
-        if self.val_loader is None or dataset is not None:
-            data = dataset if dataset is not None else make_dataset(self.cfg, self.task, self.n_classes, train=False)
-            self.val_loader = self._scan_batches(data, train=False)
-        model = self.model
-        was_training = model.training
-        model.eval()
-        self.val_loader.set_epoch(epoch if isinstance(epoch, int) else 0)
-        meter = ClassificationMeter(self.n_classes)
-        step = self._val_runner(hip_graph)
-        sums = torch.zeros(4, dtype=torch.float64, device=self.device)            # loss, loss_cls, loss_seg, batches
+        sums = torch.zeros(len(p.val_terms) + 1, dtype=torch.float64, device=self.device)            # the terms, batches
+        meter = p.val_meter(self)
         with torch.no_grad():
             for batch in self.val_loader:
-                loss, cls_loss, seg_loss, logits, mask_logits = step(*batch)
-                sums += torch.stack([loss, cls_loss, seg_loss, torch.ones_like(loss)]).double()
-                meter.update(logits, mask_logits, batch[1], batch[2])
+                terms = p.val_batch(self, step, batch, meter)
+                sums += torch.stack([*terms, torch.ones_like(terms[0])]).double()
         model.train(was_training)
         if parallel._active(self.dist):
             self.dist.all_reduce(sums)
-            meter.reduce(self.dist)
+            if meter is not None:
+                meter.reduce(self.dist)
         s = sums.tolist()
-        n = max(s[3], 1.0)
-        rec = {"epoch": epoch, "iters": self.iters, "batches": int(s[3]), "loss": s[0] / n, "loss_cls": s[1] / n, "loss_seg": s[2] / n}
-        rec.update(meter.result())
-        rec["best"], rec["macc_best"] = bool(rec["cls_acc"] > self.best_acc), bool(rec["m_acc"] > self.best_macc)
-        if rec["best"]:
-            self.best_acc = rec["cls_acc"]
-        if rec["macc_best"]:
-            self.best_macc = rec["m_acc"]
+        n = max(s[-1], 1.0)
+        rec = {"epoch": epoch, "iters": self.iters, "batches": int(s[-1])}
+        rec.update((k, v / n) for k, v in zip(p.val_terms, s))
+        if meter is not None:
+            rec.update(meter.result())
+        flags = p.best(rec)
+        rec.update(flags)
         if self.rank == 0:
-            step = epoch if isinstance(epoch, int) else self.iters
-            for k in ("loss", "loss_cls", "loss_seg", "cls_acc", "seg_acc", "m_acc"):
-                self.writer.add_scalar("val/" + k, rec[k], global_step=step)
+            at = epoch if isinstance(epoch, int) else self.iters
+            for tag, v in p.val_scalars(rec).items():
+                self.writer.add_scalar(tag, v, global_step=at)
             if self.exp_dir is not None:
-                with open(str(Path(self.exp_dir) / "classification_val.jsonl"), "a") as f:
+                with open(str(Path(self.exp_dir) / p.val_file), "a") as f:
                     f.write(json.dumps(rec) + "\n")
-                for flag in ("best", "macc_best"):
-                    if rec[flag]:
+                for flag, on in flags.items():
+                    if on:
                         parallel.save_exp_parallel([self.model, self.optimizer], ["generator", "g_opt"], exp_path=self.exp_dir,
                                                    epoch=0, epoch_name=flag)
         self.val_records.append(rec)
         return [rec]
 
-    def _validate_blocks(self, epoch, dataset=None, hip_graph=None):
-        """train_segmentation.py:244-288: eval mode, no grad, the blocks of `data.test_area` in batches of `data.batch_size_val`
-        (shuffled points, no augmentation); the loss averaged over the batches and the ranks, the confusion matrix filled on the
-        device (SegmentationMeter) and all-reduced over the ranks, `return_metrics_dict`'s numbers from it (sums and counts stay
-        on the device until the two reads at the end).  As in the reference the shards are padded to equal length, so with
-        several ranks a few blocks count twice."""
-        import json
-        from .data.s3dis_blocks import SegmentationMeter
-        if self.val_loader is None or dataset is not None:
-            data = dataset if dataset is not None else make_dataset(self.cfg, self.task, self.n_classes, train=False)
-            self.val_loader = self._block_batches(data, train=False)
-        model = self.model
-        was_training = model.training
-        model.eval()
-        self.val_loader.set_epoch(epoch if isinstance(epoch, int) else 0)
-        meter = SegmentationMeter(self.n_classes)
-        step = self._val_runner(hip_graph)
-        sums = torch.zeros(2, dtype=torch.float64, device=self.device)            # loss, batches
-        with torch.no_grad():
-            for pcd, labels in self.val_loader:
-                pred, loss = step(pcd, labels)
-                sums += torch.stack([loss, torch.ones_like(loss)]).double()
-                meter.update(pred, labels)
-        model.train(was_training)
-        if parallel._active(self.dist):
-            self.dist.all_reduce(sums)
-            meter.reduce(self.dist)
-        s = sums.tolist()
-        rec = {"epoch": epoch, "iters": self.iters, "batches": int(s[1]), "loss": s[0] / max(s[1], 1.0)}
-        rec.update(meter.result())
-        if self.rank == 0:
-            step = epoch if isinstance(epoch, int) else self.iters
-            for k, v in rec.items():
-                if k not in ("epoch", "iters", "batches"):
-                    self.writer.add_scalar("val/" + k, v, global_step=step)
-            if self.exp_dir is not None:
-                with open(str(Path(self.exp_dir) / "segmentation_val.jsonl"), "a") as f:
-                    f.write(json.dumps(rec) + "\n")
-        self.val_records.append(rec)
-        return [rec]
-
-    def _report_train_confusion(self, epoch):
-        """The epoch's train metrics (train_segmentation.py:236-237) from the confusion matrix the steps filled; it starts anew."""
-        if self.train_meter.conf is None:
-            return
-        if parallel._active(self.dist):
-            self.train_meter.reduce(self.dist)
-        rec = dict(self.train_meter.result(), epoch=epoch, iters=self.iters)
-        self.train_meter.reset()
-        if self.rank == 0:
-            for k, v in rec.items():
-                if k not in ("epoch", "iters"):
-                    self.writer.add_scalar("train/" + k, v, global_step=epoch)
-        self.train_records.append(rec)
-
-    def validate(self, num_votes=None, epoch=None, hip_graph=None):
-        """segmentation_kpconv: one validation of `num_votes` vote passes (train_kpconv.KPConvData.validate) on the unwrapped
-        model; the records go to the writer and, on rank 0, to <exp>/kpconv_val.jsonl.  Returns them.
-        completion (`num_votes` is not used): one pass over the VAL subset (`_validate_completion`), its record appended to
-        <exp>/completion_val.jsonl and, on a new minimum of the loss, `generator_best_0.t7` / `g_opt_best_0.t7` saved.
-        classification_scanobjectnn (`num_votes` is not used): one pass over `data.path_val` (`_validate_scan`), its record
-        (losses, cls_acc, seg_acc, m_acc, class_acc) appended to <exp>/classification_val.jsonl; `generator_best_0.t7` /
-        `g_opt_best_0.t7` saved on a new best cls_acc, `generator_macc_best_0.t7` / `g_opt_macc_best_0.t7` on a new best m_acc.
-        segmentation_blocks (`num_votes` is not used): one pass over the blocks of `data.test_area` (`_validate_blocks`), its record
-        (loss, overall_acc, mean_class_acc, iou_<name>, mean_iou) appended to <exp>/segmentation_val.jsonl.
-        reconstruction (`num_votes` is not used): one pass over the 'val' split (`_validate_reconstruction`), its record (loss_emd,
-        loss_chamfer) appended to <exp>/reconstruction_val.jsonl; `generator_best_0.t7` / `g_opt_best_0.t7` on a new minimum.
+    def validate(self, num_votes=None, epoch=None, hip_graph=None, dataset=None):
+        """One validation of the task (the protocol's `validate`: `_validate`, or the KPConv vote passes, which alone use
+        `num_votes`); returns its records.  `dataset`: validate on this set instead of the config's (the loader is rebuilt).
 
         `hip_graph` (default: `train.hip_graph_val` of the config, else False; independent of `train.hip_graph`): the per-batch
         work — eval-mode forward plus the validation loss terms, `_val_step` — runs by replay of one HIP graph per batch shape
         (`_val_runner`, graphs.GraphedForward); the meters and tables stay eager on the graph's static outputs.  The graphs read
         the parameters where they live and are kept between validations: training steps in between need no new capture."""
-        import json
-        if self.task == "reconstruction":
-            return self._validate_reconstruction(epoch, hip_graph=hip_graph)
-        if self.task == "segmentation_blocks":
-            return self._validate_blocks(epoch, hip_graph=hip_graph)
-        if self.task == "completion":
-            return self._validate_completion(epoch, hip_graph=hip_graph)
-        if self.task == "classification_scanobjectnn":
-            return self._validate_scan(epoch, hip_graph=hip_graph)
-        records = self.kp.validate(parallel._plain_module(self.model), num_votes, epoch, step=self._val_runner(hip_graph))
-        if self.rank == 0:
-            for rec in records:
-                step = self.iters
-                for k in ("loss", "part_miou", "running_sub_miou", "sub_miou", "full_miou"):
-                    self.writer.add_scalar("val/%s_v%d" % (k, rec["vote"]), rec[k], global_step=step)
-            if self.exp_dir is not None:
-                with open(str(Path(self.exp_dir) / "kpconv_val.jsonl"), "a") as f:
-                    for rec in records:
-                        f.write(json.dumps(rec) + "\n")
-        self.val_records += records
-        return records
+        return self.protocol.validate(self, num_votes, epoch, hip_graph, dataset)
 
     def _clip(self):
         if self.clip is not None:
@@ -864,8 +383,7 @@ class Trainer:
     # -- one training step -------------------------------------------------------------------------------------------
     def _eager_step(self, batch):
         loss = self._loss(batch)
-        if self.blocks:
-            self.train_meter.update(self._pred, batch[1])
+        self.protocol.after_step(self.protocol.out, batch)
         loss.backward()
         self._clip()
         self.optimizer.step()
@@ -882,9 +400,8 @@ class Trainer:
         gradient all-reduce and the norms' statistics exchanges: RCCL collectives are captured like kernels); the optimizer
         step stays outside.  The blocks' eager launch rate is host-bound (~250 launches per block through Python / ctypes:
         the segmenter step 30.8 ms eager vs 24.8 ms graphed, profiles/r3_tools_output.txt).  Returns the record of the
-        capture: (graph, static inputs, static loss, the gradient tensors the graph writes).  Reconstruction: the static inputs
-        are (image, cloud, noise) — the noise is an input of the graph, and neither the warm-up nor the capture draws from
-        `_noise_gen`; `last_chamfer` of the capture is a static output."""
+        capture: (graph, static inputs, static loss, the gradient tensors the graph writes, the protocol's `out` of the captured
+        step: static too).  The static inputs are the protocol's `graph_inputs`; the warm-up and the capture take them as given."""
         static = [t.to(self.device).clone() for t in batch]
         buffers = [b.clone() for b in self.model.buffers()]          # the warm-up passes must not count as training steps
         params = [p for p in self.model.parameters() if p.requires_grad]
@@ -908,7 +425,7 @@ class Trainer:
         with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
             static_loss = self._loss(static)
             static_loss.backward()
-        return graph, static, static_loss, [p.grad for p in params]
+        return graph, static, static_loss, [p.grad for p in params], self.protocol.out
 
     def _graph_step(self, batch):
         """One step by graph replay.  A graph is captured per batch SHAPE (a ragged last batch, `data.drop_last: false`,
@@ -917,18 +434,12 @@ class Trainer:
         captured tensors with zero_grad(), would silently stop the training."""
         key = tuple(tuple(t.shape) for t in batch)
         rec = self._graphs.get(key)
-        if self.recon and rec is not False:
-            # the step's noise: the same generator, the same call and the same one draw per step as the eager step's, drawn
-            # here, outside the graph, and handed to it as a third static input (an eager fall-back step draws its own)
-            batch = (batch[0], batch[1], self._draw_noise(batch[1]))
+        if rec is not False:
+            batch = self.protocol.graph_inputs(self, batch)      # (drawn out here, outside the graph; an eager fall-back step makes its own)
         if rec is None:
             rec, failure = None, None
             try:
                 rec = self._capture(batch)
-                if self.blocks:
-                    self._graph_preds[key] = self._pred       # the graph's static prediction: read after every replay
-                if self.recon:
-                    self._graph_chamfers[key] = self.last_chamfer      # likewise the logged Chamfer term
             except RuntimeError as ex:
                 # only what a refused CAPTURE raises (HIP's stream-capture errors, e.g. the process group's watchdog touching an
                 # event of the capturing stream); a genuine error inside the model or the loss is not swallowed as "capture failed"
@@ -953,15 +464,12 @@ class Trainer:
                 rec = False
             self._graphs[key] = rec
         if rec is False:
-            return self._eager_step(batch)            # (reconstruction: a noise drawn above rides along as batch[2])
-        graph, static, static_loss, grads = rec
+            return self._eager_step(batch)            # (graph inputs made above ride along in the batch)
+        graph, static, static_loss, grads, out = rec
         for dst, src in zip(static, batch):
             dst.copy_(src, non_blocking=True)
         graph.replay()
-        if self.blocks:
-            self.train_meter.update(self._graph_preds[key], static[1])
-        if self.recon:
-            self.last_chamfer = self._graph_chamfers[key]             # static: _fit appends a clone
+        self.protocol.after_step(out, static)         # (`out` is static: the next replay overwrites it)
         for p, g in zip((p for p in self.model.parameters() if p.requires_grad), grads):
             p.grad = g
         self._clip()
@@ -978,9 +486,8 @@ class Trainer:
         torchrun users set it themselves; the price is that a hung collective then hangs the job instead of aborting it.  A capture that
         fails falls back to eager steps on one device and RAISES under DistributedDataParallel — the ranks agree on it first).  Losses stay on the
         device and are read back every `log_each` steps (default `train.log_each`, else 10) in ONE transfer — no host
-        synchronisation per step (the reference reads the loss every step: train_segmentation.py:180-186).  The reconstruction
-        task's sphere noise is an INPUT of its graph: one eager draw per step from `_noise_gen`, before the replay, in step order,
-        so a graphed and an eager run of one seed see the same noise at step k; the logged Chamfer term is a static output.
+        synchronisation per step (the reference reads the loss every step: train_segmentation.py:180-186); so are the protocol's
+        `logged` scalars (the reconstruction's Chamfer term; its noise under `hip_graph`: protocols.Reconstruction).
 
         `train.deterministic: true` runs the whole fit in deterministic mode (determinism.py: run-to-run equal gradients from
         the library's kernels, all five tasks); the seeds are set as without it and nothing else changes.
@@ -1006,33 +513,31 @@ class Trainer:
                 scopes.enter_context(precision.conv_precision(self.cfg["train"]["conv_precision"]))
             return self._fit(max_iters, hip_graph, log_each)
 
+    def _flush(self):
+        """The pending losses (and logged scalars) of this rank to the history and the writer: one transfer each."""
+        if self.device.type == "cuda":
+            from . import ops
+            ops.mhct_core_check()        # (the one place the loop waits for the device anyway: a cluster timeout raises here)
+        for pending in (self._pending, self._pending_logged):
+            if pending and self.rank == 0:
+                tags, stamps, vals = zip(*pending)
+                for tag, it, v in zip(tags, stamps, torch.stack(vals).tolist()):      # one device-to-host copy for the interval
+                    if tag == "train/loss":
+                        self._history.append(v)
+                    self.writer.add_scalar(tag, v, global_step=it)
+            pending.clear()
+
     def _fit(self, max_iters, hip_graph, log_each):
-        tr = self.cfg["train"]
+        tr, p = self.cfg["train"], self.protocol
         use_graph = bool(tr.get("hip_graph", False) if hip_graph is None else hip_graph)
         log_each = int(tr.get("log_each", 10) if log_each is None else log_each)
-        self._graphs, self._graph_preds, self._graph_chamfers = {}, {}, {}
-        history, pending, pending_chamfer = [], [], []
-
-        def flush():
-            if self.device.type == "cuda":
-                from . import ops
-                ops.mhct_core_check()        # (the one place the loop waits for the device anyway: a cluster timeout raises here)
-            if pending and self.rank == 0:
-                stamps, vals = zip(*pending)
-                for it, v in zip(stamps, torch.stack(vals).tolist()):      # one device-to-host copy for the interval
-                    history.append(v)
-                    self.writer.add_scalar("train/loss", v, global_step=it)
-            pending.clear()
-            if pending_chamfer and self.rank == 0:
-                stamps, vals = zip(*pending_chamfer)
-                for it, v in zip(stamps, torch.stack(vals).tolist()):
-                    self.writer.add_scalar("train/loss_chamfer", v, global_step=it)
-            pending_chamfer.clear()
-
+        self._graphs = {}
+        self._history, self._pending, self._pending_logged = [], [], []
+        history = self._history
         for epoch in range(tr["num_epochs"]):
             if self.sampler is not None:
                 self.sampler.set_epoch(epoch)
-            if self.scan or self.blocks or self.recon or self.shapenet_device:
+            if p.loader_epochs:
                 self.loader.set_epoch(epoch)
             self.model.train()
             end = time.time()
@@ -1047,60 +552,25 @@ class Trainer:
                 if self.scheduler is not None:
                     self.scheduler.step()
                 reduced = parallel.reduce_loss_dict(self.dist, {"loss": loss})
-                pending.append((self.iters, reduced["loss"].detach().reshape(())))
-                if self.recon and self.last_chamfer is not None:
-                    chamfer = parallel.reduce_loss_dict(self.dist, {"loss_chamfer": self.last_chamfer})["loss_chamfer"]
-                    chamfer = chamfer.detach().reshape(())
-                    # (under hip_graph `last_chamfer` is a static output that the next replay overwrites: a clone is kept)
-                    pending_chamfer.append((self.iters, chamfer.clone() if use_graph else chamfer))
+                self._pending.append(("train/loss", self.iters, reduced["loss"].detach().reshape(())))
+                if p.logged is not None:
+                    for k, v in parallel.reduce_loss_dict(self.dist, p.logged).items():
+                        v = v.detach().reshape(())
+                        # (under hip_graph a logged scalar is a static output that the next replay overwrites: a clone is kept)
+                        self._pending_logged.append(("train/" + k, self.iters, v.clone() if use_graph else v))
                 self.iters += 1
                 if self.iters % log_each == 0:
-                    flush()
+                    self._flush()
                     if self.rank == 0:
                         self.writer.add_scalar("train/batch_time", (time.time() - end) / log_each, global_step=self.iters)
                     end = time.time()
-                if self.kp is None and self.iters % tr.get("save_each", 1 << 62) == 0:
+                if p.save_by_iter and self.iters % tr.get("save_each", 1 << 62) == 0:
                     self.save()
                 if max_iters is not None and self.iters >= max_iters:
-                    flush()
+                    self._flush()
                     return history
-            if self.kp is not None:
-                # train_segmentation_kpconv.py:240-266: 2-vote validation every val_step epochs, checkpoints per epoch
-                flush()
-                e = epoch + 1
-                if self.rank == 0:
-                    self.writer.add_scalar("learning_rate", self.optimizer.param_groups[0]["lr"], global_step=e)
-                if e % int(tr["val_step"]) == 0:
-                    self.validate(int(tr["val_votes"]), e)
-                if e % int(tr["save_each_epoch"]) == 0:
-                    self.save(epoch=e)
-            if self.shapenet:
-                flush()
-                self.validate(epoch=epoch)                # train_inpainter.py:253-311: once per epoch
-            if self.blocks:
-                # train_segmentation.py:236-244: the train metrics, then checkpoints and validation by the 0-based epoch
-                flush()
-                self._report_train_confusion(epoch)
-                if epoch > 0 and epoch % int(tr["save_each_epoch"]) == 0:
-                    self.save(epoch=epoch)
-                if epoch % int(tr["val_step"]) == 0:
-                    self.validate(epoch=epoch)
-            if self.recon:
-                # train_image_reconstruction.py:225-268: a validation every epoch, checkpoints by the 0-based epoch
-                flush()
-                self.validate(epoch=epoch)
-                if epoch % int(tr["save_each_epoch"]) == 0:
-                    self.save(epoch=epoch)
-            if self.scan:
-                # train_classification.py:281-286: checkpoints and validation by the 0-based epoch
-                flush()
-                if epoch > 0 and epoch % int(tr["save_each_epoch"]) == 0:
-                    self.save(epoch=epoch)
-                if epoch % int(tr["val_step"]) == 0:
-                    self.validate(epoch=epoch)
-        flush()
-        if self.kp is not None:
-            self.validate(int(tr["final_votes"]), "Last")
+            p.after_epoch(self, epoch)
+        self._flush()
         return history
 
 

@@ -67,6 +67,33 @@ def rank_env(rank, world, port, base=None, capture=False):
     return env
 
 
+def run_entry(script, argv, gpus, config, body, spawn=True):
+    """What the training entry points share.  With `gpus` > 1, `spawn` and no launcher above: start `script` (a file: the
+    entry's `__file__`) as `gpus` ranks with `argv` less its `--gpus` option, `capture` as `train.hip_graph` of the YAML `config`
+    says, raise SystemExit on a non-zero code and return [].  Otherwise run `body(dist)` in this process — under a launcher
+    `dist` is torch.distributed with the RCCL group of this rank's device initialised, and destroyed afterwards; else None."""
+    if gpus > 1 and spawn and not under_launcher():
+        from .harness import load_config
+        rest = [a for i, a in enumerate(argv) if a != "--gpus" and (i == 0 or argv[i - 1] != "--gpus") and not a.startswith("--gpus=")]
+        rc = spawn_ranks(os.path.abspath(script), rest, gpus, capture=bool(load_config(config).get("train", {}).get("hip_graph", False)))
+        if rc != 0:
+            raise SystemExit(rc)
+        return []
+    dist = None
+    if under_launcher():
+        import torch
+        import torch.distributed as dist
+        local = int(os.environ.get("LOCAL_RANK", "0"))
+        torch.cuda.set_device(local)
+        dist.init_process_group("nccl", rank=int(os.environ["RANK"]), world_size=int(os.environ["WORLD_SIZE"]),
+                                device_id=torch.device("cuda", local))
+    try:
+        return body(dist)
+    finally:
+        if dist is not None:
+            dist.destroy_process_group()
+
+
 def spawn_ranks(script, argv, nproc, timeout=None, python=None, capture=False):
     """Run `python script argv...` as ranks 0..nproc-1 of one job; stdout/stderr are inherited (rank 0 prints the
     result line).  Returns 0 when every rank exited 0, else the first non-zero code (the other ranks are

@@ -17,28 +17,18 @@ are HDF5 (or their .npz twins: data/datasets.py).
   work by HIP-graph replay, as in the validations of a training run); its record is printed and returned.
 - `--gpus N > 1`: N ranks through `launch.spawn_ranks`, one process group over RCCL (training only)."""
 import argparse
-import copy
 import json
 import os
 import sys
 
 import torch
 
-CLASSIFICATION_DATA = {"kind": "scanobjectnn_device", "n_classes": 15, "jitter_sigma": 0.01, "jitter_clip": 0.05, "seed": 0,
-                       "center": True, "normalize": True}
-CLASSIFICATION_TRAIN = {"seg_weight": 0.5, "val_step": 1, "save_each_epoch": 10}
-
 
 def classification_config(cfg):
-    """A copy of `cfg` with the protocol's defaults (train_classification.py:146,176,281-286; datasets/scanobjectnn.py:30)
-    under the keys it lacks; `data.batch_size_val` defaults to `data.batch_size`."""
-    cfg = copy.deepcopy(cfg)
-    for key, defaults in (("data", CLASSIFICATION_DATA), ("train", CLASSIFICATION_TRAIN)):
-        sect = cfg.setdefault(key, {})
-        for k, v in defaults.items():
-            sect.setdefault(k, v)
-    cfg["data"].setdefault("batch_size_val", cfg["data"].get("batch_size", 1))
-    return cfg
+    """A copy of `cfg` with the protocol's defaults (protocols.Scan `DATA` / `TRAIN`) under the keys it lacks;
+    `data.batch_size_val` defaults to `data.batch_size`."""
+    from .protocols import Scan
+    return Scan.config(cfg)
 
 
 def _parse(argv):
@@ -55,21 +45,8 @@ def main(argv=None):
     from . import harness, launch
     argv = list(sys.argv[1:] if argv is None else argv)
     args = _parse(argv)
-    if args.gpus > 1 and not args.eval and not launch.under_launcher():
-        rest = [a for i, a in enumerate(argv) if a != "--gpus" and (i == 0 or argv[i - 1] != "--gpus") and not a.startswith("--gpus=")]
-        cfg = harness.load_config(args.config)
-        rc = launch.spawn_ranks(os.path.abspath(__file__), rest, args.gpus, capture=bool(cfg.get("train", {}).get("hip_graph", False)))
-        if rc != 0:
-            raise SystemExit(rc)
-        return []
-    dist = None
-    if launch.under_launcher():
-        import torch.distributed as dist
-        local = int(os.environ.get("LOCAL_RANK", "0"))
-        torch.cuda.set_device(local)
-        dist.init_process_group("nccl", rank=int(os.environ["RANK"]), world_size=int(os.environ["WORLD_SIZE"]),
-                                device_id=torch.device("cuda", local))
-    try:
+
+    def run(dist):
         cfg = classification_config(harness.load_config(args.config))
         task, n_classes = "classification_scanobjectnn", int(cfg["data"]["n_classes"])
         if args.eval:
@@ -79,16 +56,15 @@ def main(argv=None):
             device = torch.device("cuda", torch.cuda.current_device())
             val = DeviceScanObjectNN(harness.make_dataset(cfg, task, n_classes, train=False), device)      # (the training file is not read)
             tr = harness.Trainer(cfg, task, n_classes, device=device, dist=dist, exp_name=args.exp_name, dataset=val)
-            rec = tr._validate_scan("eval", dataset=val)[0]
+            rec = tr.validate(epoch="eval", dataset=val)[0]
             if tr.rank == 0:
                 print(json.dumps(rec))
             return rec
         tr = harness.Trainer(cfg, task, n_classes, dist=dist, exp_name=args.exp_name)
         tr.fit()
         return tr.val_records
-    finally:
-        if dist is not None:
-            dist.destroy_process_group()
+
+    return launch.run_entry(__file__, argv, args.gpus, args.config, run, spawn=not args.eval)
 
 
 if __name__ == "__main__":

@@ -16,7 +16,6 @@ The config is the reference's YAML as it is (`data.category_path`, `data.partial
   device, the sums per taxonomy in a `metrics.TableMeter`, one copy at the end.
 - `--gpus N > 1`: N ranks through `launch.spawn_ranks`, one process group over RCCL (training only)."""
 import argparse
-import copy
 import json
 import os
 import sys
@@ -31,13 +30,8 @@ COMPLETION_TRAIN = {"val_emd_eps": 0.004, "val_emd_iters": 3000, "emd_eps": 0.00
 def completion_config(cfg):
     """A copy of `cfg` with the protocol's defaults (train_inpainter.py:186-192, :267-269) under the keys it lacks;
     `data.batch_size_val` defaults to `data.batch_size`."""
-    cfg = copy.deepcopy(cfg)
-    for key, defaults in (("data", COMPLETION_DATA), ("train", COMPLETION_TRAIN)):
-        sect = cfg.setdefault(key, {})
-        for k, v in defaults.items():
-            sect.setdefault(k, v)
-    cfg["data"].setdefault("batch_size_val", cfg["data"].get("batch_size", 1))
-    return cfg
+    from .protocols import with_defaults
+    return with_defaults(cfg, COMPLETION_DATA, COMPLETION_TRAIN)
 
 
 def eval_batch_size(cfg):
@@ -190,21 +184,8 @@ def main(argv=None):
     from . import harness, launch, parallel
     argv = list(sys.argv[1:] if argv is None else argv)
     args = _parse(argv)
-    if args.gpus > 1 and not args.eval and not launch.under_launcher():
-        rest = [a for i, a in enumerate(argv) if a != "--gpus" and (i == 0 or argv[i - 1] != "--gpus") and not a.startswith("--gpus=")]
-        cfg = harness.load_config(args.config)
-        rc = launch.spawn_ranks(os.path.abspath(__file__), rest, args.gpus, capture=bool(cfg.get("train", {}).get("hip_graph", False)))
-        if rc != 0:
-            raise SystemExit(rc)
-        return []
-    dist = None
-    if launch.under_launcher():
-        import torch.distributed as dist
-        local = int(os.environ.get("LOCAL_RANK", "0"))
-        torch.cuda.set_device(local)
-        dist.init_process_group("nccl", rank=int(os.environ["RANK"]), world_size=int(os.environ["WORLD_SIZE"]),
-                                device_id=torch.device("cuda", local))
-    try:
+
+    def run(dist):
         cfg = completion_config(harness.load_config(args.config))
         n_in = int(cfg["data"]["input_size"])
         if args.eval:
@@ -213,14 +194,13 @@ def main(argv=None):
             from .data.completion import DatasetSubset, shapenet_loader
             tr = harness.Trainer(cfg, "completion", n_in, dist=dist, exp_name=args.exp_name,
                                  dataset=shapenet_loader(cfg["data"]).get_dataset(DatasetSubset.TEST))
-            resident = tr.loader.ds if tr.shapenet_device else None
+            resident = tr.loader.ds if tr.protocol.shapenet_device else None
             return evaluate(parallel._plain_module(tr.model), cfg, tr.device, exp_dir=tr.exp_dir, resident=resident)
         tr = harness.Trainer(cfg, "completion", n_in, dist=dist, exp_name=args.exp_name)
         tr.fit()
         return tr.val_records
-    finally:
-        if dist is not None:
-            dist.destroy_process_group()
+
+    return launch.run_entry(__file__, argv, args.gpus, args.config, run, spawn=not args.eval)
 
 
 if __name__ == "__main__":

@@ -14,28 +14,20 @@ reference hard-codes in its FakeCFG (train_segmentation_kpconv.py:84-114) are de
   (`train.hip_graph_val: true`: forward and loss of every vote batch by HIP-graph replay, `VoteEvaluator.add` eager).
 - `--gpus N > 1`: N ranks through `launch.spawn_ranks`, one process group over RCCL."""
 import argparse
-import copy
-import json
 import math
 import os
 import sys
 
 import torch
 
-KPCONV_DATA = {"kind": "s3dis_kpconv", "num_steps": 2000, "input_features_dim": 4, "num_classes": 13, "sampleDl": 0.04,
-               "in_radius": 2.0, "color_drop": 0.2, "val_color_drop": 0.2, "test_area": "Area_5", "seed": 0}
-KPCONV_TRAIN = {"clip_grad_norm": 10.0, "val_step": 1, "save_each_epoch": 1, "val_votes": 2, "final_votes": 20}
 ALL_AREAS = ["Area_%d" % k for k in range(1, 7)]
 
 
 def kpconv_config(cfg):
-    """A copy of `cfg` with the protocol's defaults (train_segmentation_kpconv.py:84-114, :240-266) under the keys it lacks."""
-    cfg = copy.deepcopy(cfg)
-    for key, defaults in (("data", KPCONV_DATA), ("train", KPCONV_TRAIN)):
-        sect = cfg.setdefault(key, {})
-        for k, v in defaults.items():
-            sect.setdefault(k, v)
-    return cfg
+    """A copy of `cfg` with the protocol's defaults (protocols.KPConv `DATA` / `TRAIN`: train_segmentation_kpconv.py:84-114,
+    :240-266) under the keys it lacks."""
+    from .protocols import KPConv
+    return KPConv.config(cfg)
 
 
 def load_kpconv_areas(cfg, train=True, device=None):
@@ -166,21 +158,8 @@ def main(argv=None):
     from . import harness, launch
     argv = list(sys.argv[1:] if argv is None else argv)
     args = _parse(argv)
-    if args.gpus > 1 and not launch.under_launcher():
-        rest = [a for i, a in enumerate(argv) if a != "--gpus" and (i == 0 or argv[i - 1] != "--gpus") and not a.startswith("--gpus=")]
-        cfg = harness.load_config(args.config)
-        rc = launch.spawn_ranks(os.path.abspath(__file__), rest, args.gpus, capture=bool(cfg.get("train", {}).get("hip_graph", False)))
-        if rc != 0:
-            raise SystemExit(rc)
-        return []
-    dist = None
-    if launch.under_launcher():
-        import torch.distributed as dist
-        local = int(os.environ.get("LOCAL_RANK", "0"))
-        torch.cuda.set_device(local)
-        dist.init_process_group("nccl", rank=int(os.environ["RANK"]), world_size=int(os.environ["WORLD_SIZE"]),
-                                device_id=torch.device("cuda", local))
-    try:
+
+    def run(dist):
         cfg = kpconv_config(harness.load_config(args.config))
         areas = load_kpconv_areas(cfg, train=not args.eval, device=torch.device("cuda", torch.cuda.current_device()))
         tr = harness.Trainer(cfg, "segmentation_kpconv", int(cfg["data"]["num_classes"]), dist=dist, exp_name=args.exp_name,
@@ -189,9 +168,8 @@ def main(argv=None):
             return tr.validate(int(cfg["train"]["final_votes"]), "Last")
         tr.fit()
         return tr.val_records
-    finally:
-        if dist is not None:
-            dist.destroy_process_group()
+
+    return launch.run_entry(__file__, argv, args.gpus, args.config, run)              # (--eval runs on N ranks too)
 
 
 if __name__ == "__main__":

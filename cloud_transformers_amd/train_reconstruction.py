@@ -22,28 +22,18 @@ forwards as HIP graphs; the sphere noise is drawn eagerly before every replay an
   printed and written to <exp>/reconstruction_test.json (the reference's per-batch pickles are not written).
 - `--gpus N > 1`: N ranks through `launch.spawn_ranks`, one process group over RCCL (training only)."""
 import argparse
-import copy
 import json
 import os
 import sys
 
 import torch
 
-RECONSTRUCTION_DATA = {"kind": "what3d_device", "im_size": 128, "gt_size": 8192, "seed": 42, "eval_points": 10000, "eval_noise": 8192}
-RECONSTRUCTION_TRAIN = {"emd_eps": 0.005, "emd_iters": 50, "val_emd_eps": 0.004, "val_emd_iters": 3000, "f1_threshold": 0.01,
-                        "save_each_epoch": 1}
-
 
 def reconstruction_config(cfg):
-    """A copy of `cfg` with the protocol's defaults (train_image_reconstruction.py:95-96,173-174,237-239;
-    eval_reconstruction_f1.py:51,98-104) under the keys it lacks; `data.batch_size_val` defaults to `data.batch_size`."""
-    cfg = copy.deepcopy(cfg)
-    for key, defaults in (("data", RECONSTRUCTION_DATA), ("train", RECONSTRUCTION_TRAIN)):
-        sect = cfg.setdefault(key, {})
-        for k, v in defaults.items():
-            sect.setdefault(k, v)
-    cfg["data"].setdefault("batch_size_val", cfg["data"].get("batch_size", 1))
-    return cfg
+    """A copy of `cfg` with the protocol's defaults (protocols.Reconstruction `DATA` / `TRAIN`) under the keys it lacks;
+    `data.batch_size_val` defaults to `data.batch_size`."""
+    from .protocols import Reconstruction
+    return Reconstruction.config(cfg)
 
 
 def evaluate(model, batches, cfg, exp_dir=None, generator=None, verbose=True):
@@ -104,21 +94,8 @@ def main(argv=None):
     from . import harness, launch, parallel
     argv = list(sys.argv[1:] if argv is None else argv)
     args = _parse(argv)
-    if args.gpus > 1 and not args.eval and not launch.under_launcher():
-        rest = [a for i, a in enumerate(argv) if a != "--gpus" and (i == 0 or argv[i - 1] != "--gpus") and not a.startswith("--gpus=")]
-        cfg = harness.load_config(args.config)
-        rc = launch.spawn_ranks(os.path.abspath(__file__), rest, args.gpus, capture=bool(cfg.get("train", {}).get("hip_graph", False)))
-        if rc != 0:
-            raise SystemExit(rc)
-        return []
-    dist = None
-    if launch.under_launcher():
-        import torch.distributed as dist
-        local = int(os.environ.get("LOCAL_RANK", "0"))
-        torch.cuda.set_device(local)
-        dist.init_process_group("nccl", rank=int(os.environ["RANK"]), world_size=int(os.environ["WORLD_SIZE"]),
-                                device_id=torch.device("cuda", local))
-    try:
+
+    def run(dist):
         cfg = reconstruction_config(harness.load_config(args.config))
         task = "reconstruction"
         if args.eval:
@@ -135,9 +112,8 @@ def main(argv=None):
         tr = harness.Trainer(cfg, task, None, dist=dist, exp_name=args.exp_name)
         tr.fit()
         return tr.val_records
-    finally:
-        if dist is not None:
-            dist.destroy_process_group()
+
+    return launch.run_entry(__file__, argv, args.gpus, args.config, run, spawn=not args.eval)
 
 
 if __name__ == "__main__":

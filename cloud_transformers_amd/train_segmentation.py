@@ -19,30 +19,18 @@ is filled in.  The values the reference hard-codes are defaults here: `data.n_cl
   returned.
 - `--gpus N > 1`: N ranks through `launch.spawn_ranks`, one process group over RCCL (training only)."""
 import argparse
-import copy
 import json
 import os
 import sys
 
 import torch
 
-SEGMENTATION_DATA = {"kind": "s3dis_device", "n_classes": 13, "seed": 0, "jitter_sigma": 0.01, "jitter_clip": 0.05,
-                     "color_jitter_std": 0.05, "color_shift_ratio": 0.1, "hue_max": 0.5, "saturation_max": 0.2,
-                     "test_area": "Area_5", "data_percent": 1.0, "aug": False}
-SEGMENTATION_TRAIN = {"val_step": 1, "save_each_epoch": 100}
-
 
 def segmentation_config(cfg):
-    """A copy of `cfg` with the protocol's defaults (datasets/s3dis_v2.py:185-196,246-366,546-554: the transforms' constants;
-    train_segmentation.py:71-73,175: `aug` off unless the config asks, 13 classes) under the keys it lacks;
+    """A copy of `cfg` with the protocol's defaults (protocols.Blocks `DATA` / `TRAIN`) under the keys it lacks;
     `data.batch_size_val` defaults to `data.batch_size`."""
-    cfg = copy.deepcopy(cfg)
-    for key, defaults in (("data", SEGMENTATION_DATA), ("train", SEGMENTATION_TRAIN)):
-        sect = cfg.setdefault(key, {})
-        for k, v in defaults.items():
-            sect.setdefault(k, v)
-    cfg["data"].setdefault("batch_size_val", cfg["data"].get("batch_size", 1))
-    return cfg
+    from .protocols import Blocks
+    return Blocks.config(cfg)
 
 
 def _parse(argv):
@@ -59,21 +47,8 @@ def main(argv=None):
     from . import harness, launch
     argv = list(sys.argv[1:] if argv is None else argv)
     args = _parse(argv)
-    if args.gpus > 1 and not args.eval and not launch.under_launcher():
-        rest = [a for i, a in enumerate(argv) if a != "--gpus" and (i == 0 or argv[i - 1] != "--gpus") and not a.startswith("--gpus=")]
-        cfg = harness.load_config(args.config)
-        rc = launch.spawn_ranks(os.path.abspath(__file__), rest, args.gpus, capture=bool(cfg.get("train", {}).get("hip_graph", False)))
-        if rc != 0:
-            raise SystemExit(rc)
-        return []
-    dist = None
-    if launch.under_launcher():
-        import torch.distributed as dist
-        local = int(os.environ.get("LOCAL_RANK", "0"))
-        torch.cuda.set_device(local)
-        dist.init_process_group("nccl", rank=int(os.environ["RANK"]), world_size=int(os.environ["WORLD_SIZE"]),
-                                device_id=torch.device("cuda", local))
-    try:
+
+    def run(dist):
         cfg = segmentation_config(harness.load_config(args.config))
         task, n_classes = "segmentation_blocks", int(cfg["data"]["n_classes"])
         if args.eval:
@@ -83,16 +58,15 @@ def main(argv=None):
             device = torch.device("cuda", torch.cuda.current_device())
             val = DeviceS3DISBlocks(harness.make_dataset(cfg, task, n_classes, train=False), device)      # (only the test Area is uploaded)
             tr = harness.Trainer(cfg, task, n_classes, device=device, dist=dist, exp_name=args.exp_name, dataset=val)
-            rec = tr._validate_blocks("eval", dataset=val)[0]
+            rec = tr.validate(epoch="eval", dataset=val)[0]
             if tr.rank == 0:
                 print(json.dumps(rec))
             return rec
         tr = harness.Trainer(cfg, task, n_classes, dist=dist, exp_name=args.exp_name)
         tr.fit()
         return tr.val_records
-    finally:
-        if dist is not None:
-            dist.destroy_process_group()
+
+    return launch.run_entry(__file__, argv, args.gpus, args.config, run, spawn=not args.eval)
 
 
 if __name__ == "__main__":

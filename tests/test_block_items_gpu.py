@@ -407,15 +407,15 @@ def trained(tmp_path_factory):
     batch = next(it)
     want = expected_loss(tr.model, batch)
     res["steps"].append((float(tr._eager_step(batch)), want))
-    res["conf_eager"] = (tr.train_meter.conf.clone(), tr._pred.detach().clone(), batch[1].clone())
+    res["conf_eager"] = (tr.protocol.train_meter.conf.clone(), tr.protocol.out.detach().clone(), batch[1].clone())
     res["hist"] = tr.fit(max_iters=1, hip_graph=False)
     tr._graphs = {}                                                        # (what fit(hip_graph=True) starts from)
-    before = tr.train_meter.conf.clone()
+    before = tr.protocol.train_meter.conf.clone()
     batch = next(it)
     want = expected_loss(tr.model, batch)
     res["steps"].append((float(tr._graph_step(batch)), want))
-    key = next(iter(tr._graph_preds))
-    res["conf_graph"] = (tr.train_meter.conf - before, tr._graph_preds[key].detach().clone(), batch[1].clone())
+    (rec,) = tr._graphs.values()                                           # (the captured step's prediction is in its record)
+    res["conf_graph"] = (tr.protocol.train_meter.conf - before, rec[4].detach().clone(), batch[1].clone())
     tr.save()
     tr.validate(epoch=0)
     res["val_state"] = tr.val_loader.generator.get_state()
@@ -501,7 +501,7 @@ def test_fit_reports_the_train_confusion_and_validates(tmp_path):
     hist = tr.fit()
     assert len(hist) == 3 and np.isfinite(hist).all() and tr.iters == 3
     assert len(tr._graphs) == 1 and all(rec is not False for rec in tr._graphs.values())
-    assert len(tr.train_records) == 1 and tr.train_records[0]["epoch"] == 0 and 0.0 <= tr.train_records[0]["overall_acc"] <= 1.0
-    assert int(tr.train_meter.conf.sum()) == 0                             # started anew for the next epoch
+    assert len(tr.protocol.train_records) == 1 and tr.protocol.train_records[0]["epoch"] == 0 and 0.0 <= tr.protocol.train_records[0]["overall_acc"] <= 1.0
+    assert int(tr.protocol.train_meter.conf.sum()) == 0                             # started anew for the next epoch
     assert len(tr.val_records) == 1 and (tr.exp_dir / "segmentation_val.jsonl").exists()
     assert (tr.exp_dir / "generator_iter_2.t7").exists() and not (tr.exp_dir / "generator_iter_3.t7").exists()

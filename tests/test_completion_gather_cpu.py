@@ -244,13 +244,13 @@ def test_harness_picks_the_device_kind(tree, tmp_path):
     assert isinstance(data, C.Dataset) and data.options["shuffle"] and data.options["n_renderings"] == 2
     assert not H.make_dataset(cfg, "completion", N_IN, train=False).options["shuffle"]
     tr = H.Trainer(cfg, "completion", N_IN, device=torch.device("cpu"), make_dirs=False)
-    assert tr.shapenet and tr.shapenet_device and tr.sampler is None
+    assert tr.protocol.shapenet and tr.protocol.shapenet_device and tr.sampler is None
     assert isinstance(tr.loader, C.DeviceCompletionBatches) and tr.loader.train and tr.loader.drop_last and len(tr.loader) == 1
     assert isinstance(tr.loader.ds, C.DeviceShapeNetCompletion) and (tr.loader.ds.n_in, tr.loader.ds.n_out) == (N_IN, N_OUT)
     assert os.listdir(str(tmp_path / "cache"))                             # data.cache_dir is used
     host = H.Trainer(completion_config(_config(tree, tmp_path, "shapenet_completion")), "completion", N_IN, device=torch.device("cpu"),
                      make_dirs=False)
-    assert host.shapenet and not host.shapenet_device and isinstance(host.loader, C.CompletionBatches)
+    assert host.protocol.shapenet and not host.protocol.shapenet_device and isinstance(host.loader, C.CompletionBatches)
 
 
 def test_unknown_kind_still_raises(tree, tmp_path):

@@ -65,7 +65,7 @@ def _trainer(workload, **data):
 
 
 def _noise_generator(workload):
-    """Seeded as Trainer seeds `_noise_gen` on rank 0."""
+    """Seeded as the reconstruction protocol seeds `noise_gen` on rank 0."""
     return torch.Generator(device=DEV).manual_seed(workload["seed"] * 1000003 + 15485863)
 
 
@@ -74,7 +74,7 @@ def _three_steps(workload, hip_graph):
     chamfers = []
     tr.writer.add_scalar = lambda tag, value, global_step=None: chamfers.append(float(value)) if tag == "train/loss_chamfer" else None
     history = tr.fit(max_iters=3, hip_graph=hip_graph)
-    return {"history": history, "chamfers": chamfers, "state": tr._noise_gen.get_state().clone(), "graphs": dict(tr._graphs)}
+    return {"history": history, "chamfers": chamfers, "state": tr.protocol.noise_gen.get_state().clone(), "graphs": dict(tr._graphs)}
 
 
 @pytest.fixture(scope="module")
@@ -125,7 +125,7 @@ def test_the_noise_buffer_holds_the_draw_of_its_step(workload):
     from cloud_transformers_amd.metrics import sphere_noise
     tr = _trainer(workload)
     ref = _noise_generator(workload)
-    tr._graphs, tr._graph_preds, tr._graph_chamfers = {}, {}, {}
+    tr._graphs = {}
     tr.model.train()
     tr.loader.set_epoch(0)
     seen = []
@@ -142,7 +142,7 @@ def test_the_noise_buffer_holds_the_draw_of_its_step(workload):
         assert torch.equal(static[0], batch[0]) and torch.equal(static[1], batch[1])
         seen.append(static[2].clone())
     assert len(seen) == 3 and not torch.equal(seen[0], seen[1]) and not torch.equal(seen[1], seen[2])
-    assert torch.equal(tr._noise_gen.get_state(), ref.get_state())
+    assert torch.equal(tr.protocol.noise_gen.get_state(), ref.get_state())
 
 
 def test_a_ragged_last_batch_gets_its_own_graph(workload):

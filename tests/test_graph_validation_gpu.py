@@ -123,7 +123,7 @@ def test_graphed_validation_returns_the_eager_record(workloads, task):
     assert eager._val_graph is None
     if task == "reconstruction":
         assert _captured(graphed) == 2 and got[0]["batches"] == 3              # batches of 3, 3 and 2: the ragged one has its graph
-        assert torch.equal(graphed._noise_gen.get_state(), eager._noise_gen.get_state())        # the warm-ups drew nothing
+        assert torch.equal(graphed.protocol.noise_gen.get_state(), eager.protocol.noise_gen.get_state())        # the warm-ups drew nothing
 
 
 def test_the_config_key_selects_it_and_the_default_launches_no_graph(workloads):
@@ -146,7 +146,7 @@ def _rewind(tr, state):
 def blocks(workloads):
     """A blocks trainer after one graphed validation, and the state its validation loader's generator started that pass from."""
     tr = _trainer(workloads, "segmentation_blocks")
-    tr.val_loader = tr._block_batches(_val_data(tr), train=False)
+    tr.val_loader = tr.protocol.loader(tr, _val_data(tr), train=False)
     state = tr.val_loader.generator.get_state().clone()
     first = _validate(tr, True)
     return tr, state, first
@@ -226,7 +226,7 @@ def test_emd_validation_steps_replay_without_a_host_synchronisation(workloads, t
     tr.model.eval()
     if task == "reconstruction":
         img, pcd = next(iter(tr.val_loader))
-        args = (img, pcd, tr._draw_noise(pcd))
+        args = (img, pcd, tr.protocol._draw_noise(pcd))
     else:
         args = tuple(next(iter(tr.val_loader)))
     n = _captured(tr)

@@ -180,17 +180,14 @@ def build(name):
 
 
 def bare_trainer(task, model, train_cfg):
-    """A harness.Trainer without its data side: what `_loss`, `_eager_step`, `_graph_step`, `_val_step` and `_val_runner` read."""
+    """A harness.Trainer without its data side: the task's protocol and what the steps and `_val_runner` read of the trainer."""
     import torch
-    from torch import nn
-    from cloud_transformers_amd import harness as H
+    from cloud_transformers_amd import harness as H, protocols
     tr = object.__new__(H.Trainer)
-    tr.task, tr.cfg, tr.model, tr.device = task, {"train": dict(train_cfg)}, model, torch.device("cuda", torch.cuda.current_device())
-    tr.dist, tr.rank, tr._stream, tr.clip, tr.kp = None, 0, None, None, None
-    tr.recon, tr.blocks, tr.train_meter, tr._pred, tr.last_chamfer = task == "reconstruction", False, None, None, None
-    tr._graphs, tr._graph_preds, tr._graph_chamfers, tr._val_graph = {}, {}, {}, None
-    tr._noise_gen = torch.Generator(device=tr.device).manual_seed(3)
-    tr.ce, tr.bce = nn.CrossEntropyLoss(), nn.BCEWithLogitsLoss()
+    tr.cfg, tr.model, tr.device = {"data": {"seed": 0}, "train": dict(train_cfg)}, model, torch.device("cuda", torch.cuda.current_device())
+    tr.dist, tr.rank, tr.n_classes, tr._stream, tr.clip, tr._graphs, tr._val_graph = None, 0, 13, None, None, {}, None
+    tr.protocol = protocols.PROTOCOLS[task](tr)
+    tr.protocol.noise_gen = torch.Generator(device=tr.device).manual_seed(3)
     tr.optimizer = torch.optim.Adam(model.parameters(), lr=1e-5)
     return tr
 
@@ -226,13 +223,14 @@ def row(name, windows, iters, window_ms):
         tr = bare_trainer(task, net, dict(emd, seg_weight=0.5))
         net.eval()
         replay = tr._val_runner(True)
+        inputs = (lambda: args + (tr.protocol._draw_noise(args[1]),)) if task == "reconstruction" else (lambda: args)
 
         def eager():
             with torch.no_grad():
-                tr._val_step(*(args + ((tr._draw_noise(args[1]),) if tr.recon else ())))
+                tr._val_step(*inputs())
 
         def graphed():
-            replay(*(args + ((tr._draw_noise(args[1]),) if tr.recon else ())))
+            replay(*inputs())
 
     for _ in range(2):                               # warm-up of both, the capture included
         eager()
