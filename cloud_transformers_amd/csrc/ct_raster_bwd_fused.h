@@ -37,12 +37,16 @@
 //   Per four-channel group:
 //     stage (g_out in sorted order, the z cells)  | barrier | items (slice_bwd_sorted_kernel's; the first item carries the requests
 //     of the group's FEAT rows, one channel per entry) | barrier | thread = cell: its four accumulator words and its z word,
-//     the g_z elements stored, the non-zero cells counted | barrier | the pair tile {z(2p), z(2p+1), g(2p), g(2p+1)}
-//     over the tile and accumulator areas (empty cells: kNoMatch) | barrier | splat_bwd_quad's optimistic body on the thread's quad
-//     (one point carries one channel of the NEXT group's g_out requests), g_feat rows stored, matches counted | barrier | the
-//     group's tie test (non-zero cells against matches), accumulators cleared.
+//     the g_z elements stored, its accumulator words cleared, the non-zero cells counted, its two words of the pair tile
+//     {z(2p), z(2p+1), g(2p), g(2p+1)} written over the dead STAGE area (empty cells: kNoMatch; a thread touches its own words
+//     only: no barrier in between) | barrier | splat_bwd_quad's optimistic body on the thread's quad (one point carries one channel
+//     of the NEXT group's g_out requests), g_feat rows stored, matches counted | barrier | the group's tie test (non-zero cells
+//     against matches).  Four barriers per group; the next staging restores the stage area's zero entry.
 //   Behind the loop: a tied group is redone as splat_max_bwd_hot_kernel redoes it (pairs staged again from z and the g_z this
-//   workgroup stored, splat_bwd_quad<.., CLAIMS, DELTA>); then the key cotangents.
+//   workgroup stored, over the tile and accumulator areas, splat_bwd_quad<.., CLAIMS, DELTA>); then the key cotangents.
+//   Vector instructions the loop does without (profiles/fused_bwd_valu_ab.txt): the cross-row steps, readlane and lane election of
+//   its six reductions (row_max_u32 / row_sum_i32 below), the convert phase's second fx_quantum (q from iq's bits on the scalar
+//   unit), the register copies of the Splat body's loaded pairs.
 //   grid = (1, H, B)
 // ---------------------------------------------------------------------------
 // A stream of the plane behind a buffer descriptor: raw buffer, 32-bit byte offsets (a scalar row + the lane's), range-checked
@@ -72,6 +76,30 @@ __device__ __forceinline__ void buf_st_stream(const StreamBuf& b, unsigned voff,
   __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), b.r, (int)voff, (int)soff, kBufNt);
 }
 
+// The group loop's own reductions: the four row steps of wave_max_u32 / wave_sum_i32 (lanes without a source read 0, the identity
+// of both) and no more — lane 15 of each 16-lane row holds its row's result and hands it to the LDS atomic itself: four lanes a
+// wave instead of one, and neither the two cross-row steps nor the readlane.  Integer max and add: exact in any order.
+__device__ __forceinline__ unsigned row_max_u32(unsigned v) {
+#define CT_UMAX(a, b) max((a), (b))
+  CT_DPP_STEP(v, CT_UMAX, 0x111, 0xf);
+  CT_DPP_STEP(v, CT_UMAX, 0x112, 0xf);
+  CT_DPP_STEP(v, CT_UMAX, 0x114, 0xf);
+  CT_DPP_STEP(v, CT_UMAX, 0x118, 0xf);
+#undef CT_UMAX
+  asm volatile("" : "+v"(v));      // (the last step stays here, folded like the others, and does not sink to the user's branch)
+  return v;
+}
+__device__ __forceinline__ int row_sum_i32(int v) {
+#define CT_IADD(a, b) ((a) + (b))
+  CT_DPP_STEP(v, CT_IADD, 0x111, 0xf);
+  CT_DPP_STEP(v, CT_IADD, 0x112, 0xf);
+  CT_DPP_STEP(v, CT_IADD, 0x114, 0xf);
+  CT_DPP_STEP(v, CT_IADD, 0x118, 0xf);
+#undef CT_IADD
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
 template <bool HAS_PAD, int WT, int NT = 0, int CT = 0>
 __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArgs a_arg, GridW<2> g_arg) {
   const GridW<2> g = grid2_of<WT>(g_arg);
@@ -83,12 +111,14 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
   const SortLds L = sort_lds(G, N, C);
   float4* T4 = (float4*)(lds_raw + L.tile);
   int* acc = (int*)(lds_raw + L.acc);
-  float4* ZG = (float4*)(lds_raw + L.tile);          // the pair tile: the tile and accumulator areas together (2 x 16 G bytes)
+  float4* ZG = (float4*)(lds_raw + L.tile);          // the tied-group redo's pair tile: the tile and accumulator areas together
   float4* Sg = (float4*)(lds_raw + L.stage);
   const float2* AB = (const float2*)(lds_raw + L.ab);
   unsigned* s_max = (unsigned*)(lds_raw + L.misc);
   unsigned* s_k = s_max + C;
   int* s_tie = (int*)(s_k + 1);                       // the sort's scan scratch, dead behind it: [parity][non-zero cells, matches]
+  float4* PZ = (float4*)(lds_raw + L.stage);          // the group loop's pair tile: over the stage area (2 x 16 G bytes of its >= 64 G)
+  const bool row_last = (threadIdx.x & 15) == 15;
   const int b = blockIdx.z;
   const size_t bh = (size_t)b * a.H + blockIdx.y;
   const int tid = threadIdx.x;
@@ -139,7 +169,6 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
   uint2* const s_cell = (uint2*)(lds_raw + L.mark);
   s_cell[tid] = make_uint2((unsigned)PK.base[0] | (unsigned)PK.base[1] << 16, (unsigned)PK.base[2] | (unsigned)PK.base[3] << 16);
   for (int i = tid; i < G; i += kSortThreads) ((int4*)acc)[i] = make_int4(0, 0, 0, 0);
-  if (tid == 0) Sg[N] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   if (tid < 4) s_tie[tid] = 0;
   const float Kf = (float)(*s_k);
 
@@ -160,6 +189,15 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
     // (opaque per group, as the items' offsets below: the unpacked positions would otherwise be kept across the loop, in scratch)
     asm volatile("" : "+v"(S.rk01), "+v"(S.rk23), "+v"(cell01));
     const int cell[2] = {(int)(short)(cell01 & 0xffffu), (int)cell01 >> 16};
+    unsigned rowmax[4];
+    // (a lane offset the compiler cannot see through: with a wave-uniform address its atomic optimizer folds the rows' atomics into
+    // one lane's, through a scalar loop over the active lanes.  To recheck with another toolchain, read the headline instance's ISA:
+    // the staging phase holds four ds_max_u32 under one exec mask and no s_cbranch loop with v_readlane in front of them, the
+    // convert phase and the end of the Splat body one ds_add_u32 each.  Bits are the same either way; the loop is slower.)
+    unsigned lane0;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(lane0));
+    unsigned* const s_max_lane = s_max + lane0;
+    int* const s_tie_lane = s_tie + lane0;
 #pragma unroll
     for (int cj = 0; cj < 4; ++cj) {
       float m = 0.0f;
@@ -171,9 +209,15 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
         x = fabsf(x);
         m = fmaxf(m, (x < __builtin_inff()) ? x : __builtin_inff());     // inf / NaN -> inf
       }
-      const unsigned mb = wave_max_u32(__float_as_uint(m));
-      if ((tid & 63) == 0) atomicMax(&s_max[ch0 + cj], mb);
+      rowmax[cj] = row_max_u32(__float_as_uint(m));
     }
+    if (row_last) {
+#pragma unroll
+      for (int cj = 0; cj < 4; ++cj) atomicMax(s_max_lane + ch0 + cj, rowmax[cj]);
+    }
+    // The stage area's zero entry, which padded item slots read: written here for every group, the first included (nowhere else) —
+    // the previous group's pair tile lay over the stage area, over this entry too where N < 2 G.
+    if (tid == 0) Sg[N] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (has) {
       const unsigned rk[4] = {S.rk01 & kRankMask, (S.rk01 >> 16) & kRankMask, S.rk23 & kRankMask, (S.rk23 >> 16) & kRankMask};
 #pragma unroll
@@ -182,7 +226,7 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
     if (tid < G) T4[tid] = make_float4(cvq[0], cvq[1], cvq[2], cvq[3]);
     __syncthreads();
 
-    float iq[4];
+    float iq[4], qs[4];
     bool any_float = false;
 #pragma unroll
     for (int cj = 0; cj < 4; ++cj) {
@@ -194,6 +238,9 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
         any_float = true;
       }
       iq[cj] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(iq[cj])));
+      // The quantum the convert phase multiplies by, kept from here: q = 2^(ex - 30) and iq = 2^(30 - ex) are both normal (-90 <= ex
+      // <= 123), so q's bits are 0x7f000000 - iq's, a scalar subtraction on the wave-uniform iq (iq == 0: the float path).
+      qs[cj] = __uint_as_float(0x7f000000u - __float_as_uint(iq[cj]));
     }
     // the item body of slice_bwd_sorted_kernel; the first item carries the requests of this group's feat rows
     auto item = [&](auto U) {
@@ -269,26 +316,26 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
       zc = T4[tid];
 #pragma unroll
       for (int cj = 0; cj < 4; ++cj) {
-        float q, iqd;
-        bool fixed;
-        fx_quantum(__uint_as_float(s_max[ch0 + cj]) * Kf, q, iqd, fixed);
         const int r = acc[cj * G + tid];
-        gv[cj] = fixed ? (float)r * q : __int_as_float(r);
+        gv[cj] = iq[cj] != 0.0f ? (float)r * qs[cj] : __int_as_float(r);
         buf_st_stream(b_gz, vo_cell, (unsigned)(ch0 + cj) * cell_row, gv[cj]);
+        acc[cj * G + tid] = 0;      // the thread's own words, cleared for the next group's items
       }
     }
     const unsigned zw[4] = {__float_as_uint(zc.x), __float_as_uint(zc.y), __float_as_uint(zc.z), __float_as_uint(zc.w)};
+    // The pair tile goes over the stage area: read by the items only, dead since the barrier above until the next group's staging
+    // behind this group's last barrier, and never smaller than 64 G bytes (the sort's histograms).  A thread has touched its own
+    // words only: no barrier between the accumulators' last readers and the pair words' writers.
+    if (tid < G) {
+      PZ[tid] = make_float4(__uint_as_float(zw[0] ? zw[0] : kNoMatch), __uint_as_float(zw[1] ? zw[1] : kNoMatch), gv[0], gv[1]);
+      PZ[G + tid] = make_float4(__uint_as_float(zw[2] ? zw[2] : kNoMatch), __uint_as_float(zw[3] ? zw[3] : kNoMatch), gv[2], gv[3]);
+    }
     {
       int nzt = 0;
 #pragma unroll
       for (int k = 0; k < 4; ++k) nzt += (zw[k] != 0u);
-      nzt = wave_sum_i32(nzt);
-      if ((tid & 63) == 0 && nzt) atomicAdd(&s_tie[(grp & 1) * 2], nzt);
-    }
-    __syncthreads();            // every thread holds its inputs: the second pair word lies over other cells' accumulators
-    if (tid < G) {
-      ZG[tid] = make_float4(__uint_as_float(zw[0] ? zw[0] : kNoMatch), __uint_as_float(zw[1] ? zw[1] : kNoMatch), gv[0], gv[1]);
-      ZG[G + tid] = make_float4(__uint_as_float(zw[2] ? zw[2] : kNoMatch), __uint_as_float(zw[3] ? zw[3] : kNoMatch), gv[2], gv[3]);
+      nzt = row_sum_i32(nzt);
+      if (row_last && nzt) atomicAdd(s_tie_lane + (grp & 1) * 2, nzt);
     }
     __syncthreads();
 
@@ -311,14 +358,18 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
         float gw[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int pr = 0; pr < 2; ++pr) {
-          const float4* Zp = ZG + (size_t)pr * G + p.base;
+          const float4* Zp = PZ + (size_t)pr * G + p.base;
           const float xa = HAS_PAD ? fq[2 * pr][i] * pv[i] : fq[2 * pr][i];
           const float xb = HAS_PAD ? fq[2 * pr + 1][i] * pv[i] : fq[2 * pr + 1][i];
           ct_f4 zg[4];
 #pragma unroll
           for (int v = 0; v < 4; ++v) zg[v] = *(const ct_f4*)(Zp + off[v]);
+          // (the general-grid instance alone keeps its loaded pairs pinned: without the pin two scratch reloads land in its group
+          // loop; with it the tiled instances copy them around — 94 v_mov per group in the headline instance)
+          if constexpr (WT == 0) {
 #pragma unroll
-          for (int v = 0; v < 4; ++v) asm volatile("" : "+v"(zg[v].x), "+v"(zg[v].y), "+v"(zg[v].z), "+v"(zg[v].w));
+            for (int v = 0; v < 4; ++v) asm volatile("" : "+v"(zg[v].x), "+v"(zg[v].y), "+v"(zg[v].z), "+v"(zg[v].w));
+          }
           float gfa = 0.0f, gfb = 0.0f;
 #pragma unroll
           for (int v = 0; v < 4; ++v) {
@@ -348,18 +399,14 @@ __global__ void __launch_bounds__(kSortThreads) slice_splat_bwd_kernel(RasterArg
 #pragma unroll
       for (int cj = 0; cj < 4; ++cj) request1(grp + 1, cj);      // (a thread without a quad still stages its conv cell)
     }
-    nm = wave_sum_i32(nm);
-    if ((tid & 63) == 0 && nm) atomicAdd(&s_tie[(grp & 1) * 2 + 1], nm);
+    nm = row_sum_i32(nm);
+    if (row_last && nm) atomicAdd(s_tie_lane + (grp & 1) * 2 + 1, nm);
     __syncthreads();
     // the group's tie test (block-uniform); the other parity's words — read behind the previous group's barrier here, added to
     // behind the next group's later barriers — are cleared for the next group
     const int* tw = s_tie + (grp & 1) * 2;
     if (tw[0] != tw[1]) tied |= 1ull << grp;
     if (tid < 2) s_tie[((grp & 1) ^ 1) * 2 + tid] = 0;
-    // (the zero is made per group: one kept across the loop as a 16-byte vector was spilled and reloaded here)
-    int zero;
-    asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
-    if (tid < G) ((int4*)acc)[tid] = make_int4(zero, zero, zero, zero);
   };
   int grp = 0;
   for (; grp + 1 < ngroups; ++grp) group(grp, std::true_type{});
